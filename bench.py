@@ -19,9 +19,16 @@ Rank 0 prints ONE JSON line.  Besides the contract keys it carries
                  ALGORITHMIC bytes = external products x 4*N*(k+1)*((k+1)*l+2) bytes,
                  duration measured with HIP events on the kernel's own stream during the timed
                  region;
-  cpu_baseline : the literal CPU restatement of the reference (oracle, kind "port": the Rust
+  cpu_baseline : (--full) the literal CPU restatement of the reference (oracle, kind "port": the Rust
                  reference cannot be built in this image) timed single-threaded on a bounded
                  sample of the same workload, on this box's host cores (N=1, rank 0 only).
+
+A plain run sets up, warms up, times --steps steps and prints the line.  Everything else it used to
+measure or check moves behind --full: the stream-copy HBM roofline, the CPU baseline and the oracle's
+re-computation of rows of the timed batch (`verified`), the aligned-decomposer leg and the exact-NTT
+backend beside the headline.  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (float64: every wrapping-u32 word is exact), so that two builds can be compared output
+for output; the inputs are drawn from a fixed seed and are the same from run to run.
 """
 from __future__ import annotations
 
@@ -130,6 +137,42 @@ WORKLOADS = {
 }
 CPU_BASELINE_PBS = 3        # >= 3 PBS on one thread (the reference is single-threaded)
 CPU_ALIGNED_CHECK_ROWS = 16  # rows of the aligned-decomposer leg the oracle re-computes (the leg whose digits are non-zero)
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: at most this many bytes of .npy files in all
+DUMP_SAMPLE_SEED = 0x74666865  # the rows kept of an output too large for its share of the budget
+
+
+def dump_outputs(directory: str, arrays: dict, budget: int = DUMP_BUDGET_BYTES) -> dict:
+    """--dump-outputs: each named output (ciphertext words, wrapping u32 in int32 storage; a torch tensor or a numpy
+    array, rows first) -> DIR/<name>.npy in float64, where every u32 word is exact.  The budget is shared evenly by the
+    arrays; one larger than its share keeps a fixed, seeded sample of its rows, in ascending order, and the row indices
+    go beside it as DIR/<name>_rows.npy.  -> {name: {"shape": written shape, "rows_of": rows of the output}}."""
+    os.makedirs(directory, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    written = {}
+    for name, a in arrays.items():
+        rows = int(a.shape[0])
+        row_bytes = 8 * int(np.prod(a.shape[1:], dtype=np.int64))
+        keep = None
+        if rows * row_bytes > share - 1024:  # 1 KiB for the .npy headers
+            count = max(1, (share - 1024) // (row_bytes + 8))
+            keep = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, size=min(rows, count), replace=False))
+        if hasattr(a, "index_select"):  # a torch tensor: the sample is taken on its device, then copied
+            import torch
+            if keep is not None:
+                a = a.index_select(0, torch.from_numpy(keep).to(a.device))
+            a = a.cpu().numpy()
+        elif keep is not None:
+            a = np.asarray(a)[keep]
+        a = np.asarray(a)
+        if a.dtype == np.int32:
+            a = a.view(np.uint32)
+        if a.dtype != np.uint32:
+            raise TypeError(f"dump_outputs: {name} holds {a.dtype}, not ciphertext words")
+        np.save(os.path.join(directory, name + ".npy"), a.astype(np.float64))
+        if keep is not None:
+            np.save(os.path.join(directory, name + "_rows.npy"), keep.astype(np.float64))
+        written[name] = {"shape": list(a.shape), "rows_of": rows}
+    return written
 
 
 def usable_cores() -> dict:
@@ -274,9 +317,9 @@ def bench_external_product(args, pkg, params, batch, dev, rand_words, world, ran
 
     # One launch is ~0.1 ms: a handful of launches runs on a chip that has not reached its sustained clocks
     # (20 launches after 3 of warm-up measured 0.123 ms per launch, 200 after 300 measured 0.103 ms, 1000
-    # after 1000 the same 0.103 ms).  So: at least 300 untimed launches, at least 200 timed ones.
-    steps = max(args.steps, 200)
-    warmup = max(args.warmup, 300)
+    # after 1000 the same 0.103 ms).  So a figure of this kernel wants --warmup 300 --steps 200 at least.
+    steps = args.steps
+    warmup = args.warmup
     for _ in range(warmup):
         ctx.external_product_prepared(prepared, glwe, out=out)
     barrier()
@@ -287,11 +330,15 @@ def bench_external_product(args, pkg, params, batch, dev, rand_words, world, ran
         kms.append(ctx.last_kernel_ms()[0])
     barrier()
     dt = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, {"glwe_out" if world == 1 else f"glwe_out_rank{rank}": out},
+                              DUMP_BUDGET_BYTES // world)
     # The reference's call shape hands over the GGSW as raw u32 (ggsw.rs:132-161): 4x fewer key bytes than
     # the prepared form, but every key polynomial needs F::kParts forward transforms first.  Timed here as
     # what the host entry point does on the device: prepare kernel + product kernel, per launch pair.
     raw_ms = None
-    if args.ggsw_per_sample:
+    if args.ggsw_per_sample and args.full:
         start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         scratch = torch.empty_like(prepared)
         for _ in range(2):
@@ -317,7 +364,7 @@ def bench_external_product(args, pkg, params, batch, dev, rand_words, world, ran
     glwe_only = 8 * params.N * (params.k + 1)
     algo_shared = batch * glwe_only + params.R * (params.k + 1) * params.N * 4
     achieved_shared = algo_shared / (kernel_ms * 1e-3) / 1e9
-    hbm_copy = measure_hbm_copy_gbs(torch, dev, ctx=ctx)
+    hbm_copy = measure_hbm_copy_gbs(torch, dev, ctx=ctx) if args.full else None
     result = {
         "metric": "external_products_per_sec", "value": batch * world * steps / dt, "unit": "products/s",
         "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": dt / steps * 1e3,
@@ -328,21 +375,23 @@ def bench_external_product(args, pkg, params, batch, dev, rand_words, world, ran
                                + ("one prepared GGSW per sample" if args.ggsw_per_sample else "one GGSW shared by the batch")},
         "roofline": {"kernel": f"external_product_kernel<{ctx.backend},{params.glwe_poly_degree},{params.k}>",
                      "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "hbm_copy_measured_GBps": hbm_copy,
-                     "frac_of_measured_hbm": achieved / hbm_copy,
+                     "frac": achieved / HBM_PEAK_GBS,
                      "traffic": None, "kernel_ms": kernel_ms, "algorithmic_bytes_per_launch": algo,
                      "physical_operand_bytes_per_launch": physical,
                      "physical_GBps": physical / (kernel_ms * 1e-3) / 1e9},
     }
+    if hbm_copy is not None:
+        result["roofline"].update({"hbm_copy_measured_GBps": hbm_copy, "frac_of_measured_hbm": achieved / hbm_copy})
     if not args.ggsw_per_sample:
         result["roofline"].update({
             "accounting": "achieved/frac price every product at 4N(k+1)((k+1)l+2) bytes (GGSW + GLWE in + GLWE out, SURVEY 8d's "
                           "unit) although this launch reads ONE GGSW for the whole batch; achieved_shared_ggsw prices what "
                           "the shape really moves: 8N(k+1) bytes per product + the GGSW once",
             "achieved_shared_ggsw": achieved_shared, "frac_shared_ggsw": achieved_shared / HBM_PEAK_GBS,
-            "frac_of_measured_hbm_shared_ggsw": achieved_shared / hbm_copy,
             "algorithmic_bytes_per_launch_shared_ggsw": algo_shared,
             "bound": "valu-issue (the operands are L2-resident; neither accounting comes near HBM)"})
+        if hbm_copy is not None:
+            result["roofline"]["frac_of_measured_hbm_shared_ggsw"] = achieved_shared / hbm_copy
     if raw_ms is not None:
         raw_bytes = count * params.R * (params.k + 1) * params.N * 4 + 2 * batch * (params.k + 1) * params.N * 4
         result["raw_u32_ggsw"] = {
@@ -350,6 +399,8 @@ def bench_external_product(args, pkg, params, batch, dev, rand_words, world, ran
             "the raw GGSW being the only key bytes read from HBM by the pair's first kernel",
             "raw_operand_bytes": raw_bytes, "algorithmic_GBps": algo / (raw_ms * 1e-3) / 1e9,
             "faster_than_prepared_stream": bool(raw_ms < kernel_ms)}
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
     ctx.close()
     if rank == 0:
         print(json.dumps(result), flush=True)
@@ -425,10 +476,13 @@ def bench_pool(args, pkg, params, batch, devices, backend):
     k, n, logn = params.k, params.n, params.glwe_poly_degree
     members = len(devices)
     dev0 = torch.device("cuda", devices[0])
-    gen = torch.Generator(device=dev0)
-    gen.manual_seed(0x74666865)
-    rand = lambda dev, *shape: torch.randint(-(1 << 31), (1 << 31) - 1, shape, dtype=torch.int32, device=dev,
-                                             generator=gen if dev == dev0 else None)
+    gens = {}  # one seeded generator per device: the same arguments draw the same inputs from run to run
+
+    def rand(dev, *shape):
+        if dev not in gens:
+            gens[dev] = torch.Generator(device=dev)
+            gens[dev].manual_seed(0x74666865 + (0 if dev == dev0 else 1 + dev.index))
+        return torch.randint(-(1 << 31), (1 << 31) - 1, shape, dtype=torch.int32, device=dev, generator=gens[dev])
     pool = pkg.Pool(params, devices, backend=backend)
     t_key = time.perf_counter()
     bsk, ksk = rand(dev0, *params.bsk_shape()), rand(dev0, *params.ksk_shape())
@@ -455,6 +509,9 @@ def bench_pool(args, pkg, params, batch, devices, backend):
         pool.bootstrap_shards(shards, tvs, outs)   # enqueue only: every member has its own stream
     pool.synchronize()
     dt = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, {f"lwe_out_member{i}": o for i, o in enumerate(outs)})
     br = float(np.mean([ctx0.kernel_ms_ago(i)[0] for i in range(min(args.steps, 64))]))
     algo = batch * n * params.external_product_bytes()
     achieved = algo / (br * 1e-3) / 1e9
@@ -476,6 +533,8 @@ def bench_pool(args, pkg, params, batch, devices, backend):
                      "traffic": None, "kernel_ms": br, "algorithmic_bytes_per_launch": algo,
                      "note": "member 0's kernel; every member runs the same launch on its own shard"},
     }
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
     pool.close()
     print(json.dumps(result), flush=True)
 
@@ -487,9 +546,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=0, help="ciphertexts per GPU per step (default: workload's)")
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, everything else the line can carry: the stream-copy HBM roofline, the CPU "
+                         "baseline and the oracle's check of rows of the timed batch, the aligned-decomposer and exact-NTT "
+                         "legs (bootstrap), the raw-GGSW leg (external_product).  Off: set up, warm up, time, print")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, "
+                         f"at most {DUMP_BUDGET_BYTES >> 20} MB in all: a seeded sample of the rows of a larger output)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=15.0,
                     help="time budget of the single-thread CPU leg (it stops after CPU_BASELINE_PBS bootstraps anyway)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU legs")
     ap.add_argument("--backend", default="auto", choices=["auto", "goldilocks", "fp64", "goldilocks-split", "fp64-p49", "fp64-fft"])
     ap.add_argument("--kernel", default="bootstrap", choices=["bootstrap", "external_product"],
                     help="external_product: time the standalone GGSW x GLWE kernel (ggsw.rs:132-161) instead of the PBS")
@@ -506,8 +572,8 @@ def main():
                     help="comma-separated HIP device ordinals: time the multi-GPU pool of the C ABI (tfhe_pool_*) in ONE "
                          "process instead of one process per GPU, e.g. 0,1,2,3,4,5,6,7 (0,0 rehearses it on one GPU)")
     ap.add_argument("--no-secondary-legs", action="store_true",
-                    help="skip the figures taken after the timed region (aligned decomposer, exact prime-field backend): for "
-                         "rocprofv3 --stats runs whose per-kernel averages should contain the timed launches only")
+                    help="--full without the figures taken after the timed region (aligned decomposer, exact prime-field "
+                         "backend): for rocprofv3 --stats runs whose per-kernel averages should contain the timed launches only")
     ap.add_argument("--batch-sweep", action="store_true",
                     help="latency of one call and rate of back-to-back calls at batches 1 .. 4096 (the reference's call shape is "
                          "ONE ciphertext per bootstrap()); prints one JSON line with a row per (workload, batch)")
@@ -518,6 +584,8 @@ def main():
     ap.add_argument("--gate", default="", choices=["", "nand", "and", "or", "xor"],
                     help="step = one homomorphic gate over the batch (boolean.rs: bootstrap(2*ct1 + ct0)) instead of a plain PBS")
     args = ap.parse_args()
+    if args.dump_outputs and args.batch_sweep:
+        raise SystemExit("--dump-outputs: the batch sweep has no single timed path to dump")
 
     import torch
     import torch.distributed as dist
@@ -603,7 +671,8 @@ def main():
     ctx.load_bootstrapping_key(bsk, ksk)
     # the CPU legs re-compute rows of the TIMED batch with the oracle: they need the same keys on the host
     plain_pbs = not args.gate and not args.scatter_gather
-    check_bits = plain_pbs and not args.no_cpu_baseline
+    check_bits = plain_pbs and args.full and not args.no_cpu_baseline
+    secondary_legs = args.full and not args.no_secondary_legs
     host = None
     if check_bits:
         u32 = lambda t: t.cpu().numpy().view(np.uint32)
@@ -623,7 +692,7 @@ def main():
         lwe2 = rand_words(batch, n + 1)
 
         def step():
-            ctx.gate(truth, lwe, lwe2, out=out)
+            return ctx.gate(truth, lwe, lwe2, out=out)
     elif args.scatter_gather:
         if not use_dist:
             raise SystemExit("--scatter-gather needs torch.distributed.run (RANK/WORLD_SIZE in the environment)")
@@ -633,21 +702,27 @@ def main():
 
         def step():
             # rank 0 owns the whole batch: scatter rows over RCCL, bootstrap the local shard, gather
-            sharding.bootstrap_sharded(lambda shard, tvv: ctx.bootstrap(shard, tvv), full, tv, root=0,
-                                       batch=batch * world, width=n + 1, like=lwe)
+            return sharding.bootstrap_sharded(lambda shard, tvv: ctx.bootstrap(shard, tvv), full, tv, root=0,
+                                              batch=batch * world, width=n + 1, like=lwe)
     else:
         def step():
-            ctx.bootstrap(lwe, tv, out=out)
+            return ctx.bootstrap(lwe, tv, out=out)
 
     for _ in range(args.warmup):
         step()
     barrier()
     br_ms, ks_ms = [], []
+    last = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()  # enqueued back to back: the context records this step's events in its ring, nothing waits here
+        last = step()  # enqueued back to back: the context records this step's events in its ring, nothing waits here
     barrier()
     dt = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and last is not None:  # scatter-gather: the batch comes back to rank 0 only
+        # before any leg below reuses `out`: what the last timed step computed, as its caller receives it
+        dumped = dump_outputs(args.dump_outputs, {"lwe_out" if world == 1 or args.scatter_gather else f"lwe_out_rank{rank}": last},
+                              DUMP_BUDGET_BYTES if args.scatter_gather else DUMP_BUDGET_BYTES // world)
     # per-launch durations of the timed steps (HIP events on the kernel's own stream, the last 64 at most)
     for ago in range(min(args.steps, 64)):
         b, s = ctx.kernel_ms_ago(ago)
@@ -678,7 +753,7 @@ def main():
     achieved = algo_bytes / (br_avg * 1e-3) / 1e9
     kernel_name = f"blind_rotate_kernel<{backend_name},{logn},{k}>"
     traffic, traffic_source, valu_view = pmc_traffic(kernel_name, args.workload, batch)
-    hbm_copy = measure_hbm_copy_gbs(torch, dev, ctx=ctx)
+    hbm_copy = measure_hbm_copy_gbs(torch, dev, ctx=ctx) if args.full else None
     result = {
         "metric": "homomorphic_gates_per_sec" if args.gate else "programmable_bootstraps_per_sec",
         "value": value,
@@ -717,8 +792,6 @@ def main():
             "traffic": traffic,
             "traffic_source": traffic_source,
             "valu": valu_view,  # VALU-issue view from the same PMC passes (SURVEY 8d asks for both)
-            "hbm_copy_measured_GBps": hbm_copy,
-            "frac_of_measured_hbm": achieved / hbm_copy,
             # kernel_ms: HIP events on the context's stream around ALL blind-rotation launches of one step (launch_plan:
             # a batch larger than the chip goes out as `segments` launches per rotation -- one slice of the key each -- on
             # `streams` alternating streams, joined before the closing event); "per launch" below = per step's rotations
@@ -732,6 +805,10 @@ def main():
                     + "the key is shared by the batch and stays in L2/Infinity Cache; HBM fraction reported as the metric asks",
         },
     }
+    if hbm_copy is not None:
+        result["roofline"].update({"hbm_copy_measured_GBps": hbm_copy, "frac_of_measured_hbm": achieved / hbm_copy})
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
     if use_dist and world > 1 and args.scatter_gather_figure and not args.scatter_gather and not args.gate:
         # second figure, outside the timed region above: the same step with rank 0 owning the whole
         # batch -- RCCL scatter of [B/N][n+1] rows, local bootstrap, gather (sharding.bootstrap_sharded)
@@ -756,7 +833,7 @@ def main():
             "ms_per_step": float(t_sg.item()) / sg_steps * 1e3,
             "what": f"rank 0 holds all {batch * world} ciphertexts: isend/recv scatter of {batch * (n + 1) * 4 / 1e6:.0f} MB per peer "
                     "over RCCL/xGMI, local bootstrap, gather back; NOT the headline value"}
-    if plain_pbs and not args.no_secondary_legs and pbs[0] * (32 // pbs[0]) != 32:
+    if plain_pbs and secondary_legs and pbs[0] * (32 // pbs[0]) != 32:
         # log2 B does not divide 32 (cfg2: 7): with the reference's literal decomposer the top 32 mod log2 B bits of a
         # word are never decomposed, a trivially encrypted accumulator has no bit below them, every digit is zero and
         # the blind rotation never depends on the key -- in the reference too (decomposer.rs:42-80).  The
@@ -802,7 +879,7 @@ def main():
         except Exception as e:  # noqa: BLE001 - a secondary figure must not lose the benchmark line
             result["aligned_decomposer"] = {"error": str(e)}
     ctx.close()
-    if world == 1 and backend_name == "fp64-fft" and not args.gate and args.backend == "auto" and not args.no_secondary_legs:
+    if world == 1 and backend_name == "fp64-fft" and not args.gate and args.backend == "auto" and secondary_legs:
         # beside the headline (never instead of it): the same step in the exact prime-field NTT the complex-FFT backend
         # replaced as the default (same ciphertexts and key-switching key, a fresh random bootstrapping key: the time does
         # not depend on the data), so that both arithmetic routes are in one record

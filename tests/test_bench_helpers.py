@@ -1,6 +1,7 @@
 """CPU: the parts of bench.py that do not need a GPU -- the CPU legs (baseline + verification of the timed rows) on a
 small parameter set with the 'GPU rows' played by the oracle itself (and by a corrupted copy: the run must fail), the
-row selection, the usable-core count, and the kernel-source hash that gates the committed PMC traffic record."""
+row selection, the usable-core count, the kernel-source hash that gates the committed PMC traffic record, and the
+--dump-outputs writer."""
 import os
 import sys
 
@@ -83,3 +84,34 @@ def test_cpu_legs_verify_the_timed_rows_and_fail_on_a_wrong_word(oracle, monkeyp
     _, ver = bench.cpu_legs("tiny", 30.0, good)
     assert not ver["bit_exact"] and not ver["aligned_decomposer"]["bit_exact"]
     oracle.set_poly_mul_mode(1)
+
+
+def test_dump_outputs_is_exact_bounded_and_repeatable(tmp_path):
+    """--dump-outputs: ciphertext words come back exactly (every u32 is a float64); an output larger than its share of
+    the budget keeps the same seeded sample of rows on every call, with the row indices beside it; the files stay
+    inside the budget; a torch tensor is sampled like a numpy array"""
+    import torch
+    words = np.array([[0, 1, 2, 3], [(1 << 31) - 1, 1 << 31, (1 << 32) - 2, (1 << 32) - 1]], dtype=np.uint64).astype(np.uint32)
+    got = bench.dump_outputs(str(tmp_path / "small"), {"lwe_out": words.view(np.int32)})
+    back = np.load(tmp_path / "small" / "lwe_out.npy")
+    assert back.dtype == np.float64 and np.array_equal(back, words.astype(np.float64))
+    assert got == {"lwe_out": {"shape": [2, 4], "rows_of": 2}} and not (tmp_path / "small" / "lwe_out_rows.npy").exists()
+
+    rng = np.random.default_rng(5)
+    big = rng.integers(-(1 << 31), 1 << 31, size=(1000, 64), dtype=np.int64).astype(np.int32)
+    budget = 64 << 10
+    dirs = [tmp_path / "a", tmp_path / "b", tmp_path / "t"]
+    bench.dump_outputs(str(dirs[0]), {"x": big, "y": big[:10]}, budget)
+    bench.dump_outputs(str(dirs[1]), {"x": big, "y": big[:10]}, budget)
+    bench.dump_outputs(str(dirs[2]), {"x": torch.from_numpy(big), "y": torch.from_numpy(big[:10])}, budget)
+    assert sum(f.stat().st_size for f in dirs[0].iterdir()) <= budget
+    rows = np.load(dirs[0] / "x_rows.npy").astype(np.int64)
+    assert 1 < len(rows) < 1000 and np.array_equal(rows, np.unique(rows))
+    x = np.load(dirs[0] / "x.npy")
+    assert np.array_equal(x, big[rows].view(np.uint32).astype(np.float64))
+    assert np.array_equal(np.load(dirs[0] / "y.npy"), big[:10].view(np.uint32).astype(np.float64))
+    for d in dirs[1:]:
+        for name in ("x.npy", "x_rows.npy", "y.npy"):
+            assert np.array_equal(np.load(d / name), np.load(dirs[0] / name)), (d, name)
+    with pytest.raises(TypeError):
+        bench.dump_outputs(str(tmp_path / "f"), {"z": np.zeros((2, 2), dtype=np.float32)})

@@ -1,5 +1,5 @@
 """Effective shader clock of the blind-rotation launches, per leg of one bench.py run under
-  rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-include-regex blind_rotate -d DIR -o run --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline
+  rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-include-regex blind_rotate -d DIR -o run --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline
 usage: effective_clock.py DIR/.../run_counter_collection.csv [launches per step] [kernel name filter, default FftField]
 GRBM_GUI_ACTIVE is summed over the XCDs (8 on gfx950); a launch's cycles / 8 over its End - Start time is the clock the
 launch really ran at.  Launches are taken in dispatch order: step 0 = the literal decomposer's timed step, the following
