@@ -483,6 +483,48 @@ KeySwitchingKey generate_ksk(Engine& e, const LweSecretKey& from_lwe_sk, const L
                             to_n, ksk.data.data()));
   return ksk;
 }
+// ---- packing key switch (tfhe_hip.h: many LWE results into one GLWE) ----
+// These wrappers run on the engine's first device only (Engine::raw()): the packing key is not replicated over a pool.
+// (from_dimension * l_ks, k+1, N): row i*l_ks + l encrypts from_sk[i] * g_l under the GLWE key
+struct PackingKey {
+  std::vector<uint32_t> data;
+  size_t from_dimension = 0;
+};
+template <class Rng>
+PackingKey generate_packing_key(Engine& e, const LweSecretKey& from_lwe_sk, const GlweSecretKey& glwe_sk, Rng& rng) {
+  const TfheParams& p = e.params();
+  const size_t row_words = (p.glwe_dimension + 1) * p.degree();
+  const size_t rows = from_lwe_sk.data.size() * p.ks_decomposer.levels;
+  PackingKey pk{std::vector<uint32_t>(rows * row_words), from_lwe_sk.data.size()};
+  for (size_t r = 0; r < rows; ++r) fill_glwe_samples(p, rng, pk.data.data() + r * row_words);
+  e.check(tfhe_generate_packing_key(e.raw(), from_lwe_sk.data.data(), from_lwe_sk.data.size(), glwe_sk.data.data(),
+                                    pk.data.data()));
+  return pk;
+}
+// TFHE_ERR_EXACTNESS where the engine's backend cannot pack exactly under the KS decomposer
+inline void load_packing_key(Engine& e, const PackingKey& pk) {
+  const TfheParams& p = e.params();
+  if (pk.data.size() != pk.from_dimension * p.ks_decomposer.levels * (p.glwe_dimension + 1) * p.degree())
+    throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "packing key shape");
+  e.check(tfhe_load_packing_key(e.raw(), pk.data.data(), pk.from_dimension));
+}
+// up to N ciphertexts under the packing key's LWE key -> one GLWE whose coefficient j decrypts to what cts[j] does
+inline GlweCiphertext pack_lwe(Engine& e, const std::vector<LweCiphertext>& cts) {
+  const TfheParams& p = e.params();
+  if (cts.empty() || cts.size() > p.degree()) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "1 .. N ciphertexts per GLWE");
+  size_t from_dimension = 0;
+  int st = tfhe_packing_key_dimension(e.raw(), &from_dimension);
+  if (st != TFHE_OK) throw TfheError(st, "pack_lwe: load a packing key first");
+  const size_t width = from_dimension + 1;  // what the ABI reads per ciphertext
+  std::vector<uint32_t> in(cts.size() * width);
+  for (size_t j = 0; j < cts.size(); ++j) {
+    if (cts[j].data.size() != width) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "LWE length");
+    std::copy(cts[j].data.begin(), cts[j].data.end(), in.begin() + j * width);
+  }
+  GlweCiphertext out{std::vector<uint32_t>((p.glwe_dimension + 1) * p.degree())};
+  e.check(tfhe_pack_lwe_batch(e.raw(), in.data(), 1, cts.size(), out.data.data()));
+  return out;
+}
 // bootstrapping_key_gen bootstrapping.rs:23-56; the generated key is also installed in the engine.
 // bmmp = true makes the key of the unrolled blind rotation instead (notes/BMMP Bootstrapping.md:22-24:
 // GGSW(s s'), GGSW(s (1-s')), GGSW(s' (1-s)) per pair of key bits; N = 512, even n).

@@ -172,6 +172,46 @@ int tfhe_key_switch_batch(tfhe_context *ctx, const uint32_t *lwe_in, size_t batc
 int tfhe_key_switch_batch_device(tfhe_context *ctx, const uint32_t *lwe_in, size_t batch,
                                  uint32_t *lwe_out);
 
+/* ---- packing key switch (no reference counterpart): many LWE results into one GLWE ciphertext ---
+ * Pack(c_0 .. c_{m-1}) = (0, .., 0, sum_j b_j X^j) - sum_{i<d} sum_{l<l_ks} dec_l(A_i) (*) PK[i*l_ks + l] with
+ * A_i(X) = sum_j a_j,i X^j, dec_l the KS decomposer's signed digit of level l coefficient by coefficient and (*) the
+ * negacyclic product with every component of the key row.  Coefficient j of the result decrypts (under the GLWE key)
+ * to what c_j decrypts to, coefficients >= m to 0; sample_extract(.., j) + key switch gives an LWE of message j again.
+ * m LWEs of d+1 words become (k+1) N words: the inverse direction of tfhe_sample_extract_batch.
+ *
+ * Packing key: pksk [from_dimension*l_ks][k+1][N], row i*l_ks + l a GLWE encryption under glwe_sk of the constant
+ * polynomial from_sk[i] * g_l (g_l: the gadget factor tfhe_generate_ksk uses, in the context's alignment mode).
+ * tfhe_generate_packing_key completes a buffer pre-filled row by row like tfhe_glwe_encrypt_zero_batch (masks uniform,
+ * body = error); from_sk [from_dimension] and glwe_sk [k][N] are binary host arrays; the _device form takes pksk on the
+ * device.  tfhe_load_packing_key prepares the key and keeps it in the context, independently of the bootstrapping
+ * key; it also sizes the workspace, so that tfhe_pack_lwe_batch_device never allocates or synchronises (everything is
+ * ordered on the context's stream; safe under stream capture).
+ *
+ * Exactness: a call sums (k+1) l_ks key rows at a time in the backend's transform domain -- the external product's
+ * shape with the KS decomposer.  Where the backend's bound does not hold for that shape, tfhe_load_packing_key*
+ * returns TFHE_ERR_EXACTNESS with the reason in tfhe_last_error; nothing is computed outside a proven bound.
+ *
+ * Noise: every output coefficient carries the noise of its input plus, per coefficient, variance
+ *   d * l_ks * m * E[digit^2] * (sigma_glwe * 2^32)^2      (the key rows' errors, E[digit^2] ~ B^2/12)
+ *   + (d/2) * 2^(2*ignored_bits_ks) / 12                  (rounding to the decomposer's precision, binary key)
+ * in units of the 32-bit torus; m = per_group.
+ *
+ * lwe_in [groups][per_group][from_dimension+1], 1 <= per_group <= N; glwe_out [groups][k+1][N].
+ * TFHE_ERR_NO_KEY before a packing key is loaded. */
+int tfhe_generate_packing_key(tfhe_context *ctx, const uint32_t *from_sk, size_t from_dimension,
+                              const uint32_t *glwe_sk, uint32_t *pksk);
+int tfhe_generate_packing_key_device(tfhe_context *ctx, const uint32_t *from_sk, size_t from_dimension,
+                                     const uint32_t *glwe_sk, uint32_t *pksk);
+int tfhe_load_packing_key(tfhe_context *ctx, const uint32_t *pksk, size_t from_dimension);
+int tfhe_load_packing_key_device(tfhe_context *ctx, const uint32_t *pksk, size_t from_dimension);
+/* dimension of the LWE key the loaded packing key packs from: tfhe_pack_lwe_batch* reads from_dimension+1 words per
+ * ciphertext, so a caller that holds shaped arrays checks their width against it; TFHE_ERR_NO_KEY if none is loaded */
+int tfhe_packing_key_dimension(const tfhe_context *ctx, size_t *from_dimension);
+int tfhe_pack_lwe_batch(tfhe_context *ctx, const uint32_t *lwe_in, size_t groups, size_t per_group,
+                        uint32_t *glwe_out);
+int tfhe_pack_lwe_batch_device(tfhe_context *ctx, const uint32_t *lwe_in, size_t groups, size_t per_group,
+                               uint32_t *glwe_out);
+
 /* ---- ggsw.rs ------------------------------------------------------------------------------ */
 /* external_product(): ggsw.rs:132-161.  ggsw [ggsw_count][(k+1)*l][k+1][N] with ggsw_count = 1
  * (one GGSW for the whole batch, the blind-rotation shape) or batch; glwe [batch][k+1][N]. */
@@ -353,6 +393,7 @@ int tfhe_context_set_decomposer_alignment(tfhe_context *ctx, int aligned);
 #define TFHE_FILE_GLWE 4  /* [batch][k+1][N] */
 #define TFHE_FILE_GGSW 5  /* [count][(k+1)l][k+1][N] */
 #define TFHE_FILE_WORDS 6 /* any other u32 array (test vectors [N], mod-switched masks, ...) */
+#define TFHE_FILE_PKSK 7  /* [from_dimension*l_ks][k+1][N] (tfhe_generate_packing_key) */
 #define TFHE_FILE_FLAG_ALIGNED 1u
 int tfhe_file_write(const char *path, uint32_t kind, const tfhe_params *params, uint32_t flags,
                     const uint32_t *dims, uint32_t ndims, const uint32_t *data);

@@ -49,6 +49,13 @@ extern "C" {
     fn tfhe_key_switch_batch(ctx: *mut TfheContext, lwe_in: *const u32, batch: usize, lwe_out: *mut u32) -> c_int;
     fn tfhe_external_product_batch(ctx: *mut TfheContext, ggsw: *const u32, ggsw_count: usize,
                                    glwe_in: *const u32, batch: usize, glwe_out: *mut u32) -> c_int;
+    // packing key switch (include/tfhe_hip.h): many LWE results into one GLWE ciphertext
+    fn tfhe_generate_packing_key(ctx: *mut TfheContext, from_sk: *const u32, from_dimension: usize,
+                                 glwe_sk: *const u32, pksk: *mut u32) -> c_int;
+    fn tfhe_load_packing_key(ctx: *mut TfheContext, pksk: *const u32, from_dimension: usize) -> c_int;
+    fn tfhe_packing_key_dimension(ctx: *const TfheContext, from_dimension: *mut usize) -> c_int;
+    fn tfhe_pack_lwe_batch(ctx: *mut TfheContext, lwe_in: *const u32, groups: usize, per_group: usize,
+                           glwe_out: *mut u32) -> c_int;
     fn tfhe_cmux_batch(ctx: *mut TfheContext, ggsw: *const u32, ggsw_count: usize, ct0: *const u32,
                        ct1: *mut u32, batch: usize, glwe_out: *mut u32) -> c_int;
     fn tfhe_gate_batch(ctx: *mut TfheContext, truth: *const u32, ct0: *const u32, ct1: *const u32,
@@ -176,6 +183,35 @@ pub fn gate_batch(bk: &GpuBootstrappingKey, truth: [u32; 4], ct0: &Array2<u32>, 
 pub fn key_switch_lwe(bk: &GpuBootstrappingKey, lwe_ciphertext: &Array1<u32>) -> Array1<u32> {
     let mut out = Array1::<u32>::zeros(bk.params.lwe_dimension as usize + 1);
     check(bk.ctx, unsafe { tfhe_key_switch_batch(bk.ctx, lwe_ciphertext.as_slice().unwrap().as_ptr(), 1, out.as_slice_mut().unwrap().as_mut_ptr()) }, "key_switch_lwe");
+    out
+}
+
+/// Completes a packing key [from_dimension*l_ks][k+1][N] whose rows the caller pre-filled like zero GLWE encryptions
+/// (uniform masks, error in the body): row i*l_ks + l encrypts from_sk[i] * g_l under `glwe_sk` (no reference counterpart).
+pub fn generate_packing_key(bk: &GpuBootstrappingKey, from_sk: &Array1<u32>, glwe_sk: &Array2<u32>, samples: &mut Array3<u32>) {
+    check(bk.ctx, unsafe {
+        tfhe_generate_packing_key(bk.ctx, from_sk.as_slice().unwrap().as_ptr(), from_sk.len(),
+                                  glwe_sk.as_slice().unwrap().as_ptr(), samples.as_slice_mut().unwrap().as_mut_ptr())
+    }, "generate_packing_key");
+}
+
+/// Prepares and keeps a packing key from an LWE key of `from_dimension` bits (independent of the bootstrapping key).
+pub fn load_packing_key(bk: &GpuBootstrappingKey, pksk: &Array3<u32>, from_dimension: usize) {
+    check(bk.ctx, unsafe { tfhe_load_packing_key(bk.ctx, pksk.as_slice().unwrap().as_ptr(), from_dimension) }, "load_packing_key");
+}
+
+/// Up to N LWE ciphertexts (rows of `lwe`, from_dimension+1 words each) -> one GLWE (k+1, N) whose coefficient j
+/// decrypts to what row j decrypts to.
+pub fn pack_lwe(bk: &GpuBootstrappingKey, lwe: &Array2<u32>) -> Array2<u32> {
+    let n = 1usize << bk.params.glwe_poly_degree;
+    let mut from_dimension = 0usize;
+    check(bk.ctx, unsafe { tfhe_packing_key_dimension(bk.ctx, &mut from_dimension) }, "pack_lwe: no packing key loaded");
+    // the ABI reads from_dimension+1 words per ciphertext
+    assert!(lwe.ncols() == from_dimension + 1 && lwe.nrows() >= 1 && lwe.nrows() <= n, "pack_lwe: rows of from_dimension+1 words, 1..=N of them");
+    let mut out = Array2::<u32>::zeros((bk.params.glwe_dimension as usize + 1, n));
+    check(bk.ctx, unsafe {
+        tfhe_pack_lwe_batch(bk.ctx, lwe.as_slice().unwrap().as_ptr(), 1, lwe.nrows(), out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "pack_lwe");
     out
 }
 

@@ -28,7 +28,7 @@ STATUS_NAMES = {
 }
 (TFHE_ERR_INVALID_PARAMS, TFHE_ERR_UNSUPPORTED, TFHE_ERR_NO_KEY, TFHE_ERR_HIP, TFHE_ERR_INVALID_ARGUMENT,
  TFHE_ERR_NO_DEVICE, TFHE_ERR_EXACTNESS, TFHE_ERR_IO) = range(1, 9)
-FILE_BSK, FILE_KSK, FILE_LWE, FILE_GLWE, FILE_GGSW, FILE_WORDS = 1, 2, 3, 4, 5, 6
+FILE_BSK, FILE_KSK, FILE_LWE, FILE_GLWE, FILE_GGSW, FILE_WORDS, FILE_PKSK = 1, 2, 3, 4, 5, 6, 7
 DECOMPOSER_PBS, DECOMPOSER_KS = 0, 1
 BACKEND_AUTO, BACKEND_GOLDILOCKS, BACKEND_FP64, BACKEND_GOLDILOCKS_SPLIT, BACKEND_FP64_P49, BACKEND_FP64_FFT = 0, 1, 2, 3, 4, 5
 SHAPE_AUTO, SHAPE_WIDE, SHAPE_TEAM = 0, 1, 2   # tfhe_context_set_kernel_shape
@@ -108,6 +108,10 @@ class TfheParams:
 
     def ksk_shape(self):
         return (self.big_n * self.ks_decomposer.levels, self.n + 1)
+
+    def pksk_shape(self, from_dimension: int):
+        """the packing key from an LWE key of `from_dimension` bits: one GLWE row per (key bit, KS level)"""
+        return (from_dimension * self.ks_decomposer.levels, self.k + 1, self.N)
 
     def external_product_bytes(self) -> int:
         """algorithmic bytes of one GGSW x GLWE external product in the reference's u32 layout,
@@ -341,6 +345,12 @@ class Context:
         if st:
             raise TfheError(st, lib().tfhe_last_error(self._h).decode())
 
+    @staticmethod
+    def _check_quiet(st: int, message: str):
+        """for entry points that set no tfhe_last_error"""
+        if st:
+            raise TfheError(st, message)
+
     @property
     def backend(self) -> str:
         return lib().tfhe_context_backend(self._h).decode()
@@ -551,6 +561,67 @@ class Context:
         x = _np(lwe_big).reshape(-1, p.big_n + 1)
         res = np.zeros((x.shape[0], p.n + 1), dtype=np.uint32)
         self._check(lib().tfhe_key_switch_batch(self._h, _hp(x), C.c_size_t(x.shape[0]), _hp(res)))
+        return res
+
+    # -- packing key switch: many LWE results into one GLWE (include/tfhe_hip.h states the operation) --
+    def generate_packing_key(self, from_sk, glwe_sk, samples):
+        """samples [from_dim*l_ks][k+1][N] pre-filled row by row like glwe_encrypt_zero (uniform masks, errors in
+        the body) -> the packing key from `from_sk` (any dimension) to `glwe_sk`, with the context's ks_decomposer.
+        A torch device tensor is completed in place and returned."""
+        p = self.params
+        f, sk = _np(from_sk).reshape(-1), _np(glwe_sk).reshape(p.k, p.N)
+        if _is_torch(samples):
+            self._bind_torch()
+            assert tuple(samples.shape) == p.pksk_shape(f.size)
+            self._check(lib().tfhe_generate_packing_key_device(self._h, _hp(f), C.c_size_t(f.size), _hp(sk),
+                                                               _dp(samples)))
+            return samples
+        out = _np(samples).copy()
+        assert out.shape == p.pksk_shape(f.size)
+        self._check(lib().tfhe_generate_packing_key(self._h, _hp(f), C.c_size_t(f.size), _hp(sk), _hp(out)))
+        return out
+
+    def load_packing_key(self, pksk):
+        """prepares pksk [from_dim*l_ks][k+1][N] (numpy or torch device tensor) and keeps it: independent of the
+        bootstrapping key.  TfheError(TFHE_ERR_EXACTNESS) where the backend cannot pack exactly under the KS decomposer."""
+        p = self.params
+        rows = int(pksk.shape[0])
+        assert tuple(pksk.shape[1:]) == (p.k + 1, p.N) and rows % p.ks_decomposer.levels == 0
+        dim = rows // p.ks_decomposer.levels
+        if _is_torch(pksk):
+            self._bind_torch()
+            self._check(lib().tfhe_load_packing_key_device(self._h, _dp(pksk), C.c_size_t(dim)))
+        else:
+            self._check(lib().tfhe_load_packing_key(self._h, _hp(_np(pksk)), C.c_size_t(dim)))
+
+    def pack_lwe(self, lwe, out=None):
+        """lwe [groups][per_group][from_dim+1] (or [per_group][from_dim+1]: one group), per_group <= N ->
+        GLWE [groups][k+1][N] whose coefficient j decrypts to what ciphertext j of the group decrypts to."""
+        p = self.params
+        dim = C.c_size_t()
+        self._check_quiet(lib().tfhe_packing_key_dimension(self._h, C.byref(dim)), "load a packing key first")
+        if not _is_torch(lwe):
+            lwe = _np(lwe)
+        # the ABI reads from_dim+1 words per ciphertext: a wrong width would be read out of bounds
+        if lwe.ndim not in (2, 3) or lwe.shape[-1] != dim.value + 1:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"pack_lwe: ciphertexts of {dim.value + 1} words expected "
+                                                       f"([groups][per_group][from_dim+1]), got shape {tuple(lwe.shape)}")
+        if _is_torch(lwe):
+            self._bind_torch()
+            import torch
+            if not lwe.is_contiguous():
+                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "pack_lwe: the device tensor must be contiguous")
+            x = lwe if lwe.dim() == 3 else lwe.unsqueeze(0)
+            if out is None:
+                out = torch.empty((x.shape[0], p.k + 1, p.N), dtype=lwe.dtype, device=lwe.device)
+            self._check(lib().tfhe_pack_lwe_batch_device(self._h, _dp(x), C.c_size_t(x.shape[0]),
+                                                         C.c_size_t(x.shape[1]), _dp(out)))
+            return out
+        x = _np(lwe)
+        x = x if x.ndim == 3 else x[None]
+        res = np.zeros((x.shape[0], p.k + 1, p.N), dtype=np.uint32)
+        self._check(lib().tfhe_pack_lwe_batch(self._h, _hp(x), C.c_size_t(x.shape[0]), C.c_size_t(x.shape[1]),
+                                              _hp(res)))
         return res
 
     def external_product(self, ggsw, glwe) -> np.ndarray:
@@ -866,6 +937,19 @@ class Context:
         gen = self.bootstrapping_key_gen_bmmp if bmmp else self.bootstrapping_key_gen
         bsk, ksk = gen(lwe_sk, glwe_sk, bsk, ksk, load=load)
         return lwe_sk, glwe_sk, bsk, ksk
+
+    def generate_packing_key_random(self, from_sk, glwe_sk, rng=None, load: bool = True) -> np.ndarray:
+        """generate_packing_key with masks and errors (glwe_std_dev) drawn here, the way generate_keys draws the
+        bootstrapping key's (the OS CSPRNG unless the test hook `rng=` is given); `load` installs it."""
+        p = self.params
+        rng = rng if rng is not None else SystemRng()
+        shape = p.pksk_shape(_np(from_sk).size)
+        samples = rng.integers(0, 1 << 32, size=shape, dtype=np.uint64).astype(np.uint32)
+        samples[:, p.k, :] = self._noise(rng, p.glwe_std_dev, (shape[0], p.N))
+        pksk = self.generate_packing_key(from_sk, glwe_sk, samples)
+        if load:
+            self.load_packing_key(pksk)
+        return pksk
 
     def encrypt_bits(self, lwe_sk, messages, rng=None) -> np.ndarray:
         """LweCleartext::encode_message + encrypt_lwe_plaintext (lwe.rs:81-92,138-160) for a batch

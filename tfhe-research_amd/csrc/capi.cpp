@@ -472,7 +472,7 @@ void tfhe_context_destroy(tfhe_context* ctx) {
   void* ptrs[] = {ctx->d_queue,  ctx->d_tw,     ctx->d_bsk,    ctx->d_ksk,    ctx->d_lwe_in, ctx->d_lwe_in2,
                   ctx->d_lwe_big, ctx->d_lwe_out, ctx->d_lwe_ks, ctx->d_glwe_a, ctx->d_glwe_b, ctx->d_glwe_c,
                   ctx->d_tv,     ctx->d_misc,   ctx->d_ggsw_tmp, ctx->d_ggsw_raw,
-                  ctx->d_key_tmp};
+                  ctx->d_key_tmp, ctx->d_pksk, ctx->d_pack_cols};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& g : ctx->gate_tvs)
@@ -1368,6 +1368,247 @@ int tfhe_bootstrapping_key_gen_bmmp(tfhe_context* ctx, const uint32_t* lwe_sk, c
   return st;
 }
 
+// ---------------------------------------------------------------------------------- packing key switch
+namespace {
+
+// transposed inputs of one launch pair of a packing call: as many outputs as fit 64 MiB (cfg2: 24 of 2.6 MB), at
+// least one.  Sized at key load, so that tfhe_pack_lwe_batch_device never allocates.
+constexpr size_t kPackColsWords = (size_t)16 << 20;
+
+size_t pack_cols_words_per_group(const tfhe_context* ctx) { return (ctx->pksk_dim + 1) * (size_t)ctx->N; }
+
+// Why this backend cannot pack under the context's KS decomposer, or "" if it can.  A packing call sums the
+// R_c = (k+1) l_ks rows of one slice in the transform domain and nothing more (pbs_wave.h::pack_lwe_team), so the bounds
+// are the external product's with R_c rows and the KS base.
+std::string packing_refusal(const tfhe_context* ctx) {
+  const tfhe_params& p = ctx->params;
+  const int rows = (int)((p.glwe_dimension + 1) * ctx->ks.levels);
+  const int lb = (int)ctx->ks.log_base;
+  const double bits = std::log2((double)rows) + p.glwe_poly_degree + lb;
+  auto prime = [&](const char* name, double key_bits, double exact_bits, int max_rows, int small_bits, int max_log_base) {
+    char buf[256];
+    if (lb > max_log_base || lb > small_bits) {
+      std::snprintf(buf, sizeof buf, "%s: KS log_base %d exceeds the backend's largest gadget base 2^%d", name, lb,
+                    std::min(max_log_base, small_bits));
+      return std::string(buf);
+    }
+    if (rows > max_rows) {
+      std::snprintf(buf, sizeof buf, "%s: (k+1) l_ks = %d rows per slice exceed the backend's %d", name, rows, max_rows);
+      return std::string(buf);
+    }
+    if (!(bits + key_bits < exact_bits)) {
+      std::snprintf(buf, sizeof buf, "%s: a slice of (k+1) l_ks = %d rows in base 2^%d needs %.2f bits, the field lifts %.2f",
+                    name, rows, lb, bits + key_bits, exact_bits);
+      return std::string(buf);
+    }
+    return std::string();
+  };
+  switch (ctx->field) {
+    case launch::kFieldFp64:
+      return prime("fp64-p42", FpField::key_bits(), FpField::exact_bits(), FpField::kMaxRows, FpField::kSmallBits, FpField::kMaxLogBase);
+    case launch::kFieldFp49:
+      return prime("fp64-p49", Fp49Field::key_bits(), Fp49Field::exact_bits(), Fp49Field::kMaxRows, Fp49Field::kSmallBits, Fp49Field::kMaxLogBase);
+    case launch::kFieldGoldilocks:
+      return prime("goldilocks", GlField::key_bits(), GlField::exact_bits(), GlField::kMaxRows, GlField::kSmallBits, GlField::kMaxLogBase);
+    case launch::kFieldGoldilocksSplit:
+      return prime("goldilocks-split", GlSplitField::key_bits(), GlSplitField::exact_bits(), GlSplitField::kMaxRows,
+                   GlSplitField::kSmallBits, GlSplitField::kMaxLogBase);
+    default: {
+      char buf[256];
+      if (lb > FftField::kMaxLogBase || lb > FftField::kSmallBits) {
+        std::snprintf(buf, sizeof buf, "fp64-fft: KS log_base %d exceeds FftField::kMaxLogBase = %d", lb, FftField::kMaxLogBase);
+        return std::string(buf);
+      }
+      if (rows > FftField::kMaxRows) {
+        std::snprintf(buf, sizeof buf, "fp64-fft: (k+1) l_ks = %d rows per slice exceed FftField::kMaxRows = %d", rows, FftField::kMaxRows);
+        return std::string(buf);
+      }
+      const double err = FftField::error_bound((int)p.glwe_poly_degree, rows, lb);
+      if (!(err < FftField::kMaxError)) {
+        std::snprintf(buf, sizeof buf, "fp64-fft: rounding bound %.4g of a slice of %d rows in base 2^%d is not below %.4g", err,
+                      rows, lb, FftField::kMaxError);
+        return std::string(buf);
+      }
+      return std::string();
+    }
+  }
+}
+
+// d_raw: [from_dimension * l_ks][k+1][N] on the device
+int load_packing_key_common(tfhe_context* ctx, const u32* d_raw, size_t from_dimension) {
+  const std::string why = packing_refusal(ctx);
+  if (!why.empty()) return fail(ctx, TFHE_ERR_EXACTNESS, "packing key refused: " + why);
+  const u32 k1 = ctx->params.glwe_dimension + 1;
+  const size_t slices = (from_dimension + k1 - 1) / k1;
+  const size_t poly_bytes = (size_t)ctx->parts * ctx->N * sizeof(u64);  // one prepared key polynomial
+  const size_t polys = from_dimension * ctx->ks.levels * k1;
+  const size_t bytes = slices * k1 * ctx->ks.levels * k1 * poly_bytes;
+  // until the new key is complete the context holds none
+  ctx->have_pksk = false;
+  if (ctx->d_pksk && ctx->pksk_bytes != bytes) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    hipError_t e = hipFree(ctx->d_pksk);
+    ctx->d_pksk = nullptr;
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipFree(pksk)");
+  }
+  if (!ctx->d_pksk) {
+    HIP_TRY(ctx, hipMalloc(&ctx->d_pksk, bytes));
+    ctx->pksk_bytes = bytes;
+  }
+  ctx->pksk_dim = from_dimension;
+  const size_t want_cols = std::max(kPackColsWords, pack_cols_words_per_group(ctx));
+  if (ctx->pack_cols_words < want_cols) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    int st = ensure(ctx, &ctx->d_pack_cols, &ctx->pack_cols_words, want_cols);
+    if (st) return st;
+  }
+  // rows past from_dimension (the last slice, when k+1 does not divide it): zero spectra
+  if (polys * poly_bytes < bytes)
+    HIP_TRY(ctx, hipMemsetAsync(static_cast<unsigned char*>(ctx->d_pksk) + polys * poly_bytes, 0, bytes - polys * poly_bytes, ctx->stream));
+  HIP_TRY(ctx, launch::bsk_prepare(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->pbs.k, ctx->d_tw, d_raw, polys, ctx->d_pksk));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->have_pksk = true;
+  return TFHE_OK;
+}
+
+int check_packing_dimension(tfhe_context* ctx, size_t from_dimension) {
+  if (from_dimension == 0 || from_dimension >= (1u << 24))
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "from_dimension must be in [1, 2^24)");
+  return TFHE_OK;
+}
+
+}  // namespace
+
+int tfhe_generate_packing_key_device(tfhe_context* ctx, const uint32_t* from_sk, size_t from_dimension,
+                                     const uint32_t* glwe_sk, uint32_t* pksk) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  if (!from_sk || !glwe_sk || !pksk) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  if ((st = check_packing_dimension(ctx, from_dimension))) return st;
+  const u32 k = ctx->params.glwe_dimension;
+  const size_t kn = (size_t)k * ctx->N;
+  if ((st = check_binary(ctx, from_sk, from_dimension, "from secret key"))) return st;
+  if ((st = check_binary(ctx, glwe_sk, kn, "glwe secret key"))) return st;
+  const u32 levels = ctx->ks.levels, log_base = ctx->ks.log_base;
+  const u32 top = gadget_top(ctx, log_base);
+  const size_t rows = from_dimension * levels;
+  // row i*levels + level is a zero encryption plus s_i g_level on coefficient 0 of the body (the factors of ksk_gen_device)
+  std::vector<u32> factor(rows);
+  for (size_t i = 0; i < from_dimension; ++i)
+    for (u32 level = 0; level < levels; ++level)
+      factor[i * levels + level] = (1u << (top - log_base * (level + 1))) * from_sk[i];
+  if ((st = ensure_key_tmp(ctx, kn + rows))) return st;
+  if ((st = to_key_tmp(ctx, glwe_sk, kn, 0))) return st;
+  if ((st = to_key_tmp(ctx, factor.data(), rows, kn))) return st;
+  if ((st = glwe_rows_add_mask_dot_key(ctx, pksk, rows))) return st;
+  HIP_TRY(ctx, launch::packing_add_gadget(ctx->stream, pksk, rows, k, ctx->pbs.log_n, ctx->d_key_tmp + kn));
+  // `factor` is pageable host memory: the async copy has staged it before returning
+  return TFHE_OK;
+}
+
+int tfhe_generate_packing_key(tfhe_context* ctx, const uint32_t* from_sk, size_t from_dimension,
+                              const uint32_t* glwe_sk, uint32_t* pksk) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  if (!from_sk || !glwe_sk || !pksk) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  if ((st = check_packing_dimension(ctx, from_dimension))) return st;
+  const size_t words = from_dimension * ctx->ks.levels * (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
+  if ((st = ensure_misc(ctx, words * sizeof(u32)))) return st;
+  u32* d = reinterpret_cast<u32*>(ctx->d_misc);
+  HIP_TRY(ctx, hipMemcpyAsync(d, pksk, words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
+  if ((st = tfhe_generate_packing_key_device(ctx, from_sk, from_dimension, glwe_sk, d))) return st;
+  HIP_TRY(ctx, hipMemcpyAsync(pksk, d, words * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return TFHE_OK;
+}
+
+int tfhe_load_packing_key_device(tfhe_context* ctx, const uint32_t* pksk, size_t from_dimension) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  if (!pksk) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null key pointer");
+  if ((st = check_packing_dimension(ctx, from_dimension))) return st;
+  return load_packing_key_common(ctx, pksk, from_dimension);
+}
+
+int tfhe_load_packing_key(tfhe_context* ctx, const uint32_t* pksk, size_t from_dimension) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  if (!pksk) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null key pointer");
+  if ((st = check_packing_dimension(ctx, from_dimension))) return st;
+  const std::string why = packing_refusal(ctx);  // before the upload
+  if (!why.empty()) return fail(ctx, TFHE_ERR_EXACTNESS, "packing key refused: " + why);
+  const size_t words = from_dimension * ctx->ks.levels * (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
+  u32* d_raw = nullptr;
+  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&d_raw), words * sizeof(u32)));
+  hipError_t e = hipMemcpy(d_raw, pksk, words * sizeof(u32), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(d_raw);
+    return hip_fail(ctx, e, "packing key upload");
+  }
+  st = load_packing_key_common(ctx, d_raw, from_dimension);
+  (void)hipFree(d_raw);
+  return st;
+}
+
+int tfhe_packing_key_dimension(const tfhe_context* ctx, size_t* from_dimension) {
+  if (!ctx || !from_dimension) return TFHE_ERR_INVALID_ARGUMENT;
+  if (!ctx->have_pksk) return TFHE_ERR_NO_KEY;
+  *from_dimension = ctx->pksk_dim;
+  return TFHE_OK;
+}
+
+static int check_pack_args(tfhe_context* ctx, const void* in, size_t groups, size_t per_group, const void* out) {
+  if (!in || !out) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  if (groups == 0 || groups > kMaxBatch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "groups must be in [1, 2^31)");
+  if (per_group == 0 || per_group > ctx->N)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "per_group must be in [1, N]: a GLWE has N coefficients");
+  if (!ctx->have_pksk) return fail(ctx, TFHE_ERR_NO_KEY, "load a packing key first (tfhe_load_packing_key)");
+  return TFHE_OK;
+}
+
+int tfhe_pack_lwe_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_t groups, size_t per_group,
+                               uint32_t* glwe_out) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  if ((st = check_pack_args(ctx, lwe_in, groups, per_group, glwe_out))) return st;
+  const u32 d = (u32)ctx->pksk_dim;
+  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
+  // the decomposer may have been re-aligned since the key was loaded (as for the KSK, the caller keeps them in step)
+  PbsParams P = ctx->pbs;
+  P.log_base = ctx->ks.log_base;
+  P.levels = ctx->ks.levels;
+  P.ignored_bits = ctx->ks.ignored_bits;
+  P.first_shift = ctx->ks.first_shift;
+  // the teams add their partial sums into the output (a memset node under stream capture)
+  HIP_TRY(ctx, hipMemsetAsync(glwe_out, 0, groups * glwe * sizeof(u32), ctx->stream));
+  const size_t chunk = ctx->pack_cols_words / pack_cols_words_per_group(ctx);  // >= 1 by construction
+  for (size_t g0 = 0; g0 < groups; g0 += chunk) {
+    const size_t here = std::min(chunk, groups - g0);
+    HIP_TRY(ctx, launch::pack_transpose(ctx->stream, lwe_in + g0 * per_group * ((size_t)d + 1), here, (u32)per_group, d,
+                                        ctx->pbs.log_n, ctx->d_pack_cols));
+    HIP_TRY(ctx, launch::pack_lwe(ctx->stream, ctx->field, P, ctx->d_tw, ctx->d_pksk, ctx->d_pack_cols, d, here,
+                                  glwe_out + g0 * glwe));
+  }
+  return TFHE_OK;
+}
+
+int tfhe_pack_lwe_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t groups, size_t per_group,
+                        uint32_t* glwe_out) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  if ((st = check_pack_args(ctx, lwe_in, groups, per_group, glwe_out))) return st;
+  const size_t in_words = groups * per_group * (ctx->pksk_dim + 1);
+  const size_t out_words = groups * (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
+  if ((st = ensure_misc(ctx, (in_words + out_words) * sizeof(u32)))) return st;
+  u32* d_in = reinterpret_cast<u32*>(ctx->d_misc);
+  u32* d_out = d_in + in_words;
+  HIP_TRY(ctx, hipMemcpyAsync(d_in, lwe_in, in_words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
+  if ((st = tfhe_pack_lwe_batch_device(ctx, d_in, groups, per_group, d_out))) return st;
+  HIP_TRY(ctx, hipMemcpyAsync(glwe_out, d_out, out_words * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return TFHE_OK;
+}
+
 // ---------------------------------------------------------------------------------- on-disk format
 namespace {
 
@@ -1423,7 +1664,7 @@ int read_header(std::FILE* f, FileHeader* h) {
   for (int i = 0; i < 4; ++i) h->dims[i] = get_u32(b + 68 + 4 * i);
   h->words = get_u64(b + 88);
   h->checksum = get_u64(b + 96);
-  if (h->kind < TFHE_FILE_BSK || h->kind > TFHE_FILE_WORDS || h->ndims == 0 || h->ndims > 4) return TFHE_ERR_IO;
+  if (h->kind < TFHE_FILE_BSK || h->kind > TFHE_FILE_PKSK || h->ndims == 0 || h->ndims > 4) return TFHE_ERR_IO;
   u64 prod = 1;
   for (u32 i = 0; i < 4; ++i) {
     if (h->dims[i] == 0 || (i >= h->ndims && h->dims[i] != 1)) return TFHE_ERR_IO;
@@ -1441,7 +1682,7 @@ int read_header(std::FILE* f, FileHeader* h) {
 
 int tfhe_file_write(const char* path, uint32_t kind, const tfhe_params* params, uint32_t flags,
                     const uint32_t* dims, uint32_t ndims, const uint32_t* data) {
-  if (!path || !params || !dims || !data || ndims == 0 || ndims > 4 || kind < TFHE_FILE_BSK || kind > TFHE_FILE_WORDS)
+  if (!path || !params || !dims || !data || ndims == 0 || ndims > 4 || kind < TFHE_FILE_BSK || kind > TFHE_FILE_PKSK)
     return TFHE_ERR_INVALID_ARGUMENT;
   u64 words = 1;
   for (u32 i = 0; i < ndims; ++i) {

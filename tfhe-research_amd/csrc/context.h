@@ -31,6 +31,13 @@ struct tfhe_context {
   bool have_key = false;
   bool bmmp = false;          // the loaded key is a BMMP key: n/2 * 3 GGSWs (tfhe_load_bootstrapping_key_bmmp)
   size_t bsk_ggsws = 0;       // GGSWs d_bsk was allocated for
+  // packing key (tfhe_load_packing_key): independent of the bootstrapping key
+  void* d_pksk = nullptr;     // prepared: ceil(pksk_dim / (k+1)) slices of [(k+1) l_ks][k+1][parts][N], zero-filled past pksk_dim
+  size_t pksk_bytes = 0;
+  size_t pksk_dim = 0;        // dimension of the LWE key it packs from
+  bool have_pksk = false;
+  u32* d_pack_cols = nullptr; // transposed inputs of a packing call, kPackColsWords words (capi.cpp) or one output's worth
+  size_t pack_cols_words = 0;
   bool aligned = false;       // decomposer alignment (tfhe_context_set_decomposer_alignment)
   bool ks_first = false;      // bootstrap order (tfhe_context_set_bootstrap_order)
   int shape = 0;              // kernel shape of the blind rotation (tfhe_context_set_kernel_shape): launch::kShape*

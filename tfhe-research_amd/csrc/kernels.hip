@@ -677,6 +677,74 @@ external_product_kernel(PbsParams P, const typename F::elem* __restrict__ tw,
   }
 }
 
+// ------------------------------------------------------------------------------ packing key switch
+// pbs_wave.h::pack_lwe_team states the operation and its exactness bound.  Two kernels per call:
+//
+// pack_transpose_kernel: lwe_in [groups][m][d+1] -> cols [groups][d+1][N], cols[g][i][j] = lwe_in[g][j][i] for j < m
+// and 0 for m <= j < N (row d is the body polynomial sum_j b_j X^j).  32 x 32 tiles through LDS (33-word rows: no bank
+// conflicts either way), 128-byte segments on both sides; grid (tiles over i, tiles over j, groups -- strided).
+//
+// pack_lwe_kernel: grid (output GLWE, run of key-row slices), x fastest, so that the teams in flight at one time are
+// all the outputs of a few runs and read the same slices of the key while those are hot in the L2s.  A team sums its
+// slices in LDS and adds the partial result to the pre-zeroed output with u32 atomic adds -- 64 consecutive words per
+// wave instruction; wrapping addition is associative and commutative, so the bits do not depend on the order the
+// teams arrive in.  Run 0 of an output also contributes the body row.
+constexpr int kPackTile = 32;
+__global__ void __launch_bounds__(256) pack_transpose_kernel(const u32* __restrict__ lwe_in, size_t groups, u32 m, u32 d,
+                                                             u32 log_n, u32* __restrict__ cols) {
+  __shared__ u32 tile[kPackTile][kPackTile + 1];
+  const u32 N = 1u << log_n;
+  const u32 width = d + 1;
+  const u32 tx = threadIdx.x & (kPackTile - 1), ty = threadIdx.x / kPackTile;  // ty 0..7
+  const u32 i0 = blockIdx.x * kPackTile, j0 = blockIdx.y * kPackTile;
+  for (size_t g = blockIdx.z; g < groups; g += gridDim.z) {
+    const u32* in = lwe_in + g * (size_t)m * width;
+    u32* out = cols + g * (size_t)width * N;
+#pragma unroll
+    for (u32 t = 0; t < kPackTile; t += 8) {
+      const u32 j = j0 + ty + t, i = i0 + tx;
+      tile[ty + t][tx] = (j < m && i < width) ? in[(size_t)j * width + i] : 0u;
+    }
+    __syncthreads();
+#pragma unroll
+    for (u32 t = 0; t < kPackTile; t += 8) {
+      const u32 i = i0 + ty + t, j = j0 + tx;  // j < N: N is a multiple of the tile
+      if (i < width) out[(size_t)i * N + j] = tile[tx][ty + t];
+    }
+    __syncthreads();
+  }
+}
+
+template <class F, int LOGN, int K>
+__global__ void __launch_bounds__((TeamCfg<F, LOGN, K, 1>::kThreads),
+                                  (F::kId == FpField::kId || F::kId == Fp49Field::kId || F::kId == FftField::kId
+                                       ? TeamCfg<F, LOGN, K, 1>::kMinWavesFp
+                                       : TeamCfg<F, LOGN, K, 1>::kMinWavesGl))
+pack_lwe_kernel(PbsParams P /* the KS decomposer */, const typename F::elem* __restrict__ tw,
+                const typename F::elem* __restrict__ key, const u32* __restrict__ cols, u32 d, u32 slices,
+                u32 slices_per_run, u32* glwe_out) {
+  using C = TeamCfg<F, LOGN, K, 1>;
+  constexpr int N = C::N;
+  constexpr int G = C::G;
+  constexpr int E = NttShape<LOGN, G>::kE;
+  constexpr int T = NttShape<LOGN, G>::kThreads;
+  auto w = make_wave<F, LOGN, K, 1>(g_smem, tw);
+  const u32 s0 = blockIdx.y * slices_per_run;
+  const u32 s1 = s0 + slices_per_run < slices ? s0 + slices_per_run : slices;
+  const u32* mine = cols + (size_t)blockIdx.x * ((size_t)d + 1) * N;
+  pack_lwe_team<F, LOGN, K, G>(w, P, mine, d, blockIdx.y == 0 ? mine + (size_t)d * N : nullptr, key, s0, s1);
+  u32* dst = glwe_out + ((size_t)blockIdx.x * (K + 1) + w.group()) * N;
+  const int tid = w.tid();
+#pragma unroll
+  for (int r = 0; r < E; ++r) atomicAdd(&dst[r * T + tid], w.acc()[r * T + tid]);
+}
+
+// dst row `row` = GLWE [k+1][N]: coefficient 0 of the body += factor[row] (the packing key's s_i g_l)
+__global__ void packing_add_gadget_kernel(u32* pksk, size_t rows, u32 k, u32 log_n, const u32* __restrict__ factor) {
+  for (size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x; row < rows; row += (size_t)gridDim.x * blockDim.x)
+    pksk[(row * (k + 1) + k) << log_n] += factor[row];
+}
+
 // ------------------------------------------------------------------------------ key switch
 // out[b][c] = -sum_{i<big_n, l<levels} digit_l(lwe[b][i]) * ksk[i*levels + l][c];  out[b][n] += b
 // Tiled as a wrapping-u32 GEMM: a workgroup owns kKsSamples samples x 128 output columns and walks
@@ -1415,6 +1483,36 @@ hipError_t launch_external_product(hipStream_t s, const PbsParams& P, const void
   }
 }
 
+// workgroups a packing launch aims at: the slices of an output are cut into runs until the grid reaches a few teams
+// per team slot of the chip (1,024 at cfg2); more runs mean more partial results to add atomically
+constexpr unsigned kPackTargetWgs = 2048u;
+
+template <class F, int LOGN, int K>
+hipError_t launch_pack_lwe(hipStream_t s, const PbsParams& P, const void* tw_v, const void* key_v, const u32* cols,
+                           u32 d, size_t groups, u32* glwe_out) {
+  if constexpr (!field_shape_ok<F, LOGN>()) {
+    return hipErrorInvalidValue;
+  } else {
+    using C = TeamCfg<F, LOGN, K, 1>;
+    auto tw = static_cast<const typename F::elem*>(tw_v);
+    auto key = static_cast<const typename F::elem*>(key_v);
+    auto kern = pack_lwe_kernel<F, LOGN, K>;
+    static std::atomic<unsigned long long> lds_done{0};
+    hipError_t e = allow_lds(kern, C::kLds, lds_done);
+    if (e != hipSuccess) return e;
+    const u32 slices = (d + K) / (K + 1);
+    size_t runs = kPackTargetWgs / groups;
+    if (runs > slices) runs = slices;
+    if (runs > 65535u) runs = 65535u;
+    if (runs < 1u) runs = 1u;
+    const u32 per_run = (u32)((slices + runs - 1) / runs);
+    runs = (slices + per_run - 1) / per_run;
+    hipLaunchKernelGGL(kern, dim3((unsigned)groups, (unsigned)runs), dim3(C::kThreads), C::kLds, s, P, tw, key, cols, d,
+                       slices, per_run, glwe_out);
+    return hipGetLastError();
+  }
+}
+
 template <class F, int LOGN>
 hipError_t launch_bsk_prepare(hipStream_t s, const void* tw_v, const u32* polys, size_t poly_count,
                               void* spectra_v, u32 k) {
@@ -1610,6 +1708,23 @@ hipError_t external_product(hipStream_t s, int field, const PbsParams& P, const 
   TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k,
                       (launch_external_product<FF, LL, KK>(s, P, tw, ggsw, ggsw_stride_words, glwe_in,
                                                            ct1_inout, cmux_ct0, batch, glwe_out, queue))));
+}
+
+hipError_t pack_transpose(hipStream_t s, const u32* lwe_in, size_t groups, u32 per_group, u32 d, u32 log_n, u32* cols) {
+  const unsigned gz = (unsigned)(groups < 65535u ? groups : 65535u);
+  dim3 grid((d + 1 + kPackTile - 1) / kPackTile, (1u << log_n) / kPackTile, gz);
+  hipLaunchKernelGGL(pack_transpose_kernel, grid, dim3(256), 0, s, lwe_in, groups, per_group, d, log_n, cols);
+  return hipGetLastError();
+}
+
+hipError_t pack_lwe(hipStream_t s, int field, const PbsParams& P, const void* tw, const void* key, const u32* cols, u32 d,
+                    size_t groups, u32* glwe_out) {
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (launch_pack_lwe<FF, LL, KK>(s, P, tw, key, cols, d, groups, glwe_out))));
+}
+
+hipError_t packing_add_gadget(hipStream_t s, u32* pksk, size_t rows, u32 k, u32 log_n, const u32* factor) {
+  hipLaunchKernelGGL(packing_add_gadget_kernel, dim3(grid_for(rows, 256)), dim3(256), 0, s, pksk, rows, k, log_n, factor);
+  return hipGetLastError();
 }
 
 hipError_t key_switch(hipStream_t s, const KsParams& K, u32 big_n, u32 n, const u32* lwe_in,

@@ -84,6 +84,17 @@ hipError_t external_product(hipStream_t s, int field, const PbsParams& P, const 
 hipError_t key_switch(hipStream_t s, const KsParams& K, u32 big_n, u32 n, const u32* lwe_in,
                       size_t batch, const u32* ksk, u32* lwe_out);
 
+// ---- packing key switch (pbs_wave.h::pack_lwe_team): `groups` outputs of up to N LWE ciphertexts of dimension d each
+// cols [groups][d+1][N] = the transposed ciphertexts of lwe_in [groups][per_group][d+1], zero above per_group
+hipError_t pack_transpose(hipStream_t s, const u32* lwe_in, size_t groups, u32 per_group, u32 d, u32 log_n, u32* cols);
+// glwe_out [groups][k+1][N] (ZEROED by the caller, on s) += the packed ciphertexts.  P: log_n, k and the KS decomposer
+// in log_base / levels / ignored_bits / first_shift; key: the packing key prepared by bsk_prepare(.., k, ..) as
+// ceil(d / (k+1)) GGSW-shaped slices of (k+1) l_ks rows (rows past d l_ks zero-filled)
+hipError_t pack_lwe(hipStream_t s, int field, const PbsParams& P, const void* tw, const void* key, const u32* cols, u32 d,
+                    size_t groups, u32* glwe_out);
+// pksk [rows][k+1][N]: body coefficient 0 of row r += factor[r]
+hipError_t packing_add_gadget(hipStream_t s, u32* pksk, size_t rows, u32 k, u32 log_n, const u32* factor);
+
 // elementwise helpers.  first_shift = bit of the lowest kept limb (PbsParams::first_shift)
 hipError_t decompose_words(hipStream_t s, u32 log_base, u32 levels, u32 first_shift, const u32* values,
                            size_t count, u32* digits /* [count][levels] */);

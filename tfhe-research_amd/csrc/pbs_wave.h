@@ -538,6 +538,57 @@ TFHE_HD void external_product_team(const Ctx& c, const PbsParams& P, const typen
 }
 
 // ---------------------------------------------------------------------------------------------
+// Packing key switch (no reference counterpart): m <= N LWE ciphertexts (a_j, b_j) under a binary key s of dimension
+// d become ONE GLWE whose coefficient j decrypts to what ciphertext j decrypts to,
+//   Pack = (0, .., 0, sum_j b_j X^j) - sum_{i<d} sum_{l<l_ks} dec_l(A_i) (*) PK[i l_ks + l],   A_i(X) = sum_j a_j,i X^j,
+// PK[i l_ks + l] a GLWE encryption of the constant s_i g_l (g_l: the KS decomposer's gadget factor).  Read as an external
+// product: the "GLWE" has d polynomials A_i, the "GGSW" d l_ks rows.  A SLICE is K+1 consecutive mask indices
+// i = slice (K+1) + c, c = 0..K -- exactly one external_product_team call with the KS decomposer in P, the transposed
+// mask column A_i as polynomial c and the slice's (K+1) l_ks prepared key rows as the GGSW (rows past d: zero digits
+// against zero-filled key rows).
+//
+// Exactness.  Only the (K+1) l_ks rows of ONE slice are ever summed in the transform domain; every slice is lifted to
+// integers mod 2^32 on its own and the slices meet in wrapping u32 additions.  So the bound of a product is the
+// external product's with R_c = (K+1) l_ks rows and the KS base -- FftField::error_bound(log N, R_c, lb_ks) <
+// FftField::kMaxError (field_fft.h), log2(R_c) + log N + lb_ks + key_bits < exact_bits in the prime fields, and each
+// field's kMaxRows / kSmallBits / kMaxLogBase -- and does not grow with d.  The host admits a packing key only under
+// that bound (capi.cpp::packing_refusal); nothing is computed outside it.
+//
+// The team walks slices [slice_begin, slice_end) and keeps the running (negated) sum of their lifted results in its
+// accumulator polynomials c.acc(): lane-owned words (index j = r T + tid, as out() hands them over), so the sum needs
+// no barrier of its own.  `body` (the b_j in coefficient order, zero above m; null: none) starts polynomial K off.
+//   masks_t  [d][N]: row i = A_i, zero above m (the caller's transpose: the LWE layout would make this a 4-byte gather)
+// ---------------------------------------------------------------------------------------------
+template <class F, int LOGN, int K, int G, class Ctx>
+TFHE_HD void pack_lwe_team(const Ctx& c, const PbsParams& P, const u32* masks_t, u32 d, const u32* body,
+                           const typename F::elem* key /* prepared, slice-major */, u32 slice_begin, u32 slice_end) {
+  constexpr int E = NttShape<LOGN, G>::kE;
+  constexpr int T = NttShape<LOGN, G>::kThreads;
+  constexpr int N = 1 << LOGN;
+  const int lane = c.tid();
+  const int me = c.group();
+  u32* acc = c.acc();
+#pragma unroll
+  for (int r = 0; r < E; ++r) acc[r * T + lane] = (me == K && body != nullptr) ? body[r * T + lane] : 0u;
+  const size_t slice_words = (size_t)(K + 1) * P.levels * (K + 1) * F::kParts * (N >> F::kLogShrink);  // elements
+#pragma unroll 1
+  for (u32 s = slice_begin; s < slice_end; ++s) {
+    const u32 i = c.uniform(s * (u32)(K + 1) + (u32)me);  // wave-uniform: the column's address stays in scalar registers
+    const bool live = i < d;
+    const u32* column = masks_t + (size_t)(live ? i : 0u) * N;
+    auto src = [&](int j) -> u32 { return live ? column[j] : 0u; };
+    auto out = [&](int j, u32 value) { c.lds_add(acc + j, 0u - value); };
+    external_product_team<F, LOGN, K, G>(c, P, key + (size_t)s * slice_words, src, out);
+    // Between two products nothing of mine needs a barrier: the accumulator words are lane-owned and src reads global
+    // memory.  The exchange buffers are the product's own business: with one buffer it ends in a team barrier, with two
+    // in team_sync.  A group of several waves (G > 1) with ONE buffer would still have its inverse transform's
+    // cross-wave transposes in flight when the next forward transform starts: the same barrier blind_rotate_team_multi
+    // places there (no such shape is instantiated today: G > 1 only at N = 2048, which has two buffers)
+    if (G > 1 && c.exchange_buffers() != 2) c.poly_sync();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Blind rotation of NS LWE samples (bootstrapping.rs:67-105 for each) by a team of K+1 groups of G waves.
 // Group c keeps polynomial c of sample s's accumulator in its LDS array c.acc(s) (N u32, natural order)
 // for all n iterations; on return it holds polynomial c of the final GLWE accumulator of sample s.
