@@ -525,6 +525,51 @@ inline GlweCiphertext pack_lwe(Engine& e, const std::vector<LweCiphertext>& cts)
   e.check(tfhe_pack_lwe_batch(e.raw(), in.data(), 1, cts.size(), out.data.data()));
   return out;
 }
+// ---- CMUX tree and encrypted table lookup (tfhe_hip.h states the operations; first device only, like packing) ----
+// GGSW encryptions of the `depth` address bits, least significant first: selector i of cmux_tree / table_lookup
+template <class Rng>
+std::vector<GgswCiphertext> encrypt_address(Engine& e, uint64_t address, size_t depth, const GlweSecretKey& sk, Rng& rng) {
+  if (depth == 0 || depth > 63 || (address >> depth) != 0) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "address below 2^depth, depth 1..63");
+  std::vector<GgswCiphertext> out;
+  for (size_t i = 0; i < depth; ++i) out.push_back(encrypt_ggsw_plaintext(e, (uint32_t)((address >> i) & 1u), sk, rng));
+  return out;
+}
+inline std::vector<uint32_t> flatten_selectors(const TfheParams& p, const std::vector<GgswCiphertext>& selectors) {
+  const size_t words = p.ggsw_rows() * (p.glwe_dimension + 1) * p.degree();
+  std::vector<uint32_t> flat(selectors.size() * words);
+  for (size_t i = 0; i < selectors.size(); ++i) {
+    if (selectors[i].data.size() != words) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "GGSW shape");
+    std::copy(selectors[i].data.begin(), selectors[i].data.end(), flat.begin() + i * words);
+  }
+  return flat;
+}
+// Tree(C_0 .. C_{d-1}; leaves): 2^d leaves, the result is leaf sum_i b_i 2^i where C_i encrypts b_i
+inline GlweCiphertext cmux_tree(Engine& e, const std::vector<GgswCiphertext>& selectors, const std::vector<GlweCiphertext>& leaves) {
+  const TfheParams& p = e.params();
+  const size_t depth = selectors.size(), glwe = (p.glwe_dimension + 1) * p.degree();
+  if (depth == 0 || depth > 20 || leaves.size() != (size_t)1 << depth) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "2^depth leaves, depth 1..20");
+  const std::vector<uint32_t> sel = flatten_selectors(p, selectors);
+  std::vector<uint32_t> in(leaves.size() * glwe);
+  for (size_t i = 0; i < leaves.size(); ++i) {
+    if (leaves[i].data.size() != glwe) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "GLWE shape");
+    std::copy(leaves[i].data.begin(), leaves[i].data.end(), in.begin() + i * glwe);
+  }
+  GlweCiphertext out{std::vector<uint32_t>(glwe)};
+  e.check(tfhe_cmux_tree(e.raw(), sel.data(), 1, depth, in.data(), 1, 1, out.data.data()));
+  return out;
+}
+// table[address] of a clear table of 2^depth un-encoded values < 2^log_p -> LWE of k N + 1 words under the flattened
+// GLWE key (key_switch_lwe brings it to dimension n)
+inline LweCiphertext table_lookup(Engine& e, const std::vector<GgswCiphertext>& selectors, const std::vector<uint32_t>& table) {
+  const TfheParams& p = e.params();
+  const size_t depth = selectors.size();
+  if (depth == 0 || depth > p.glwe_poly_degree + 20 || table.size() != (size_t)1 << depth)
+    throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "2^depth table entries, depth 1..log2 N + 20");
+  const std::vector<uint32_t> sel = flatten_selectors(p, selectors);
+  LweCiphertext out{std::vector<uint32_t>(p.glwe_dimension * p.degree() + 1)};
+  e.check(tfhe_table_lookup(e.raw(), sel.data(), 1, depth, table.data(), 1, 1, out.data.data()));
+  return out;
+}
 // bootstrapping_key_gen bootstrapping.rs:23-56; the generated key is also installed in the engine.
 // bmmp = true makes the key of the unrolled blind rotation instead (notes/BMMP Bootstrapping.md:22-24:
 // GGSW(s s'), GGSW(s (1-s')), GGSW(s' (1-s)) per pair of key bits; N = 512, even n).

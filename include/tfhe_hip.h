@@ -228,6 +228,71 @@ int tfhe_external_product_prepared_device(tfhe_context *ctx, const void *ggsw_pr
 /* cmux(): ggsw.rs:164-178.  Like the reference, ct1 is CLOBBERED with ct1 - ct0. */
 int tfhe_cmux_batch(tfhe_context *ctx, const uint32_t *ggsw, size_t ggsw_count,
                     const uint32_t *ct0, uint32_t *ct1, size_t batch, uint32_t *glwe_out);
+/* The same CMUX on the device with GGSW(s) prepared by tfhe_prepare_ggsw_device (ggsw_count = 1 or batch):
+ * glwe_out[b] = ct0[b] + external_product(ggsw, ct1[b] - ct0[b]).  NOTHING is clobbered; glwe_out may not alias the
+ * inputs.  Ordered on the context's stream, allocates nothing: safe under stream capture.  (It is a tree of one level
+ * per sample in the tree kernel, one workgroup per sample: the CMUX path of the external-product kernel writes
+ * ct1 - ct0 back, as the reference does, and is left as it is.) */
+int tfhe_cmux_prepared_device(tfhe_context *ctx, const void *ggsw_prepared, size_t ggsw_count, const uint32_t *ct0,
+                              const uint32_t *ct1, size_t batch, uint32_t *glwe_out);
+
+/* ---- CMUX tree and encrypted table lookup (no reference counterpart; the reference stops at one cmux()) ----------
+ * All arithmetic mod 2^32; ext = external_product (ggsw.rs:132-161) with the PBS decomposer in the context's alignment
+ * mode; cmux(C, d0, d1) = d0 + ext(C, d1 - d0).
+ *   Tree(C_0 .. C_{d-1}; L_0 .. L_{2^d - 1}):  L(0) = L,  L(i+1)_j = cmux(C_i, L(i)_{2j}, L(i)_{2j+1}),  result L(d)_0.
+ *     With C_i a GGSW encryption of the bit b_i the tree selects leaf a = sum_i b_i 2^i: selector 0 is the least
+ *     significant address bit and pairs neighbouring leaves.
+ *   Lookup(C_0 .. C_{D-1}; T[0 .. 2^D)), T un-encoded values < 2^log_p, d_lo = min(D, log2 N), d_hi = D - d_lo:
+ *     leaf h < 2^d_hi is the trivial GLWE (zero masks) whose body coefficient j is
+ *     T[h 2^d_lo + j] << (32 - log_p - padding_bits) for j < 2^d_lo and 0 above;
+ *     root = Tree(C_{d_lo} .. C_{D-1}; leaves) (leaf 0 if d_hi = 0);
+ *     for i = 0 .. d_lo - 1 in this order: root = cmux(C_i, root, X^{-2^i} root)  (monomial index 2N - 2^i);
+ *     out = sample_extract(root, 0): k N + 1 words under the flattened GLWE key, phase encode(T[a]) + noise.  The
+ *     result feeds tfhe_key_switch_batch_device / tfhe_bootstrap_batch_device (KS-first order) unchanged.
+ * No bootstrapping key is involved (nothing here returns TFHE_ERR_NO_KEY) and no new exactness rule applies: every
+ * product has the (k+1) l rows and the base the context was admitted with.  A lookup is (2^d_hi - 1) + d_lo products.
+ *
+ * Noise: the selectors' errors and the decomposer's rounding add per product, so the error grows with D, not 2^D:
+ *   sigma^2 <= D * [ (k+1) l N (B^2/12 + 1/6) (sigma_glwe 2^32)^2 + (1 + k N / 2) 2^(2 ignored_bits) / 12 ]
+ * in units of the 32-bit torus, on top of the selected leaf's own noise (none for a clear table).
+ *
+ * Layouts.  selectors_prepared [queries][depth] prepared GGSWs (tfhe_prepare_ggsw_device over the raw
+ * [queries][depth][(k+1) l][k+1][N]; selector i of a query is its address bit i).  Query q reads leaf set q, or the
+ * one shared set (leaf_sets / table_sets = 1 or queries), once per table:
+ *   leaves [leaf_sets][tables][2^depth][k+1][N]  ->  glwe_out [queries][tables][k+1][N]
+ *   table  [table_sets][tables][2^depth] u32     ->  lwe_out  [queries][tables][k N + 1]
+ * Values >= 2^log_p in a table are the caller's business (as with test vectors on the device).  Outputs may not alias
+ * inputs.  Tree depth 1 .. 20, lookup depth 1 .. log2 N + 20.
+ *
+ * The _device forms run on the context's stream in a workspace sized by tfhe_context_reserve_lookup(max_trees,
+ * max_tree_depth, max_lookup_bits) -- trees = queries * tables -- so that they never allocate or synchronise (safe under
+ * stream capture; no second stream is used).  The reservation is a maximum: it covers every tfhe_cmux_tree_device call
+ * of at most max_tree_depth levels and every tfhe_table_lookup_device call of at most max_lookup_bits address bits
+ * (either may be 0: no such calls) over at most max_trees trees, under any subtree height, set before or after it.
+ * It takes at most 3/4 * max_trees * 2^d * (k+1) * N * 4 bytes, d = max(max_tree_depth, max_lookup_bits - log2 N):
+ * a lookup is sized by its OWN tree, so 1,024 lookups of 16 bits at N = 1024, k = 1 (d = 6) reserve 384 MiB, and
+ * lookups of at most log2 N bits reserve nothing to speak of.  A call beyond the reservation returns
+ * TFHE_ERR_INVALID_ARGUMENT with the reason.  The host forms take raw GGSWs and host arrays, upload, prepare the
+ * selectors once, reserve for themselves and block.
+ *
+ * A call is ceil(d / h) launches, d the tree depth (d_hi for a lookup; one launch if d_hi = 0) and h the subtree
+ * height one workgroup reduces.  The automatic h (the default) depends on d and on trees = queries * tables -- many
+ * trees fill the chip with deep subtrees in one launch, a single tree goes out in short passes -- so the launches of
+ * a call depend on its depth and its number of trees, but there is never a loop of launches over queries.
+ * tfhe_context_set_lookup_subtree_height(h) fixes h (0: automatic again), and with it the launches whatever the
+ * number of trees; the bits do not depend on it.  tfhe_debug_lookup_plan reports the height and the launches of a
+ * tree of `depth` levels over `trees` trees (depth 0: a lookup without tree levels). */
+int tfhe_context_reserve_lookup(tfhe_context *ctx, size_t max_trees, size_t max_tree_depth, size_t max_lookup_bits);
+int tfhe_context_set_lookup_subtree_height(tfhe_context *ctx, unsigned height);
+int tfhe_debug_lookup_plan(tfhe_context *ctx, size_t trees, size_t depth, unsigned *subtree_height, unsigned *launches);
+int tfhe_cmux_tree_device(tfhe_context *ctx, const void *selectors_prepared, size_t queries, size_t depth,
+                          const uint32_t *leaves, size_t leaf_sets, size_t tables, uint32_t *glwe_out);
+int tfhe_cmux_tree(tfhe_context *ctx, const uint32_t *selectors, size_t queries, size_t depth, const uint32_t *leaves,
+                   size_t leaf_sets, size_t tables, uint32_t *glwe_out);
+int tfhe_table_lookup_device(tfhe_context *ctx, const void *selectors_prepared, size_t queries, size_t depth,
+                             const uint32_t *table, size_t table_sets, size_t tables, uint32_t *lwe_out);
+int tfhe_table_lookup(tfhe_context *ctx, const uint32_t *selectors, size_t queries, size_t depth, const uint32_t *table,
+                      size_t table_sets, size_t tables, uint32_t *lwe_out);
 
 /* ---- decomposer.rs / glwe.rs / utils.rs --------------------------------------------------- */
 /* SignedDecomposer::decompose: decomposer.rs:42-80.  digits_out [count][levels], MSB first. */

@@ -56,6 +56,11 @@ extern "C" {
     fn tfhe_packing_key_dimension(ctx: *const TfheContext, from_dimension: *mut usize) -> c_int;
     fn tfhe_pack_lwe_batch(ctx: *mut TfheContext, lwe_in: *const u32, groups: usize, per_group: usize,
                            glwe_out: *mut u32) -> c_int;
+    // CMUX tree / encrypted table lookup (include/tfhe_hip.h)
+    fn tfhe_cmux_tree(ctx: *mut TfheContext, selectors: *const u32, queries: usize, depth: usize, leaves: *const u32,
+                      leaf_sets: usize, tables: usize, glwe_out: *mut u32) -> c_int;
+    fn tfhe_table_lookup(ctx: *mut TfheContext, selectors: *const u32, queries: usize, depth: usize, table: *const u32,
+                         table_sets: usize, tables: usize, lwe_out: *mut u32) -> c_int;
     fn tfhe_cmux_batch(ctx: *mut TfheContext, ggsw: *const u32, ggsw_count: usize, ct0: *const u32,
                        ct1: *mut u32, batch: usize, glwe_out: *mut u32) -> c_int;
     fn tfhe_gate_batch(ctx: *mut TfheContext, truth: *const u32, ct0: *const u32, ct1: *const u32,
@@ -212,6 +217,42 @@ pub fn pack_lwe(bk: &GpuBootstrappingKey, lwe: &Array2<u32>) -> Array2<u32> {
     check(bk.ctx, unsafe {
         tfhe_pack_lwe_batch(bk.ctx, lwe.as_slice().unwrap().as_ptr(), 1, lwe.nrows(), out.as_slice_mut().unwrap().as_mut_ptr())
     }, "pack_lwe");
+    out
+}
+
+/// Tree over `selectors` (depth, (k+1)l, k+1, N) flattened to Array2 rows -- selector i is address bit i -- and 2^depth
+/// leaves (2^depth, k+1, N): the GLWE (k+1, N) of leaf sum_i b_i 2^i (no reference counterpart).
+pub fn cmux_tree(bk: &GpuBootstrappingKey, selectors: &Array2<u32>, leaves: &Array3<u32>) -> Array2<u32> {
+    let n = 1usize << bk.params.glwe_poly_degree;
+    let k1 = bk.params.glwe_dimension as usize + 1;
+    let depth = selectors.nrows();
+    let ggsw = k1 * bk.params.pbs_decomposer.levels as usize * k1 * n;
+    // the ABI reads depth GGSWs and 2^depth GLWEs
+    assert!(depth >= 1 && depth <= 20 && selectors.ncols() == ggsw, "cmux_tree: depth rows of (k+1) l (k+1) N words, depth 1..=20");
+    assert!(leaves.dim() == (1usize << depth, k1, n), "cmux_tree: 2^depth leaves of (k+1, N)");
+    let mut out = Array2::<u32>::zeros((k1, n));
+    check(bk.ctx, unsafe {
+        tfhe_cmux_tree(bk.ctx, selectors.as_slice().unwrap().as_ptr(), 1, depth, leaves.as_slice().unwrap().as_ptr(), 1, 1,
+                       out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "cmux_tree");
+    out
+}
+
+/// table[address] for a clear table of 2^depth un-encoded values below 2^log_p and the address bits GGSW-encrypted in
+/// `selectors` (as for cmux_tree): an LWE of k N + 1 words under the flattened GLWE key.
+pub fn table_lookup(bk: &GpuBootstrappingKey, selectors: &Array2<u32>, table: &Array1<u32>) -> Array1<u32> {
+    let n = 1usize << bk.params.glwe_poly_degree;
+    let k = bk.params.glwe_dimension as usize;
+    let depth = selectors.nrows();
+    let ggsw = (k + 1) * bk.params.pbs_decomposer.levels as usize * (k + 1) * n;
+    assert!(depth >= 1 && depth <= bk.params.glwe_poly_degree as usize + 20 && selectors.ncols() == ggsw,
+            "table_lookup: depth rows of (k+1) l (k+1) N words, depth 1..=log2 N + 20");
+    assert!(table.len() == 1usize << depth, "table_lookup: 2^depth entries");
+    let mut out = Array1::<u32>::zeros(k * n + 1);
+    check(bk.ctx, unsafe {
+        tfhe_table_lookup(bk.ctx, selectors.as_slice().unwrap().as_ptr(), 1, depth, table.as_slice().unwrap().as_ptr(), 1, 1,
+                          out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "table_lookup");
     out
 }
 

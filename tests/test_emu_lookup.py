@@ -1,0 +1,130 @@
+"""The device source of the CMUX tree / table lookup (csrc/pbs_wave.h::cmux_tree_team) through the host SIMT emulator
+(tests/emu/emu_lookup.cpp, its own shared object), every output word against the clear model
+(tests/clear_model_lookup.py): arbitrary GGSWs and leaves, one pass and two passes, lookups with and without tree levels."""
+import ctypes as C
+import functools
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+sys.path.insert(0, HERE)
+import clear_model as cm  # noqa: E402
+import clear_model_lookup as cl  # noqa: E402
+
+EMU_DIR = os.path.join(HERE, "emu")
+CSRC = os.path.join(ROOT, "tfhe-research_amd", "csrc")
+GL, FFT = 1, 5
+
+# field, log2 N (k = 1, one wave per polynomial): the shapes emu_lookup.cpp instantiates
+SHAPES = [(FFT, 9), (GL, 9), (FFT, 10)]
+# log_base, levels, aligned
+DECOMPOSERS = [(7, 3, False), (7, 3, True), (4, 6, False)]
+
+
+def p32(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def p64(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+@pytest.fixture(scope="module")
+def emu_lookup():
+    so = os.path.join(EMU_DIR, "libtfhe_emu_lookup.so")
+    srcs = [os.path.join(EMU_DIR, f) for f in ("emu_lookup.cpp", "emu.cpp")] + \
+           [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-I", CSRC,
+                        "-o", so + ".tmp", os.path.join(EMU_DIR, "emu_lookup.cpp")], check=True)
+        os.replace(so + ".tmp", so)
+    return C.CDLL(so)
+
+
+def prepared(emu, field, k, logn, ggsws):
+    flat = np.ascontiguousarray(ggsws, dtype=np.uint32).reshape(-1, 1 << logn)
+    out = np.zeros((flat.shape[0], emu.emu_field_parts(field), 1 << logn), dtype=np.uint64)
+    emu.emu_set_key_k(k)  # the key's layout depends on (field, N, k): pbs_wave.h::key_layout_e
+    try:
+        assert emu.emu_bsk_prepare(field, logn, 1, C.c_size_t(flat.shape[0]), p32(flat), p64(out)) == 0
+    finally:
+        emu.emu_set_key_k(0)
+    return out
+
+
+def operands(logn, levels, queries, depth, shape, seed):
+    """arbitrary selectors [queries][depth][R][2][N] and data of `shape`, random with clear_model.edge_words() mixed in"""
+    rng = np.random.default_rng(seed)
+    N = 1 << logn
+    sel = rng.integers(0, 1 << 32, size=(queries, depth, 2 * levels, 2, N), dtype=np.uint64).astype(np.uint32)
+    edge = cm.edge_words()
+    sel[0, 0, 0, 0, :] = edge[:N]
+    sel[-1, -1, -1, 1, :] = edge[N:2 * N]
+    data = rng.integers(0, 1 << 32, size=shape, dtype=np.uint64).astype(np.uint32)
+    flat = data.reshape(-1)
+    take = min(flat.size // 2, edge.size)
+    flat[:take] = edge[:take]
+    return sel, data
+
+
+@functools.lru_cache(maxsize=None)
+def tree_case(logn, lb, levels, aligned):
+    """depth 3, two queries with their own selectors, one shared leaf set, two tables -> (selectors, leaves, model)"""
+    N = 1 << logn
+    sel, leaves = operands(logn, levels, 2, 3, (1, 2, 8, 2, N), seed=logn * 100 + lb)
+    want = np.stack([cl.tree_model(sel[q], leaves[0], lb, levels, aligned) for q in range(2)])
+    return sel, leaves, want
+
+
+@functools.lru_cache(maxsize=None)
+def lookup_case(logn, lb, levels, aligned, D):
+    """two queries, per-query table sets, one table each -> (selectors, tables, model)"""
+    rng = np.random.default_rng(logn * 1000 + lb * 10 + D)
+    sel, _ = operands(logn, levels, 2, D, (1,), seed=logn * 200 + lb + D)
+    log_p = 4
+    table = rng.integers(0, 1 << log_p, size=(2, 1, 1 << D)).astype(np.uint32)
+    want = np.stack([cl.lookup_model(sel[q], table[q], 1, 1 << logn, log_p, lb, levels, aligned) for q in range(2)])
+    return sel, table, log_p, want
+
+
+@pytest.mark.parametrize("lb,levels,aligned", DECOMPOSERS)
+@pytest.mark.parametrize("field,logn", SHAPES)
+@pytest.mark.parametrize("height", [0, 2])
+def test_tree_matches_the_model(emu_lookup, field, logn, lb, levels, aligned, height):
+    """depth 3 in one subtree (height 0: the whole tree) and as two passes (heights 2 + 1 through the result buffers)"""
+    sel, leaves, want = tree_case(logn, lb, levels, aligned)
+    spec = prepared(emu_lookup, field, 1, logn, sel)
+    out = np.zeros((2, 2, 2, 1 << logn), dtype=np.uint32)
+    emu_lookup.emu_set_aligned(int(aligned))
+    try:
+        rc = emu_lookup.emu_lookup(field, 1, 1, logn, 4, 1, lb, levels, p64(spec), C.c_size_t(2), 3, 0, 3, height, p32(leaves), None,
+                                   1, 2, p32(out), None)
+    finally:
+        emu_lookup.emu_set_aligned(0)
+    assert rc == 0
+    assert np.array_equal(out, want)
+
+
+@pytest.mark.parametrize("lb,levels,aligned", DECOMPOSERS)
+@pytest.mark.parametrize("field,logn", SHAPES)
+@pytest.mark.parametrize("extra", [2, None])
+def test_lookup_matches_the_model(emu_lookup, field, logn, lb, levels, aligned, extra):
+    """D = log2 N + 2 (d_lo = log2 N, a tree of two levels, the full rotation chain) and D = 3 < log2 N (no tree)"""
+    D = 3 if extra is None else logn + extra
+    d_lo = min(D, logn)
+    sel, table, log_p, want = lookup_case(logn, lb, levels, aligned, D)
+    spec = prepared(emu_lookup, field, 1, logn, sel)
+    out = np.zeros((2, 1, (1 << logn) + 1), dtype=np.uint32)
+    emu_lookup.emu_set_aligned(int(aligned))
+    try:
+        rc = emu_lookup.emu_lookup(field, 1, 1, logn, log_p, 1, lb, levels, p64(spec), C.c_size_t(2), D, d_lo, D - d_lo, 0, None,
+                                   p32(table), 0, 1, None, p32(out))
+    finally:
+        emu_lookup.emu_set_aligned(0)
+    assert rc == 0
+    assert np.array_equal(out, want)

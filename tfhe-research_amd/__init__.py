@@ -671,6 +671,128 @@ class Context:
                                           C.c_size_t(c0.shape[0]), _hp(res)))
         return res, c1
 
+    # -- CMUX tree / encrypted table lookup (include/tfhe_hip.h states the operations) ---------------------------
+    def cmux_prepared(self, ggsw_prepared, ct0, ct1, out=None):
+        """ct0 + external_product(ggsw, ct1 - ct0) on the device with prepared GGSW(s) [1 or batch][words] (int64);
+        ct0 / ct1 [batch][k+1][N] device tensors, left intact."""
+        self._bind_torch()
+        p = self.params
+        if tuple(ct0.shape) != tuple(ct1.shape) or ct0.dim() != 3 or tuple(ct0.shape[1:]) != (p.k + 1, p.N):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"cmux_prepared: ct0 / ct1 [batch][k+1][N] expected, got "
+                                                       f"{tuple(ct0.shape)} and {tuple(ct1.shape)}")
+        self._check_prepared(ggsw_prepared, (1, ct0.shape[0]), "cmux_prepared")
+        out = self._lookup_out("cmux_prepared", out, tuple(ct0.shape), ct0)
+        self._check(lib().tfhe_cmux_prepared_device(self._h, C.c_void_p(ggsw_prepared.data_ptr()),
+                                                    C.c_size_t(ggsw_prepared.shape[0]), _dp(ct0), _dp(ct1),
+                                                    C.c_size_t(ct0.shape[0]), _dp(out)))
+        return out
+
+    def _check_prepared(self, prepared, counts, what: str):
+        """the ABI reads prepared_ggsw_words() 8-byte words per GGSW: a wrong shape would be read out of bounds"""
+        if (not _is_torch(prepared) or prepared.dim() != 2 or prepared.element_size() != 8 or not prepared.is_contiguous()
+                or prepared.shape[0] not in counts or prepared.shape[1] != self.prepared_ggsw_words()):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT,
+                            f"{what}: prepared GGSWs [{' or '.join(str(c) for c in counts)}][{self.prepared_ggsw_words()}] "
+                            f"of 8-byte words expected (prepare_ggsw_device)")
+
+    def reserve_lookup(self, max_trees: int, max_tree_depth: int = 0, max_lookup_bits: int = 0):
+        """size the workspace of the device forms for cmux_tree calls of up to max_tree_depth levels and table_lookup
+        calls of up to max_lookup_bits address bits over up to max_trees = queries * tables trees (a maximum: smaller
+        calls fit, under any subtree height); include/tfhe_hip.h states the bytes"""
+        self._check(lib().tfhe_context_reserve_lookup(self._h, C.c_size_t(max_trees), C.c_size_t(max_tree_depth),
+                                                      C.c_size_t(max_lookup_bits)))
+
+    def set_lookup_subtree_height(self, height: int):
+        """tree levels one workgroup reduces (0: automatic); the bits do not depend on it"""
+        self._check(lib().tfhe_context_set_lookup_subtree_height(self._h, C.c_uint(height)))
+
+    def lookup_plan(self, trees: int, depth: int) -> dict:
+        """how a tree of `depth` levels over `trees` trees goes out (tfhe_debug_lookup_plan)"""
+        height, launches = C.c_uint(), C.c_uint()
+        self._check(lib().tfhe_debug_lookup_plan(self._h, C.c_size_t(trees), C.c_size_t(depth), C.byref(height),
+                                                 C.byref(launches)))
+        return {"subtree_height": height.value, "launches": launches.value}
+
+    def _lookup_shapes(self, what, selectors, data, entry_shape):
+        """-> (queries, depth, sets, tables) after checking selectors [queries][depth][..] against data
+        [sets][tables][2^depth] + entry_shape"""
+        p = self.params
+        if _is_torch(selectors):
+            if selectors.dim() != 3 or selectors.element_size() != 8 or selectors.shape[2] != self.prepared_ggsw_words() \
+                    or not selectors.is_contiguous() or not selectors.is_cuda:
+                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: prepared selectors [queries][depth]"
+                                                           f"[{self.prepared_ggsw_words()}] (contiguous int64, on the device) expected")
+            # the ABI reads 4-byte words: an int64 table of the right shape would be read as pairs of words
+            if data.element_size() != 4 or data.is_floating_point() or not data.is_contiguous() or data.device != selectors.device:
+                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: data must be a contiguous 32-bit integer tensor on the "
+                                                           f"selectors' device, got {data.dtype} on {data.device}")
+        elif selectors.ndim != 5 or tuple(selectors.shape[2:]) != (p.R, p.k + 1, p.N):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: raw selectors [queries][depth][R][k+1][N] expected, got "
+                                                       f"{tuple(selectors.shape)}")
+        queries, depth = int(selectors.shape[0]), int(selectors.shape[1])
+        nd = 3 + len(entry_shape)
+        if len(data.shape) != nd or int(data.shape[0]) not in (1, queries) or depth >= 40 \
+                or int(data.shape[2]) != 1 << depth or tuple(data.shape[3:]) != tuple(entry_shape):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT,
+                            f"{what}: data [1 or {queries}][tables][2^{depth}]{list(entry_shape)} expected, got {tuple(data.shape)}")
+        return queries, depth, int(data.shape[0]), int(data.shape[1])
+
+    def _lookup_out(self, what, out, shape, like):
+        """the caller's output tensor, or a new one: the ABI writes prod(shape) 4-byte words"""
+        import torch
+        if out is None:
+            return torch.empty(shape, dtype=like.dtype, device=like.device)
+        if not _is_torch(out) or tuple(out.shape) != tuple(shape) or out.element_size() != 4 or out.is_floating_point() \
+                or not out.is_contiguous() or out.device != like.device:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: out must be a contiguous 32-bit integer tensor {list(shape)} "
+                                                       f"on {like.device}")
+        return out
+
+    def cmux_tree(self, selectors, leaves, out=None):
+        """Tree(C_0 .. C_{d-1}; leaves): selector i is address bit i and the result is leaf sum_i b_i 2^i.
+        numpy: raw selectors [queries][depth][R][k+1][N] and leaves [1 or queries][tables][2^depth][k+1][N] (host
+        form, blocks).  torch: prepared selectors [queries][depth][words] (prepare_ggsw_device) and device leaves, in
+        the workspace of reserve_lookup.  -> [queries][tables][k+1][N]"""
+        p = self.params
+        if _is_torch(selectors) != _is_torch(leaves):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "cmux_tree: selectors and leaves must both be numpy or both torch")
+        if not _is_torch(selectors):
+            selectors, leaves = _np(selectors), _np(leaves)
+        queries, depth, sets, tables = self._lookup_shapes("cmux_tree", selectors, leaves, (p.k + 1, p.N))
+        if _is_torch(selectors):
+            self._bind_torch()
+            out = self._lookup_out("cmux_tree", out, (queries, tables, p.k + 1, p.N), leaves)
+            self._check(lib().tfhe_cmux_tree_device(self._h, C.c_void_p(selectors.data_ptr()), C.c_size_t(queries),
+                                                    C.c_size_t(depth), _dp(leaves), C.c_size_t(sets), C.c_size_t(tables),
+                                                    _dp(out)))
+            return out
+        res = np.zeros((queries, tables, p.k + 1, p.N), dtype=np.uint32)
+        self._check(lib().tfhe_cmux_tree(self._h, _hp(selectors), C.c_size_t(queries), C.c_size_t(depth), _hp(leaves),
+                                         C.c_size_t(sets), C.c_size_t(tables), _hp(res)))
+        return res
+
+    def table_lookup(self, selectors, table, out=None):
+        """Encrypted lookup of T[address] in clear tables [1 or queries][tables][2^depth] of un-encoded values
+        < 2^log_p; selectors as for cmux_tree (address bit i = selector i).  -> LWE [queries][tables][k N + 1] under
+        the flattened GLWE key, phase encode(T[a]) + noise (key_switch brings it to dimension n)."""
+        p = self.params
+        if _is_torch(selectors) != _is_torch(table):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "table_lookup: selectors and table must both be numpy or both torch")
+        if not _is_torch(selectors):
+            selectors, table = _np(selectors), _np(table)
+        queries, depth, sets, tables = self._lookup_shapes("table_lookup", selectors, table, ())
+        if _is_torch(selectors):
+            self._bind_torch()
+            out = self._lookup_out("table_lookup", out, (queries, tables, p.big_n + 1), table)
+            self._check(lib().tfhe_table_lookup_device(self._h, C.c_void_p(selectors.data_ptr()), C.c_size_t(queries),
+                                                       C.c_size_t(depth), _dp(table), C.c_size_t(sets), C.c_size_t(tables),
+                                                       _dp(out)))
+            return out
+        res = np.zeros((queries, tables, p.big_n + 1), dtype=np.uint32)
+        self._check(lib().tfhe_table_lookup(self._h, _hp(selectors), C.c_size_t(queries), C.c_size_t(depth), _hp(table),
+                                            C.c_size_t(sets), C.c_size_t(tables), _hp(res)))
+        return res
+
     # -- small ops ------------------------------------------------------------------------------
     def decompose(self, values, which: int = DECOMPOSER_PBS) -> np.ndarray:
         v = _np(values).ravel()
@@ -950,6 +1072,21 @@ class Context:
         if load:
             self.load_packing_key(pksk)
         return pksk
+
+    def encrypt_address(self, glwe_sk, addresses, depth: int, rng=None) -> np.ndarray:
+        """GGSW encryptions of the `depth` bits of every address (bit i -> selector i) under glwe_sk with glwe_std_dev
+        -> raw selectors [queries][depth][R][k+1][N] for cmux_tree / table_lookup.  Masks and errors come from the OS
+        CSPRNG unless the test hook `rng=` is given (see generate_keys)."""
+        p = self.params
+        rng = rng if rng is not None else SystemRng()
+        addr = np.asarray(addresses, dtype=np.uint64).reshape(-1)
+        if depth < 1 or depth > 63 or (addr.size and int(addr.max()) >> depth):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "encrypt_address: addresses must be below 2^depth, depth in [1, 63]")
+        bits = ((addr[:, None] >> np.arange(depth, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.uint32).reshape(-1)
+        shape = (bits.size, p.R, p.k + 1, p.N)
+        samples = rng.integers(0, 1 << 32, size=shape, dtype=np.uint64).astype(np.uint32)
+        samples[:, :, p.k, :] = self._noise(rng, p.glwe_std_dev, (shape[0], p.R, p.N))
+        return self.ggsw_encrypt(glwe_sk, bits, samples).reshape(addr.size, depth, p.R, p.k + 1, p.N)
 
     def encrypt_bits(self, lwe_sk, messages, rng=None) -> np.ndarray:
         """LweCleartext::encode_message + encrypt_lwe_plaintext (lwe.rs:81-92,138-160) for a batch

@@ -472,7 +472,7 @@ void tfhe_context_destroy(tfhe_context* ctx) {
   void* ptrs[] = {ctx->d_queue,  ctx->d_tw,     ctx->d_bsk,    ctx->d_ksk,    ctx->d_lwe_in, ctx->d_lwe_in2,
                   ctx->d_lwe_big, ctx->d_lwe_out, ctx->d_lwe_ks, ctx->d_glwe_a, ctx->d_glwe_b, ctx->d_glwe_c,
                   ctx->d_tv,     ctx->d_misc,   ctx->d_ggsw_tmp, ctx->d_ggsw_raw,
-                  ctx->d_key_tmp, ctx->d_pksk, ctx->d_pack_cols};
+                  ctx->d_key_tmp, ctx->d_pksk, ctx->d_pack_cols, ctx->d_lookup_ws};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& g : ctx->gate_tvs)
@@ -953,6 +953,242 @@ int tfhe_cmux_batch(tfhe_context* ctx, const uint32_t* ggsw, size_t ggsw_count, 
   HIP_TRY(ctx, hipMemcpyAsync(ct1, ctx->d_glwe_b, batch * glwe * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return TFHE_OK;
+}
+
+// ---------------------------------------------------------------------------------- CMUX tree / table lookup
+// include/tfhe_hip.h states the operations, pbs_wave.h::cmux_tree_team the walk, kernels.hip::lookup_plan_for the plan.
+namespace {
+
+constexpr size_t kMaxTreeDepth = 20;
+
+int lookup_plan_of(tfhe_context* ctx, size_t trees, size_t depth, launch::LookupPlanInfo* plan) {
+  hipError_t e = launch::lookup_plan(ctx->field, ctx->pbs, trees, (u32)depth, ctx->lookup_height, plan);
+  if (e == hipErrorInvalidValue)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "trees * 2^(depth - subtree height) exceeds the 2^31 - 1 teams of one launch");
+  if (e != hipSuccess) return hip_fail(ctx, e, "lookup plan");
+  return TFHE_OK;
+}
+
+// Words that cover EVERY call of at most `trees` trees and tree depths up to `depth`, whatever the subtree height is
+// set to then: the need under a given height is proportional to the number of trees (launch::lookup_workspace_glwes)
+// and the automatic rule picks one of the heights 1 .. d -- so the largest need over all heights at `trees` bounds them
+// all (at most 3/4 trees 2^depth GLWEs: height 1).  (The automatic height itself is NOT monotone in the number of
+// trees: sampling tree counts would miss some.)  Heights whose first pass would not fit a grid are skipped: such a call
+// is refused.  Host arithmetic only.
+size_t lookup_workspace_need(const tfhe_context* ctx, size_t trees, size_t depth) {
+  size_t glwes = 0;
+  for (size_t d = 1; d <= depth; ++d)
+    for (u32 h = 1; h <= d; ++h) {
+      size_t n = 0;
+      if (launch::lookup_workspace_glwes(trees, (u32)d, h, &n)) glwes = std::max(glwes, n);
+    }
+  return std::max<size_t>(1, glwes * (ctx->params.glwe_dimension + 1) * ctx->N);
+}
+
+int grow_lookup_workspace(tfhe_context* ctx, size_t words) {
+  if (words <= ctx->lookup_ws_words) return TFHE_OK;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return ensure(ctx, &ctx->d_lookup_ws, &ctx->lookup_ws_words, words);
+}
+
+// What a tree / lookup call reads its leaves from: GLWEs [sets][tables][2^depth][k+1][N] or a clear table
+// [sets][tables][2^address_bits]
+struct LookupLeaves {
+  const u32* glwe;
+  const u32* table;
+  bool shared;  // one set for all queries
+};
+
+// `tree_depth` tree levels with selectors [first, first + tree_depth) of every query's `address_bits` selectors, then
+// (lwe_out only) min(address_bits, log2 N) rotation steps with selectors [0, first) and the sample extraction
+int run_lookup(tfhe_context* ctx, const void* selectors, size_t queries, size_t address_bits, size_t first, size_t tree_depth,
+               const LookupLeaves& leaves, size_t tables, u32* glwe_out, u32* lwe_out) {
+  const size_t trees = queries * tables;
+  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
+  launch::LookupPlanInfo plan{};
+  int st = lookup_plan_of(ctx, trees, tree_depth, &plan);
+  if (st) return st;
+  if (plan.workspace_words > ctx->lookup_ws_words)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "the call needs " + std::to_string(plan.workspace_words) + " words of lookup workspace, " +
+                    std::to_string(ctx->lookup_ws_words) + " are reserved (tfhe_context_reserve_lookup)");
+  const size_t ggsw8 = ggsw_words(ctx) * ctx->parts;  // 8-byte words of one prepared GGSW
+  const unsigned char* sel = static_cast<const unsigned char*>(selectors);
+  // workspace: [results of passes 0, 2, ..][results of passes 1, 3, ..][pending slots]
+  const size_t h = plan.height;
+  const size_t res_a = plan.launches >= 2 ? (trees << (tree_depth - h)) * glwe : 0;
+  const size_t res_b = plan.launches >= 3 ? (trees << (tree_depth - 2 * h)) * glwe : 0;
+  u32* results[2] = {ctx->d_lookup_ws, ctx->d_lookup_ws + res_a};
+  u32* pending = ctx->d_lookup_ws + res_a + res_b;
+  size_t done = 0;
+  const u32* from = nullptr;  // the previous pass's results
+  for (u32 i = 0; i < plan.launches; ++i) {
+    const size_t here = std::min(h, tree_depth - done);  // 0 only for tree_depth == 0
+    const bool last = i + 1 == plan.launches;
+    CmuxTreePass pass{};
+    pass.selectors = sel + (first + done) * ggsw8 * 8;
+    pass.rot_selectors = sel;
+    pass.query_stride = address_bits * ggsw8;
+    pass.tables = (u32)tables;
+    pass.height = (u32)here;
+    pass.log_subtrees = (u32)(tree_depth - done - here);
+    const size_t leaves_per_tree = (size_t)1 << (tree_depth - done);
+    if (i == 0 && leaves.table) {
+      pass.shared_sets = leaves.shared;
+      pass.table = leaves.table;
+      pass.table_stride = (size_t)1 << address_bits;
+      pass.log_entries = (u32)first;
+    } else {
+      const u32* base = i == 0 ? leaves.glwe : from;
+      pass.shared_sets = i == 0 && leaves.shared;
+      pass.even = base;
+      pass.odd = base + glwe;
+      pass.pair_stride = 2 * glwe;
+      pass.set_stride = leaves_per_tree * glwe;
+    }
+    pass.pending = pending;
+    pass.rot_steps = last && lwe_out ? (u32)first : 0u;
+    pass.glwe_out = last ? glwe_out : results[i & 1];
+    pass.lwe_out = last ? lwe_out : nullptr;
+    HIP_TRY(ctx, launch::cmux_tree_pass(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, pass, trees << pass.log_subtrees));
+    from = results[i & 1];
+    done += here;
+  }
+  return TFHE_OK;
+}
+
+int check_lookup_args(tfhe_context* ctx, const void* selectors, const void* data, const void* out, size_t queries, size_t depth,
+                      size_t max_depth, size_t sets, size_t tables) {
+  if (!selectors || !data || !out) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  if (queries == 0 || tables == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "queries and tables must be at least 1");
+  if (depth == 0 || depth > max_depth)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "depth must be in [1, " + std::to_string(max_depth) + "]");
+  if (sets != 1 && sets != queries) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "leaf_sets / table_sets must be 1 or queries");
+  if (queries > kMaxBatch || tables > kMaxBatch || queries * tables > kMaxBatch)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "queries * tables exceeds 2^31 - 1");
+  return TFHE_OK;
+}
+
+}  // namespace
+
+int tfhe_context_reserve_lookup(tfhe_context* ctx, size_t max_trees, size_t max_tree_depth, size_t max_lookup_bits) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  if (max_trees == 0 || max_trees > kMaxBatch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "max_trees must be in [1, 2^31)");
+  if (max_tree_depth > kMaxTreeDepth) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "max_tree_depth must be in [0, 20]");
+  if (max_lookup_bits > ctx->pbs.log_n + kMaxTreeDepth)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "max_lookup_bits must be in [0, log2 N + 20]");
+  if (max_tree_depth == 0 && max_lookup_bits == 0)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "max_tree_depth and max_lookup_bits are both 0: nothing to reserve for");
+  // a lookup of D address bits runs a tree of D - log2 N levels (none up to log2 N bits)
+  const size_t lookup_depth = max_lookup_bits > ctx->pbs.log_n ? max_lookup_bits - ctx->pbs.log_n : 0;
+  return grow_lookup_workspace(ctx, lookup_workspace_need(ctx, max_trees, std::max(max_tree_depth, lookup_depth)));
+}
+
+int tfhe_context_set_lookup_subtree_height(tfhe_context* ctx, unsigned height) {
+  if (!ctx) return TFHE_ERR_INVALID_ARGUMENT;
+  if (height > kMaxTreeDepth) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "subtree height must be in [0, 20] (0: automatic)");
+  ctx->lookup_height = height;
+  return TFHE_OK;
+}
+
+int tfhe_debug_lookup_plan(tfhe_context* ctx, size_t trees, size_t depth, unsigned* subtree_height, unsigned* launches) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  if (!subtree_height || !launches) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  if (trees == 0 || trees > kMaxBatch || depth > kMaxTreeDepth)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "trees must be in [1, 2^31), depth in [0, 20]");
+  launch::LookupPlanInfo plan{};
+  if ((st = lookup_plan_of(ctx, trees, depth, &plan))) return st;
+  *subtree_height = plan.height;
+  *launches = plan.launches;
+  return TFHE_OK;
+}
+
+int tfhe_cmux_prepared_device(tfhe_context* ctx, const void* ggsw_prepared, size_t ggsw_count, const uint32_t* ct0,
+                              const uint32_t* ct1, size_t batch, uint32_t* glwe_out) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  if (!ggsw_prepared || !ct0 || !ct1 || !glwe_out || batch == 0)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
+  if (ggsw_count != 1 && ggsw_count != batch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "ggsw_count must be 1 or batch");
+  if (batch > kMaxBatch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "batch exceeds 2^31 - 1");
+  // a tree of one level per sample whose two leaves live in two arrays: one team per sample, no workspace
+  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
+  CmuxTreePass pass{};
+  pass.selectors = pass.rot_selectors = ggsw_prepared;
+  pass.query_stride = ggsw_count == 1 ? 0 : ggsw_words(ctx) * ctx->parts;
+  pass.tables = 1;
+  pass.height = 1;
+  pass.even = ct0;
+  pass.odd = ct1;
+  pass.set_stride = glwe;
+  pass.glwe_out = glwe_out;
+  HIP_TRY(ctx, launch::cmux_tree_pass(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, pass, batch));
+  return TFHE_OK;
+}
+
+int tfhe_cmux_tree_device(tfhe_context* ctx, const void* selectors_prepared, size_t queries, size_t depth,
+                          const uint32_t* leaves, size_t leaf_sets, size_t tables, uint32_t* glwe_out) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  if ((st = check_lookup_args(ctx, selectors_prepared, leaves, glwe_out, queries, depth, kMaxTreeDepth, leaf_sets, tables))) return st;
+  return run_lookup(ctx, selectors_prepared, queries, depth, 0, depth, LookupLeaves{leaves, nullptr, leaf_sets == 1 && queries > 1},
+                    tables, glwe_out, nullptr);
+}
+
+int tfhe_table_lookup_device(tfhe_context* ctx, const void* selectors_prepared, size_t queries, size_t depth,
+                             const uint32_t* table, size_t table_sets, size_t tables, uint32_t* lwe_out) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  if ((st = check_lookup_args(ctx, selectors_prepared, table, lwe_out, queries, depth, ctx->pbs.log_n + kMaxTreeDepth, table_sets, tables)))
+    return st;
+  const size_t d_lo = std::min(depth, (size_t)ctx->pbs.log_n);
+  return run_lookup(ctx, selectors_prepared, queries, depth, d_lo, depth - d_lo, LookupLeaves{nullptr, table, table_sets == 1 && queries > 1},
+                    tables, nullptr, lwe_out);
+}
+
+// host forms: selectors [queries][depth][R][k+1][N] raw; everything uploaded, the selectors prepared once
+static int lookup_host(tfhe_context* ctx, const uint32_t* selectors, size_t queries, size_t depth, const uint32_t* data,
+                       size_t sets, size_t tables, bool is_table, uint32_t* out) {
+  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
+  const size_t d_lo = is_table ? std::min(depth, (size_t)ctx->pbs.log_n) : 0;
+  const size_t tree_depth = depth - d_lo;
+  const size_t trees = queries * tables;
+  const size_t in_words = sets * tables * ((size_t)1 << depth) * (is_table ? 1 : glwe);
+  const size_t out_words = trees * (is_table ? (size_t)ctx->big_n + 1 : glwe);
+  launch::LookupPlanInfo plan{};
+  int st = lookup_plan_of(ctx, trees, tree_depth, &plan);
+  if (st) return st;
+  if ((st = grow_lookup_workspace(ctx, std::max<size_t>(plan.workspace_words, 1)))) return st;
+  if ((st = ensure_misc(ctx, (in_words + out_words) * sizeof(u32)))) return st;
+  if ((st = upload_and_prepare_ggsw(ctx, selectors, queries * depth))) return st;
+  u32* d_in = reinterpret_cast<u32*>(ctx->d_misc);
+  u32* d_out = d_in + in_words;
+  HIP_TRY(ctx, hipMemcpyAsync(d_in, data, in_words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
+  st = is_table ? tfhe_table_lookup_device(ctx, ctx->d_ggsw_tmp, queries, depth, d_in, sets, tables, d_out)
+                : tfhe_cmux_tree_device(ctx, ctx->d_ggsw_tmp, queries, depth, d_in, sets, tables, d_out);
+  if (st) return st;
+  HIP_TRY(ctx, hipMemcpyAsync(out, d_out, out_words * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return TFHE_OK;
+}
+
+int tfhe_cmux_tree(tfhe_context* ctx, const uint32_t* selectors, size_t queries, size_t depth, const uint32_t* leaves,
+                   size_t leaf_sets, size_t tables, uint32_t* glwe_out) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  if ((st = check_lookup_args(ctx, selectors, leaves, glwe_out, queries, depth, kMaxTreeDepth, leaf_sets, tables))) return st;
+  return lookup_host(ctx, selectors, queries, depth, leaves, leaf_sets, tables, false, glwe_out);
+}
+
+int tfhe_table_lookup(tfhe_context* ctx, const uint32_t* selectors, size_t queries, size_t depth, const uint32_t* table,
+                      size_t table_sets, size_t tables, uint32_t* lwe_out) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  if ((st = check_lookup_args(ctx, selectors, table, lwe_out, queries, depth, ctx->pbs.log_n + kMaxTreeDepth, table_sets, tables)))
+    return st;
+  return lookup_host(ctx, selectors, queries, depth, table, table_sets, tables, true, lwe_out);
 }
 
 // ---------------------------------------------------------------------------------- small ops

@@ -38,6 +38,10 @@ struct tfhe_context {
   bool have_pksk = false;
   u32* d_pack_cols = nullptr; // transposed inputs of a packing call, kPackColsWords words (capi.cpp) or one output's worth
   size_t pack_cols_words = 0;
+  // CMUX tree / table lookup (tfhe_context_reserve_lookup): partial results of the passes and the teams' pending slots
+  u32* d_lookup_ws = nullptr;
+  size_t lookup_ws_words = 0;
+  unsigned lookup_height = 0; // subtree height a team reduces (tfhe_context_set_lookup_subtree_height); 0: automatic
   bool aligned = false;       // decomposer alignment (tfhe_context_set_decomposer_alignment)
   bool ks_first = false;      // bootstrap order (tfhe_context_set_bootstrap_order)
   int shape = 0;              // kernel shape of the blind rotation (tfhe_context_set_kernel_shape): launch::kShape*

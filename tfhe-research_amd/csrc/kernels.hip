@@ -6,6 +6,7 @@
 // team meets at a workgroup barrier once or twice per gadget level (two or one LDS exchange
 // buffers per group) to hand the digit spectra around.
 #include <atomic>
+#include <cmath>
 #include <cstdlib>
 
 #include "launch.h"
@@ -737,6 +738,22 @@ pack_lwe_kernel(PbsParams P /* the KS decomposer */, const typename F::elem* __r
   const int tid = w.tid();
 #pragma unroll
   for (int r = 0; r < E; ++r) atomicAdd(&dst[r * T + tid], w.acc()[r * T + tid]);
+}
+
+// ------------------------------------------------------------------------------ CMUX tree / encrypted table lookup
+// pbs_wave.h::cmux_tree_team states the operations.  One team per (tree, subtree) of a pass, tree = blockIdx.x >>
+// log_subtrees; the team's LDS and registers are external_product_kernel's (one product at a time, x in c.acc(), the
+// pending partial results in the team's slots of the workspace), so its residency is that kernel's.
+template <class F, int LOGN, int K>
+__global__ void __launch_bounds__((TeamCfg<F, LOGN, K, 1>::kThreads),
+                                  (F::kId == FpField::kId || F::kId == Fp49Field::kId || F::kId == FftField::kId
+                                       ? TeamCfg<F, LOGN, K, 1>::kMinWavesFp
+                                       : TeamCfg<F, LOGN, K, 1>::kMinWavesGl))
+cmux_tree_kernel(PbsParams P, const typename F::elem* __restrict__ tw, CmuxTreePass pass) {
+  using C = TeamCfg<F, LOGN, K, 1>;
+  auto w = make_wave<F, LOGN, K, 1>(g_smem, tw);
+  cmux_tree_team<F, LOGN, K, C::G>(w, P, pass, (size_t)(blockIdx.x >> pass.log_subtrees),
+                                   blockIdx.x & ((1u << pass.log_subtrees) - 1u));
 }
 
 // dst row `row` = GLWE [k+1][N]: coefficient 0 of the body += factor[row] (the packing key's s_i g_l)
@@ -1513,6 +1530,102 @@ hipError_t launch_pack_lwe(hipStream_t s, const PbsParams& P, const void* tw_v, 
   }
 }
 
+// How a CMUX tree of `depth` levels over `trees` trees goes out (capi.cpp sequences the launches).
+//   height    levels a team reduces: passes = ceil(depth / height) launches; every pass but the last takes `height`
+//             levels, the last one the rest (and, in a lookup, the rotation chain and the sample extraction).  Pass i
+//             writes trees 2^(depth - levels so far) partial results to the workspace, the next one reads them as its
+//             leaves (two buffers in turn).  A depth of 0 (a lookup of at most log2 N address bits) is one launch.
+// The automatic height trades passes against teams: a team of height h makes 2^h - 1 products one after the other, a
+// pass of T teams on a chip that holds R of them at once takes ceil(T / R) rounds of that, and every launch costs
+// about kLookupLaunchCost products (launch + the chip draining and refilling; a guess, not measured).  The height with
+// the smallest sum over its passes is taken, the larger one on a tie -- many trees: one pass, deep subtrees, nothing
+// through the workspace; one tree: short passes that spread its leaves over the chip.  The rule depends on the shape
+// of the call only (trees, depth), never on data; tfhe_context_set_lookup_subtree_height overrides it.
+constexpr unsigned kLookupLaunchCost = 2;
+constexpr size_t kMaxGrid = 0x7FFFFFFFull;
+struct LookupPlan {
+  u32 height;
+  u32 launches;
+  size_t workspace_words;  // partial results of the passes + the teams' pending slots
+};
+template <class F, int LOGN, int K>
+struct TreeKernel {
+  using C = TeamCfg<F, LOGN, K, 1>;
+  static constexpr int kThreads = C::kThreads;
+  static constexpr size_t kLds = C::kLds;
+  static auto get() { return cmux_tree_kernel<F, LOGN, K>; }
+};
+inline double lookup_cost(size_t trees, u32 depth, u32 h, size_t resident) {
+  double cost = 0;
+  for (u32 done = 0; done < depth;) {
+    const u32 here = depth - done < h ? depth - done : h;
+    done += here;
+    const double teams = (double)trees * (double)((size_t)1 << (depth - done));
+    cost += std::ceil(teams / (double)resident) * (double)(((size_t)1 << here) - 1) + kLookupLaunchCost;
+  }
+  return cost;
+}
+inline bool lookup_plan_for(size_t trees, u32 depth, u32 forced_height, size_t resident, size_t glwe_words, LookupPlan* out) {
+  if (depth == 0) {
+    *out = LookupPlan{0u, 1u, 0};
+    return trees <= kMaxGrid;
+  }
+  u32 h = forced_height > depth ? depth : forced_height;
+  if (h == 0) {
+    double best = 0;
+    for (u32 cand = 1; cand <= depth; ++cand) {
+      if ((double)trees * (double)((size_t)1 << (depth - cand)) > (double)kMaxGrid) continue;
+      const double cost = lookup_cost(trees, depth, cand, resident);
+      if (h == 0 || cost <= best) {
+        best = cost;
+        h = cand;
+      }
+    }
+    if (h == 0) return false;
+  }
+  const u32 passes = (depth + h - 1) / h;
+  size_t glwes = 0;
+  if (!launch::lookup_workspace_glwes(trees, depth, h, &glwes)) return false;
+  *out = LookupPlan{h, passes, glwes * glwe_words};
+  return true;
+}
+
+template <class F, int LOGN, int K>
+hipError_t plan_lookup(size_t trees, u32 depth, u32 forced_height, launch::LookupPlanInfo* out) {
+  if constexpr (!field_shape_ok<F, LOGN>()) {
+    return hipErrorInvalidValue;
+  } else {
+    unsigned resident = 0;
+    hipError_t e = resident_teams<TreeKernel<F, LOGN, K>>(&resident);
+    if (e != hipSuccess) return e;
+    LookupPlan plan{};
+    if (!lookup_plan_for(trees, depth, forced_height, resident, (size_t)(K + 1) << LOGN, &plan)) return hipErrorInvalidValue;
+    out->height = plan.height;
+    out->launches = plan.launches;
+    out->workspace_words = plan.workspace_words;
+    return hipSuccess;
+  }
+}
+
+// pass.query_stride arrives in 8-byte words, like launch_external_product's stride
+template <class F, int LOGN, int K>
+hipError_t launch_cmux_tree_pass(hipStream_t s, const PbsParams& P, const void* tw_v, CmuxTreePass pass, size_t teams) {
+  if constexpr (!field_shape_ok<F, LOGN>()) {
+    return hipErrorInvalidValue;
+  } else {
+    using C = TeamCfg<F, LOGN, K, 1>;
+    if (teams == 0 || teams > kMaxGrid) return hipErrorInvalidValue;
+    auto tw = static_cast<const typename F::elem*>(tw_v);
+    auto kern = cmux_tree_kernel<F, LOGN, K>;
+    static std::atomic<unsigned long long> lds_done{0};
+    hipError_t e = allow_lds(kern, C::kLds, lds_done);
+    if (e != hipSuccess) return e;
+    pass.query_stride /= sizeof(typename F::elem) / 8;
+    hipLaunchKernelGGL(kern, dim3((unsigned)teams), dim3(C::kThreads), C::kLds, s, P, tw, pass);
+    return hipGetLastError();
+  }
+}
+
 template <class F, int LOGN>
 hipError_t launch_bsk_prepare(hipStream_t s, const void* tw_v, const u32* polys, size_t poly_count,
                               void* spectra_v, u32 k) {
@@ -1725,6 +1838,30 @@ hipError_t pack_lwe(hipStream_t s, int field, const PbsParams& P, const void* tw
 hipError_t packing_add_gadget(hipStream_t s, u32* pksk, size_t rows, u32 k, u32 log_n, const u32* factor) {
   hipLaunchKernelGGL(packing_add_gadget_kernel, dim3(grid_for(rows, 256)), dim3(256), 0, s, pksk, rows, k, log_n, factor);
   return hipGetLastError();
+}
+
+bool lookup_workspace_glwes(size_t trees, u32 depth, u32 height, size_t* glwes) {
+  if (depth == 0) {
+    *glwes = 0;
+    return trees <= 0x7FFFFFFFull;
+  }
+  const u32 h = height > depth ? depth : height;
+  const u32 passes = (depth + h - 1) / h;
+  const double teams0 = (double)trees * (double)((size_t)1 << (depth - h));
+  if (h == 0 || teams0 > (double)0x7FFFFFFFull) return false;
+  size_t n = (size_t)teams0 * (h - 1);                              // pending slots: the first pass has the most teams
+  if (passes >= 2) n += (size_t)teams0;                              // results of passes 0, 2, ..
+  if (passes >= 3) n += trees * ((size_t)1 << (depth - 2 * h));      // results of passes 1, 3, ..
+  *glwes = n;
+  return true;
+}
+
+hipError_t lookup_plan(int field, const PbsParams& P, size_t trees, u32 depth, u32 forced_height, LookupPlanInfo* out) {
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (plan_lookup<FF, LL, KK>(trees, depth, forced_height, out))));
+}
+
+hipError_t cmux_tree_pass(hipStream_t s, int field, const PbsParams& P, const void* tw, const CmuxTreePass& pass, size_t teams) {
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (launch_cmux_tree_pass<FF, LL, KK>(s, P, tw, pass, teams))));
 }
 
 hipError_t key_switch(hipStream_t s, const KsParams& K, u32 big_n, u32 n, const u32* lwe_in,

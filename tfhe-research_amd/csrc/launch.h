@@ -95,6 +95,22 @@ hipError_t pack_lwe(hipStream_t s, int field, const PbsParams& P, const void* tw
 // pksk [rows][k+1][N]: body coefficient 0 of row r += factor[r]
 hipError_t packing_add_gadget(hipStream_t s, u32* pksk, size_t rows, u32 k, u32 log_n, const u32* factor);
 
+// ---- CMUX tree / encrypted table lookup (pbs_wave.h::cmux_tree_team)
+// How a tree of `depth` levels over `trees` trees goes out (kernels.hip::lookup_plan_for); forced_height 0: automatic.
+// hipErrorInvalidValue: no height keeps the first pass inside a grid of 2^31 - 1 teams.
+struct LookupPlanInfo {
+  u32 height;              // levels a team reduces (0 for depth 0)
+  u32 launches;            // ceil(depth / height), at least 1
+  size_t workspace_words;  // u32 words of scratch the passes need (partial results and pending slots)
+};
+hipError_t lookup_plan(int field, const PbsParams& P, size_t trees, u32 depth, u32 forced_height, LookupPlanInfo* out);
+// GLWEs of scratch a tree of `depth` levels over `trees` trees needs at subtree height `height` >= 1 (pending slots of
+// the first pass + the two result buffers): host arithmetic on the shape alone, proportional to `trees`.  false: the
+// first pass would not fit a grid of 2^31 - 1 teams.
+bool lookup_workspace_glwes(size_t trees, u32 depth, u32 height, size_t* glwes);
+// one pass: `teams` = trees << pass.log_subtrees workgroups.  pass.query_stride in 8-byte words here.
+hipError_t cmux_tree_pass(hipStream_t s, int field, const PbsParams& P, const void* tw, const CmuxTreePass& pass, size_t teams);
+
 // elementwise helpers.  first_shift = bit of the lowest kept limb (PbsParams::first_shift)
 hipError_t decompose_words(hipStream_t s, u32 log_base, u32 levels, u32 first_shift, const u32* values,
                            size_t count, u32* digits /* [count][levels] */);

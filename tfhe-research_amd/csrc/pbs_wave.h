@@ -1191,6 +1191,146 @@ TFHE_HD void sample_extract_team(const Ctx& c, u32* out /* K*N + 1 */, int s = 0
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Encrypted table lookup (no reference counterpart; the reference stops at one cmux(), ggsw.rs:164-178): a CMUX tree
+// over GGSW-encrypted address bits, then a rotation chain and one sample extraction.  All arithmetic mod 2^32:
+//   cmux(C, d0, d1) = d0 + external_product(C, d1 - d0)                       (the inputs are not modified)
+//   Tree(C_0 .. C_{d-1}; L_0 .. L_{2^d - 1}):  L(0) = L,  L(i+1)_j = cmux(C_i, L(i)_{2j}, L(i)_{2j+1}),  result L(d)_0
+//     -- with C_i encrypting bit b_i it selects leaf sum_i b_i 2^i (selector 0 pairs neighbouring leaves)
+//   Lookup(C_0 .. C_{D-1}; T[0 .. 2^D)), d_lo = min(D, log2 N), d_hi = D - d_lo:
+//     leaf h = the trivial GLWE with body coefficient j = T[h 2^d_lo + j] << tv_shift for j < 2^d_lo, 0 above
+//     root = Tree(C_{d_lo} .. C_{D-1}; leaves);  for i = 0 .. d_lo - 1 in this order: root = cmux(C_i, root, X^{-2^i} root)
+//     out = sample_extract(root, 0)
+// Every product is external_product_team with the (K+1) l rows and the base the context was admitted with: no new
+// exactness rule.
+//
+// cmux_tree_team: ONE team reduces a subtree of 2^height leaves depth-first with the binary-counter walk and then runs
+// `rot_steps` rotation steps on the result.  For leaf pair p: x = cmux(C_0, leaf_{2p}, leaf_{2p+1}); while bit t-1 of p
+// is set: x = cmux(C_t, pending[t], x), t++; then pending[t] = x.  x lives in c.acc(); pending[1 .. height) are slots of
+// global memory that belong to this team.  That is 2^height - 1 products, the same for every wave of the team (p and t
+// are team-uniform).  All of them go through ONE call site whose operand functors branch on the (uniform) kind of step:
+//   leaf pair   src(j) = leaf_{2p+1}[j] - leaf_{2p}[j]               out(j, v): acc[j] = leaf_{2p}[j] + v
+//   pending     src(j) = acc[j] - pending[t][j]                      out(j, v): acc[j] = pending[t][j] + v
+//   rotation i  src(j) = (X^{2N - 2^i} acc)[j] - acc[j]              out(j, v): acc[j] += v     (the blind rotation's)
+// In the first two every word -- of acc and of a pending slot -- is read and written only by the lane that owns index
+// j (src and out walk the same indices r T + tid), so the walk needs no barrier and no fence of its own: the lane
+// that parks pending[t] is the one that reads it back.  A rotation reads other lanes' words: it starts behind
+// poly_sync, and all its rotated reads precede the product's first inverse transform.  After a product on ONE
+// exchange buffer poly_sync also keeps a group of several waves (G > 1) from starting the next forward transform under
+// the inverse transform's cross-wave transposes (pack_lwe_team); with two buffers the product ends in a team barrier.
+//
+// CmuxTreePass: what one launch (kernels.hip::cmux_tree_kernel) reduces -- plain data, the same for every team.  Team
+// (tree, subtree) of a pass reduces leaves [subtree 2^height, (subtree + 1) 2^height) of tree = query * tables + table
+// with selectors [0, height) of the pass; a tree deeper than the pass goes on in the next pass, whose leaves are this
+// one's results.  Strides count u32 words, selector strides field elements.
+// ---------------------------------------------------------------------------------------------
+struct CmuxTreePass {
+  const void* selectors;      // prepared GGSWs: selector t of query q at selectors + q * query_stride + t * ggsw_words
+  const void* rot_selectors;  // the same for rotation step i (used if rot_steps > 0)
+  size_t query_stride;        // elements from one query's selectors to the next one's; 0: all queries share them
+  u32 tables;                 // trees per query
+  u32 height;                 // tree levels of this pass; 0: the leaf itself (a lookup of at most log2 N address bits)
+  u32 log_subtrees;           // the pass reduces 2^log_subtrees subtrees per tree
+  u32 shared_sets;            // 1: tree (q, table) reads leaf / table set `table`; 0: set q * tables + table
+  // leaves in memory (even != nullptr): leaf 2g of a set at even + set * set_stride + g * pair_stride, leaf 2g + 1 at
+  // odd + the same ([2^depth][K+1][N] sets: odd = even + (K+1) N, pair_stride = 2 (K+1) N; a single CMUX: two arrays)
+  const u32* even;
+  const u32* odd;
+  size_t pair_stride, set_stride;
+  // or a clear table (even == nullptr): leaf h of a set is trivial, body coefficient j = table[set * table_stride +
+  // (h << log_entries) + j] << tv_shift for j < 2^log_entries
+  const u32* table;
+  size_t table_stride;
+  u32 log_entries;
+  u32 rot_steps;   // rotation steps after the tree (the last pass of a lookup: min(D, log2 N))
+  u32* pending;    // [team][height - 1][K+1][N], team = tree * 2^log_subtrees + subtree (unused if height < 2)
+  u32* glwe_out;   // [team][K+1][N], or null
+  u32* lwe_out;    // [team][K N + 1]: sample_extract(result, 0), or null
+};
+
+template <class F, int LOGN, int K, int G, class Ctx>
+TFHE_HD void cmux_tree_team(const Ctx& c, const PbsParams& P, const CmuxTreePass& A, size_t tree, u32 subtree) {
+  typedef typename F::elem elem;
+  constexpr int E = NttShape<LOGN, G>::kE;
+  constexpr int T = NttShape<LOGN, G>::kThreads;
+  constexpr int N = 1 << LOGN;
+  constexpr size_t GLWE = (size_t)(K + 1) * N;
+  const int lane = c.tid();
+  const int me = c.group();
+  u32* acc = c.acc();
+  const size_t ggsw_words = (size_t)(K + 1) * P.levels * (K + 1) * F::kParts * (N >> F::kLogShrink);  // elements
+  const size_t query = tree / A.tables;
+  const size_t set = A.shared_sets ? tree % A.tables : tree;
+  const elem* sel = static_cast<const elem*>(A.selectors) + query * A.query_stride;
+  const elem* rot = static_cast<const elem*>(A.rot_selectors) + query * A.query_stride;
+  const size_t team = (tree << A.log_subtrees) + subtree;
+  // my polynomial's pending slots, slot t at + (t - 1) GLWE (a pass of one level has none)
+  u32* pending = A.height > 1 ? A.pending + team * (A.height - 1) * GLWE + (size_t)me * N : nullptr;
+  const bool from_table = A.even == nullptr;
+  const u32* tab = from_table ? A.table + set * A.table_stride : nullptr;
+  const u32 entries = 1u << A.log_entries;
+  const size_t leaf0 = (size_t)subtree << A.height;  // my first leaf inside the tree
+  // coefficient j of my polynomial of leaf `leaf` of the tree (lane-local)
+  auto table_word = [&](size_t leaf, int j) -> u32 {
+    return (me == K && (u32)j < entries) ? tab[(leaf << A.log_entries) + (u32)j] << P.tv_shift : 0u;
+  };
+
+  if (A.height == 0) {
+    const u32* only = from_table ? nullptr : A.even + set * A.set_stride + (size_t)me * N;
+#pragma unroll
+    for (int r = 0; r < E; ++r) acc[r * T + lane] = from_table ? table_word(leaf0, r * T + lane) : only[r * T + lane];
+  }
+  const u32 tree_products = A.height ? (1u << A.height) - 1u : 0u;
+  const u32 products = tree_products + A.rot_steps;
+  if (products > tree_products && tree_products == 0) c.poly_sync();  // the rotation reads words other lanes wrote
+  u32 p = 0, t = 0;  // the next tree product: level t of leaf pair p
+#pragma unroll 1
+  for (u32 step = 0; step < products; ++step) {
+    const bool rotating = step >= tree_products;
+    const bool at_leaves = !rotating && t == 0;
+    const size_t pair = (leaf0 >> 1) + p;
+    const size_t leaf_at = set * A.set_stride + pair * A.pair_stride + (size_t)me * N;
+    // d0 of a tree product: the even leaf or the parked partial result (null where the step has neither)
+    const u32* a = rotating ? nullptr : !at_leaves ? pending + (size_t)(t - 1) * GLWE : from_table ? nullptr : A.even + leaf_at;
+    const u32* b = (at_leaves && !from_table) ? A.odd + leaf_at : nullptr;
+    const u32 m = c.uniform(2u * N - (1u << (rotating ? step - tree_products : 0u)));  // X^{-2^i}
+    auto src = [&](int j) -> u32 {
+      if (rotating) return monomial_coeff<LOGN>(acc, j, m) - acc[j];
+      if (!at_leaves) return acc[j] - a[j];
+      if (from_table) return table_word(2 * pair + 1, j) - table_word(2 * pair, j);
+      return b[j] - a[j];
+    };
+    auto out = [&](int j, u32 value) {
+      if (rotating) c.lds_add(acc + j, value);
+      else if (at_leaves && from_table) acc[j] = table_word(2 * pair, j) + value;
+      else acc[j] = a[j] + value;
+    };
+    external_product_team<F, LOGN, K, G>(c, P, (rotating ? rot + (size_t)(step - tree_products) * ggsw_words : sel + (size_t)t * ggsw_words), src, out);
+    if (c.exchange_buffers() != 2) c.poly_sync();
+    if (!rotating) {
+      ++t;
+      if (!((p >> (t - 1)) & 1u)) {  // the walk climbs while bit t-1 of p is set; here it parks x and takes the next pair
+        if (t < A.height) {
+          u32* slot = pending + (size_t)(t - 1) * GLWE;
+#pragma unroll
+          for (int r = 0; r < E; ++r) slot[r * T + lane] = acc[r * T + lane];
+        }
+        ++p;
+        t = 0;
+      }
+    }
+  }
+  if (A.glwe_out) {
+    u32* dst = A.glwe_out + team * GLWE + (size_t)me * N;
+#pragma unroll
+    for (int r = 0; r < E; ++r) dst[r * T + lane] = acc[r * T + lane];
+  }
+  if (A.lwe_out) {
+    c.poly_sync();  // sample_extract reads words other lanes wrote
+    sample_extract_team<LOGN, K, G>(c, A.lwe_out + team * ((size_t)K * N + 1));
+  }
+}
+
 // Forward NTT of one u32 polynomial of the bootstrapping key into the prepared layout,
 // pre-scaled by N^-1.
 // LAYOUT_E: the shape the key is laid out for (key_layout_e; 0: this transform's own)
