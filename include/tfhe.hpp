@@ -570,6 +570,46 @@ inline LweCiphertext table_lookup(Engine& e, const std::vector<GgswCiphertext>& 
   e.check(tfhe_table_lookup(e.raw(), sel.data(), 1, depth, table.data(), 1, 1, out.data.data()));
   return out;
 }
+// ---- rotation from a GLWE accumulator and the tree LUT (tfhe_hip.h states the operations; first device only) ----
+// X^{-(b~ + rotation_offset)} acc, then the n CMUXes: the accumulator's words are taken as they are (already encoded)
+inline GlweCiphertext blind_rotate_glwe(Engine& e, const LweCiphertext& ct, const GlweCiphertext& acc, size_t rotation_offset = 0) {
+  const TfheParams& p = e.params();
+  const size_t glwe = (p.glwe_dimension + 1) * p.degree();
+  if (ct.data.size() != size_t(p.lwe_dimension) + 1) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "LWE length");
+  if (acc.data.size() != glwe) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "GLWE shape");
+  if (rotation_offset >= 2 * p.degree()) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "rotation_offset below 2N");
+  GlweCiphertext out{std::vector<uint32_t>(glwe)};
+  e.check(tfhe_blind_rotate_glwe_batch(e.raw(), ct.data.data(), 1, acc.data.data(), 1, rotation_offset, out.data.data()));
+  return out;
+}
+// ... + sample_extract(.., 0) + key_switch_lwe (the reference's order): a bootstrap whose table the server cannot read
+// when acc is a GLWE encryption of the encoded test vector
+inline LweCiphertext bootstrap_glwe(Engine& e, const LweCiphertext& ct, const GlweCiphertext& acc, size_t rotation_offset = 0) {
+  const TfheParams& p = e.params();
+  if (ct.data.size() != size_t(p.lwe_dimension) + 1) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "LWE length");
+  if (acc.data.size() != (p.glwe_dimension + 1) * p.degree()) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "GLWE shape");
+  if (rotation_offset >= 2 * p.degree()) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "rotation_offset below 2N");
+  LweCiphertext out{std::vector<uint32_t>(ct.data.size())};
+  e.check(tfhe_bootstrap_glwe_batch(e.raw(), ct.data.data(), 1, acc.data.data(), 1, rotation_offset, out.data.data()));
+  return out;
+}
+// table[sum_t x_t B^t] of d = digits.size() encrypted digits below B = 2^log_p (digit 0 least significant), table of
+// B^d un-encoded values < B: an ordinary LWE of n + 1 words.  Needs the bootstrapping key and a packing key from the
+// flattened GLWE key (generate_packing_key(e, lwe_secret_key_from(glwe_sk), glwe_sk, rng)).
+inline LweCiphertext tree_lut(Engine& e, const std::vector<LweCiphertext>& digits, const std::vector<uint32_t>& table) {
+  const TfheParams& p = e.params();
+  const size_t d = digits.size();
+  if (d == 0 || d * p.log_p > 16 || table.size() != (size_t)1 << (d * p.log_p))
+    throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "B^d table entries, d * log_p in 1..16");
+  std::vector<const uint32_t*> ptrs(d);
+  for (size_t t = 0; t < d; ++t) {
+    if (digits[t].data.size() != size_t(p.lwe_dimension) + 1) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "LWE length");
+    ptrs[t] = digits[t].data.data();
+  }
+  LweCiphertext out{std::vector<uint32_t>(size_t(p.lwe_dimension) + 1)};
+  e.check(tfhe_tree_lut_batch(e.raw(), ptrs.data(), d, 1, table.data(), 1, 1, out.data.data()));
+  return out;
+}
 // bootstrapping_key_gen bootstrapping.rs:23-56; the generated key is also installed in the engine.
 // bmmp = true makes the key of the unrolled blind rotation instead (notes/BMMP Bootstrapping.md:22-24:
 // GGSW(s s'), GGSW(s (1-s')), GGSW(s' (1-s)) per pair of key bits; N = 512, even n).

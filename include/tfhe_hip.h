@@ -161,6 +161,39 @@ int tfhe_blind_rotate_batch_device(tfhe_context *ctx, const uint32_t *lwe_in, si
                                    const uint32_t *test_vector_poly, size_t tv_count,
                                    uint32_t *glwe_out);
 
+/* ---- blind rotation and bootstrap from a GLWE accumulator (no reference counterpart) -------------------------------
+ * The reference's rotation starts from a clear test vector (bootstrapping.rs:67-78).  Here the initial accumulator is
+ * any GLWE ciphertext: acc_in [acc_count][k+1][N], acc_count = 1 (every row starts from the same one) or batch.  All
+ * arithmetic mod 2^32:
+ *   acc_0 = X^{(2N - b~ - rotation_offset) mod 2N} * acc_in,  b~ = switch_modulus(b, 32, log2(2N)), rotation_offset < 2N
+ *     -- the negacyclic monomial product on all k+1 polynomials; the words of acc_in are taken as they are (already
+ *     encoded: no shift by 32 - log_p - padding_bits);
+ *   then the n CMUXes of bootstrapping.rs:79-105, unchanged.
+ * tfhe_blind_rotate_glwe_batch* returns the final accumulators, lwe_in [batch][n+1] -> glwe_out [batch][k+1][N].
+ * tfhe_bootstrap_glwe_batch* adds sample extraction at index 0 and the key switch like tfhe_bootstrap_batch*, in the
+ * order tfhe_context_set_bootstrap_order selected (KS first: input and output have k*N+1 words).  The result's phase
+ * is coefficient (phase(lwe_in) 2N / 2^32 + rotation_offset) mod 2N of phase(acc_in), negated from N on.
+ *
+ * With acc_in = (0, .., 0, tv << (32 - log_p - padding_bits)), acc_count = tv_count and rotation_offset 0 the words
+ * equal tfhe_blind_rotate_batch's and tfhe_bootstrap_batch's bit for bit.  What it adds: the table may stay secret
+ * (a GLWE encryption of the encoded test vector), and a packed GLWE of results (tfhe_pack_lwe_batch) is bootstrapped
+ * again without unpacking: with 2^log_p results on N / 2^log_p coefficients each, rotation_offset = N / 2^(log_p+1)
+ * selects the one the input encrypts (the tree LUT below).  No new exactness rule: from the first CMUX on the products'
+ * inputs are arbitrary words already.  Noise: the rotation's own plus that of the selected coefficient of acc_in.
+ *
+ * Every kernel shape and backend the context was admitted with; the kernels are the ones of tfhe_blind_rotate_batch
+ * (their accumulator set-up reads acc_in through the rotated index).  With a BMMP key loaded: TFHE_ERR_UNSUPPORTED.
+ * acc_in may not overlap glwe_out.  The _device forms run on the context's stream, allocate nothing after
+ * tfhe_context_reserve(max_batch) and are capturable wherever tfhe_bootstrap_batch_device is. */
+int tfhe_blind_rotate_glwe_batch(tfhe_context *ctx, const uint32_t *lwe_in, size_t batch, const uint32_t *acc_in,
+                                 size_t acc_count, size_t rotation_offset, uint32_t *glwe_out);
+int tfhe_blind_rotate_glwe_batch_device(tfhe_context *ctx, const uint32_t *lwe_in, size_t batch, const uint32_t *acc_in,
+                                        size_t acc_count, size_t rotation_offset, uint32_t *glwe_out);
+int tfhe_bootstrap_glwe_batch(tfhe_context *ctx, const uint32_t *lwe_in, size_t batch, const uint32_t *acc_in,
+                              size_t acc_count, size_t rotation_offset, uint32_t *lwe_out);
+int tfhe_bootstrap_glwe_batch_device(tfhe_context *ctx, const uint32_t *lwe_in, size_t batch, const uint32_t *acc_in,
+                                     size_t acc_count, size_t rotation_offset, uint32_t *lwe_out);
+
 /* sample_extract(): bootstrapping.rs:122-156.  glwe [batch][k+1][N] -> lwe_out [batch][k*N+1] */
 int tfhe_sample_extract_batch(tfhe_context *ctx, const uint32_t *glwe, size_t batch,
                               size_t sample_index, uint32_t *lwe_out);
@@ -211,6 +244,57 @@ int tfhe_pack_lwe_batch(tfhe_context *ctx, const uint32_t *lwe_in, size_t groups
                         uint32_t *glwe_out);
 int tfhe_pack_lwe_batch_device(tfhe_context *ctx, const uint32_t *lwe_in, size_t groups, size_t per_group,
                                uint32_t *glwe_out);
+
+/* ---- tree LUT: a function of d digits of log_p bits each (no reference counterpart) ---------------------------------
+ * The tree-based bootstrap of Guimaraes, Borin and Aranha (2021).  Inputs and output are ordinary LWE ciphertexts at
+ * the bootstrap boundary, so it composes with gates, gate graphs and itself; its noise does not depend on the table
+ * size.  B = 2^log_p, rep = N / B; digits[t] [batch][io_words] encrypts digit x_t < B (digit 0 least significant),
+ * table [table_sets][tables][B^d] holds un-encoded values < B, table_sets = 1 or batch; every intermediate LWE is a
+ * k N-dimensional sample extraction:
+ *   R0_h = sample_extract(BlindRotate(c_0; construct_test_from_lut(T[h B .. h B + B))), 0)        for h < B^(d-1)
+ *   for t = 1 .. d-1 and h < B^(d-1-t):
+ *     G_h  = Pack(L_0 .. L_{N-1}),  L_j = R(t-1)_{h B + floor(j / rep)}   (the packing formula above with per_group = N:
+ *            result v occupies coefficients [v rep, (v+1) rep))
+ *     Rt_h = sample_extract(BlindRotateGLWE(c_t; G_h, rotation_offset = rep / 2), 0)
+ *   out = R(d-1)_0, key-switched in the reference's order; with the key switch first every digit is key-switched once,
+ *   before its level, and the output has k N + 1 words.  lwe_out [batch][tables][io_words] decodes to
+ *   T[sum_t x_t B^t].  Its padding bit is the one the reference's bootstrap of digit 0 leaves: that test vector
+ *   answers x_0 = 0 under a negative phase error with -(B - T) Delta = T Delta - 2^31, the same message with the
+ *   padding bit set; the upper levels (offset rep / 2) add nothing of the kind and pass it through.
+ * The words equal the composition of tfhe_blind_rotate_batch, tfhe_sample_extract_batch, tfhe_pack_lwe_batch on the
+ * materialised N-fold list, tfhe_blind_rotate_glwe_batch and tfhe_key_switch_batch; d = 1 equals tfhe_bootstrap_batch.
+ * Cost: (B^d - 1) / (B - 1) rotations per (row, table) -- 85 for 8 bits at log_p = 2 -- and (B^(d-1) - 1) / (B - 1)
+ * packings.  A level is one rotation call over all rows x tables x sub-tables and one packing call (in the chunks
+ * the packing workspace holds, as tfhe_pack_lwe_batch_device); there is no host loop over rows, tables or sub-tables.
+ *
+ * Keys: the bootstrapping key and a packing key with from_dimension = k N made from the flattened GLWE key
+ * (tfhe_generate_packing_key(ctx, flattened glwe_sk, k N, glwe_sk, ..)).  TFHE_ERR_NO_KEY when either is missing,
+ * TFHE_ERR_INVALID_ARGUMENT when the packing key has another dimension, TFHE_ERR_UNSUPPORTED with a BMMP key.  A backend
+ * that refuses the packing key (tfhe_load_packing_key: TFHE_ERR_EXACTNESS) cannot run it.
+ *
+ * Limits: 1 <= log_p < log2 N, d * log_p <= 16 (a table of at most 65,536 entries) and batch * tables * B^(d-1) < 2^31.
+ * Workspace: tfhe_context_reserve_tree_lut(max_batch, max_digits, max_tables) reserves, for R = max_batch * max_tables *
+ * B^(max_digits-1) level-0 rotations, R * [(n+1) + N + (k+1) N + (k N + 1)] + (R / B) * [(k N + 1) + (k+1) N] +
+ * max_batch * (n+1) words: each rotation's copy of its row's digit and its test vector (the rotate kernels address sample
+ * r's inputs at r * stride; copies instead of an index map keep them unchanged), the accumulators between the launches
+ * of a segmented rotation, the two levels' results and the packed GLWEs.  At N = 1024, k = 1, n = 630, log_p = 2 that
+ * is ~21 KiB per rotation: 1.3 GiB for 1,024 rows of 4 digits.  It covers every smaller call.  The _device form runs on
+ * the context's stream and allocates nothing after it; a call beyond the reservation returns TFHE_ERR_INVALID_ARGUMENT
+ * with the need in bytes.  digits is a host array of d device pointers.  The host form reserves for itself and blocks.
+ *
+ * Noise, in units of the 32-bit torus.  A level adds the rotation's
+ *   s_br^2 = n * [ (k+1) l N (B_pbs^2/12 + 1/6) (sigma_glwe 2^32)^2 + (1 + k N / 2) 2^(2 ignored_bits_pbs) / 12 ]
+ * and every level but the last the packing formula's with m = N and d = k N
+ *   s_pk^2 = k N * l_ks * N * (B_ks^2/12 + 1/6) (sigma_glwe 2^32)^2 + (k N / 2) 2^(2 ignored_bits_ks) / 12
+ * so the extraction R(d-1)_0 carries  sigma^2 = d * s_br^2 + (d-1) * s_pk^2,  independent of B^d; in the reference's
+ * order the final key switch adds its own k N * l_ks (B_ks^2/12 + 1/6) (sigma_lwe 2^32)^2 + (k N / 2)
+ * 2^(2 ignored_bits_ks) / 12.  A digit selects its block as long as its own phase error, after the modulus switch to
+ * 2N, stays below half a block (2^32 / 4B), exactly as in a plain bootstrap. */
+int tfhe_context_reserve_tree_lut(tfhe_context *ctx, size_t max_batch, size_t max_digits, size_t max_tables);
+int tfhe_tree_lut_batch(tfhe_context *ctx, const uint32_t *const *digits, size_t d, size_t batch, const uint32_t *table,
+                        size_t table_sets, size_t tables, uint32_t *lwe_out);
+int tfhe_tree_lut_batch_device(tfhe_context *ctx, const uint32_t *const *digits, size_t d, size_t batch,
+                               const uint32_t *table, size_t table_sets, size_t tables, uint32_t *lwe_out);
 
 /* ---- ggsw.rs ------------------------------------------------------------------------------ */
 /* external_product(): ggsw.rs:132-161.  ggsw [ggsw_count][(k+1)*l][k+1][N] with ggsw_count = 1

@@ -61,6 +61,13 @@ extern "C" {
                       leaf_sets: usize, tables: usize, glwe_out: *mut u32) -> c_int;
     fn tfhe_table_lookup(ctx: *mut TfheContext, selectors: *const u32, queries: usize, depth: usize, table: *const u32,
                          table_sets: usize, tables: usize, lwe_out: *mut u32) -> c_int;
+    // rotation from a GLWE accumulator and the tree LUT (include/tfhe_hip.h)
+    fn tfhe_blind_rotate_glwe_batch(ctx: *mut TfheContext, lwe_in: *const u32, batch: usize, acc_in: *const u32,
+                                    acc_count: usize, rotation_offset: usize, glwe_out: *mut u32) -> c_int;
+    fn tfhe_bootstrap_glwe_batch(ctx: *mut TfheContext, lwe_in: *const u32, batch: usize, acc_in: *const u32,
+                                 acc_count: usize, rotation_offset: usize, lwe_out: *mut u32) -> c_int;
+    fn tfhe_tree_lut_batch(ctx: *mut TfheContext, digits: *const *const u32, d: usize, batch: usize, table: *const u32,
+                           table_sets: usize, tables: usize, lwe_out: *mut u32) -> c_int;
     fn tfhe_cmux_batch(ctx: *mut TfheContext, ggsw: *const u32, ggsw_count: usize, ct0: *const u32,
                        ct1: *mut u32, batch: usize, glwe_out: *mut u32) -> c_int;
     fn tfhe_gate_batch(ctx: *mut TfheContext, truth: *const u32, ct0: *const u32, ct1: *const u32,
@@ -253,6 +260,54 @@ pub fn table_lookup(bk: &GpuBootstrappingKey, selectors: &Array2<u32>, table: &A
         tfhe_table_lookup(bk.ctx, selectors.as_slice().unwrap().as_ptr(), 1, depth, table.as_slice().unwrap().as_ptr(), 1, 1,
                           out.as_slice_mut().unwrap().as_mut_ptr())
     }, "table_lookup");
+    out
+}
+
+/// Blind rotation that starts from the GLWE ciphertext `acc` (k+1, N), words already encoded:
+/// X^{-(b~ + rotation_offset)} acc, then the n CMUXes (no reference counterpart).
+pub fn blind_rotate_glwe(bk: &GpuBootstrappingKey, lwe: &Array1<u32>, acc: &Array2<u32>, rotation_offset: usize) -> Array2<u32> {
+    let n = 1usize << bk.params.glwe_poly_degree;
+    let k1 = bk.params.glwe_dimension as usize + 1;
+    assert!(lwe.len() == bk.params.lwe_dimension as usize + 1 && acc.dim() == (k1, n) && rotation_offset < 2 * n,
+            "blind_rotate_glwe: lwe of n+1 words, acc (k+1, N), rotation_offset below 2N");
+    let mut out = Array2::<u32>::zeros((k1, n));
+    check(bk.ctx, unsafe {
+        tfhe_blind_rotate_glwe_batch(bk.ctx, lwe.as_slice().unwrap().as_ptr(), 1, acc.as_slice().unwrap().as_ptr(), 1,
+                                     rotation_offset, out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "blind_rotate_glwe");
+    out
+}
+
+/// blind_rotate_glwe + sample extraction at 0 + key switch: with `acc` a GLWE encryption of the encoded test vector,
+/// a bootstrap against a table the server cannot read.
+pub fn bootstrap_glwe(bk: &GpuBootstrappingKey, lwe: &Array1<u32>, acc: &Array2<u32>, rotation_offset: usize) -> Array1<u32> {
+    let n = 1usize << bk.params.glwe_poly_degree;
+    let k1 = bk.params.glwe_dimension as usize + 1;
+    assert!(lwe.len() == bk.params.lwe_dimension as usize + 1 && acc.dim() == (k1, n) && rotation_offset < 2 * n,
+            "bootstrap_glwe: lwe of n+1 words, acc (k+1, N), rotation_offset below 2N");
+    let mut out = Array1::<u32>::zeros(lwe.len());
+    check(bk.ctx, unsafe {
+        tfhe_bootstrap_glwe_batch(bk.ctx, lwe.as_slice().unwrap().as_ptr(), 1, acc.as_slice().unwrap().as_ptr(), 1,
+                                  rotation_offset, out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "bootstrap_glwe");
+    out
+}
+
+/// table[sum_t x_t B^t] of the d encrypted digits in the rows of `digits` (d, n+1), B = 2^log_p, digit 0 least
+/// significant; `table` holds B^d un-encoded values below B.  Needs a packing key from the flattened GLWE key.
+pub fn tree_lut(bk: &GpuBootstrappingKey, digits: &Array2<u32>, table: &Array1<u32>) -> Array1<u32> {
+    let d = digits.nrows();
+    let log_p = bk.params.log_p as usize;
+    let width = bk.params.lwe_dimension as usize + 1;
+    assert!(d >= 1 && d * log_p <= 16 && digits.ncols() == width, "tree_lut: d rows of n+1 words, d * log_p in 1..=16");
+    assert!(table.len() == 1usize << (d * log_p), "tree_lut: B^d entries");
+    let flat = digits.as_slice().unwrap();
+    let ptrs: Vec<*const u32> = (0..d).map(|t| flat[t * width..].as_ptr()).collect();
+    let mut out = Array1::<u32>::zeros(width);
+    check(bk.ctx, unsafe {
+        tfhe_tree_lut_batch(bk.ctx, ptrs.as_ptr(), d, 1, table.as_slice().unwrap().as_ptr(), 1, 1,
+                            out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "tree_lut");
     out
 }
 

@@ -539,6 +539,117 @@ class Context:
                                                   C.c_size_t(self._tv_count(tv, lwe2.shape[0])), _hp(res)))
         return res
 
+    # -- rotation from a GLWE accumulator (include/tfhe_hip.h states the operation) --------------
+    def _glwe_acc_args(self, what, lwe_in, acc_in, rotation_offset, width):
+        """-> (lwe [batch][width], acc [acc_count][k+1][N], acc_count) after the checks the ABI cannot make on bare
+        pointers: it reads batch * width and acc_count * (k+1) * N words"""
+        p = self.params
+        if _is_torch(lwe_in) != _is_torch(acc_in):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: lwe_in and acc_in must both be numpy or both torch")
+        if _is_torch(lwe_in):
+            for name, t in (("lwe_in", lwe_in), ("acc_in", acc_in)):
+                if not t.is_cuda or not t.is_contiguous() or t.element_size() != 4 or t.is_floating_point():
+                    raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: {name} must be a contiguous 32-bit integer device tensor")
+            lwe = lwe_in
+            acc = acc_in if acc_in.dim() == 3 else acc_in.unsqueeze(0)
+        else:
+            lwe = _np(lwe_in)
+            lwe = lwe.reshape(-1, lwe.shape[-1])
+            acc = _np(acc_in)
+            acc = acc if acc.ndim == 3 else acc[None]
+        if len(lwe.shape) != 2 or lwe.shape[1] != width:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: lwe_in [batch][{width}] expected, got {tuple(lwe.shape)}")
+        batch = int(lwe.shape[0])
+        if len(acc.shape) != 3 or tuple(acc.shape[1:]) != (p.k + 1, p.N) or int(acc.shape[0]) not in (1, batch):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT,
+                            f"{what}: acc_in [1 or {batch}][{p.k + 1}][{p.N}] expected, got {tuple(acc.shape)}")
+        if not 0 <= int(rotation_offset) < 2 * p.N:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: rotation_offset must be in [0, 2N = {2 * p.N})")
+        return lwe, acc, int(acc.shape[0])
+
+    def blind_rotate_glwe(self, lwe_in, acc_in, rotation_offset: int = 0, out=None):
+        """Blind rotation that starts from GLWE ciphertext(s) acc_in [k+1][N] (shared) or [batch][k+1][N], words already
+        encoded: X^{-(b~ + rotation_offset)} acc_in, then the n CMUXes -> [batch][k+1][N].  numpy (blocks) or torch
+        device tensors (the context's stream)."""
+        p = self.params
+        lwe, acc, count = self._glwe_acc_args("blind_rotate_glwe", lwe_in, acc_in, rotation_offset, p.n + 1)
+        batch = int(lwe.shape[0])
+        if _is_torch(lwe):
+            self._bind_torch()
+            out = self._lookup_out("blind_rotate_glwe", out, (batch, p.k + 1, p.N), lwe)
+            self._check(lib().tfhe_blind_rotate_glwe_batch_device(self._h, _dp(lwe), C.c_size_t(batch), _dp(acc), C.c_size_t(count),
+                                                                  C.c_size_t(rotation_offset), _dp(out)))
+            return out
+        res = np.zeros((batch, p.k + 1, p.N), dtype=np.uint32)
+        self._check(lib().tfhe_blind_rotate_glwe_batch(self._h, _hp(lwe), C.c_size_t(batch), _hp(acc), C.c_size_t(count),
+                                                       C.c_size_t(rotation_offset), _hp(res)))
+        return res
+
+    def bootstrap_glwe(self, lwe_in, acc_in, rotation_offset: int = 0, out=None):
+        """blind_rotate_glwe + sample extraction at 0 + key switch, in the context's bootstrap order: [batch][io_dim+1]
+        -> [batch][io_dim+1].  With acc_in = encrypt_test_vector(..) and offset 0: a bootstrap with a secret table."""
+        lwe, acc, count = self._glwe_acc_args("bootstrap_glwe", lwe_in, acc_in, rotation_offset, self.io_dim + 1)
+        batch = int(lwe.shape[0])
+        if _is_torch(lwe):
+            self._bind_torch()
+            out = self._lookup_out("bootstrap_glwe", out, (batch, self.io_dim + 1), lwe)
+            self._check(lib().tfhe_bootstrap_glwe_batch_device(self._h, _dp(lwe), C.c_size_t(batch), _dp(acc), C.c_size_t(count),
+                                                               C.c_size_t(rotation_offset), _dp(out)))
+            return out
+        res = np.zeros((batch, self.io_dim + 1), dtype=np.uint32)
+        self._check(lib().tfhe_bootstrap_glwe_batch(self._h, _hp(lwe), C.c_size_t(batch), _hp(acc), C.c_size_t(count),
+                                                    C.c_size_t(rotation_offset), _hp(res)))
+        return res
+
+    # -- tree LUT: a function of d digits of log_p bits (include/tfhe_hip.h states the operation) --
+    def reserve_tree_lut(self, max_batch: int, max_digits: int, max_tables: int = 1):
+        """size the workspace of the device form of tree_lut (a maximum: smaller calls fit); the header states the bytes"""
+        self._check(lib().tfhe_context_reserve_tree_lut(self._h, C.c_size_t(max_batch), C.c_size_t(max_digits),
+                                                        C.c_size_t(max_tables)))
+
+    def tree_lut(self, digits, table, out=None):
+        """T[sum_t x_t B^t] of d encrypted digits, B = 2^log_p: digits is a sequence of d arrays [batch][io_dim+1]
+        (digit 0 least significant), table [1 or batch][tables][B^d] (or [tables][B^d] / [B^d]: shared) of un-encoded
+        values < B -> LWE [batch][tables][io_dim+1].  Needs the bootstrapping key and a packing key from the flattened
+        GLWE key.  numpy (host form: reserves for itself, blocks) or torch device tensors (reserve_tree_lut first)."""
+        p = self.params
+        d = len(digits)
+        if d < 1 or d * p.log_p > 16:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"tree_lut: 1 <= d and d * log_p <= 16 expected, got d = {d}")
+        dev = _is_torch(digits[0])
+        if any(_is_torch(x) != dev for x in list(digits) + [table]):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "tree_lut: digits and table must all be numpy or all torch")
+        if not dev:
+            digits, table = [_np(x) for x in digits], _np(table)
+        while len(table.shape) < 3:
+            table = table.unsqueeze(0) if dev else table[None]
+        batch = int(digits[0].shape[0]) if len(digits[0].shape) == 2 else -1
+        width = self.io_dim + 1
+        for x in digits:
+            if tuple(x.shape) != (batch, width) or (dev and (not x.is_cuda or not x.is_contiguous() or x.element_size() != 4
+                                                               or x.is_floating_point())):
+                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"tree_lut: every digit must be a contiguous 32-bit [batch][{width}] array")
+        sets, tables = int(table.shape[0]), int(table.shape[1])
+        if len(table.shape) != 3 or sets not in (1, batch) or int(table.shape[2]) != 1 << (p.log_p * d) or \
+                (dev and (not table.is_cuda or not table.is_contiguous() or table.element_size() != 4 or table.is_floating_point())):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT,
+                            f"tree_lut: table [1 or {batch}][tables][{1 << (p.log_p * d)}] of 32-bit integers expected, got {tuple(table.shape)}")
+        ptrs = (_u32p * d)()
+        if dev:
+            self._bind_torch()
+            for i, x in enumerate(digits):
+                ptrs[i] = _dp(x)
+            out = self._lookup_out("tree_lut", out, (batch, tables, width), digits[0])
+            self._check(lib().tfhe_tree_lut_batch_device(self._h, ptrs, C.c_size_t(d), C.c_size_t(batch), _dp(table),
+                                                         C.c_size_t(sets), C.c_size_t(tables), _dp(out)))
+            return out
+        for i, x in enumerate(digits):
+            ptrs[i] = _hp(x)
+        res = np.zeros((batch, tables, width), dtype=np.uint32)
+        self._check(lib().tfhe_tree_lut_batch(self._h, ptrs, C.c_size_t(d), C.c_size_t(batch), _hp(table), C.c_size_t(sets),
+                                              C.c_size_t(tables), _hp(res)))
+        return res
+
     def sample_extract(self, glwe, sample_index: int = 0) -> np.ndarray:
         p = self.params
         g = _np(glwe).reshape(-1, p.k + 1, p.N)
@@ -1087,6 +1198,18 @@ class Context:
         samples = rng.integers(0, 1 << 32, size=shape, dtype=np.uint64).astype(np.uint32)
         samples[:, :, p.k, :] = self._noise(rng, p.glwe_std_dev, (shape[0], p.R, p.N))
         return self.ggsw_encrypt(glwe_sk, bits, samples).reshape(addr.size, depth, p.R, p.k + 1, p.N)
+
+    def encrypt_test_vector(self, glwe_sk, lut, rng=None) -> np.ndarray:
+        """GLWE encryption under glwe_sk (glwe_std_dev) of the ENCODED construct_test_from_lut(lut), lut of 2^log_p
+        values < 2^log_p -> [k+1][N]: the accumulator of bootstrap_glwe / blind_rotate_glwe with rotation_offset 0, so
+        that the server bootstraps against a table it cannot read.  Masks and errors come from the OS CSPRNG unless the
+        test hook `rng=` is given (see generate_keys)."""
+        p = self.params
+        rng = rng if rng is not None else SystemRng()
+        tv = construct_test_from_lut(p, lut)
+        samples = rng.integers(0, 1 << 32, size=(1, p.k + 1, p.N), dtype=np.uint64).astype(np.uint32)
+        samples[0, p.k] = self._noise(rng, p.glwe_std_dev, p.N) + (tv << np.uint32(32 - p.log_p - p.padding_bits))
+        return self.glwe_encrypt_zero(glwe_sk, samples)[0]
 
     def encrypt_bits(self, lwe_sk, messages, rng=None) -> np.ndarray:
         """LweCleartext::encode_message + encrypt_lwe_plaintext (lwe.rs:81-92,138-160) for a batch

@@ -132,20 +132,33 @@ using tfhe::host::io_words;
 
 // the blind rotation the loaded key calls for: bootstrapping.rs:79-105, or the unrolled loop of
 // notes/BMMP Bootstrapping.md with a BMMP key
+// Where a rotation's accumulator starts: the clear test vector(s) tv [tv_count][N], or (glwe) the GLWE ciphertext(s)
+// tv [tv_count][k+1][N], already encoded, rotated by `offset` more (PbsParams::acc_glwe / acc_offset; not with a BMMP key:
+// the entry points refuse that before they get here)
+struct AccSource {
+  bool glwe = false;
+  u32 offset = 0;
+  u32* state = nullptr;  // [batch][k+1][N] for the segments' accumulators instead of the context's workspace (tree LUT)
+};
+
 hipError_t enqueue_blind_rotate(tfhe_context* ctx, const u32* lwe_in, size_t batch, const u32* tv,
-                                size_t tv_count, u32* glwe_out, u32* lwe_extracted) {
+                                size_t tv_count, u32* glwe_out, u32* lwe_extracted, AccSource from = AccSource()) {
   if (ctx->bmmp)
     return launch::blind_rotate_bmmp(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, lwe_in, batch, tv,
                                      tv_count == 1 ? 0 : ctx->N, ctx->d_bsk, glwe_out, lwe_extracted);
   // accumulators between the launches of a segmented rotation: the caller's output, or the workspace (sized by reserve)
-  u32* state = glwe_out ? glwe_out : (batch <= ctx->ws_batch ? ctx->d_glwe_c : nullptr);
-  return launch::blind_rotate(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, lwe_in, batch, tv, tv_count == 1 ? 0 : ctx->N,
+  u32* state = glwe_out ? glwe_out : from.state ? from.state : (batch <= ctx->ws_batch ? ctx->d_glwe_c : nullptr);
+  PbsParams P = ctx->pbs;
+  P.acc_glwe = from.glwe ? 1u : 0u;
+  P.acc_offset = from.offset;
+  const size_t tv_words = from.glwe ? (size_t)(ctx->params.glwe_dimension + 1) * ctx->N : (size_t)ctx->N;
+  return launch::blind_rotate(ctx->stream, ctx->field, P, ctx->d_tw, lwe_in, batch, tv, tv_count == 1 ? 0 : tv_words,
                               ctx->d_bsk, glwe_out, lwe_extracted, state, &ctx->side, ctx->shape);
 }
 
 // d_lwe_big: [batch][k*N+1] scratch of the reference order (unused when the key switch comes first)
 int enqueue_bootstrap(tfhe_context* ctx, const u32* d_lwe_in, size_t batch, const u32* d_tv,
-                      size_t tv_count, u32* d_lwe_big, u32* d_lwe_out) {
+                      size_t tv_count, u32* d_lwe_big, u32* d_lwe_out, AccSource from = AccSource()) {
   const u32* br_in = d_lwe_in;
   u32* br_out = d_lwe_big;
   if (ctx->timing) {  // next slot of the ring
@@ -162,7 +175,7 @@ int enqueue_bootstrap(tfhe_context* ctx, const u32* d_lwe_in, size_t batch, cons
     br_out = d_lwe_out;
   }
   if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-  HIP_TRY(ctx, enqueue_blind_rotate(ctx, br_in, batch, d_tv, tv_count, nullptr, br_out));
+  HIP_TRY(ctx, enqueue_blind_rotate(ctx, br_in, batch, d_tv, tv_count, nullptr, br_out, from));
   if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
   if (!ctx->ks_first) {
     if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
@@ -472,7 +485,7 @@ void tfhe_context_destroy(tfhe_context* ctx) {
   void* ptrs[] = {ctx->d_queue,  ctx->d_tw,     ctx->d_bsk,    ctx->d_ksk,    ctx->d_lwe_in, ctx->d_lwe_in2,
                   ctx->d_lwe_big, ctx->d_lwe_out, ctx->d_lwe_ks, ctx->d_glwe_a, ctx->d_glwe_b, ctx->d_glwe_c,
                   ctx->d_tv,     ctx->d_misc,   ctx->d_ggsw_tmp, ctx->d_ggsw_raw,
-                  ctx->d_key_tmp, ctx->d_pksk, ctx->d_pack_cols, ctx->d_lookup_ws};
+                  ctx->d_key_tmp, ctx->d_pksk, ctx->d_pack_cols, ctx->d_lookup_ws, ctx->d_tree_ws};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& g : ctx->gate_tvs)
@@ -822,6 +835,84 @@ int tfhe_blind_rotate_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t ba
   if ((st = tfhe_blind_rotate_batch_device(ctx, ctx->d_lwe_in, batch, ctx->d_tv, tv_count, ctx->d_glwe_a)))
     return st;
   HIP_TRY(ctx, hipMemcpyAsync(glwe_out, ctx->d_glwe_a, batch * glwe * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return TFHE_OK;
+}
+
+// ------------------------------------------------- blind rotation / bootstrap from a GLWE accumulator
+namespace {
+int check_glwe_acc_args(tfhe_context* ctx, const void* lwe_in, const void* acc_in, const void* out, size_t batch,
+                        size_t acc_count, size_t rotation_offset) {
+  if (!lwe_in || !acc_in || !out) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  if (batch == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "empty batch");
+  if (batch > kMaxBatch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "batch exceeds 2^31 - 1 (one workgroup per sample)");
+  if (acc_count != 1 && acc_count != batch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "acc_count must be 1 or batch");
+  if (rotation_offset >= 2 * (size_t)ctx->N)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "rotation_offset must be below 2N = " + std::to_string(2 * (size_t)ctx->N));
+  if (!ctx->have_key) return fail(ctx, TFHE_ERR_NO_KEY, "load the bootstrapping key first");
+  if (ctx->bmmp)
+    return fail(ctx, TFHE_ERR_UNSUPPORTED,
+                "a BMMP key is loaded: the unrolled rotation starts from a clear test vector only (load a plain "
+                "bootstrapping key for a GLWE accumulator)");
+  return TFHE_OK;
+}
+}  // namespace
+
+int tfhe_blind_rotate_glwe_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, const uint32_t* acc_in,
+                                        size_t acc_count, size_t rotation_offset, uint32_t* glwe_out) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  if ((st = check_glwe_acc_args(ctx, lwe_in, acc_in, glwe_out, batch, acc_count, rotation_offset))) return st;
+  if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+  HIP_TRY(ctx, enqueue_blind_rotate(ctx, lwe_in, batch, acc_in, acc_count, glwe_out, nullptr, AccSource{true, (u32)rotation_offset}));
+  if (ctx->timing) {
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    ctx->ev_valid_br = true;
+    ctx->ev_valid_ks = false;
+  }
+  return TFHE_OK;
+}
+
+int tfhe_blind_rotate_glwe_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, const uint32_t* acc_in,
+                                 size_t acc_count, size_t rotation_offset, uint32_t* glwe_out) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  if ((st = check_glwe_acc_args(ctx, lwe_in, acc_in, glwe_out, batch, acc_count, rotation_offset))) return st;
+  if ((st = reserve(ctx, batch))) return st;
+  const size_t n1 = (size_t)ctx->params.lwe_dimension + 1;
+  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_lwe_in, lwe_in, batch * n1 * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_glwe_a, acc_in, acc_count * glwe * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
+  if ((st = tfhe_blind_rotate_glwe_batch_device(ctx, ctx->d_lwe_in, batch, ctx->d_glwe_a, acc_count, rotation_offset, ctx->d_glwe_b)))
+    return st;
+  HIP_TRY(ctx, hipMemcpyAsync(glwe_out, ctx->d_glwe_b, batch * glwe * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return TFHE_OK;
+}
+
+int tfhe_bootstrap_glwe_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, const uint32_t* acc_in,
+                                     size_t acc_count, size_t rotation_offset, uint32_t* lwe_out) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  if ((st = check_glwe_acc_args(ctx, lwe_in, acc_in, lwe_out, batch, acc_count, rotation_offset))) return st;
+  if ((st = reserve(ctx, batch))) return st;
+  return enqueue_bootstrap(ctx, lwe_in, batch, acc_in, acc_count, ctx->d_lwe_big, lwe_out, AccSource{true, (u32)rotation_offset});
+}
+
+int tfhe_bootstrap_glwe_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, const uint32_t* acc_in,
+                              size_t acc_count, size_t rotation_offset, uint32_t* lwe_out) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  if ((st = check_glwe_acc_args(ctx, lwe_in, acc_in, lwe_out, batch, acc_count, rotation_offset))) return st;
+  if ((st = reserve(ctx, batch))) return st;
+  const size_t n1 = io_words(ctx);
+  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_lwe_in, lwe_in, batch * n1 * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_glwe_a, acc_in, acc_count * glwe * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
+  if ((st = enqueue_bootstrap(ctx, ctx->d_lwe_in, batch, ctx->d_glwe_a, acc_count, ctx->d_lwe_big, ctx->d_lwe_out,
+                              AccSource{true, (u32)rotation_offset})))
+    return st;
+  HIP_TRY(ctx, hipMemcpyAsync(lwe_out, ctx->d_lwe_out, batch * n1 * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return TFHE_OK;
 }
@@ -1841,6 +1932,184 @@ int tfhe_pack_lwe_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t groups
   HIP_TRY(ctx, hipMemcpyAsync(d_in, lwe_in, in_words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
   if ((st = tfhe_pack_lwe_batch_device(ctx, d_in, groups, per_group, d_out))) return st;
   HIP_TRY(ctx, hipMemcpyAsync(glwe_out, d_out, out_words * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return TFHE_OK;
+}
+
+// ---------------------------------------------------------------------------------- tree LUT
+// tfhe_hip.h states the operation.  Level t is ONE rotation call over all rows x tables x sub-tables and one packing
+// call (in the chunks the packing workspace holds, like tfhe_pack_lwe_batch_device); the only host loop is the one over
+// the d levels.
+//
+// How the rotations of a level share a row's digit and -- at level 0 -- a (set, table)'s test vectors: EXPANDED BUFFERS
+// in the reserved workspace, not an index map.  The rotate kernels address sample r's inputs at r * stride; an index map
+// would be one more argument (and one more dependent load before the first CMUX) in every rotate kernel, team, pair and
+// wide -- the kernels whose loops this feature promises to leave alone.  The copies are n + 1 + N words per rotation,
+// about what a rotation writes back (k N + 1 words), written by two small kernels per call.
+namespace {
+
+constexpr size_t kTreeLutMaxBits = 16;  // d * log_p: the table has at most 2^16 entries per (set, table)
+
+struct TreeLutLayout {
+  size_t rotations = 0;  // level 0: batch * tables * B^(d-1)
+  size_t ks_digit = 0, lwe = 0, tv = 0, state = 0, res_a = 0, res_b = 0, glwe = 0;  // offsets in words
+  size_t words = 0;
+};
+
+// false: the sizes overflow / the first level does not fit one grid
+bool tree_lut_layout(const tfhe_context* ctx, size_t batch, size_t digits, size_t tables, TreeLutLayout* L) {
+  const u32 log_p = ctx->params.log_p;
+  const double r0 = (double)batch * (double)tables * std::ldexp(1.0, (int)(log_p * (digits - 1)));
+  if (r0 > (double)kMaxBatch) return false;
+  const size_t R0 = batch * tables << (log_p * (digits - 1));
+  const size_t G1 = digits > 1 ? R0 >> log_p : 0;
+  const size_t n1 = (size_t)ctx->params.lwe_dimension + 1, big1 = (size_t)ctx->big_n + 1;
+  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
+  auto pad = [](size_t w) { return (w + 3) & ~(size_t)3; };  // 16-byte buffers
+  size_t at = 0;
+  auto take = [&](size_t w) { const size_t o = at; at += pad(w); return o; };
+  L->rotations = R0;
+  L->ks_digit = take(batch * n1);  // reserved for either bootstrap order
+  L->lwe = take(R0 * n1);
+  L->tv = take(R0 * ctx->N);
+  L->state = take(R0 * glwe);
+  L->res_a = take(R0 * big1);
+  L->res_b = take(G1 * big1);
+  L->glwe = take(G1 * glwe);
+  L->words = at;
+  return true;
+}
+
+int check_tree_lut_shape(tfhe_context* ctx, size_t batch, size_t digits, size_t tables, TreeLutLayout* L) {
+  const u32 log_p = ctx->params.log_p;
+  if (batch == 0 || tables == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "batch and tables must be at least 1");
+  if (log_p == 0 || log_p >= ctx->pbs.log_n)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "the tree LUT needs 1 <= log_p < log2 N (at least two coefficients per value)");
+  const size_t max_digits = kTreeLutMaxBits / log_p;
+  if (digits == 0 || digits > max_digits)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "digits must be in [1, " + std::to_string(max_digits) + "]: d * log_p <= " + std::to_string(kTreeLutMaxBits));
+  if (batch > kMaxBatch || tables > kMaxBatch || !tree_lut_layout(ctx, batch, digits, tables, L))
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "batch * tables * B^(d-1) rotations exceed 2^31 - 1 (one workgroup per sample)");
+  return TFHE_OK;
+}
+
+int check_tree_lut_keys(tfhe_context* ctx) {
+  if (!ctx->have_key) return fail(ctx, TFHE_ERR_NO_KEY, "load the bootstrapping key first");
+  if (!ctx->have_pksk) return fail(ctx, TFHE_ERR_NO_KEY, "load a packing key first (tfhe_load_packing_key, from the flattened GLWE key)");
+  if (ctx->pksk_dim != ctx->big_n)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "the packing key packs from dimension " + std::to_string(ctx->pksk_dim) + ", the tree LUT packs sample extractions: k N = " +
+                    std::to_string(ctx->big_n));
+  if (ctx->bmmp)
+    return fail(ctx, TFHE_ERR_UNSUPPORTED, "a BMMP key is loaded: the upper levels rotate a GLWE accumulator, which the unrolled rotation does not do");
+  return TFHE_OK;
+}
+
+}  // namespace
+
+int tfhe_context_reserve_tree_lut(tfhe_context* ctx, size_t max_batch, size_t max_digits, size_t max_tables) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  TreeLutLayout L;
+  if ((st = check_tree_lut_shape(ctx, max_batch, max_digits, max_tables, &L))) return st;
+  if (L.words <= ctx->tree_ws_words) return TFHE_OK;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return ensure(ctx, &ctx->d_tree_ws, &ctx->tree_ws_words, L.words);
+}
+
+int tfhe_tree_lut_batch_device(tfhe_context* ctx, const uint32_t* const* digits, size_t d, size_t batch, const uint32_t* table,
+                               size_t table_sets, size_t tables, uint32_t* lwe_out) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  if (!digits || !table || !lwe_out) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  TreeLutLayout L;
+  if ((st = check_tree_lut_shape(ctx, batch, d, tables, &L))) return st;
+  for (size_t t = 0; t < d; ++t)
+    if (!digits[t]) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null digit pointer");
+  if (table_sets != 1 && table_sets != batch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "table_sets must be 1 or batch");
+  if ((st = check_tree_lut_keys(ctx))) return st;
+  if (L.words > ctx->tree_ws_words)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "the call needs " + std::to_string(L.words * sizeof(u32)) + " bytes of tree-LUT workspace, " +
+                    std::to_string(ctx->tree_ws_words * sizeof(u32)) + " are reserved (tfhe_context_reserve_tree_lut)");
+  const u32 log_p = ctx->params.log_p, log_n = ctx->pbs.log_n, n = ctx->params.lwe_dimension;
+  const u32 log_rep = log_n - log_p;
+  const size_t n1 = (size_t)n + 1, big1 = (size_t)ctx->big_n + 1;
+  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
+  u32* ws = ctx->d_tree_ws;
+  u32 *ks_digit = ws + L.ks_digit, *lwe = ws + L.lwe, *tv = ws + L.tv, *state = ws + L.state, *glwes = ws + L.glwe;
+  u32* results[2] = {ws + L.res_a, ws + L.res_b};
+  hipStream_t s = ctx->stream;
+  // the digit a level rotates by, [batch][n+1]: key-switched first in the KS-first order
+  auto digit_of = [&](size_t t, const u32** out) -> int {
+    *out = digits[t];
+    if (!ctx->ks_first) return TFHE_OK;
+    HIP_TRY(ctx, launch::key_switch(s, ctx->ks, ctx->big_n, n, digits[t], batch, ctx->d_ksk, ks_digit));
+    *out = ks_digit;
+    return TFHE_OK;
+  };
+  // level 0: rotation (row, table, h) bootstraps c_0[row] against sub-table h of (set, table)
+  size_t count = L.rotations;
+  const u32* digit = nullptr;
+  if ((st = digit_of(0, &digit))) return st;
+  HIP_TRY(ctx, launch::tree_lut_expand(s, digit, count, count / batch, (u32)n1, lwe));
+  HIP_TRY(ctx, launch::tree_lut_test_vectors(s, table, table_sets == 1 ? 0 : tables << (log_p * d), count, count / batch, log_p, log_n, tv));
+  u32* cur = d == 1 && ctx->ks_first ? lwe_out : results[0];
+  HIP_TRY(ctx, enqueue_blind_rotate(ctx, lwe, count, tv, count, nullptr, cur, AccSource{false, 0u, state}));
+  // the packing decomposer (tfhe_pack_lwe_batch_device)
+  PbsParams PK = ctx->pbs;
+  PK.log_base = ctx->ks.log_base;
+  PK.levels = ctx->ks.levels;
+  PK.ignored_bits = ctx->ks.ignored_bits;
+  PK.first_shift = ctx->ks.first_shift;
+  const size_t chunk = ctx->pack_cols_words / pack_cols_words_per_group(ctx);  // >= 1 by construction
+  for (size_t t = 1; t < d; ++t) {
+    // G_h = Pack of the B results [h B, (h + 1) B), each on N / B neighbouring coefficients
+    const size_t groups = count >> log_p;
+    HIP_TRY(ctx, hipMemsetAsync(glwes, 0, groups * glwe * sizeof(u32), s));
+    for (size_t g0 = 0; g0 < groups; g0 += chunk) {
+      const size_t here = std::min(chunk, groups - g0);
+      HIP_TRY(ctx, launch::pack_transpose(s, cur + (g0 << log_p) * big1, here, 1u << log_p, ctx->big_n, log_n, ctx->d_pack_cols, log_rep));
+      HIP_TRY(ctx, launch::pack_lwe(s, ctx->field, PK, ctx->d_tw, ctx->d_pksk, ctx->d_pack_cols, ctx->big_n, here, glwes + g0 * glwe));
+    }
+    if ((st = digit_of(t, &digit))) return st;
+    HIP_TRY(ctx, launch::tree_lut_expand(s, digit, groups, groups / batch, (u32)n1, lwe));
+    u32* next = t + 1 == d && ctx->ks_first ? lwe_out : results[t & 1];
+    HIP_TRY(ctx, enqueue_blind_rotate(ctx, lwe, groups, glwes, groups, nullptr, next, AccSource{true, (1u << log_rep) >> 1, state}));
+    cur = next;
+    count = groups;
+  }
+  if (!ctx->ks_first) HIP_TRY(ctx, launch::key_switch(s, ctx->ks, ctx->big_n, n, cur, count, ctx->d_ksk, lwe_out));
+  return TFHE_OK;
+}
+
+int tfhe_tree_lut_batch(tfhe_context* ctx, const uint32_t* const* digits, size_t d, size_t batch, const uint32_t* table,
+                        size_t table_sets, size_t tables, uint32_t* lwe_out) {
+  int st = check_ctx(ctx);
+  if (st) return st;
+  if (!digits || !table || !lwe_out) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  TreeLutLayout L;
+  if ((st = check_tree_lut_shape(ctx, batch, d, tables, &L))) return st;
+  for (size_t t = 0; t < d; ++t)
+    if (!digits[t]) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null digit pointer");
+  if (table_sets != 1 && table_sets != batch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "table_sets must be 1 or batch");
+  if ((st = check_tree_lut_keys(ctx))) return st;
+  if ((st = tfhe_context_reserve_tree_lut(ctx, batch, d, tables))) return st;
+  const size_t io = io_words(ctx);
+  const size_t digit_words = batch * io, table_words = table_sets * tables << (ctx->params.log_p * d), out_words = batch * tables * io;
+  if ((st = ensure_misc(ctx, (d * digit_words + table_words + out_words) * sizeof(u32)))) return st;
+  u32* d_digits = reinterpret_cast<u32*>(ctx->d_misc);
+  u32* d_table = d_digits + d * digit_words;
+  u32* d_out = d_table + table_words;
+  std::vector<const uint32_t*> ptrs(d);
+  for (size_t t = 0; t < d; ++t) {
+    HIP_TRY(ctx, hipMemcpyAsync(d_digits + t * digit_words, digits[t], digit_words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
+    ptrs[t] = d_digits + t * digit_words;
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(d_table, table, table_words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
+  if ((st = tfhe_tree_lut_batch_device(ctx, ptrs.data(), d, batch, d_table, table_sets, tables, d_out))) return st;
+  HIP_TRY(ctx, hipMemcpyAsync(lwe_out, d_out, out_words * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return TFHE_OK;
 }

@@ -42,6 +42,9 @@ struct tfhe_context {
   u32* d_lookup_ws = nullptr;
   size_t lookup_ws_words = 0;
   unsigned lookup_height = 0; // subtree height a team reduces (tfhe_context_set_lookup_subtree_height); 0: automatic
+  // tree LUT (tfhe_context_reserve_tree_lut): per-rotation inputs, segment state, the levels' results and packed GLWEs
+  u32* d_tree_ws = nullptr;
+  size_t tree_ws_words = 0;
   bool aligned = false;       // decomposer alignment (tfhe_context_set_decomposer_alignment)
   bool ks_first = false;      // bootstrap order (tfhe_context_set_bootstrap_order)
   int shape = 0;              // kernel shape of the blind rotation (tfhe_context_set_kernel_shape): launch::kShape*

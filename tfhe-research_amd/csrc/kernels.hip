@@ -691,8 +691,10 @@ external_product_kernel(PbsParams P, const typename F::elem* __restrict__ tw,
 // wave instruction; wrapping addition is associative and commutative, so the bits do not depend on the order the
 // teams arrive in.  Run 0 of an output also contributes the body row.
 constexpr int kPackTile = 32;
+// log_rep > 0 (the tree LUT's replicated layout): column j holds ciphertext j >> log_rep of the group, so that each of
+// the m = N >> log_rep inputs fills 2^log_rep neighbouring coefficients -- the N-fold list is never written out.
 __global__ void __launch_bounds__(256) pack_transpose_kernel(const u32* __restrict__ lwe_in, size_t groups, u32 m, u32 d,
-                                                             u32 log_n, u32* __restrict__ cols) {
+                                                             u32 log_n, u32* __restrict__ cols, u32 log_rep) {
   __shared__ u32 tile[kPackTile][kPackTile + 1];
   const u32 N = 1u << log_n;
   const u32 width = d + 1;
@@ -703,7 +705,7 @@ __global__ void __launch_bounds__(256) pack_transpose_kernel(const u32* __restri
     u32* out = cols + g * (size_t)width * N;
 #pragma unroll
     for (u32 t = 0; t < kPackTile; t += 8) {
-      const u32 j = j0 + ty + t, i = i0 + tx;
+      const u32 j = (j0 + ty + t) >> log_rep, i = i0 + tx;
       tile[ty + t][tx] = (j < m && i < width) ? in[(size_t)j * width + i] : 0u;
     }
     __syncthreads();
@@ -713,6 +715,39 @@ __global__ void __launch_bounds__(256) pack_transpose_kernel(const u32* __restri
       if (i < width) out[(size_t)i * N + j] = tile[tx][ty + t];
     }
     __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------------------ tree LUT: the rotations' inputs
+// The rotate kernels address sample r's ciphertext and test vector at r * stride: rotation r = (row, table, sub-table) of
+// a tree-LUT level gets its own copy of the row's digit and -- at level 0 -- its own test vector, in the reserved
+// workspace (capi.cpp::tfhe_tree_lut_batch_device).  One workgroup per rotation, grid-strided.
+//
+// tree_lut_expand_kernel: out [rows * per_row][words], out[r] = in[r / per_row]
+__global__ void __launch_bounds__(256) tree_lut_expand_kernel(const u32* __restrict__ in, size_t count, size_t per_row, u32 words,
+                                                              u32* __restrict__ out) {
+  for (size_t r = blockIdx.x; r < count; r += gridDim.x) {
+    const u32* src = in + (r / per_row) * words;
+    u32* dst = out + r * words;
+    for (u32 i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
+  }
+}
+// tree_lut_test_vectors_kernel: tv [rows][tables][subs][N], tv[row][t][h] = construct_test_from_lut(T[set][t][h B .. h B + B))
+// (test_vector.rs:38-67: every value `rep` = N / B times, the first rep / 2 negated mod B, rotated left by rep / 2), B = 2^log_p,
+// T = table + row * set_stride (0: one shared set), un-encoded like every clear test vector
+__global__ void __launch_bounds__(256) tree_lut_test_vectors_kernel(const u32* __restrict__ table, size_t set_stride, size_t count,
+                                                                    size_t per_row /* tables * subs */, u32 log_p, u32 log_n,
+                                                                    u32* __restrict__ tv) {
+  const u32 N = 1u << log_n, log_rep = log_n - log_p, mid = (1u << log_rep) >> 1;
+  for (size_t r = blockIdx.x; r < count; r += gridDim.x) {
+    const u32* lut = table + (r / per_row) * set_stride + ((r % per_row) << log_p);
+    u32* dst = tv + r * N;
+    for (u32 i = threadIdx.x; i < N; i += blockDim.x) {
+      const u32 idx = (i + mid) & (N - 1u);
+      u32 val = lut[idx >> log_rep];
+      if (idx < mid && val != 0u) val = (1u << log_p) - val;
+      dst[i] = val;
+    }
   }
 }
 
@@ -1823,10 +1858,24 @@ hipError_t external_product(hipStream_t s, int field, const PbsParams& P, const 
                                                            ct1_inout, cmux_ct0, batch, glwe_out, queue))));
 }
 
-hipError_t pack_transpose(hipStream_t s, const u32* lwe_in, size_t groups, u32 per_group, u32 d, u32 log_n, u32* cols) {
+hipError_t pack_transpose(hipStream_t s, const u32* lwe_in, size_t groups, u32 per_group, u32 d, u32 log_n, u32* cols,
+                          u32 log_rep) {
   const unsigned gz = (unsigned)(groups < 65535u ? groups : 65535u);
   dim3 grid((d + 1 + kPackTile - 1) / kPackTile, (1u << log_n) / kPackTile, gz);
-  hipLaunchKernelGGL(pack_transpose_kernel, grid, dim3(256), 0, s, lwe_in, groups, per_group, d, log_n, cols);
+  hipLaunchKernelGGL(pack_transpose_kernel, grid, dim3(256), 0, s, lwe_in, groups, per_group, d, log_n, cols, log_rep);
+  return hipGetLastError();
+}
+
+hipError_t tree_lut_expand(hipStream_t s, const u32* in, size_t count, size_t per_row, u32 words, u32* out) {
+  const unsigned grid = (unsigned)(count < ((size_t)1 << 20) ? count : (size_t)1 << 20);
+  hipLaunchKernelGGL(tree_lut_expand_kernel, dim3(grid), dim3(256), 0, s, in, count, per_row, words, out);
+  return hipGetLastError();
+}
+
+hipError_t tree_lut_test_vectors(hipStream_t s, const u32* table, size_t set_stride, size_t count, size_t per_row, u32 log_p,
+                                 u32 log_n, u32* tv) {
+  const unsigned grid = (unsigned)(count < ((size_t)1 << 20) ? count : (size_t)1 << 20);
+  hipLaunchKernelGGL(tree_lut_test_vectors_kernel, dim3(grid), dim3(256), 0, s, table, set_stride, count, per_row, log_p, log_n, tv);
   return hipGetLastError();
 }
 

@@ -86,7 +86,10 @@ hipError_t key_switch(hipStream_t s, const KsParams& K, u32 big_n, u32 n, const 
 
 // ---- packing key switch (pbs_wave.h::pack_lwe_team): `groups` outputs of up to N LWE ciphertexts of dimension d each
 // cols [groups][d+1][N] = the transposed ciphertexts of lwe_in [groups][per_group][d+1], zero above per_group
-hipError_t pack_transpose(hipStream_t s, const u32* lwe_in, size_t groups, u32 per_group, u32 d, u32 log_n, u32* cols);
+// log_rep > 0: the replicated layout of the tree LUT -- lwe_in [groups][per_group][d+1] with per_group = N >> log_rep,
+// cols[g][i][j] = lwe_in[g][j >> log_rep][i] (the same bits as the plain transpose of the materialised N-fold list)
+hipError_t pack_transpose(hipStream_t s, const u32* lwe_in, size_t groups, u32 per_group, u32 d, u32 log_n, u32* cols,
+                          u32 log_rep = 0);
 // glwe_out [groups][k+1][N] (ZEROED by the caller, on s) += the packed ciphertexts.  P: log_n, k and the KS decomposer
 // in log_base / levels / ignored_bits / first_shift; key: the packing key prepared by bsk_prepare(.., k, ..) as
 // ceil(d / (k+1)) GGSW-shaped slices of (k+1) l_ks rows (rows past d l_ks zero-filled)
@@ -94,6 +97,14 @@ hipError_t pack_lwe(hipStream_t s, int field, const PbsParams& P, const void* tw
                     size_t groups, u32* glwe_out);
 // pksk [rows][k+1][N]: body coefficient 0 of row r += factor[r]
 hipError_t packing_add_gadget(hipStream_t s, u32* pksk, size_t rows, u32 k, u32 log_n, const u32* factor);
+
+// ---- tree LUT (capi.cpp::tfhe_tree_lut_batch_device): the per-rotation inputs of a level, in the reserved workspace
+// out [count][words], out[r] = in[r / per_row]: rotation r's copy of its row's digit
+hipError_t tree_lut_expand(hipStream_t s, const u32* in, size_t count, size_t per_row, u32 words, u32* out);
+// tv [count][N], tv[r] = construct_test_from_lut of the 2^log_p table entries at table + (r / per_row) * set_stride +
+// (r % per_row) * 2^log_p (set_stride 0: every row reads the one shared set); un-encoded
+hipError_t tree_lut_test_vectors(hipStream_t s, const u32* table, size_t set_stride, size_t count, size_t per_row, u32 log_p,
+                                 u32 log_n, u32* tv);
 
 // ---- CMUX tree / encrypted table lookup (pbs_wave.h::cmux_tree_team)
 // How a tree of `depth` levels over `trees` trees goes out (kernels.hip::lookup_plan_for); forced_height 0: automatic.

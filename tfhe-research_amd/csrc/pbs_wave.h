@@ -54,6 +54,12 @@ struct PbsParams {
   u32 levels;
   u32 ignored_bits;  // 32 - log_base*levels        (decomposer.rs:28)
   u32 first_shift;   // log_base * (floor(32/log_base) - levels): bit offset of the lowest kept limb
+  // Source of a blind rotation's initial accumulator, set per call by the entry point (0, 0: the clear test vector).
+  // acc_glwe = 1: the rotation starts from a GLWE ciphertext -- the kernels' `tv` argument then points at [K+1][N]
+  // already encoded words per sample (no tv_shift) and acc_0 = X^{(2N - b~ - acc_offset) mod 2N} * that ciphertext
+  // (rotate_init_fill below); acc_offset < 2N.
+  u32 acc_glwe = 0;
+  u32 acc_offset = 0;
 };
 
 struct KsParams {
@@ -589,6 +595,49 @@ TFHE_HD void pack_lwe_team(const Ctx& c, const PbsParams& P, const u32* masks_t,
 }
 
 // ---------------------------------------------------------------------------------------------
+// Initial accumulator of a blind rotation (bootstrapping.rs:67-78, and its GLWE-accumulator form): word j of
+// polynomial `me` of  X^m * source,  m = (2N - b~ - P.acc_offset) mod 2N = deg + N flip.  The source is the trivial
+// ciphertext (0, ..., 0, tv << tv_shift) or, with P.acc_glwe (team-uniform: a kernel argument), the K+1 polynomials at
+// `tv` as they are (no shift).  Negacyclic: coefficient j comes from index (j - deg) mod N, negated once for the wrap and once
+// for flip.
+// ---------------------------------------------------------------------------------------------
+struct RotateInit {
+  int deg;
+  u32 flip;
+};
+template <int LOGN>
+TFHE_HD RotateInit rotate_init(const PbsParams& P, u32 body) {
+  constexpr u32 N = 1u << LOGN;
+  const u32 b_tilde = switch_modulus_2n(body, LOGN);
+  const u32 m = (2u * N - b_tilde + 2u * N - P.acc_offset) & (2u * N - 1u);
+  return RotateInit{(int)(m & (N - 1)), (m >> LOGN) & 1u};
+}
+// word j of X^m * poly, poly's words shifted left by `shift` first
+template <int LOGN>
+TFHE_HD u32 rotate_init_word(const RotateInit& ri, const u32* poly, int j, u32 shift) {
+  constexpr int N = 1 << LOGN;
+  const u32 t = poly[(j - ri.deg) & (N - 1)] << shift;
+  return (ri.flip ^ (u32)(j < ri.deg)) ? (0u - t) : t;
+}
+// acc[index(r)] for r < COUNT: my polynomial `me` of the initial accumulator.  ONE team-uniform branch on the source
+// around the whole fill (P is a kernel argument), as cmux_tree_team branches on its step kind: no second copy of any
+// rotate kernel, and the clear-test-vector side is the fill as it was.  (Selecting the pointer and the shift instead of
+// branching was built and compared with tools/isa_report.py: it moved the register allocation of more kernels, not
+// fewer -- profiles/tree_lut_isa_resources.txt.)
+template <int LOGN, int K, int COUNT, class Index>
+TFHE_HD void rotate_init_fill(const PbsParams& P, const RotateInit& ri, const u32* tv, int me, u32* acc, Index index) {
+  constexpr int N = 1 << LOGN;
+  if (P.acc_glwe) {
+    const u32* mine = tv + (size_t)me * N;
+#pragma unroll
+    for (int r = 0; r < COUNT; ++r) acc[index(r)] = rotate_init_word<LOGN>(ri, mine, index(r), 0u);
+  } else {
+#pragma unroll
+    for (int r = 0; r < COUNT; ++r) acc[index(r)] = me == K ? rotate_init_word<LOGN>(ri, tv, index(r), P.tv_shift) : 0u;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Blind rotation of NS LWE samples (bootstrapping.rs:67-105 for each) by a team of K+1 groups of G waves.
 // Group c keeps polynomial c of sample s's accumulator in its LDS array c.acc(s) (N u32, natural order)
 // for all n iterations; on return it holds polynomial c of the final GLWE accumulator of sample s.
@@ -620,24 +669,13 @@ TFHE_HD void blind_rotate_team_multi(const Ctx& c, const PbsParams& P, const u32
       for (int r = 0; r < E; ++r) acc[r * T + lane] = from[r * T + lane];
     }
   } else {
-  // acc = X^{-b~} * (0, ..., 0, tv << tv_shift): only the body polynomial (wave K) is non-zero
+  // acc = X^{-b~} * (0, ..., 0, tv << tv_shift): only the body polynomial (wave K) is non-zero; or the rotated GLWE
+  // accumulator, all K+1 polynomials (rotate_init_fill)
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
     u32* acc = c.acc(s);
-    const u32 b_tilde = switch_modulus_2n(lwe[s][P.n], LOGN);
-    const u32 m = (2u * N - b_tilde) & (2u * N - 1u);
-    const int deg = (int)(m & (N - 1));
-    const u32 flip = (m >> LOGN) & 1u;
-#pragma unroll
-    for (int r = 0; r < E; ++r) {
-      const int j = r * T + lane;
-      u32 val = 0;
-      if (me == K) {
-        const u32 t = tv[s][(j - deg) & (N - 1)] << P.tv_shift;
-        val = (flip ^ (u32)(j < deg)) ? (0u - t) : t;
-      }
-      acc[j] = val;
-    }
+    const RotateInit ri = rotate_init<LOGN>(P, lwe[s][P.n]);
+    rotate_init_fill<LOGN, K, E>(P, ri, tv[s], me, acc, [&](int r) { return r * T + lane; });
   }
   }
   c.poly_sync();
@@ -908,21 +946,9 @@ TFHE_HD void blind_rotate_team_wide(const Ctx& c, const PbsParams& P, const u32*
 #pragma unroll
     for (int r = 0; r < EC / 2; ++r) acc[(r + q * (EC / 2)) * 64 + lane] = from[(r + q * (EC / 2)) * 64 + lane];
   } else {
-    // acc = X^{-b~} * (0, ..., 0, tv << tv_shift)
-    const u32 b_tilde = switch_modulus_2n(lwe[P.n], LOGN);
-    const u32 m = (2u * N - b_tilde) & (2u * N - 1u);
-    const int deg = (int)(m & (N - 1));
-    const u32 flip = (m >> LOGN) & 1u;
-#pragma unroll
-    for (int r = 0; r < EC / 2; ++r) {
-      const int j = (r + q * (EC / 2)) * 64 + lane;
-      u32 val = 0;
-      if (me == K) {
-        const u32 t = tv[(j - deg) & (N - 1)] << P.tv_shift;
-        val = (flip ^ (u32)(j < deg)) ? (0u - t) : t;
-      }
-      acc[j] = val;
-    }
+    // acc = X^{-b~} * (0, ..., 0, tv << tv_shift), or the rotated GLWE accumulator (rotate_init_fill)
+    const RotateInit ri = rotate_init<LOGN>(P, lwe[P.n]);
+    rotate_init_fill<LOGN, K, EC / 2>(P, ri, tv, me, acc, [&](int r) { return (r + q * (EC / 2)) * 64 + lane; });
   }
   c.team_sync();
 #pragma unroll 1
@@ -1075,21 +1101,9 @@ TFHE_HD void blind_rotate_pair(const Ctx& c, const PbsParams& P, const u32* lwe 
 #pragma unroll
     for (int r = 0; r < EC; ++r) acc[r * T + tid] = from[r * T + tid];
   } else {
-    // acc = X^{-b~} * (0, tv << tv_shift)
-    const u32 b_tilde = switch_modulus_2n(lwe[P.n], LOGN);
-    const u32 m = (2u * N - b_tilde) & (2u * N - 1u);
-    const int deg = (int)(m & (N - 1));
-    const u32 flip = (m >> LOGN) & 1u;
-#pragma unroll
-    for (int r = 0; r < EC; ++r) {
-      const int j = r * T + tid;
-      u32 val = 0;
-      if (me == K) {
-        const u32 t = tv[(j - deg) & (N - 1)] << P.tv_shift;
-        val = (flip ^ (u32)(j < deg)) ? (0u - t) : t;
-      }
-      acc[j] = val;
-    }
+    // acc = X^{-b~} * (0, tv << tv_shift), or the rotated GLWE accumulator (rotate_init_fill)
+    const RotateInit ri = rotate_init<LOGN>(P, lwe[P.n]);
+    rotate_init_fill<LOGN, K, EC>(P, ri, tv, me, acc, [&](int r) { return r * T + tid; });
   }
   c.wave_sync();
   const size_t ggsw_words = (size_t)(K + 1) * P.levels * (K + 1) * 2 * (N >> 1);  // elements
