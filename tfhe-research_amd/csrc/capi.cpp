@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <algorithm>
 #include <string>
@@ -17,8 +18,7 @@
 
 namespace {
 
-using tfhe::host::fail;
-using tfhe::host::hip_fail;
+using namespace tfhe::host;  // fail, hip_fail, the sizes
 
 // Bit just above the most significant limb: gadget factor of level i is 2^{top - log_base*(i+1)} and
 // the lowest kept limb starts at top - log_base*levels.  Literal (reference, decomposer.rs:48-70 /
@@ -55,7 +55,7 @@ int reserve(tfhe_context* ctx, size_t batch) {
   // every LWE buffer can hold either boundary dimension (n for the reference's PBS-then-KS order,
   // k*N for KS-then-PBS), so switching the order never reallocates
   const size_t n1 = std::max((size_t)ctx->params.lwe_dimension, (size_t)ctx->big_n) + 1;
-  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
+  const size_t glwe = glwe_words(ctx);
   u32** ptrs[] = {&ctx->d_lwe_in, &ctx->d_lwe_in2, &ctx->d_lwe_big, &ctx->d_lwe_out, &ctx->d_lwe_ks,
                   &ctx->d_glwe_a, &ctx->d_glwe_b,   &ctx->d_glwe_c,  &ctx->d_tv};
   const size_t sizes[] = {batch * n1, batch * n1, batch * n1, batch * n1, batch * n1,
@@ -98,6 +98,144 @@ int check_ctx(tfhe_context* ctx) {
   return TFHE_OK;
 }
 
+// every pointer there and the count not 0, or the refusal `what`
+int check_present(tfhe_context* ctx, std::initializer_list<const void*> ptrs, size_t count = 1,
+                  const char* what = "null pointer / empty batch") {
+  for (const void* p : ptrs)
+    if (!p) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, what);
+  if (count == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, what);
+  return TFHE_OK;
+}
+
+// The pointers, the batch and the 1-or-batch count (`count_name` in the refusal) of a batched family.  The rotations
+// and bootstraps name each failure and look at the grid limit first; the products (external product, CMUX) grew up with
+// one text for null / empty and the count first, and their host forms without the grid limit (a batch beyond it fails
+// in reserve()): a refusal's status, text and precedence are part of the ABI.
+enum BatchFamily { kRotations, kProducts, kHostProducts };
+
+int check_batch(tfhe_context* ctx, std::initializer_list<const void*> ptrs, size_t batch, size_t count,
+                const char* count_name, BatchFamily family = kRotations) {
+  const bool count_ok = count == 1 || count == batch;
+  const std::string bad_count = std::string(count_name) + " must be 1 or batch";
+  if (family != kRotations) {
+    TFHE_TRY(check_present(ctx, ptrs, batch));
+    if (!count_ok) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, bad_count);
+    if (family == kProducts && batch > kMaxBatch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "batch exceeds 2^31 - 1");
+    return TFHE_OK;
+  }
+  TFHE_TRY(check_present(ctx, ptrs, 1, "null pointer"));
+  if (batch == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "empty batch");
+  if (batch > kMaxBatch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "batch exceeds 2^31 - 1 (one workgroup per sample)");
+  if (!count_ok) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, bad_count);
+  return TFHE_OK;
+}
+
+// ---- staging of the host forms: copy in, the _device form, copy out, ONE synchronisation -- all on the context's stream
+int upload(tfhe_context* ctx, u32* dev, const void* host, size_t words) {
+  HIP_TRY(ctx, hipMemcpyAsync(dev, host, words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
+  return TFHE_OK;
+}
+
+int download(tfhe_context* ctx, void* host, const u32* dev, size_t words) {
+  HIP_TRY(ctx, hipMemcpyAsync(host, dev, words * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+  return TFHE_OK;
+}
+
+// how a host form ends: its result comes back and the stream drains
+int download_and_wait(tfhe_context* ctx, void* host, const u32* dev, size_t words) {
+  TFHE_TRY(download(ctx, host, dev, words));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return TFHE_OK;
+}
+
+// The small entry points stage in the context's scratch buffer (d_misc): segments of 32-bit words back to back, in the
+// order given, unpadded.  (The forms whose operands have a buffer in the reserve() workspace stage there instead.)
+class Staging {
+ public:
+  Staging(tfhe_context* ctx, std::vector<size_t> words) : ctx_(ctx), words_(std::move(words)) {}
+  // grows the scratch buffer if the segments need it (ensure_misc: synchronises only then); call first
+  int reserve() {
+    size_t total = 0;
+    for (size_t w : words_) total += w;
+    return ensure_misc(ctx_, total * sizeof(u32));
+  }
+  u32* operator[](size_t seg) const {
+    u32* p = static_cast<u32*>(ctx_->d_misc);
+    for (size_t i = 0; i < seg; ++i) p += words_[i];
+    return p;
+  }
+  int upload(size_t seg, const void* host) const { return ::upload(ctx_, (*this)[seg], host, words_[seg]); }
+  int download_and_wait(size_t seg, void* host) const { return ::download_and_wait(ctx_, host, (*this)[seg], words_[seg]); }
+
+ private:
+  tfhe_context* ctx_;
+  std::vector<size_t> words_;
+};
+
+// A host form whose one buffer [words] goes in, is completed by the _device form, and comes back
+template <class DeviceForm>
+int in_place_host_form(tfhe_context* ctx, u32* host, size_t words, DeviceForm device_form) {
+  Staging s(ctx, {words});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(0, host));
+  TFHE_TRY(device_form(s[0]));
+  return s.download_and_wait(0, host);
+}
+
+// a temporary device buffer of a key load / key generation from host memory: freed on every way out
+struct DeviceWords {
+  u32* p = nullptr;
+  DeviceWords() = default;
+  DeviceWords(const DeviceWords&) = delete;
+  DeviceWords& operator=(const DeviceWords&) = delete;
+  ~DeviceWords() {
+    if (p) (void)hipFree(p);
+  }
+  hipError_t alloc(size_t words) { return hipMalloc(reinterpret_cast<void**>(&p), words * sizeof(u32)); }
+};
+
+// Row s*levels + level of a key-switching key (key_switching.rs:36-45) or a packing key carries
+// sk[s] * 2^{log_base*(l - (level+1))}, the KS decomposer's gadget factor of that level
+std::vector<u32> gadget_factors(const tfhe_context* ctx, const u32* sk, size_t dimension) {
+  const u32 levels = ctx->ks.levels, log_base = ctx->ks.log_base;
+  const u32 top = gadget_top(ctx, log_base);
+  std::vector<u32> factor(dimension * levels);
+  for (size_t s = 0; s < dimension; ++s)
+    for (u32 level = 0; level < levels; ++level)
+      factor[s * levels + level] = (1u << (top - log_base * (level + 1))) * sk[s];
+  return factor;
+}
+
+// The external product's parameters with the KS decomposer.  Read per call: the decomposer may have been re-aligned since
+// the key was loaded (as for the KSK, the caller keeps them in step)
+PbsParams packing_params(const tfhe_context* ctx) {
+  PbsParams P = ctx->pbs;
+  P.log_base = ctx->ks.log_base;
+  P.levels = ctx->ks.levels;
+  P.ignored_bits = ctx->ks.ignored_bits;
+  P.first_shift = ctx->ks.first_shift;
+  return P;
+}
+
+// ---- timing spans: events 0/1 bracket a rotation, 2/3 a key switch (tfhe_last_kernel_ms)
+enum Span { kRotationSpan = 0, kKeySwitchSpan = 2 };
+
+int span_begin(tfhe_context* ctx, Span span) {
+  if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[span], ctx->stream));
+  return TFHE_OK;
+}
+
+// alone: the call times this span only, the other one's events are stale (a bootstrap ends both and says so itself)
+int span_end(tfhe_context* ctx, Span span, bool alone = true) {
+  if (!ctx->timing) return TFHE_OK;
+  HIP_TRY(ctx, hipEventRecord(ctx->ev[span + 1], ctx->stream));
+  if (alone) {
+    ctx->ev_valid_br = span == kRotationSpan;
+    ctx->ev_valid_ks = span == kKeySwitchSpan;
+  }
+  return TFHE_OK;
+}
+
 // construct_test_from_lut: test_vector.rs:38-67
 int test_from_lut(const tfhe_params* p, const u32* lut, size_t lut_len, u32* out) {
   const u32 plaintext_modulus = 1u << p->log_p;
@@ -125,11 +263,6 @@ int check_tv_host(tfhe_context* ctx, const u32* tv, size_t words) {
   return TFHE_OK;
 }
 
-// Enqueue the whole PBS on device buffers: blind rotation (+ fused sample extract), key switch.
-// words of one ciphertext at the bootstrap boundary: n+1 in the reference's order (PBS then KS,
-// bootstrapping.rs:58-120), k*N+1 when the key switch comes first
-using tfhe::host::io_words;
-
 // the blind rotation the loaded key calls for: bootstrapping.rs:79-105, or the unrolled loop of
 // notes/BMMP Bootstrapping.md with a BMMP key
 // Where a rotation's accumulator starts: the clear test vector(s) tv [tv_count][N], or (glwe) the GLWE ciphertext(s)
@@ -151,12 +284,13 @@ hipError_t enqueue_blind_rotate(tfhe_context* ctx, const u32* lwe_in, size_t bat
   PbsParams P = ctx->pbs;
   P.acc_glwe = from.glwe ? 1u : 0u;
   P.acc_offset = from.offset;
-  const size_t tv_words = from.glwe ? (size_t)(ctx->params.glwe_dimension + 1) * ctx->N : (size_t)ctx->N;
+  const size_t tv_words = from.glwe ? glwe_words(ctx) : (size_t)ctx->N;
   return launch::blind_rotate(ctx->stream, ctx->field, P, ctx->d_tw, lwe_in, batch, tv, tv_count == 1 ? 0 : tv_words,
                               ctx->d_bsk, glwe_out, lwe_extracted, state, &ctx->side, ctx->shape);
 }
 
-// d_lwe_big: [batch][k*N+1] scratch of the reference order (unused when the key switch comes first)
+// Enqueue the whole PBS on device buffers: blind rotation (+ fused sample extract), key switch (bootstrapping.rs:58-120),
+// or the key switch first.  d_lwe_big: [batch][k*N+1] scratch of the reference order (unused when the key switch comes first)
 int enqueue_bootstrap(tfhe_context* ctx, const u32* d_lwe_in, size_t batch, const u32* d_tv,
                       size_t tv_count, u32* d_lwe_big, u32* d_lwe_out, AccSource from = AccSource()) {
   const u32* br_in = d_lwe_in;
@@ -166,39 +300,22 @@ int enqueue_bootstrap(tfhe_context* ctx, const u32* d_lwe_in, size_t batch, cons
     ctx->ev = ctx->ev_ring[ctx->ev_slot];
     ++ctx->timed_bootstraps;
   }
+  auto key_switch = [&](const u32* in, u32* out) -> int {
+    TFHE_TRY(span_begin(ctx, kKeySwitchSpan));
+    HIP_TRY(ctx, launch::key_switch(ctx->stream, ctx->ks, ctx->big_n, ctx->params.lwe_dimension, in, batch, ctx->d_ksk, out));
+    return span_end(ctx, kKeySwitchSpan, false);
+  };
   if (ctx->ks_first) {  // notes/TFHE.md:367-400: key switch k*N -> n, then PBS back to k*N
-    if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-    HIP_TRY(ctx, launch::key_switch(ctx->stream, ctx->ks, ctx->big_n, ctx->params.lwe_dimension,
-                                    d_lwe_in, batch, ctx->d_ksk, ctx->d_lwe_ks));
-    if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+    TFHE_TRY(key_switch(d_lwe_in, ctx->d_lwe_ks));
     br_in = ctx->d_lwe_ks;
     br_out = d_lwe_out;
   }
-  if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+  TFHE_TRY(span_begin(ctx, kRotationSpan));
   HIP_TRY(ctx, enqueue_blind_rotate(ctx, br_in, batch, d_tv, tv_count, nullptr, br_out, from));
-  if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-  if (!ctx->ks_first) {
-    if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-    HIP_TRY(ctx, launch::key_switch(ctx->stream, ctx->ks, ctx->big_n, ctx->params.lwe_dimension,
-                                    d_lwe_big, batch, ctx->d_ksk, d_lwe_out));
-    if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
-  }
+  TFHE_TRY(span_end(ctx, kRotationSpan, false));
+  if (!ctx->ks_first) TFHE_TRY(key_switch(d_lwe_big, d_lwe_out));
   if (ctx->timing) ctx->ev_valid_br = ctx->ev_valid_ks = true;
   return TFHE_OK;
-}
-
-int check_batch_args(tfhe_context* ctx, const void* a, const void* b, const void* c, size_t batch,
-                     size_t tv_count) {
-  if (!a || !b || !c) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
-  if (batch == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "empty batch");
-  if (batch > kMaxBatch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "batch exceeds 2^31 - 1 (one workgroup per sample)");
-  if (tv_count != 1 && tv_count != batch)
-    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "tv_count must be 1 or batch");
-  return TFHE_OK;
-}
-
-size_t ggsw_words(const tfhe_context* ctx) {
-  return (size_t)ctx->R * (ctx->params.glwe_dimension + 1) * ctx->N;
 }
 
 // log2 of the worst-case |integer convolution value| one inverse transform has to lift:
@@ -223,10 +340,6 @@ hipError_t upload_twiddles(tfhe_context* ctx) {
 namespace tfhe {
 namespace host {
 
-size_t io_words(const tfhe_context* ctx) {
-  return (ctx->ks_first ? (size_t)ctx->big_n : (size_t)ctx->params.lwe_dimension) + 1;
-}
-
 int adopt_prepared_key(tfhe_context* dst, const tfhe_context* src) {
   if (!dst || !src || !src->have_key) return fail(dst, TFHE_ERR_NO_KEY, "source context holds no key");
   if (std::memcmp(&dst->params, &src->params, sizeof(tfhe_params)) != 0 || dst->field != src->field ||
@@ -237,8 +350,7 @@ int adopt_prepared_key(tfhe_context* dst, const tfhe_context* src) {
   dst->have_key = false;
   HIP_TRY(dst, hipSetDevice(dst->device));
   const size_t ggsws = src->bsk_ggsws;
-  const size_t bsk_bytes = ggsws * src->R * (src->params.glwe_dimension + 1) * (size_t)src->parts * src->N * sizeof(u64);
-  const size_t ksk_bytes = (size_t)src->big_n * src->ks.levels * ((size_t)src->params.lwe_dimension + 1) * sizeof(u32);
+  const size_t bsk_bytes = prepared_bsk_bytes(src, ggsws), ksk_bytes = ksk_words(src) * sizeof(u32);
   if (dst->d_bsk && dst->bsk_ggsws != ggsws) {
     HIP_TRY(dst, hipStreamSynchronize(dst->stream));
     hipError_t e = hipFree(dst->d_bsk);
@@ -474,7 +586,7 @@ const char* tfhe_context_backend(const tfhe_context* ctx) {
 
 int tfhe_prepared_ggsw_words(const tfhe_context* ctx, size_t* words) {
   if (!ctx || !words) return TFHE_ERR_INVALID_ARGUMENT;
-  *words = ggsw_words(ctx) * ctx->parts;
+  *words = prepared_ggsw_words(ctx);
   return TFHE_OK;
 }
 
@@ -504,8 +616,7 @@ void tfhe_context_destroy(tfhe_context* ctx) {
 }
 
 int tfhe_context_set_stream(tfhe_context* ctx, void* hip_stream) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+  TFHE_TRY(check_ctx(ctx));
   if (ctx->stream || !ctx->own_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (ctx->own_stream && ctx->stream) HIP_TRY(ctx, hipStreamDestroy(ctx->stream));
   // a null handle is HIP's default stream, which is what torch.cuda.current_stream().cuda_stream
@@ -516,8 +627,7 @@ int tfhe_context_set_stream(tfhe_context* ctx, void* hip_stream) {
 }
 
 int tfhe_context_use_own_stream(tfhe_context* ctx) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+  TFHE_TRY(check_ctx(ctx));
   if (ctx->own_stream) return TFHE_OK;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
@@ -526,8 +636,7 @@ int tfhe_context_use_own_stream(tfhe_context* ctx) {
 }
 
 int tfhe_context_set_decomposer_alignment(tfhe_context* ctx, int aligned) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+  TFHE_TRY(check_ctx(ctx));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->aligned = aligned != 0;
   ctx->pbs.first_shift = gadget_top(ctx, ctx->pbs.log_base) - ctx->pbs.log_base * ctx->pbs.levels;
@@ -544,23 +653,20 @@ int tfhe_context_set_kernel_shape(tfhe_context* ctx, int shape) {
 }
 
 int tfhe_context_set_bootstrap_order(tfhe_context* ctx, int ks_first) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+  TFHE_TRY(check_ctx(ctx));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->ks_first = ks_first != 0;
   return TFHE_OK;
 }
 
 int tfhe_context_synchronize(tfhe_context* ctx) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+  TFHE_TRY(check_ctx(ctx));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return TFHE_OK;
 }
 
 int tfhe_context_reserve(tfhe_context* ctx, size_t max_batch) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+  TFHE_TRY(check_ctx(ctx));
   if (max_batch == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "max_batch == 0");
   return reserve(ctx, max_batch);
 }
@@ -574,8 +680,7 @@ int tfhe_context_set_timing(tfhe_context* ctx, int enable) {
 }
 
 int tfhe_measure_hbm_copy(tfhe_context* ctx, size_t bytes, int reps, double* gb_per_s) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+  TFHE_TRY(check_ctx(ctx));
   if (!gb_per_s || bytes < 16 || reps <= 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "bytes >= 16, reps >= 1");
   bytes &= ~(size_t)15;
   void *src = nullptr, *dst = nullptr;
@@ -602,8 +707,7 @@ int tfhe_measure_hbm_copy(tfhe_context* ctx, size_t bytes, int reps, double* gb_
 }
 
 int tfhe_debug_fft_margin(tfhe_context* ctx, double* worst, int reset) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+  TFHE_TRY(check_ctx(ctx));
 #if defined(TFHE_FFT_TRACK_ERROR)
   HIP_TRY(ctx, launch::fft_margin(worst, reset != 0));
   return TFHE_OK;
@@ -616,9 +720,8 @@ int tfhe_debug_fft_margin(tfhe_context* ctx, double* worst, int reset) {
 
 int tfhe_debug_blind_rotate_plan(tfhe_context* ctx, size_t batch, size_t* samples_per_group, unsigned* segments,
                                  unsigned* streams, size_t* resident_samples) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!samples_per_group || !segments || !streams || !resident_samples) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {samples_per_group, segments, streams, resident_samples}, 1, "null pointer"));
   launch::BlindRotatePlanInfo plan{};
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   // the plan of tfhe_bootstrap_batch[_device], which reserve the workspace the accumulators are parked in
@@ -631,9 +734,8 @@ int tfhe_debug_blind_rotate_plan(tfhe_context* ctx, size_t batch, size_t* sample
 }
 
 int tfhe_debug_blind_rotate_shape(tfhe_context* ctx, size_t batch, unsigned* waves_per_sample, unsigned* samples_per_team) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!waves_per_sample || !samples_per_team) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {waves_per_sample, samples_per_team}, 1, "null pointer"));
   launch::BlindRotatePlanInfo plan{};
   HIP_TRY(ctx, launch::blind_rotate_plan(ctx->field, ctx->pbs, batch, !ctx->bmmp, ctx->side.stream != nullptr, &plan, ctx->shape));
   *waves_per_sample = (unsigned)plan.waves_per_sample;
@@ -642,9 +744,8 @@ int tfhe_debug_blind_rotate_shape(tfhe_context* ctx, size_t batch, unsigned* wav
 }
 
 int tfhe_kernel_ms_ago(tfhe_context* ctx, unsigned steps_ago, float* blind_rotate_ms, float* key_switch_ms) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!blind_rotate_ms || !key_switch_ms) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {blind_rotate_ms, key_switch_ms}, 1, "null pointer"));
   if (steps_ago >= (unsigned)tfhe_context::kTimingSlots || (unsigned long long)steps_ago >= ctx->timed_bootstraps)
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "no timed bootstrap that far back");
   hipEvent_t* ev = ctx->ev_ring[(ctx->ev_slot + tfhe_context::kTimingSlots - (int)steps_ago) % tfhe_context::kTimingSlots];
@@ -656,8 +757,7 @@ int tfhe_kernel_ms_ago(tfhe_context* ctx, unsigned steps_ago, float* blind_rotat
 }
 
 int tfhe_last_kernel_ms(tfhe_context* ctx, float* blind_rotate_ms, float* key_switch_ms) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+  TFHE_TRY(check_ctx(ctx));
   if (blind_rotate_ms) *blind_rotate_ms = -1.0f;
   if (key_switch_ms) *key_switch_ms = -1.0f;
   if (ctx->ev_valid_br && blind_rotate_ms) {
@@ -694,7 +794,6 @@ static int load_key_common(tfhe_context* ctx, const u32* d_bsk_raw, const u32* d
                            bool ksk_needs_copy, bool bmmp = false) {
   const size_t ggsws = key_ggsws(ctx, bmmp);
   const size_t bsk_polys = ggsws * ctx->R * (ctx->params.glwe_dimension + 1);
-  const size_t ksk_words = (size_t)ctx->big_n * ctx->ks.levels * ((size_t)ctx->params.lwe_dimension + 1);
   // the key buffers are overwritten in place: until the new key is complete the context holds none (a failure half way
   // must not leave it bootstrapping under a half-written key)
   ctx->have_key = false;
@@ -705,15 +804,14 @@ static int load_key_common(tfhe_context* ctx, const u32* d_bsk_raw, const u32* d
     if (e != hipSuccess) return hip_fail(ctx, e, "hipFree(bsk)");
   }
   if (!ctx->d_bsk) {
-    HIP_TRY(ctx, hipMalloc(&ctx->d_bsk, bsk_polys * ctx->parts * ctx->N * sizeof(u64)));
+    HIP_TRY(ctx, hipMalloc(&ctx->d_bsk, prepared_bsk_bytes(ctx, ggsws)));
     ctx->bsk_ggsws = ggsws;
   }
   if (!ctx->d_ksk)
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_ksk), ksk_words * sizeof(u32)));
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_ksk), ksk_words(ctx) * sizeof(u32)));
   HIP_TRY(ctx, launch::bsk_prepare(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->pbs.k, ctx->d_tw, d_bsk_raw, bsk_polys, ctx->d_bsk));
   if (ksk_needs_copy)
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ksk, d_ksk_raw, ksk_words * sizeof(u32),
-                                hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ksk, d_ksk_raw, ksk_words(ctx) * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->have_key = true;
   ctx->bmmp = bmmp;
@@ -723,52 +821,42 @@ static int load_key_common(tfhe_context* ctx, const u32* d_bsk_raw, const u32* d
 static int load_key_host(tfhe_context* ctx, const uint32_t* bsk, const uint32_t* ksk, bool bmmp) {
   if (!bsk || !ksk) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null key pointer");
   const size_t bsk_words = key_ggsws(ctx, bmmp) * ggsw_words(ctx);
-  const size_t ksk_words = (size_t)ctx->big_n * ctx->ks.levels * ((size_t)ctx->params.lwe_dimension + 1);
-  u32* d_raw = nullptr;
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&d_raw), bsk_words * sizeof(u32)));
-  hipError_t e = hipMemcpy(d_raw, bsk, bsk_words * sizeof(u32), hipMemcpyHostToDevice);
+  DeviceWords raw;
+  HIP_TRY(ctx, raw.alloc(bsk_words));
+  hipError_t e = hipMemcpy(raw.p, bsk, bsk_words * sizeof(u32), hipMemcpyHostToDevice);
   if (e == hipSuccess && !ctx->d_ksk)
-    e = hipMalloc(reinterpret_cast<void**>(&ctx->d_ksk), ksk_words * sizeof(u32));
+    e = hipMalloc(reinterpret_cast<void**>(&ctx->d_ksk), ksk_words(ctx) * sizeof(u32));
   // the key-switching key is overwritten in place by a copy that does not order itself behind the context's stream:
   // whatever was enqueued under the old key finishes first, and from here on the context holds no key
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e == hipSuccess) {
     ctx->have_key = false;
-    e = hipMemcpy(ctx->d_ksk, ksk, ksk_words * sizeof(u32), hipMemcpyHostToDevice);
+    e = hipMemcpy(ctx->d_ksk, ksk, ksk_words(ctx) * sizeof(u32), hipMemcpyHostToDevice);
   }
-  if (e != hipSuccess) {
-    (void)hipFree(d_raw);
-    return hip_fail(ctx, e, "key upload");
-  }
-  int st = load_key_common(ctx, d_raw, nullptr, false, bmmp);
-  (void)hipFree(d_raw);
-  return st;
+  if (e != hipSuccess) return hip_fail(ctx, e, "key upload");
+  return load_key_common(ctx, raw.p, nullptr, false, bmmp);
 }
 
 int tfhe_load_bootstrapping_key(tfhe_context* ctx, const uint32_t* bsk, const uint32_t* ksk) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+  TFHE_TRY(check_ctx(ctx));
   return load_key_host(ctx, bsk, ksk, false);
 }
 
 int tfhe_load_bootstrapping_key_device(tfhe_context* ctx, const uint32_t* bsk, const uint32_t* ksk) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+  TFHE_TRY(check_ctx(ctx));
   if (!bsk || !ksk) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null key pointer");
   return load_key_common(ctx, bsk, ksk, true);
 }
 
 int tfhe_load_bootstrapping_key_bmmp(tfhe_context* ctx, const uint32_t* bsk_bmmp, const uint32_t* ksk) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if ((st = check_bmmp(ctx))) return st;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_bmmp(ctx));
   return load_key_host(ctx, bsk_bmmp, ksk, true);
 }
 
 int tfhe_load_bootstrapping_key_bmmp_device(tfhe_context* ctx, const uint32_t* bsk_bmmp, const uint32_t* ksk) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if ((st = check_bmmp(ctx))) return st;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_bmmp(ctx));
   if (!bsk_bmmp || !ksk) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null key pointer");
   return load_key_common(ctx, bsk_bmmp, ksk, true, true);
 }
@@ -776,202 +864,153 @@ int tfhe_load_bootstrapping_key_bmmp_device(tfhe_context* ctx, const uint32_t* b
 int tfhe_context_uses_bmmp(const tfhe_context* ctx) { return ctx && ctx->have_key && ctx->bmmp ? 1 : 0; }
 
 // ---------------------------------------------------------------------------------- bootstrap
-int tfhe_bootstrap_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch,
-                                const uint32_t* tv, size_t tv_count, uint32_t* lwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if ((st = check_batch_args(ctx, lwe_in, tv, lwe_out, batch, tv_count))) return st;
-  if (!ctx->have_key) return fail(ctx, TFHE_ERR_NO_KEY, "load the bootstrapping key first");
-  if ((st = reserve(ctx, batch))) return st;
-  return enqueue_bootstrap(ctx, lwe_in, batch, tv, tv_count, ctx->d_lwe_big, lwe_out);
-}
-
-int tfhe_bootstrap_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, const uint32_t* tv,
-                         size_t tv_count, uint32_t* lwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if ((st = check_batch_args(ctx, lwe_in, tv, lwe_out, batch, tv_count))) return st;
-  if (!ctx->have_key) return fail(ctx, TFHE_ERR_NO_KEY, "load the bootstrapping key first");
-  if ((st = check_tv_host(ctx, tv, tv_count * ctx->N))) return st;
-  if ((st = reserve(ctx, batch))) return st;
-  const size_t n1 = io_words(ctx);
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_lwe_in, lwe_in, batch * n1 * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tv, tv, tv_count * ctx->N * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  if ((st = enqueue_bootstrap(ctx, ctx->d_lwe_in, batch, ctx->d_tv, tv_count, ctx->d_lwe_big, ctx->d_lwe_out)))
-    return st;
-  HIP_TRY(ctx, hipMemcpyAsync(lwe_out, ctx->d_lwe_out, batch * n1 * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
-}
-
-int tfhe_blind_rotate_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch,
-                                   const uint32_t* tv, size_t tv_count, uint32_t* glwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if ((st = check_batch_args(ctx, lwe_in, tv, glwe_out, batch, tv_count))) return st;
-  if (!ctx->have_key) return fail(ctx, TFHE_ERR_NO_KEY, "load the bootstrapping key first");
-  if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-  HIP_TRY(ctx, enqueue_blind_rotate(ctx, lwe_in, batch, tv, tv_count, glwe_out, nullptr));
-  if (ctx->timing) {
-    HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    ctx->ev_valid_br = true;
-    ctx->ev_valid_ks = false;
-  }
-  return TFHE_OK;
-}
-
-int tfhe_blind_rotate_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch,
-                            const uint32_t* tv, size_t tv_count, uint32_t* glwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if ((st = check_batch_args(ctx, lwe_in, tv, glwe_out, batch, tv_count))) return st;
-  if (!ctx->have_key) return fail(ctx, TFHE_ERR_NO_KEY, "load the bootstrapping key first");
-  if ((st = check_tv_host(ctx, tv, tv_count * ctx->N))) return st;
-  if ((st = reserve(ctx, batch))) return st;
-  const size_t n1 = (size_t)ctx->params.lwe_dimension + 1;
-  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_lwe_in, lwe_in, batch * n1 * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tv, tv, tv_count * ctx->N * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  if ((st = tfhe_blind_rotate_batch_device(ctx, ctx->d_lwe_in, batch, ctx->d_tv, tv_count, ctx->d_glwe_a)))
-    return st;
-  HIP_TRY(ctx, hipMemcpyAsync(glwe_out, ctx->d_glwe_a, batch * glwe * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
-}
-
-// ------------------------------------------------- blind rotation / bootstrap from a GLWE accumulator
 namespace {
-int check_glwe_acc_args(tfhe_context* ctx, const void* lwe_in, const void* acc_in, const void* out, size_t batch,
-                        size_t acc_count, size_t rotation_offset) {
-  if (!lwe_in || !acc_in || !out) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
-  if (batch == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "empty batch");
-  if (batch > kMaxBatch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "batch exceeds 2^31 - 1 (one workgroup per sample)");
-  if (acc_count != 1 && acc_count != batch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "acc_count must be 1 or batch");
-  if (rotation_offset >= 2 * (size_t)ctx->N)
+// The arguments of a rotation or a bootstrap, clear test vectors or (rotation_offset given) GLWE accumulators [count]
+int check_rotate_args(tfhe_context* ctx, const void* lwe_in, const void* acc, const void* out, size_t batch, size_t count,
+                      const size_t* rotation_offset = nullptr) {
+  TFHE_TRY(check_batch(ctx, {lwe_in, acc, out}, batch, count, rotation_offset ? "acc_count" : "tv_count"));
+  if (rotation_offset && *rotation_offset >= 2 * (size_t)ctx->N)
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "rotation_offset must be below 2N = " + std::to_string(2 * (size_t)ctx->N));
   if (!ctx->have_key) return fail(ctx, TFHE_ERR_NO_KEY, "load the bootstrapping key first");
-  if (ctx->bmmp)
+  if (rotation_offset && ctx->bmmp)
     return fail(ctx, TFHE_ERR_UNSUPPORTED,
                 "a BMMP key is loaded: the unrolled rotation starts from a clear test vector only (load a plain "
                 "bootstrapping key for a GLWE accumulator)");
   return TFHE_OK;
 }
+
+// rotation only, timed as one
+int rotate_device(tfhe_context* ctx, const u32* lwe_in, size_t batch, const u32* acc, size_t count, u32* glwe_out, AccSource from) {
+  TFHE_TRY(span_begin(ctx, kRotationSpan));
+  HIP_TRY(ctx, enqueue_blind_rotate(ctx, lwe_in, batch, acc, count, glwe_out, nullptr, from));
+  return span_end(ctx, kRotationSpan);
+}
 }  // namespace
 
+int tfhe_bootstrap_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch,
+                                const uint32_t* tv, size_t tv_count, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_rotate_args(ctx, lwe_in, tv, lwe_out, batch, tv_count));
+  TFHE_TRY(reserve(ctx, batch));
+  return enqueue_bootstrap(ctx, lwe_in, batch, tv, tv_count, ctx->d_lwe_big, lwe_out);
+}
+
+int tfhe_bootstrap_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, const uint32_t* tv,
+                         size_t tv_count, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_rotate_args(ctx, lwe_in, tv, lwe_out, batch, tv_count));
+  TFHE_TRY(check_tv_host(ctx, tv, tv_count * ctx->N));
+  TFHE_TRY(reserve(ctx, batch));
+  TFHE_TRY(upload(ctx, ctx->d_lwe_in, lwe_in, batch * io_words(ctx)));
+  TFHE_TRY(upload(ctx, ctx->d_tv, tv, tv_count * ctx->N));
+  TFHE_TRY(enqueue_bootstrap(ctx, ctx->d_lwe_in, batch, ctx->d_tv, tv_count, ctx->d_lwe_big, ctx->d_lwe_out));
+  return download_and_wait(ctx, lwe_out, ctx->d_lwe_out, batch * io_words(ctx));
+}
+
+int tfhe_blind_rotate_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch,
+                                   const uint32_t* tv, size_t tv_count, uint32_t* glwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_rotate_args(ctx, lwe_in, tv, glwe_out, batch, tv_count));
+  return rotate_device(ctx, lwe_in, batch, tv, tv_count, glwe_out, AccSource());
+}
+
+// (the rotation-only forms read n+1 words per input whatever the bootstrap order is)
+int tfhe_blind_rotate_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch,
+                            const uint32_t* tv, size_t tv_count, uint32_t* glwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_rotate_args(ctx, lwe_in, tv, glwe_out, batch, tv_count));
+  TFHE_TRY(check_tv_host(ctx, tv, tv_count * ctx->N));
+  TFHE_TRY(reserve(ctx, batch));
+  TFHE_TRY(upload(ctx, ctx->d_lwe_in, lwe_in, batch * lwe_words(ctx)));
+  TFHE_TRY(upload(ctx, ctx->d_tv, tv, tv_count * ctx->N));
+  TFHE_TRY(rotate_device(ctx, ctx->d_lwe_in, batch, ctx->d_tv, tv_count, ctx->d_glwe_a, AccSource()));
+  return download_and_wait(ctx, glwe_out, ctx->d_glwe_a, batch * glwe_words(ctx));
+}
+
+// ------------------------------------------------- blind rotation / bootstrap from a GLWE accumulator
 int tfhe_blind_rotate_glwe_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, const uint32_t* acc_in,
                                         size_t acc_count, size_t rotation_offset, uint32_t* glwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if ((st = check_glwe_acc_args(ctx, lwe_in, acc_in, glwe_out, batch, acc_count, rotation_offset))) return st;
-  if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-  HIP_TRY(ctx, enqueue_blind_rotate(ctx, lwe_in, batch, acc_in, acc_count, glwe_out, nullptr, AccSource{true, (u32)rotation_offset}));
-  if (ctx->timing) {
-    HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    ctx->ev_valid_br = true;
-    ctx->ev_valid_ks = false;
-  }
-  return TFHE_OK;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_rotate_args(ctx, lwe_in, acc_in, glwe_out, batch, acc_count, &rotation_offset));
+  return rotate_device(ctx, lwe_in, batch, acc_in, acc_count, glwe_out, AccSource{true, (u32)rotation_offset});
 }
 
 int tfhe_blind_rotate_glwe_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, const uint32_t* acc_in,
                                  size_t acc_count, size_t rotation_offset, uint32_t* glwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if ((st = check_glwe_acc_args(ctx, lwe_in, acc_in, glwe_out, batch, acc_count, rotation_offset))) return st;
-  if ((st = reserve(ctx, batch))) return st;
-  const size_t n1 = (size_t)ctx->params.lwe_dimension + 1;
-  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_lwe_in, lwe_in, batch * n1 * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_glwe_a, acc_in, acc_count * glwe * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  if ((st = tfhe_blind_rotate_glwe_batch_device(ctx, ctx->d_lwe_in, batch, ctx->d_glwe_a, acc_count, rotation_offset, ctx->d_glwe_b)))
-    return st;
-  HIP_TRY(ctx, hipMemcpyAsync(glwe_out, ctx->d_glwe_b, batch * glwe * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_rotate_args(ctx, lwe_in, acc_in, glwe_out, batch, acc_count, &rotation_offset));
+  TFHE_TRY(reserve(ctx, batch));
+  TFHE_TRY(upload(ctx, ctx->d_lwe_in, lwe_in, batch * lwe_words(ctx)));
+  TFHE_TRY(upload(ctx, ctx->d_glwe_a, acc_in, acc_count * glwe_words(ctx)));
+  TFHE_TRY(rotate_device(ctx, ctx->d_lwe_in, batch, ctx->d_glwe_a, acc_count, ctx->d_glwe_b, AccSource{true, (u32)rotation_offset}));
+  return download_and_wait(ctx, glwe_out, ctx->d_glwe_b, batch * glwe_words(ctx));
 }
 
 int tfhe_bootstrap_glwe_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, const uint32_t* acc_in,
                                      size_t acc_count, size_t rotation_offset, uint32_t* lwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if ((st = check_glwe_acc_args(ctx, lwe_in, acc_in, lwe_out, batch, acc_count, rotation_offset))) return st;
-  if ((st = reserve(ctx, batch))) return st;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_rotate_args(ctx, lwe_in, acc_in, lwe_out, batch, acc_count, &rotation_offset));
+  TFHE_TRY(reserve(ctx, batch));
   return enqueue_bootstrap(ctx, lwe_in, batch, acc_in, acc_count, ctx->d_lwe_big, lwe_out, AccSource{true, (u32)rotation_offset});
 }
 
 int tfhe_bootstrap_glwe_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, const uint32_t* acc_in,
                               size_t acc_count, size_t rotation_offset, uint32_t* lwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if ((st = check_glwe_acc_args(ctx, lwe_in, acc_in, lwe_out, batch, acc_count, rotation_offset))) return st;
-  if ((st = reserve(ctx, batch))) return st;
-  const size_t n1 = io_words(ctx);
-  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_lwe_in, lwe_in, batch * n1 * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_glwe_a, acc_in, acc_count * glwe * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  if ((st = enqueue_bootstrap(ctx, ctx->d_lwe_in, batch, ctx->d_glwe_a, acc_count, ctx->d_lwe_big, ctx->d_lwe_out,
-                              AccSource{true, (u32)rotation_offset})))
-    return st;
-  HIP_TRY(ctx, hipMemcpyAsync(lwe_out, ctx->d_lwe_out, batch * n1 * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_rotate_args(ctx, lwe_in, acc_in, lwe_out, batch, acc_count, &rotation_offset));
+  TFHE_TRY(reserve(ctx, batch));
+  TFHE_TRY(upload(ctx, ctx->d_lwe_in, lwe_in, batch * io_words(ctx)));
+  TFHE_TRY(upload(ctx, ctx->d_glwe_a, acc_in, acc_count * glwe_words(ctx)));
+  TFHE_TRY(enqueue_bootstrap(ctx, ctx->d_lwe_in, batch, ctx->d_glwe_a, acc_count, ctx->d_lwe_big, ctx->d_lwe_out,
+                             AccSource{true, (u32)rotation_offset}));
+  return download_and_wait(ctx, lwe_out, ctx->d_lwe_out, batch * io_words(ctx));
 }
 
 int tfhe_sample_extract_batch(tfhe_context* ctx, const uint32_t* glwe, size_t batch,
                               size_t sample_index, uint32_t* lwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!glwe || !lwe_out || batch == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {glwe, lwe_out}, batch));
   if (sample_index >= ctx->N)  // assert!(sample_index < degree), bootstrapping.rs:127
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "sample_index >= N (bootstrapping.rs:127)");
-  if ((st = reserve(ctx, batch))) return st;
-  const size_t glwe_w = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
-  const size_t out_w = (size_t)ctx->big_n + 1;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_glwe_a, glwe, batch * glwe_w * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
+  TFHE_TRY(reserve(ctx, batch));
+  TFHE_TRY(upload(ctx, ctx->d_glwe_a, glwe, batch * glwe_words(ctx)));
   HIP_TRY(ctx, launch::sample_extract(ctx->stream, ctx->pbs.log_n, ctx->pbs.k, ctx->d_glwe_a, batch,
                                       (u32)sample_index, ctx->d_lwe_big));
-  HIP_TRY(ctx, hipMemcpyAsync(lwe_out, ctx->d_lwe_big, batch * out_w * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return download_and_wait(ctx, lwe_out, ctx->d_lwe_big, batch * big_lwe_words(ctx));
+}
+
+namespace {
+int check_key_switch_args(tfhe_context* ctx, const void* lwe_in, const void* lwe_out, size_t batch) {
+  TFHE_TRY(check_present(ctx, {lwe_in, lwe_out}, batch));
+  if (!ctx->have_key) return fail(ctx, TFHE_ERR_NO_KEY, "load the bootstrapping key first");
   return TFHE_OK;
 }
+}  // namespace
 
 int tfhe_key_switch_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch,
                                  uint32_t* lwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!lwe_in || !lwe_out || batch == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
-  if (!ctx->have_key) return fail(ctx, TFHE_ERR_NO_KEY, "load the bootstrapping key first");
-  if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_key_switch_args(ctx, lwe_in, lwe_out, batch));
+  TFHE_TRY(span_begin(ctx, kKeySwitchSpan));
   HIP_TRY(ctx, launch::key_switch(ctx->stream, ctx->ks, ctx->big_n, ctx->params.lwe_dimension, lwe_in,
                                   batch, ctx->d_ksk, lwe_out));
-  if (ctx->timing) {
-    HIP_TRY(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
-    ctx->ev_valid_ks = true;
-    ctx->ev_valid_br = false;
-  }
-  return TFHE_OK;
+  return span_end(ctx, kKeySwitchSpan);
 }
 
 int tfhe_key_switch_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, uint32_t* lwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!lwe_in || !lwe_out || batch == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
-  if (!ctx->have_key) return fail(ctx, TFHE_ERR_NO_KEY, "load the bootstrapping key first");
-  if ((st = reserve(ctx, batch))) return st;
-  const size_t in_w = (size_t)ctx->big_n + 1, out_w = (size_t)ctx->params.lwe_dimension + 1;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_lwe_big, lwe_in, batch * in_w * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  if ((st = tfhe_key_switch_batch_device(ctx, ctx->d_lwe_big, batch, ctx->d_lwe_out))) return st;
-  HIP_TRY(ctx, hipMemcpyAsync(lwe_out, ctx->d_lwe_out, batch * out_w * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_key_switch_args(ctx, lwe_in, lwe_out, batch));
+  TFHE_TRY(reserve(ctx, batch));
+  TFHE_TRY(upload(ctx, ctx->d_lwe_big, lwe_in, batch * big_lwe_words(ctx)));
+  TFHE_TRY(tfhe_key_switch_batch_device(ctx, ctx->d_lwe_big, batch, ctx->d_lwe_out));
+  return download_and_wait(ctx, lwe_out, ctx->d_lwe_out, batch * lwe_words(ctx));
 }
 
 // ---------------------------------------------------------------------------------- ggsw.rs
 int tfhe_prepare_ggsw_device(tfhe_context* ctx, const uint32_t* ggsw, size_t ggsw_count,
                              void* ggsw_prepared) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!ggsw || !ggsw_prepared || ggsw_count == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / zero count");
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {ggsw, ggsw_prepared}, ggsw_count, "null pointer / zero count"));
   const size_t polys = ggsw_count * ctx->R * (ctx->params.glwe_dimension + 1);
   HIP_TRY(ctx, launch::bsk_prepare(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->pbs.k, ctx->d_tw, ggsw, polys, ggsw_prepared));
   return TFHE_OK;
@@ -980,70 +1019,50 @@ int tfhe_prepare_ggsw_device(tfhe_context* ctx, const uint32_t* ggsw, size_t ggs
 int tfhe_external_product_prepared_device(tfhe_context* ctx, const void* ggsw_prepared,
                                           size_t ggsw_count, const uint32_t* glwe_in, size_t batch,
                                           uint32_t* glwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!ggsw_prepared || !glwe_in || !glwe_out || batch == 0)
-    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
-  if (ggsw_count != 1 && ggsw_count != batch)
-    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "ggsw_count must be 1 or batch");
-  if (batch > kMaxBatch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "batch exceeds 2^31 - 1");
-  if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_batch(ctx, {ggsw_prepared, glwe_in, glwe_out}, batch, ggsw_count, "ggsw_count", kProducts));
+  TFHE_TRY(span_begin(ctx, kRotationSpan));
   HIP_TRY(ctx, launch::external_product(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, ggsw_prepared,
-                                        ggsw_count == 1 ? 0 : ggsw_words(ctx) * ctx->parts, glwe_in,
+                                        ggsw_count == 1 ? 0 : prepared_ggsw_words(ctx), glwe_in,
                                         nullptr, nullptr, batch, glwe_out, ctx->d_queue));
-  if (ctx->timing) {
-    HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    ctx->ev_valid_br = true;
-    ctx->ev_valid_ks = false;
-  }
-  return TFHE_OK;
+  return span_end(ctx, kRotationSpan);
 }
 
+// host GGSWs: uploaded raw, prepared into d_ggsw_tmp
 static int upload_and_prepare_ggsw(tfhe_context* ctx, const u32* ggsw, size_t ggsw_count) {
   const size_t words = ggsw_count * ggsw_words(ctx);
-  int st;
-  if ((st = ensure(ctx, &ctx->d_ggsw_raw, &ctx->ggsw_raw_words, words))) return st;
-  if ((st = ensure(ctx, &ctx->d_ggsw_tmp, &ctx->ggsw_tmp_words, words * ctx->parts))) return st;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ggsw_raw, ggsw, words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
+  TFHE_TRY(ensure(ctx, &ctx->d_ggsw_raw, &ctx->ggsw_raw_words, words));
+  TFHE_TRY(ensure(ctx, &ctx->d_ggsw_tmp, &ctx->ggsw_tmp_words, words * ctx->parts));
+  TFHE_TRY(upload(ctx, ctx->d_ggsw_raw, ggsw, words));
   return tfhe_prepare_ggsw_device(ctx, ctx->d_ggsw_raw, ggsw_count, ctx->d_ggsw_tmp);
 }
 
 int tfhe_external_product_batch(tfhe_context* ctx, const uint32_t* ggsw, size_t ggsw_count,
                                 const uint32_t* glwe_in, size_t batch, uint32_t* glwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!ggsw || !glwe_in || !glwe_out || batch == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
-  if (ggsw_count != 1 && ggsw_count != batch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "ggsw_count must be 1 or batch");
-  if ((st = reserve(ctx, batch))) return st;
-  if ((st = upload_and_prepare_ggsw(ctx, ggsw, ggsw_count))) return st;
-  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_glwe_a, glwe_in, batch * glwe * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  if ((st = tfhe_external_product_prepared_device(ctx, ctx->d_ggsw_tmp, ggsw_count,
-                                                  ctx->d_glwe_a, batch, ctx->d_glwe_b)))
-    return st;
-  HIP_TRY(ctx, hipMemcpyAsync(glwe_out, ctx->d_glwe_b, batch * glwe * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_batch(ctx, {ggsw, glwe_in, glwe_out}, batch, ggsw_count, "ggsw_count", kHostProducts));
+  TFHE_TRY(reserve(ctx, batch));
+  TFHE_TRY(upload_and_prepare_ggsw(ctx, ggsw, ggsw_count));
+  TFHE_TRY(upload(ctx, ctx->d_glwe_a, glwe_in, batch * glwe_words(ctx)));
+  TFHE_TRY(tfhe_external_product_prepared_device(ctx, ctx->d_ggsw_tmp, ggsw_count,
+                                                 ctx->d_glwe_a, batch, ctx->d_glwe_b));
+  return download_and_wait(ctx, glwe_out, ctx->d_glwe_b, batch * glwe_words(ctx));
 }
 
 int tfhe_cmux_batch(tfhe_context* ctx, const uint32_t* ggsw, size_t ggsw_count, const uint32_t* ct0,
                     uint32_t* ct1, size_t batch, uint32_t* glwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!ggsw || !ct0 || !ct1 || !glwe_out || batch == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
-  if (ggsw_count != 1 && ggsw_count != batch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "ggsw_count must be 1 or batch");
-  if ((st = reserve(ctx, batch))) return st;
-  if ((st = upload_and_prepare_ggsw(ctx, ggsw, ggsw_count))) return st;
-  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_glwe_a, ct0, batch * glwe * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_glwe_b, ct1, batch * glwe * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_batch(ctx, {ggsw, ct0, ct1, glwe_out}, batch, ggsw_count, "ggsw_count", kHostProducts));
+  TFHE_TRY(reserve(ctx, batch));
+  TFHE_TRY(upload_and_prepare_ggsw(ctx, ggsw, ggsw_count));
+  const size_t words = batch * glwe_words(ctx);
+  TFHE_TRY(upload(ctx, ctx->d_glwe_a, ct0, words));
+  TFHE_TRY(upload(ctx, ctx->d_glwe_b, ct1, words));
   HIP_TRY(ctx, launch::external_product(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, ctx->d_ggsw_tmp,
-                                        ggsw_count == 1 ? 0 : ggsw_words(ctx) * ctx->parts, nullptr,
+                                        ggsw_count == 1 ? 0 : prepared_ggsw_words(ctx), nullptr,
                                         ctx->d_glwe_b, ctx->d_glwe_a, batch, ctx->d_glwe_c, ctx->d_queue));
-  HIP_TRY(ctx, hipMemcpyAsync(glwe_out, ctx->d_glwe_c, batch * glwe * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ct1, ctx->d_glwe_b, batch * glwe * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  TFHE_TRY(download(ctx, glwe_out, ctx->d_glwe_c, words));
+  return download_and_wait(ctx, ct1, ctx->d_glwe_b, words);
 }
 
 // ---------------------------------------------------------------------------------- CMUX tree / table lookup
@@ -1073,7 +1092,7 @@ size_t lookup_workspace_need(const tfhe_context* ctx, size_t trees, size_t depth
       size_t n = 0;
       if (launch::lookup_workspace_glwes(trees, (u32)d, h, &n)) glwes = std::max(glwes, n);
     }
-  return std::max<size_t>(1, glwes * (ctx->params.glwe_dimension + 1) * ctx->N);
+  return std::max<size_t>(1, glwes * glwe_words(ctx));
 }
 
 int grow_lookup_workspace(tfhe_context* ctx, size_t words) {
@@ -1095,15 +1114,14 @@ struct LookupLeaves {
 int run_lookup(tfhe_context* ctx, const void* selectors, size_t queries, size_t address_bits, size_t first, size_t tree_depth,
                const LookupLeaves& leaves, size_t tables, u32* glwe_out, u32* lwe_out) {
   const size_t trees = queries * tables;
-  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
+  const size_t glwe = glwe_words(ctx);
   launch::LookupPlanInfo plan{};
-  int st = lookup_plan_of(ctx, trees, tree_depth, &plan);
-  if (st) return st;
+  TFHE_TRY(lookup_plan_of(ctx, trees, tree_depth, &plan));
   if (plan.workspace_words > ctx->lookup_ws_words)
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
                 "the call needs " + std::to_string(plan.workspace_words) + " words of lookup workspace, " +
                     std::to_string(ctx->lookup_ws_words) + " are reserved (tfhe_context_reserve_lookup)");
-  const size_t ggsw8 = ggsw_words(ctx) * ctx->parts;  // 8-byte words of one prepared GGSW
+  const size_t ggsw8 = prepared_ggsw_words(ctx);
   const unsigned char* sel = static_cast<const unsigned char*>(selectors);
   // workspace: [results of passes 0, 2, ..][results of passes 1, 3, ..][pending slots]
   const size_t h = plan.height;
@@ -1150,7 +1168,7 @@ int run_lookup(tfhe_context* ctx, const void* selectors, size_t queries, size_t 
 
 int check_lookup_args(tfhe_context* ctx, const void* selectors, const void* data, const void* out, size_t queries, size_t depth,
                       size_t max_depth, size_t sets, size_t tables) {
-  if (!selectors || !data || !out) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  TFHE_TRY(check_present(ctx, {selectors, data, out}, 1, "null pointer"));
   if (queries == 0 || tables == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "queries and tables must be at least 1");
   if (depth == 0 || depth > max_depth)
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "depth must be in [1, " + std::to_string(max_depth) + "]");
@@ -1163,8 +1181,7 @@ int check_lookup_args(tfhe_context* ctx, const void* selectors, const void* data
 }  // namespace
 
 int tfhe_context_reserve_lookup(tfhe_context* ctx, size_t max_trees, size_t max_tree_depth, size_t max_lookup_bits) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+  TFHE_TRY(check_ctx(ctx));
   if (max_trees == 0 || max_trees > kMaxBatch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "max_trees must be in [1, 2^31)");
   if (max_tree_depth > kMaxTreeDepth) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "max_tree_depth must be in [0, 20]");
   if (max_lookup_bits > ctx->pbs.log_n + kMaxTreeDepth)
@@ -1184,13 +1201,12 @@ int tfhe_context_set_lookup_subtree_height(tfhe_context* ctx, unsigned height) {
 }
 
 int tfhe_debug_lookup_plan(tfhe_context* ctx, size_t trees, size_t depth, unsigned* subtree_height, unsigned* launches) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!subtree_height || !launches) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {subtree_height, launches}, 1, "null pointer"));
   if (trees == 0 || trees > kMaxBatch || depth > kMaxTreeDepth)
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "trees must be in [1, 2^31), depth in [0, 20]");
   launch::LookupPlanInfo plan{};
-  if ((st = lookup_plan_of(ctx, trees, depth, &plan))) return st;
+  TFHE_TRY(lookup_plan_of(ctx, trees, depth, &plan));
   *subtree_height = plan.height;
   *launches = plan.launches;
   return TFHE_OK;
@@ -1198,22 +1214,17 @@ int tfhe_debug_lookup_plan(tfhe_context* ctx, size_t trees, size_t depth, unsign
 
 int tfhe_cmux_prepared_device(tfhe_context* ctx, const void* ggsw_prepared, size_t ggsw_count, const uint32_t* ct0,
                               const uint32_t* ct1, size_t batch, uint32_t* glwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!ggsw_prepared || !ct0 || !ct1 || !glwe_out || batch == 0)
-    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
-  if (ggsw_count != 1 && ggsw_count != batch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "ggsw_count must be 1 or batch");
-  if (batch > kMaxBatch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "batch exceeds 2^31 - 1");
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_batch(ctx, {ggsw_prepared, ct0, ct1, glwe_out}, batch, ggsw_count, "ggsw_count", kProducts));
   // a tree of one level per sample whose two leaves live in two arrays: one team per sample, no workspace
-  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
   CmuxTreePass pass{};
   pass.selectors = pass.rot_selectors = ggsw_prepared;
-  pass.query_stride = ggsw_count == 1 ? 0 : ggsw_words(ctx) * ctx->parts;
+  pass.query_stride = ggsw_count == 1 ? 0 : prepared_ggsw_words(ctx);
   pass.tables = 1;
   pass.height = 1;
   pass.even = ct0;
   pass.odd = ct1;
-  pass.set_stride = glwe;
+  pass.set_stride = glwe_words(ctx);
   pass.glwe_out = glwe_out;
   HIP_TRY(ctx, launch::cmux_tree_pass(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, pass, batch));
   return TFHE_OK;
@@ -1221,19 +1232,16 @@ int tfhe_cmux_prepared_device(tfhe_context* ctx, const void* ggsw_prepared, size
 
 int tfhe_cmux_tree_device(tfhe_context* ctx, const void* selectors_prepared, size_t queries, size_t depth,
                           const uint32_t* leaves, size_t leaf_sets, size_t tables, uint32_t* glwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if ((st = check_lookup_args(ctx, selectors_prepared, leaves, glwe_out, queries, depth, kMaxTreeDepth, leaf_sets, tables))) return st;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_lookup_args(ctx, selectors_prepared, leaves, glwe_out, queries, depth, kMaxTreeDepth, leaf_sets, tables));
   return run_lookup(ctx, selectors_prepared, queries, depth, 0, depth, LookupLeaves{leaves, nullptr, leaf_sets == 1 && queries > 1},
                     tables, glwe_out, nullptr);
 }
 
 int tfhe_table_lookup_device(tfhe_context* ctx, const void* selectors_prepared, size_t queries, size_t depth,
                              const uint32_t* table, size_t table_sets, size_t tables, uint32_t* lwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if ((st = check_lookup_args(ctx, selectors_prepared, table, lwe_out, queries, depth, ctx->pbs.log_n + kMaxTreeDepth, table_sets, tables)))
-    return st;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_lookup_args(ctx, selectors_prepared, table, lwe_out, queries, depth, ctx->pbs.log_n + kMaxTreeDepth, table_sets, tables));
   const size_t d_lo = std::min(depth, (size_t)ctx->pbs.log_n);
   return run_lookup(ctx, selectors_prepared, queries, depth, d_lo, depth - d_lo, LookupLeaves{nullptr, table, table_sets == 1 && queries > 1},
                     tables, nullptr, lwe_out);
@@ -1242,147 +1250,123 @@ int tfhe_table_lookup_device(tfhe_context* ctx, const void* selectors_prepared, 
 // host forms: selectors [queries][depth][R][k+1][N] raw; everything uploaded, the selectors prepared once
 static int lookup_host(tfhe_context* ctx, const uint32_t* selectors, size_t queries, size_t depth, const uint32_t* data,
                        size_t sets, size_t tables, bool is_table, uint32_t* out) {
-  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
   const size_t d_lo = is_table ? std::min(depth, (size_t)ctx->pbs.log_n) : 0;
-  const size_t tree_depth = depth - d_lo;
   const size_t trees = queries * tables;
-  const size_t in_words = sets * tables * ((size_t)1 << depth) * (is_table ? 1 : glwe);
-  const size_t out_words = trees * (is_table ? (size_t)ctx->big_n + 1 : glwe);
   launch::LookupPlanInfo plan{};
-  int st = lookup_plan_of(ctx, trees, tree_depth, &plan);
-  if (st) return st;
-  if ((st = grow_lookup_workspace(ctx, std::max<size_t>(plan.workspace_words, 1)))) return st;
-  if ((st = ensure_misc(ctx, (in_words + out_words) * sizeof(u32)))) return st;
-  if ((st = upload_and_prepare_ggsw(ctx, selectors, queries * depth))) return st;
-  u32* d_in = reinterpret_cast<u32*>(ctx->d_misc);
-  u32* d_out = d_in + in_words;
-  HIP_TRY(ctx, hipMemcpyAsync(d_in, data, in_words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  st = is_table ? tfhe_table_lookup_device(ctx, ctx->d_ggsw_tmp, queries, depth, d_in, sets, tables, d_out)
-                : tfhe_cmux_tree_device(ctx, ctx->d_ggsw_tmp, queries, depth, d_in, sets, tables, d_out);
-  if (st) return st;
-  HIP_TRY(ctx, hipMemcpyAsync(out, d_out, out_words * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  TFHE_TRY(lookup_plan_of(ctx, trees, depth - d_lo, &plan));
+  TFHE_TRY(grow_lookup_workspace(ctx, std::max<size_t>(plan.workspace_words, 1)));
+  enum { kIn, kOut };
+  Staging s(ctx, {sets * tables * ((size_t)1 << depth) * (is_table ? 1 : glwe_words(ctx)),
+                  trees * (is_table ? big_lwe_words(ctx) : glwe_words(ctx))});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(upload_and_prepare_ggsw(ctx, selectors, queries * depth));
+  TFHE_TRY(s.upload(kIn, data));
+  TFHE_TRY(is_table ? tfhe_table_lookup_device(ctx, ctx->d_ggsw_tmp, queries, depth, s[kIn], sets, tables, s[kOut])
+                    : tfhe_cmux_tree_device(ctx, ctx->d_ggsw_tmp, queries, depth, s[kIn], sets, tables, s[kOut]));
+  return s.download_and_wait(kOut, out);
 }
 
 int tfhe_cmux_tree(tfhe_context* ctx, const uint32_t* selectors, size_t queries, size_t depth, const uint32_t* leaves,
                    size_t leaf_sets, size_t tables, uint32_t* glwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if ((st = check_lookup_args(ctx, selectors, leaves, glwe_out, queries, depth, kMaxTreeDepth, leaf_sets, tables))) return st;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_lookup_args(ctx, selectors, leaves, glwe_out, queries, depth, kMaxTreeDepth, leaf_sets, tables));
   return lookup_host(ctx, selectors, queries, depth, leaves, leaf_sets, tables, false, glwe_out);
 }
 
 int tfhe_table_lookup(tfhe_context* ctx, const uint32_t* selectors, size_t queries, size_t depth, const uint32_t* table,
                       size_t table_sets, size_t tables, uint32_t* lwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if ((st = check_lookup_args(ctx, selectors, table, lwe_out, queries, depth, ctx->pbs.log_n + kMaxTreeDepth, table_sets, tables)))
-    return st;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_lookup_args(ctx, selectors, table, lwe_out, queries, depth, ctx->pbs.log_n + kMaxTreeDepth, table_sets, tables));
   return lookup_host(ctx, selectors, queries, depth, table, table_sets, tables, true, lwe_out);
 }
 
 // ---------------------------------------------------------------------------------- small ops
 int tfhe_decompose(tfhe_context* ctx, int which, const uint32_t* values, size_t count, uint32_t* digits_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!values || !digits_out || count == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / zero count");
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {values, digits_out}, count, "null pointer / zero count"));
   if (which != TFHE_DECOMPOSER_PBS && which != TFHE_DECOMPOSER_KS) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "bad decomposer selector");
   const tfhe_decomposer_params& d = which == TFHE_DECOMPOSER_PBS ? ctx->params.pbs_decomposer : ctx->params.ks_decomposer;
-  const size_t in_b = count * sizeof(u32), out_b = count * d.levels * sizeof(u32);
-  if ((st = ensure_misc(ctx, in_b + out_b))) return st;
-  u32* d_in = reinterpret_cast<u32*>(ctx->d_misc);
-  u32* d_out = d_in + count;
-  HIP_TRY(ctx, hipMemcpyAsync(d_in, values, in_b, hipMemcpyHostToDevice, ctx->stream));
+  enum { kIn, kOut };
+  Staging s(ctx, {count, count * d.levels});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(kIn, values));
   HIP_TRY(ctx, launch::decompose_words(ctx->stream, d.log_base, d.levels,
-                                       gadget_top(ctx, d.log_base) - d.log_base * d.levels, d_in, count, d_out));
-  HIP_TRY(ctx, hipMemcpyAsync(digits_out, d_out, out_b, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+                                       gadget_top(ctx, d.log_base) - d.log_base * d.levels, s[kIn], count, s[kOut]));
+  return s.download_and_wait(kOut, digits_out);
 }
 
 int tfhe_decompose_glwe_batch(tfhe_context* ctx, const uint32_t* glwe, size_t batch, uint32_t* digits_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!glwe || !digits_out || batch == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {glwe, digits_out}, batch));
   const u32 polys = ctx->params.glwe_dimension + 1;
-  const size_t in_w = batch * polys * ctx->N, out_w = in_w * ctx->pbs.levels;
-  if ((st = ensure_misc(ctx, (in_w + out_w) * sizeof(u32)))) return st;
-  u32* d_in = reinterpret_cast<u32*>(ctx->d_misc);
-  u32* d_out = d_in + in_w;
-  HIP_TRY(ctx, hipMemcpyAsync(d_in, glwe, in_w * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, launch::decompose_glwe(ctx->stream, ctx->pbs.log_base, ctx->pbs.levels, ctx->pbs.first_shift, polys, ctx->N, d_in, batch, d_out));
-  HIP_TRY(ctx, hipMemcpyAsync(digits_out, d_out, out_w * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  enum { kIn, kOut };
+  Staging s(ctx, {batch * glwe_words(ctx), batch * glwe_words(ctx) * ctx->pbs.levels});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(kIn, glwe));
+  HIP_TRY(ctx, launch::decompose_glwe(ctx->stream, ctx->pbs.log_base, ctx->pbs.levels, ctx->pbs.first_shift, polys, ctx->N, s[kIn], batch, s[kOut]));
+  return s.download_and_wait(kOut, digits_out);
 }
 
 int tfhe_switch_modulus(tfhe_context* ctx, const uint32_t* values, size_t count, uint32_t log_from,
                         uint32_t log_to, uint32_t* out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!values || !out || count == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / zero count");
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {values, out}, count, "null pointer / zero count"));
   // `1 << (log_from - log_to)` and `1 << log_to` on u32 (utils.rs:27-28)
   if (log_from > 32 || log_to > log_from || log_from - log_to >= 32 || log_to >= 32)
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "switch_modulus shift out of range");
-  if ((st = ensure_misc(ctx, 2 * count * sizeof(u32)))) return st;
-  u32* d_in = reinterpret_cast<u32*>(ctx->d_misc);
-  u32* d_out = d_in + count;
-  HIP_TRY(ctx, hipMemcpyAsync(d_in, values, count * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, launch::switch_modulus(ctx->stream, d_in, count, log_from, log_to, d_out));
-  HIP_TRY(ctx, hipMemcpyAsync(out, d_out, count * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  enum { kIn, kOut };
+  Staging s(ctx, {count, count});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(kIn, values));
+  HIP_TRY(ctx, launch::switch_modulus(ctx->stream, s[kIn], count, log_from, log_to, s[kOut]));
+  return s.download_and_wait(kOut, out);
 }
 
 int tfhe_glwe_mul_monomial_batch(tfhe_context* ctx, const uint32_t* glwe_in, size_t batch,
                                  const int64_t* monomial_index, uint32_t* glwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!glwe_in || !monomial_index || !glwe_out || batch == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
-  const u32 polys = ctx->params.glwe_dimension + 1;
-  const size_t w = batch * polys * ctx->N;
-  const size_t idx_b = ((batch * sizeof(i64) + 15) / 16) * 16;
-  if ((st = ensure_misc(ctx, idx_b + 2 * w * sizeof(u32)))) return st;
-  i64* d_idx = reinterpret_cast<i64*>(ctx->d_misc);
-  u32* d_in = reinterpret_cast<u32*>(reinterpret_cast<char*>(ctx->d_misc) + idx_b);
-  u32* d_out = d_in + w;
-  HIP_TRY(ctx, hipMemcpyAsync(d_idx, monomial_index, batch * sizeof(i64), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_in, glwe_in, w * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, launch::glwe_mul_monomial(ctx->stream, ctx->pbs.log_n, polys, d_in, batch, d_idx, d_out));
-  HIP_TRY(ctx, hipMemcpyAsync(glwe_out, d_out, w * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {glwe_in, monomial_index, glwe_out}, batch));
+  const size_t w = batch * glwe_words(ctx);
+  enum { kIndex, kIn, kOut };  // the 8-byte indices first, in a segment of whole 16-byte units
+  Staging s(ctx, {(batch * sizeof(i64) + 15) / 16 * 4, w, w});
+  TFHE_TRY(s.reserve());
+  HIP_TRY(ctx, hipMemcpyAsync(s[kIndex], monomial_index, batch * sizeof(i64), hipMemcpyHostToDevice, ctx->stream));
+  TFHE_TRY(s.upload(kIn, glwe_in));
+  HIP_TRY(ctx, launch::glwe_mul_monomial(ctx->stream, ctx->pbs.log_n, ctx->params.glwe_dimension + 1, s[kIn], batch,
+                                         reinterpret_cast<const i64*>(s[kIndex]), s[kOut]));
+  return s.download_and_wait(kOut, glwe_out);
 }
 
 // ---------------------------------------------------------------------------------- lwe.rs
-int tfhe_lwe_linear_batch_device(tfhe_context* ctx, uint32_t c0, const uint32_t* ct0, uint32_t c1,
-                                 const uint32_t* ct1, size_t batch, size_t words_per_ct, uint32_t* out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+namespace {
+int check_lwe_linear_args(tfhe_context* ctx, const void* ct0, uint32_t c1, const void* ct1, size_t batch, size_t words_per_ct,
+                          const void* out) {
   if (!ct0 || !out || batch == 0 || words_per_ct == 0 || (c1 != 0 && !ct1))
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
+  return TFHE_OK;
+}
+}  // namespace
+
+int tfhe_lwe_linear_batch_device(tfhe_context* ctx, uint32_t c0, const uint32_t* ct0, uint32_t c1,
+                                 const uint32_t* ct1, size_t batch, size_t words_per_ct, uint32_t* out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_lwe_linear_args(ctx, ct0, c1, ct1, batch, words_per_ct, out));
   HIP_TRY(ctx, launch::lwe_linear(ctx->stream, c0, ct0, c1, c1 ? ct1 : nullptr, batch * words_per_ct, out));
   return TFHE_OK;
 }
 
 int tfhe_lwe_linear_batch(tfhe_context* ctx, uint32_t c0, const uint32_t* ct0, uint32_t c1,
                           const uint32_t* ct1, size_t batch, size_t words_per_ct, uint32_t* out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!ct0 || !out || batch == 0 || words_per_ct == 0 || (c1 != 0 && !ct1))
-    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_lwe_linear_args(ctx, ct0, c1, ct1, batch, words_per_ct, out));
   const size_t words = batch * words_per_ct;
-  if ((st = ensure_misc(ctx, 3 * words * sizeof(u32)))) return st;
-  u32* d0 = reinterpret_cast<u32*>(ctx->d_misc);
-  u32* d1 = d0 + words;
-  u32* dout = d1 + words;
-  HIP_TRY(ctx, hipMemcpyAsync(d0, ct0, words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  if (c1) HIP_TRY(ctx, hipMemcpyAsync(d1, ct1, words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  if ((st = tfhe_lwe_linear_batch_device(ctx, c0, d0, c1, c1 ? d1 : nullptr, batch, words_per_ct, dout))) return st;
-  HIP_TRY(ctx, hipMemcpyAsync(out, dout, words * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  enum { kCt0, kCt1, kOut };
+  Staging s(ctx, {words, words, words});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(kCt0, ct0));
+  if (c1) TFHE_TRY(s.upload(kCt1, ct1));
+  TFHE_TRY(tfhe_lwe_linear_batch_device(ctx, c0, s[kCt0], c1, c1 ? s[kCt1] : nullptr, batch, words_per_ct, s[kOut]));
+  return s.download_and_wait(kOut, out);
 }
 
 // ---------------------------------------------------------------------------------- encryption side
@@ -1420,18 +1404,11 @@ int glwe_rows_add_mask_dot_key(tfhe_context* ctx, u32* d_rows, size_t rows) {
 // generate_ksk (key_switching.rs:20-60) on device rows; both keys are host pointers
 int ksk_gen_device(tfhe_context* ctx, const u32* from_sk, size_t from_dim, const u32* to_sk,
                    size_t to_dim, u32* d_ksk) {
-  int st;
-  const u32 levels = ctx->ks.levels, log_base = ctx->ks.log_base;
-  const u32 top = gadget_top(ctx, log_base);
-  const size_t rows = from_dim * levels;
-  // row s*levels + level carries s_bit * 2^{log_base*(l - (level+1))} in its b slot (:36-45)
-  std::vector<u32> factor(rows);
-  for (size_t s = 0; s < from_dim; ++s)
-    for (u32 level = 0; level < levels; ++level)
-      factor[s * levels + level] = (1u << (top - log_base * (level + 1))) * from_sk[s];
-  if ((st = ensure_key_tmp(ctx, to_dim + rows))) return st;
-  if ((st = to_key_tmp(ctx, to_sk, to_dim, 0))) return st;
-  if ((st = to_key_tmp(ctx, factor.data(), rows, to_dim))) return st;
+  const std::vector<u32> factor = gadget_factors(ctx, from_sk, from_dim);  // in the rows' b slots
+  const size_t rows = factor.size();
+  TFHE_TRY(ensure_key_tmp(ctx, to_dim + rows));
+  TFHE_TRY(to_key_tmp(ctx, to_sk, to_dim, 0));
+  TFHE_TRY(to_key_tmp(ctx, factor.data(), rows, to_dim));
   HIP_TRY(ctx, launch::lwe_body(ctx->stream, d_ksk, rows, (u32)to_dim, ctx->d_key_tmp,
                                 ctx->d_key_tmp + to_dim, d_ksk + to_dim, to_dim + 1, false));
   // `factor` is pageable host memory: the async copy has staged it before returning
@@ -1442,64 +1419,51 @@ int ksk_gen_device(tfhe_context* ctx, const u32* from_sk, size_t from_dim, const
 
 int tfhe_glwe_encrypt_zero_batch_device(tfhe_context* ctx, const uint32_t* glwe_sk, uint32_t* glwe,
                                         size_t count) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!glwe_sk || !glwe || count == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
-  const size_t kn = (size_t)ctx->params.glwe_dimension * ctx->N;
-  if ((st = check_binary(ctx, glwe_sk, kn, "glwe secret key"))) return st;
-  if ((st = ensure_key_tmp(ctx, kn))) return st;
-  if ((st = to_key_tmp(ctx, glwe_sk, kn, 0))) return st;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {glwe_sk, glwe}, count));
+  const size_t kn = ctx->big_n;
+  TFHE_TRY(check_binary(ctx, glwe_sk, kn, "glwe secret key"));
+  TFHE_TRY(ensure_key_tmp(ctx, kn));
+  TFHE_TRY(to_key_tmp(ctx, glwe_sk, kn, 0));
   return glwe_rows_add_mask_dot_key(ctx, glwe, count);
 }
 
 int tfhe_glwe_encrypt_zero_batch(tfhe_context* ctx, const uint32_t* glwe_sk, uint32_t* glwe, size_t count) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!glwe_sk || !glwe || count == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
-  const size_t words = count * (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
-  if ((st = ensure_misc(ctx, words * sizeof(u32)))) return st;
-  u32* d = reinterpret_cast<u32*>(ctx->d_misc);
-  HIP_TRY(ctx, hipMemcpyAsync(d, glwe, words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  if ((st = tfhe_glwe_encrypt_zero_batch_device(ctx, glwe_sk, d, count))) return st;
-  HIP_TRY(ctx, hipMemcpyAsync(glwe, d, words * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {glwe_sk, glwe}, count));
+  return in_place_host_form(ctx, glwe, count * glwe_words(ctx),
+                            [&](u32* d) { return tfhe_glwe_encrypt_zero_batch_device(ctx, glwe_sk, d, count); });
 }
 
 int tfhe_glwe_decrypt_batch(tfhe_context* ctx, const uint32_t* glwe_sk, const uint32_t* glwe, size_t count,
                             uint32_t* plaintext_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!glwe_sk || !glwe || !plaintext_out || count == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {glwe_sk, glwe, plaintext_out}, count));
   const u32 k = ctx->params.glwe_dimension;
-  const size_t kn = (size_t)k * ctx->N;
-  const size_t words = count * (size_t)(k + 1) * ctx->N;
-  if ((st = check_binary(ctx, glwe_sk, kn, "glwe secret key"))) return st;
-  if ((st = ensure_key_tmp(ctx, kn))) return st;
-  if ((st = ensure_misc(ctx, (words + count * ctx->N) * sizeof(u32)))) return st;
-  u32* d = reinterpret_cast<u32*>(ctx->d_misc);
-  u32* d_out = d + words;
-  if ((st = to_key_tmp(ctx, glwe_sk, kn, 0))) return st;
-  HIP_TRY(ctx, hipMemcpyAsync(d, glwe, words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, launch::glwe_body(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->d_tw, k, d, count,
-                                 ctx->d_key_tmp, d_out, ctx->N, true));
-  HIP_TRY(ctx, hipMemcpyAsync(plaintext_out, d_out, count * ctx->N * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  const size_t kn = ctx->big_n;
+  TFHE_TRY(check_binary(ctx, glwe_sk, kn, "glwe secret key"));
+  TFHE_TRY(ensure_key_tmp(ctx, kn));
+  enum { kIn, kOut };
+  Staging s(ctx, {count * glwe_words(ctx), count * ctx->N});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(to_key_tmp(ctx, glwe_sk, kn, 0));
+  TFHE_TRY(s.upload(kIn, glwe));
+  HIP_TRY(ctx, launch::glwe_body(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->d_tw, k, s[kIn], count,
+                                 ctx->d_key_tmp, s[kOut], ctx->N, true));
+  return s.download_and_wait(kOut, plaintext_out);
 }
 
 int tfhe_ggsw_encrypt_batch_device(tfhe_context* ctx, const uint32_t* glwe_sk, const uint32_t* messages,
                                    uint32_t* ggsw, size_t count) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!glwe_sk || !messages || !ggsw || count == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {glwe_sk, messages, ggsw}, count));
   const u32 k = ctx->params.glwe_dimension;
-  const size_t kn = (size_t)k * ctx->N;
-  if ((st = check_binary(ctx, glwe_sk, kn, "glwe secret key"))) return st;
-  if ((st = ensure_key_tmp(ctx, kn + count))) return st;
-  if ((st = to_key_tmp(ctx, glwe_sk, kn, 0))) return st;
-  if ((st = to_key_tmp(ctx, messages, count, kn))) return st;
-  if ((st = glwe_rows_add_mask_dot_key(ctx, ggsw, count * ctx->R))) return st;
+  const size_t kn = ctx->big_n;
+  TFHE_TRY(check_binary(ctx, glwe_sk, kn, "glwe secret key"));
+  TFHE_TRY(ensure_key_tmp(ctx, kn + count));
+  TFHE_TRY(to_key_tmp(ctx, glwe_sk, kn, 0));
+  TFHE_TRY(to_key_tmp(ctx, messages, count, kn));
+  TFHE_TRY(glwe_rows_add_mask_dot_key(ctx, ggsw, count * ctx->R));
   HIP_TRY(ctx, launch::ggsw_add_gadget(ctx->stream, ggsw, count, k, ctx->pbs.log_n, ctx->pbs.levels,
                                        ctx->pbs.log_base, gadget_top(ctx, ctx->pbs.log_base),
                                        ctx->d_key_tmp + kn));
@@ -1508,28 +1472,20 @@ int tfhe_ggsw_encrypt_batch_device(tfhe_context* ctx, const uint32_t* glwe_sk, c
 
 int tfhe_ggsw_encrypt_batch(tfhe_context* ctx, const uint32_t* glwe_sk, const uint32_t* messages,
                             uint32_t* ggsw, size_t count) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!glwe_sk || !messages || !ggsw || count == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
-  const size_t words = count * ggsw_words(ctx);
-  if ((st = ensure_misc(ctx, words * sizeof(u32)))) return st;
-  u32* d = reinterpret_cast<u32*>(ctx->d_misc);
-  HIP_TRY(ctx, hipMemcpyAsync(d, ggsw, words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  if ((st = tfhe_ggsw_encrypt_batch_device(ctx, glwe_sk, messages, d, count))) return st;
-  HIP_TRY(ctx, hipMemcpyAsync(ggsw, d, words * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {glwe_sk, messages, ggsw}, count));
+  return in_place_host_form(ctx, ggsw, count * ggsw_words(ctx),
+                            [&](u32* d) { return tfhe_ggsw_encrypt_batch_device(ctx, glwe_sk, messages, d, count); });
 }
 
 int tfhe_lwe_encrypt_batch_device(tfhe_context* ctx, const uint32_t* lwe_sk, size_t dimension,
                                   const uint32_t* plaintexts, uint32_t* lwe, size_t batch) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+  TFHE_TRY(check_ctx(ctx));
   if (!lwe_sk || !lwe || batch == 0 || dimension == 0 || dimension >= (1u << 31))
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch / bad dimension");
-  if ((st = check_binary(ctx, lwe_sk, dimension, "lwe secret key"))) return st;
-  if ((st = ensure_key_tmp(ctx, dimension))) return st;
-  if ((st = to_key_tmp(ctx, lwe_sk, dimension, 0))) return st;
+  TFHE_TRY(check_binary(ctx, lwe_sk, dimension, "lwe secret key"));
+  TFHE_TRY(ensure_key_tmp(ctx, dimension));
+  TFHE_TRY(to_key_tmp(ctx, lwe_sk, dimension, 0));
   HIP_TRY(ctx, launch::lwe_body(ctx->stream, lwe, batch, (u32)dimension, ctx->d_key_tmp, plaintexts,
                                 lwe + dimension, dimension + 1, false));
   return TFHE_OK;
@@ -1537,31 +1493,25 @@ int tfhe_lwe_encrypt_batch_device(tfhe_context* ctx, const uint32_t* lwe_sk, siz
 
 int tfhe_lwe_encrypt_batch(tfhe_context* ctx, const uint32_t* lwe_sk, size_t dimension,
                            const uint32_t* plaintexts, uint32_t* lwe, size_t batch) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!lwe_sk || !lwe || batch == 0 || dimension == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
-  const size_t words = batch * (dimension + 1);
-  if ((st = ensure_misc(ctx, (words + batch) * sizeof(u32)))) return st;
-  u32* d = reinterpret_cast<u32*>(ctx->d_misc);
-  u32* d_pt = d + words;
-  HIP_TRY(ctx, hipMemcpyAsync(d, lwe, words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  if (plaintexts)
-    HIP_TRY(ctx, hipMemcpyAsync(d_pt, plaintexts, batch * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  if ((st = tfhe_lwe_encrypt_batch_device(ctx, lwe_sk, dimension, plaintexts ? d_pt : nullptr, d, batch))) return st;
-  HIP_TRY(ctx, hipMemcpyAsync(lwe, d, words * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {lwe_sk, lwe}, batch && dimension));
+  enum { kLwe, kPlaintexts };
+  Staging s(ctx, {batch * (dimension + 1), batch});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(kLwe, lwe));
+  if (plaintexts) TFHE_TRY(s.upload(kPlaintexts, plaintexts));
+  TFHE_TRY(tfhe_lwe_encrypt_batch_device(ctx, lwe_sk, dimension, plaintexts ? s[kPlaintexts] : nullptr, s[kLwe], batch));
+  return s.download_and_wait(kLwe, lwe);
 }
 
 int tfhe_lwe_decrypt_batch_device(tfhe_context* ctx, const uint32_t* lwe_sk, size_t dimension,
                                   const uint32_t* lwe, size_t batch, uint32_t* plaintext_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+  TFHE_TRY(check_ctx(ctx));
   if (!lwe_sk || !lwe || !plaintext_out || batch == 0 || dimension == 0 || dimension >= (1u << 31))
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch / bad dimension");
-  if ((st = check_binary(ctx, lwe_sk, dimension, "lwe secret key"))) return st;
-  if ((st = ensure_key_tmp(ctx, dimension))) return st;
-  if ((st = to_key_tmp(ctx, lwe_sk, dimension, 0))) return st;
+  TFHE_TRY(check_binary(ctx, lwe_sk, dimension, "lwe secret key"));
+  TFHE_TRY(ensure_key_tmp(ctx, dimension));
+  TFHE_TRY(to_key_tmp(ctx, lwe_sk, dimension, 0));
   HIP_TRY(ctx, launch::lwe_body(ctx->stream, lwe, batch, (u32)dimension, ctx->d_key_tmp, nullptr,
                                 plaintext_out, 1, true));
   return TFHE_OK;
@@ -1569,76 +1519,25 @@ int tfhe_lwe_decrypt_batch_device(tfhe_context* ctx, const uint32_t* lwe_sk, siz
 
 int tfhe_lwe_decrypt_batch(tfhe_context* ctx, const uint32_t* lwe_sk, size_t dimension, const uint32_t* lwe,
                            size_t batch, uint32_t* plaintext_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!lwe_sk || !lwe || !plaintext_out || batch == 0 || dimension == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
-  const size_t words = batch * (dimension + 1);
-  if ((st = ensure_misc(ctx, (words + batch) * sizeof(u32)))) return st;
-  u32* d = reinterpret_cast<u32*>(ctx->d_misc);
-  u32* d_out = d + words;
-  HIP_TRY(ctx, hipMemcpyAsync(d, lwe, words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  if ((st = tfhe_lwe_decrypt_batch_device(ctx, lwe_sk, dimension, d, batch, d_out))) return st;
-  HIP_TRY(ctx, hipMemcpyAsync(plaintext_out, d_out, batch * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {lwe_sk, lwe, plaintext_out}, batch && dimension));
+  enum { kLwe, kOut };
+  Staging s(ctx, {batch * (dimension + 1), batch});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(kLwe, lwe));
+  TFHE_TRY(tfhe_lwe_decrypt_batch_device(ctx, lwe_sk, dimension, s[kLwe], batch, s[kOut]));
+  return s.download_and_wait(kOut, plaintext_out);
 }
 
 int tfhe_generate_ksk(tfhe_context* ctx, const uint32_t* from_sk, size_t from_dimension,
                       const uint32_t* to_sk, size_t to_dimension, uint32_t* ksk) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+  TFHE_TRY(check_ctx(ctx));
   if (!from_sk || !to_sk || !ksk || from_dimension == 0 || to_dimension == 0 || to_dimension >= (1u << 31))
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / bad dimension");
-  if ((st = check_binary(ctx, from_sk, from_dimension, "from secret key"))) return st;
-  if ((st = check_binary(ctx, to_sk, to_dimension, "to secret key"))) return st;
-  const size_t words = from_dimension * ctx->ks.levels * (to_dimension + 1);
-  if ((st = ensure_misc(ctx, words * sizeof(u32)))) return st;
-  u32* d = reinterpret_cast<u32*>(ctx->d_misc);
-  HIP_TRY(ctx, hipMemcpyAsync(d, ksk, words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  if ((st = ksk_gen_device(ctx, from_sk, from_dimension, to_sk, to_dimension, d))) return st;
-  HIP_TRY(ctx, hipMemcpyAsync(ksk, d, words * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
-}
-
-int tfhe_bootstrapping_key_gen_device(tfhe_context* ctx, const uint32_t* lwe_sk, const uint32_t* glwe_sk,
-                                      uint32_t* bsk, uint32_t* ksk, int load) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!lwe_sk || !glwe_sk || !bsk || !ksk) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
-  const size_t n = ctx->params.lwe_dimension;
-  if ((st = check_binary(ctx, lwe_sk, n, "lwe secret key"))) return st;
-  // encrypt each bit of the lwe secret key (bootstrapping.rs:32-38)
-  if ((st = tfhe_ggsw_encrypt_batch_device(ctx, glwe_sk, lwe_sk, bsk, n))) return st;
-  // key switching key from the flattened GLWE key to the LWE key (:41-51, lwe.rs:62-73)
-  if ((st = ksk_gen_device(ctx, glwe_sk, ctx->big_n, lwe_sk, n, ksk))) return st;
-  if (load) return load_key_common(ctx, bsk, ksk, true);
-  return TFHE_OK;
-}
-
-int tfhe_bootstrapping_key_gen(tfhe_context* ctx, const uint32_t* lwe_sk, const uint32_t* glwe_sk,
-                               uint32_t* bsk, uint32_t* ksk, int load) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!lwe_sk || !glwe_sk || !bsk || !ksk) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
-  const size_t bsk_words = (size_t)ctx->params.lwe_dimension * ggsw_words(ctx);
-  const size_t ksk_words = (size_t)ctx->big_n * ctx->ks.levels * ((size_t)ctx->params.lwe_dimension + 1);
-  u32 *d_bsk = nullptr, *d_ksk = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_bsk), bsk_words * sizeof(u32));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_ksk), ksk_words * sizeof(u32));
-  if (e == hipSuccess) e = hipMemcpy(d_bsk, bsk, bsk_words * sizeof(u32), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_ksk, ksk, ksk_words * sizeof(u32), hipMemcpyHostToDevice);
-  st = (e == hipSuccess) ? tfhe_bootstrapping_key_gen_device(ctx, lwe_sk, glwe_sk, d_bsk, d_ksk, load)
-                         : hip_fail(ctx, e, "key buffers");
-  if (st == TFHE_OK) {
-    e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = hipMemcpy(bsk, d_bsk, bsk_words * sizeof(u32), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(ksk, d_ksk, ksk_words * sizeof(u32), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) st = hip_fail(ctx, e, "key download");
-  }
-  if (d_bsk) (void)hipFree(d_bsk);
-  if (d_ksk) (void)hipFree(d_ksk);
-  return st;
+  TFHE_TRY(check_binary(ctx, from_sk, from_dimension, "from secret key"));
+  TFHE_TRY(check_binary(ctx, to_sk, to_dimension, "to secret key"));
+  return in_place_host_form(ctx, ksk, from_dimension * ctx->ks.levels * (to_dimension + 1),
+                            [&](u32* d) { return ksk_gen_device(ctx, from_sk, from_dimension, to_sk, to_dimension, d); });
 }
 
 // notes/BMMP Bootstrapping.md:22-24: the three GGSW messages of key-bit pair j
@@ -1653,46 +1552,58 @@ static std::vector<u32> bmmp_messages(const u32* lwe_sk, size_t n) {
   return m;
 }
 
+// bootstrapping_key_gen: a GGSW per key bit (bootstrapping.rs:32-38) -- per message of a pair of key bits with bmmp --
+// and the key-switching key from the flattened GLWE key to the LWE key (:41-51, lwe.rs:62-73)
+static int key_gen_device(tfhe_context* ctx, const u32* lwe_sk, const u32* glwe_sk, u32* bsk, u32* ksk, int load, bool bmmp) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {lwe_sk, glwe_sk, bsk, ksk}, 1, "null pointer"));
+  if (bmmp) TFHE_TRY(check_bmmp(ctx));
+  const size_t n = ctx->params.lwe_dimension;
+  TFHE_TRY(check_binary(ctx, lwe_sk, n, "lwe secret key"));
+  const std::vector<u32> messages = bmmp ? bmmp_messages(lwe_sk, n) : std::vector<u32>(lwe_sk, lwe_sk + n);
+  TFHE_TRY(tfhe_ggsw_encrypt_batch_device(ctx, glwe_sk, messages.data(), bsk, messages.size()));
+  TFHE_TRY(ksk_gen_device(ctx, glwe_sk, ctx->big_n, lwe_sk, n, ksk));
+  // `messages` is pageable host memory: the async copy inside has staged it before returning
+  if (load) return load_key_common(ctx, bsk, ksk, true, bmmp);
+  return TFHE_OK;
+}
+
+static int key_gen_host(tfhe_context* ctx, const u32* lwe_sk, const u32* glwe_sk, u32* bsk, u32* ksk, int load, bool bmmp) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {lwe_sk, glwe_sk, bsk, ksk}, 1, "null pointer"));
+  if (bmmp) TFHE_TRY(check_bmmp(ctx));
+  const size_t bsk_bytes = key_ggsws(ctx, bmmp) * ggsw_words(ctx) * sizeof(u32), ksk_bytes = ksk_words(ctx) * sizeof(u32);
+  DeviceWords d_bsk, d_ksk;
+  hipError_t e = d_bsk.alloc(bsk_bytes / sizeof(u32));
+  if (e == hipSuccess) e = d_ksk.alloc(ksk_bytes / sizeof(u32));
+  if (e == hipSuccess) e = hipMemcpy(d_bsk.p, bsk, bsk_bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_ksk.p, ksk, ksk_bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) return hip_fail(ctx, e, "key buffers");
+  TFHE_TRY(key_gen_device(ctx, lwe_sk, glwe_sk, d_bsk.p, d_ksk.p, load, bmmp));
+  e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = hipMemcpy(bsk, d_bsk.p, bsk_bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(ksk, d_ksk.p, ksk_bytes, hipMemcpyDeviceToHost);
+  return e == hipSuccess ? TFHE_OK : hip_fail(ctx, e, "key download");
+}
+
+int tfhe_bootstrapping_key_gen_device(tfhe_context* ctx, const uint32_t* lwe_sk, const uint32_t* glwe_sk,
+                                      uint32_t* bsk, uint32_t* ksk, int load) {
+  return key_gen_device(ctx, lwe_sk, glwe_sk, bsk, ksk, load, false);
+}
+
+int tfhe_bootstrapping_key_gen(tfhe_context* ctx, const uint32_t* lwe_sk, const uint32_t* glwe_sk,
+                               uint32_t* bsk, uint32_t* ksk, int load) {
+  return key_gen_host(ctx, lwe_sk, glwe_sk, bsk, ksk, load, false);
+}
+
 int tfhe_bootstrapping_key_gen_bmmp_device(tfhe_context* ctx, const uint32_t* lwe_sk, const uint32_t* glwe_sk,
                                            uint32_t* bsk_bmmp, uint32_t* ksk, int load) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!lwe_sk || !glwe_sk || !bsk_bmmp || !ksk) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
-  if ((st = check_bmmp(ctx))) return st;
-  const size_t n = ctx->params.lwe_dimension;
-  if ((st = check_binary(ctx, lwe_sk, n, "lwe secret key"))) return st;
-  const std::vector<u32> messages = bmmp_messages(lwe_sk, n);
-  if ((st = tfhe_ggsw_encrypt_batch_device(ctx, glwe_sk, messages.data(), bsk_bmmp, messages.size()))) return st;
-  if ((st = ksk_gen_device(ctx, glwe_sk, ctx->big_n, lwe_sk, n, ksk))) return st;
-  // `messages` is pageable host memory: the async copy inside has staged it before returning
-  if (load) return load_key_common(ctx, bsk_bmmp, ksk, true, true);
-  return TFHE_OK;
+  return key_gen_device(ctx, lwe_sk, glwe_sk, bsk_bmmp, ksk, load, true);
 }
 
 int tfhe_bootstrapping_key_gen_bmmp(tfhe_context* ctx, const uint32_t* lwe_sk, const uint32_t* glwe_sk,
                                     uint32_t* bsk_bmmp, uint32_t* ksk, int load) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!lwe_sk || !glwe_sk || !bsk_bmmp || !ksk) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
-  if ((st = check_bmmp(ctx))) return st;
-  const size_t bsk_words = key_ggsws(ctx, true) * ggsw_words(ctx);
-  const size_t ksk_words = (size_t)ctx->big_n * ctx->ks.levels * ((size_t)ctx->params.lwe_dimension + 1);
-  u32 *d_bsk = nullptr, *d_ksk = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_bsk), bsk_words * sizeof(u32));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_ksk), ksk_words * sizeof(u32));
-  if (e == hipSuccess) e = hipMemcpy(d_bsk, bsk_bmmp, bsk_words * sizeof(u32), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_ksk, ksk, ksk_words * sizeof(u32), hipMemcpyHostToDevice);
-  st = (e == hipSuccess) ? tfhe_bootstrapping_key_gen_bmmp_device(ctx, lwe_sk, glwe_sk, d_bsk, d_ksk, load)
-                         : hip_fail(ctx, e, "key buffers");
-  if (st == TFHE_OK) {
-    e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = hipMemcpy(bsk_bmmp, d_bsk, bsk_words * sizeof(u32), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(ksk, d_ksk, ksk_words * sizeof(u32), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) st = hip_fail(ctx, e, "key download");
-  }
-  if (d_bsk) (void)hipFree(d_bsk);
-  if (d_ksk) (void)hipFree(d_ksk);
-  return st;
+  return key_gen_host(ctx, lwe_sk, glwe_sk, bsk_bmmp, ksk, load, true);
 }
 
 // ---------------------------------------------------------------------------------- packing key switch
@@ -1786,8 +1697,7 @@ int load_packing_key_common(tfhe_context* ctx, const u32* d_raw, size_t from_dim
   const size_t want_cols = std::max(kPackColsWords, pack_cols_words_per_group(ctx));
   if (ctx->pack_cols_words < want_cols) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    int st = ensure(ctx, &ctx->d_pack_cols, &ctx->pack_cols_words, want_cols);
-    if (st) return st;
+    TFHE_TRY(ensure(ctx, &ctx->d_pack_cols, &ctx->pack_cols_words, want_cols));
   }
   // rows past from_dimension (the last slice, when k+1 does not divide it): zero spectra
   if (polys * poly_bytes < bytes)
@@ -1804,77 +1714,77 @@ int check_packing_dimension(tfhe_context* ctx, size_t from_dimension) {
   return TFHE_OK;
 }
 
+int check_packing_key_args(tfhe_context* ctx, std::initializer_list<const void*> ptrs, const char* null_text, size_t from_dimension) {
+  TFHE_TRY(check_present(ctx, ptrs, 1, null_text));
+  return check_packing_dimension(ctx, from_dimension);
+}
+
+// glwe_out [groups][k+1][N] = Pack of lwe_in [groups][per_group][pksk_dim + 1], input j on coefficients
+// [j << log_rep, (j+1) << log_rep): a memset (a memset node under stream capture; the teams add their partial sums into
+// the output), then a transpose and a packing launch per chunk of groups the transposed-input workspace holds
+int enqueue_pack(tfhe_context* ctx, const u32* lwe_in, size_t groups, u32 per_group, u32* glwe_out, u32 log_rep = 0) {
+  const u32 d = (u32)ctx->pksk_dim;
+  const size_t glwe = glwe_words(ctx);
+  const PbsParams P = packing_params(ctx);
+  HIP_TRY(ctx, hipMemsetAsync(glwe_out, 0, groups * glwe * sizeof(u32), ctx->stream));
+  const size_t chunk = ctx->pack_cols_words / pack_cols_words_per_group(ctx);  // >= 1 by construction
+  for (size_t g0 = 0; g0 < groups; g0 += chunk) {
+    const size_t here = std::min(chunk, groups - g0);
+    HIP_TRY(ctx, launch::pack_transpose(ctx->stream, lwe_in + g0 * per_group * ((size_t)d + 1), here, per_group, d,
+                                        ctx->pbs.log_n, ctx->d_pack_cols, log_rep));
+    HIP_TRY(ctx, launch::pack_lwe(ctx->stream, ctx->field, P, ctx->d_tw, ctx->d_pksk, ctx->d_pack_cols, d, here,
+                                  glwe_out + g0 * glwe));
+  }
+  return TFHE_OK;
+}
+
 }  // namespace
 
 int tfhe_generate_packing_key_device(tfhe_context* ctx, const uint32_t* from_sk, size_t from_dimension,
                                      const uint32_t* glwe_sk, uint32_t* pksk) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!from_sk || !glwe_sk || !pksk) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
-  if ((st = check_packing_dimension(ctx, from_dimension))) return st;
-  const u32 k = ctx->params.glwe_dimension;
-  const size_t kn = (size_t)k * ctx->N;
-  if ((st = check_binary(ctx, from_sk, from_dimension, "from secret key"))) return st;
-  if ((st = check_binary(ctx, glwe_sk, kn, "glwe secret key"))) return st;
-  const u32 levels = ctx->ks.levels, log_base = ctx->ks.log_base;
-  const u32 top = gadget_top(ctx, log_base);
-  const size_t rows = from_dimension * levels;
-  // row i*levels + level is a zero encryption plus s_i g_level on coefficient 0 of the body (the factors of ksk_gen_device)
-  std::vector<u32> factor(rows);
-  for (size_t i = 0; i < from_dimension; ++i)
-    for (u32 level = 0; level < levels; ++level)
-      factor[i * levels + level] = (1u << (top - log_base * (level + 1))) * from_sk[i];
-  if ((st = ensure_key_tmp(ctx, kn + rows))) return st;
-  if ((st = to_key_tmp(ctx, glwe_sk, kn, 0))) return st;
-  if ((st = to_key_tmp(ctx, factor.data(), rows, kn))) return st;
-  if ((st = glwe_rows_add_mask_dot_key(ctx, pksk, rows))) return st;
-  HIP_TRY(ctx, launch::packing_add_gadget(ctx->stream, pksk, rows, k, ctx->pbs.log_n, ctx->d_key_tmp + kn));
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_packing_key_args(ctx, {from_sk, glwe_sk, pksk}, "null pointer", from_dimension));
+  const size_t kn = ctx->big_n;
+  TFHE_TRY(check_binary(ctx, from_sk, from_dimension, "from secret key"));
+  TFHE_TRY(check_binary(ctx, glwe_sk, kn, "glwe secret key"));
+  // row i*levels + level is a zero encryption plus s_i g_level on coefficient 0 of the body
+  const std::vector<u32> factor = gadget_factors(ctx, from_sk, from_dimension);
+  const size_t rows = factor.size();
+  TFHE_TRY(ensure_key_tmp(ctx, kn + rows));
+  TFHE_TRY(to_key_tmp(ctx, glwe_sk, kn, 0));
+  TFHE_TRY(to_key_tmp(ctx, factor.data(), rows, kn));
+  TFHE_TRY(glwe_rows_add_mask_dot_key(ctx, pksk, rows));
+  HIP_TRY(ctx, launch::packing_add_gadget(ctx->stream, pksk, rows, ctx->params.glwe_dimension, ctx->pbs.log_n, ctx->d_key_tmp + kn));
   // `factor` is pageable host memory: the async copy has staged it before returning
   return TFHE_OK;
 }
 
 int tfhe_generate_packing_key(tfhe_context* ctx, const uint32_t* from_sk, size_t from_dimension,
                               const uint32_t* glwe_sk, uint32_t* pksk) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!from_sk || !glwe_sk || !pksk) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
-  if ((st = check_packing_dimension(ctx, from_dimension))) return st;
-  const size_t words = from_dimension * ctx->ks.levels * (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
-  if ((st = ensure_misc(ctx, words * sizeof(u32)))) return st;
-  u32* d = reinterpret_cast<u32*>(ctx->d_misc);
-  HIP_TRY(ctx, hipMemcpyAsync(d, pksk, words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  if ((st = tfhe_generate_packing_key_device(ctx, from_sk, from_dimension, glwe_sk, d))) return st;
-  HIP_TRY(ctx, hipMemcpyAsync(pksk, d, words * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_packing_key_args(ctx, {from_sk, glwe_sk, pksk}, "null pointer", from_dimension));
+  return in_place_host_form(ctx, pksk, packing_key_words(ctx, from_dimension), [&](u32* d) {
+    return tfhe_generate_packing_key_device(ctx, from_sk, from_dimension, glwe_sk, d);
+  });
 }
 
 int tfhe_load_packing_key_device(tfhe_context* ctx, const uint32_t* pksk, size_t from_dimension) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!pksk) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null key pointer");
-  if ((st = check_packing_dimension(ctx, from_dimension))) return st;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_packing_key_args(ctx, {pksk}, "null key pointer", from_dimension));
   return load_packing_key_common(ctx, pksk, from_dimension);
 }
 
 int tfhe_load_packing_key(tfhe_context* ctx, const uint32_t* pksk, size_t from_dimension) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!pksk) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null key pointer");
-  if ((st = check_packing_dimension(ctx, from_dimension))) return st;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_packing_key_args(ctx, {pksk}, "null key pointer", from_dimension));
   const std::string why = packing_refusal(ctx);  // before the upload
   if (!why.empty()) return fail(ctx, TFHE_ERR_EXACTNESS, "packing key refused: " + why);
-  const size_t words = from_dimension * ctx->ks.levels * (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
-  u32* d_raw = nullptr;
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&d_raw), words * sizeof(u32)));
-  hipError_t e = hipMemcpy(d_raw, pksk, words * sizeof(u32), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(d_raw);
-    return hip_fail(ctx, e, "packing key upload");
-  }
-  st = load_packing_key_common(ctx, d_raw, from_dimension);
-  (void)hipFree(d_raw);
-  return st;
+  const size_t words = packing_key_words(ctx, from_dimension);
+  DeviceWords raw;
+  HIP_TRY(ctx, raw.alloc(words));
+  hipError_t e = hipMemcpy(raw.p, pksk, words * sizeof(u32), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return hip_fail(ctx, e, "packing key upload");
+  return load_packing_key_common(ctx, raw.p, from_dimension);
 }
 
 int tfhe_packing_key_dimension(const tfhe_context* ctx, size_t* from_dimension) {
@@ -1885,7 +1795,7 @@ int tfhe_packing_key_dimension(const tfhe_context* ctx, size_t* from_dimension) 
 }
 
 static int check_pack_args(tfhe_context* ctx, const void* in, size_t groups, size_t per_group, const void* out) {
-  if (!in || !out) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  TFHE_TRY(check_present(ctx, {in, out}, 1, "null pointer"));
   if (groups == 0 || groups > kMaxBatch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "groups must be in [1, 2^31)");
   if (per_group == 0 || per_group > ctx->N)
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "per_group must be in [1, N]: a GLWE has N coefficients");
@@ -1895,45 +1805,21 @@ static int check_pack_args(tfhe_context* ctx, const void* in, size_t groups, siz
 
 int tfhe_pack_lwe_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_t groups, size_t per_group,
                                uint32_t* glwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if ((st = check_pack_args(ctx, lwe_in, groups, per_group, glwe_out))) return st;
-  const u32 d = (u32)ctx->pksk_dim;
-  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
-  // the decomposer may have been re-aligned since the key was loaded (as for the KSK, the caller keeps them in step)
-  PbsParams P = ctx->pbs;
-  P.log_base = ctx->ks.log_base;
-  P.levels = ctx->ks.levels;
-  P.ignored_bits = ctx->ks.ignored_bits;
-  P.first_shift = ctx->ks.first_shift;
-  // the teams add their partial sums into the output (a memset node under stream capture)
-  HIP_TRY(ctx, hipMemsetAsync(glwe_out, 0, groups * glwe * sizeof(u32), ctx->stream));
-  const size_t chunk = ctx->pack_cols_words / pack_cols_words_per_group(ctx);  // >= 1 by construction
-  for (size_t g0 = 0; g0 < groups; g0 += chunk) {
-    const size_t here = std::min(chunk, groups - g0);
-    HIP_TRY(ctx, launch::pack_transpose(ctx->stream, lwe_in + g0 * per_group * ((size_t)d + 1), here, (u32)per_group, d,
-                                        ctx->pbs.log_n, ctx->d_pack_cols));
-    HIP_TRY(ctx, launch::pack_lwe(ctx->stream, ctx->field, P, ctx->d_tw, ctx->d_pksk, ctx->d_pack_cols, d, here,
-                                  glwe_out + g0 * glwe));
-  }
-  return TFHE_OK;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_pack_args(ctx, lwe_in, groups, per_group, glwe_out));
+  return enqueue_pack(ctx, lwe_in, groups, (u32)per_group, glwe_out);
 }
 
 int tfhe_pack_lwe_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t groups, size_t per_group,
                         uint32_t* glwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if ((st = check_pack_args(ctx, lwe_in, groups, per_group, glwe_out))) return st;
-  const size_t in_words = groups * per_group * (ctx->pksk_dim + 1);
-  const size_t out_words = groups * (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
-  if ((st = ensure_misc(ctx, (in_words + out_words) * sizeof(u32)))) return st;
-  u32* d_in = reinterpret_cast<u32*>(ctx->d_misc);
-  u32* d_out = d_in + in_words;
-  HIP_TRY(ctx, hipMemcpyAsync(d_in, lwe_in, in_words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  if ((st = tfhe_pack_lwe_batch_device(ctx, d_in, groups, per_group, d_out))) return st;
-  HIP_TRY(ctx, hipMemcpyAsync(glwe_out, d_out, out_words * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_pack_args(ctx, lwe_in, groups, per_group, glwe_out));
+  enum { kIn, kOut };
+  Staging s(ctx, {groups * per_group * (ctx->pksk_dim + 1), groups * glwe_words(ctx)});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(kIn, lwe_in));
+  TFHE_TRY(tfhe_pack_lwe_batch_device(ctx, s[kIn], groups, per_group, s[kOut]));
+  return s.download_and_wait(kOut, glwe_out);
 }
 
 // ---------------------------------------------------------------------------------- tree LUT
@@ -1963,8 +1849,7 @@ bool tree_lut_layout(const tfhe_context* ctx, size_t batch, size_t digits, size_
   if (r0 > (double)kMaxBatch) return false;
   const size_t R0 = batch * tables << (log_p * (digits - 1));
   const size_t G1 = digits > 1 ? R0 >> log_p : 0;
-  const size_t n1 = (size_t)ctx->params.lwe_dimension + 1, big1 = (size_t)ctx->big_n + 1;
-  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
+  const size_t n1 = lwe_words(ctx), big1 = big_lwe_words(ctx), glwe = glwe_words(ctx);
   auto pad = [](size_t w) { return (w + 3) & ~(size_t)3; };  // 16-byte buffers
   size_t at = 0;
   auto take = [&](size_t w) { const size_t o = at; at += pad(w); return o; };
@@ -2006,13 +1891,23 @@ int check_tree_lut_keys(tfhe_context* ctx) {
   return TFHE_OK;
 }
 
+// everything a tree-LUT call is refused for before its workspace is looked at; -> the layout of the call
+int check_tree_lut_args(tfhe_context* ctx, const uint32_t* const* digits, size_t d, size_t batch, const void* table,
+                        size_t table_sets, size_t tables, const void* lwe_out, TreeLutLayout* L) {
+  TFHE_TRY(check_present(ctx, {digits, table, lwe_out}, 1, "null pointer"));
+  TFHE_TRY(check_tree_lut_shape(ctx, batch, d, tables, L));
+  for (size_t t = 0; t < d; ++t)
+    if (!digits[t]) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null digit pointer");
+  if (table_sets != 1 && table_sets != batch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "table_sets must be 1 or batch");
+  return check_tree_lut_keys(ctx);
+}
+
 }  // namespace
 
 int tfhe_context_reserve_tree_lut(tfhe_context* ctx, size_t max_batch, size_t max_digits, size_t max_tables) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+  TFHE_TRY(check_ctx(ctx));
   TreeLutLayout L;
-  if ((st = check_tree_lut_shape(ctx, max_batch, max_digits, max_tables, &L))) return st;
+  TFHE_TRY(check_tree_lut_shape(ctx, max_batch, max_digits, max_tables, &L));
   if (L.words <= ctx->tree_ws_words) return TFHE_OK;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return ensure(ctx, &ctx->d_tree_ws, &ctx->tree_ws_words, L.words);
@@ -2020,23 +1915,16 @@ int tfhe_context_reserve_tree_lut(tfhe_context* ctx, size_t max_batch, size_t ma
 
 int tfhe_tree_lut_batch_device(tfhe_context* ctx, const uint32_t* const* digits, size_t d, size_t batch, const uint32_t* table,
                                size_t table_sets, size_t tables, uint32_t* lwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!digits || !table || !lwe_out) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  TFHE_TRY(check_ctx(ctx));
   TreeLutLayout L;
-  if ((st = check_tree_lut_shape(ctx, batch, d, tables, &L))) return st;
-  for (size_t t = 0; t < d; ++t)
-    if (!digits[t]) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null digit pointer");
-  if (table_sets != 1 && table_sets != batch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "table_sets must be 1 or batch");
-  if ((st = check_tree_lut_keys(ctx))) return st;
+  TFHE_TRY(check_tree_lut_args(ctx, digits, d, batch, table, table_sets, tables, lwe_out, &L));
   if (L.words > ctx->tree_ws_words)
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
                 "the call needs " + std::to_string(L.words * sizeof(u32)) + " bytes of tree-LUT workspace, " +
                     std::to_string(ctx->tree_ws_words * sizeof(u32)) + " are reserved (tfhe_context_reserve_tree_lut)");
   const u32 log_p = ctx->params.log_p, log_n = ctx->pbs.log_n, n = ctx->params.lwe_dimension;
   const u32 log_rep = log_n - log_p;
-  const size_t n1 = (size_t)n + 1, big1 = (size_t)ctx->big_n + 1;
-  const size_t glwe = (size_t)(ctx->params.glwe_dimension + 1) * ctx->N;
+  const size_t n1 = lwe_words(ctx);
   u32* ws = ctx->d_tree_ws;
   u32 *ks_digit = ws + L.ks_digit, *lwe = ws + L.lwe, *tv = ws + L.tv, *state = ws + L.state, *glwes = ws + L.glwe;
   u32* results[2] = {ws + L.res_a, ws + L.res_b};
@@ -2052,28 +1940,16 @@ int tfhe_tree_lut_batch_device(tfhe_context* ctx, const uint32_t* const* digits,
   // level 0: rotation (row, table, h) bootstraps c_0[row] against sub-table h of (set, table)
   size_t count = L.rotations;
   const u32* digit = nullptr;
-  if ((st = digit_of(0, &digit))) return st;
+  TFHE_TRY(digit_of(0, &digit));
   HIP_TRY(ctx, launch::tree_lut_expand(s, digit, count, count / batch, (u32)n1, lwe));
   HIP_TRY(ctx, launch::tree_lut_test_vectors(s, table, table_sets == 1 ? 0 : tables << (log_p * d), count, count / batch, log_p, log_n, tv));
   u32* cur = d == 1 && ctx->ks_first ? lwe_out : results[0];
   HIP_TRY(ctx, enqueue_blind_rotate(ctx, lwe, count, tv, count, nullptr, cur, AccSource{false, 0u, state}));
-  // the packing decomposer (tfhe_pack_lwe_batch_device)
-  PbsParams PK = ctx->pbs;
-  PK.log_base = ctx->ks.log_base;
-  PK.levels = ctx->ks.levels;
-  PK.ignored_bits = ctx->ks.ignored_bits;
-  PK.first_shift = ctx->ks.first_shift;
-  const size_t chunk = ctx->pack_cols_words / pack_cols_words_per_group(ctx);  // >= 1 by construction
   for (size_t t = 1; t < d; ++t) {
     // G_h = Pack of the B results [h B, (h + 1) B), each on N / B neighbouring coefficients
     const size_t groups = count >> log_p;
-    HIP_TRY(ctx, hipMemsetAsync(glwes, 0, groups * glwe * sizeof(u32), s));
-    for (size_t g0 = 0; g0 < groups; g0 += chunk) {
-      const size_t here = std::min(chunk, groups - g0);
-      HIP_TRY(ctx, launch::pack_transpose(s, cur + (g0 << log_p) * big1, here, 1u << log_p, ctx->big_n, log_n, ctx->d_pack_cols, log_rep));
-      HIP_TRY(ctx, launch::pack_lwe(s, ctx->field, PK, ctx->d_tw, ctx->d_pksk, ctx->d_pack_cols, ctx->big_n, here, glwes + g0 * glwe));
-    }
-    if ((st = digit_of(t, &digit))) return st;
+    TFHE_TRY(enqueue_pack(ctx, cur, groups, 1u << log_p, glwes, log_rep));
+    TFHE_TRY(digit_of(t, &digit));
     HIP_TRY(ctx, launch::tree_lut_expand(s, digit, groups, groups / batch, (u32)n1, lwe));
     u32* next = t + 1 == d && ctx->ks_first ? lwe_out : results[t & 1];
     HIP_TRY(ctx, enqueue_blind_rotate(ctx, lwe, groups, glwes, groups, nullptr, next, AccSource{true, (1u << log_rep) >> 1, state}));
@@ -2086,32 +1962,24 @@ int tfhe_tree_lut_batch_device(tfhe_context* ctx, const uint32_t* const* digits,
 
 int tfhe_tree_lut_batch(tfhe_context* ctx, const uint32_t* const* digits, size_t d, size_t batch, const uint32_t* table,
                         size_t table_sets, size_t tables, uint32_t* lwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!digits || !table || !lwe_out) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  TFHE_TRY(check_ctx(ctx));
   TreeLutLayout L;
-  if ((st = check_tree_lut_shape(ctx, batch, d, tables, &L))) return st;
-  for (size_t t = 0; t < d; ++t)
-    if (!digits[t]) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null digit pointer");
-  if (table_sets != 1 && table_sets != batch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "table_sets must be 1 or batch");
-  if ((st = check_tree_lut_keys(ctx))) return st;
-  if ((st = tfhe_context_reserve_tree_lut(ctx, batch, d, tables))) return st;
+  TFHE_TRY(check_tree_lut_args(ctx, digits, d, batch, table, table_sets, tables, lwe_out, &L));
+  TFHE_TRY(tfhe_context_reserve_tree_lut(ctx, batch, d, tables));
   const size_t io = io_words(ctx);
-  const size_t digit_words = batch * io, table_words = table_sets * tables << (ctx->params.log_p * d), out_words = batch * tables * io;
-  if ((st = ensure_misc(ctx, (d * digit_words + table_words + out_words) * sizeof(u32)))) return st;
-  u32* d_digits = reinterpret_cast<u32*>(ctx->d_misc);
-  u32* d_table = d_digits + d * digit_words;
-  u32* d_out = d_table + table_words;
+  std::vector<size_t> words(d, batch * io);  // segments 0 .. d-1: the digits; then the table and the result
+  words.push_back(table_sets * tables << (ctx->params.log_p * d));
+  words.push_back(batch * tables * io);
+  Staging s(ctx, words);
+  TFHE_TRY(s.reserve());
   std::vector<const uint32_t*> ptrs(d);
   for (size_t t = 0; t < d; ++t) {
-    HIP_TRY(ctx, hipMemcpyAsync(d_digits + t * digit_words, digits[t], digit_words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-    ptrs[t] = d_digits + t * digit_words;
+    TFHE_TRY(s.upload(t, digits[t]));
+    ptrs[t] = s[t];
   }
-  HIP_TRY(ctx, hipMemcpyAsync(d_table, table, table_words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  if ((st = tfhe_tree_lut_batch_device(ctx, ptrs.data(), d, batch, d_table, table_sets, tables, d_out))) return st;
-  HIP_TRY(ctx, hipMemcpyAsync(lwe_out, d_out, out_words * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  TFHE_TRY(s.upload(d, table));
+  TFHE_TRY(tfhe_tree_lut_batch_device(ctx, ptrs.data(), d, batch, s[d], table_sets, tables, s[d + 1]));
+  return s.download_and_wait(d + 1, lwe_out);
 }
 
 // ---------------------------------------------------------------------------------- on-disk format
@@ -2277,14 +2145,13 @@ int tfhe_construct_test_vector_boolean(const tfhe_params* params, const uint32_t
 // test vector of lut[x] = truth[x mod 2^m]; and()/or() (boolean.rs:9-53) are the m = 2 case.
 static int lut_gate_device(tfhe_context* ctx, const u32* truth, u32 inputs, const u32* const* cts,
                            size_t batch, u32* lwe_out) {
-  int st;
-  if (!truth || !cts || !lwe_out || batch == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
+  TFHE_TRY(check_present(ctx, {truth, cts, lwe_out}, batch));
   if (inputs == 0 || inputs > ctx->params.log_p || inputs > 8)
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "gate inputs must be 1..min(log_p, 8): the plaintext space holds log_p bits");
   for (u32 i = 0; i < inputs; ++i)
     if (!cts[i]) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null input ciphertext");
   if (!ctx->have_key) return fail(ctx, TFHE_ERR_NO_KEY, "load the bootstrapping key first");
-  if ((st = reserve(ctx, batch))) return st;
+  TFHE_TRY(reserve(ctx, batch));
   const size_t words = batch * io_words(ctx);
   const u32 entries = 1u << inputs;
   tfhe_context::GateTv* slot = nullptr;
@@ -2298,9 +2165,9 @@ static int lut_gate_device(tfhe_context* ctx, const u32* truth, u32 inputs, cons
     const u32 pm = 1u << ctx->params.log_p;
     std::vector<u32> lut(pm), tv(ctx->N);
     for (u32 x = 0; x < pm; ++x) lut[x] = truth[x & (entries - 1)];  // test_vector.rs:16 for m = 2
-    if ((st = test_from_lut(&ctx->params, lut.data(), pm, tv.data())))
+    if (int st = test_from_lut(&ctx->params, lut.data(), pm, tv.data()))
       return fail(ctx, st, "truth table / plaintext space mismatch");
-    if ((st = check_tv_host(ctx, tv.data(), ctx->N))) return st;
+    TFHE_TRY(check_tv_host(ctx, tv.data(), ctx->N));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->gate_tvs.size() < kMaxGateTvs) {
       ctx->gate_tvs.emplace_back();
@@ -2326,8 +2193,7 @@ static int lut_gate_device(tfhe_context* ctx, const u32* truth, u32 inputs, cons
 
 int tfhe_gate_batch_device(tfhe_context* ctx, const uint32_t truth[4], const uint32_t* ct0,
                            const uint32_t* ct1, size_t batch, uint32_t* lwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+  TFHE_TRY(check_ctx(ctx));
   if (!ct0 || !ct1) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
   const u32* cts[2] = {ct0, ct1};
   return lut_gate_device(ctx, truth, 2, cts, batch, lwe_out);
@@ -2335,31 +2201,25 @@ int tfhe_gate_batch_device(tfhe_context* ctx, const uint32_t truth[4], const uin
 
 int tfhe_lut_gate_batch_device(tfhe_context* ctx, const uint32_t* truth, uint32_t inputs,
                                const uint32_t* const* cts, size_t batch, uint32_t* lwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+  TFHE_TRY(check_ctx(ctx));
   return lut_gate_device(ctx, truth, inputs, cts, batch, lwe_out);
 }
 
 int tfhe_lut_gate_batch(tfhe_context* ctx, const uint32_t* truth, uint32_t inputs, const uint32_t* const* cts,
                         size_t batch, uint32_t* lwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
+  TFHE_TRY(check_ctx(ctx));
   if (!truth || !cts || !lwe_out || batch == 0 || inputs == 0 || inputs > 8)
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch / bad input count");
-  const size_t words = batch * io_words(ctx);
-  if ((st = ensure_misc(ctx, (size_t)(inputs + 1) * words * sizeof(u32)))) return st;
-  u32* d = reinterpret_cast<u32*>(ctx->d_misc);
+  Staging s(ctx, std::vector<size_t>(inputs + 1, batch * io_words(ctx)));  // the inputs, then the result
+  TFHE_TRY(s.reserve());
   const u32* d_cts[8];
   for (u32 i = 0; i < inputs; ++i) {
     if (!cts[i]) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null input ciphertext");
-    HIP_TRY(ctx, hipMemcpyAsync(d + i * words, cts[i], words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-    d_cts[i] = d + i * words;
+    TFHE_TRY(s.upload(i, cts[i]));
+    d_cts[i] = s[i];
   }
-  u32* d_out = d + (size_t)inputs * words;
-  if ((st = lut_gate_device(ctx, truth, inputs, d_cts, batch, d_out))) return st;
-  HIP_TRY(ctx, hipMemcpyAsync(lwe_out, d_out, words * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  TFHE_TRY(lut_gate_device(ctx, truth, inputs, d_cts, batch, s[inputs]));
+  return s.download_and_wait(inputs, lwe_out);
 }
 
 int tfhe_gate_batch(tfhe_context* ctx, const uint32_t truth[4], const uint32_t* ct0,
@@ -2371,9 +2231,8 @@ int tfhe_gate_batch(tfhe_context* ctx, const uint32_t truth[4], const uint32_t* 
 
 // NOT needs no bootstrap: an encryption of 1 - m is (-a, enc(1) - b), enc(1) = 1 << (32 - log_p - padding)
 int tfhe_lwe_not_batch_device(tfhe_context* ctx, const uint32_t* ct, size_t batch, uint32_t* lwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!ct || !lwe_out || batch == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {ct, lwe_out}, batch));
   const size_t n1 = io_words(ctx);
   const u32 one = 1u << (32 - ctx->params.log_p - ctx->params.padding_bits);
   HIP_TRY(ctx, launch::lwe_linear(ctx->stream, 0xFFFFFFFFu, ct, 0u, nullptr, batch * n1, lwe_out, n1, one));
@@ -2381,17 +2240,14 @@ int tfhe_lwe_not_batch_device(tfhe_context* ctx, const uint32_t* ct, size_t batc
 }
 
 int tfhe_lwe_not_batch(tfhe_context* ctx, const uint32_t* ct, size_t batch, uint32_t* lwe_out) {
-  int st = check_ctx(ctx);
-  if (st) return st;
-  if (!ct || !lwe_out || batch == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer / empty batch");
-  const size_t words = batch * io_words(ctx);
-  if ((st = ensure_misc(ctx, 2 * words * sizeof(u32)))) return st;
-  u32* d = reinterpret_cast<u32*>(ctx->d_misc);
-  HIP_TRY(ctx, hipMemcpyAsync(d, ct, words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-  if ((st = tfhe_lwe_not_batch_device(ctx, d, batch, d + words))) return st;
-  HIP_TRY(ctx, hipMemcpyAsync(lwe_out, d + words, words * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return TFHE_OK;
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {ct, lwe_out}, batch));
+  enum { kIn, kOut };
+  Staging s(ctx, {batch * io_words(ctx), batch * io_words(ctx)});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(kIn, ct));
+  TFHE_TRY(tfhe_lwe_not_batch_device(ctx, s[kIn], batch, s[kOut]));
+  return s.download_and_wait(kOut, lwe_out);
 }
 
 }  // extern "C"

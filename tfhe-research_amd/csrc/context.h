@@ -109,14 +109,36 @@ inline int hip_fail(tfhe_context* ctx, hipError_t e, const char* what) {
 // key device to device (peer copy over xGMI, or a plain device copy when both contexts sit on one GPU) on dst's
 // stream; dst must have been created with the same parameters and backend (capi.cpp)
 int adopt_prepared_key(tfhe_context* dst, const tfhe_context* src);
+
+// Sizes, each spelled out once.  32-bit words unless the name says otherwise.
+inline size_t glwe_words(const tfhe_context* ctx) { return (size_t)(ctx->params.glwe_dimension + 1) * ctx->N; }
+inline size_t lwe_words(const tfhe_context* ctx) { return (size_t)ctx->params.lwe_dimension + 1; }  // an LWE at n
+inline size_t big_lwe_words(const tfhe_context* ctx) { return (size_t)ctx->big_n + 1; }             // an LWE at k*N
 // words of one ciphertext at the bootstrap boundary (n+1, or k*N+1 in KS-first order)
-size_t io_words(const tfhe_context* ctx);
+inline size_t io_words(const tfhe_context* ctx) { return ctx->ks_first ? big_lwe_words(ctx) : lwe_words(ctx); }
+inline size_t ggsw_words(const tfhe_context* ctx) { return (size_t)ctx->R * glwe_words(ctx); }  // a raw GGSW
+inline size_t prepared_ggsw_words(const tfhe_context* ctx) { return ggsw_words(ctx) * ctx->parts; }  // 8-byte words
+inline size_t ksk_words(const tfhe_context* ctx) { return (size_t)ctx->big_n * ctx->ks.levels * lwe_words(ctx); }
+// the raw packing key from an LWE key of `from_dimension` bits: one GLWE row per (key bit, KS level)
+inline size_t packing_key_words(const tfhe_context* ctx, size_t from_dimension) {
+  return from_dimension * ctx->ks.levels * glwe_words(ctx);
+}
+inline size_t prepared_bsk_bytes(const tfhe_context* ctx, size_t ggsws) {
+  return ggsws * prepared_ggsw_words(ctx) * sizeof(u64);
+}
 
 }  // namespace host
 }  // namespace tfhe
 
+// return from the calling function unless a HIP call / a call that returns a tfhe status succeeded
 #define HIP_TRY(ctx, expr)                                              \
   do {                                                                  \
     hipError_t _e = (expr);                                             \
     if (_e != hipSuccess) return tfhe::host::hip_fail((ctx), _e, #expr); \
+  } while (0)
+
+#define TFHE_TRY(expr)          \
+  do {                          \
+    int _st = (expr);           \
+    if (_st != TFHE_OK) return _st; \
   } while (0)
