@@ -127,3 +127,40 @@ def test_wrong_bits_probes_need_a_dev_build():
     for flag in ("-DTFHE_DEV_BUILD", "-DTFHE_PROBE_HOT_KEY=1"):
         with pytest.raises(ValueError):
             builder._compile("/tmp/never.so", [flag], False, "never")
+
+
+def _preprocessor_tested_names(text: str):
+    """identifiers a preprocessor conditional tests: the operands of #if / #ifdef / #ifndef / #elif lines (defined(X) included),
+    continuation lines joined"""
+    text = re.sub(r"\\\n", " ", text)
+    names = set()
+    for line in re.findall(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b(.*)$", text, flags=re.M):
+        line = re.sub(r"//.*$|/\*.*?\*/", "", line)
+        names.update(n for n in re.findall(r"[A-Za-z_]\w*", line) if n != "defined")
+    return names
+
+
+def test_device_sources_have_no_tuning_switches():
+    """The device sources build ONE configuration: the only TFHE_* names a preprocessor conditional may test are the dev /
+    probe instrumentation (csrc/dev_switches.h, the TFHE_DEV_* build narrowing, TFHE_FFT_TRACK_ERROR); a compile-time tuning or
+    experiment switch (#ifndef TFHE_X / #define TFHE_X <default>) does not come back, and the product recipe passes none."""
+    csrc = os.path.join(ROOT, "tfhe-research_amd", "csrc")
+    allowed = re.compile(r"TFHE_DEV_\w+|TFHE_PROBE_\w+|TFHE_ANY_PROBE|TFHE_FFT_TRACK_ERROR")
+    # what platform.h tests to tell hipcc from the emulator's g++: the compiler's own names, no TFHE_* one
+    platform_names = {"__HIPCC__", "__HIP_DEVICE_COMPILE__"}
+    scanned = 0
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".h", ".hip")):
+            continue
+        scanned += 1
+        tested = _preprocessor_tested_names(open(os.path.join(csrc, f)).read())
+        if f == "platform.h":
+            assert tested == platform_names, tested
+        stray = sorted(n for n in tested if n.startswith("TFHE_") and not allowed.fullmatch(n))
+        assert not stray, f"{f}: preprocessor conditionals on {stray}"
+    assert scanned >= 10
+    # build.py: the product recipe passes no -DTFHE_ flag; the two it names are build_probe's instrumentation
+    recipe = open(os.path.join(ROOT, "tfhe-research_amd", "build.py")).read()
+    product, probe = recipe.split("def build_probe")
+    assert "-DTFHE_" not in product
+    assert set(re.findall(r"-DTFHE_\w+", probe)) == {"-DTFHE_DEV_FIELD_FFT_ONLY", "-DTFHE_FFT_TRACK_ERROR"}

@@ -48,7 +48,6 @@ def _compile(lib: str, extra, verbose: bool, tag: str, force: bool = False) -> s
         if "TFHE_DEV_BUILD" in flag or "TFHE_PROBE_" in flag:
             raise ValueError(f"build.py does not build dev/probe libraries: {flag} (use tools/dev_build.sh)")
     common = [_hipcc(), "-O3", "-std=c++17", "-ffp-contract=off", "--offload-arch=gfx950", "-fPIC",
-              "-DTFHE_WAVES_PER_SIMD_FP=2", "-DTFHE_WAVES_PER_SIMD_GL=2",
               "-I", os.path.join(ROOT, "include"), "-I", CSRC] + list(extra)
     objdir = os.path.join(HERE, "_build", tag)
     os.makedirs(objdir, exist_ok=True)

@@ -115,12 +115,6 @@ struct FftField {
   static constexpr double kMaxError = 0.25;
 
   TFHE_HD static elem zero() { return elem{0.0, 0.0}; }
-  TFHE_HD static elem add(elem a, elem b) { return elem{a.re + b.re, a.im + b.im}; }
-  TFHE_HD static elem sub(elem a, elem b) { return elem{a.re - b.re, a.im - b.im}; }
-  // complex product, 2 multiplications + 2 FMAs
-  TFHE_HD static elem mul(elem a, elem w) {
-    return elem{__builtin_fma(a.re, w.re, -(a.im * w.im)), __builtin_fma(a.re, w.im, a.im * w.re)};
-  }
   // The forward butterfly (u + w b, u - w b) in SIX fused multiply-adds instead of a complex product (4) and two
   // complex sums (4): y0 = u + w b is two chained FMAs per component, and y1 = u - w b = 2 u - y0 one more.
   // Its rounding stays inside the eta the bound above is evaluated with.  With a = u, U = 2^-53, A = |a|, B = |b|:
@@ -132,10 +126,6 @@ struct FftField {
   // eigenvalue of [[13, 17.75], [17.75, 24.305]] is 37.28), and a stage multiplies the 2-norm of its input by exactly
   // sqrt 2: the stage's relative perturbation is <= 6.11 / sqrt 2 = 4.32 U < eta = 7.1 U -- Higham's Theorem 24.2 only
   // needs ||dA_k||_2 <= eta ||A_k||_2 per stage, whatever the order of the operations inside the butterfly.
-#ifndef TFHE_FFT_FMA_BUTTERFLY
-#define TFHE_FFT_FMA_BUTTERFLY 1  // 0: the 8-instruction product + two sums (A/B builds only)
-#endif
-  static constexpr bool kFusedForwardButterfly = TFHE_FFT_FMA_BUTTERFLY != 0;
   TFHE_HD static void butterfly_forward(elem u, elem b, elem w, elem& y0, elem& y1) {
     const double re = __builtin_fma(-b.im, w.im, __builtin_fma(b.re, w.re, u.re));
     const double im = __builtin_fma(b.im, w.re, __builtin_fma(b.re, w.im, u.im));
@@ -151,21 +141,16 @@ struct FftField {
   }
   // the low register windows' twiddles are read a transpose ahead of their pass (wave_ntt.h::PassTwiddles)
   static constexpr bool kPreloadTwiddles = true;
-  // a * (-conj(w)): the inverse butterfly's twiddle
-  TFHE_HD static elem mul_inverse(elem a, elem w) {
-    return elem{-__builtin_fma(a.re, w.re, a.im * w.im), __builtin_fma(a.re, w.im, -(a.im * w.re))};
-  }
   // acc + d * k: 4 FMAs
   static constexpr bool kFusedMac = true;
   TFHE_HD static elem mul_add(elem d, elem k, elem acc) {
     return elem{__builtin_fma(-d.im, k.im, __builtin_fma(d.re, k.re, acc.re)),
                 __builtin_fma(d.im, k.re, __builtin_fma(d.re, k.im, acc.im))};
   }
-  // table entry the inverse butterfly of node h + i reads (mul_inverse conjugates it)
+  // table entry the inverse butterfly of node h + i reads (butterfly_inverse conjugates it)
   TFHE_HD static constexpr int inverse_twiddle_index(int h, int i) { return h + i; }
   static constexpr int kSmallBits = 31;
   static constexpr int kMaxLogBase = 16;  // far beyond what the error bound admits
-  TFHE_HD static elem mul_small(elem a, elem w) { return mul(a, w); }
   static constexpr bool kFuseFirstTwo = false;
   TFHE_HD static void radix4_small(elem&, elem&, elem&, elem&, elem, elem, elem, elem, elem) {}
   TFHE_HD static elem radix8_small_v(elem, elem, elem, elem, elem, elem, elem, elem) { return zero(); }

@@ -18,25 +18,17 @@ namespace {
 // (With two waves -- 16 elements, 256 VGPRs -- a k = 2 team is 6 waves on a CU that then has room
 // for 8: SIMDs end up with 2, 2, 1, 1 waves and the team runs at the pace of the shared ones.  Four
 // waves per polynomial fit 170 VGPRs, so the 12-wave team sits 3, 3, 3, 3.)
-#ifndef TFHE_GROUP_N2048
-#define TFHE_GROUP_N2048 4
-#endif
-#ifndef TFHE_GROUP_N2048_FFT
-#define TFHE_GROUP_N2048_FFT 4
-#endif
 // (N = 1024 over two waves was measured too: 97.9 ms against 64.0 ms per cfg2 batch -- a fourth
-// register pass and cross-wave barriers cost more than the third wave per SIMD gives.)
-// (experiment flag: the complex transform at N = 1024 over two waves per polynomial -- 4 elements per lane, registers
-// for two samples per team; profiles/r03_kernel_ab.txt)
-#ifndef TFHE_GROUP_N1024_FFT
-#define TFHE_GROUP_N1024_FFT 1
-#endif
+// register pass and cross-wave barriers cost more than the third wave per SIMD gives; the complex transform at
+// N = 1024 over two waves, 4 elements per lane with registers for two samples per team, lost as well:
+// profiles/r03_kernel_ab.txt.)
+// The complex transform has N/2 elements of 16 bytes: four waves per polynomial at N = 2048 hold 4 of them per lane
+// and array (two waves, 8 per lane -- the register footprint of one wave at N = 1024 -- make one 6-wave team per CU:
+// see field_shape_ok).
+constexpr int kGroupN2048 = 4;
 template <class F, int LOGN>
 struct GroupOf {
-  // the complex transform has N/2 elements of 16 bytes: two waves per polynomial at N = 2048 hold 8 of
-  // them per lane and array (the register footprint of one wave at N = 1024)
-  static constexpr int value = (LOGN >= 11) ? (F::kLogShrink ? TFHE_GROUP_N2048_FFT : TFHE_GROUP_N2048)
-                               : (LOGN == 10 && F::kLogShrink) ? TFHE_GROUP_N1024_FFT : 1;
+  static constexpr int value = (LOGN >= 11) ? kGroupN2048 : 1;
 };
 
 // Shapes a transform policy is instantiated for.  The complex transform (field_fft.h) holds two
@@ -44,16 +36,13 @@ struct GroupOf {
 // per polynomial and 4 at N = 512 (four register passes of two bits); N = 2048 is bit-exact both over two waves per
 // polynomial (8 elements per lane, one 6-wave team per CU: 137 ms per 1024 cfg5 bootstraps) and over four (4 elements
 // per lane, five register passes, 12 waves: 79.2 ms) but does not beat the 42-bit field's 77.2 ms -- a 12-wave team
-// is bound by its barriers, not its arithmetic (profiles/r02_kernel_ab.txt) -- so it is not instantiated.
-// the complex transform at N = 2048: over four waves per polynomial (4 elements per lane, five register passes) with
-// TWO samples per team -- 57.4 ms per 1024 cfg5 bootstraps against 77.5 ms for the 42-bit field and 80.1 ms with one
-// sample per team (profiles/r03_kernel_ab.txt); 0: not instantiated (round 2's state)
-#ifndef TFHE_FFT_N2048
-#define TFHE_FFT_N2048 1
-#endif
+// is bound by its barriers, not its arithmetic (profiles/r02_kernel_ab.txt).  What is instantiated at N = 2048 is
+// the complex transform over four waves per polynomial (4 elements per lane, five register passes) with TWO samples
+// per team -- 57.4 ms per 1024 cfg5 bootstraps against 77.5 ms for the 42-bit field and 80.1 ms with one sample per
+// team (profiles/r03_kernel_ab.txt).
 template <class F, int LOGN>
 constexpr bool field_shape_ok() {
-  return F::kLogShrink == 0 || LOGN == 10 || LOGN == 9 || (TFHE_FFT_N2048 && LOGN == 11);
+  return F::kLogShrink == 0 || (LOGN >= 9 && LOGN <= 11);
 }
 
 // bytes of the twiddle table of a field at ring degree 2^LOGN
@@ -132,26 +121,12 @@ struct DeviceWave {
   __device__ __forceinline__ const Elem* twiddles_uniform() const { return twg_; }
   __device__ __forceinline__ u32 uniform(u32 v) const { return __builtin_amdgcn_readfirstlane(v); }
   // *p += v on an LDS word this lane owns: one ds_add_u32 (no return value) instead of a read, an add and a write
-#ifndef TFHE_LDS_ADD
-#define TFHE_LDS_ADD 1
-#endif
   __device__ __forceinline__ void lds_add(u32* p, u32 v) const {
-    if (TFHE_LDS_ADD) (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else *p += v;
+    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   }
   // compiler-only barrier: memory operations are not moved across it
   __device__ __forceinline__ void compiler_fence() const { asm volatile("" ::: "memory"); }
 };
-
-#ifndef TFHE_WAVES_PER_SIMD_GL
-#define TFHE_WAVES_PER_SIMD_GL 2
-#endif
-#ifndef TFHE_WAVES_PER_SIMD_FP
-#define TFHE_WAVES_PER_SIMD_FP 2
-#endif
-#ifndef TFHE_WAVES_PER_SIMD_E8  // shapes with 8 ring coefficients per lane and array
-#define TFHE_WAVES_PER_SIMD_E8 3
-#endif
 
 // One workgroup = one team = K+1 polynomial groups of G waves = one LWE sample.
 // LDS (dynamic, 16-B aligned base, no static LDS): [ twiddles (N+2) x 8 B ][ group c: EXB transpose/
@@ -160,12 +135,9 @@ struct DeviceWave {
 // where one 12-wave team per CU leaves LDS to spare and the barriers of a 768-thread workgroup are
 // dear (+5 % at cfg5).  One at N = 1024 (4 teams per CU would need 192 KiB with two) and at N = 512
 // (two fit, 139 KiB, but measured no gain at cfg3: 114.6 vs 116.1 ms per 4096 gates).
-#ifndef TFHE_EXB_N512
-#define TFHE_EXB_N512 1
-#endif
 template <int LOGN>
 struct ExchangeBuffersOf {
-  static constexpr int value = (LOGN >= 11) ? 2 : (LOGN == 9) ? TFHE_EXB_N512 : 1;
+  static constexpr int value = (LOGN >= 11) ? 2 : 1;
 };
 
 // (Two and four teams per workgroup -- one barrier sequence, one twiddle table, the second wave that asks for
@@ -175,22 +147,9 @@ struct ExchangeBuffersOf {
 // Samples per team in the blind rotation (pbs_wave.h::external_product_team_multi): two where the registers allow it
 // (the complex transform with 4 elements per lane) AND the kernel waits on its key stream or its barriers -- the
 // twelve-wave team of N = 2048 and the many digit rows of N = 512, k = 2.  Measured per shape, profiles/r03_kernel_ab.txt.
-#ifndef TFHE_NS_N2048
-#define TFHE_NS_N2048 2
-#endif
-#ifndef TFHE_NS_N512_K2
-#define TFHE_NS_N512_K2 2
-#endif
-#ifndef TFHE_NS_N512_K1
-#define TFHE_NS_N512_K1 1
-#endif
-#ifndef TFHE_NS_N1024
-#define TFHE_NS_N1024 1
-#endif
 template <class F, int LOGN, int K>
 struct SamplesPerTeam {
-  static constexpr int value = !F::kLogShrink ? 1 : LOGN == 11 ? TFHE_NS_N2048 : LOGN == 9 ? (K == 2 ? TFHE_NS_N512_K2 : TFHE_NS_N512_K1)
-                               : LOGN == 10 ? TFHE_NS_N1024 : 1;
+  static constexpr int value = (F::kLogShrink && (LOGN == 11 || (LOGN == 9 && K == 2))) ? 2 : 1;
 };
 
 template <class F, int LOGN, int K, int NS_ = SamplesPerTeam<F, LOGN, K>::value>
@@ -205,8 +164,9 @@ struct TeamCfg {
   // the working copy of the table: (N + 18) 8-byte elements, or N/2 16-byte ones
   static constexpr size_t kTwBytes = (size_t)staged_twiddle_words<F, LOGN>() * sizeof(typename F::elem);  // multiple of 16
   static constexpr size_t kLds = kTwBytes + (size_t)(K + 1) * kGroupLds;
-  static constexpr int kMinWavesGl = (NttShape<LOGN, G>::kE == 8) ? TFHE_WAVES_PER_SIMD_E8 : TFHE_WAVES_PER_SIMD_GL;
-  static constexpr int kMinWavesFp = (NttShape<LOGN, G>::kE == 8) ? TFHE_WAVES_PER_SIMD_E8 : TFHE_WAVES_PER_SIMD_FP;
+  // waves per SIMD the kernels' register budget is set for: three in the shapes with 8 ring coefficients per lane and
+  // array, two elsewhere
+  static constexpr int kMinWaves = (NttShape<LOGN, G>::kE == 8) ? 3 : 2;
 };
 
 template <class F, int LOGN, int K, int NS = SamplesPerTeam<F, LOGN, K>::value>
@@ -279,10 +239,7 @@ __global__ void __launch_bounds__(256) bsk_prepare_kernel(const typename F::elem
 
 // ------------------------------------------------------------------------------ blind rotation
 template <class F, int LOGN, int K>
-__global__ void __launch_bounds__((TeamCfg<F, LOGN, K>::kThreads),
-                                  (F::kId == FpField::kId || F::kId == Fp49Field::kId || F::kId == FftField::kId
-                                       ? TeamCfg<F, LOGN, K>::kMinWavesFp
-                                       : TeamCfg<F, LOGN, K>::kMinWavesGl))
+__global__ void __launch_bounds__((TeamCfg<F, LOGN, K>::kThreads), (TeamCfg<F, LOGN, K>::kMinWaves))
 blind_rotate_kernel(PbsParams P, const typename F::elem* __restrict__ tw,
                     const u32* __restrict__ lwe_in, size_t batch, const u32* __restrict__ tv,
                     size_t tv_stride, const typename F::elem* __restrict__ bsk,
@@ -309,18 +266,6 @@ blind_rotate_kernel(PbsParams P, const typename F::elem* __restrict__ tw,
     tvs[s] = tv + sample[s] * tv_stride;
   }
 
-  // (TFHE_STAGGER: experiment -- teams that are likely to share a CU start a fraction of a level apart, so that one team's
-  // multiply-accumulate (key fill) overlaps another's transforms (VALU); units of 64 cycles per phase step)
-#ifndef TFHE_STAGGER
-#define TFHE_STAGGER 0
-#endif
-#ifndef TFHE_STAGGER_SHIFT
-#define TFHE_STAGGER_SHIFT 8
-#endif
-  if (TFHE_STAGGER > 0) {
-    const unsigned phase = (blockIdx.x >> TFHE_STAGGER_SHIFT) & 3u;
-    for (unsigned i = 0; i < phase; ++i) __builtin_amdgcn_s_sleep(TFHE_STAGGER);
-  }
   const u32* resume[NS];
 #pragma unroll
   for (int s = 0; s < NS; ++s) resume[s] = i_begin > 0 ? glwe_state + sample[s] * (size_t)(K + 1) * N : nullptr;  // (null state: one launch)
@@ -395,11 +340,9 @@ struct PairCfg {
   static constexpr size_t kLds = kTwBytes + 2 * (size_t)kBufferBytes + 2 * (size_t)N * 4;
 };
 
-#ifndef TFHE_PAIR_MIN_WAVES
-#define TFHE_PAIR_MIN_WAVES 2
-#endif
+constexpr int kPairMinWaves = 2;  // 2 waves per SIMD = 8 samples per CU, at the N = 1024 kernel's register footprint
 template <class F, int LOGN>
-__global__ void __launch_bounds__(64, TFHE_PAIR_MIN_WAVES)
+__global__ void __launch_bounds__(64, kPairMinWaves)
 blind_rotate_pair_kernel(PbsParams P, const typename F::elem* __restrict__ tw, const u32* __restrict__ lwe_in, size_t batch,
                          const u32* __restrict__ tv, size_t tv_stride, const typename F::elem* __restrict__ bsk,
                          u32* glwe_out, u32* __restrict__ lwe_extracted, u32 i_begin, u32 i_end, u32* glwe_state) {
@@ -469,11 +412,8 @@ struct RotateKernelPair {
   static constexpr int kWaves = 1;
   static auto get() { return blind_rotate_pair_kernel<FftField, LOGN>; }
 };
-#ifndef TFHE_PAIR_KERNEL
-#define TFHE_PAIR_KERNEL 1  // 0: A/B builds that keep the two-wave team at N = 512, k = 1 (the key keeps the pair layout)
-#endif
 template <class F, int LOGN, int K>
-using PairOrTeamKernel = typename std::conditional<(TFHE_PAIR_KERNEL && pair_shape<F, LOGN, K>()), RotateKernelPair<LOGN, K>, RotateKernel<F, LOGN, K>>::type;
+using PairOrTeamKernel = typename std::conditional<pair_shape<F, LOGN, K>(), RotateKernelPair<LOGN, K>, RotateKernel<F, LOGN, K>>::type;
 
 // ------------------------------------------------------------------------------ blind rotation, wide team
 // The latency shape (pbs_wave.h::blind_rotate_team_wide): 2 (K+1) waves per sample -- wave (c, q) transforms half of
@@ -527,11 +467,9 @@ struct WideCfg {
 // kernel (run-time level count, key chunks one ahead).  Register budget: a k = 1 team is four waves, one per SIMD, and
 // one team per CU is all its LDS allows -- a wave may use the SIMD's whole file (512 registers: the allocator takes
 // AGPRs beyond 256): 224 for the ring; a k = 2 team's six waves put two on two of the SIMDs: 256 each, 112 for the ring.
-#ifndef TFHE_WIDE_MIN_WAVES_K2
-#define TFHE_WIDE_MIN_WAVES_K2 2
-#endif
+constexpr int kWideMinWaves = 2;  // waves per SIMD of the generic kernel and of a k = 2 team (its six waves double up on two SIMDs)
 template <class F, int LOGN, int K, int LEVELS>
-__global__ void __launch_bounds__((WideCfg<F, LOGN, K>::kThreads), (K == 1 && LEVELS > 0 ? 1 : TFHE_WIDE_MIN_WAVES_K2))
+__global__ void __launch_bounds__((WideCfg<F, LOGN, K>::kThreads), (K == 1 && LEVELS > 0 ? 1 : kWideMinWaves))
 blind_rotate_wide_kernel(PbsParams P, const typename F::elem* __restrict__ tw, const u32* __restrict__ lwe_in, size_t batch,
                          const u32* __restrict__ tv, size_t tv_stride, const typename F::elem* __restrict__ bsk,
                          u32* glwe_out, u32* __restrict__ lwe_extracted, u32 i_begin, u32 i_end, u32* glwe_state) {
@@ -585,11 +523,9 @@ blind_rotate_wide_kernel(PbsParams P, const typename F::elem* __restrict__ tw, c
 
 // unrolled blind rotation (two key bits per step, pbs_wave.h::blind_rotate_bmmp_team); offered where a
 // lane holds 8 elements per array and one wave owns a polynomial: N = 512
-#ifndef TFHE_BMMP_MIN_WAVES
-#define TFHE_BMMP_MIN_WAVES 3
-#endif
+constexpr int kBmmpMinWaves = 3;
 template <class F, int LOGN, int K>
-__global__ void __launch_bounds__((TeamCfg<F, LOGN, K, 1>::kThreads), TFHE_BMMP_MIN_WAVES)
+__global__ void __launch_bounds__((TeamCfg<F, LOGN, K, 1>::kThreads), kBmmpMinWaves)
 blind_rotate_bmmp_kernel(PbsParams P, const typename F::elem* __restrict__ tw,
                          const u32* __restrict__ lwe_in, size_t batch, const u32* __restrict__ tv,
                          size_t tv_stride, const typename F::elem* __restrict__ bsk,
@@ -630,10 +566,7 @@ blind_rotate_bmmp_kernel(PbsParams P, const typename F::elem* __restrict__ tw,
 // the teams out of phase left the time per product unchanged within 2 %; with loads and stores compiled
 // out the kernel is only 4 % faster.)
 template <class F, int LOGN, int K>
-__global__ void __launch_bounds__((TeamCfg<F, LOGN, K>::kThreads),
-                                  (F::kId == FpField::kId || F::kId == Fp49Field::kId || F::kId == FftField::kId
-                                       ? TeamCfg<F, LOGN, K, 1>::kMinWavesFp
-                                       : TeamCfg<F, LOGN, K, 1>::kMinWavesGl))
+__global__ void __launch_bounds__((TeamCfg<F, LOGN, K>::kThreads), (TeamCfg<F, LOGN, K, 1>::kMinWaves))
 external_product_kernel(PbsParams P, const typename F::elem* __restrict__ tw,
                         const typename F::elem* __restrict__ ggsw, size_t ggsw_stride_words,
                         const u32* glwe_in, u32* ct1_inout, const u32* cmux_ct0, size_t batch,
@@ -752,10 +685,7 @@ __global__ void __launch_bounds__(256) tree_lut_test_vectors_kernel(const u32* _
 }
 
 template <class F, int LOGN, int K>
-__global__ void __launch_bounds__((TeamCfg<F, LOGN, K, 1>::kThreads),
-                                  (F::kId == FpField::kId || F::kId == Fp49Field::kId || F::kId == FftField::kId
-                                       ? TeamCfg<F, LOGN, K, 1>::kMinWavesFp
-                                       : TeamCfg<F, LOGN, K, 1>::kMinWavesGl))
+__global__ void __launch_bounds__((TeamCfg<F, LOGN, K, 1>::kThreads), (TeamCfg<F, LOGN, K, 1>::kMinWaves))
 pack_lwe_kernel(PbsParams P /* the KS decomposer */, const typename F::elem* __restrict__ tw,
                 const typename F::elem* __restrict__ key, const u32* __restrict__ cols, u32 d, u32 slices,
                 u32 slices_per_run, u32* glwe_out) {
@@ -780,10 +710,7 @@ pack_lwe_kernel(PbsParams P /* the KS decomposer */, const typename F::elem* __r
 // log_subtrees; the team's LDS and registers are external_product_kernel's (one product at a time, x in c.acc(), the
 // pending partial results in the team's slots of the workspace), so its residency is that kernel's.
 template <class F, int LOGN, int K>
-__global__ void __launch_bounds__((TeamCfg<F, LOGN, K, 1>::kThreads),
-                                  (F::kId == FpField::kId || F::kId == Fp49Field::kId || F::kId == FftField::kId
-                                       ? TeamCfg<F, LOGN, K, 1>::kMinWavesFp
-                                       : TeamCfg<F, LOGN, K, 1>::kMinWavesGl))
+__global__ void __launch_bounds__((TeamCfg<F, LOGN, K, 1>::kThreads), (TeamCfg<F, LOGN, K, 1>::kMinWaves))
 cmux_tree_kernel(PbsParams P, const typename F::elem* __restrict__ tw, CmuxTreePass pass) {
   using C = TeamCfg<F, LOGN, K, 1>;
   auto w = make_wave<F, LOGN, K, 1>(g_smem, tw);
@@ -818,9 +745,7 @@ constexpr int kKsKeyRows = 16;     // key rows staged in LDS per step (x 128 col
 constexpr int kKsLoads = kKsKeyRows * kKsCols / 256;  // key words each thread moves per step
 // workgroups a launch should reach before the mask words stop being split over gridDim.z: 16 per CU
 // (cfg2, batch 4096: 640 tiles -> 0.90 ms unsplit, 0.70 ms at 3 splits, 0.59 ms at 6; flat beyond)
-#ifndef TFHE_KS_TARGET_WGS
-#define TFHE_KS_TARGET_WGS 4096u
-#endif
+constexpr unsigned kKsTargetWgs = 4096u;
 
 __global__ void __launch_bounds__(256) key_switch_kernel(KsParams Kp, u32 big_n, u32 n,
                                                          const u32* __restrict__ lwe_in, size_t batch,
@@ -1278,7 +1203,7 @@ hipError_t resident_teams(unsigned* out) {
 // profiles/r04_kernel_ab.txt).  TFHE_BR_PAIR_MIN overrides the threshold (batches >= it take the pair kernel).
 template <class F, int LOGN, int K>
 bool use_pair_kernel(size_t batch) {
-  if constexpr (!(TFHE_PAIR_KERNEL && pair_shape<F, LOGN, K>())) {
+  if constexpr (!pair_shape<F, LOGN, K>()) {
     return false;
   } else {
     static const long env_min = std::getenv("TFHE_BR_PAIR_MIN") ? std::atol(std::getenv("TFHE_BR_PAIR_MIN")) : -1;
@@ -1309,10 +1234,7 @@ size_t wide_max_batch(const PbsParams& P, int shape) {
     if (env_wide >= 0) return (size_t)env_wide;
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, current_device_slot()) != hipSuccess || cus <= 0) cus = 256;
-#ifndef TFHE_WIDE_BATCH_PER_CU
-#define TFHE_WIDE_BATCH_PER_CU 1
-#endif
-    return (size_t)cus * TFHE_WIDE_BATCH_PER_CU;
+    return (size_t)cus;  // one sample per CU
   }
 }
 
@@ -1336,19 +1258,13 @@ hipError_t launch_blind_rotate_wide(hipStream_t s, const PbsParams& P, const typ
                          bsk, glwe_out, lwe_extracted, 0u, P.n, static_cast<u32*>(nullptr));
       return hipGetLastError();
     };
-#ifndef TFHE_WIDE_KEY_RING
-#define TFHE_WIDE_KEY_RING 1
-#endif
-    if (TFHE_WIDE_KEY_RING) {
-      switch (P.levels) {
-        case 2: return launch(IntC<2>{});
-        case 3: return launch(IntC<3>{});
-        case 4: return launch(IntC<4>{});
-        case 6: return launch(IntC<6>{});
-        default: break;
-      }
+    switch (P.levels) {
+      case 2: return launch(IntC<2>{});
+      case 3: return launch(IntC<3>{});
+      case 4: return launch(IntC<4>{});
+      case 6: return launch(IntC<6>{});
+      default: return launch(IntC<0>{});
     }
-    return launch(IntC<0>{});
   }
 }
 
@@ -1472,13 +1388,8 @@ template <class F, int LOGN, int K>
 hipError_t launch_blind_rotate_bmmp(hipStream_t s, const PbsParams& P, const void* tw_v, const u32* lwe_in,
                                     size_t batch, const u32* tv, size_t tv_stride, const void* bsk_v,
                                     u32* glwe_out, u32* lwe_extracted) {
-  // (TFHE_BMMP_FFT: A/B builds only -- the unrolled rotation in the complex transform, measured and not offered:
-  // profiles/r04_kernel_ab.txt)
-#ifndef TFHE_BMMP_FFT
-#define TFHE_BMMP_FFT 0
-#endif
-  if constexpr (LOGN != 9 || !field_shape_ok<F, LOGN>() ||
-                !(F::kId == GlField::kId || F::kId == Fp49Field::kId || (TFHE_BMMP_FFT && F::kId == FftField::kId))) {
+  // (the unrolled rotation in the complex transform was measured and is not offered: profiles/r04_kernel_ab.txt)
+  if constexpr (LOGN != 9 || !(F::kId == GlField::kId || F::kId == Fp49Field::kId)) {
     return hipErrorInvalidValue;  // shape_supported_bmmp() / field_supported_bmmp() keep callers away
   } else {
     using C = TeamCfg<F, LOGN, K, 1>;
@@ -1719,12 +1630,12 @@ bool shape_supported_bmmp(u32 log_n, u32 k) { return log_n == 9 && (k == 1 || k 
 // mode is at least even with the loop: Goldilocks (+10 % at the reference's default parameters) and the single-spectrum
 // 49-bit field (-5 %, 17-23 spilled registers).  In the two-spectra fields it ran 1.9-3.4x slower than the loop on 50-172
 // spilled registers (profiles/r02_kernel_ab.txt, r02_h_isa_resources_all_kernels.txt): not instantiated, refused at load.
-bool field_supported_bmmp(int field) { return field == kFieldGoldilocks || field == kFieldFp49 || (TFHE_BMMP_FFT && field == kFieldFft); }
+bool field_supported_bmmp(int field) { return field == kFieldGoldilocks || field == kFieldFp49; }
 
 int field_parts(int field) { return (field == kFieldGoldilocks || field == kFieldFp49) ? 1 : 2; }
 
 bool field_shape_supported(int field, u32 log_n) {
-  return field != kFieldFft || log_n == 9 || log_n == 10 || (TFHE_FFT_N2048 && log_n == 11);
+  return field != kFieldFft || (log_n >= 9 && log_n <= 11);
 }
 
 int samples_per_team(int field, u32 log_n, u32 k) {
@@ -1918,8 +1829,8 @@ hipError_t key_switch(hipStream_t s, const KsParams& K, u32 big_n, u32 n, const 
   const size_t lds = ((size_t)kKsWords * K.levels * kKsSamples + 2 * (size_t)kKsKeyRows * kKsCols) * sizeof(u32);
   if (lds > 64 * 1024) return hipErrorInvalidValue;
   dim3 grid((n + 1 + kKsCols - 1) / kKsCols, (unsigned)((batch + kKsSamples - 1) / kKsSamples));
-  // aim at TFHE_KS_TARGET_WGS workgroups; a split covers a multiple of kKsWords words, at least 64
-  unsigned splits = TFHE_KS_TARGET_WGS / (grid.x * grid.y);
+  // aim at kKsTargetWgs workgroups; a split covers a multiple of kKsWords words, at least 64
+  unsigned splits = kKsTargetWgs / (grid.x * grid.y);
   const unsigned max_splits = (big_n + 63u) / 64u;
   if (splits > max_splits) splits = max_splits;
   if (splits > 32u) splits = 32u;

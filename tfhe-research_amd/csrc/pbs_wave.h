@@ -172,9 +172,6 @@ TFHE_HD u32 monomial_coeff(const u32* poly, int j, u32 m) {
 // notes/BMMP Bootstrapping.md needs three products of the same accumulator).  out(m, j, value) is
 // called for key m = 0 .. KEYS-1 in turn, end_of_key(m) once after the last coefficient of key m.
 // ---------------------------------------------------------------------------------------------
-#ifndef TFHE_TOP_PREFETCH
-#define TFHE_TOP_PREFETCH 1
-#endif
 // NS > 1: the team multiplies NS GLWE operands (NS independent samples of a batch) with the SAME prepared GGSW in
 // one pass.  Every key chunk is fetched from L2 once and used NS times, the NS transforms of a step run in lockstep
 // through one set of transposes and barriers (ntt_forward_multi), and a team barrier covers NS products instead
@@ -224,31 +221,26 @@ TFHE_HD void external_product_team_multi(const Ctx& c, const PbsParams& P, const
   // while the operand is read and rounded, stay in scalar registers for all levels, and make room for
   // the inverse transforms' block after the last level.
   TopConsts<F, LT, G, true> ftop;
-  if constexpr (TFHE_TOP_PREFETCH) ftop.issue(c.twiddles_uniform());
+  ftop.issue(c.twiddles_uniform());
   u32 v[NS][EC];
   const RoundConsts rc = round_consts(P.ignored_bits);
 #pragma unroll
   for (int s = 0; s < NS; ++s)
 #pragma unroll
     for (int r = 0; r < EC; ++r) v[s][r] = round_value_fast(src(s, r * T + lane), rc);
-  if constexpr (TFHE_TOP_PREFETCH) ftop.ready();
+  ftop.ready();
 
   // Key tiles of one level for my column: idx = s * PARTS + q, s = source polynomial 0..K, q = part.
   // A tile is consumed in chunks of CH registers (order: s, piece of the spectrum, q); chunks are staged
   // through two register buffers: the loads of chunk i+1 are issued before the arithmetic of chunk
   // i, and chunk 0 of a level is loaded before that level's forward transform, so no key load sits
-  // on the critical path.  CH = 8 keeps the staging at 3 x 16 VGPRs whatever E is (16 measured the
-  // same speed with more spill: profiles/r01_chunk_ab.txt).
-#ifndef TFHE_CHUNK
-#define TFHE_CHUNK 8
-#endif
+  // on the critical path.  Chunks of 8 eight-byte registers keep the staging at 3 x 16 VGPRs whatever E is (16
+  // measured the same speed with more spill: profiles/r01_chunk_ab.txt).
+  constexpr int kChunkRegisters = 8;
   constexpr int TILES = (K + 1) * ACCS;
   // (NS samples share a chunk: half the registers per chunk give the same arithmetic per fetch, and the staging
   // buffers and the digit-spectrum pieces of NS samples fit beside NS accumulator sets)
-#ifndef TFHE_NS_CHUNK_DIV
-#define TFHE_NS_CHUNK_DIV 2
-#endif
-  constexpr int CH_MAX = TFHE_CHUNK * 8 / (int)sizeof(elem) / (NS > 1 ? TFHE_NS_CHUNK_DIV : 1);  // TFHE_CHUNK counts 8-byte registers
+  constexpr int CH_MAX = kChunkRegisters * 8 / (int)sizeof(elem) / (NS > 1 ? 2 : 1);
   constexpr int CH = E < CH_MAX ? E : CH_MAX;
   constexpr int CHUNKS = TILES * (E / CH);
   // tile of source polynomial sp and accumulator a = (key m, part q)
@@ -266,21 +258,12 @@ TFHE_HD void external_product_team_multi(const Ctx& c, const PbsParams& P, const
   // writes buffer 0 again).  The inverse transforms run in buffer levels & 1 under the same rule.
   // With NS samples buffer s belongs to sample s and every level has its two barriers -- for NS products.
   const bool two = NS == 1 && c.exchange_buffers() == 2;
-#ifndef TFHE_KEY_BUFFERS
-#define TFHE_KEY_BUFFERS 2
-#endif
-  // staging buffers: chunk i + NB - 1 is fetched while chunk i is consumed.  Two everywhere (three and four measured
-  // nothing at one sample per team, profiles/r02_kernel_ab.txt).  The half-size chunks of two samples per team with one
-  // wave per polynomial had a third while the key came from beyond the L2s (cfg3 in one launch over the whole key:
-  // 68.6 -> 63.8 ms; a fourth 65.9; at N = 2048 the third costs 31 more spilled registers: 57.3 -> 63.2 ms); with the key
-  // blocked for the L2s (kernels.hip::blind_rotate_plan) two are enough and spill nothing: cfg3 53.6 -> 52.8 ms
-  // (three: 10 spilled registers, four: 54.1 ms; profiles/r03_kernel_ab.txt)
-#ifndef TFHE_KEY_BUFFERS_NS
-#define TFHE_KEY_BUFFERS_NS 2
-#endif
-  constexpr int NB = (NS > 1 && G == 1) ? TFHE_KEY_BUFFERS_NS : TFHE_KEY_BUFFERS;
-  elem kbuf[NB][CH];
-  // OWN (TFHE_OWN_FIRST): a wave starts every level's multiply-accumulate with the digit spectrum it has just computed
+  // TWO staging buffers: chunk i + 1 is fetched while chunk i is consumed.  Three and four measured nothing at one sample
+  // per team (profiles/r02_kernel_ab.txt); with two samples per team and the key blocked for the L2s
+  // (kernels.hip::blind_rotate_plan) two spill nothing and three spill 10 registers at cfg3: 53.6 -> 52.8 ms, four 54.1 ms;
+  // at N = 2048 a third costs 31 more spilled registers, 57.3 -> 63.2 ms (profiles/r03_kernel_ab.txt)
+  elem kbuf[2][CH];
+  // OWN: a wave starts every level's multiply-accumulate with the digit spectrum it has just computed
   // itself -- straight from its registers, BEFORE the team barrier that makes the other groups' spectra visible -- and takes
   // the source polynomials in the order me, me + 1, ... (mod k + 1): one spectrum fewer to read back from LDS per level, and
   // a (k+1)-th of the products under the barrier's wait.  (The order of the exact integer sum changes, its value does not.)
@@ -288,20 +271,17 @@ TFHE_HD void external_product_team_multi(const Ctx& c, const PbsParams& P, const
   // spectrum back from LDS, i.e. the barrier overlap alone: 30.8), cfg1 10.6 -> 10.5.  Not elsewhere: with two samples per
   // team the kept spectra spill (cfg3 52.7 -> 55.6 ms; through LDS: level; cfg5 51 -> 55-66 ms), the prime fields'
   // 16-element arrays spill or gain nothing (+-1 %) -- profiles/r03_kernel_ab.txt.
-#ifndef TFHE_OWN_FIRST
-#define TFHE_OWN_FIRST 1
-#endif
-  constexpr bool OWN = TFHE_OWN_FIRST && F::kLogShrink == 1 && NS == 1 && G == 1 && !SPLIT;
+  constexpr bool OWN = F::kLogShrink == 1 && NS == 1 && G == 1 && !SPLIT;
+  // (a second name for the same predicate, kept on purpose: the generic lambdas below capture every constant they name in a
+  // dependent expression, so folding the two names into one changes their closures and, through them, the instruction
+  // schedule of the one-sample kernels)
   constexpr bool OWN_REGS = OWN;
-  // LATE (TFHE_LATE_BARRIER): the barrier that ends a level -- everyone is done reading the spectra before a buffer is
+  // LATE: the barrier that ends a level -- everyone is done reading the spectra before a buffer is
   // written again -- moves from behind the multiply-accumulate to just in front of the NEXT transform's first store into
   // the buffer (its first transpose; the inverse transform's after the last level): decomposition and the first register
   // pass touch no buffer and run under the barrier's wait.  Same shapes as OWN: cfg2 30.15 -> 28.9 ms, cfg1 10.5 -> 10.45;
   // with two samples per team level (cfg3 51.4 -> 51.3 ms) or worse (cfg5 51.0 -> 54.2 ms, 9 more spilled registers).
-#ifndef TFHE_LATE_BARRIER
-#define TFHE_LATE_BARRIER 1
-#endif
-  constexpr bool LATE = TFHE_LATE_BARRIER && TFHE_TOP_PREFETCH && OWN;
+  constexpr bool LATE = OWN;
   auto source_of = [&](int sp) -> int {  // the source polynomial behind chunk position sp
     if (!OWN) return sp;
     const int at = me + sp;
@@ -330,16 +310,17 @@ TFHE_HD void external_product_team_multi(const Ctx& c, const PbsParams& P, const
     const u32 shift = P.first_shift + P.log_base * t;
     Ctx cl[NS];
     buffers_of_level(t, cl);
-    static_for<0, (NB - 1 < CHUNKS ? NB - 1 : CHUNKS)>([&](auto pre_c) { load_chunk(level, pre_c, decltype(pre_c)::value); });
+    // chunk 0 (through static_for like every later chunk: called directly, the prime fields' kernels with 8 elements per
+    // lane come out with another instruction schedule)
+    static_for<0, 1>([&](auto pre_c) { load_chunk(level, pre_c, decltype(pre_c)::value); });
     c.compiler_fence();
-    // The samples' digit rows are transformed one after the other (TFHE_NS_LOCKSTEP_FORWARD = 0): in lockstep
-    // (ntt_forward_multi over all of them, shared transposes) two working arrays are live next to every sample's
-    // accumulators and the kernels of the 168-register shapes spill (89 / 33 registers at N = 2048 / N = 512, k = 2);
+    // The samples' digit rows are transformed one after the other: in lockstep (ntt_forward_multi over all of them,
+    // shared transposes) two working arrays are live next to every sample's accumulators and the kernels of the
+    // 168-register shapes spill (89 / 33 registers at N = 2048 / N = 512, k = 2; profiles/r03_kernel_ab.txt);
     // the inverse transforms do run in lockstep -- their arrays ARE the accumulators.
-#ifndef TFHE_NS_LOCKSTEP_FORWARD
-#define TFHE_NS_LOCKSTEP_FORWARD 0
-#endif
-    constexpr int FS = (NS > 1 && !TFHE_NS_LOCKSTEP_FORWARD) ? 1 : NS;  // samples per forward transform call
+    // (FS, the samples per forward transform call, is 1; the loop nest keeps its shape because flattening it, or dropping
+    // s0 from the barrier lambda's captures, moves the instruction schedule of the one-sample kernels)
+    constexpr int FS = 1;
     const u32 carry_width = (t == 0) ? 0u : 1u;  // wave-uniform: the lowest kept limb has no carry-in
     elem own[OWN_REGS ? NS : 1][OWN_REGS ? E : 1];  // OWN_REGS: my digit spectrum of this level, as published
 #pragma unroll
@@ -377,11 +358,8 @@ TFHE_HD void external_product_team_multi(const Ctx& c, const PbsParams& P, const
       if constexpr (LATE) {
         // (level 0 follows the previous product's inverse transforms, which use a wave's own buffer only: no barrier owed)
         ntt_forward_multi<F, LT, G, true, true>(cf, work, ftop, [&]() { if (t > 0 && !two && s0 == 0) c.team_sync(); });
-      } else if constexpr (TFHE_TOP_PREFETCH) {
-        ntt_forward_multi<F, LT, G, true, true>(cf, work, ftop);
       } else {
-        const TopFromTable<elem> top{c.twiddles_uniform(), 1 << LT};
-        ntt_forward_multi<F, LT, G, true, true>(cf, work, top);
+        ntt_forward_multi<F, LT, G, true, true>(cf, work, ftop);
       }
 #pragma unroll
       for (int s = 0; s < FS; ++s) {
@@ -411,9 +389,9 @@ TFHE_HD void external_product_team_multi(const Ctx& c, const PbsParams& P, const
       constexpr int ci = decltype(ci_c)::value;
       constexpr int PIECES = E / CH;
       constexpr int q = ci % ACCS, r0 = ((ci / ACCS) % PIECES) * CH, sp = ci / (ACCS * PIECES);
-      constexpr int cur = ci % NB;
+      constexpr int cur = ci % 2;
       if constexpr (OWN && ci == ACCS * PIECES) c.team_sync();  // my own spectrum is done with: now the others'
-      if constexpr (ci + NB - 1 < CHUNKS) load_chunk(level, IntC<ci + NB - 1>{}, (ci + NB - 1) % NB);
+      if constexpr (ci + 1 < CHUNKS) load_chunk(level, IntC<ci + 1>{}, (ci + 1) % 2);
       // (TFHE_PROBE_NO_EXCHANGE_READS: dev_switches.h -- a WRONG-BITS timing probe, TFHE_DEV_BUILD only)
       if constexpr (OWN_REGS && sp == 0) {
         if constexpr (q == 0) {
@@ -453,16 +431,12 @@ TFHE_HD void external_product_team_multi(const Ctx& c, const PbsParams& P, const
   Ctx ci[NS];
   buffers_of_level(P.levels, ci);
   TopConsts<F, LT, G, false> itop;  // arrives during the first two passes of the first inverse transform
-  if constexpr (TFHE_TOP_PREFETCH) itop.issue(c.twiddles_uniform());
-  // (TFHE_INVERSE_PAIR: one sample's two key parts go through the inverse transform half a step apart, each one's
-  // transposes covered by the other's register passes -- wave_ntt.h::ntt_inverse_pair)
-#ifndef TFHE_INVERSE_PAIR
-#define TFHE_INVERSE_PAIR 1
-#endif
-  // Measured where it is on (profiles/r03_kernel_ab.txt): the complex transform at 8 elements per lane (N = 1024), +0.9 %;
-  // at 4 elements per lane (N = 512) it is level, the prime fields' 16-element arrays spill with it.
-  constexpr bool PAIR = TFHE_INVERSE_PAIR && NS == 1 && PARTS == 2 && G == 1 && !SPLIT && NttShape<LT, G>::kPasses == 3 &&
-                        TFHE_TOP_PREFETCH && F::kLogShrink == 1 && E == 8;
+  itop.issue(c.twiddles_uniform());
+  // PAIR: one sample's two key parts go through the inverse transform half a step apart, each one's transposes covered
+  // by the other's register passes (wave_ntt.h::ntt_inverse_pair).  Measured where it is on (profiles/r03_kernel_ab.txt):
+  // the complex transform at 8 elements per lane (N = 1024), +0.9 %; at 4 elements per lane (N = 512) it is level, the
+  // prime fields' 16-element arrays spill with it.
+  constexpr bool PAIR = NS == 1 && PARTS == 2 && G == 1 && !SPLIT && NttShape<LT, G>::kPasses == 3 && F::kLogShrink == 1 && E == 8;
   static_for<0, KEYS>([&](auto key_c) {
     constexpr int m = decltype(key_c)::value;
     if constexpr (PAIR) {
@@ -494,12 +468,9 @@ TFHE_HD void external_product_team_multi(const Ctx& c, const PbsParams& P, const
         } else {
           ntt_inverse_multi<F, LT, G>(ci, x, itop);
         }
-      } else if constexpr (TFHE_TOP_PREFETCH) {
+      } else {
         if constexpr (q == 0) itop.ready();  // nothing else is in flight here: the wait is for the block alone
         ntt_inverse_multi<F, LT, G>(ci, x, itop);
-      } else {
-        const TopFromTable<elem> top{c.twiddles_uniform(), 1 << LT};
-        ntt_inverse_multi<F, LT, G>(ci, x, top);
       }
 #pragma unroll
       for (int s = 0; s < NS; ++s)
@@ -1014,13 +985,16 @@ TFHE_HD void external_product_pair(const Ctx& c, const PbsParams& P, const typen
   constexpr int PIECES = E / CH;
   constexpr int CHUNKS = 2 * PIECES * 2;  // per level
   elem kbuf[2][CH];
+  // the key of this parameter set is laid out for THIS kernel's shape (key_layout_e), whatever other kernels read it too
+  constexpr int KEY_E = key_layout_e<F, LOGN, 1>();
+  static_assert(KEY_E == E, "the prepared key of the pair shape has the pair kernel's layout");
   auto load_chunk = [&](u32 level, auto ci_c, int buf) {
     constexpr int ci = decltype(ci_c)::value;
     constexpr int q = ci % 2, r0 = ((ci / 2) % PIECES) * CH, other = ci / (2 * PIECES);
     const int sp = other ? 1 - me : me;
     const elem* tile = ggsw + ((((size_t)sp * P.levels + level) * (K + 1) + me) * 2 + q) * N;
 #pragma unroll
-    for (int r = 0; r < CH; ++r) kbuf[buf][r] = tile[spectrum_slot<LT, G, (int)sizeof(elem)>(tid, r0 + r)];
+    for (int r = 0; r < CH; ++r) kbuf[buf][r] = tile[spectrum_slot<LT, G, (int)sizeof(elem), KEY_E>(tid, r0 + r)];
   };
 #pragma unroll 1
   for (u32 t = 0; t < P.levels; ++t) {

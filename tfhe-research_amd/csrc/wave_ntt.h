@@ -97,21 +97,15 @@ TFHE_HD int ntt_stage_window_lo(int b) {
   return b >= S::kLo1 ? S::kLo1 : b >= S::kLo2 ? S::kLo2 : b >= S::kLo3 ? S::kLo3 : b >= S::kLo4 ? S::kLo4 : S::kLo5;
 }
 
-#ifndef TFHE_TW_TRANSPOSED
-#define TFHE_TW_TRANSPOSED 0
-#endif
-#ifndef TFHE_RADIX8
-#define TFHE_RADIX8 1
-#endif
 // (the transposed layout costs the 8-byte fields their ds_read_b128 of two adjacent twiddles and measured 6 %
 // SLOWER there, so they keep table order; the complex transform's 16-byte entries are one ds_read_b128 either
 // way and it gains 1.2 % -- a third of its LDS-active cycles were conflict cycles: profiles/r02_kernel_ab.txt)
 template <int ELEM_BYTES>
 constexpr bool ntt_twiddles_transposed() {
-  return TFHE_TW_TRANSPOSED || ELEM_BYTES == 16;
+  return ELEM_BYTES == 16;
 }
 
-template <int LOGN, int G, bool TRANSPOSED = (TFHE_TW_TRANSPOSED != 0)>
+template <int LOGN, int G, bool TRANSPOSED = false>
 TFHE_HD int ntt_twiddle_slot(int idx) {
   using S = NttShape<LOGN, G>;
   if (!TRANSPOSED || idx <= 0 || idx >= S::kN) return idx;
@@ -228,7 +222,7 @@ struct TopConsts {
   static constexpr int e = NttShape<LOGN, G>::kEBits;
   static constexpr int N = 1 << LOGN;
   static constexpr bool FUSE = FORWARD_SMALL && F::kFuseFirstTwo && e >= 2;
-  static constexpr bool FUSE3 = TFHE_RADIX8 && FUSE && e >= 3;
+  static constexpr bool FUSE3 = FUSE && e >= 3;
   static_assert(!FUSE || W == 1, "fused stages: one-word elements");
   static constexpr int kFirstPlain = FUSE3 ? 8 : FUSE ? 4 : 1;  // lowest table index a plain stage reads
   static constexpr int kWords = E * W;                          // the window reads words [W, kWords)
@@ -290,14 +284,14 @@ struct TopConsts {
   }
 };
 
-// fields whose forward butterfly is one fused step (F::kFusedForwardButterfly + F::butterfly_forward)
+// fields whose butterflies are one fused step each (F::butterfly_forward, F::butterfly_inverse)
 template <class F, class = void>
 struct FusedForwardButterfly {
   static constexpr bool value = false;
 };
 template <class F>
-struct FusedForwardButterfly<F, decltype((void)F::kFusedForwardButterfly)> {
-  static constexpr bool value = F::kFusedForwardButterfly;
+struct FusedForwardButterfly<F, decltype((void)&F::butterfly_forward)> {
+  static constexpr bool value = true;
 };
 
 // XOR swizzle of the transpose buffer (element = 8 bytes).  Each one makes every ds_write_b64 and
@@ -392,33 +386,21 @@ TFHE_HD int exchange_slot(int tid, int r) {
 // half of a with the lower half of b: exactly "the lanes whose bit is 1 hand their a over for the b of the lanes whose bit
 // is 0", one instruction per dword pair and bit -- 16 VALU instructions for a two-bit window of four 16-byte elements
 // instead of four stores and four loads through the LDS path (74 cycles of it, plus the round trip).  Taken where the
-// kernel has VALU issue to spare and the LDS path is the busier pipe (TFHE_SWAP_TRANSPOSE: the two-bit windows of the
-// complex transform at N = 512 with k = 2 and at N = 2048; profiles/r04_kernel_ab.txt).  The host emulator keeps the LDS
-// path (same values).
-#ifndef TFHE_SWAP_TRANSPOSE
-#define TFHE_SWAP_TRANSPOSE 1
-#endif
-// Which lane bits may be exchanged in registers (TFHE_SWAP_LOW_BIT: the lowest one; 6 = never): bits 5 and 4 by the permlane
-// swaps (1 instruction per dword pair), bits 3 and 2 by bank-masked DPP moves -- a row of 16 lanes is four banks of 4, lane bit
-// 2 picks the odd banks, lane bit 3 the upper two, so "the lanes whose bit is 0 take their partner's a into b" is ONE
-// v_mov_b32_dpp whose bank mask leaves the other lanes' b alone (2 instructions per dword pair) --, bits 1 and 0 by quad
-// permutes and selects (4 per pair: measured slower than LDS, profiles/r04_kernel_ab.txt, so the default stops at bit 2).
-// Per shape (TFHE_SWAP_E8: also for the three-bit windows of 8 elements per lane): see swap_transpose_low_bit.
-#ifndef TFHE_SWAP_LOW_BIT
-#define TFHE_SWAP_LOW_BIT 2
-#endif
-#ifndef TFHE_SWAP_E8
-#define TFHE_SWAP_E8 0
-#endif
+// kernel has VALU issue to spare and the LDS path is the busier pipe: the two-bit windows of the complex transform at
+// N = 512 with k = 2 and at N = 2048 (profiles/r04_kernel_ab.txt).  The host emulator keeps the LDS path (same values).
+// Which lane bits are exchanged in registers: bits 5 and 4 by the permlane swaps (1 instruction per dword pair), bits 3 and 2
+// by bank-masked DPP moves -- a row of 16 lanes is four banks of 4, lane bit 2 picks the odd banks, lane bit 3 the upper
+// two, so "the lanes whose bit is 0 take their partner's a into b" is ONE v_mov_b32_dpp whose bank mask leaves the other
+// lanes' b alone (2 instructions per dword pair).  Bits 1 and 0 would take quad permutes and selects (4 per pair) and the
+// three-bit windows of 8 elements per lane three exchanges: both measured slower than LDS (profiles/r04_kernel_ab.txt),
+// so the rule stops at lane bit 2 and at two-bit windows.
 template <int LOGN, int G, int LO_FROM, int LO_TO>
 constexpr int swap_transpose_low_bit() {  // lowest exchanged lane bit, or -1: through LDS
   constexpr int e = NttShape<LOGN, G>::kEBits;
   constexpr int lo = LO_FROM < LO_TO ? LO_FROM : LO_TO, hi = LO_FROM < LO_TO ? LO_TO : LO_FROM;
-  // adjacent windows of lane bits only (thread bit = lane bit below 6; half-wave groups: below 5)
-  if (!TFHE_SWAP_TRANSPOSE || hi - lo != e || lo + e > (G == 0 ? 5 : 6)) return -1;
-  if (e == 3 && !TFHE_SWAP_E8) return -1;
-  if (e != 2 && e != 3) return -1;
-  return lo >= TFHE_SWAP_LOW_BIT ? lo : -1;
+  // adjacent two-bit windows of lane bits only (thread bit = lane bit below 6; half-wave groups: below 5)
+  if (e != 2 || hi - lo != e || lo + e > (G == 0 ? 5 : 6)) return -1;
+  return lo >= 2 ? lo : -1;
 }
 template <int LOGN, int G, int LO_FROM, int LO_TO>
 constexpr bool swap_transpose_shape() {
@@ -430,7 +412,8 @@ constexpr bool swap_transpose_shape() {
 // builtins, not inline assembly -- the hazard recogniser has to see them: issued as asm statements the swaps returned wrong
 // words at N = 512)
 template <int RB, int LB, int E, int W>
-__device__ __forceinline__ void exchange_register_bit_with_lane_bit(u32 (&w)[E][W], int lane) {
+__device__ __forceinline__ void exchange_register_bit_with_lane_bit(u32 (&w)[E][W]) {
+  static_assert(LB >= 2 && LB <= 5, "lane bits 2..5 (swap_transpose_low_bit)");
 #pragma unroll
   for (int r0 = 0; r0 < E; ++r0) {
     if ((r0 >> RB) & 1) continue;
@@ -449,35 +432,28 @@ __device__ __forceinline__ void exchange_register_bit_with_lane_bit(u32 (&w)[E][
       } else if constexpr (LB == 3) {  // row_ror:8 = lane ^ 8; banks 0,1 have bit 3 clear
         w[r1][i] = (u32)__builtin_amdgcn_update_dpp((int)b, (int)a, 0x128, 0xF, 0x3, false);
         w[r0][i] = (u32)__builtin_amdgcn_update_dpp((int)a, (int)b, 0x128, 0xF, 0xC, false);
-      } else if constexpr (LB == 2) {  // row_shl:4 reads lane + 4 (banks 0,2: bit 2 clear), row_shr:4 lane - 4
+      } else {  // LB == 2: row_shl:4 reads lane + 4 (banks 0,2: bit 2 clear), row_shr:4 lane - 4
         w[r1][i] = (u32)__builtin_amdgcn_update_dpp((int)b, (int)a, 0x104, 0xF, 0x5, false);
         w[r0][i] = (u32)__builtin_amdgcn_update_dpp((int)a, (int)b, 0x114, 0xF, 0xA, false);
-      } else {  // quad_perm:[1,0,3,2] = lane ^ 1, quad_perm:[2,3,0,1] = lane ^ 2, and selects
-        constexpr int ctrl = LB == 0 ? 0xB1 : 0x4E;
-        const bool bit = ((lane >> LB) & 1) != 0;
-        const u32 pa = (u32)__builtin_amdgcn_update_dpp(0, (int)a, ctrl, 0xF, 0xF, true);
-        const u32 pb = (u32)__builtin_amdgcn_update_dpp(0, (int)b, ctrl, 0xF, 0xF, true);
-        w[r1][i] = bit ? b : pa;
-        w[r0][i] = bit ? pb : a;
       }
     }
   }
 }
 template <class Elem, int E, int LOW>
-__device__ __forceinline__ void swap_transpose(Elem (&x)[E], int lane) {
+__device__ __forceinline__ void swap_transpose(Elem (&x)[E]) {
+  static_assert(E == 4, "two-bit windows");
   constexpr int W = (int)(sizeof(Elem) / 4);
   u32 w[E][W];
 #pragma unroll
   for (int r = 0; r < E; ++r) __builtin_memcpy(w[r], &x[r], sizeof(Elem));
-  exchange_register_bit_with_lane_bit<0, LOW, E, W>(w, lane);
-  exchange_register_bit_with_lane_bit<1, LOW + 1, E, W>(w, lane);
-  if constexpr (E == 8) exchange_register_bit_with_lane_bit<2, LOW + 2, E, W>(w, lane);
+  exchange_register_bit_with_lane_bit<0, LOW, E, W>(w);
+  exchange_register_bit_with_lane_bit<1, LOW + 1, E, W>(w);
 #pragma unroll
   for (int r = 0; r < E; ++r) __builtin_memcpy(&x[r], w[r], sizeof(Elem));
 }
 #endif
 
-// Issue priority by phase (TFHE_PHASE_PRIORITY).  A wave drops to priority 0 while it MOVES data -- while it issues the
+// Issue priority by phase.  A wave drops to priority 0 while it MOVES data -- while it issues the
 // stores and the loads of a transpose through LDS here (the s_waitcnt for the loaded registers comes later, where a wave
 // issues nothing anyway); in the shapes with 8 ring coefficients per lane also for the multiply-accumulate with its key
 // loads and spectrum reads (pbs_wave.h) -- and runs its register passes, the digit chain and everything else at priority
@@ -491,27 +467,19 @@ __device__ __forceinline__ void swap_transpose(Elem (&x)[E], int lane) {
 //      fp64-p49 67.75 -> 65.45, Goldilocks 221.0 -> 205.0.
 // (Raising the priority INSIDE the transposes, the operand read and the final update low too, and fixed different priorities
 // per wave slot: level or worse.)
-#ifndef TFHE_PHASE_PRIORITY
-#define TFHE_PHASE_PRIORITY 1
-#endif
-template <class Elem, int E>
-constexpr bool transpose_lowers_priority() {
-  return TFHE_PHASE_PRIORITY != 0;
-}
 template <class Elem, int E>
 constexpr bool mac_lowers_priority() {  // 8 ring coefficients per lane: 4 complex elements or 8 field elements
-  return TFHE_PHASE_PRIORITY && E * (int)sizeof(Elem) == 64;
+  return E * (int)sizeof(Elem) == 64;
 }
 
 template <class F, int LOGN, int G, int LO_FROM, int LO_TO, bool SKIP_LEAD = false, int NS, class Ctx>
 TFHE_HD void ntt_transpose_multi(const Ctx (&c)[NS], typename F::elem (&x)[NS][NttShape<LOGN, G>::kE]) {
   constexpr int E = NttShape<LOGN, G>::kE;
-  constexpr bool PRIO = transpose_lowers_priority<typename F::elem, E>();
 #if defined(__HIP_DEVICE_COMPILE__)
   if constexpr (swap_transpose_shape<LOGN, G, LO_FROM, LO_TO>()) {
     constexpr int LOW = swap_transpose_low_bit<LOGN, G, LO_FROM, LO_TO>();
 #pragma unroll
-    for (int s = 0; s < NS; ++s) swap_transpose<typename F::elem, E, LOW>(x[s], c[0].tid());
+    for (int s = 0; s < NS; ++s) swap_transpose<typename F::elem, E, LOW>(x[s]);
     return;
   }
 #endif
@@ -522,7 +490,7 @@ TFHE_HD void ntt_transpose_multi(const Ctx (&c)[NS], typename F::elem (&x)[NS][N
   // (TFHE_PROBE_NO_TRANSPOSE: dev_switches.h -- a WRONG-BITS timing probe, TFHE_DEV_BUILD only)
   if (TFHE_PROBE_NO_TRANSPOSE) return;
   if (WRITES_CROSS && !SKIP_LEAD) c[0].poly_sync();
-  if constexpr (PRIO) wave_priority<0>();
+  wave_priority<0>();
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
     typename F::elem* buf = c[s].scratch();
@@ -537,7 +505,7 @@ TFHE_HD void ntt_transpose_multi(const Ctx (&c)[NS], typename F::elem (&x)[NS][N
     for (int r = 0; r < E; ++r) x[s][r] = buf[ntt_swizzle<LOGN, G>(ntt_index<LOGN, G, LO_TO>(tid, r))];
   }
   if (READS_CROSS) c[0].poly_sync(); else c[0].wave_sync();
-  if constexpr (PRIO) wave_priority<2>();
+  wave_priority<2>();
 }
 
 template <class F, int LOGN, int G, int LO_FROM, int LO_TO, bool SKIP_LEAD = false, class Ctx>
@@ -558,16 +526,13 @@ TFHE_HD void ntt_transpose(const Ctx& c, typename F::elem (&x)[NttShape<LOGN, G>
 // (28 VGPRs for 16-byte elements at e = 3) across the transpose, so a field opts in (F::kPreloadTwiddles): the
 // complex transform has them, the 8-byte fields at 16 elements per lane do not.
 // ---------------------------------------------------------------------------------------------
-#ifndef TFHE_PRELOAD_TWIDDLES
-#define TFHE_PRELOAD_TWIDDLES 1
-#endif
 template <class F, class = void>
 struct PreloadsTwiddles {
   static constexpr bool value = false;
 };
 template <class F>
 struct PreloadsTwiddles<F, decltype((void)F::kPreloadTwiddles)> {
-  static constexpr bool value = F::kPreloadTwiddles && TFHE_PRELOAD_TWIDDLES != 0;
+  static constexpr bool value = F::kPreloadTwiddles;
 };
 
 // position in the working copy of the twiddle that stage b of window [LO, LO+e) uses for register pair group i
@@ -634,7 +599,7 @@ TFHE_HD void ntt_pass_forward(const Ctx& c, typename F::elem (&x)[NttShape<LOGN,
   // 16 pre-multiplied coefficients at [N+2 .. N+17] (F::radix8_small_v): 34 instructions per eight
   // elements instead of 52.  (The top window's twiddles are the same for every lane: hi = 0.)
   constexpr bool FUSE = SMALL_FIRST && F::kFuseFirstTwo && BHI == LOGN - 1 && BHI - BLO >= 1;
-  constexpr bool FUSE3 = TFHE_RADIX8 && FUSE && BHI - BLO >= 2;
+  constexpr bool FUSE3 = FUSE && BHI - BLO >= 2;
   if constexpr (FUSE) {
     constexpr int s1 = 1 << (BHI - LO), s2 = s1 >> 1, s3 = s2 >> 1;
     static_assert(!FUSE || TOP, "the fused stages are the top ones");
@@ -710,7 +675,7 @@ TFHE_HD void ntt_pass_inverse(const Ctx& c, typename F::elem (&x)[NttShape<LOGN,
       if ((r0 >> rb) & 1) continue;
       const int r1 = r0 | (1 << rb);
       // (F::inverse_twiddle_index(h, i) = 2h - 1 - i in the prime fields, h + i for the complex transform,
-      // whose mul_inverse conjugates the entry)
+      // whose butterfly_inverse conjugates the entry)
       elem w;
       if constexpr (TOP) w = top.tw(F::inverse_twiddle_index(h, r0 >> (rb + 1)));
       else if constexpr (PRE) w = pre.get(b, r0 >> (rb + 1));
@@ -769,7 +734,7 @@ struct LowPassTwiddles<F, LOGN, G, LO, BHI, BLO, INVERSE, false> : NoPassTwiddle
 };
 
 // before_first_store(): called once, after the first register pass and before the first store into the buffer -- the
-// place for a barrier that only has to precede the buffer's reuse (pbs_wave.h, TFHE_LATE_BARRIER)
+// place for a barrier that only has to precede the buffer's reuse (pbs_wave.h: LATE)
 struct NothingBefore {
   TFHE_HD void operator()() const {}
 };

@@ -4,6 +4,7 @@ histogram, read back from tfhe-research_amd/libtfhe_hip.so (not from a side comp
 
     python tools/isa_report.py                                  # resource table of every kernel
     python tools/isa_report.py --kernel 'blind_rotate_kernel<tfhe::FpField, 10, 1>' [--asm out.s]
+    python tools/isa_report.py --digest [--lib other.so]        # one line per kernel, for diff
 
 How: the gfx950 code object is unbundled from the .hip_fatbin section (llvm-objcopy +
 clang-offload-bundler), its AMDGPU metadata note gives VGPR / SGPR / AGPR counts, spills, scratch
@@ -16,6 +17,7 @@ from __future__ import annotations
 
 import argparse
 import collections
+import hashlib
 import os
 import re
 import subprocess
@@ -115,6 +117,28 @@ def disassemble(co: str, mangled: str):
     return insts, out
 
 
+def digest_lines(co: str, kernels):
+    """-> one line per kernel, sorted by name: every resource figure of the metadata note and a sha256 of the
+    instruction stream (mnemonics and operands in order; addresses and encoding bytes dropped).  Two builds
+    generate the same code for a kernel exactly when its two lines are equal."""
+    streams, cur = {}, None
+    for line in run(f"{LLVM}/llvm-objdump", "-d", co).splitlines():
+        m = re.match(r"[0-9A-Fa-f]+ <(.+)>:\s*$", line)
+        if m:
+            cur = streams.setdefault(m.group(1), hashlib.sha256())
+            continue
+        m = re.match(r"\s+(\S+)\s*(.*?)\s*//\s*[0-9A-Fa-f]+:", line)
+        if m and cur is not None:
+            cur.update(f"{m.group(1)} {m.group(2)}\n".encode())
+    keys = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count",
+            "private_segment_fixed_size", "group_segment_fixed_size", "kernarg_segment_size", "max_flat_workgroup_size")
+    lines = []
+    for k in sorted(kernels, key=lambda k: k["demangled"]):
+        res = " ".join(f"{key.replace('_count', '').replace('_segment', '').replace('_size', '')}={k.get(key, 0)}" for key in keys)
+        lines.append(f"{k['demangled']} {res} isa={streams[k['name']].hexdigest()}")
+    return lines
+
+
 def loops_of(insts):
     """backward branches -> [(head index, tail index)] (a loop = the address range [target, branch])"""
     addr_index = {a: i for i, (a, _, _) in enumerate(insts)}
@@ -153,10 +177,16 @@ def main():
     ap.add_argument("--lib", default=LIB)
     ap.add_argument("--kernel", action="append", default=[], help="substring of the demangled kernel name; repeatable")
     ap.add_argument("--asm", default="", help="also write the disassembly of the (last) selected kernel to this file")
+    ap.add_argument("--digest", action="store_true",
+                    help="one line per kernel (resources + sha256 of the normalised instruction stream), sorted: diff two builds")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         co = extract_code_object(args.lib, tmp)
         kernels = kernel_table(co)
+        if args.digest:
+            print(f"# {len(kernels)} gfx950 kernels")
+            print("\n".join(digest_lines(co, kernels)))
+            return 0
         print(f"# {os.path.relpath(args.lib, ROOT)}: {len(kernels)} gfx950 kernels (code object unbundled from .hip_fatbin)")
         print(f"{'kernel':<74}{'VGPR':>5}{'AGPR':>5}{'SGPR':>5}{'spillV':>7}{'scratch B':>10}{'waves/SIMD':>11}")
         for k in sorted(kernels, key=lambda k: k["demangled"]):
