@@ -162,9 +162,8 @@ def negacyclic_matrix(s) -> np.ndarray:
     """T with x @ T = x * s (negacyclic) for row vectors x: T[j, i] = s[i - j], negated where i < j"""
     s = np.asarray(s, dtype=np.float64)
     N = s.shape[-1]
-    j = np.arange(N)[:, None]
-    i = np.arange(N)[None, :]
-    return np.where(i >= j, 1.0, -1.0) * s[(i - j) % N]
+    # row j is the window of (-s, s) that starts at N - j: a read-only view, no N x N index arithmetic
+    return np.lib.stride_tricks.sliding_window_view(np.concatenate([-s, s]), N)[N:0:-1]
 
 
 def _limbs16(x):

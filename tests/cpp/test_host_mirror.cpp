@@ -209,6 +209,105 @@ int main() {
       EXPECT(e2.uses_bmmp(), "BMMP key reloaded");
     }
   }
+  // The wrappers beyond the reference (packing key switch, CMUX tree / table lookup, rotation from a GLWE accumulator,
+  // tree LUT): each regroups vectors into the ABI's layouts, so each is driven once with keys made by the mirror itself
+  // and checked by decryption, or against the entry it must agree with bit for bit
+  {
+    std::mt19937_64 gen(20261018);
+    Engine e3(tfhe_params);
+    LweSecretKey lwe_secret_key = LweSecretKey::random(n, gen);
+    GlweSecretKey glwe_secret_key = GlweSecretKey::random(tfhe_params, gen);
+    LweSecretKey big_key = lwe_secret_key_from(glwe_secret_key);
+    bootstrapping_key_gen(e3, lwe_secret_key, glwe_secret_key, gen);
+    const uint32_t half = 1u << (32 - tfhe_params.log_p - tfhe_params.padding_bits - 1);
+    auto decode = [&](uint32_t raw) { return decode_plaintext(raw + half, tfhe_params) & 3u; };
+    auto enc = [&](uint32_t m) {
+      return encrypt_lwe_plaintext(e3, tfhe_params.lwe_std_dev, lwe_secret_key, encode_message(m, tfhe_params), gen);
+    };
+    auto dec_msg = [&](const LweCiphertext& ct) { return decode(decrypt_lwe(e3, lwe_secret_key, ct)); };
+    const size_t l_ks = tfhe_params.ks_decomposer.levels, glwe_words = (k + 1) * N;
+
+    // generate_packing_key / load_packing_key / pack_lwe: coefficient j decrypts to what ciphertext j does, zero above
+    {
+      PackingKey pk = generate_packing_key(e3, lwe_secret_key, glwe_secret_key, gen);
+      EXPECT(pk.from_dimension == n && pk.data.size() == n * l_ks * glwe_words, "packing key shape");
+      load_packing_key(e3, pk);
+      std::vector<LweCiphertext> cts;
+      for (uint32_t j = 0; j < 7; ++j) cts.push_back(enc((j * 3 + 1) & 3u));
+      GlweCiphertext packed = pack_lwe(e3, cts);
+      EXPECT(packed.data.size() == glwe_words, "packed GLWE shape");
+      auto pt = decrypt_glwe_ciphertext(e3, glwe_secret_key, packed);
+      bool ok = true;
+      for (size_t j = 0; j < N; ++j) ok = ok && decode(pt[j]) == (j < cts.size() ? dec_msg(cts[j]) : 0u);
+      for (size_t j = 0; j < cts.size(); ++j) ok = ok && dec_msg(cts[j]) == ((j * 3 + 1) & 3u);
+      EXPECT(ok, "pack_lwe: coefficient j decrypts to ciphertext j, the rest to zero");
+      bool threw = false;
+      try {
+        PackingKey bad = pk;
+        bad.data.pop_back();
+        load_packing_key(e3, bad);
+      } catch (const TfheError&) { threw = true; }
+      EXPECT(threw, "packing key of the wrong size refused");
+    }
+    // encrypt_address + cmux_tree and table_lookup: every address of eight leaves / an eight-entry table
+    {
+      const size_t depth = 3;
+      std::vector<GlweCiphertext> leaves;
+      std::vector<uint32_t> table;
+      for (uint32_t leaf = 0; leaf < (1u << depth); ++leaf) {
+        std::vector<uint32_t> msg(N);
+        for (size_t i = 0; i < N; ++i) msg[i] = encode_message((uint32_t)((leaf * 5 + i) & 3u), tfhe_params);
+        leaves.push_back(encrypt_glwe_plaintext(e3, msg, glwe_secret_key, gen));
+        table.push_back((leaf * 3 + 2) & 3u);
+      }
+      for (uint64_t address = 0; address < (1u << depth); ++address) {
+        std::vector<GgswCiphertext> selectors = encrypt_address(e3, address, depth, glwe_secret_key, gen);
+        EXPECT(selectors.size() == depth, "one GGSW per address bit");
+        auto pt = decrypt_glwe_ciphertext(e3, glwe_secret_key, cmux_tree(e3, selectors, leaves));
+        bool ok = true;
+        for (size_t i = 0; i < N; ++i) ok = ok && decode(pt[i]) == (uint32_t)((address * 5 + i) & 3u);
+        EXPECT(ok, "cmux_tree selects the addressed leaf");
+        LweCiphertext looked = table_lookup(e3, selectors, table);
+        EXPECT(looked.data.size() == k * N + 1, "table_lookup result is under the flattened GLWE key");
+        EXPECT(decode(decrypt_lwe(e3, big_key, looked)) == table[address], "table_lookup returns table[address]");
+        EXPECT(dec_msg(key_switch_lwe(e3, looked)) == table[address], "table_lookup result survives the key switch");
+      }
+    }
+    // blind_rotate_glwe / bootstrap_glwe on the trivial accumulator (0, .., 0, tv << tv_shift) with offset 0 are the
+    // rotation and the bootstrap from the clear test vector, bit for bit; with an offset the two wrappers still agree
+    {
+      const std::vector<uint32_t> tv = construct_test_from_lut(tfhe_params, {1, 3, 0, 2});
+      GlweCiphertext acc{std::vector<uint32_t>(glwe_words, 0u)};
+      for (size_t i = 0; i < N; ++i) acc.data[k * N + i] = tv[i] << (32 - tfhe_params.log_p - tfhe_params.padding_bits);
+      for (uint32_t m = 0; m < 4; ++m) {
+        LweCiphertext ct = enc(m);
+        std::vector<uint32_t> want(glwe_words);
+        e3.check(tfhe_blind_rotate_batch(e3.raw(), ct.data.data(), 1, tv.data(), 1, want.data()));
+        EXPECT(blind_rotate_glwe(e3, ct, acc).data == want, "blind_rotate_glwe on a trivial accumulator == blind_rotate");
+        EXPECT(bootstrap_glwe(e3, ct, acc).data == bootstrap(e3, ct, tv).data, "bootstrap_glwe on a trivial accumulator == bootstrap");
+        const size_t offset = 2 * N - 3;
+        LweCiphertext by_hand = key_switch_lwe(e3, sample_extract(e3, blind_rotate_glwe(e3, ct, acc, offset), 0));
+        EXPECT(bootstrap_glwe(e3, ct, acc, offset).data == by_hand.data, "bootstrap_glwe == rotate, extract, key switch");
+      }
+    }
+    // tree_lut with d = 2: every input decodes to the table entry (packing key from the flattened GLWE key)
+    {
+      load_packing_key(e3, generate_packing_key(e3, big_key, glwe_secret_key, gen));
+      std::vector<uint32_t> table(16);
+      for (uint32_t x = 0; x < 16; ++x) table[x] = (x * 7 + 3 + (x >> 2)) & 3u;
+      bool ok = true;
+      for (uint32_t x = 0; x < 16; ++x) {
+        LweCiphertext out = tree_lut(e3, {enc(x & 3u), enc(x >> 2)}, table);
+        ok = ok && out.data.size() == n + 1 && dec_msg(out) == table[x];
+      }
+      EXPECT(ok, "tree_lut: table[x_0 + 4 x_1] for all 16 inputs");
+      // d = 1 is the bootstrap against the table's test vector
+      LweCiphertext one = enc(2);
+      std::vector<uint32_t> lut(table.begin(), table.begin() + 4);
+      EXPECT(tree_lut(e3, {one}, lut).data == bootstrap(e3, one, construct_test_from_lut(tfhe_params, lut)).data,
+             "tree_lut with one digit == bootstrap");
+    }
+  }
   // error behaviour: the reference panics, the mirror throws
   {
     bool threw = false;

@@ -75,16 +75,23 @@ int emu_lookup(int field, int g, u32 k, u32 logn, u32 log_p, u32 padding, u32 lo
                size_t queries, u32 address_bits, u32 first, u32 tree_depth, u32 height, const u32* leaves, const u32* table,
                int shared, u32 tables, u32* glwe_out, u32* lwe_out) {
   PbsParams P = make_params(0, k, logn, log_p, padding, log_base, levels);
-  // few shapes: the complex transform and Goldilocks at N = 512, the complex transform at N = 1024; k = 1, one wave
-  // per polynomial
-#define LOOKUP(FF, L)                                                                                                      \
-  lookup<FF, L, 1, 1>(P, (const FF::elem*)selectors, queries, address_bits, first, tree_depth, height, leaves, table, shared, \
-                      tables, glwe_out, lwe_out)
-  if (k != 1 || g != 1) return 2;
-  if (field == 5 && logn == 9) LOOKUP(FftField, 9);
-  else if (field == 5 && logn == 10) LOOKUP(FftField, 10);
-  else if (field == 1 && logn == 9) LOOKUP(GlField, 9);
-  else return 1;
+  // few shapes: the complex transform and Goldilocks at N = 512, the complex transform at N = 1024 (k = 1, one wave per
+  // polynomial); the complex transform at k = 2: N = 512, and N = 2048 over four waves per polynomial
+#define LOOKUP(FF, L, KK, GG)                                                                                                \
+  lookup<FF, L, KK, GG>(P, (const FF::elem*)selectors, queries, address_bits, first, tree_depth, height, leaves, table, shared, \
+                        tables, glwe_out, lwe_out)
+  if (k == 1 && g == 1) {
+    if (field == 5 && logn == 9) LOOKUP(FftField, 9, 1, 1);
+    else if (field == 5 && logn == 10) LOOKUP(FftField, 10, 1, 1);
+    else if (field == 1 && logn == 9) LOOKUP(GlField, 9, 1, 1);
+    else return 1;
+  } else if (k == 2 && field == 5) {
+    if (logn == 9 && g == 1) LOOKUP(FftField, 9, 2, 1);
+    else if (logn == 11 && g == 4) LOOKUP(FftField, 11, 2, 4);
+    else return 1;
+  } else {
+    return 2;
+  }
 #undef LOOKUP
   return 0;
 }

@@ -9,26 +9,32 @@
 extern "C" {
 
 // kernel: 0 = team, one sample per team; 1 = team, two samples (call emu_set_samples_per_team(2) first; complex
-// transform only); 2 = wide team; 3 = pair kernel (complex transform, N = 512).  k = 1, one wave per polynomial.
-// acc [acc_count][2][N], acc_count = 1 or batch.  emu_set_segments cuts the rotation as for emu_blind_rotate.
-int emu_blind_rotate_glwe(int field, int kernel, u32 n, u32 logn, u32 log_base, u32 levels, size_t batch, const u32* lwe,
-                          const u32* acc, size_t acc_count, u32 offset, const void* bsk, u32* out_glwe, u32* out_lwe) {
-  PbsParams P = make_params(n, 1, logn, 2, 1, log_base, levels);
+// transform only); 2 = wide team; 3 = pair kernel (complex transform, N = 512).  g waves per polynomial; the wide team
+// and the pair kernel: k = 1, g = 1.
+// acc [acc_count][k+1][N], acc_count = 1 or batch.  emu_set_segments cuts the rotation as for emu_blind_rotate.
+int emu_blind_rotate_glwe(int field, int kernel, int g, u32 k, u32 n, u32 logn, u32 log_base, u32 levels, size_t batch,
+                          const u32* lwe, const u32* acc, size_t acc_count, u32 offset, const void* bsk, u32* out_glwe,
+                          u32* out_lwe) {
+  PbsParams P = make_params(n, k, logn, 2, 1, log_base, levels);
   P.acc_glwe = 1;
   P.acc_offset = offset;
-  const size_t stride = acc_count == 1 ? 0 : (size_t)2 << logn;
+  const size_t stride = acc_count == 1 ? 0 : (size_t)(k + 1) << logn;
   if (acc_count != 1 && acc_count != batch) return 5;
   if (offset >= (2u << logn)) return 6;
-#define TEAM(FF, L, NS) blind_rotate<FF, L, 1, 1, NS>(P, batch, lwe, acc, stride, (const FF::elem*)bsk, out_glwe, out_lwe)
+  if (kernel >= 2 && (k != 1 || g != 1)) return 1;
+#define TEAM(FF, L, KK, GG, NS) blind_rotate<FF, L, KK, GG, NS>(P, batch, lwe, acc, stride, (const FF::elem*)bsk, out_glwe, out_lwe)
   if (kernel == 0) {
-    if (field == 5 && logn == 9) TEAM(FftField, 9, 1);
-    else if (field == 5 && logn == 10) TEAM(FftField, 10, 1);
-    else if (field == 1 && logn == 9) TEAM(GlField, 9, 1);
+    if (field == 5 && logn == 9 && k == 1 && g == 1) TEAM(FftField, 9, 1, 1, 1);
+    else if (field == 5 && logn == 10 && k == 1 && g == 1) TEAM(FftField, 10, 1, 1, 1);
+    else if (field == 1 && logn == 9 && k == 1 && g == 1) TEAM(GlField, 9, 1, 1, 1);
+    else if (field == 5 && logn == 9 && k == 2 && g == 1) TEAM(FftField, 9, 2, 1, 1);
     else return 1;
   } else if (kernel == 1) {
-    if (g_samples_per_team != 2) return 4;
-    if (field == 5 && logn == 9) TEAM(FftField, 9, 2);
-    else if (field == 5 && logn == 10) TEAM(FftField, 10, 2);
+    if (g_samples_per_team != 2 || field != 5) return 4;
+    if (logn == 9 && k == 1 && g == 1) TEAM(FftField, 9, 1, 1, 2);
+    else if (logn == 10 && k == 1 && g == 1) TEAM(FftField, 10, 1, 1, 2);
+    else if (logn == 9 && k == 2 && g == 1) TEAM(FftField, 9, 2, 1, 2);
+    else if (logn == 11 && k == 2 && g == 4) TEAM(FftField, 11, 2, 4, 2);
     else return 1;
   } else if (kernel == 2) {
     if (field != 5) return 1;

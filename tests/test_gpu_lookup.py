@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 BACKENDS = {"goldilocks": 1, "fp64-p42": 2, "goldilocks-split": 3, "fp64-p49": 4, "fp64-fft": 5}
-SHAPES = [(1, 9), (1, 10), (2, 9), (2, 11)]  # (k, log2 N)
+SHAPES = [(1, 9), (1, 10), (1, 11), (2, 9), (2, 10), (2, 11)]  # (k, log2 N): every instantiated ring shape
 DECOMPOSERS = [((8, 4), False), ((4, 6), False), ((2, 5), False), ((7, 3), False), ((7, 3), True)]
 # depth, queries, tables, one shared leaf set: depths 1, 2, 3, 5; queries 1 and 3; tables 1 and 2; both kinds of sets
 TREES = [(1, 3, 2, True), (2, 1, 1, False), (3, 3, 1, False), (3, 3, 2, True), (5, 1, 2, True), (5, 3, 2, False)]

@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 BACKENDS = {"goldilocks": 1, "fp64-p42": 2, "goldilocks-split": 3, "fp64-p49": 4, "fp64-fft": 5}
-SHAPES = [(1, 9), (1, 10), (2, 9), (2, 11)]  # (k, log2 N)
+SHAPES = [(1, 9), (1, 10), (1, 11), (2, 9), (2, 10), (2, 11)]  # (k, log2 N): every instantiated ring shape
 KS_DECS = [((4, 8), False), ((8, 4), False), ((2, 16), False), ((7, 3), False), ((7, 3), True)]
 PBS_ANY = (2, 5)  # a PBS decomposer every backend admits at every shape: the KS decomposer is what these tests vary
 

@@ -15,6 +15,7 @@ import clear_model_packing as cmp_
 import clear_model_tree as ct
 import golden_common as gc
 import test_gpu_clear_model as tcm
+import test_gpu_packing as tgp
 from gpu_common import pkg, rand_u32
 
 pytestmark = pytest.mark.gpu
@@ -114,7 +115,7 @@ def test_segmented_two_stream_rotation_initialises_in_segment_zero():
 
 # ------------------------------------------------------------------------------------------------ 3: clear model (I10)
 @pytest.mark.parametrize("dec,aligned", [((4, 8), False), ((7, 3), True)])
-@pytest.mark.parametrize("k,logn", [(1, 9), (2, 9), (1, 10), (1, 11)])
+@pytest.mark.parametrize("k,logn", [(1, 9), (2, 9), (1, 10), (1, 11), (2, 10), (2, 11)])
 def test_i10_rotation_of_masked_accumulators(k, logn, dec, aligned):
     """noise-free keys, random masked accumulators, 64 rows with the edge inputs: phi_S(out) = X^{rho - o} phi_S(acc) on all N
     coefficients of every row for offsets 0, rep/2 and 2N-1 -- exactly with (4,8) (no ignored bits); with (7,3) aligned
@@ -175,6 +176,16 @@ class TreeKeys(tcm.Keys):
         return c
 
 
+def pack_folded(ctx, res, rep, limit_words=1 << 26):
+    """Pack of the materialised N-fold list of res [groups][B][k N + 1] (every result `rep` times): as many groups per
+    pack_lwe call as keep the list under 256 MiB -- at N = 2048, k = 2 one group's list is 32 MiB.  (A call of several
+    groups is the calls of its groups: tests/test_gpu_packing.py.)"""
+    groups, B, width = res.shape
+    per = max(1, limit_words // (B * rep * width))
+    return np.concatenate([ctx.pack_lwe(np.ascontiguousarray(np.repeat(res[g0:g0 + per], rep, axis=1)))
+                           for g0 in range(0, groups, per)])
+
+
 def compose(ctx, p, digits, table):
     """the tree LUT from public entry points, host forms: digits d x [rows][n+1], table [sets][tables][B^d]"""
     m = pkg()
@@ -186,8 +197,7 @@ def compose(ctx, p, digits, table):
     res = ctx.sample_extract(ctx.blind_rotate(np.repeat(digits[0], tables * subs, axis=0), tvs), 0)
     for t in range(1, d):
         groups = res.shape[0] // B
-        folded = np.ascontiguousarray(np.repeat(res.reshape(groups, B, -1), rep, axis=1))  # the materialised N-fold list
-        packed = ctx.pack_lwe(folded)
+        packed = pack_folded(ctx, res.reshape(groups, B, -1), rep)
         res = ctx.sample_extract(ctx.blind_rotate_glwe(np.repeat(digits[t], groups // rows, axis=0), packed, rep // 2), 0)
     return ctx.key_switch(res).reshape(rows, tables, -1)
 
@@ -289,6 +299,221 @@ def test_tree_lut_with_three_bit_digits_at_n1024():
             assert np.array_equal(cm.lwe_phase(out, keys.s.cpu().numpy()), expected_phase(p, digits, x, table, keys.s.cpu().numpy())), call
             if call == 0:
                 assert np.array_equal(out, compose(ctx, p, digits, table))
+
+
+# ------------------------------------------------------------------------------------------------ 4b: every shape
+KS_N2048 = (8, 2)  # two levels: a packing key from dimension k N is k N l_ks (k+1) N words, 200 MB at (2, 11) even so
+PACK_COLS_WORDS = 16 << 20  # capi.cpp::kPackColsWords: transposed inputs of one launch pair of a packing call
+
+
+def tree_backend(p, b, k, logn, ks, load):
+    """a context of backend b with load(ctx) done, or None after asserting the refusal the two independent tables state:
+    the PBS decomposer at context creation (test_gpu_clear_model.refused), the KS decomposer at the packing key's load
+    (test_gpu_packing.packing_refused)"""
+    m = pkg()
+    pbs = (p.pbs_decomposer.log_base, p.pbs_decomposer.levels)
+    try:
+        ctx = tcm.context(p, b)
+    except m.TfheError as e:
+        assert e.status == m.TFHE_ERR_EXACTNESS and tcm.refused(b, k, logn, pbs), (b, k, logn, e.status)
+        return None
+    assert not tcm.refused(b, k, logn, pbs), (b, k, logn)
+    try:
+        load(ctx)
+    except m.TfheError as e:
+        ctx.close()
+        assert e.status == m.TFHE_ERR_EXACTNESS and tgp.packing_refused(b, k, logn, ks), (b, k, logn, ks, e.status)
+        return None
+    assert not tgp.packing_refused(b, k, logn, ks), (b, k, logn, ks)
+    return ctx
+
+
+@pytest.mark.parametrize("k,logn", tcm.SHAPES)
+def test_tree_lut_every_shape_every_admitting_backend(k, logn):
+    """n = 4, log_p = 2, d = 2, all 16 inputs in ONE call, two tables, per-row table sets: 128 rotations at level 0, 32
+    packed groups at level 1 -- more than one launch pair of the packing wherever 16 Mi words hold fewer than 32 groups'
+    transposed inputs (every shape but (1, 9); one group per pair at (2, 11); a ragged last pair at (1, 10), (1, 11)).
+    Every backend that admits PBS (4, 8) and the KS decomposer runs; the others' refusals are asserted.
+    N <= 1024: noise-free keys, KS (4, 8): I12 on every row in every backend.  N = 2048: KS (8, 2) and uniformly random
+    key words made on the device (the arithmetic is total).  Every backend's words equal compose() -- evaluated once per
+    shape, in the first backend that runs: the entry points it is made of are pinned per backend by their own tests."""
+    N = 1 << logn
+    exact = logn <= 10
+    ks = (4, 8) if exact else KS_N2048
+    p = tcm.params(k, logn, 4, (4, 8), ks=ks)
+    B, d, batch, tables = 4, 2, 16, 2
+    groups = batch * tables * B ** (d - 1) // B
+    chunk = PACK_COLS_WORDS // ((p.big_n + 1) * N)
+    assert groups == 32 and chunk >= 1
+    assert (chunk < groups) == ((k, logn) != (1, 9)), chunk       # the level's packing goes out in several launch pairs
+    assert (chunk == 1) == ((k, logn) == (2, 11)), chunk
+    if (k, logn) in ((1, 10), (1, 11)):
+        assert groups % chunk != 0, chunk                          # a ragged last pair
+    g = tcm.gen(8200 + 10 * logn + k)
+    rng = np.random.default_rng(8200 + 10 * logn + k)
+    xs = np.arange(B ** d)
+    x = [(xs >> (p.log_p * t)) & (B - 1) for t in range(d)]
+    table = rng.integers(0, B, (batch, tables, B ** d)).astype(np.uint32)
+    if exact:
+        keys = TreeKeys(p, 8200 + 10 * logn + k)
+        s_host = keys.s.cpu().numpy()
+        digits = [host(cm.t_to_u32(keys.encrypt(g, torch.from_numpy(v).to(DEV), p.log_p))) for v in x]
+        load = keys.load
+    else:
+        bsk, ksk = cm.t_to_u32(tcm.rand_words(g, p.bsk_shape())), cm.t_to_u32(tcm.rand_words(g, p.ksk_shape()))
+        pksk = cm.t_to_u32(tcm.rand_words(g, p.pksk_shape(p.big_n)))
+        digits = [host(cm.t_to_u32(tcm.edge_lwes(g, batch, p.n, N))) for _ in range(d)]
+
+        def load(ctx):
+            ctx.load_bootstrapping_key(bsk, ksk)
+            ctx.load_packing_key(pksk)
+    want, ran = None, []
+    for b in BACKENDS:
+        ctx = tree_backend(p, b, k, logn, ks, load)
+        if ctx is None:
+            continue
+        with ctx:
+            out = ctx.tree_lut(digits, table)
+            assert out.shape == (batch, tables, p.n + 1)
+            if want is None:
+                want = compose(ctx, p, digits, table)
+            bad = np.argwhere(out != want)
+            assert bad.size == 0, (b, ran, bad[:4].tolist())
+            if exact:
+                got = cm.lwe_phase(out, s_host)
+                assert np.array_equal(got, expected_phase(p, digits, x, table, s_host)), b
+                assert np.array_equal(got & 0x7FFFFFFF, cm.encode(ct.table_entry(table, x, p.log_p), p.log_p)), b
+            ctx.set_stream(None)
+        ran.append(b)
+    assert len(ran) >= 2, ran
+
+
+# ------------------------------------------------------------------------------------------------ 4c: digit widths
+def edge_digit_rows(B, d, rows):
+    """`rows` digit tuples with 0 and B - 1 in every position: row 0 alternates 0, B-1, .., row 1 the opposite, the rest
+    fixed mid-range values -> x as d arrays [rows]"""
+    x = np.zeros((d, rows), dtype=np.int64)
+    for t in range(d):
+        x[t, 0] = 0 if t % 2 == 0 else B - 1
+        x[t, 1] = B - 1 if t % 2 == 0 else 0
+        for r in range(2, rows):
+            x[t, r] = (5 * r + 3 * t + 1) % B
+    assert all(0 in x[t] and B - 1 in x[t] for t in range(d))
+    return [x[t] for t in range(d)]
+
+
+# k, log2 N, log_p, d, rows, tables, one shared table set
+WIDTHS = [(1, 9, 1, 3, 4, 2, False),     # B = 2: the narrowest digit, rep = 256
+          (1, 9, 6, 2, 3, 1, False),     # B = 64, rep = 8
+          (1, 9, 8, 2, 2, 1, True),      # B = 256, rep = 2, mid = 1: 65,536 entries, the most a call may have
+          (1, 10, 4, 3, 3, 1, True)]     # B = 16, d = 3 at N = 1024: 256 sub-tables per (row, table)
+
+
+@pytest.fixture(scope="module")
+def tree_keys_n1024():
+    p = tcm.params(1, 10, 4, (4, 8), ks=(4, 8))
+    return p, TreeKeys(p, 8300)
+
+
+@pytest.mark.parametrize("k,logn,log_p,d,rows,tables,shared", WIDTHS)
+def test_tree_lut_digit_width_edges(tree_keys, tree_keys_n1024, k, logn, log_p, d, rows, tables, shared):
+    """log_p in {1, 6, 8} at N = 512 and 4 at N = 1024, digits with 0 and B - 1 in every position: the call equals compose()
+    bit for bit; I12 where its premise can be guaranteed -- n = 4 noise-free digits drift by at most (n + 1) / 2 = 2.5
+    units of 1/2N (the body's rounding and one per key bit), inside rep / 2 for rep >= 8 and not for rep = 2.
+    tree_lut_test_vectors_kernel on its own at the same width: the d = 1 call equals bootstrap against
+    construct_test_from_lut of each row's table, and those test vectors are clear_model_tree.test_from_lut."""
+    m = pkg()
+    _, keys = tree_keys if logn == 9 else tree_keys_n1024
+    p = tcm.params(k, logn, 4, (4, 8), ks=(4, 8), log_p=log_p)
+    B, rep = 1 << log_p, p.N >> log_p
+    s_host = keys.s.cpu().numpy()
+    g = tcm.gen(8400 + log_p)
+    rng = np.random.default_rng(8400 + log_p)
+    x = edge_digit_rows(B, d, rows)
+    table = rng.integers(0, B, (1 if shared else rows, tables, B ** d)).astype(np.uint32)
+    digits = [host(cm.t_to_u32(keys.encrypt(g, torch.from_numpy(v).to(DEV), log_p))) for v in x]
+    with tcm.context(p) as ctx:
+        keys.load(ctx)
+        out = ctx.tree_lut(digits, table)
+        assert out.shape == (rows, tables, p.n + 1)
+        assert np.array_equal(out, compose(ctx, p, digits, table))
+        if rep >= 8:
+            assert (p.n + 1) / 2 < rep // 2
+            got = cm.lwe_phase(out, s_host)
+            assert np.array_equal(got, expected_phase(p, digits, x, table, s_host))
+            assert np.array_equal(got & 0x7FFFFFFF, cm.encode(ct.table_entry(table, x, log_p), log_p))
+        # one digit: the level-0 test vectors alone
+        luts = np.broadcast_to(table, (rows, tables, B ** d))[:, :, :B]
+        one = ctx.tree_lut(digits[:1], np.ascontiguousarray(luts))
+        for t in range(tables):
+            tvs = np.stack([m.construct_test_from_lut(p, lut) for lut in luts[:, t]])
+            assert np.array_equal(tvs, ct.test_from_lut(luts[:, t], p.N, log_p)), t
+            assert np.array_equal(one[:, t], ctx.bootstrap(digits[0], tvs)), t
+        ctx.set_stream(None)
+
+
+# ------------------------------------------------------------------------------------------------ 4d: KS-first, k = 2
+def test_tree_lut_key_switch_first_order_k2_three_digits():
+    """(2, 9), d = 3, per-row table sets, three tables, KS-first: digits and output under the flattened GLWE key (k N =
+    1024 mask words), every digit key-switched before its level; I12 against the key-switched digits' rotation indices"""
+    p = tcm.params(2, 9, 4, (4, 8), ks=(4, 8))
+    keys = TreeKeys(p, 8500)
+    B, d, tables = 1 << p.log_p, 3, 3
+    xs = np.array([0, 63, 21, 42, 7, 56, 30, 33])
+    batch = xs.size
+    x = [(xs >> (p.log_p * t)) & (B - 1) for t in range(d)]
+    g = tcm.gen(97)
+    rng = np.random.default_rng(97)
+    table = rng.integers(0, B, (batch, tables, B ** d)).astype(np.uint32)
+    flat = keys.S.reshape(-1)
+    with tcm.context(p) as ctx:
+        keys.load(ctx)
+        ctx.set_bootstrap_order(True)
+        digits = [host(cm.t_to_u32(keys.encrypt(g, torch.from_numpy(v).to(DEV), p.log_p, key=flat))) for v in x]
+        out = ctx.tree_lut(digits, table)
+        assert out.shape == (batch, tables, p.big_n + 1)
+        small = [ctx.key_switch(c) for c in digits]  # what each level rotates by
+        got = cm.lwe_phase(out, flat.cpu().numpy())
+        assert np.array_equal(got, expected_phase(p, small, x, table, keys.s.cpu().numpy()))
+        assert np.array_equal(got & 0x7FFFFFFF, cm.encode(ct.table_entry(table, x, p.log_p), p.log_p))
+
+
+# ------------------------------------------------------------------------------------------------ 4e: segmented level 0
+def test_level_zero_above_the_resident_samples_goes_out_in_segments():
+    """(1, 9), n = 16, d = 3, log_p = 2: level 0 has 16 rotations per row, and the batch is chosen from the context's own plan
+    so that they exceed what the chip holds -- the rotation over the EXPANDED digit and test-vector buffers goes out in
+    key-slice segments on two streams.  Random keys.  The first, middle and last three rows equal the same rows sent as a
+    call of three (per-row table sets travel with their rows); the device form after reserve_tree_lut gives the bytes of
+    the host form."""
+    p = tcm.params(1, 9, 16, (2, 16), ks=(4, 5))  # 32 digit rows: a prepared key of several L2-sized slices at N = 512
+    B, d, tables = 1 << p.log_p, 3, 1
+    per_row = tables * B ** (d - 1)
+    g = tcm.gen(4)
+    with tcm.context(p) as ctx:
+        ctx.load_bootstrapping_key(cm.t_to_u32(tcm.rand_words(g, p.bsk_shape())), cm.t_to_u32(tcm.rand_words(g, p.ksk_shape())))
+        ctx.load_packing_key(cm.t_to_u32(tcm.rand_words(g, p.pksk_shape(p.big_n))))
+        # the kernel -- and with it what the chip holds -- depends on the count: step past the resident samples of the kernel
+        # the plan picks until it cuts the rotation
+        batch = 1
+        for _ in range(4):
+            plan = ctx.blind_rotate_plan(batch * per_row)
+            if plan["segments"] > 1:
+                break
+            batch = plan["resident_samples"] // per_row + 3
+        assert plan["segments"] > 1 and batch * per_row > plan["resident_samples"], plan
+        digits = [cm.t_to_u32(tcm.rand_words(g, (batch, p.n + 1))) for _ in range(d)]
+        table = torch.randint(0, B, (batch, tables, B ** d), generator=g, device=DEV, dtype=torch.int32)
+        ctx.reserve_tree_lut(batch, d, tables)
+        on_device = ctx.tree_lut(digits, table)
+        torch.cuda.synchronize()
+        ctx.set_stream(None)
+        h_digits, h_table = [host(c) for c in digits], host(table)
+        out = ctx.tree_lut(h_digits, h_table)
+        assert out.shape == (batch, tables, p.n + 1)
+        assert np.array_equal(host(on_device), out)
+        for rows in (slice(0, 3), slice(batch // 2, batch // 2 + 3), slice(batch - 3, batch)):
+            few = ctx.tree_lut([np.ascontiguousarray(c[rows]) for c in h_digits], np.ascontiguousarray(h_table[rows]))
+            assert np.array_equal(out[rows], few), rows
 
 
 # ------------------------------------------------------------------------------------------------ 5: real noise
