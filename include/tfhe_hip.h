@@ -114,7 +114,11 @@ void tfhe_context_destroy(tfhe_context *ctx);
 int tfhe_context_set_stream(tfhe_context *ctx, void *hip_stream);
 int tfhe_context_use_own_stream(tfhe_context *ctx);
 int tfhe_context_synchronize(tfhe_context *ctx);
-/* Pre-sizes the per-batch workspace so that later _device calls up to `max_batch` never allocate. */
+/* Pre-sizes the per-batch workspace so that later _device calls up to `max_batch` never allocate.
+ * A call beyond the reservation (a host form of a larger batch, a larger tfhe_context_reserve) frees the
+ * workspace and allocates a larger one.  A captured graph (hipGraph) of _device calls has the workspace's
+ * device pointers baked in, so reserve the largest batch BEFORE capturing: a graph captured earlier must
+ * not be replayed after the workspace grew (it would touch freed memory), it has to be captured again. */
 int tfhe_context_reserve(tfhe_context *ctx, size_t max_batch);
 const char *tfhe_last_error(const tfhe_context *ctx);
 const char *tfhe_status_string(int status);
@@ -411,7 +415,19 @@ int tfhe_construct_test_from_lut(const tfhe_params *params, const uint32_t *lut,
 int tfhe_construct_test_vector_boolean(const tfhe_params *params, const uint32_t truth[4],
                                        uint32_t *out);
 /* and()/or(): boolean.rs:9-53 generalised over the closure: out = bootstrap(2*ct1 + ct0) with the
- * closure's test vector.  AND = {0,0,0,1}, OR = {0,1,1,1}, NAND = {1,1,1,0}, XOR = {0,1,1,0}. */
+ * closure's test vector.  AND = {0,0,0,1}, OR = {0,1,1,1}, NAND = {1,1,1,0}, XOR = {0,1,1,0}.
+ *
+ * The table cache (tfhe_gate_batch* and tfhe_lut_gate_batch*).  The context keeps the device test vector of
+ * every truth table it has seen, keyed on the table's length and entries: 64 tables, the least recently used
+ * one replaced by the 65th.  The FIRST use of a table (and the first after it was replaced) builds the test
+ * vector on the host and uploads it, which synchronises the context's stream; a call with a cached table
+ * enqueues only.  An upload cannot happen while the stream is capturing: there the first use of a table is
+ * refused with TFHE_ERR_INVALID_ARGUMENT and nothing enqueued (the capture stays valid), so run every gate
+ * of a graph once eagerly before capturing it.
+ * Guarantee for captured graphs: a table looked up during a capture is pinned for the life of the context.
+ * Pinned tables are never replaced and do not count towards the 64 (each costs 4 N bytes of device memory),
+ * so the test vector a captured graph reads is never rewritten with another table, however many other
+ * tables go through the cache between replays. */
 int tfhe_gate_batch(tfhe_context *ctx, const uint32_t truth[4], const uint32_t *ct0,
                     const uint32_t *ct1, size_t batch, uint32_t *lwe_out);
 int tfhe_gate_batch_device(tfhe_context *ctx, const uint32_t truth[4], const uint32_t *ct0,

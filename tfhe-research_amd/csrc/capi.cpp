@@ -2157,11 +2157,17 @@ static int lut_gate_device(tfhe_context* ctx, const u32* truth, u32 inputs, cons
   tfhe_context::GateTv* slot = nullptr;
   for (auto& g : ctx->gate_tvs)
     if (g.truth.size() == entries && std::memcmp(g.truth.data(), truth, entries * sizeof(u32)) == 0) slot = &g;
+  // A captured graph keeps slot->d_tv and its replays never come back here, so a table looked up during a capture is
+  // pinned: its buffer is not handed to another table.  (A failed query is read as a capture, as the blind rotation's fork reads it.)
+  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+  const bool capturing = hipStreamIsCapturing(ctx->stream, &capture) != hipSuccess || capture != hipStreamCaptureStatusNone;
   if (!slot) {
     // first use of this truth table: build its test vector on the host and upload it (this one
     // call synchronises; later calls with a table already seen do not).  At most kMaxGateTvs
-    // tables are kept; the least recently used one is replaced.
-    constexpr size_t kMaxGateTvs = 64;
+    // unpinned tables are kept; the least recently used of them is replaced.
+    if (capturing)
+      return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                  "first use of this truth table during a stream capture: its upload synchronises, run the gate once before capturing");
     const u32 pm = 1u << ctx->params.log_p;
     std::vector<u32> lut(pm), tv(ctx->N);
     for (u32 x = 0; x < pm; ++x) lut[x] = truth[x & (entries - 1)];  // test_vector.rs:16 for m = 2
@@ -2169,20 +2175,23 @@ static int lut_gate_device(tfhe_context* ctx, const u32* truth, u32 inputs, cons
       return fail(ctx, st, "truth table / plaintext space mismatch");
     TFHE_TRY(check_tv_host(ctx, tv.data(), ctx->N));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->gate_tvs.size() < kMaxGateTvs) {
+    size_t unpinned = 0;
+    for (auto& g : ctx->gate_tvs) {
+      if (g.pinned) continue;
+      ++unpinned;
+      if (!slot || g.last_use < slot->last_use) slot = &g;  // the victim, if one is needed
+    }
+    if (unpinned < tfhe_context::kMaxGateTvs) {  // room left, or every entry is pinned: the cache grows
       ctx->gate_tvs.emplace_back();
       slot = &ctx->gate_tvs.back();
       HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&slot->d_tv), ctx->N * sizeof(u32)));
-    } else {
-      slot = &ctx->gate_tvs[0];
-      for (auto& g : ctx->gate_tvs)
-        if (g.last_use < slot->last_use) slot = &g;
     }
     slot->truth.clear();  // not a valid entry until the upload has succeeded
     HIP_TRY(ctx, hipMemcpy(slot->d_tv, tv.data(), ctx->N * sizeof(u32), hipMemcpyHostToDevice));
     slot->truth.assign(truth, truth + entries);
   }
   slot->last_use = ++ctx->gate_clock;
+  if (capturing) slot->pinned = true;
   const u32* d_in = cts[0];
   for (u32 i = 1; i < inputs; ++i) {  // 2*ct1 + ct0 (boolean.rs:18), then + 4*ct2, ...
     HIP_TRY(ctx, launch::lwe_linear(ctx->stream, 1u, d_in, 1u << i, cts[i], words, ctx->d_lwe_in2));

@@ -61,11 +61,16 @@ struct tfhe_context {
   u32* d_glwe_c = nullptr;
   u32* d_tv = nullptr;        // [batch][N] (or [1][N])
   // test vectors of gate calls, one [N] device buffer per truth table seen (a gate graph alternates
-  // between a handful of tables; re-uploading on every switch would synchronise the stream)
+  // between a handful of tables; re-uploading on every switch would synchronise the stream).  kMaxGateTvs unpinned
+  // tables are kept, the least recently used one is replaced.  A table looked up while the stream is capturing is
+  // pinned for the life of the context: the captured graph holds d_tv, a replay does not pass through the cache, so
+  // that buffer is never rewritten with another table (pinned entries do not count towards the limit).
+  static constexpr size_t kMaxGateTvs = 64;
   struct GateTv {
     std::vector<u32> truth;  // 2^inputs entries
     u32* d_tv = nullptr;
     unsigned long long last_use = 0;
+    bool pinned = false;
   };
   std::vector<GateTv> gate_tvs;
   unsigned long long gate_clock = 0;
