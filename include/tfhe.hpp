@@ -570,6 +570,58 @@ inline LweCiphertext table_lookup(Engine& e, const std::vector<GgswCiphertext>& 
   e.check(tfhe_table_lookup(e.raw(), sel.data(), 1, depth, table.data(), 1, 1, out.data.data()));
   return out;
 }
+// ---- DEMUX tree and encrypted table update (tfhe_hip.h states the operations; first device only) ----
+// Demux(C_0 .. C_{d-1}; x): 2^d leaves, leaf sum_i b_i 2^i carries x and every other one an encryption of 0
+inline std::vector<GlweCiphertext> demux_tree(Engine& e, const std::vector<GgswCiphertext>& selectors, const GlweCiphertext& x) {
+  const TfheParams& p = e.params();
+  const size_t depth = selectors.size(), glwe = (p.glwe_dimension + 1) * p.degree();
+  if (depth == 0 || depth > 20 || x.data.size() != glwe) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "one GLWE, depth 1..20");
+  const std::vector<uint32_t> sel = flatten_selectors(p, selectors);
+  std::vector<uint32_t> flat(((size_t)1 << depth) * glwe);
+  e.check(tfhe_demux_tree(e.raw(), sel.data(), 1, depth, x.data.data(), 1, flat.data(), 1, 0));
+  std::vector<GlweCiphertext> leaves;
+  for (size_t i = 0; i < (size_t)1 << depth; ++i)
+    leaves.push_back(GlweCiphertext{std::vector<uint32_t>(flat.begin() + i * glwe, flat.begin() + (i + 1) * glwe)});
+  return leaves;
+}
+// A table of 2^depth entries as table_write / table_lookup_glwe hold it: max(1, 2^depth / N) GLWEs, entry a in
+// coefficient a mod N of GLWE a / N.  (A trivial GLWE of encoded values is a valid start: see tfhe_hip.h.)
+inline size_t table_glwes(const TfheParams& p, size_t depth) {
+  return (size_t)1 << (depth > p.glwe_poly_degree ? depth - p.glwe_poly_degree : 0);
+}
+// table[address] += value, obliviously; `value` holds the encoded value in coefficient 0 of its phase.  The write ADDS:
+// to replace an entry write new - old (old = table_lookup_glwe, packed with pack_lwe of that one ciphertext).
+inline void table_write(Engine& e, const std::vector<GgswCiphertext>& selectors, const GlweCiphertext& value,
+                        std::vector<GlweCiphertext>& table) {
+  const TfheParams& p = e.params();
+  const size_t depth = selectors.size(), glwe = (p.glwe_dimension + 1) * p.degree();
+  if (depth == 0 || depth > p.glwe_poly_degree + 20 || table.size() != table_glwes(p, depth) || value.data.size() != glwe)
+    throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "max(1, 2^depth / N) table GLWEs, depth 1..log2 N + 20");
+  const std::vector<uint32_t> sel = flatten_selectors(p, selectors);
+  std::vector<uint32_t> flat(table.size() * glwe);
+  for (size_t i = 0; i < table.size(); ++i) {
+    if (table[i].data.size() != glwe) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "GLWE shape");
+    std::copy(table[i].data.begin(), table[i].data.end(), flat.begin() + i * glwe);
+  }
+  e.check(tfhe_table_write(e.raw(), sel.data(), 1, depth, value.data.data(), flat.data(), 1, 1));
+  for (size_t i = 0; i < table.size(); ++i) std::copy(flat.begin() + i * glwe, flat.begin() + (i + 1) * glwe, table[i].data.begin());
+}
+// table[address] of an encrypted table (table_write's layout) -> LWE of k N + 1 words under the flattened GLWE key
+inline LweCiphertext table_lookup_glwe(Engine& e, const std::vector<GgswCiphertext>& selectors, const std::vector<GlweCiphertext>& table) {
+  const TfheParams& p = e.params();
+  const size_t depth = selectors.size(), glwe = (p.glwe_dimension + 1) * p.degree();
+  if (depth == 0 || depth > p.glwe_poly_degree + 20 || table.size() != table_glwes(p, depth))
+    throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "max(1, 2^depth / N) table GLWEs, depth 1..log2 N + 20");
+  const std::vector<uint32_t> sel = flatten_selectors(p, selectors);
+  std::vector<uint32_t> flat(table.size() * glwe);
+  for (size_t i = 0; i < table.size(); ++i) {
+    if (table[i].data.size() != glwe) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "GLWE shape");
+    std::copy(table[i].data.begin(), table[i].data.end(), flat.begin() + i * glwe);
+  }
+  LweCiphertext out{std::vector<uint32_t>(p.glwe_dimension * p.degree() + 1)};
+  e.check(tfhe_table_lookup_glwe(e.raw(), sel.data(), 1, depth, flat.data(), 1, 1, out.data.data()));
+  return out;
+}
 // ---- rotation from a GLWE accumulator and the tree LUT (tfhe_hip.h states the operations; first device only) ----
 // X^{-(b~ + rotation_offset)} acc, then the n CMUXes: the accumulator's words are taken as they are (already encoded)
 inline GlweCiphertext blind_rotate_glwe(Engine& e, const LweCiphertext& ct, const GlweCiphertext& acc, size_t rotation_offset = 0) {

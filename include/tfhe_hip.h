@@ -382,6 +382,81 @@ int tfhe_table_lookup_device(tfhe_context *ctx, const void *selectors_prepared, 
 int tfhe_table_lookup(tfhe_context *ctx, const uint32_t *selectors, size_t queries, size_t depth, const uint32_t *table,
                       size_t table_sets, size_t tables, uint32_t *lwe_out);
 
+/* ---- DEMUX tree and encrypted table update (no reference counterpart): the write port of the lookup ---------------
+ * All arithmetic mod 2^32; ext and cmux as above.  The DEMUX tree is the transpose of Tree: it pushes ONE GLWE down the
+ * selectors.
+ *   Demux(C_0 .. C_{d-1}; x):  M(d)_0 = x
+ *     for i = d-1 down to 0, j < 2^(d-1-i):
+ *        M(i)_{2j+1} = ext(C_i, M(i+1)_j)
+ *        M(i)_{2j}   = M(i+1)_j - M(i)_{2j+1}
+ *     leaves M(0)_0 .. M(0)_{2^d - 1}
+ *     Selector 0 is the least significant address bit and separates neighbouring leaves -- the convention of Tree, so
+ *     Tree and Demux address the same leaf.  With C_i a GGSW encryption of the bit b_i, leaf a = sum_i b_i 2^i has the
+ *     phase of x and every other leaf has phase 0.  Whatever the GGSWs hold, the leaves add up to x word for word.
+ *   Write(C_0 .. C_{D-1}; V; table), d_lo = min(D, log2 N), d_hi = D - d_lo:
+ *     x = V
+ *     for i = 0 .. d_lo - 1 in this order: x = cmux(C_i, x, X^{2^i} x)          (monomial index 2^i)
+ *     table[h] += Demux(C_{d_lo} .. C_{D-1}; x)_h   for h < 2^d_hi               (d_hi = 0: table[0] += x)
+ *     V is a GLWE whose phase holds the encoded value in coefficient 0: a fresh encryption, or tfhe_pack_lwe_batch with
+ *     per_group = 1 on a lookup's or a bootstrap's result.  Coefficients of V other than 0 move with it and wrap
+ *     negacyclically: coefficient c of V lands on coefficient c + (a mod 2^d_lo) of leaf a >> d_lo, negated past N.
+ *     The table is [2^d_hi][k+1][N] GLWEs with 2^d_lo entries per GLWE -- the leaf layout Lookup builds from a clear
+ *     table: entry a is coefficient a mod 2^d_lo of leaf a >> d_lo.
+ *   LookupGLWE(C_0 .. C_{D-1}; leaves [2^d_hi][k+1][N]):
+ *     root = Tree(C_{d_lo} .. ; leaves) (leaf 0 if d_hi = 0); the rotation chain of Lookup; out = sample_extract(root, 0)
+ *     -- the lookup over encrypted leaves instead of a clear table: what reads a written table back.
+ * A DEMUX tree is 2^d - 1 products, a write d_lo + 2^d_hi - 1.  No bootstrapping key is involved (nothing here returns
+ * TFHE_ERR_NO_KEY) and no new exactness rule applies.
+ *
+ * The write is ADDITIVE.  To replace entry a the caller writes new - old: old = tfhe_table_lookup_glwe at a, packed with
+ * tfhe_pack_lwe_batch(per_group = 1), subtracted from the GLWE of the new value word by word, then written at a.  Several
+ * queries into one shared table are a scatter-add: the leaves arrive as wrapping u32 atomic adds, which commute, so the
+ * words do not depend on the order of arrival.
+ *
+ * Noise: every leaf, addressed or not, gains at most the lookup's per-product variance times the number of address bits,
+ *   sigma^2 <= D * [ (k+1) l N (B^2/12 + 1/6) (sigma_glwe 2^32)^2 + (1 + k N / 2) 2^(2 ignored_bits) / 12 ]
+ * on top of the value's own noise: W writes into one table followed by a read carry at most (W + 1) D of those terms on
+ * every entry.
+ *
+ * Layouts.  selectors[_prepared] as for the lookup.  Query q writes leaf set q, or the one shared set (leaf_sets /
+ * table_sets = 1 or queries), once per value / table:
+ *   tfhe_demux_tree:        glwe_in [queries][values][k+1][N] -> leaves_out [leaf_sets][values][2^depth][k+1][N];
+ *                           accumulate = 0 stores and needs leaf_sets == queries, accumulate = 1 adds into what is there
+ *   tfhe_table_write:       values [queries][tables][k+1][N]  -> table_inout [table_sets][tables][2^d_hi][k+1][N], always adds
+ *   tfhe_table_lookup_glwe: leaves [leaf_sets][tables][2^d_hi][k+1][N] -> lwe_out [queries][tables][k N + 1]
+ * Outputs may not alias inputs.  Tree depth 1 .. 20, write and lookup depth 1 .. log2 N + 20.
+ *
+ * The _device forms of the first two run on the context's stream in a workspace sized by tfhe_context_reserve_demux(
+ * max_trees, max_tree_depth, max_write_bits) -- trees = queries * values (tables) -- and never allocate or synchronise
+ * (safe under stream capture; no second stream).  The reservation is a maximum: it covers every tfhe_demux_tree_device
+ * call of at most max_tree_depth levels and every tfhe_table_write_device call of at most max_write_bits address bits
+ * (either may be 0) over at most max_trees trees, under any subtree height.  It is the largest need over the heights
+ * 1 .. d of  trees 2^(d-h) (h - 1)  parked nodes  +  trees 2^(d-h)  [ceil(d/h) >= 2]  +  trees 2^(d-2h)  [ceil(d/h) >= 3]
+ * GLWEs of (k+1) N 4 bytes, d = max(max_tree_depth, max_write_bits - log2 N): at most 3/4 max_trees 2^d GLWEs.  A call
+ * beyond the reservation returns TFHE_ERR_INVALID_ARGUMENT with the need in bytes and enqueues nothing.
+ * tfhe_table_lookup_glwe_device runs in the lookup's workspace under tfhe_context_reserve_lookup's rule with
+ * max_lookup_bits.  The host forms take raw GGSWs and host arrays, upload, prepare the selectors once, reserve for
+ * themselves and block.
+ *
+ * A call is ceil(d / h) launches, top pass first: the lookup's plan walked in reverse, the top pass takes
+ * d - (ceil(d / h) - 1) h levels and every later one h.  tfhe_context_set_demux_subtree_height(h) fixes h (0: automatic,
+ * the lookup's rule); the bits do not depend on it.  tfhe_debug_demux_plan reports the height and the launches. */
+int tfhe_context_reserve_demux(tfhe_context *ctx, size_t max_trees, size_t max_tree_depth, size_t max_write_bits);
+int tfhe_context_set_demux_subtree_height(tfhe_context *ctx, unsigned height);
+int tfhe_debug_demux_plan(tfhe_context *ctx, size_t trees, size_t depth, unsigned *subtree_height, unsigned *launches);
+int tfhe_demux_tree_device(tfhe_context *ctx, const void *selectors_prepared, size_t queries, size_t depth,
+                           const uint32_t *glwe_in, size_t values, uint32_t *leaves_out, size_t leaf_sets, int accumulate);
+int tfhe_demux_tree(tfhe_context *ctx, const uint32_t *selectors, size_t queries, size_t depth, const uint32_t *glwe_in,
+                    size_t values, uint32_t *leaves_out, size_t leaf_sets, int accumulate);
+int tfhe_table_write_device(tfhe_context *ctx, const void *selectors_prepared, size_t queries, size_t depth,
+                            const uint32_t *values, uint32_t *table_inout, size_t table_sets, size_t tables);
+int tfhe_table_write(tfhe_context *ctx, const uint32_t *selectors, size_t queries, size_t depth, const uint32_t *values,
+                     uint32_t *table_inout, size_t table_sets, size_t tables);
+int tfhe_table_lookup_glwe_device(tfhe_context *ctx, const void *selectors_prepared, size_t queries, size_t depth,
+                                  const uint32_t *leaves, size_t leaf_sets, size_t tables, uint32_t *lwe_out);
+int tfhe_table_lookup_glwe(tfhe_context *ctx, const uint32_t *selectors, size_t queries, size_t depth,
+                           const uint32_t *leaves, size_t leaf_sets, size_t tables, uint32_t *lwe_out);
+
 /* ---- decomposer.rs / glwe.rs / utils.rs --------------------------------------------------- */
 /* SignedDecomposer::decompose: decomposer.rs:42-80.  digits_out [count][levels], MSB first. */
 int tfhe_decompose(tfhe_context *ctx, int which_decomposer, const uint32_t *values, size_t count,

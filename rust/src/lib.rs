@@ -61,6 +61,13 @@ extern "C" {
                       leaf_sets: usize, tables: usize, glwe_out: *mut u32) -> c_int;
     fn tfhe_table_lookup(ctx: *mut TfheContext, selectors: *const u32, queries: usize, depth: usize, table: *const u32,
                          table_sets: usize, tables: usize, lwe_out: *mut u32) -> c_int;
+    // DEMUX tree / encrypted table update (include/tfhe_hip.h)
+    fn tfhe_demux_tree(ctx: *mut TfheContext, selectors: *const u32, queries: usize, depth: usize, glwe_in: *const u32,
+                       values: usize, leaves_out: *mut u32, leaf_sets: usize, accumulate: c_int) -> c_int;
+    fn tfhe_table_write(ctx: *mut TfheContext, selectors: *const u32, queries: usize, depth: usize, values: *const u32,
+                        table_inout: *mut u32, table_sets: usize, tables: usize) -> c_int;
+    fn tfhe_table_lookup_glwe(ctx: *mut TfheContext, selectors: *const u32, queries: usize, depth: usize, leaves: *const u32,
+                              leaf_sets: usize, tables: usize, lwe_out: *mut u32) -> c_int;
     // rotation from a GLWE accumulator and the tree LUT (include/tfhe_hip.h)
     fn tfhe_blind_rotate_glwe_batch(ctx: *mut TfheContext, lwe_in: *const u32, batch: usize, acc_in: *const u32,
                                     acc_count: usize, rotation_offset: usize, glwe_out: *mut u32) -> c_int;
@@ -260,6 +267,60 @@ pub fn table_lookup(bk: &GpuBootstrappingKey, selectors: &Array2<u32>, table: &A
         tfhe_table_lookup(bk.ctx, selectors.as_slice().unwrap().as_ptr(), 1, depth, table.as_slice().unwrap().as_ptr(), 1, 1,
                           out.as_slice_mut().unwrap().as_mut_ptr())
     }, "table_lookup");
+    out
+}
+
+/// Demux over `selectors` (as for cmux_tree) of one GLWE `x` (k+1, N): 2^depth leaves (2^depth, k+1, N), leaf
+/// sum_i b_i 2^i carries x and every other one an encryption of 0 (no reference counterpart).
+pub fn demux_tree(bk: &GpuBootstrappingKey, selectors: &Array2<u32>, x: &Array2<u32>) -> Array3<u32> {
+    let n = 1usize << bk.params.glwe_poly_degree;
+    let k1 = bk.params.glwe_dimension as usize + 1;
+    let depth = selectors.nrows();
+    let ggsw = k1 * bk.params.pbs_decomposer.levels as usize * k1 * n;
+    assert!(depth >= 1 && depth <= 20 && selectors.ncols() == ggsw, "demux_tree: depth rows of (k+1) l (k+1) N words, depth 1..=20");
+    assert!(x.dim() == (k1, n), "demux_tree: one GLWE of (k+1, N)");
+    let mut out = Array3::<u32>::zeros((1usize << depth, k1, n));
+    check(bk.ctx, unsafe {
+        tfhe_demux_tree(bk.ctx, selectors.as_slice().unwrap().as_ptr(), 1, depth, x.as_slice().unwrap().as_ptr(), 1,
+                        out.as_slice_mut().unwrap().as_mut_ptr(), 1, 0)
+    }, "demux_tree");
+    out
+}
+
+/// table[address] += value, obliviously: `table` (max(1, 2^depth / N), k+1, N) holds entry a in coefficient a mod N of
+/// GLWE a / N and is updated in place; `value` (k+1, N) holds the encoded value in coefficient 0 of its phase.  The
+/// write adds: to replace an entry write new - old.
+pub fn table_write(bk: &GpuBootstrappingKey, selectors: &Array2<u32>, value: &Array2<u32>, table: &mut Array3<u32>) {
+    let n = 1usize << bk.params.glwe_poly_degree;
+    let k1 = bk.params.glwe_dimension as usize + 1;
+    let depth = selectors.nrows();
+    let ggsw = k1 * bk.params.pbs_decomposer.levels as usize * k1 * n;
+    let log_n = bk.params.glwe_poly_degree as usize;
+    assert!(depth >= 1 && depth <= log_n + 20 && selectors.ncols() == ggsw,
+            "table_write: depth rows of (k+1) l (k+1) N words, depth 1..=log2 N + 20");
+    let glwes = 1usize << depth.saturating_sub(log_n);
+    assert!(value.dim() == (k1, n) && table.dim() == (glwes, k1, n), "table_write: a value (k+1, N) and max(1, 2^depth / N) table GLWEs");
+    check(bk.ctx, unsafe {
+        tfhe_table_write(bk.ctx, selectors.as_slice().unwrap().as_ptr(), 1, depth, value.as_slice().unwrap().as_ptr(),
+                         table.as_slice_mut().unwrap().as_mut_ptr(), 1, 1)
+    }, "table_write");
+}
+
+/// table[address] of an encrypted table in table_write's layout: an LWE of k N + 1 words under the flattened GLWE key.
+pub fn table_lookup_glwe(bk: &GpuBootstrappingKey, selectors: &Array2<u32>, table: &Array3<u32>) -> Array1<u32> {
+    let n = 1usize << bk.params.glwe_poly_degree;
+    let k = bk.params.glwe_dimension as usize;
+    let depth = selectors.nrows();
+    let ggsw = (k + 1) * bk.params.pbs_decomposer.levels as usize * (k + 1) * n;
+    let log_n = bk.params.glwe_poly_degree as usize;
+    assert!(depth >= 1 && depth <= log_n + 20 && selectors.ncols() == ggsw,
+            "table_lookup_glwe: depth rows of (k+1) l (k+1) N words, depth 1..=log2 N + 20");
+    assert!(table.dim() == (1usize << depth.saturating_sub(log_n), k + 1, n), "table_lookup_glwe: max(1, 2^depth / N) table GLWEs");
+    let mut out = Array1::<u32>::zeros(k * n + 1);
+    check(bk.ctx, unsafe {
+        tfhe_table_lookup_glwe(bk.ctx, selectors.as_slice().unwrap().as_ptr(), 1, depth, table.as_slice().unwrap().as_ptr(), 1, 1,
+                               out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "table_lookup_glwe");
     out
 }
 

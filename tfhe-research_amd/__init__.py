@@ -904,6 +904,148 @@ class Context:
                                             C.c_size_t(sets), C.c_size_t(tables), _hp(res)))
         return res
 
+    # -- DEMUX tree / encrypted table update (include/tfhe_hip.h states the operations) ---------------------------
+    def reserve_demux(self, max_trees: int, max_tree_depth: int = 0, max_write_bits: int = 0):
+        """size the workspace of the device forms for demux_tree calls of up to max_tree_depth levels and table_write
+        calls of up to max_write_bits address bits over up to max_trees = queries * values trees (a maximum: smaller
+        calls fit, under any subtree height); include/tfhe_hip.h states the bytes"""
+        self._check(lib().tfhe_context_reserve_demux(self._h, C.c_size_t(max_trees), C.c_size_t(max_tree_depth),
+                                                     C.c_size_t(max_write_bits)))
+
+    def set_demux_subtree_height(self, height: int):
+        """tree levels one workgroup expands (0: automatic); the bits do not depend on it"""
+        self._check(lib().tfhe_context_set_demux_subtree_height(self._h, C.c_uint(height)))
+
+    def demux_plan(self, trees: int, depth: int) -> dict:
+        """how a DEMUX tree of `depth` levels over `trees` trees goes out (tfhe_debug_demux_plan)"""
+        height, launches = C.c_uint(), C.c_uint()
+        self._check(lib().tfhe_debug_demux_plan(self._h, C.c_size_t(trees), C.c_size_t(depth), C.byref(height),
+                                                C.byref(launches)))
+        return {"subtree_height": height.value, "launches": launches.value}
+
+    def _demux_shapes(self, what, selectors, glwe, out, accumulate, max_depth, tree_levels):
+        """-> (queries, depth, values, sets) after checking selectors [queries][depth][..], glwe [queries][values][k+1][N]
+        and (if given) out [1 or queries][values][2^tree_levels(depth)][k+1][N]"""
+        p = self.params
+        if _is_torch(selectors):
+            if selectors.dim() != 3 or selectors.element_size() != 8 or selectors.shape[2] != self.prepared_ggsw_words() \
+                    or not selectors.is_contiguous() or not selectors.is_cuda:
+                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: prepared selectors [queries][depth]"
+                                                           f"[{self.prepared_ggsw_words()}] (contiguous int64, on the device) expected")
+            for t in (glwe, out):
+                if t is not None and (not _is_torch(t) or t.element_size() != 4 or t.is_floating_point() or not t.is_contiguous()
+                                      or t.device != selectors.device):
+                    raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: inputs and outputs must be contiguous 32-bit integer "
+                                                               f"tensors on the selectors' device")
+        elif selectors.ndim != 5 or tuple(selectors.shape[2:]) != (p.R, p.k + 1, p.N):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: raw selectors [queries][depth][R][k+1][N] expected, got "
+                                                       f"{tuple(selectors.shape)}")
+        queries, depth = int(selectors.shape[0]), int(selectors.shape[1])
+        if depth < 1 or depth > max_depth:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: depth must be in [1, {max_depth}]")
+        if len(glwe.shape) != 4 or int(glwe.shape[0]) != queries or tuple(glwe.shape[2:]) != (p.k + 1, p.N):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: GLWEs [{queries}][values][k+1][N] expected, got {tuple(glwe.shape)}")
+        values = int(glwe.shape[1])
+        if out is None:
+            if accumulate:
+                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: accumulate adds into `out`, which must be given")
+            return queries, depth, values, queries
+        want = (values, 1 << tree_levels(depth), p.k + 1, p.N)
+        if len(out.shape) != 5 or int(out.shape[0]) not in (1, queries) or tuple(out.shape[1:]) != want:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: out [1 or {queries}]{list(want)} expected, got {tuple(out.shape)}")
+        return queries, depth, values, int(out.shape[0])
+
+    def demux_tree(self, selectors, glwe, out=None, accumulate: bool = False):
+        """Demux(C_0 .. C_{d-1}; x): leaf sum_i b_i 2^i carries x, every other leaf an encryption of 0 -- the transpose of
+        cmux_tree under the same selectors.  glwe [queries][values][k+1][N] -> leaves [1 or queries][values][2^depth][k+1][N].
+        accumulate=False stores into per-query sets (`out` optional); accumulate=True adds into `out` as it stands, one
+        set per query or one shared by all (a scatter-add).  numpy: raw selectors, host form, `out` is updated in place
+        and returned.  torch: prepared selectors and device tensors in the workspace of reserve_demux."""
+        if _is_torch(selectors) != _is_torch(glwe) or (out is not None and _is_torch(out) != _is_torch(glwe)):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "demux_tree: selectors, glwe and out must all be numpy or all torch")
+        p = self.params
+        if not _is_torch(selectors):
+            selectors, glwe = _np(selectors), _np(glwe)
+            if out is not None and (not isinstance(out, np.ndarray) or out.dtype != np.uint32 or not out.flags.c_contiguous):
+                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "demux_tree: out must be a C-contiguous uint32 array")
+        queries, depth, values, sets = self._demux_shapes("demux_tree", selectors, glwe, out, accumulate, 20, lambda d: d)
+        shape = (sets, values, 1 << depth, p.k + 1, p.N)
+        if _is_torch(selectors):
+            self._bind_torch()
+            out = self._lookup_out("demux_tree", out, shape, glwe)
+            self._check(lib().tfhe_demux_tree_device(self._h, C.c_void_p(selectors.data_ptr()), C.c_size_t(queries),
+                                                     C.c_size_t(depth), _dp(glwe), C.c_size_t(values), _dp(out),
+                                                     C.c_size_t(sets), C.c_int(int(bool(accumulate)))))
+            return out
+        if out is None:
+            out = np.zeros(shape, dtype=np.uint32)
+        self._check(lib().tfhe_demux_tree(self._h, _hp(selectors), C.c_size_t(queries), C.c_size_t(depth), _hp(glwe),
+                                          C.c_size_t(values), _hp(out), C.c_size_t(sets), C.c_int(int(bool(accumulate)))))
+        return out
+
+    def table_write(self, selectors, values, table):
+        """table[address] += value, obliviously: values [queries][tables][k+1][N] are GLWEs with the encoded value in
+        coefficient 0 of their phase (encrypt_value, or pack_lwe with per_group = 1 on a lookup's / bootstrap's result);
+        table [1 or queries][tables][2^d_hi][k+1][N] holds 2^d_lo = min(2^depth, N) entries per GLWE (the layout of
+        table_lookup's leaves) and is updated in place and returned.  The write ADDS: to replace an entry write
+        new - old, old read with table_lookup_glwe and packed with per_group = 1.  Selectors as for table_lookup."""
+        if _is_torch(selectors) != _is_torch(values) or _is_torch(table) != _is_torch(values):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "table_write: selectors, values and table must all be numpy or all torch")
+        p = self.params
+        if not _is_torch(selectors):
+            selectors, values = _np(selectors), _np(values)
+            if not isinstance(table, np.ndarray) or table.dtype != np.uint32 or not table.flags.c_contiguous:
+                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "table_write: table must be a C-contiguous uint32 array (updated in place)")
+        queries, depth, tables, sets = self._demux_shapes("table_write", selectors, values, table, True, p.glwe_poly_degree + 20,
+                                                          lambda d: d - min(d, p.glwe_poly_degree))
+        if _is_torch(selectors):
+            self._bind_torch()
+            self._check(lib().tfhe_table_write_device(self._h, C.c_void_p(selectors.data_ptr()), C.c_size_t(queries),
+                                                      C.c_size_t(depth), _dp(values), _dp(table), C.c_size_t(sets),
+                                                      C.c_size_t(tables)))
+            return table
+        self._check(lib().tfhe_table_write(self._h, _hp(selectors), C.c_size_t(queries), C.c_size_t(depth), _hp(values),
+                                           _hp(table), C.c_size_t(sets), C.c_size_t(tables)))
+        return table
+
+    def table_lookup_glwe(self, selectors, leaves, out=None):
+        """table_lookup over encrypted leaves [1 or queries][tables][2^d_hi][k+1][N] (what table_write maintains) instead
+        of a clear table: the tree over address bits log2 N and up, the rotation chain, the sample extraction.
+        -> LWE [queries][tables][k N + 1].  torch: in the workspace of reserve_lookup (max_lookup_bits)."""
+        p = self.params
+        if _is_torch(selectors) != _is_torch(leaves):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "table_lookup_glwe: selectors and leaves must both be numpy or both torch")
+        if not _is_torch(selectors):
+            selectors, leaves = _np(selectors), _np(leaves)
+        depth = int(selectors.shape[1]) if len(selectors.shape) > 1 else 0
+        d_hi = depth - min(depth, p.glwe_poly_degree)
+        if len(leaves.shape) != 5 or depth < 1 or depth > p.glwe_poly_degree + 20 or int(leaves.shape[2]) != 1 << d_hi:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"table_lookup_glwe: leaves [1 or queries][tables][2^{d_hi}][k+1][N] "
+                                                       f"expected for {depth} address bits, got {tuple(leaves.shape)}")
+        queries, sets, tables = int(selectors.shape[0]), int(leaves.shape[0]), int(leaves.shape[1])
+        if sets not in (1, queries) or tuple(leaves.shape[3:]) != (p.k + 1, p.N):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"table_lookup_glwe: leaves [1 or {queries}][tables][2^{d_hi}][k+1][N] "
+                                                       f"expected, got {tuple(leaves.shape)}")
+        if _is_torch(selectors):
+            self._bind_torch()
+            if selectors.dim() != 3 or selectors.element_size() != 8 or selectors.shape[2] != self.prepared_ggsw_words() \
+                    or not selectors.is_contiguous() or not selectors.is_cuda or leaves.element_size() != 4 \
+                    or leaves.is_floating_point() or not leaves.is_contiguous() or leaves.device != selectors.device:
+                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "table_lookup_glwe: prepared selectors [queries][depth][words] (int64) "
+                                                           "and contiguous 32-bit leaves on one device expected")
+            out = self._lookup_out("table_lookup_glwe", out, (queries, tables, p.big_n + 1), leaves)
+            self._check(lib().tfhe_table_lookup_glwe_device(self._h, C.c_void_p(selectors.data_ptr()), C.c_size_t(queries),
+                                                            C.c_size_t(depth), _dp(leaves), C.c_size_t(sets),
+                                                            C.c_size_t(tables), _dp(out)))
+            return out
+        if selectors.ndim != 5 or tuple(selectors.shape[2:]) != (p.R, p.k + 1, p.N):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"table_lookup_glwe: raw selectors [queries][depth][R][k+1][N] expected, "
+                                                       f"got {tuple(selectors.shape)}")
+        res = np.zeros((queries, tables, p.big_n + 1), dtype=np.uint32)
+        self._check(lib().tfhe_table_lookup_glwe(self._h, _hp(selectors), C.c_size_t(queries), C.c_size_t(depth), _hp(leaves),
+                                                 C.c_size_t(sets), C.c_size_t(tables), _hp(res)))
+        return res
+
     # -- small ops ------------------------------------------------------------------------------
     def decompose(self, values, which: int = DECOMPOSER_PBS) -> np.ndarray:
         v = _np(values).ravel()
@@ -1198,6 +1340,20 @@ class Context:
         samples = rng.integers(0, 1 << 32, size=shape, dtype=np.uint64).astype(np.uint32)
         samples[:, :, p.k, :] = self._noise(rng, p.glwe_std_dev, (shape[0], p.R, p.N))
         return self.ggsw_encrypt(glwe_sk, bits, samples).reshape(addr.size, depth, p.R, p.k + 1, p.N)
+
+    def encrypt_value(self, glwe_sk, values, rng=None) -> np.ndarray:
+        """GLWE encryptions under glwe_sk (glwe_std_dev) of encode(value) in coefficient 0, values < 2^log_p
+        -> [count][k+1][N]: what table_write adds at an encrypted address.  Masks and errors come from the OS CSPRNG
+        unless the test hook `rng=` is given (see generate_keys)."""
+        p = self.params
+        rng = rng if rng is not None else SystemRng()
+        msg = np.asarray(values, dtype=np.uint32).reshape(-1)
+        if msg.size and int(msg.max()) >> p.log_p:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "encrypt_value: values must be below 2^log_p")
+        samples = rng.integers(0, 1 << 32, size=(msg.size, p.k + 1, p.N), dtype=np.uint64).astype(np.uint32)
+        samples[:, p.k, :] = self._noise(rng, p.glwe_std_dev, (msg.size, p.N))
+        samples[:, p.k, 0] += msg << np.uint32(32 - p.log_p - p.padding_bits)
+        return self.glwe_encrypt_zero(glwe_sk, samples)
 
     def encrypt_test_vector(self, glwe_sk, lut, rng=None) -> np.ndarray:
         """GLWE encryption under glwe_sk (glwe_std_dev) of the ENCODED construct_test_from_lut(lut), lut of 2^log_p

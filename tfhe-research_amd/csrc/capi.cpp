@@ -597,7 +597,8 @@ void tfhe_context_destroy(tfhe_context* ctx) {
   void* ptrs[] = {ctx->d_queue,  ctx->d_tw,     ctx->d_bsk,    ctx->d_ksk,    ctx->d_lwe_in, ctx->d_lwe_in2,
                   ctx->d_lwe_big, ctx->d_lwe_out, ctx->d_lwe_ks, ctx->d_glwe_a, ctx->d_glwe_b, ctx->d_glwe_c,
                   ctx->d_tv,     ctx->d_misc,   ctx->d_ggsw_tmp, ctx->d_ggsw_raw,
-                  ctx->d_key_tmp, ctx->d_pksk, ctx->d_pack_cols, ctx->d_lookup_ws, ctx->d_tree_ws};
+                  ctx->d_key_tmp, ctx->d_pksk, ctx->d_pack_cols, ctx->d_lookup_ws, ctx->d_tree_ws,
+                  ctx->d_demux_ws};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& g : ctx->gate_tvs)
@@ -1278,6 +1279,204 @@ int tfhe_table_lookup(tfhe_context* ctx, const uint32_t* selectors, size_t queri
   TFHE_TRY(check_ctx(ctx));
   TFHE_TRY(check_lookup_args(ctx, selectors, table, lwe_out, queries, depth, ctx->pbs.log_n + kMaxTreeDepth, table_sets, tables));
   return lookup_host(ctx, selectors, queries, depth, table, table_sets, tables, true, lwe_out);
+}
+
+// ---------------------------------------------------------------------------------- DEMUX tree / table update
+// include/tfhe_hip.h states the operations, pbs_wave.h::demux_tree_team the walk; the plan is the lookup's walked in
+// reverse (kernels.hip::lookup_plan_for): the top pass takes what ceil(d / h) - 1 passes of h levels leave over.
+namespace {
+
+int demux_plan_of(tfhe_context* ctx, size_t trees, size_t depth, launch::LookupPlanInfo* plan) {
+  hipError_t e = launch::demux_plan(ctx->field, ctx->pbs, trees, (u32)depth, ctx->demux_height, plan);
+  if (e == hipErrorInvalidValue)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "trees * 2^(depth - subtree height) exceeds the 2^31 - 1 teams of one launch");
+  if (e != hipSuccess) return hip_fail(ctx, e, "demux plan");
+  return TFHE_OK;
+}
+
+int grow_demux_workspace(tfhe_context* ctx, size_t words) {
+  if (words <= ctx->demux_ws_words) return TFHE_OK;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return ensure(ctx, &ctx->d_demux_ws, &ctx->demux_ws_words, words);
+}
+
+bool overlap(const void* a, size_t a_words, const void* b, size_t b_words) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + b_words * sizeof(u32) && b0 < a0 + a_words * sizeof(u32);
+}
+
+// `rot_steps` rotation steps with selectors [0, rot_steps) of every query's `address_bits` selectors on roots
+// [queries][values][k+1][N], then `tree_depth` tree levels with selectors [rot_steps, rot_steps + tree_depth); the
+// leaves are stored to / added into leaves [sets][values][2^tree_depth][k+1][N]
+int run_demux(tfhe_context* ctx, const void* selectors, size_t queries, size_t address_bits, size_t rot_steps, size_t tree_depth,
+              const u32* roots, size_t values, u32* leaves, bool shared, bool accumulate) {
+  const size_t trees = queries * values;
+  const size_t glwe = glwe_words(ctx);
+  if (overlap(roots, trees * glwe, leaves, ((shared ? values : trees) << tree_depth) * glwe))
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "the output overlaps the input");
+  launch::LookupPlanInfo plan{};
+  TFHE_TRY(demux_plan_of(ctx, trees, tree_depth, &plan));
+  if (plan.workspace_words > ctx->demux_ws_words)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "the call needs " + std::to_string(plan.workspace_words * sizeof(u32)) + " bytes of demux workspace, " +
+                    std::to_string(ctx->demux_ws_words * sizeof(u32)) + " are reserved (tfhe_context_reserve_demux)");
+  const size_t ggsw8 = prepared_ggsw_words(ctx);
+  const unsigned char* sel = static_cast<const unsigned char*>(selectors);
+  // workspace: [nodes of the passes launches - 2, launches - 4, ..][nodes of the passes launches - 3, ..][parked nodes]
+  const size_t h = plan.height;
+  const size_t res_a = plan.launches >= 2 ? (trees << (tree_depth - h)) * glwe : 0;
+  const size_t res_b = plan.launches >= 3 ? (trees << (tree_depth - 2 * h)) * glwe : 0;
+  u32* results[2] = {ctx->d_demux_ws, ctx->d_demux_ws + res_a};
+  u32* pending = ctx->d_demux_ws + res_a + res_b;
+  size_t done = 0;
+  const u32* from = roots;
+  for (u32 i = 0; i < plan.launches; ++i) {
+    const size_t here = i == 0 ? tree_depth - (plan.launches - 1) * h : h;  // 0 only for tree_depth == 0
+    const bool last = i + 1 == plan.launches;
+    DemuxTreePass pass{};
+    pass.selectors = sel + (rot_steps + tree_depth - done - here) * ggsw8 * 8;
+    pass.rot_selectors = sel;
+    pass.query_stride = address_bits * ggsw8;
+    pass.values = (u32)values;
+    pass.height = (u32)here;
+    pass.log_subtrees = (u32)done;
+    pass.rot_steps = i == 0 ? (u32)rot_steps : 0u;
+    pass.roots = from;
+    pass.pending = pending;
+    u32* to = last ? leaves : results[(plan.launches - 2 - i) & 1];
+    pass.leaves = to;
+    pass.set_stride = ((size_t)1 << (done + here)) * glwe;
+    pass.shared_sets = last && shared;
+    pass.accumulate = last && accumulate;
+    HIP_TRY(ctx, launch::demux_tree_pass(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, pass, trees << done));
+    from = to;
+    done += here;
+  }
+  return TFHE_OK;
+}
+
+int check_demux_args(tfhe_context* ctx, const void* selectors, const void* in, const void* out, size_t queries, size_t depth,
+                     size_t max_depth, size_t sets, size_t values, bool accumulate) {
+  TFHE_TRY(check_lookup_args(ctx, selectors, in, out, queries, depth, max_depth, sets, values));
+  if (!accumulate && sets != queries)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "accumulate = 0 stores: every query needs its own leaf set (leaf_sets == queries)");
+  return TFHE_OK;
+}
+
+}  // namespace
+
+int tfhe_context_reserve_demux(tfhe_context* ctx, size_t max_trees, size_t max_tree_depth, size_t max_write_bits) {
+  TFHE_TRY(check_ctx(ctx));
+  if (max_trees == 0 || max_trees > kMaxBatch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "max_trees must be in [1, 2^31)");
+  if (max_tree_depth > kMaxTreeDepth) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "max_tree_depth must be in [0, 20]");
+  if (max_write_bits > ctx->pbs.log_n + kMaxTreeDepth)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "max_write_bits must be in [0, log2 N + 20]");
+  if (max_tree_depth == 0 && max_write_bits == 0)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "max_tree_depth and max_write_bits are both 0: nothing to reserve for");
+  // a write of D address bits runs a tree of D - log2 N levels (none up to log2 N bits); the need is the lookup's
+  const size_t write_depth = max_write_bits > ctx->pbs.log_n ? max_write_bits - ctx->pbs.log_n : 0;
+  return grow_demux_workspace(ctx, lookup_workspace_need(ctx, max_trees, std::max(max_tree_depth, write_depth)));
+}
+
+int tfhe_context_set_demux_subtree_height(tfhe_context* ctx, unsigned height) {
+  if (!ctx) return TFHE_ERR_INVALID_ARGUMENT;
+  if (height > kMaxTreeDepth) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "subtree height must be in [0, 20] (0: automatic)");
+  ctx->demux_height = height;
+  return TFHE_OK;
+}
+
+int tfhe_debug_demux_plan(tfhe_context* ctx, size_t trees, size_t depth, unsigned* subtree_height, unsigned* launches) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {subtree_height, launches}, 1, "null pointer"));
+  if (trees == 0 || trees > kMaxBatch || depth > kMaxTreeDepth)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "trees must be in [1, 2^31), depth in [0, 20]");
+  launch::LookupPlanInfo plan{};
+  TFHE_TRY(demux_plan_of(ctx, trees, depth, &plan));
+  *subtree_height = plan.height;
+  *launches = plan.launches;
+  return TFHE_OK;
+}
+
+int tfhe_demux_tree_device(tfhe_context* ctx, const void* selectors_prepared, size_t queries, size_t depth,
+                           const uint32_t* glwe_in, size_t values, uint32_t* leaves_out, size_t leaf_sets, int accumulate) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_demux_args(ctx, selectors_prepared, glwe_in, leaves_out, queries, depth, kMaxTreeDepth, leaf_sets, values,
+                            accumulate != 0));
+  return run_demux(ctx, selectors_prepared, queries, depth, 0, depth, glwe_in, values, leaves_out, leaf_sets == 1 && queries > 1,
+                   accumulate != 0);
+}
+
+int tfhe_table_write_device(tfhe_context* ctx, const void* selectors_prepared, size_t queries, size_t depth,
+                            const uint32_t* values, uint32_t* table_inout, size_t table_sets, size_t tables) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_demux_args(ctx, selectors_prepared, values, table_inout, queries, depth, ctx->pbs.log_n + kMaxTreeDepth,
+                            table_sets, tables, true));
+  const size_t d_lo = std::min(depth, (size_t)ctx->pbs.log_n);
+  return run_demux(ctx, selectors_prepared, queries, depth, d_lo, depth - d_lo, values, tables, table_inout,
+                   table_sets == 1 && queries > 1, true);
+}
+
+int tfhe_table_lookup_glwe_device(tfhe_context* ctx, const void* selectors_prepared, size_t queries, size_t depth,
+                                  const uint32_t* leaves, size_t leaf_sets, size_t tables, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_lookup_args(ctx, selectors_prepared, leaves, lwe_out, queries, depth, ctx->pbs.log_n + kMaxTreeDepth, leaf_sets, tables));
+  const size_t d_lo = std::min(depth, (size_t)ctx->pbs.log_n);
+  return run_lookup(ctx, selectors_prepared, queries, depth, d_lo, depth - d_lo, LookupLeaves{leaves, nullptr, leaf_sets == 1 && queries > 1},
+                    tables, nullptr, lwe_out);
+}
+
+// host forms: selectors [queries][depth][R][k+1][N] raw; everything uploaded, the selectors prepared once
+static int demux_host(tfhe_context* ctx, const uint32_t* selectors, size_t queries, size_t depth, const uint32_t* in, size_t values,
+                      uint32_t* out, size_t sets, bool is_write, bool accumulate) {
+  const size_t d_lo = is_write ? std::min(depth, (size_t)ctx->pbs.log_n) : 0;
+  const size_t trees = queries * values, glwe = glwe_words(ctx);
+  const size_t out_words = ((sets * values) << (depth - d_lo)) * glwe;
+  if (overlap(in, trees * glwe, out, out_words)) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "the output overlaps the input");
+  launch::LookupPlanInfo plan{};
+  TFHE_TRY(demux_plan_of(ctx, trees, depth - d_lo, &plan));
+  TFHE_TRY(grow_demux_workspace(ctx, std::max<size_t>(plan.workspace_words, 1)));
+  enum { kIn, kOut };
+  Staging s(ctx, {trees * glwe, out_words});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(upload_and_prepare_ggsw(ctx, selectors, queries * depth));
+  TFHE_TRY(s.upload(kIn, in));
+  if (accumulate) TFHE_TRY(s.upload(kOut, out));
+  TFHE_TRY(is_write ? tfhe_table_write_device(ctx, ctx->d_ggsw_tmp, queries, depth, s[kIn], s[kOut], sets, values)
+                    : tfhe_demux_tree_device(ctx, ctx->d_ggsw_tmp, queries, depth, s[kIn], values, s[kOut], sets, accumulate));
+  return s.download_and_wait(kOut, out);
+}
+
+int tfhe_demux_tree(tfhe_context* ctx, const uint32_t* selectors, size_t queries, size_t depth, const uint32_t* glwe_in,
+                    size_t values, uint32_t* leaves_out, size_t leaf_sets, int accumulate) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_demux_args(ctx, selectors, glwe_in, leaves_out, queries, depth, kMaxTreeDepth, leaf_sets, values, accumulate != 0));
+  return demux_host(ctx, selectors, queries, depth, glwe_in, values, leaves_out, leaf_sets, false, accumulate != 0);
+}
+
+int tfhe_table_write(tfhe_context* ctx, const uint32_t* selectors, size_t queries, size_t depth, const uint32_t* values,
+                     uint32_t* table_inout, size_t table_sets, size_t tables) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_demux_args(ctx, selectors, values, table_inout, queries, depth, ctx->pbs.log_n + kMaxTreeDepth, table_sets,
+                            tables, true));
+  return demux_host(ctx, selectors, queries, depth, values, tables, table_inout, table_sets, true, true);
+}
+
+int tfhe_table_lookup_glwe(tfhe_context* ctx, const uint32_t* selectors, size_t queries, size_t depth, const uint32_t* leaves,
+                           size_t leaf_sets, size_t tables, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_lookup_args(ctx, selectors, leaves, lwe_out, queries, depth, ctx->pbs.log_n + kMaxTreeDepth, leaf_sets, tables));
+  const size_t d_hi = depth - std::min(depth, (size_t)ctx->pbs.log_n);
+  const size_t trees = queries * tables;
+  launch::LookupPlanInfo plan{};
+  TFHE_TRY(lookup_plan_of(ctx, trees, d_hi, &plan));
+  TFHE_TRY(grow_lookup_workspace(ctx, std::max<size_t>(plan.workspace_words, 1)));
+  enum { kIn, kOut };
+  Staging s(ctx, {((leaf_sets * tables) << d_hi) * glwe_words(ctx), trees * big_lwe_words(ctx)});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(upload_and_prepare_ggsw(ctx, selectors, queries * depth));
+  TFHE_TRY(s.upload(kIn, leaves));
+  TFHE_TRY(tfhe_table_lookup_glwe_device(ctx, ctx->d_ggsw_tmp, queries, depth, s[kIn], leaf_sets, tables, s[kOut]));
+  return s.download_and_wait(kOut, lwe_out);
 }
 
 // ---------------------------------------------------------------------------------- small ops

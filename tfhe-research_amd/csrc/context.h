@@ -42,6 +42,10 @@ struct tfhe_context {
   u32* d_lookup_ws = nullptr;
   size_t lookup_ws_words = 0;
   unsigned lookup_height = 0; // subtree height a team reduces (tfhe_context_set_lookup_subtree_height); 0: automatic
+  // DEMUX tree / table update (tfhe_context_reserve_demux): the passes' nodes and the teams' parked nodes
+  u32* d_demux_ws = nullptr;
+  size_t demux_ws_words = 0;
+  unsigned demux_height = 0;  // subtree height a team expands (tfhe_context_set_demux_subtree_height); 0: automatic
   // tree LUT (tfhe_context_reserve_tree_lut): per-rotation inputs, segment state, the levels' results and packed GLWEs
   u32* d_tree_ws = nullptr;
   size_t tree_ws_words = 0;

@@ -718,6 +718,18 @@ cmux_tree_kernel(PbsParams P, const typename F::elem* __restrict__ tw, CmuxTreeP
                                    blockIdx.x & ((1u << pass.log_subtrees) - 1u));
 }
 
+// ------------------------------------------------------------------------------ DEMUX tree / encrypted table update
+// pbs_wave.h::demux_tree_team states the operations.  One team per (tree, root) of a pass, as in cmux_tree_kernel; the
+// team's LDS is that kernel's (one product at a time, x in c.acc(), the parked nodes in the team's slots of the workspace).
+template <class F, int LOGN, int K>
+__global__ void __launch_bounds__((TeamCfg<F, LOGN, K, 1>::kThreads), (TeamCfg<F, LOGN, K, 1>::kMinWaves))
+demux_tree_kernel(PbsParams P, const typename F::elem* __restrict__ tw, DemuxTreePass pass) {
+  using C = TeamCfg<F, LOGN, K, 1>;
+  auto w = make_wave<F, LOGN, K, 1>(g_smem, tw);
+  demux_tree_team<F, LOGN, K, C::G>(w, P, pass, (size_t)(blockIdx.x >> pass.log_subtrees),
+                                    blockIdx.x & ((1u << pass.log_subtrees) - 1u));
+}
+
 // dst row `row` = GLWE [k+1][N]: coefficient 0 of the body += factor[row] (the packing key's s_i g_l)
 __global__ void packing_add_gadget_kernel(u32* pksk, size_t rows, u32 k, u32 log_n, const u32* __restrict__ factor) {
   for (size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x; row < rows; row += (size_t)gridDim.x * blockDim.x)
@@ -1501,6 +1513,16 @@ struct TreeKernel {
   static constexpr size_t kLds = C::kLds;
   static auto get() { return cmux_tree_kernel<F, LOGN, K>; }
 };
+// The DEMUX tree goes out by the same plan walked in reverse (capi.cpp::run_demux): the top pass takes the rest, every
+// later one `height` levels, so pass i of one is pass (launches - 1 - i) of the other -- the same teams, products and
+// workspace -- with the residency of its own kernel.
+template <class F, int LOGN, int K>
+struct DemuxKernel {
+  using C = TeamCfg<F, LOGN, K, 1>;
+  static constexpr int kThreads = C::kThreads;
+  static constexpr size_t kLds = C::kLds;
+  static auto get() { return demux_tree_kernel<F, LOGN, K>; }
+};
 inline double lookup_cost(size_t trees, u32 depth, u32 h, size_t resident) {
   double cost = 0;
   for (u32 done = 0; done < depth;) {
@@ -1536,13 +1558,13 @@ inline bool lookup_plan_for(size_t trees, u32 depth, u32 forced_height, size_t r
   return true;
 }
 
-template <class F, int LOGN, int K>
+template <class F, int LOGN, int K, template <class, int, int> class Kernel = TreeKernel>
 hipError_t plan_lookup(size_t trees, u32 depth, u32 forced_height, launch::LookupPlanInfo* out) {
   if constexpr (!field_shape_ok<F, LOGN>()) {
     return hipErrorInvalidValue;
   } else {
     unsigned resident = 0;
-    hipError_t e = resident_teams<TreeKernel<F, LOGN, K>>(&resident);
+    hipError_t e = resident_teams<Kernel<F, LOGN, K>>(&resident);
     if (e != hipSuccess) return e;
     LookupPlan plan{};
     if (!lookup_plan_for(trees, depth, forced_height, resident, (size_t)(K + 1) << LOGN, &plan)) return hipErrorInvalidValue;
@@ -1563,6 +1585,24 @@ hipError_t launch_cmux_tree_pass(hipStream_t s, const PbsParams& P, const void* 
     if (teams == 0 || teams > kMaxGrid) return hipErrorInvalidValue;
     auto tw = static_cast<const typename F::elem*>(tw_v);
     auto kern = cmux_tree_kernel<F, LOGN, K>;
+    static std::atomic<unsigned long long> lds_done{0};
+    hipError_t e = allow_lds(kern, C::kLds, lds_done);
+    if (e != hipSuccess) return e;
+    pass.query_stride /= sizeof(typename F::elem) / 8;
+    hipLaunchKernelGGL(kern, dim3((unsigned)teams), dim3(C::kThreads), C::kLds, s, P, tw, pass);
+    return hipGetLastError();
+  }
+}
+
+template <class F, int LOGN, int K>
+hipError_t launch_demux_tree_pass(hipStream_t s, const PbsParams& P, const void* tw_v, DemuxTreePass pass, size_t teams) {
+  if constexpr (!field_shape_ok<F, LOGN>()) {
+    return hipErrorInvalidValue;
+  } else {
+    using C = TeamCfg<F, LOGN, K, 1>;
+    if (teams == 0 || teams > kMaxGrid) return hipErrorInvalidValue;
+    auto tw = static_cast<const typename F::elem*>(tw_v);
+    auto kern = demux_tree_kernel<F, LOGN, K>;
     static std::atomic<unsigned long long> lds_done{0};
     hipError_t e = allow_lds(kern, C::kLds, lds_done);
     if (e != hipSuccess) return e;
@@ -1822,6 +1862,14 @@ hipError_t lookup_plan(int field, const PbsParams& P, size_t trees, u32 depth, u
 
 hipError_t cmux_tree_pass(hipStream_t s, int field, const PbsParams& P, const void* tw, const CmuxTreePass& pass, size_t teams) {
   TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (launch_cmux_tree_pass<FF, LL, KK>(s, P, tw, pass, teams))));
+}
+
+hipError_t demux_plan(int field, const PbsParams& P, size_t trees, u32 depth, u32 forced_height, LookupPlanInfo* out) {
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (plan_lookup<FF, LL, KK, DemuxKernel>(trees, depth, forced_height, out))));
+}
+
+hipError_t demux_tree_pass(hipStream_t s, int field, const PbsParams& P, const void* tw, const DemuxTreePass& pass, size_t teams) {
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (launch_demux_tree_pass<FF, LL, KK>(s, P, tw, pass, teams))));
 }
 
 hipError_t key_switch(hipStream_t s, const KsParams& K, u32 big_n, u32 n, const u32* lwe_in,

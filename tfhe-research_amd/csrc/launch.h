@@ -122,6 +122,13 @@ bool lookup_workspace_glwes(size_t trees, u32 depth, u32 height, size_t* glwes);
 // one pass: `teams` = trees << pass.log_subtrees workgroups.  pass.query_stride in 8-byte words here.
 hipError_t cmux_tree_pass(hipStream_t s, int field, const PbsParams& P, const void* tw, const CmuxTreePass& pass, size_t teams);
 
+// ---- DEMUX tree / encrypted table update (pbs_wave.h::demux_tree_team): the lookup's plan walked in reverse -- the top
+// pass takes depth - (launches - 1) height levels, every later one `height` -- with the same workspace
+// (lookup_workspace_glwes) and the residency of the DEMUX kernel
+hipError_t demux_plan(int field, const PbsParams& P, size_t trees, u32 depth, u32 forced_height, LookupPlanInfo* out);
+// one pass: `teams` = trees << pass.log_subtrees workgroups.  pass.query_stride in 8-byte words here.
+hipError_t demux_tree_pass(hipStream_t s, int field, const PbsParams& P, const void* tw, const DemuxTreePass& pass, size_t teams);
+
 // elementwise helpers.  first_shift = bit of the lowest kept limb (PbsParams::first_shift)
 hipError_t decompose_words(hipStream_t s, u32 log_base, u32 levels, u32 first_shift, const u32* values,
                            size_t count, u32* digits /* [count][levels] */);

@@ -1319,6 +1319,135 @@ TFHE_HD void cmux_tree_team(const Ctx& c, const PbsParams& P, const CmuxTreePass
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Encrypted table update (no reference counterpart): the transpose of the tree above.  A DEMUX tree pushes ONE GLWE
+// down the selectors; all arithmetic mod 2^32:
+//   Demux(C_0 .. C_{d-1}; x):  M(d)_0 = x;  for i = d-1 down to 0, j < 2^(d-1-i):
+//     M(i)_{2j+1} = external_product(C_i, M(i+1)_j),  M(i)_{2j} = M(i+1)_j - M(i)_{2j+1};  leaves M(0)_0 .. M(0)_{2^d - 1}
+//     -- with C_i encrypting bit b_i leaf sum_i b_i 2^i carries x and every other leaf an encryption of 0 (the leaf that
+//     Tree selects under the same selectors); the leaves add up to x word for word whatever the GGSWs are
+//   Write(C_0 .. C_{D-1}; V; table), d_lo = min(D, log2 N), d_hi = D - d_lo:
+//     x = V;  for i = 0 .. d_lo - 1 in this order: x = cmux(C_i, x, X^{2^i} x);  table[h] += Demux(C_{d_lo} ..; x)_h
+//
+// demux_tree_team: ONE team expands a subtree of 2^height leaves top-down and depth-first, after `rot_steps` rotation
+// steps on its root.  x = the node at hand lives in c.acc().  At level t (selector t - 1, t = height .. 1):
+// v = ext(C_{t-1}, x); above the last level the left child x - v is parked in pending[t - 1] and the walk goes on with
+// the right child v; at the last level both children leave as leaves 2 node + 1 and 2 node.  Then the deepest parked
+// node comes back: the left sibling at level ctz(node) + 1, node (node >> ctz) - 1 of that level -- until node 0 has
+// left.  That is 2^height - 1 products, the same for every wave (node and t are team-uniform), through ONE call site:
+//   rotation i  src(j) = (X^{2^i} acc)[j] - acc[j]     out(j, v): acc[j] += v
+//   inner node  src(j) = acc[j]                        out(j, v): pending[t-1][j] = acc[j] - v, acc[j] = v
+//   last level  src(j) = acc[j]                        out(j, v): leaf_{2 node + 1}[j] (+)= v, leaf_{2 node}[j] (+)= acc[j] - v
+// As in cmux_tree_team every word of acc and of a pending slot is read and written by the lane that owns index j, so
+// the walk has no barrier or fence of its own; the rotations start behind poly_sync.  Leaves leave as plain stores or
+// (accumulate) as wrapping u32 atomic adds, 64 consecutive words per wave instruction: wrapping addition commutes, so
+// the words do not depend on the order in which teams -- of one launch or of several queries -- arrive.
+//
+// DemuxTreePass: one launch (kernels.hip::demux_tree_kernel).  Team (tree, subtree) of a pass expands root `subtree`
+// of tree = query * values + value with selectors [0, height) of the pass into leaves [subtree 2^height, (subtree + 1)
+// 2^height) of the tree; a tree deeper than the pass went through the passes above first, whose leaves are this one's
+// roots.  Strides count u32 words, selector strides field elements.
+// ---------------------------------------------------------------------------------------------
+TFHE_HD void global_add(u32* p, u32 v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  atomicAdd(p, v);
+#else
+  __atomic_fetch_add(p, v, __ATOMIC_RELAXED);
+#endif
+}
+
+struct DemuxTreePass {
+  const void* selectors;      // prepared GGSWs: selector t of query q at selectors + q * query_stride + t * ggsw_words
+  const void* rot_selectors;  // the same for rotation step i (used if rot_steps > 0)
+  size_t query_stride;        // elements from one query's selectors to the next one's
+  u32 values;                 // trees per query
+  u32 height;                 // tree levels of this pass; 0: the root itself leaves as leaf `subtree` (a write of at most log2 N bits)
+  u32 log_subtrees;           // the pass expands 2^log_subtrees roots per tree
+  u32 shared_sets;            // 1: tree (q, value) writes leaf set `value`; 0: set q * values + value
+  u32 rot_steps;              // rotation steps before the tree (the first pass of a write: min(D, log2 N))
+  u32 accumulate;             // 1: leaves are added to what is there; 0: stored
+  const u32* roots;           // [tree][2^log_subtrees][K+1][N]
+  u32* pending;               // [team][height - 1][K+1][N], team = tree * 2^log_subtrees + subtree (unused if height < 2)
+  u32* leaves;                // leaf g of a set at leaves + set * set_stride + g * (K+1) N
+  size_t set_stride;
+};
+
+template <class F, int LOGN, int K, int G, class Ctx>
+TFHE_HD void demux_tree_team(const Ctx& c, const PbsParams& P, const DemuxTreePass& A, size_t tree, u32 subtree) {
+  typedef typename F::elem elem;
+  constexpr int E = NttShape<LOGN, G>::kE;
+  constexpr int T = NttShape<LOGN, G>::kThreads;
+  constexpr int N = 1 << LOGN;
+  constexpr size_t GLWE = (size_t)(K + 1) * N;
+  const int lane = c.tid();
+  const int me = c.group();
+  u32* acc = c.acc();
+  const size_t ggsw_words = (size_t)(K + 1) * P.levels * (K + 1) * F::kParts * (N >> F::kLogShrink);  // elements
+  const size_t query = tree / A.values;
+  const size_t set = A.shared_sets ? tree % A.values : tree;
+  const elem* sel = static_cast<const elem*>(A.selectors) + query * A.query_stride;
+  const elem* rot = static_cast<const elem*>(A.rot_selectors) + query * A.query_stride;
+  const size_t team = (tree << A.log_subtrees) + subtree;
+  // my polynomial's pending slots, the slot of level t at + (t - 1) GLWE (a pass of one level has none)
+  u32* pending = A.height > 1 ? A.pending + team * (A.height - 1) * GLWE + (size_t)me * N : nullptr;
+  // my polynomial of my first leaf
+  u32* leaves = A.leaves + set * A.set_stride + ((size_t)subtree << A.height) * GLWE + (size_t)me * N;
+  const bool adding = A.accumulate != 0;
+  auto emit = [&](u32* dst, u32 value) {
+    if (adding) global_add(dst, value);
+    else *dst = value;
+  };
+
+  const u32* root = A.roots + team * GLWE + (size_t)me * N;
+#pragma unroll
+  for (int r = 0; r < E; ++r) acc[r * T + lane] = root[r * T + lane];
+  const u32 tree_products = A.height ? (1u << A.height) - 1u : 0u;
+  const u32 products = A.rot_steps + tree_products;
+  if (A.rot_steps) c.poly_sync();  // the rotation reads words other lanes wrote
+  u32 t = A.height, node = 0;  // the next tree product: node `node` of level t
+#pragma unroll 1
+  for (u32 step = 0; step < products; ++step) {
+    const bool rotating = step < A.rot_steps;
+    const bool last_level = !rotating && t == 1;
+    const u32 m = c.uniform(1u << (rotating ? step : 0u));  // X^{2^i}
+    u32* slot = (rotating || last_level) ? nullptr : pending + (size_t)(t - 2) * GLWE;
+    u32* left = last_level ? leaves + (size_t)(2 * node) * GLWE : nullptr;
+    auto src = [&](int j) -> u32 {
+      if (rotating) return monomial_coeff<LOGN>(acc, j, m) - acc[j];
+      return acc[j];
+    };
+    auto out = [&](int j, u32 value) {
+      if (rotating) {
+        c.lds_add(acc + j, value);
+      } else if (last_level) {
+        emit(left + GLWE + j, value);
+        emit(left + j, acc[j] - value);
+      } else {
+        slot[j] = acc[j] - value;
+        acc[j] = value;
+      }
+    };
+    external_product_team<F, LOGN, K, G>(c, P, (rotating ? rot + (size_t)step * ggsw_words : sel + (size_t)(t - 1) * ggsw_words), src, out);
+    if (c.exchange_buffers() != 2) c.poly_sync();
+    if (rotating) continue;
+    if (!last_level) {  // down to the right child
+      node = 2 * node + 1;
+      --t;
+    } else if (node != 0) {  // the deepest parked node: the left sibling of the last right turn
+      const u32 up = (u32)__builtin_ctz(node);
+      node = (node >> up) - 1u;
+      t = up + 1u;
+      const u32* parked = pending + (size_t)(t - 1) * GLWE;
+#pragma unroll
+      for (int r = 0; r < E; ++r) acc[r * T + lane] = parked[r * T + lane];
+    }
+  }
+  if (A.height == 0) {
+#pragma unroll
+    for (int r = 0; r < E; ++r) emit(leaves + r * T + lane, acc[r * T + lane]);
+  }
+}
+
 // Forward NTT of one u32 polynomial of the bootstrapping key into the prepared layout,
 // pre-scaled by N^-1.
 // LAYOUT_E: the shape the key is laid out for (key_layout_e; 0: this transform's own)
