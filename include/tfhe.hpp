@@ -570,6 +570,26 @@ inline LweCiphertext table_lookup(Engine& e, const std::vector<GgswCiphertext>& 
   e.check(tfhe_table_lookup(e.raw(), sel.data(), 1, depth, table.data(), 1, 1, out.data.data()));
   return out;
 }
+// ---- encrypted branching program (tfhe_hip.h states the operations; first device only) ----
+// nodes in topological order, terminals [n_terminals][N] clear message words, outputs: references (terminal t -> t, node
+// i -> n_terminals + i).  selectors[s] encrypts input bit s.  -> one LWE of k N + 1 words per output under the
+// flattened GLWE key
+inline std::vector<LweCiphertext> cmux_program(Engine& e, const std::vector<GgswCiphertext>& selectors,
+                                               const std::vector<tfhe_program_node>& nodes, const std::vector<uint32_t>& terminals,
+                                               const std::vector<uint32_t>& outputs) {
+  const TfheParams& p = e.params();
+  const size_t lwe = p.glwe_dimension * p.degree() + 1;
+  if (terminals.empty() || terminals.size() % p.degree() != 0 || outputs.empty())
+    throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "terminals of N words each and at least one output");
+  const std::vector<uint32_t> sel = flatten_selectors(p, selectors);
+  std::vector<uint32_t> flat(outputs.size() * lwe);
+  e.check(tfhe_cmux_program(e.raw(), sel.data(), 1, selectors.size(), 1, nodes.data(), nodes.size(), terminals.data(),
+                            terminals.size() / p.degree(), outputs.data(), outputs.size(), nullptr, flat.data()));
+  std::vector<LweCiphertext> out;
+  for (size_t i = 0; i < outputs.size(); ++i)
+    out.push_back(LweCiphertext{std::vector<uint32_t>(flat.begin() + i * lwe, flat.begin() + (i + 1) * lwe)});
+  return out;
+}
 // ---- DEMUX tree and encrypted table update (tfhe_hip.h states the operations; first device only) ----
 // Demux(C_0 .. C_{d-1}; x): 2^d leaves, leaf sum_i b_i 2^i carries x and every other one an encryption of 0
 inline std::vector<GlweCiphertext> demux_tree(Engine& e, const std::vector<GgswCiphertext>& selectors, const GlweCiphertext& x) {

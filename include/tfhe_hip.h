@@ -457,6 +457,73 @@ int tfhe_table_lookup_glwe_device(tfhe_context *ctx, const void *selectors_prepa
 int tfhe_table_lookup_glwe(tfhe_context *ctx, const uint32_t *selectors, size_t queries, size_t depth,
                            const uint32_t *leaves, size_t leaf_sets, size_t tables, uint32_t *lwe_out);
 
+/* ---- Encrypted branching programs (no reference counterpart): the lookup's CMUX over a DAG instead of a full tree -----
+ * All arithmetic mod 2^32; ext and cmux as above.  A function of many input bits that has a small ordered binary
+ * decision diagram -- a comparison, an equality, a range check, a carry chain -- costs one product per diagram node
+ * (Chillotti, Gama, Georgieva, Izabachene 2017, section 5) where a table lookup costs 2^D / N.
+ *
+ * A PROGRAM over n_inputs selectors (GGSWs C_0 .. C_{n_inputs-1}, as for the lookup):
+ *   terminals [n_terminals][N] clear message words; terminal t is the trivial GLWE with zero mask and body coefficient
+ *     j = terminals[t][j] << tv_shift (the encoding of the lookup's leaves)
+ *   nodes [n_nodes] of tfhe_program_node.  A reference r names terminal r if r < n_terminals, else node r - n_terminals.
+ *     Node i may only reference terminals and nodes < i (topological order).  Its value is
+ *       V_i = cmux(C_sel, R(lo), X^rot R(hi)),   sel < n_inputs,  rot in [0, 2N) a negacyclic monomial
+ *     -- R(lo) where the selector holds 0, X^rot R(hi) where it holds 1.  A tree node has rot = 0; the lookup's rotation
+ *     step i is lo = hi, rot = 2N - 2^i; the write's is lo = hi, rot = 2^i.
+ *   outputs [n_outputs >= 1] references (a terminal is allowed: a constant function reduces to one)
+ * Results: glwe_out [queries][n_outputs][k+1][N], and / or lwe_out [queries][n_outputs][k N + 1] = sample_extract(., 0)
+ * under the flattened GLWE key -- what tfhe_key_switch_batch_device and tfhe_bootstrap_batch_device take (one of the two
+ * may be NULL).  The program is clear and shared by all queries.  selectors[_prepared] [selector_sets][n_inputs] GGSWs,
+ * selector_sets = queries (query q uses set q) or 1 (all queries share them); the host form takes raw GGSWs
+ * [..][R][k+1][N] and host arrays, the device form prepared ones (tfhe_prepare_ggsw_device).  `nodes` and `outputs` are
+ * HOST arrays in both forms (the program is clear: it is checked and planned on the host); `terminals`, the selectors
+ * and the results are device memory in the device form.
+ *
+ * Noise: a CMUX adds one product's noise to the child it selects and the terminals are noise-free, so an output carries
+ * at most the lookup's per-product variance times the DEPTH of the program (its longest path in products), not its size:
+ *   sigma^2 <= depth * [ (k+1) l N (B^2/12 + 1/6) (sigma_glwe 2^32)^2 + (1 + k N / 2) 2^(2 ignored_bits) / 12 ]
+ * No bootstrapping key is involved (nothing here returns TFHE_ERR_NO_KEY) and no new exactness rule applies: every
+ * product has the (k+1) l rows and the base the context was admitted with.
+ *
+ * tfhe_cmux_program_device runs on the context's stream in the workspace of tfhe_context_reserve_program(max_queries,
+ * max_nodes, max_outputs).  The need is host arithmetic:
+ *   max_queries max_nodes (k+1) N 4 bytes   one GLWE per (query, node): the simple layout, no slot reuse
+ *   + 4 (20 max_nodes + 4 max_outputs) bytes   four program images
+ * and covers every call with at most that many queries, nodes and outputs under any split.  A call beyond it returns
+ * TFHE_ERR_INVALID_ARGUMENT with its need in bytes and enqueues nothing.  The device form never allocates.  The FIRST
+ * call with a given program uploads its image (the nodes ordered by dependency level) into one of the four image slots
+ * of the workspace and synchronises the stream once; later calls with a program that is still resident (the four most
+ * recently used) neither synchronise nor copy and are safe under stream capture.  A first use during a capture is
+ * refused: run the program once before capturing.  An image used during a capture stays resident until the next
+ * growing tfhe_context_reserve_program (which voids such graphs); if all four are held so, a fifth program is refused.
+ * The host form reserves for itself, uploads, prepares the selectors once and blocks.
+ *
+ * Plan.  The host orders the nodes by dependency level (terminals 0, a node one more than its deeper operand).  With
+ * one team per query the whole program is ONE launch: the throughput case.  With few queries the levels go out in
+ * turn, the nodes of a level dealt to up to `parts` teams per query, consecutive levels of one team merged into one
+ * launch; values that cross teams cross a launch boundary.  tfhe_context_set_program_split(parts) fixes parts (1: one
+ * launch; 0: automatic, the cheapest of 1, 2, 4, .. under the lookup's cost model, whose per-launch cost is a guess,
+ * not measured).  The output words do not depend on it.  tfhe_debug_program_plan reports the launches and the most
+ * teams a launch gives one query for a program with one output.
+ *
+ * Refused with TFHE_ERR_INVALID_ARGUMENT and a message in tfhe_last_error: a forward or self reference, sel >=
+ * n_inputs, rot >= 2N, an output reference out of range, n_outputs == 0, n_terminals == 0, selector_sets other than 1
+ * or queries, NULL handles. */
+typedef struct tfhe_program_node {
+  uint32_t sel, lo, hi, rot;
+} tfhe_program_node;
+int tfhe_context_reserve_program(tfhe_context *ctx, size_t max_queries, size_t max_nodes, size_t max_outputs);
+int tfhe_context_set_program_split(tfhe_context *ctx, unsigned parts);
+int tfhe_debug_program_plan(tfhe_context *ctx, size_t queries, const tfhe_program_node *nodes, size_t n_nodes,
+                            size_t n_terminals, unsigned *launches, unsigned *teams_per_query);
+int tfhe_cmux_program_device(tfhe_context *ctx, const void *selectors_prepared, size_t queries, size_t n_inputs,
+                             size_t selector_sets, const tfhe_program_node *nodes, size_t n_nodes, const uint32_t *terminals,
+                             size_t n_terminals, const uint32_t *outputs, size_t n_outputs, uint32_t *glwe_out,
+                             uint32_t *lwe_out);
+int tfhe_cmux_program(tfhe_context *ctx, const uint32_t *selectors, size_t queries, size_t n_inputs, size_t selector_sets,
+                      const tfhe_program_node *nodes, size_t n_nodes, const uint32_t *terminals, size_t n_terminals,
+                      const uint32_t *outputs, size_t n_outputs, uint32_t *glwe_out, uint32_t *lwe_out);
+
 /* ---- decomposer.rs / glwe.rs / utils.rs --------------------------------------------------- */
 /* SignedDecomposer::decompose: decomposer.rs:42-80.  digits_out [count][levels], MSB first. */
 int tfhe_decompose(tfhe_context *ctx, int which_decomposer, const uint32_t *values, size_t count,

@@ -61,6 +61,10 @@ extern "C" {
                       leaf_sets: usize, tables: usize, glwe_out: *mut u32) -> c_int;
     fn tfhe_table_lookup(ctx: *mut TfheContext, selectors: *const u32, queries: usize, depth: usize, table: *const u32,
                          table_sets: usize, tables: usize, lwe_out: *mut u32) -> c_int;
+    // encrypted branching program (include/tfhe_hip.h)
+    fn tfhe_cmux_program(ctx: *mut TfheContext, selectors: *const u32, queries: usize, n_inputs: usize, selector_sets: usize,
+                         nodes: *const ProgramNode, n_nodes: usize, terminals: *const u32, n_terminals: usize,
+                         outputs: *const u32, n_outputs: usize, glwe_out: *mut u32, lwe_out: *mut u32) -> c_int;
     // DEMUX tree / encrypted table update (include/tfhe_hip.h)
     fn tfhe_demux_tree(ctx: *mut TfheContext, selectors: *const u32, queries: usize, depth: usize, glwe_in: *const u32,
                        values: usize, leaves_out: *mut u32, leaf_sets: usize, accumulate: c_int) -> c_int;
@@ -267,6 +271,36 @@ pub fn table_lookup(bk: &GpuBootstrappingKey, selectors: &Array2<u32>, table: &A
         tfhe_table_lookup(bk.ctx, selectors.as_slice().unwrap().as_ptr(), 1, depth, table.as_slice().unwrap().as_ptr(), 1, 1,
                           out.as_slice_mut().unwrap().as_mut_ptr())
     }, "table_lookup");
+    out
+}
+
+/// One node of a branching program: cmux(C_sel, R(lo), X^rot R(hi)); a reference below n_terminals names a terminal,
+/// any other node `reference - n_terminals`, which must come earlier (tfhe_program_node of include/tfhe_hip.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ProgramNode {
+    pub sel: u32,
+    pub lo: u32,
+    pub hi: u32,
+    pub rot: u32,
+}
+
+/// Evaluate a branching program on the input bits GGSW-encrypted in `selectors` (row s = input s, as for cmux_tree):
+/// `terminals` (n_terminals, N) clear message words, `outputs` references.  One LWE of k N + 1 words per output under
+/// the flattened GLWE key (no reference counterpart).
+pub fn cmux_program(bk: &GpuBootstrappingKey, selectors: &Array2<u32>, nodes: &[ProgramNode], terminals: &Array2<u32>,
+                    outputs: &[u32]) -> Array2<u32> {
+    let n = 1usize << bk.params.glwe_poly_degree;
+    let k = bk.params.glwe_dimension as usize;
+    let ggsw = (k + 1) * bk.params.pbs_decomposer.levels as usize * (k + 1) * n;
+    assert!(selectors.ncols() == ggsw, "cmux_program: one row of (k+1) l (k+1) N words per input");
+    assert!(terminals.nrows() >= 1 && terminals.ncols() == n && !outputs.is_empty(), "cmux_program: terminals (n_terminals, N), at least one output");
+    let mut out = Array2::<u32>::zeros((outputs.len(), k * n + 1));
+    check(bk.ctx, unsafe {
+        tfhe_cmux_program(bk.ctx, selectors.as_slice().unwrap().as_ptr(), 1, selectors.nrows(), 1, nodes.as_ptr(), nodes.len(),
+                          terminals.as_slice().unwrap().as_ptr(), terminals.nrows(), outputs.as_ptr(), outputs.len(),
+                          std::ptr::null_mut(), out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "cmux_program");
     out
 }
 

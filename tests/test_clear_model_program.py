@@ -1,0 +1,153 @@
+"""The clear model of the encrypted branching program (tests/clear_model_program.py) and the builder and constructors of
+tfhe-research_amd/branching.py: the lookup as a program, identity I16, the reduced BDD of a truth table, and the
+comparison programs against Python integers.  CPU only; small rings, since the algebra does not depend on N."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import clear_model as cm  # noqa: E402
+import clear_model_lookup as cl  # noqa: E402
+import clear_model_program as cp  # noqa: E402
+
+bp = cp.branching()
+
+# k, log2 N, log_base, levels, aligned: two sets that ignore no bits, (7, 3) in both alignment modes
+CASES = [(1, 5, 8, 4, False), (2, 4, 4, 8, False), (1, 5, 7, 3, True), (1, 5, 7, 3, False)]
+
+
+def words(rng, shape):
+    return rng.integers(0, 1 << 32, size=shape, dtype=np.uint64).astype(np.uint32)
+
+
+def centered(diff, bits=32):
+    """differences mod 2^bits as signed numbers in [-2^(bits-1), 2^(bits-1))"""
+    d = np.asarray(diff).astype(np.int64)
+    return (d + (1 << (bits - 1))) % (1 << bits) - (1 << (bits - 1))
+
+
+def noise_free_selectors(rng, bits, S, lb, levels, aligned=False):
+    k, N = S.shape
+    masks = words(rng, (len(bits), (k + 1) * levels, k, N))
+    return cm.ggsw_noise_free(np.array(bits, dtype=np.uint32), masks, S, lb, levels, aligned)
+
+
+def phase_is_exact(lb, levels, aligned):
+    return cm.ignored_bits(lb, levels) == 0 and (aligned or 32 % lb == 0)
+
+
+@pytest.mark.parametrize("lb,levels,aligned", [(7, 3, False), (7, 3, True), (4, 6, False)])
+@pytest.mark.parametrize("D", ["logn+2", 3])
+def test_the_lookup_as_a_program_is_the_lookup(lb, levels, aligned, D):
+    """lookup(table, D, N) through the program model = lookup_model, word for word, for arbitrary selector words:
+    D = log2 N + 2 (two tree levels, the full rotation chain) and D = 3 (no tree)"""
+    k, logn, log_p = 1, 4, 4
+    N = 1 << logn
+    D = logn + 2 if D == "logn+2" else D
+    rng = np.random.default_rng(lb * 100 + D)
+    sel = words(rng, (D, (k + 1) * levels, k + 1, N))
+    sel[0, 0, 0, :] = cm.edge_words()[:N]
+    table = rng.integers(0, 1 << log_p, size=1 << D).astype(np.uint32)
+    prog = bp.lookup(table, D, N)
+    assert prog.n_nodes == (1 << (D - min(D, logn))) - 1 + min(D, logn) and prog.depth == D
+    nodes, terminals, outputs = prog.arrays()
+    got = cp.program_lwe_model(nodes, terminals, outputs, sel, k, log_p, lb, levels, aligned)
+    assert np.array_equal(got[0], cl.lookup_model(sel, table, k, N, log_p, lb, levels, aligned))
+
+
+@pytest.mark.parametrize("k,logn,lb,levels,aligned", CASES)
+def test_i16_the_output_is_the_terminal_reached_times_the_monomials(k, logn, lb, levels, aligned):
+    """I16 on the program that holds every path, at all 16 inputs, all N coefficients of all three outputs; (7, 3)
+    within the rounding bound of the program's depth.  The literal (7, 3) decomposer is kept in: its gadget tops out at
+    bit 28 = 7 floor(32 / 7), so Rec is round_value only mod 2^28 (I1) and the top four bits of a phase -- where the
+    message sits -- are not carried.  Every later step is linear mod 2^32, hence mod 2^28 too, so I16 and its rounding
+    bound hold for it modulo 2^rec_modulus_bits; the other three cases have rec_modulus_bits = 32."""
+    rng = np.random.default_rng(16 * lb + k)
+    N, log_p = 1 << logn, 4
+    prog = cp.every_path_program(N)
+    nodes, terminals, outputs = prog.arrays()
+    S = rng.integers(0, 2, size=(k, N)).astype(np.uint32)
+    bound = 0 if phase_is_exact(lb, levels, aligned) else cl.rounding_bound(k, N, lb, levels, prog.depth)
+    for x in range(16):
+        bits = bp.bits_of(x, 4)
+        sel = noise_free_selectors(rng, bits, S, lb, levels, aligned)
+        got = cm.glwe_phase(cp.program_model(nodes, terminals, outputs, sel, k, log_p, lb, levels, aligned), S)
+        want = cm.encode(prog.evaluate_clear(bits), log_p)
+        assert int(np.abs(centered(got - want, cm.rec_modulus_bits(lb, aligned))).max()) <= bound, x
+
+
+def test_evaluate_clear_follows_the_edges():
+    N = 8
+    p = bp.BranchingProgram(2, N)
+    t0, t1 = p.terminal([1, 2, 3]), p.terminal(5)
+    n0 = p.node(0, t0, t1, rot=N + 2)   # bit 0: X^{N+2} * 5 = -5 X^2
+    n1 = p.node(1, n0, n0, rot=7)       # bit 1: X^7 on top
+    p.output(n1)
+    assert p.depth == 2 and p.level_widths() == [1, 1]
+    assert p.trace([0, 0]) == [(0, 0)] and p.trace([1, 1]) == [(1, (N + 9) % (2 * N))]
+    assert p.evaluate_clear([0, 0])[0].tolist() == [1, 2, 3, 0, 0, 0, 0, 0]
+    assert p.evaluate_clear([1, 0])[0].tolist() == [0, 0, (1 << 32) - 5, 0, 0, 0, 0, 0]
+    assert p.evaluate_clear([1, 1])[0].tolist() == [0, 5, 0, 0, 0, 0, 0, 0]          # X^{N+9} = X: 5 X
+    assert p.evaluate_clear([0, 1])[0].tolist() == [(1 << 32) - 2, (1 << 32) - 3, 0, 0, 0, 0, 0, 1]
+    with pytest.raises(ValueError):
+        p.node(0, n1 + 1, t0)  # a forward reference
+    with pytest.raises(ValueError):
+        p.node(2, t0, t0)
+    with pytest.raises(ValueError):
+        p.node(0, t0, t0, rot=2 * N)
+
+
+def test_from_truth_table_reproduces_its_table():
+    """D = 8: all 256 inputs; a constant table is a single terminal; a table of one variable is one node"""
+    D, N = 8, 16
+    rng = np.random.default_rng(8)
+    table = rng.integers(0, 4, size=1 << D).astype(np.uint32)
+    prog = bp.from_truth_table(table, D, N)
+    assert prog.n_nodes <= (1 << D) - 1 and prog.depth <= D
+    for a in range(1 << D):
+        assert int(prog.evaluate_clear(bp.bits_of(a, D))[0, 0]) == int(table[a]), a
+    const = bp.from_truth_table(np.full(1 << D, 3, dtype=np.uint32), D, N)
+    assert const.n_nodes == 0 and len(const.terminals) == 1 and const.depth == 0
+    assert const.arrays()[2].tolist() == [0] and int(const.evaluate_clear([0] * D)[0, 0]) == 3
+    bit5 = bp.from_truth_table(np.array([(a >> 5) & 1 for a in range(1 << D)], dtype=np.uint32), D, N)
+    assert bit5.n_nodes == 1 and bit5.nodes[0][0] == 5
+    # merged sub-functions: the parity of 8 bits has 2 nodes per level but the last
+    parity = bp.from_truth_table(np.array([bin(a).count("1") & 1 for a in range(1 << D)], dtype=np.uint32), D, N)
+    assert parity.n_nodes == 2 * D - 1
+
+
+def edge_pairs(width, rng, count):
+    top = (1 << width) - 1
+    pairs = [(0, 0), (top, top), (0, top), (top, 0), (5, 5), (4, 5), (5, 4), (top - 1, top), (top, top - 1), (0, 1), (1, 0),
+             (1 << (width - 1), (1 << (width - 1)) - 1), ((1 << (width - 1)) - 1, 1 << (width - 1))]
+    for _ in range(count):
+        a = int(rng.integers(0, 1 << width))
+        pairs += [(a, int(rng.integers(0, 1 << width))), (a, a), (a, a ^ 1)]
+    return pairs
+
+
+def test_less_than_and_equal_agree_with_integers():
+    """width 32: random pairs and the edge pairs (equal values, values that differ in the lowest bit only, 0, 2^32 - 1)"""
+    width, N = 32, 8
+    lt, eq = bp.less_than(width, N), bp.equal(width, N)
+    assert lt.n_inputs == eq.n_inputs == 64
+    assert lt.n_nodes <= 3 * 64 and eq.n_nodes <= 3 * 64
+    assert lt.depth == 64 and eq.depth == 64
+    for a, b in edge_pairs(width, np.random.default_rng(32), 200):
+        bits = bp.interleave(a, b, width)
+        assert int(lt.evaluate_clear(bits)[0, 0]) == int(a < b), (a, b)
+        assert int(eq.evaluate_clear(bits)[0, 0]) == int(a == b), (a, b)
+        assert not lt.evaluate_clear(bits)[0, 1:].any()
+
+
+def test_arrays_use_the_abi_references():
+    p = cp.every_path_program(16)
+    nodes, terminals, outputs = p.arrays()
+    nt = terminals.shape[0]
+    assert nodes.dtype == terminals.dtype == outputs.dtype == np.uint32 and terminals.shape == (3, 16)
+    for i, (sel, lo, hi, rot) in enumerate(nodes.tolist()):
+        assert lo < nt + i and hi < nt + i and sel < 4 and rot < 32
+    assert outputs.tolist() == [nt + p.n_nodes - 1, nt + 3, 1]
+    assert p.level_widths() == [2, 2, 1, 2, 2, 1, 1] and p.depth == 7

@@ -1046,6 +1046,86 @@ class Context:
                                                  C.c_size_t(sets), C.c_size_t(tables), _hp(res)))
         return res
 
+    # -- encrypted branching programs (include/tfhe_hip.h states the operations; branching.py builds programs) ------
+    def reserve_program(self, max_queries: int, max_nodes: int, max_outputs: int = 1):
+        """size the workspace of the device form of cmux_program: one GLWE per (query, node) and four program images
+        (a maximum: smaller calls fit, under any split); include/tfhe_hip.h states the bytes"""
+        self._check(lib().tfhe_context_reserve_program(self._h, C.c_size_t(max_queries), C.c_size_t(max_nodes),
+                                                       C.c_size_t(max_outputs)))
+
+    def set_program_split(self, parts: int):
+        """teams per query a level of a program is dealt to (1: one launch, 0: automatic); the bits do not depend on it"""
+        self._check(lib().tfhe_context_set_program_split(self._h, C.c_uint(parts)))
+
+    def program_plan(self, program, queries: int) -> dict:
+        """how `program` goes out for `queries` queries (tfhe_debug_program_plan)"""
+        nodes, terminals, _ = program.arrays() if hasattr(program, "arrays") else program
+        nodes = _np(nodes).reshape(-1, 4)
+        launches, teams = C.c_uint(), C.c_uint()
+        self._check(lib().tfhe_debug_program_plan(self._h, C.c_size_t(queries), C.c_void_p(nodes.ctypes.data),
+                                                  C.c_size_t(nodes.shape[0]), C.c_size_t(len(terminals)), C.byref(launches),
+                                                  C.byref(teams)))
+        return {"launches": launches.value, "teams_per_query": teams.value}
+
+    def cmux_program(self, program, selectors, queries: int | None = None, want: str = "lwe", terminals=None, out=None):
+        """Evaluate a branching program (branching.BranchingProgram, or its arrays() triple) on encrypted input bits:
+        selector s of a query is input bit s.  selectors [sets][n_inputs][..], sets = queries, or 1 with `queries`
+        given: all queries share them.  want = "lwe" -> [queries][n_outputs][k N + 1] under the flattened GLWE key
+        (what key_switch and bootstrap take), "glwe" -> [queries][n_outputs][k+1][N], "both" -> (glwe, lwe).
+        numpy: raw selectors [..][R][k+1][N], host form, blocks.  torch: prepared selectors [sets][n_inputs][words]
+        (prepare_ggsw_device) in the workspace of reserve_program; `terminals` may name a device copy of the
+        program's terminals (else they are uploaded on every call, which synchronises) and `out` the result tensor(s)."""
+        p = self.params
+        nodes, host_terminals, outputs = program.arrays() if hasattr(program, "arrays") else program
+        nodes, host_terminals, outputs = _np(nodes).reshape(-1, 4), _np(host_terminals), _np(outputs).reshape(-1)
+        if host_terminals.ndim != 2 or host_terminals.shape[1] != p.N:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"cmux_program: terminals [n_terminals][{p.N}] expected, got "
+                                                       f"{tuple(host_terminals.shape)}")
+        if want not in ("lwe", "glwe", "both"):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, 'cmux_program: want must be "lwe", "glwe" or "both"')
+        on_device = _is_torch(selectors)
+        if on_device:
+            if selectors.dim() != 3 or selectors.element_size() != 8 or selectors.shape[2] != self.prepared_ggsw_words() \
+                    or not selectors.is_contiguous() or not selectors.is_cuda:
+                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"cmux_program: prepared selectors [sets][n_inputs]"
+                                                           f"[{self.prepared_ggsw_words()}] (contiguous int64, on the device) expected")
+        else:
+            selectors = _np(selectors)
+            if selectors.ndim != 5 or tuple(selectors.shape[2:]) != (p.R, p.k + 1, p.N):
+                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"cmux_program: raw selectors [sets][n_inputs][R][k+1][N] expected, "
+                                                           f"got {tuple(selectors.shape)}")
+        sets, n_inputs = int(selectors.shape[0]), int(selectors.shape[1])
+        queries = sets if queries is None else int(queries)
+        n_out = outputs.size
+        shapes = {"glwe": (queries, n_out, p.k + 1, p.N), "lwe": (queries, n_out, p.big_n + 1)}
+        args = (C.c_size_t(queries), C.c_size_t(n_inputs), C.c_size_t(sets), C.c_void_p(nodes.ctypes.data),
+                C.c_size_t(nodes.shape[0]))
+        tail = (C.c_size_t(host_terminals.shape[0]), _hp(outputs), C.c_size_t(n_out))
+        if on_device:
+            import torch
+            self._bind_torch()
+            if terminals is None:
+                terminals = torch.from_numpy(host_terminals.view(np.int32)).to(selectors.device)
+            elif not _is_torch(terminals) or tuple(terminals.shape) != host_terminals.shape or terminals.element_size() != 4 \
+                    or terminals.is_floating_point() or not terminals.is_contiguous() or terminals.device != selectors.device:
+                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"cmux_program: device terminals must be a contiguous 32-bit integer "
+                                                           f"tensor {list(host_terminals.shape)} on {selectors.device}")
+            given = {"lwe": out, "glwe": out}[want] if want != "both" else None
+            outs = {}
+            for which in ("glwe", "lwe"):
+                if want in (which, "both"):
+                    o = out[("glwe", "lwe").index(which)] if want == "both" and out is not None else given
+                    outs[which] = self._lookup_out("cmux_program", o, shapes[which], terminals)
+            self._check(lib().tfhe_cmux_program_device(self._h, C.c_void_p(selectors.data_ptr()), *args, _dp(terminals), *tail,
+                                                       _dp(outs["glwe"]) if "glwe" in outs else None,
+                                                       _dp(outs["lwe"]) if "lwe" in outs else None))
+        else:
+            outs = {w: np.zeros(shapes[w], dtype=np.uint32) for w in ("glwe", "lwe") if want in (w, "both")}
+            self._check(lib().tfhe_cmux_program(self._h, _hp(selectors), *args, _hp(host_terminals), *tail,
+                                                _hp(outs["glwe"]) if "glwe" in outs else None,
+                                                _hp(outs["lwe"]) if "lwe" in outs else None))
+        return (outs["glwe"], outs["lwe"]) if want == "both" else outs[want]
+
     # -- small ops ------------------------------------------------------------------------------
     def decompose(self, values, which: int = DECOMPOSER_PBS) -> np.ndarray:
         v = _np(values).ravel()
@@ -1340,6 +1420,20 @@ class Context:
         samples = rng.integers(0, 1 << 32, size=shape, dtype=np.uint64).astype(np.uint32)
         samples[:, :, p.k, :] = self._noise(rng, p.glwe_std_dev, (shape[0], p.R, p.N))
         return self.ggsw_encrypt(glwe_sk, bits, samples).reshape(addr.size, depth, p.R, p.k + 1, p.N)
+
+    def encrypt_selector_bits(self, glwe_sk, bits, rng=None) -> np.ndarray:
+        """GGSW encryptions under glwe_sk (glwe_std_dev) of bits [queries][n_inputs] (0 or 1) -> raw selectors
+        [queries][n_inputs][R][k+1][N] for cmux_program: encrypt_address without its limit of 63 bits per query.
+        Masks and errors come from the OS CSPRNG unless the test hook `rng=` is given (see generate_keys)."""
+        p = self.params
+        rng = rng if rng is not None else SystemRng()
+        bits = np.asarray(bits)
+        if bits.ndim != 2 or bits.size == 0 or ((bits != 0) & (bits != 1)).any():
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "encrypt_selector_bits: bits [queries][n_inputs] of 0 / 1 expected")
+        shape = (bits.size, p.R, p.k + 1, p.N)
+        samples = rng.integers(0, 1 << 32, size=shape, dtype=np.uint64).astype(np.uint32)
+        samples[:, :, p.k, :] = self._noise(rng, p.glwe_std_dev, (shape[0], p.R, p.N))
+        return self.ggsw_encrypt(glwe_sk, bits.astype(np.uint32).reshape(-1), samples).reshape(bits.shape + shape[1:])
 
     def encrypt_value(self, glwe_sk, values, rng=None) -> np.ndarray:
         """GLWE encryptions under glwe_sk (glwe_std_dev) of encode(value) in coefficient 0, values < 2^log_p

@@ -598,7 +598,7 @@ void tfhe_context_destroy(tfhe_context* ctx) {
                   ctx->d_lwe_big, ctx->d_lwe_out, ctx->d_lwe_ks, ctx->d_glwe_a, ctx->d_glwe_b, ctx->d_glwe_c,
                   ctx->d_tv,     ctx->d_misc,   ctx->d_ggsw_tmp, ctx->d_ggsw_raw,
                   ctx->d_key_tmp, ctx->d_pksk, ctx->d_pack_cols, ctx->d_lookup_ws, ctx->d_tree_ws,
-                  ctx->d_demux_ws};
+                  ctx->d_demux_ws, ctx->d_program_ws};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& g : ctx->gate_tvs)
@@ -1477,6 +1477,240 @@ int tfhe_table_lookup_glwe(tfhe_context* ctx, const uint32_t* selectors, size_t 
   TFHE_TRY(s.upload(kIn, leaves));
   TFHE_TRY(tfhe_table_lookup_glwe_device(ctx, ctx->d_ggsw_tmp, queries, depth, s[kIn], leaf_sets, tables, s[kOut]));
   return s.download_and_wait(kOut, lwe_out);
+}
+
+// ---------------------------------------------------------------------------------- encrypted branching program
+// include/tfhe_hip.h states the operations, pbs_wave.h::cmux_program_team the run of one team,
+// kernels.hip::program_plan_for the plan.
+namespace {
+
+constexpr size_t kOpWords = sizeof(ProgramOp) / sizeof(u32);
+
+struct ProgramArgs {
+  size_t queries, n_inputs, selector_sets;
+  const tfhe_program_node* nodes;
+  size_t n_nodes, n_terminals;
+  const uint32_t* outputs;
+  size_t n_outputs;
+};
+
+// everything about a program that can be refused without looking at the device
+int check_program(tfhe_context* ctx, const ProgramArgs& a) {
+  if (a.queries == 0 || a.queries > kMaxBatch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "queries must be in [1, 2^31)");
+  if (a.selector_sets != 1 && a.selector_sets != a.queries)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "selector_sets must be 1 or queries");
+  if (a.n_outputs == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "n_outputs must be at least 1");
+  if (a.n_terminals == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "n_terminals must be at least 1");
+  if (a.n_nodes > 0 && (!a.nodes || a.n_inputs == 0)) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "nodes without a node array or without inputs");
+  if (a.n_inputs > kMaxBatch || a.n_terminals > kMaxBatch || a.n_nodes > kMaxBatch || a.n_outputs > kMaxBatch ||
+      a.n_terminals + a.n_nodes > kMaxBatch)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "n_inputs, n_terminals + n_nodes and n_outputs must be below 2^31");
+  for (size_t i = 0; i < a.n_nodes; ++i) {
+    const tfhe_program_node& n = a.nodes[i];
+    const std::string at = "node " + std::to_string(i) + ": ";
+    if (n.sel >= a.n_inputs) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, at + "sel " + std::to_string(n.sel) + " is not below n_inputs");
+    if (n.rot >= 2 * ctx->N) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, at + "rot " + std::to_string(n.rot) + " is not below 2N");
+    if (n.lo >= a.n_terminals + i || n.hi >= a.n_terminals + i)
+      return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, at + "a node may only reference terminals and earlier nodes (forward or self reference)");
+  }
+  for (size_t o = 0; o < a.n_outputs; ++o)
+    if (a.outputs[o] >= a.n_terminals + a.n_nodes)
+      return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "output " + std::to_string(o) + " references neither a terminal nor a node");
+  return TFHE_OK;
+}
+
+// dependency levels: terminals 0, a node one more than its deeper operand.  -> nodes per level 1 .. depth and
+// (order != nullptr) the nodes sorted by level, by index within a level
+void program_levels(const ProgramArgs& a, std::vector<u32>* level_counts, std::vector<u32>* order) {
+  std::vector<u32> level(a.n_nodes);
+  std::vector<u32>& counts = *level_counts;
+  counts.clear();
+  for (size_t i = 0; i < a.n_nodes; ++i) {
+    auto of = [&](u32 ref) { return ref < a.n_terminals ? 0u : level[ref - a.n_terminals]; };
+    level[i] = 1 + std::max(of(a.nodes[i].lo), of(a.nodes[i].hi));
+    if (level[i] > counts.size()) counts.resize(level[i], 0);
+    ++counts[level[i] - 1];
+  }
+  if (order) {
+    std::vector<u32> at(counts.size() + 1, 0);
+    for (size_t l = 0; l < counts.size(); ++l) at[l + 1] = at[l] + counts[l];
+    order->resize(a.n_nodes);
+    for (size_t i = 0; i < a.n_nodes; ++i) (*order)[at[level[i] - 1]++] = (u32)i;
+  }
+}
+
+size_t program_image_need(size_t nodes, size_t outputs) { return nodes * kOpWords + outputs; }
+size_t program_bytes(const tfhe_context* ctx, size_t queries, size_t nodes, size_t outputs) {
+  return (queries * nodes * glwe_words(ctx) + tfhe_context::kProgramImages * program_image_need(nodes, outputs)) * sizeof(u32);
+}
+
+int plan_program_of(tfhe_context* ctx, size_t queries, const std::vector<u32>& counts, size_t n_outputs,
+                    std::vector<launch::ProgramLaunch>* launches, launch::ProgramPlanInfo* info) {
+  launches->resize(counts.size() + 1);
+  hipError_t e = launch::program_plan(ctx->field, ctx->pbs, queries, counts.data(), (u32)counts.size(), (u32)n_outputs,
+                                      ctx->program_parts, launches->data(), info);
+  if (e == hipErrorInvalidValue)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "queries * teams per query exceeds the 2^31 - 1 teams of one launch");
+  if (e != hipSuccess) return hip_fail(ctx, e, "program plan");
+  launches->resize(info->launches);
+  return TFHE_OK;
+}
+
+int reserve_program(tfhe_context* ctx, size_t queries, size_t nodes, size_t outputs) {
+  const size_t values = std::max<size_t>(1, queries * nodes * glwe_words(ctx)), image = program_image_need(nodes, outputs);
+  if (values <= ctx->program_value_words && image <= ctx->program_image_words) return TFHE_OK;
+  const size_t new_values = std::max(values, ctx->program_value_words), new_image = std::max(image, ctx->program_image_words);
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  for (auto& im : ctx->program_images) im = tfhe_context::ProgramImage{};
+  ctx->program_value_words = ctx->program_image_words = 0;
+  TFHE_TRY(ensure(ctx, &ctx->d_program_ws, &ctx->program_ws_words, new_values + tfhe_context::kProgramImages * new_image));
+  ctx->program_value_words = new_values;
+  ctx->program_image_words = new_image;
+  return TFHE_OK;
+}
+
+// the resident image of the program, uploaded if this is its first use
+int program_image(tfhe_context* ctx, const ProgramArgs& a, u32** d_image, const std::vector<u32>** counts) {
+  std::vector<u32> key;
+  key.reserve(4 + a.n_nodes * 4 + a.n_outputs);
+  for (size_t v : {a.n_inputs, a.n_terminals, a.n_nodes, a.n_outputs}) key.push_back((u32)v);
+  for (size_t i = 0; i < a.n_nodes; ++i)
+    for (u32 v : {a.nodes[i].sel, a.nodes[i].lo, a.nodes[i].hi, a.nodes[i].rot}) key.push_back(v);
+  key.insert(key.end(), a.outputs, a.outputs + a.n_outputs);
+  tfhe_context::ProgramImage* slot = nullptr;
+  for (auto& im : ctx->program_images)
+    if (im.key == key) slot = &im;
+  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+  const bool capturing = hipStreamIsCapturing(ctx->stream, &capture) != hipSuccess || capture != hipStreamCaptureStatusNone;
+  if (!slot) {
+    if (capturing)
+      return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                  "first use of this program during a stream capture: its upload synchronises, run the program once before capturing");
+    for (auto& im : ctx->program_images)
+      if (!im.pinned && (!slot || im.last_use < slot->last_use)) slot = &im;
+    if (!slot)
+      return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                  "every program image of the context is held by a captured graph; tfhe_context_reserve_program with a larger "
+                  "need releases them (and voids those graphs)");
+    std::vector<u32> order, level_counts;
+    program_levels(a, &level_counts, &order);
+    std::vector<u32> image(program_image_need(a.n_nodes, a.n_outputs));
+    for (size_t i = 0; i < a.n_nodes; ++i) {
+      const tfhe_program_node& n = a.nodes[order[i]];
+      const u32 op[kOpWords] = {n.sel, n.lo, n.hi, n.rot, order[i]};
+      std::copy(op, op + kOpWords, image.begin() + i * kOpWords);
+    }
+    std::copy(a.outputs, a.outputs + a.n_outputs, image.begin() + a.n_nodes * kOpWords);
+    slot->key.clear();  // not a valid entry until the upload has succeeded
+    u32* dst = ctx->d_program_ws + ctx->program_value_words + (size_t)(slot - ctx->program_images) * ctx->program_image_words;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // launches of the image this one replaces may be in flight
+    HIP_TRY(ctx, hipMemcpy(dst, image.data(), image.size() * sizeof(u32), hipMemcpyHostToDevice));
+    slot->key = std::move(key);
+    slot->level_counts = std::move(level_counts);
+  }
+  slot->last_use = ++ctx->program_clock;
+  if (capturing) slot->pinned = true;
+  *d_image = ctx->d_program_ws + ctx->program_value_words + (size_t)(slot - ctx->program_images) * ctx->program_image_words;
+  *counts = &slot->level_counts;
+  return TFHE_OK;
+}
+
+}  // namespace
+
+int tfhe_context_reserve_program(tfhe_context* ctx, size_t max_queries, size_t max_nodes, size_t max_outputs) {
+  TFHE_TRY(check_ctx(ctx));
+  if (max_queries == 0 || max_queries > kMaxBatch || max_nodes > kMaxBatch || max_outputs == 0 || max_outputs > kMaxBatch)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "max_queries and max_outputs must be in [1, 2^31), max_nodes below 2^31");
+  return reserve_program(ctx, max_queries, max_nodes, max_outputs);
+}
+
+int tfhe_context_set_program_split(tfhe_context* ctx, unsigned parts) {
+  if (!ctx) return TFHE_ERR_INVALID_ARGUMENT;
+  if (parts > kMaxBatch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "parts must be below 2^31 (0: automatic)");
+  ctx->program_parts = parts;
+  return TFHE_OK;
+}
+
+int tfhe_debug_program_plan(tfhe_context* ctx, size_t queries, const tfhe_program_node* nodes, size_t n_nodes, size_t n_terminals,
+                            unsigned* launches, unsigned* teams_per_query) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {launches, teams_per_query}, 1, "null pointer"));
+  const uint32_t out0 = 0;
+  ProgramArgs a{queries, kMaxBatch, 1, nodes, n_nodes, n_terminals, &out0, 1};
+  TFHE_TRY(check_program(ctx, a));
+  std::vector<launch::ProgramLaunch> plan;
+  launch::ProgramPlanInfo info{};
+  std::vector<u32> counts;
+  program_levels(a, &counts, nullptr);
+  TFHE_TRY(plan_program_of(ctx, queries, counts, 1, &plan, &info));
+  *launches = info.launches;
+  *teams_per_query = info.teams_per_query;
+  return TFHE_OK;
+}
+
+int tfhe_cmux_program_device(tfhe_context* ctx, const void* selectors_prepared, size_t queries, size_t n_inputs, size_t selector_sets,
+                             const tfhe_program_node* nodes, size_t n_nodes, const uint32_t* terminals, size_t n_terminals,
+                             const uint32_t* outputs, size_t n_outputs, uint32_t* glwe_out, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {terminals, outputs}, 1, "null pointer"));
+  if (!glwe_out && !lwe_out) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "glwe_out and lwe_out are both null");
+  if (n_nodes > 0 && !selectors_prepared) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  const ProgramArgs a{queries, n_inputs, selector_sets, nodes, n_nodes, n_terminals, outputs, n_outputs};
+  TFHE_TRY(check_program(ctx, a));
+  if (std::max<size_t>(1, queries * n_nodes * glwe_words(ctx)) > ctx->program_value_words ||
+      program_image_need(n_nodes, n_outputs) > ctx->program_image_words)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "the call needs " + std::to_string(program_bytes(ctx, queries, n_nodes, n_outputs)) + " bytes of program workspace (" +
+                    std::to_string(queries) + " queries, " + std::to_string(n_nodes) + " nodes, " + std::to_string(n_outputs) +
+                    " outputs), " + std::to_string(ctx->program_ws_words * sizeof(u32)) + " are reserved (tfhe_context_reserve_program)");
+  u32* d_image = nullptr;
+  const std::vector<u32>* counts = nullptr;
+  TFHE_TRY(program_image(ctx, a, &d_image, &counts));
+  std::vector<launch::ProgramLaunch> plan;
+  launch::ProgramPlanInfo info{};
+  TFHE_TRY(plan_program_of(ctx, queries, *counts, n_outputs, &plan, &info));
+  CmuxProgramPass pass{};
+  pass.selectors = selectors_prepared;
+  pass.query_stride = selector_sets == 1 ? 0 : n_inputs * prepared_ggsw_words(ctx);
+  pass.ops = reinterpret_cast<const ProgramOp*>(d_image);
+  pass.outputs = d_image + n_nodes * kOpWords;
+  pass.terminals = terminals;
+  pass.n_terminals = (u32)n_terminals;
+  pass.n_nodes = (u32)n_nodes;
+  pass.n_outputs = (u32)n_outputs;
+  pass.values = ctx->d_program_ws;
+  pass.glwe_out = glwe_out;
+  pass.lwe_out = lwe_out;
+  for (size_t i = 0; i < plan.size(); ++i) {
+    pass.parts = plan[i].parts;
+    pass.op_begin = plan[i].op_begin;
+    pass.op_end = plan[i].op_end;
+    pass.out_end = i + 1 == plan.size() ? (u32)n_outputs : 0u;
+    HIP_TRY(ctx, launch::cmux_program_pass(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, pass, queries));
+  }
+  return TFHE_OK;
+}
+
+// host form: selectors [selector_sets][n_inputs][R][k+1][N] raw; everything uploaded, the selectors prepared once
+int tfhe_cmux_program(tfhe_context* ctx, const uint32_t* selectors, size_t queries, size_t n_inputs, size_t selector_sets,
+                      const tfhe_program_node* nodes, size_t n_nodes, const uint32_t* terminals, size_t n_terminals,
+                      const uint32_t* outputs, size_t n_outputs, uint32_t* glwe_out, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {terminals, outputs}, 1, "null pointer"));
+  if (!glwe_out && !lwe_out) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "glwe_out and lwe_out are both null");
+  if (n_nodes > 0 && !selectors) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  TFHE_TRY(check_program(ctx, ProgramArgs{queries, n_inputs, selector_sets, nodes, n_nodes, n_terminals, outputs, n_outputs}));
+  TFHE_TRY(reserve_program(ctx, queries, n_nodes, n_outputs));
+  enum { kTerminals, kGlwe, kLwe };
+  Staging s(ctx, {n_terminals * ctx->N, glwe_out ? queries * n_outputs * glwe_words(ctx) : 0, lwe_out ? queries * n_outputs * big_lwe_words(ctx) : 0});
+  TFHE_TRY(s.reserve());
+  if (n_nodes > 0) TFHE_TRY(upload_and_prepare_ggsw(ctx, selectors, selector_sets * n_inputs));
+  TFHE_TRY(s.upload(kTerminals, terminals));
+  TFHE_TRY(tfhe_cmux_program_device(ctx, n_nodes > 0 ? ctx->d_ggsw_tmp : nullptr, queries, n_inputs, selector_sets, nodes, n_nodes,
+                                    s[kTerminals], n_terminals, outputs, n_outputs, glwe_out ? s[kGlwe] : nullptr,
+                                    lwe_out ? s[kLwe] : nullptr));
+  if (glwe_out && lwe_out) TFHE_TRY(download(ctx, glwe_out, s[kGlwe], queries * n_outputs * glwe_words(ctx)));
+  return lwe_out ? s.download_and_wait(kLwe, lwe_out) : s.download_and_wait(kGlwe, glwe_out);
 }
 
 // ---------------------------------------------------------------------------------- small ops

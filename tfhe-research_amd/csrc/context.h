@@ -46,6 +46,25 @@ struct tfhe_context {
   u32* d_demux_ws = nullptr;
   size_t demux_ws_words = 0;
   unsigned demux_height = 0;  // subtree height a team expands (tfhe_context_set_demux_subtree_height); 0: automatic
+  // Encrypted branching program (tfhe_context_reserve_program): one buffer, [values: one GLWE per (query, node)] then
+  // kProgramImages images of program_image_words words each -- a program compiled for the device (its ops in execution
+  // order, then its outputs).  An image is uploaded on the first use of a program (that call synchronises; a program
+  // already resident costs a comparison on the host) and the least recently used unpinned one is replaced.  As with
+  // gate_tvs below, an image used while the stream is capturing is pinned: the graph holds its address.  Reserving
+  // again un-pins and forgets all images (the buffer may have moved: graphs captured before are void).
+  static constexpr size_t kProgramImages = 4;
+  struct ProgramImage {
+    std::vector<u32> key;            // n_inputs, n_terminals, n_nodes, n_outputs, the nodes, the outputs; empty: free
+    std::vector<u32> level_counts;   // nodes per dependency level, in execution order
+    unsigned long long last_use = 0;
+    bool pinned = false;
+  };
+  u32* d_program_ws = nullptr;
+  size_t program_ws_words = 0;
+  size_t program_value_words = 0, program_image_words = 0;
+  ProgramImage program_images[kProgramImages];
+  unsigned long long program_clock = 0;
+  unsigned program_parts = 0;  // teams per query of a split level (tfhe_context_set_program_split); 0: automatic
   // tree LUT (tfhe_context_reserve_tree_lut): per-rotation inputs, segment state, the levels' results and packed GLWEs
   u32* d_tree_ws = nullptr;
   size_t tree_ws_words = 0;

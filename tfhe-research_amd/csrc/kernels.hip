@@ -730,6 +730,17 @@ demux_tree_kernel(PbsParams P, const typename F::elem* __restrict__ tw, DemuxTre
                                     blockIdx.x & ((1u << pass.log_subtrees) - 1u));
 }
 
+// ------------------------------------------------------------------------------ encrypted branching program
+// pbs_wave.h::cmux_program_team states the operations.  One team per (query, part) of a pass; the team's LDS is
+// cmux_tree_kernel's (one product at a time; acc stages the operand of a rotated node and the outputs' extraction).
+template <class F, int LOGN, int K>
+__global__ void __launch_bounds__((TeamCfg<F, LOGN, K, 1>::kThreads), (TeamCfg<F, LOGN, K, 1>::kMinWaves))
+cmux_program_kernel(PbsParams P, const typename F::elem* __restrict__ tw, CmuxProgramPass pass) {
+  using C = TeamCfg<F, LOGN, K, 1>;
+  auto w = make_wave<F, LOGN, K, 1>(g_smem, tw);
+  cmux_program_team<F, LOGN, K, C::G>(w, P, pass, (size_t)(blockIdx.x / pass.parts), blockIdx.x % pass.parts);
+}
+
 // dst row `row` = GLWE [k+1][N]: coefficient 0 of the body += factor[row] (the packing key's s_i g_l)
 __global__ void packing_add_gadget_kernel(u32* pksk, size_t rows, u32 k, u32 log_n, const u32* __restrict__ factor) {
   for (size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x; row < rows; row += (size_t)gridDim.x * blockDim.x)
@@ -1612,6 +1623,113 @@ hipError_t launch_demux_tree_pass(hipStream_t s, const PbsParams& P, const void*
   }
 }
 
+// How a branching program goes out (capi.cpp sequences the launches).  The host orders the nodes by dependency level
+// (terminals 0, a node one more than its deeper operand), so the nodes of a level are consecutive and independent of
+// each other.  Under `parts` teams per query a level of c nodes is dealt to min(parts, c) teams in one launch of its own;
+// consecutive levels that get one team are merged into one launch (values that cross teams cross a launch boundary).
+// The outputs ride on the last launch if that one has one team per query, else on a launch of their own.  parts = 1 is
+// therefore ONE launch, one team per query: the throughput case.  The cost model is the lookup's: a launch of T teams
+// whose teams make m products one after the other takes ceil(T / resident) m products, plus kLookupLaunchCost products
+// per launch (that guess again: not measured).  The automatic rule takes the cheapest of parts = 1, 2, 4, .. up to the
+// widest level (the smaller one on a tie); it depends on the shape of the call only (queries, level widths).
+template <class F, int LOGN, int K>
+struct ProgramKernel {
+  using C = TeamCfg<F, LOGN, K, 1>;
+  static constexpr int kThreads = C::kThreads;
+  static constexpr size_t kLds = C::kLds;
+  static auto get() { return cmux_program_kernel<F, LOGN, K>; }
+};
+inline double program_split(size_t queries, const u32* counts, u32 levels, u32 n_outputs, u32 parts, size_t resident,
+                            launch::ProgramLaunch* out, u32* launches, u32* widest) {
+  double cost = 0;
+  u32 n = 0, at = 0, wide = 1, last_parts = 0;
+  auto teams_of = [&](u32 l) { return counts[l] < parts ? counts[l] : parts; };
+  for (u32 l = 0; l < levels;) {
+    const u32 tp = teams_of(l), begin = at;
+    u32 per_team = 0;
+    if (tp == 1) {
+      for (; l < levels && teams_of(l) == 1; ++l) per_team += counts[l], at += counts[l];
+    } else {
+      per_team = (counts[l] + tp - 1) / tp;
+      at += counts[l++];
+    }
+    if (out) out[n] = launch::ProgramLaunch{begin, at, tp};
+    ++n;
+    last_parts = tp;
+    if (tp > wide) wide = tp;
+    cost += std::ceil((double)queries * tp / (double)resident) * per_team + kLookupLaunchCost;
+  }
+  if (last_parts != 1) {  // no launch yet, or the last level is split
+    const u32 tp = n_outputs < parts ? n_outputs : parts;
+    if (out) out[n] = launch::ProgramLaunch{at, at, tp ? tp : 1u};
+    ++n;
+    cost += kLookupLaunchCost;
+  }
+  *launches = n;
+  *widest = wide;
+  return cost;
+}
+inline bool program_plan_for(size_t queries, const u32* counts, u32 levels, u32 n_outputs, u32 forced_parts, size_t resident,
+                             launch::ProgramLaunch* out, launch::ProgramPlanInfo* info) {
+  u32 widest_level = 1;
+  for (u32 l = 0; l < levels; ++l)
+    if (counts[l] > widest_level) widest_level = counts[l];
+  u32 parts = forced_parts;
+  u32 launches = 0, wide = 0;
+  if (parts == 0) {
+    double best = 0;
+    for (u32 cand = 1;; cand = cand * 2 < widest_level ? cand * 2 : widest_level) {
+      if ((double)queries * cand > (double)kMaxGrid) break;
+      const double cost = program_split(queries, counts, levels, n_outputs, cand, resident, nullptr, &launches, &wide);
+      if (parts == 0 || cost < best) {
+        best = cost;
+        parts = cand;
+      }
+      if (cand >= widest_level) break;
+    }
+    if (parts == 0) return false;
+  }
+  if (parts > widest_level && parts > n_outputs) parts = widest_level > n_outputs ? widest_level : n_outputs;
+  if ((double)queries * parts > (double)kMaxGrid) return false;
+  program_split(queries, counts, levels, n_outputs, parts, resident, out, &launches, &wide);
+  info->launches = launches;
+  info->teams_per_query = wide;
+  return true;
+}
+
+template <class F, int LOGN, int K>
+hipError_t plan_program(size_t queries, const u32* counts, u32 levels, u32 n_outputs, u32 forced_parts,
+                        launch::ProgramLaunch* out, launch::ProgramPlanInfo* info) {
+  if constexpr (!field_shape_ok<F, LOGN>()) {
+    return hipErrorInvalidValue;
+  } else {
+    unsigned resident = 0;
+    hipError_t e = resident_teams<ProgramKernel<F, LOGN, K>>(&resident);
+    if (e != hipSuccess) return e;
+    return program_plan_for(queries, counts, levels, n_outputs, forced_parts, resident, out, info) ? hipSuccess : hipErrorInvalidValue;
+  }
+}
+
+// pass.query_stride arrives in 8-byte words, like launch_cmux_tree_pass's
+template <class F, int LOGN, int K>
+hipError_t launch_cmux_program_pass(hipStream_t s, const PbsParams& P, const void* tw_v, CmuxProgramPass pass, size_t queries) {
+  if constexpr (!field_shape_ok<F, LOGN>()) {
+    return hipErrorInvalidValue;
+  } else {
+    using C = TeamCfg<F, LOGN, K, 1>;
+    const size_t teams = queries * pass.parts;
+    if (teams == 0 || teams > kMaxGrid) return hipErrorInvalidValue;
+    auto tw = static_cast<const typename F::elem*>(tw_v);
+    auto kern = cmux_program_kernel<F, LOGN, K>;
+    static std::atomic<unsigned long long> lds_done{0};
+    hipError_t e = allow_lds(kern, C::kLds, lds_done);
+    if (e != hipSuccess) return e;
+    pass.query_stride /= sizeof(typename F::elem) / 8;
+    hipLaunchKernelGGL(kern, dim3((unsigned)teams), dim3(C::kThreads), C::kLds, s, P, tw, pass);
+    return hipGetLastError();
+  }
+}
+
 template <class F, int LOGN>
 hipError_t launch_bsk_prepare(hipStream_t s, const void* tw_v, const u32* polys, size_t poly_count,
                               void* spectra_v, u32 k) {
@@ -1870,6 +1988,15 @@ hipError_t demux_plan(int field, const PbsParams& P, size_t trees, u32 depth, u3
 
 hipError_t demux_tree_pass(hipStream_t s, int field, const PbsParams& P, const void* tw, const DemuxTreePass& pass, size_t teams) {
   TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (launch_demux_tree_pass<FF, LL, KK>(s, P, tw, pass, teams))));
+}
+
+hipError_t program_plan(int field, const PbsParams& P, size_t queries, const u32* level_counts, u32 levels, u32 n_outputs,
+                        u32 forced_parts, ProgramLaunch* out, ProgramPlanInfo* info) {
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (plan_program<FF, LL, KK>(queries, level_counts, levels, n_outputs, forced_parts, out, info))));
+}
+
+hipError_t cmux_program_pass(hipStream_t s, int field, const PbsParams& P, const void* tw, const CmuxProgramPass& pass, size_t queries) {
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (launch_cmux_program_pass<FF, LL, KK>(s, P, tw, pass, queries))));
 }
 
 hipError_t key_switch(hipStream_t s, const KsParams& K, u32 big_n, u32 n, const u32* lwe_in,

@@ -129,6 +129,23 @@ hipError_t demux_plan(int field, const PbsParams& P, size_t trees, u32 depth, u3
 // one pass: `teams` = trees << pass.log_subtrees workgroups.  pass.query_stride in 8-byte words here.
 hipError_t demux_tree_pass(hipStream_t s, int field, const PbsParams& P, const void* tw, const DemuxTreePass& pass, size_t teams);
 
+// ---- encrypted branching program (pbs_wave.h::cmux_program_team; the plan: kernels.hip::program_plan_for)
+// one launch: ops [op_begin, op_end) of the execution order dealt to `parts` teams per query; the LAST launch of a plan
+// also carries the outputs (op_begin == op_end: only them)
+struct ProgramLaunch {
+  u32 op_begin, op_end, parts;
+};
+struct ProgramPlanInfo {
+  u32 launches;
+  u32 teams_per_query;  // the most teams any launch gives a query
+};
+// level_counts [levels]: nodes per dependency level in execution order; `out` has room for levels + 1 launches.
+// forced_parts 0: automatic.  hipErrorInvalidValue: queries * parts exceeds a grid of 2^31 - 1 teams.
+hipError_t program_plan(int field, const PbsParams& P, size_t queries, const u32* level_counts, u32 levels, u32 n_outputs,
+                        u32 forced_parts, ProgramLaunch* out, ProgramPlanInfo* info);
+// one pass: queries * pass.parts workgroups.  pass.query_stride in 8-byte words here.
+hipError_t cmux_program_pass(hipStream_t s, int field, const PbsParams& P, const void* tw, const CmuxProgramPass& pass, size_t queries);
+
 // elementwise helpers.  first_shift = bit of the lowest kept limb (PbsParams::first_shift)
 hipError_t decompose_words(hipStream_t s, u32 log_base, u32 levels, u32 first_shift, const u32* values,
                            size_t count, u32* digits /* [count][levels] */);

@@ -1448,6 +1448,112 @@ TFHE_HD void demux_tree_team(const Ctx& c, const PbsParams& P, const DemuxTreePa
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Encrypted branching program (no reference counterpart): the CMUX of the lookup over a DAG instead of a full tree.
+// All arithmetic mod 2^32.  A reference r names clear terminal r (the trivial GLWE with body coefficient j =
+// terminals[r][j] << tv_shift, the lookup's leaf encoding) if r < n_terminals, else node r - n_terminals:
+//   V_i = cmux(C_sel, R(lo), X^rot R(hi)),  rot in [0, 2N) a negacyclic monomial, lo and hi earlier than node i
+// The lookup's tree is rot = 0, its rotation step i is lo = hi, rot = 2N - 2^i, the write's lo = hi, rot = 2^i.
+//
+// cmux_program_team: ONE team executes a run of nodes in the order it is given (the host orders them by dependency
+// level), then a run of outputs.  Every node value lives in the team's query's slots of the workspace, one GLWE per
+// (query, node).  All products go through ONE call site whose operand functors branch on team-uniform facts -- terminal
+// or node operand, rot zero or not:
+//   rot == 0   src(j) = R(hi)[j] - R(lo)[j]                  out(j, v): V_i[j] = R(lo)[j] + v
+//   rot != 0   acc = R(hi); src(j) = (X^rot acc)[j] - R(lo)[j]   out(j, v): the same
+// With rot = 0 every slot word is written and later read by the lane that owns index j within one team (src and out
+// walk the indices r T + tid), so the run has no barrier or fence of its own.  A node with rot != 0 reads words other
+// lanes wrote: its operand is staged in acc by the owning lanes, the product starts behind poly_sync, and all rotated
+// reads precede the product's first inverse transform; the sync that ends every product (poly_sync on one exchange
+// buffer, the product's own team barrier on two) keeps the next staging behind those reads.  Values that cross teams
+// cross a launch boundary (kernels.hip::program_plan_for), never a barrier inside a launch.
+//
+// CmuxProgramPass: one launch (kernels.hip::cmux_program_kernel).  Team (query, part) runs the part-th share of ops
+// [op_begin, op_end) and of outputs [out_begin, out_end), shares of ceil(count / parts) consecutive entries.
+// ---------------------------------------------------------------------------------------------
+struct ProgramOp {
+  u32 sel, lo, hi, rot;  // tfhe_program_node as the caller gave it
+  u32 dst;               // the node's index: its slot of the query's values
+};
+
+struct CmuxProgramPass {
+  const void* selectors;  // prepared GGSWs: selector s of query q at selectors + q * query_stride + s * ggsw_words
+  size_t query_stride;    // elements from one query's selectors to the next one's; 0: all queries share them
+  const ProgramOp* ops;   // the program in execution order
+  const u32* outputs;     // references
+  const u32* terminals;   // [n_terminals][N] message words
+  u32 n_terminals;
+  u32 n_nodes;            // slots per query
+  u32 n_outputs;
+  u32 parts;              // teams per query
+  u32 op_begin, op_end;
+  u32 out_begin, out_end;
+  u32* values;            // [query][n_nodes][K+1][N]
+  u32* glwe_out;          // [query][n_outputs][K+1][N], or null
+  u32* lwe_out;           // [query][n_outputs][K N + 1]: sample_extract(., 0), or null
+};
+
+template <class F, int LOGN, int K, int G, class Ctx>
+TFHE_HD void cmux_program_team(const Ctx& c, const PbsParams& P, const CmuxProgramPass& A, size_t query, u32 part) {
+  typedef typename F::elem elem;
+  constexpr int E = NttShape<LOGN, G>::kE;
+  constexpr int T = NttShape<LOGN, G>::kThreads;
+  constexpr int N = 1 << LOGN;
+  constexpr size_t GLWE = (size_t)(K + 1) * N;
+  const int lane = c.tid();
+  const int me = c.group();
+  u32* acc = c.acc();
+  const size_t ggsw_words = (size_t)(K + 1) * P.levels * (K + 1) * F::kParts * (N >> F::kLogShrink);  // elements
+  const elem* sel = static_cast<const elem*>(A.selectors) + query * A.query_stride;
+  u32* values = A.values + query * A.n_nodes * GLWE + (size_t)me * N;  // my polynomial of the query's slot 0
+  const u32 nt = A.n_terminals;
+  const bool body = me == K;
+  // coefficient j of my polynomial of R(ref) (lane-local)
+  auto word = [&](u32 ref, int j) -> u32 {
+    if (ref < nt) return body ? A.terminals[(size_t)ref * N + j] << P.tv_shift : 0u;
+    return values[(size_t)(ref - nt) * GLWE + j];
+  };
+
+  const u32 op_share = (A.op_end - A.op_begin + A.parts - 1) / A.parts;
+  const u32 op_first = A.op_begin + part * op_share;
+  const u32 op_last = op_first + op_share < A.op_end ? op_first + op_share : A.op_end;
+#pragma unroll 1
+  for (u32 i = op_first; i < op_last; ++i) {
+    const u32 lo = c.uniform(A.ops[i].lo), hi = c.uniform(A.ops[i].hi), rot = c.uniform(A.ops[i].rot);
+    u32* dst = values + (size_t)c.uniform(A.ops[i].dst) * GLWE;
+    if (rot) {
+#pragma unroll
+      for (int r = 0; r < E; ++r) acc[r * T + lane] = word(hi, r * T + lane);
+      c.poly_sync();  // the rotation reads words other lanes wrote
+    }
+    auto src = [&](int j) -> u32 { return (rot ? monomial_coeff<LOGN>(acc, j, rot) : word(hi, j)) - word(lo, j); };
+    auto out = [&](int j, u32 value) { dst[j] = word(lo, j) + value; };
+    external_product_team<F, LOGN, K, G>(c, P, sel + (size_t)c.uniform(A.ops[i].sel) * ggsw_words, src, out);
+    if (c.exchange_buffers() != 2) c.poly_sync();
+  }
+
+  const u32 out_share = (A.out_end - A.out_begin + A.parts - 1) / A.parts;
+  const u32 out_first = A.out_begin + part * out_share;
+  const u32 out_last = out_first + out_share < A.out_end ? out_first + out_share : A.out_end;
+#pragma unroll 1
+  for (u32 o = out_first; o < out_last; ++o) {
+    const u32 ref = c.uniform(A.outputs[o]);
+    const size_t at = query * A.n_outputs + o;
+    if (A.glwe_out) {
+      u32* dst = A.glwe_out + at * GLWE + (size_t)me * N;
+#pragma unroll
+      for (int r = 0; r < E; ++r) dst[r * T + lane] = word(ref, r * T + lane);
+    }
+    if (A.lwe_out) {
+#pragma unroll
+      for (int r = 0; r < E; ++r) acc[r * T + lane] = word(ref, r * T + lane);
+      c.poly_sync();  // sample_extract reads words other lanes wrote
+      sample_extract_team<LOGN, K, G>(c, A.lwe_out + at * ((size_t)K * N + 1));
+      c.poly_sync();  // before the next output is staged over them
+    }
+  }
+}
+
 // Forward NTT of one u32 polynomial of the bootstrapping key into the prepared layout,
 // pre-scaled by N^-1.
 // LAYOUT_E: the shape the key is laid out for (key_layout_e; 0: this transform's own)
