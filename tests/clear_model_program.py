@@ -115,3 +115,50 @@ def small_shared_program(N: int):
     p.output(n2)
     p.output(n0)
     return p
+
+
+def wide_uneven_program(N: int):
+    """Ten nodes over four inputs in level widths 5, 3, 2 with four outputs: what a DAG has and a tree has not, at the
+    widths where a split plan deals unequal shares.  Level 1 (a0 .. a4, terminals only): rot 0, 3, 0, N + 1, and a4
+    with lo = hi on one terminal, rot 2N - 1.  Level 2: b0 = (a0, a4, rot 7), b1 = (a1, a3, rot 0), b2 with lo = hi = a2,
+    rot N.  Level 3: c0 = (b0, b2, rot 2N - 5) and c1 = (b1, a0, rot 0), whose a0 is two launches old under a split.
+    The nodes are appended a0 a1 a2 a3 b1 a4 b0 b2 c0 c1 -- NOT sorted by level (b1 precedes a4), so the host's stable
+    sort by level moves something: it runs a0 .. a4, b1, b0, b2, c0, c1 while the value slots keep the caller's indices.
+    Under a split every level-2 and level-3 node reads values other teams wrote one launch (or two) earlier, b0 and
+    b2 through rot != 0; the last level is split, so the outputs go out on a launch of their own: four outputs (c0,
+    c1, the level-1 node a3, terminal 1) are shares of 2, 2, 0 at three teams."""
+    p = branching().BranchingProgram(4, N)
+    rng = np.random.default_rng(5 * N + 3)
+    t = [p.terminal(rng.integers(0, 16, size=N)) for _ in range(3)]
+    a0 = p.node(0, t[0], t[1])
+    a1 = p.node(1, t[1], t[2], rot=3)
+    a2 = p.node(2, t[2], t[0])
+    a3 = p.node(3, t[0], t[2], rot=N + 1)
+    b1 = p.node(2, a1, a3)
+    a4 = p.node(0, t[1], t[1], rot=2 * N - 1)
+    b0 = p.node(1, a0, a4, rot=7)
+    b2 = p.node(3, a2, a2, rot=N)
+    c0 = p.node(0, b0, b2, rot=2 * N - 5)
+    c1 = p.node(1, b1, a0)
+    for ref in (c0, c1, a3, t[1]):
+        p.output(ref)
+    return p
+
+
+def program_family(N: int, v: int):
+    """Member v of a family on small_shared_program's skeleton (three nodes, two inputs, two terminals, two outputs):
+    n1's rot is N - 1 - v, and for odd v the lo and hi of n2 are swapped.  Every member has the SAME n_inputs,
+    n_terminals, n_nodes and n_outputs, and every reference of every member is in range for every other.  So if a
+    context ever hands a replayed graph (or a call) the image of another member, the launch computes wrong WORDS but
+    reads and writes exactly the buffers the right image would: a mix-up in the image cache shows as a failed
+    comparison, never as an access outside the workspace.  The tests of the cache rely on that."""
+    if not 0 <= v < N - 1:
+        raise ValueError("v in [0, N - 1) expected")
+    p = branching().BranchingProgram(2, N)
+    t0, t1 = p.terminal(np.arange(N) % 16), p.terminal(7)
+    n0 = p.node(0, t0, t1)
+    n1 = p.node(1, n0, n0, rot=N - 1 - v)
+    n2 = p.node(0, n1, n0) if v & 1 else p.node(0, n0, n1)
+    p.output(n2)
+    p.output(n0)
+    return p

@@ -1,6 +1,7 @@
 """The clear model of the encrypted branching program (tests/clear_model_program.py) and the builder and constructors of
 tfhe-research_amd/branching.py: the lookup as a program, identity I16, the reduced BDD of a truth table, and the
-comparison programs against Python integers.  CPU only; small rings, since the algebra does not depend on N."""
+comparison programs against Python integers; the helper programs of the wide-plan and image-cache tests node by node
+through the oracle's CMUX.  CPU only; small rings, since the algebra does not depend on N."""
 import os
 import sys
 
@@ -151,3 +152,65 @@ def test_arrays_use_the_abi_references():
         assert lo < nt + i and hi < nt + i and sel < 4 and rot < 32
     assert outputs.tolist() == [nt + p.n_nodes - 1, nt + 3, 1]
     assert p.level_widths() == [2, 2, 1, 2, 2, 1, 1] and p.depth == 7
+
+
+def test_the_wide_and_family_programs_have_the_shapes_their_tests_rely_on():
+    N = 32
+    w = cp.wide_uneven_program(N)
+    assert w.level_widths() == [5, 3, 2] and w.n_nodes == 10 and w.n_inputs == 4 and len(w.terminals) == 3
+    assert w._level != sorted(w._level), "the nodes must not arrive sorted by level"
+    nodes, terminals, outputs = w.arrays()
+    nt = terminals.shape[0]
+    assert outputs.tolist() == [nt + 8, nt + 9, nt + 3, 1]
+    assert sorted(nodes[[0, 1, 2, 3, 5], 3].tolist()) == sorted([0, 3, 0, N + 1, 2 * N - 1])
+    assert nodes[5, 1] == nodes[5, 2] < nt and nodes[7, 1] == nodes[7, 2] == nt + 2
+    assert sorted(set(nodes[:, 0].tolist())) == [0, 1, 2, 3]
+    family = [cp.program_family(N, v) for v in range(9)]
+    keys = set()
+    for v, f in enumerate(family):
+        assert (f.n_inputs, len(f.terminals), f.n_nodes, len(f.outputs)) == (2, 2, 3, 2)
+        assert f.nodes[1][3] == N - 1 - v and (f.nodes[2][1] > f.nodes[2][2]) == bool(v & 1)
+        assert np.array_equal(f.arrays()[1], family[0].arrays()[1]) and np.array_equal(f.arrays()[2], family[0].arrays()[2])
+        keys.add(f.arrays()[0].tobytes())
+    assert len(keys) == 9
+
+
+@pytest.mark.parametrize("aligned", [False, True])
+def test_the_new_programs_node_by_node_through_the_oracles_cmux(oracle, aligned):
+    """program_values on arbitrary selector words = the oracle's CMUX applied node by node (the hi operand rotated by
+    clear_model.negacyclic_shift), every value of every node: k = 1, N = 512, (7, 3), both alignments"""
+    k, logn, lb, levels, log_p = 1, 9, 7, 3, 4
+    N = 1 << logn
+    p = oracle.Params(k, logn, 8, oracle.Decomposer(lb, levels), log_p=log_p)
+    rng = np.random.default_rng(40 + aligned)
+    for prog in (cp.wide_uneven_program(N), cp.program_family(N, 0), cp.program_family(N, 3)):
+        nodes, terminals, _ = prog.arrays()
+        sel = words(rng, (prog.n_inputs, (k + 1) * levels, k + 1, N))
+        sel[0, 0, 0, :] = cm.edge_words()[:N]
+        got = cp.program_values(nodes, terminals, sel, k, log_p, lb, levels, aligned)
+        vals = list(cp.terminal_glwes(terminals, k, log_p))
+        with oracle.decomposer_aligned(aligned):
+            for s, lo, hi, rot in nodes.tolist():
+                vals.append(oracle.cmux(p, sel[s], vals[lo], cm.negacyclic_shift(vals[hi], rot) if rot else vals[hi])[0])
+        assert np.array_equal(got, np.stack(vals))
+
+
+@pytest.mark.parametrize("k,logn,lb,levels,aligned", CASES)
+def test_i16_the_new_programs_decrypt_to_evaluate_clear(k, logn, lb, levels, aligned):
+    """I16 on wide_uneven_program (all 16 inputs) and on members 0, 1 and 8 of program_family (all 4 inputs), all N
+    coefficients of every output, as test_i16_the_output_is_the_terminal_reached_times_the_monomials states it; and
+    from_truth_table(D = 4, 2-bit entries) at all 16 addresses"""
+    rng = np.random.default_rng(17 * lb + k)
+    N, log_p = 1 << logn, 4
+    table = np.random.default_rng(4).integers(0, 4, size=16).astype(np.uint32)
+    progs = [cp.wide_uneven_program(N), bp.from_truth_table(table, 4, N)] + [cp.program_family(N, v) for v in (0, 1, 8)]
+    S = rng.integers(0, 2, size=(k, N)).astype(np.uint32)
+    for prog in progs:
+        nodes, terminals, outputs = prog.arrays()
+        bound = 0 if phase_is_exact(lb, levels, aligned) else cl.rounding_bound(k, N, lb, levels, prog.depth)
+        for x in range(1 << prog.n_inputs):
+            bits = bp.bits_of(x, prog.n_inputs)
+            sel = noise_free_selectors(rng, bits, S, lb, levels, aligned)
+            got = cm.glwe_phase(cp.program_model(nodes, terminals, outputs, sel, k, log_p, lb, levels, aligned), S)
+            want = cm.encode(prog.evaluate_clear(bits), log_p)
+            assert int(np.abs(centered(got - want, cm.rec_modulus_bits(lb, aligned))).max()) <= bound, (prog.n_nodes, x)

@@ -1,7 +1,8 @@
 """The device source of the encrypted branching program (csrc/pbs_wave.h::cmux_program_team) through the host SIMT
 emulator (tests/emu/emu_program.cpp, its own shared object), every output word against the clear model
 (tests/clear_model_program.py): arbitrary selector words, the program that holds every path of the team, as one team
-per query and split over two."""
+per query and split over two; the wide program whose levels deal unequal and empty shares, split over up to eight; what
+branching.from_truth_table emits."""
 import ctypes as C
 import functools
 import os
@@ -131,3 +132,40 @@ def test_program_matches_the_model_at_k2(emu, logn, g, exb, lb, levels, aligned,
     exchange buffers and the smallest program that still has a shared node and one rotation, one query: a product of
     that team and the 2048 x 2048 matrices of its model are seconds each (test_emu_lookup.py::k2_sizes)"""
     check(emu, FFT, g, 2, logn, lb, levels, aligned, exb, queries=1 if small else 2, small=small)
+
+
+def check_program(emu, field, prog, seed, parts_list, shared_parts=None, k=1, logn=9, lb=7, levels=3, aligned=True, queries=2):
+    """`prog` with `queries` queries on their own arbitrary selectors under every parts of parts_list, then (shared_parts)
+    all queries on the selectors of query 0: GLWE and extracted LWE outputs against program_model"""
+    import clear_model_lookup as cl
+    arrays = prog.arrays()
+    assert int(arrays[0][:, 0].max()) + 1 == prog.n_inputs  # run() takes n_inputs from the nodes
+    sel = selectors(logn, levels, queries, prog.n_inputs, seed=seed, k=k)
+    want = np.stack([cp.program_model(*arrays, sel[q], k, LOG_P, lb, levels, aligned) for q in range(queries)])
+    spec = prepared(emu, field, k, logn, sel, 1)
+    for parts in parts_list:
+        glwe, lwe = run(emu, field, 1, k, logn, lb, levels, aligned, 1, spec, queries, False, arrays, parts)
+        assert np.array_equal(glwe, want), parts
+        assert np.array_equal(lwe, cl.sample_extract0(want)), parts
+    if shared_parts:
+        glwe, lwe = run(emu, field, 1, k, logn, lb, levels, aligned, 1, spec, queries, True, arrays, shared_parts)
+        assert np.array_equal(glwe, np.stack([want[0]] * queries))
+        assert np.array_equal(lwe, cl.sample_extract0(np.stack([want[0]] * queries)))
+
+
+@pytest.mark.parametrize("field", [FFT, GL])
+def test_wide_uneven_program_matches_the_model(emu, field):
+    """clear_model_program.wide_uneven_program (level widths 5, 3, 2, nodes not sorted by level, four outputs) at k = 1,
+    N = 512, (7, 3) aligned, two queries: parts 1, 2, 3, 4, 5 and 8 -- unequal shares (3, 2 of five nodes at two
+    teams), an empty share (2, 2, 1, 0 at four: that team's op_first lies past op_end), a split last level with the
+    outputs on a launch of their own (2, 2, 0 at three teams), cross-team reads through rot != 0 -- and both queries on
+    shared selectors at parts 3"""
+    check_program(emu, field, cp.wide_uneven_program(512), 950 + field, (1, 2, 3, 4, 5, 8), shared_parts=3)
+
+
+def test_truth_table_program_matches_the_model(emu):
+    """branching.from_truth_table(D = 4, 2-bit entries): what the shipped constructor emits, parts 1 and 4"""
+    table = np.random.default_rng(4).integers(0, 4, size=16).astype(np.uint32)
+    prog = cp.branching().from_truth_table(table, 4, 512)
+    assert prog.level_widths() == [5, 4, 2, 1]
+    check_program(emu, FFT, prog, 960, (1, 4))

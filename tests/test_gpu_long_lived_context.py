@@ -1,6 +1,6 @@
 """What a context remembers between calls (-m gpu): the gate test-vector cache and its LRU order, keys replaced on a live
-context, mode switches with keys loaded, workspaces that grow and then serve small calls, refused calls, and seeded
-interleavings of all of them.  Every comparison is bit-exact.  Expected words come from the CPU oracle, from the clear
+context, mode switches with keys loaded, workspaces that grow and then serve small calls, refused calls, seeded
+interleavings of all of them, and the image cache of the branching programs (section G).  Every comparison is bit-exact.  Expected words come from the CPU oracle, from the clear
 models of tests/clear_model*.py, or from an earlier output of the same context that was itself checked against one of
 those -- never from a second context of the library under test.
 
@@ -29,9 +29,12 @@ import pytest
 import torch
 
 import clear_model as cm
+import clear_model_demux as cd
 import clear_model_lookup as cl
 import clear_model_packing as cmp_
+import clear_model_program as cp
 import test_gpu_clear_model as tcm
+import test_gpu_program as tprog
 import test_gpu_tree_lut as ttl
 from gpu_common import pkg, rand_u32, to_pkg_params
 from test_gpu_keygen import glwe_samples, lwe_samples
@@ -952,4 +955,299 @@ def test_f_seeded_interleavings(world, expected, seed):
             log.append(kind if got is None else f"{kind} {b}")
             if got is not None:
                 assert np.array_equal(got, want), ("seed", seed, "operations so far", log)
+        ctx.set_stream(None)
+
+
+# ------------------------------------------------------------------------------------------------ G: program images and workspaces
+# include/tfhe_hip.h: the four most recently used programs are resident in the workspace of tfhe_context_reserve_program;
+# an image used during a capture stays resident until the next GROWING reservation; a fifth program is refused when all
+# four are held so; a growing reservation (the host form's own included) forgets every image.
+#
+# k = 1, N = 512, PBS (7,3), three queries of arbitrary selector words, the members P0 .. P8 of
+# clear_model_program.program_family: they share every size and all their references are valid for each other, so a
+# call or a replayed graph that is handed the wrong image computes wrong words inside the right buffers.  Expected
+# words are program_model's, computed once per (member, selectors, alignment).
+#
+# The residency probe: a device-form call inside a stream capture returns OK for a resident program and pins it; for
+# a program that is not resident it is refused ("stream capture" in the message) with the capture left intact.
+G_QUERIES = 3
+FILL = 0x5A5A5A5A
+
+
+class ProgramWorld:
+    def __init__(self):
+        m = pkg()
+        self.pbs = (7, 3)
+        self.p = p = m.TfheParams(1, 9, 8, m.DecomposerParams(*self.pbs), m.DecomposerParams(4, 5), log_p=4)
+        self.family = [cp.program_family(p.N, v) for v in range(9)]
+        self.wide = cp.wide_uneven_program(p.N)
+        rng = np.random.default_rng(20261019)
+        self.sels = [tprog.edge_mix(rng, (G_QUERIES, 2, p.R, p.k + 1, p.N), s) for s in range(4)]
+        self.wide_sels = tprog.edge_mix(rng, (G_QUERIES + 1, 4, p.R, p.k + 1, p.N), 9)
+        self.cache = {}
+
+    def model(self, prog, sel, aligned=False):
+        p = self.p
+        return np.stack([cp.program_model(*prog.arrays(), s, p.k, p.log_p, *self.pbs, aligned, p.padding_bits) for s in sel])
+
+    def want(self, v, s=0, aligned=False):
+        """program_model's GLWEs [queries][2][k+1][N] of member v (v = "wide": wide_uneven_program) on selector set s"""
+        if (v, s, aligned) not in self.cache:
+            if v == "wide":
+                self.cache[(v, s, aligned)] = self.model(self.wide, self.wide_sels[:s], aligned)  # s: the number of queries
+            else:
+                self.cache[(v, s, aligned)] = self.model(self.family[v], self.sels[s], aligned)
+        return self.cache[(v, s, aligned)]
+
+
+@pytest.fixture(scope="module")
+def programs():
+    pw = ProgramWorld()
+    for s in range(4):  # a mix-up of two members must be visible on every selector set the tests use
+        for v in range(9):
+            for w in range(v):
+                if s == 0 or 0 in (v, w):
+                    assert not np.array_equal(pw.want(v, s), pw.want(w, s)), (v, w, s)
+    return pw
+
+
+def program_buffers(ctx, pw, max_nodes=3, max_outputs=2):
+    """reserve for the family and allocate the static tensors a captured call names (on the current torch stream)"""
+    p = pw.p
+    ctx.reserve_program(G_QUERIES, max_nodes, max_outputs)
+    return SimpleNamespace(prepared=tprog.prepare(ctx, pw.sels[0]).contiguous(), terminals=dev(pw.family[0].arrays()[1]),
+                           out=torch.full((G_QUERIES, 2, p.k + 1, p.N), FILL, dtype=torch.int32, device=DEV),
+                           marker=torch.zeros(1, dtype=torch.int32, device=DEV))
+
+
+def run_member(ctx, pw, bufs, v, s=None):
+    """an eager device-form call of member v into the static buffers (s: selector set s copied in place first)"""
+    if s is not None:
+        bufs.prepared.copy_(tprog.prepare(ctx, pw.sels[s]))
+    bufs.out.fill_(FILL)
+    ctx.cmux_program(pw.family[v], bufs.prepared, want="glwe", terminals=bufs.terminals, out=bufs.out)
+    return host(bufs.out)
+
+
+def probe(ctx, pw, bufs, v, stream):
+    """the residency probe: -> (graph, None) if the captured call was accepted, (graph, the TfheError) if refused"""
+    graph, err = torch.cuda.CUDAGraph(), None
+    with torch.cuda.graph(graph, stream=stream):
+        try:
+            ctx.cmux_program(pw.family[v], bufs.prepared, want="glwe", terminals=bufs.terminals, out=bufs.out)
+        except pkg().TfheError as e:
+            err = e
+        bufs.marker.add_(1)  # the capture goes on after a refusal and ends well
+    return graph, err
+
+
+def refused_as_not_resident(ctx, bufs, err, what):
+    assert err is not None, (what, "accepted inside a capture: the program was resident")
+    assert err.status == INVALID and "stream capture" in str(err), str(err)
+    ctx.synchronize()
+    assert bool((bufs.out == FILL).all()), (what, "the refused call enqueued something")
+
+
+def replay(pw, ctx, bufs, graph, stream, s):
+    """selector set s copied into the captured buffer in place, the graph replayed once -> the words it wrote"""
+    bufs.prepared.copy_(tprog.prepare(ctx, pw.sels[s]))
+    bufs.out.fill_(FILL)
+    graph.replay()
+    stream.synchronize()
+    return host(bufs.out)
+
+
+def g1_steps(pw, ctx, bufs, side):
+    """-> P0's captured graph; leaves P0 (pinned), P4, P1 and P3 resident"""
+    for v in (0, 1, 2, 3, 0, 4):
+        check(run_member(ctx, pw, bufs, v), pw.want(v), ("member", v))
+    bufs.out.fill_(FILL)
+    side.synchronize()
+    _, err = probe(ctx, pw, bufs, 1, side)  # P1 was the least recently used when P4 arrived (P0 had been touched)
+    refused_as_not_resident(ctx, bufs, err, "P1 after P0 P1 P2 P3 P0 P4")
+    graph0, err = probe(ctx, pw, bufs, 0, side)
+    assert err is None, ("P0 was touched before P4 arrived and must still be resident", str(err))
+    check(run_member(ctx, pw, bufs, 1), pw.want(1), "P1 uploaded again")
+    return graph0
+
+
+def test_g1_program_images_leave_in_lru_order(programs):
+    """reserve once; P0 P1 P2 P3, P0 again, P4: each its own words.  The victim was P1 (refused inside a capture, nothing
+    enqueued: the output keeps its fill), not P0 (accepted); P1 again, eagerly, is uploaded again"""
+    pw, side = programs, torch.cuda.Stream()
+    with pkg().Context(pw.p) as ctx:
+        with torch.cuda.stream(side):
+            bufs = program_buffers(ctx, pw)
+            graph0 = g1_steps(pw, ctx, bufs, side)
+            check(replay(pw, ctx, bufs, graph0, side, 1), pw.want(0, 1), "P0's graph")
+        ctx.set_stream(None)
+
+
+def test_g2_a_pinned_image_survives_traffic(programs):
+    """after g1: P5 P6 P7 P8 P1 eagerly -- five uploads through the three slots P0's capture does not hold -- then P0's
+    graph twice on fresh selectors written in place; a reservation that does not grow changes nothing: the graph still
+    replays P0 and P1, which the traffic left resident, is still accepted inside a capture"""
+    pw, side = programs, torch.cuda.Stream()
+    with pkg().Context(pw.p) as ctx:
+        with torch.cuda.stream(side):
+            bufs = program_buffers(ctx, pw)
+            graph0 = g1_steps(pw, ctx, bufs, side)
+            for v in (5, 6, 7, 8, 1):
+                check(run_member(ctx, pw, bufs, v, 0), pw.want(v), ("member", v))
+            for s in (1, 2):
+                check(replay(pw, ctx, bufs, graph0, side, s), pw.want(0, s), ("P0's graph after the traffic, selectors", s))
+            ctx.reserve_program(G_QUERIES, 3, 2)
+            ctx.reserve_program(1, 1, 1)
+            check(replay(pw, ctx, bufs, graph0, side, 3), pw.want(0, 3), "P0's graph after a reservation that does not grow")
+            bufs.out.fill_(FILL)
+            side.synchronize()
+            graph1, err = probe(ctx, pw, bufs, 1, side)
+            assert err is None, ("P1 was the last program used and must be resident", str(err))
+            check(replay(pw, ctx, bufs, graph1, side, 2), pw.want(1, 2), "P1's graph")
+            check(replay(pw, ctx, bufs, graph0, side, 0), pw.want(0, 0), "P0's graph at the end")
+        ctx.set_stream(None)
+
+
+def test_g3_a_fifth_program_is_refused_when_four_are_held(programs):
+    """P0 .. P3 each run and captured in a graph of its own; P4 is refused with the header's message and enqueues nothing;
+    the four graphs still replay; a growing reservation releases the images and P4 runs.  The old graphs are deleted
+    before that and not replayed: the header declares them void (they name the workspace that was freed)"""
+    pw, side = programs, torch.cuda.Stream()
+    with pkg().Context(pw.p) as ctx:
+        with torch.cuda.stream(side):
+            bufs = program_buffers(ctx, pw)
+            graphs = []
+            for v in range(4):
+                check(run_member(ctx, pw, bufs, v), pw.want(v), ("member", v))
+                side.synchronize()
+                graph, err = probe(ctx, pw, bufs, v, side)
+                assert err is None, (v, str(err))
+                graphs.append(graph)
+            bufs.out.fill_(FILL)
+            with pytest.raises(pkg().TfheError) as e:
+                ctx.cmux_program(pw.family[4], bufs.prepared, want="glwe", terminals=bufs.terminals, out=bufs.out)
+            assert e.value.status == INVALID and "held by a captured graph" in str(e.value), str(e.value)
+            ctx.synchronize()
+            assert bool((bufs.out == FILL).all()), "the refused call enqueued something"
+            for v, graph in enumerate(graphs):
+                check(replay(pw, ctx, bufs, graph, side, 1), pw.want(v, 1), ("graph of member", v))
+            del graphs, graph
+            ctx.reserve_program(G_QUERIES + 1, 3, 2)
+            check(run_member(ctx, pw, bufs, 4, 0), pw.want(4), "P4 after the growing reservation")
+        ctx.set_stream(None)
+
+
+def test_g4_the_host_form_grows_the_reservation_by_itself(programs):
+    """P0 through the device form; the host form of wide_uneven_program with more queries and nodes than were reserved
+    (it reserves for itself: a growing reservation, which forgets every image); P0 is then not resident (refused inside
+    a capture), an eager call uploads it again and gives its words, and it is resident after that"""
+    pw, side = programs, torch.cuda.Stream()
+    with pkg().Context(pw.p) as ctx:
+        with torch.cuda.stream(side):
+            bufs = program_buffers(ctx, pw)
+            check(run_member(ctx, pw, bufs, 0), pw.want(0), "P0 before")
+            side.synchronize()
+            got = ctx.cmux_program(pw.wide, pw.wide_sels, want="glwe")
+            check(got, pw.want("wide", G_QUERIES + 1), "the host form, four queries of ten nodes")
+            bufs.out.fill_(FILL)
+            side.synchronize()
+            _, err = probe(ctx, pw, bufs, 0, side)
+            refused_as_not_resident(ctx, bufs, err, "P0 after the host form grew the workspace")
+            check(run_member(ctx, pw, bufs, 0), pw.want(0), "P0 uploaded again")
+            side.synchronize()
+            graph0, err = probe(ctx, pw, bufs, 0, side)
+            assert err is None, str(err)
+            check(replay(pw, ctx, bufs, graph0, side, 2), pw.want(0, 2), "P0's graph in the grown workspace")
+        ctx.set_stream(None)
+
+
+def test_g5_mode_flips_with_a_resident_image(programs):
+    """P0 (and wide_uneven_program, whose plan a split really changes) resident on one context while the alignment goes
+    on and off, the split to 2 and back to automatic, the stream to a second torch stream and to the context's own, and a
+    bootstrapping key is loaded: after each the words are program_model's under the alignment in force.  Graphs
+    captured before the split changed replay the same words after it"""
+    pw, side, other = programs, torch.cuda.Stream(), torch.cuda.Stream()
+    p, nq = pw.p, G_QUERIES
+    assert not np.array_equal(pw.want(0, 0, False), pw.want(0, 0, True))
+    rng = np.random.default_rng(75)
+    with pkg().Context(p) as ctx:
+        with torch.cuda.stream(side):
+            bufs = program_buffers(ctx, pw, pw.wide.n_nodes, len(pw.wide.outputs))
+            wide = SimpleNamespace(prepared=tprog.prepare(ctx, pw.wide_sels[:nq]).contiguous(), terminals=dev(pw.wide.arrays()[1]),
+                                   out=torch.full((nq, 4, p.k + 1, p.N), FILL, dtype=torch.int32, device=DEV))
+
+            def run_wide():
+                wide.out.fill_(FILL)
+                ctx.cmux_program(pw.wide, wide.prepared, want="glwe", terminals=wide.terminals, out=wide.out)
+                return host(wide.out)
+
+            check(run_member(ctx, pw, bufs, 0), pw.want(0), "P0, literal")
+            check(run_wide(), pw.want("wide", nq), "wide, literal, automatic split")
+            plan_auto = ctx.program_plan(pw.wide, nq)
+            side.synchronize()
+            graph0, err = probe(ctx, pw, bufs, 0, side)
+            assert err is None, str(err)
+            graph_wide = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph_wide, stream=side):
+                ctx.cmux_program(pw.wide, wide.prepared, want="glwe", terminals=wide.terminals, out=wide.out)
+            for aligned in (True, False):
+                ctx.set_decomposer_alignment(aligned)
+                check(run_member(ctx, pw, bufs, 0, 0), pw.want(0, 0, aligned), ("P0, aligned", aligned))
+            ctx.set_program_split(2)
+            print(f"wide_uneven_program, {nq} queries: automatic {plan_auto}, split 2 {ctx.program_plan(pw.wide, nq)}")
+            assert ctx.program_plan(pw.wide, nq) == {"launches": 4, "teams_per_query": 2}
+            check(run_member(ctx, pw, bufs, 0), pw.want(0), "P0, split 2")
+            check(run_wide(), pw.want("wide", nq), "wide, split 2")
+            check(replay(pw, ctx, bufs, graph0, side, 1), pw.want(0, 1), "P0's graph, captured before the split changed")
+            wide.out.fill_(FILL)
+            graph_wide.replay()
+            side.synchronize()
+            check(host(wide.out), pw.want("wide", nq), "the wide graph, captured before the split changed")
+            ctx.set_program_split(0)
+            assert ctx.program_plan(pw.wide, nq) == plan_auto
+            check(run_wide(), pw.want("wide", nq), "wide, automatic again")
+            side.synchronize()
+        with torch.cuda.stream(other):
+            check(run_member(ctx, pw, bufs, 0, 0), pw.want(0), "P0 on a second torch stream")
+            other.synchronize()
+        ctx.set_stream(None)
+        check(ctx.cmux_program(pw.family[0], pw.sels[2], want="glwe"), pw.want(0, 2), "P0, host form on the context's own stream")
+        ctx.load_bootstrapping_key(rand_u32(rng, p.bsk_shape()), rand_u32(rng, p.ksk_shape()))
+        check(ctx.cmux_program(pw.family[0], pw.sels[3], want="glwe"), pw.want(0, 3), "P0 after a key was loaded")
+        with torch.cuda.stream(side):
+            check(run_member(ctx, pw, bufs, 0, 0), pw.want(0), "P0, device form, back on the first stream")
+            check(replay(pw, ctx, bufs, graph0, side, 2), pw.want(0, 2), "P0's graph at the end")
+        ctx.set_stream(None)
+
+
+def test_g6_one_context_many_features(programs):
+    """host forms on one context, each regrowing or reusing what the one before left: a small program; table_write with
+    log2 N + 3 address bits (24 GGSWs, a large staging area); a larger program; table_lookup_glwe of what was written;
+    demux_tree of depth 3 with the height forced to 1, then automatic; a program through the device form.  Programs
+    against program_model, the rest against clear_model_demux"""
+    pw = programs
+    p, pbs = pw.p, pw.pbs
+    rng = np.random.default_rng(76)
+    D = p.glwe_poly_degree + 3
+    sel = tprog.edge_mix(rng, (2, D, p.R, p.k + 1, p.N), 1)
+    values = tprog.edge_mix(rng, (2, 1, p.k + 1, p.N), 2)
+    table = tprog.edge_mix(rng, (2, 1, 8, p.k + 1, p.N), 3)
+    written = np.stack([cd.write_model(sel[q], values[q], table[q], *pbs) for q in range(2)])
+    looked = np.stack([cd.lookup_glwe_model(sel[q], written[q], *pbs) for q in range(2)])
+    x = tprog.edge_mix(rng, (2, 1, p.k + 1, p.N), 4)
+    leaves = np.stack([cd.demux_model(sel[q, :3], x[q], *pbs) for q in range(2)])
+    with pkg().Context(p) as ctx:
+        check(ctx.cmux_program(pw.family[0], pw.sels[0], want="glwe"), pw.want(0), "a small program")
+        got = ctx.table_write(sel, values, table.copy())
+        check(got, written, "table_write")
+        check(ctx.cmux_program(pw.wide, pw.wide_sels, want="glwe"), pw.want("wide", G_QUERIES + 1), "a larger program")
+        check(ctx.table_lookup_glwe(sel, got), looked, "table_lookup_glwe of what was written")
+        for h in (1, 0):
+            ctx.set_demux_subtree_height(h)
+            plan = ctx.demux_plan(2, 3)
+            assert h == 0 or plan == {"subtree_height": 1, "launches": 3}, plan
+            check(ctx.demux_tree(np.ascontiguousarray(sel[:, :3]), x), leaves, ("demux_tree, height", h, plan))
+        check(ctx.cmux_program(pw.family[0], pw.sels[1], want="glwe"), pw.want(0, 1), "the small program again")
+        bufs = program_buffers(ctx, pw)
+        check(run_member(ctx, pw, bufs, 1), pw.want(1), "a program through the device form")
         ctx.set_stream(None)

@@ -1,7 +1,9 @@
 """Encrypted branching programs on the GPU (-m gpu): tfhe_cmux_program[_device] -- every bit against the node-by-node
 composition of existing entries (tfhe_cmux_prepared_device, tfhe_glwe_mul_monomial_batch), the lookup as a program
 against tfhe_table_lookup, plan independence, host / device / captured-graph forms, the reservation, identity I16 at full
-size, real noise against the predicted bound, and the refusals.  Each call runs once; nothing loops on failure."""
+size, real noise against the predicted bound, the refusals, plans wider than two teams per query on all six ring shapes
+(section 8) and the programs the shipped constructors emit, every bit and exhaustively under I16 (section 9).  Each call
+runs once; nothing loops on failure."""
 import ctypes as C
 import math
 
@@ -464,3 +466,203 @@ def test_refusals():
     # NULL contexts
     assert run(None, None, sz(1), sz(1), sz(1), None, sz(0), None, sz(1), None, sz(1), None, None) == INV
     assert lib.tfhe_context_reserve_program(None, sz(1), sz(1), sz(1)) == INV
+
+
+# ------------------------------------------------------------------------------------------------ 8: wide and uneven plans
+ALL_SHAPES = [(1, 9), (1, 10), (1, 11), (2, 9), (2, 10), (2, 11)]  # (k, log2 N): every instantiated ring shape
+
+
+def expected_plan(widths, parts):
+    """The plan tfhe_hip.h states, for a program with ONE output (what tfhe_debug_program_plan reports), parts >= 1.  The
+    levels go out in turn; a level of c nodes is dealt to up to `parts` teams, and no more than it has nodes:
+    min(c, parts); consecutive levels of one team are merged into one launch; values that cross teams cross a launch
+    boundary, so the output of a split last level -- written by another team than the one that copies it out -- needs
+    a launch of its own (one output: one team), while after a one-team level it rides on that launch.  parts beyond
+    the widest level change nothing.  -> what program_plan returns: the launches and the most teams one gives a query"""
+    assert parts >= 1
+    launches, widest, last = 0, 1, 0
+    for c in widths:
+        teams = min(c, parts)
+        if not (teams == 1 and last == 1):
+            launches += 1
+        last = teams
+        widest = max(widest, teams)
+    if last != 1:
+        launches += 1
+    return {"launches": launches, "teams_per_query": widest}
+
+
+# parts -> (launches, teams per query) of level widths 5, 3, 2, worked out by hand from the header: each of the three
+# levels is split, the outputs follow on a launch of their own, and 8 teams are no more than the widest level's 5 --
+# nor are 2^31 - 1, the most tfhe_context_set_program_split accepts: the launches are sized after the clamp, so that
+# value must not run into the limit of teams per launch
+MAX_PARTS = (1 << 31) - 1
+WIDE_PLANS = {1: (1, 1), 2: (4, 2), 3: (4, 3), 4: (4, 4), 8: (4, 5), MAX_PARTS: (4, 5)}
+
+
+def test_expected_plan_is_the_headers_rule():
+    for parts, (launches, teams) in WIDE_PLANS.items():
+        assert expected_plan([5, 3, 2], parts) == {"launches": launches, "teams_per_query": teams}, parts
+    # test_the_words_do_not_depend_on_the_plan's numbers, and the lookup as a program (one node per level: one launch)
+    assert expected_plan([2, 2, 1, 2, 2, 1, 1], 2) == expected_plan([2, 2, 1, 2, 2, 1, 1], 4) == {"launches": 6, "teams_per_query": 2}
+    assert expected_plan([1] * 12, 8) == {"launches": 1, "teams_per_query": 1}
+    assert expected_plan([], 4) == {"launches": 1, "teams_per_query": 1}
+
+
+def check_against(ctx, prog, cases, parts_list, plans, tag, host_parts=None):
+    """every (selectors, queries, want) of `cases` through the device form under every parts of parts_list -- GLWE and
+    extracted LWE outputs, the plan of every fixed parts against `plans` -- and (host_parts) the host form once"""
+    ctx.reserve_program(max(q for _, q, _ in cases), prog.n_nodes, len(prog.outputs))
+    for sel, queries, want in cases:
+        prepared = prepare(ctx, sel)
+        for parts in parts_list:
+            ctx.set_program_split(parts)
+            plan = ctx.program_plan(prog, queries)
+            if parts:
+                assert plan == plans[parts], tag + (queries, parts, plan)
+            else:
+                assert 1 <= plan["launches"] <= prog.depth + 1 and 1 <= plan["teams_per_query"] <= max(prog.level_widths()), plan
+            glwe, lwe = ctx.cmux_program(prog, prepared, queries=queries, want="both")
+            bad = np.argwhere(host(glwe) != want)
+            assert bad.size == 0, tag + (sel.shape[0], queries, parts, "device", bad[:4].tolist())
+            assert np.array_equal(host(lwe), cl.sample_extract0(want)), tag + (sel.shape[0], queries, parts, "device, lwe")
+        ctx.set_stream(None)
+    if host_parts is not None:
+        ctx.set_program_split(host_parts)
+        sel, queries, want = cases[-1]
+        glwe, lwe = ctx.cmux_program(prog, sel, queries=queries, want="both")
+        assert np.array_equal(glwe, want), tag + ("host", host_parts)
+        assert np.array_equal(lwe, cl.sample_extract0(want)), tag + ("host, lwe", host_parts)
+
+
+@pytest.mark.parametrize("pbs,aligned", DECOMPOSERS)
+@pytest.mark.parametrize("k,logn", ALL_SHAPES)
+def test_wide_and_uneven_plans_give_the_composition(k, logn, pbs, aligned):
+    """clear_model_program.wide_uneven_program (level widths 5, 3, 2, nodes not sorted by level, four outputs), arbitrary
+    (random / edge-word) GGSWs: 1 query, 3 queries with their own selectors, 3 queries on shared selectors.  The
+    composition is evaluated once (AUTO backend; at k = 1, N = 512 also against the clear model) and every backend that
+    admits the set must reproduce it in the device form under parts automatic, 1, 2, 3, 4, 8 and 2^31 - 1, and in the
+    host form at parts 3.  What runs here and nowhere else: shares of unequal length (3, 2 of level 1 at two teams), an empty share
+    (2, 2, 1, 0 at four), a split last level with the outputs on a launch of their own (four outputs as 2, 2, 0 at three
+    teams: one idle), nodes with rot != 0 reading a value another team wrote one launch earlier, a value two launches
+    old, and the host's sort by level moving a node.  program_plan must report WIDE_PLANS."""
+    p = params(k, logn, pbs)
+    rng = np.random.default_rng(8000 * logn + 100 * k + aligned)
+    prog = cp.wide_uneven_program(p.N)
+    arrays = prog.arrays()
+    assert prog.level_widths() == [5, 3, 2] and len(prog.outputs) == 4
+    plans = {parts: {"launches": l, "teams_per_query": t} for parts, (l, t) in WIDE_PLANS.items()}
+    shape = (prog.n_inputs, p.R, k + 1, p.N)
+    one, own, shared = edge_mix(rng, (1,) + shape, 1), edge_mix(rng, (3,) + shape, 2), edge_mix(rng, (1,) + shape, 3)
+    with context(p, "auto", aligned) as ref:
+        cases = [(one, 1, compose(ref, arrays, one, 1)), (shared, 3, compose(ref, arrays, shared, 3)),
+                 (own, 3, compose(ref, arrays, own, 3))]
+    if k == 1 and logn == 9:
+        model = np.stack([cp.program_model(*arrays, own[q], k, p.log_p, *pbs, aligned, p.padding_bits) for q in range(3)])
+        assert np.array_equal(cases[2][2], model), "composition vs model"
+    assert np.array_equal(cases[1][2][0], cases[1][2][2])
+    admitted = []
+    for b in BACKENDS:
+        ctx = context(p, b, aligned)
+        if ctx is None:
+            continue
+        with ctx:
+            if not admitted:
+                for parts in (0, 1, 2, 3, 4, 8, MAX_PARTS):
+                    ctx.set_program_split(parts)
+                    print(f"widths 5, 3, 2, parts {parts}: {ctx.program_plan(prog, 1)} for 1 query, {ctx.program_plan(prog, 3)} for 3")
+            check_against(ctx, prog, cases, (0, 1, 2, 3, 4, 8, MAX_PARTS), plans, (b,), host_parts=3)
+        admitted.append(b)
+    print(f"k = {k}, N = {p.N}, {pbs} {'aligned' if aligned else 'literal'}: admitted by {admitted}")
+    assert admitted
+
+
+# ------------------------------------------------------------------------------------------------ 9: the shipped constructors
+TABLE_SEED = 25  # the reduced BDD of this table has level widths 27, 16, 8, 4, 2, 1 (58 nodes)
+
+
+def truth_table(log_p=4):
+    return np.random.default_rng(TABLE_SEED).integers(0, 1 << log_p, size=64).astype(np.uint32)
+
+
+def every_bit_of_a_truth_table_program(k, logn):
+    """from_truth_table of a random D = 6 table of 4-bit entries, three queries on arbitrary selectors, every admitting
+    backend at parts automatic, 1, 2, 4 and 8, bit for bit against the composition; the plan against expected_plan"""
+    pbs, aligned = (7, 3), True
+    p = params(k, logn, pbs)
+    prog = bp.from_truth_table(truth_table(), 6, p.N)
+    widths = prog.level_widths()
+    widest = max(widths)
+    # parts = 8: shares of ceil(widest / 8), and the last team's share starts at or past the end of the level
+    assert widest > 8 and -(-widest // 8) * 7 >= widest, widths
+    rng = np.random.default_rng(9000 * logn + k)
+    own = edge_mix(rng, (3, prog.n_inputs, p.R, k + 1, p.N), 4)
+    with context(p, "auto", aligned) as ref:
+        cases = [(own, 3, compose(ref, prog.arrays(), own, 3))]
+    plans = {parts: expected_plan(widths, parts) for parts in (1, 2, 4, 8)}
+    print(f"level widths {widths}: plans {plans}")
+    admitted = []
+    for b in BACKENDS:
+        ctx = context(p, b, aligned)
+        if ctx is None:
+            continue
+        with ctx:
+            check_against(ctx, prog, cases, (0, 1, 2, 4, 8), plans, (b,))
+        admitted.append(b)
+    print(f"k = {k}, N = {p.N}: admitted by {admitted}")
+    assert admitted
+
+
+def every_address_exactly(prog, bits, values):
+    """I16 with no tolerance: k = 1, N = 1024, the decomposer that ignores no bits ((8, 4) literal: 8 | 32, 8 * 4 = 32),
+    noise-free selectors, one query per row of `bits`; parts automatic and 4, every admitting backend.  The phase of
+    every output GLWE is exactly encode(values[row]) in coefficient 0 and 0 in the other N - 1 coefficients."""
+    k, logn, pbs, aligned = 1, 10, (8, 4), False
+    assert cm.ignored_bits(*pbs) == 0 and 32 % pbs[0] == 0
+    p = params(k, logn, pbs, log_p=4)
+    bits = np.asarray(bits)
+    queries = bits.shape[0]
+    assert bits.shape == (queries, prog.n_inputs) and len(values) == queries
+    g = gen(90 + queries)
+    S = torch.randint(0, 2, (k, p.N), generator=g, device=DEV, dtype=torch.int64)
+    want = torch.zeros((queries, p.N), dtype=torch.int64, device=DEV)
+    want[:, 0] = torch.tensor([int(v) << (32 - p.log_p - p.padding_bits) for v in values], dtype=torch.int64, device=DEV)
+    raw = noise_free_selectors(p, g, bits, S, pbs, aligned)
+    admitted = []
+    for b in BACKENDS:
+        ctx = context(p, b, aligned)
+        if ctx is None:
+            continue
+        with ctx:
+            ctx.reserve_program(queries, prog.n_nodes, 1)
+            prepared = prepare(ctx, raw)
+            for parts in (0, 4):
+                ctx.set_program_split(parts)
+                out = cm.t_from_u32(ctx.cmux_program(prog, prepared, want="glwe"))
+                torch.cuda.synchronize()
+                err = (cm.t_glwe_phase(out[:, 0], S) - want) & 0xFFFFFFFF
+                err = torch.where(err >= 1 << 31, (1 << 32) - err, err)
+                print(f"{queries} rows, {b}, parts {parts} ({ctx.program_plan(prog, queries)}): max |phase - encode| = {int(err.max())}")
+                assert int(err.max()) == 0, (b, parts, err.nonzero()[:4].tolist())
+            ctx.set_stream(None)
+        admitted.append(b)
+    assert admitted
+
+
+@pytest.mark.parametrize("what", ["every-bit-k1-n1024", "every-bit-k2-n512", "table-all-64-addresses", "equal-all-256-pairs"])
+def test_truth_table_programs_run_every_address(what):
+    """What the shipped constructors emit, on the device.  (a) every bit of from_truth_table's program (level widths 27,
+    16, 8, 4, 2, 1: at parts = 8 shares of 4 with an empty one) at (k = 1, N = 1024) and (k = 2, N = 512).  (b) I16
+    exhaustively: that table at all 64 addresses, one query each, and equal(4) at all 256 input pairs: every phase is
+    exactly the encoded entry / a == b in coefficient 0 and 0 elsewhere; no row is left out and the bound is 0 (as
+    test_i16_at_full_size_on_the_device establishes for this decomposer)."""
+    if what.startswith("every-bit"):
+        every_bit_of_a_truth_table_program(*{"every-bit-k1-n1024": (1, 10), "every-bit-k2-n512": (2, 9)}[what])
+    elif what == "table-all-64-addresses":
+        table = truth_table()
+        prog = bp.from_truth_table(table, 6, 1024)
+        assert prog.n_nodes == 58 and prog.level_widths()[0] == 27
+        every_address_exactly(prog, [bp.bits_of(a, 6) for a in range(64)], table.tolist())
+    else:
+        pairs = [(a, b) for a in range(16) for b in range(16)]
+        every_address_exactly(bp.equal(4, 1024), [bp.interleave(a, b, 4) for a, b in pairs], [int(a == b) for a, b in pairs])
