@@ -682,6 +682,54 @@ inline LweCiphertext tree_lut(Engine& e, const std::vector<LweCiphertext>& digit
   e.check(tfhe_tree_lut_batch(e.raw(), ptrs.data(), d, 1, table.data(), 1, 1, out.data.data()));
   return out;
 }
+// ---- encrypted dense layers (tfhe_hip.h states the operations; first device only) ----
+// Dense(W, bias; x) for ONE query: x holds the I input ciphertexts (all of one length), weights [O][I] row-major int32,
+// bias [O] already ENCODED words or empty -> O ciphertexts of that length, out[o] = sum_i W[o][i] x[i] (+ bias[o] on the body)
+inline std::vector<LweCiphertext> dense(Engine& e, const std::vector<LweCiphertext>& x, const std::vector<int32_t>& weights,
+                                        const std::vector<uint32_t>& bias = {}) {
+  const size_t inputs = x.size();
+  if (inputs == 0 || weights.empty() || weights.size() % inputs != 0) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "weights [O][I]");
+  const size_t outputs = weights.size() / inputs, words = x[0].data.size();
+  if (!bias.empty() && bias.size() != outputs) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "bias [O]");
+  std::vector<uint32_t> flat;
+  flat.reserve(inputs * words);
+  for (const LweCiphertext& ct : x) {
+    if (ct.data.size() != words) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "LWE length");
+    flat.insert(flat.end(), ct.data.begin(), ct.data.end());
+  }
+  std::vector<uint32_t> res(outputs * words);
+  e.check(tfhe_lwe_dense_batch(e.raw(), flat.data(), 1, inputs, weights.data(), bias.empty() ? nullptr : bias.data(), outputs, words,
+                               res.data()));
+  std::vector<LweCiphertext> out;
+  for (size_t o = 0; o < outputs; ++o)
+    out.push_back(LweCiphertext{std::vector<uint32_t>(res.begin() + o * words, res.begin() + (o + 1) * words)});
+  return out;
+}
+// a whole layer for ONE query: out[o] = bootstrap(dense(x)[o]; test vector o mod tv_count); test_vectors holds one or O
+// un-encoded test vectors of N words (construct_test_from_lut); ciphertexts of n + 1 words
+inline std::vector<LweCiphertext> dense_bootstrap(Engine& e, const std::vector<LweCiphertext>& x, const std::vector<int32_t>& weights,
+                                                  const std::vector<uint32_t>& bias, const std::vector<uint32_t>& test_vectors) {
+  const TfheParams& p = e.params();
+  const size_t inputs = x.size(), words = size_t(p.lwe_dimension) + 1;
+  if (inputs == 0 || weights.empty() || weights.size() % inputs != 0) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "weights [O][I]");
+  const size_t outputs = weights.size() / inputs;
+  if (!bias.empty() && bias.size() != outputs) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "bias [O]");
+  if (test_vectors.size() != p.degree() && test_vectors.size() != outputs * p.degree())
+    throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "one or O test vectors of N words");
+  std::vector<uint32_t> flat;
+  flat.reserve(inputs * words);
+  for (const LweCiphertext& ct : x) {
+    if (ct.data.size() != words) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "LWE length");
+    flat.insert(flat.end(), ct.data.begin(), ct.data.end());
+  }
+  std::vector<uint32_t> res(outputs * words);
+  e.check(tfhe_dense_bootstrap_batch(e.raw(), flat.data(), 1, inputs, weights.data(), bias.empty() ? nullptr : bias.data(), outputs,
+                                     test_vectors.data(), test_vectors.size() / p.degree(), res.data()));
+  std::vector<LweCiphertext> out;
+  for (size_t o = 0; o < outputs; ++o)
+    out.push_back(LweCiphertext{std::vector<uint32_t>(res.begin() + o * words, res.begin() + (o + 1) * words)});
+  return out;
+}
 // bootstrapping_key_gen bootstrapping.rs:23-56; the generated key is also installed in the engine.
 // bmmp = true makes the key of the unrolled blind rotation instead (notes/BMMP Bootstrapping.md:22-24:
 // GGSW(s s'), GGSW(s (1-s')), GGSW(s' (1-s)) per pair of key bits; N = 512, even n).

@@ -548,6 +548,58 @@ int tfhe_lwe_linear_batch_device(tfhe_context *ctx, uint32_t c0, const uint32_t 
                                  const uint32_t *ct1, size_t batch, size_t words_per_ct,
                                  uint32_t *out);
 
+/* ---- encrypted dense layers (no reference counterpart) --------------------------------------------
+ * A clear integer matrix times a batch of LWE ciphertexts, and a whole layer (the product, then one programmable
+ * bootstrap per output) in one call: the discretised neural-network layer of FHE-DiNN (Bourse, Minelli, Minihold,
+ * Paillier 2018), the linear half of every "PBS as activation" pipeline.
+ *
+ *   Dense(W, bias; x):  out[q][o][c] = ( sum_{i<I} (u32)W[o][i] * x[q][i][c] )  mod 2^32      c < words_per_ct
+ *                       out[q][o][words_per_ct-1] += bias[o]                                  (bias may be NULL)
+ *
+ * x [queries][I][words_per_ct]; W [O][I] int32, any value (two's complement is exact mod 2^32); bias [O] already
+ * ENCODED words (as tfhe_lwe_encrypt_batch's plaintexts); out [queries][O][words_per_ct].  words_per_ct is explicit
+ * as in tfhe_lwe_linear_batch: both boundary dimensions (n+1, k N + 1) and any other LWE size are served.  With I = 2
+ * a row (c0, c1) of W is tfhe_lwe_linear_batch's c0*ct0 + c1*ct1.  Phases are linear: for any key,
+ * phase(out[q][o]) = sum_i W[o][i] phase(x[q][i]) + bias[o] mod 2^32 exactly; a row of W multiplies the input
+ * noise's variance by its squared Euclidean norm.
+ *
+ * Plan.  One launch of a tiled wrapping-u32 GEMM (csrc/lwe_dense.h): a workgroup owns one query, 32 outputs and 128
+ * columns.  A call with too few tiles to fill the chip splits the inputs over several workgroups, whose partial sums
+ * are added into the zeroed output (a memset node on the context's stream: the call stays capturable).
+ * tfhe_context_set_dense_split(parts) fixes the split (1: none; 0: automatic); it is held to at most one split per
+ * 16 inputs.  The output words never depend on it.  tfhe_debug_dense_plan reports the splits and the workgroups of
+ * the launch.
+ *
+ * tfhe_dense_bootstrap_batch: lwe_out[q][o] = bootstrap(Dense(x)[q][o]; tv[o mod tv_count]), tv_count 1 or O, test
+ * vectors [tv_count][N] un-encoded as for tfhe_bootstrap_batch.  x and lwe_out are at the context's boundary
+ * dimension in either bootstrap order (n+1 words, or k N + 1 after tfhe_context_set_bootstrap_order(ctx, 1)); the
+ * bootstraps are tfhe_bootstrap_batch's, [queries * O] of them.  The _device form runs in the workspace of
+ * tfhe_context_reserve_dense(max_queries, max_outputs): the layer's pre-activations, one test vector per bootstrap
+ * (per-neuron test vectors are copied out, one per (query, neuron)) and what a bootstrap of max_queries * max_outputs
+ * rows needs: 4 max_queries max_outputs (words + N) bytes at the larger boundary dimension, plus tfhe_context_reserve
+ * (max_queries * max_outputs).  Smaller calls fit.  After the reservation the _device form allocates nothing, enqueues
+ * on the context's stream only and can be captured; a call beyond the reservation is refused and names its need in
+ * bytes.  The host form reserves for itself.
+ *
+ * Refused with TFHE_ERR_INVALID_ARGUMENT and a message in tfhe_last_error: queries, I, O or words_per_ct of 0, NULL x /
+ * W / out, out overlapping x, tv_count other than 1 or O, sizes whose tiles exceed one grid (queries *
+ * ceil(words_per_ct / 128) >= 2^31, O > 32 * 65535, I >= 2^31).  The fused form: TFHE_ERR_NO_KEY without a
+ * bootstrapping key, and TFHE_ERR_UNSUPPORTED wherever tfhe_bootstrap_batch is. */
+int tfhe_context_reserve_dense(tfhe_context *ctx, size_t max_queries, size_t max_outputs);
+int tfhe_context_set_dense_split(tfhe_context *ctx, unsigned parts);
+int tfhe_debug_dense_plan(tfhe_context *ctx, size_t queries, size_t inputs, size_t outputs, size_t words_per_ct,
+                          unsigned *splits, unsigned *workgroups);
+int tfhe_lwe_dense_batch(tfhe_context *ctx, const uint32_t *x, size_t queries, size_t inputs, const int32_t *weights,
+                         const uint32_t *bias, size_t outputs, size_t words_per_ct, uint32_t *out);
+int tfhe_lwe_dense_batch_device(tfhe_context *ctx, const uint32_t *x, size_t queries, size_t inputs, const int32_t *weights,
+                                const uint32_t *bias, size_t outputs, size_t words_per_ct, uint32_t *out);
+int tfhe_dense_bootstrap_batch(tfhe_context *ctx, const uint32_t *x, size_t queries, size_t inputs, const int32_t *weights,
+                               const uint32_t *bias, size_t outputs, const uint32_t *test_vector_poly, size_t tv_count,
+                               uint32_t *lwe_out);
+int tfhe_dense_bootstrap_batch_device(tfhe_context *ctx, const uint32_t *x, size_t queries, size_t inputs,
+                                      const int32_t *weights, const uint32_t *bias, size_t outputs,
+                                      const uint32_t *test_vector_poly, size_t tv_count, uint32_t *lwe_out);
+
 /* ---- test_vector.rs / boolean.rs ---------------------------------------------------------- */
 /* construct_test_from_lut: test_vector.rs:38-67 (host-side, no GPU).  out [N] */
 int tfhe_construct_test_from_lut(const tfhe_params *params, const uint32_t *lut, size_t lut_len,

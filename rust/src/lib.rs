@@ -79,6 +79,12 @@ extern "C" {
                                  acc_count: usize, rotation_offset: usize, lwe_out: *mut u32) -> c_int;
     fn tfhe_tree_lut_batch(ctx: *mut TfheContext, digits: *const *const u32, d: usize, batch: usize, table: *const u32,
                            table_sets: usize, tables: usize, lwe_out: *mut u32) -> c_int;
+    // encrypted dense layers (include/tfhe_hip.h)
+    fn tfhe_lwe_dense_batch(ctx: *mut TfheContext, x: *const u32, queries: usize, inputs: usize, weights: *const i32,
+                            bias: *const u32, outputs: usize, words_per_ct: usize, out: *mut u32) -> c_int;
+    fn tfhe_dense_bootstrap_batch(ctx: *mut TfheContext, x: *const u32, queries: usize, inputs: usize, weights: *const i32,
+                                  bias: *const u32, outputs: usize, test_vector_poly: *const u32, tv_count: usize,
+                                  lwe_out: *mut u32) -> c_int;
     fn tfhe_cmux_batch(ctx: *mut TfheContext, ggsw: *const u32, ggsw_count: usize, ct0: *const u32,
                        ct1: *mut u32, batch: usize, glwe_out: *mut u32) -> c_int;
     fn tfhe_gate_batch(ctx: *mut TfheContext, truth: *const u32, ct0: *const u32, ct1: *const u32,
@@ -403,6 +409,42 @@ pub fn tree_lut(bk: &GpuBootstrappingKey, digits: &Array2<u32>, table: &Array1<u
         tfhe_tree_lut_batch(bk.ctx, ptrs.as_ptr(), d, 1, table.as_slice().unwrap().as_ptr(), 1, 1,
                             out.as_slice_mut().unwrap().as_mut_ptr())
     }, "tree_lut");
+    out
+}
+
+/// Dense(W, bias; x): `x` (queries, I, words), `weights` (O, I), `bias` O already ENCODED words ->
+/// (queries, O, words), out[q][o] = sum_i W[o][i] x[q][i] wrapping, bias[o] added to the body (no reference counterpart).
+pub fn dense(bk: &GpuBootstrappingKey, x: &Array3<u32>, weights: &Array2<i32>, bias: Option<&Array1<u32>>) -> Array3<u32> {
+    let (queries, inputs, words) = x.dim();
+    let outputs = weights.nrows();
+    assert!(weights.ncols() == inputs && bias.map_or(true, |b| b.len() == outputs), "dense: weights (O, I), bias O words");
+    let mut out = Array3::<u32>::zeros((queries, outputs, words));
+    check(bk.ctx, unsafe {
+        tfhe_lwe_dense_batch(bk.ctx, x.as_slice().unwrap().as_ptr(), queries, inputs, weights.as_slice().unwrap().as_ptr(),
+                             bias.map_or(std::ptr::null(), |b| b.as_slice().unwrap().as_ptr()), outputs, words,
+                             out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "dense");
+    out
+}
+
+/// A whole layer: out[q][o] = bootstrap(dense(x)[q][o]; test vector o mod tv_count); `test_vectors` (1 or O, N)
+/// un-encoded, ciphertexts of n+1 words.
+pub fn dense_bootstrap(bk: &GpuBootstrappingKey, x: &Array3<u32>, weights: &Array2<i32>, bias: Option<&Array1<u32>>,
+                       test_vectors: &Array2<u32>) -> Array3<u32> {
+    let (queries, inputs, words) = x.dim();
+    let outputs = weights.nrows();
+    let n = 1usize << bk.params.glwe_poly_degree;
+    assert!(weights.ncols() == inputs && bias.map_or(true, |b| b.len() == outputs), "dense_bootstrap: weights (O, I), bias O words");
+    assert!(words == bk.params.lwe_dimension as usize + 1 && test_vectors.ncols() == n
+            && (test_vectors.nrows() == 1 || test_vectors.nrows() == outputs),
+            "dense_bootstrap: ciphertexts of n+1 words, 1 or O test vectors of N words");
+    let mut out = Array3::<u32>::zeros((queries, outputs, words));
+    check(bk.ctx, unsafe {
+        tfhe_dense_bootstrap_batch(bk.ctx, x.as_slice().unwrap().as_ptr(), queries, inputs, weights.as_slice().unwrap().as_ptr(),
+                                   bias.map_or(std::ptr::null(), |b| b.as_slice().unwrap().as_ptr()), outputs,
+                                   test_vectors.as_slice().unwrap().as_ptr(), test_vectors.nrows(),
+                                   out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "dense_bootstrap");
     out
 }
 

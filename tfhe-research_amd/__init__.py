@@ -185,6 +185,27 @@ def _is_torch(x) -> bool:
     return type(x).__module__.startswith("torch")
 
 
+_capture_gc_forced = False
+
+
+def _collect_before_captures():
+    """The device forms are made to be captured (torch.cuda.graph).  A dead Python cycle that holds a CUDAGraph, a tensor
+    or a context -- an exception kept in a local of a frame of its own traceback is enough -- is finalised whenever the
+    cyclic collector next runs, and a graph or an allocation released in the MIDDLE of a stream capture aborts the
+    process.  torch used to collect before every capture and now does so only under this switch; the binding turns it on
+    the first time it is handed a torch tensor, so the collector finds such cycles at the start of a capture instead."""
+    global _capture_gc_forced
+    if _capture_gc_forced:
+        return
+    _capture_gc_forced = True
+    try:
+        import torch
+        if hasattr(torch.compiler.config, "force_cudagraph_gc"):
+            torch.compiler.config.force_cudagraph_gc = True
+    except Exception:
+        pass
+
+
 def _dp(t):
     """device pointer of a contiguous 4-byte torch tensor"""
     assert t.is_cuda and t.is_contiguous() and t.element_size() == 4, "need contiguous 32-bit CUDA tensor"
@@ -394,6 +415,7 @@ class Context:
         """Bind to torch's current stream now.  The torch-tensor entry points do this by themselves on
         every call (_bind_torch); this is for callers that mix in host-pointer calls."""
         import torch
+        _collect_before_captures()
         self._bound_stream = torch.cuda.current_stream().cuda_stream
         self.set_stream(self._bound_stream)
 
@@ -403,6 +425,7 @@ class Context:
         like a torch op.  Re-binding only happens when the current stream changed since the last
         call (tfhe_context_set_stream then drains the stream it leaves: the workspace is shared)."""
         import torch
+        _collect_before_captures()
         s = torch.cuda.current_stream().cuda_stream
         if getattr(self, "_bound_stream", None) != s:
             self.set_stream(s)
@@ -1177,6 +1200,105 @@ class Context:
                                                 C.c_uint32(c1 & 0xFFFFFFFF), _hp(b) if b is not None else None,
                                                 C.c_size_t(rows.shape[0]), C.c_size_t(rows.shape[1]), _hp(res)))
         return res.reshape(a.shape)
+
+    # -- encrypted dense layers (include/tfhe_hip.h states the operations; nn.py builds networks) ----------------
+    def reserve_dense(self, max_queries: int, max_outputs: int):
+        """size the workspace of the device form of dense_bootstrap: pre-activations, one test vector per bootstrap and
+        what a bootstrap of max_queries * max_outputs rows needs (a maximum: smaller calls fit)"""
+        self._check(lib().tfhe_context_reserve_dense(self._h, C.c_size_t(max_queries), C.c_size_t(max_outputs)))
+
+    def set_dense_split(self, parts: int):
+        """shares the inputs of a dense call are dealt to (1: no split, 0: automatic); the bits do not depend on it"""
+        self._check(lib().tfhe_context_set_dense_split(self._h, C.c_uint(parts)))
+
+    def dense_plan(self, queries: int, inputs: int, outputs: int, words_per_ct: int) -> dict:
+        """how a dense call of this shape goes out (tfhe_debug_dense_plan)"""
+        splits, wgs = C.c_uint(), C.c_uint()
+        self._check(lib().tfhe_debug_dense_plan(self._h, C.c_size_t(queries), C.c_size_t(inputs), C.c_size_t(outputs),
+                                                C.c_size_t(words_per_ct), C.byref(splits), C.byref(wgs)))
+        return {"splits": splits.value, "workgroups": wgs.value}
+
+    def _dense_args(self, what, x, weights, bias, width=None):
+        """-> (x [queries][I][words], W [O][I] int32, bias [O] or None) as numpy arrays or, with x on the device, torch
+        tensors there (host weights / bias are uploaded on every call, which synchronises: pass device tensors in a loop)"""
+        on_device = _is_torch(x)
+        if on_device:
+            import torch
+            if x.dim() == 2:
+                x = x.unsqueeze(0)
+            if x.dim() != 3 or x.element_size() != 4 or x.is_floating_point() or not x.is_contiguous() or not x.is_cuda:
+                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: x [queries][I][words] (contiguous 32-bit integers, on the device) expected")
+
+            def dev(a, dtype, name):
+                if a is None:
+                    return None
+                if not _is_torch(a):
+                    a = torch.from_numpy(np.ascontiguousarray(a, dtype=dtype).view(np.int32)).to(x.device)
+                if a.element_size() != 4 or a.is_floating_point() or not a.is_contiguous() or a.device != x.device:
+                    raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: {name} must be a contiguous 32-bit integer tensor on {x.device}")
+                return a
+            weights, bias = dev(weights, np.int32, "weights"), dev(bias, np.uint32, "bias")
+        else:
+            x = _np(x)
+            if x.ndim == 2:
+                x = x[None]
+            weights = np.ascontiguousarray(weights, dtype=np.int32)
+            bias = None if bias is None else _np(bias).reshape(-1)
+        if len(x.shape) != 3 or len(weights.shape) != 2 or int(weights.shape[1]) != int(x.shape[1]) or \
+                (width is not None and int(x.shape[2]) != width):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: x [queries][I][{width or 'words'}] and weights [O][I] expected, got "
+                                                       f"{tuple(x.shape)} and {tuple(weights.shape)}")
+        if bias is not None and tuple(bias.shape) != (int(weights.shape[0]),):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: bias [O] expected, got {tuple(bias.shape)}")
+        return x, weights, bias
+
+    def dense(self, x, weights, bias=None, out=None):
+        """Dense(W, bias; x): out[q][o] = sum_i W[o][i] * x[q][i] (+ bias[o], already encoded, on the body), wrapping.
+        x [queries][I][words] (or [I][words]: one query), weights [O][I] int32 -> [queries][O][words]; any LWE size.
+        numpy: host form, blocks.  torch: on torch's current stream, `out` may name the result tensor."""
+        x, weights, bias = self._dense_args("dense", x, weights, bias)
+        q, i, words = (int(v) for v in x.shape)
+        o = int(weights.shape[0])
+        sizes = (C.c_size_t(q), C.c_size_t(i))
+        if _is_torch(x):
+            self._bind_torch()
+            out = self._lookup_out("dense", out, (q, o, words), x)
+            self._check(lib().tfhe_lwe_dense_batch_device(self._h, _dp(x), *sizes, C.c_void_p(weights.data_ptr()),
+                                                          _dp(bias) if bias is not None else None, C.c_size_t(o),
+                                                          C.c_size_t(words), _dp(out)))
+            return out
+        res = np.zeros((q, o, words), dtype=np.uint32)
+        self._check(lib().tfhe_lwe_dense_batch(self._h, _hp(x), *sizes, C.c_void_p(weights.ctypes.data),
+                                               _hp(bias) if bias is not None else None, C.c_size_t(o), C.c_size_t(words), _hp(res)))
+        return res
+
+    def dense_bootstrap(self, x, weights, bias, test_vector_poly, out=None):
+        """A whole layer: out[q][o] = bootstrap(Dense(W, bias; x)[q][o]; tv[o mod tv_count]).  x [queries][I][io_dim + 1] at
+        the context's boundary dimension, test_vector_poly [N] or [O][N] (un-encoded, as for bootstrap) ->
+        [queries][O][io_dim + 1].  numpy: host form, blocks.  torch: in the workspace of reserve_dense, enqueues only."""
+        x, weights, bias = self._dense_args("dense_bootstrap", x, weights, bias, self.io_dim + 1)
+        q, i, words = (int(v) for v in x.shape)
+        o = int(weights.shape[0])
+        tv = test_vector_poly if _is_torch(test_vector_poly) else _np(test_vector_poly)
+        n_tv = 1 if len(tv.shape) == 1 else int(tv.shape[0])
+        if int(tv.shape[-1]) != self.params.N or len(tv.shape) > 2:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"dense_bootstrap: test vectors [N] or [O][N] expected, got {tuple(tv.shape)}")
+        sizes = (C.c_size_t(q), C.c_size_t(i))
+        if _is_torch(x):
+            import torch
+            self._bind_torch()
+            if not _is_torch(tv):
+                tv = torch.from_numpy(tv.view(np.int32)).to(x.device)
+            out = self._lookup_out("dense_bootstrap", out, (q, o, words), x)
+            self._check(lib().tfhe_dense_bootstrap_batch_device(self._h, _dp(x), *sizes, C.c_void_p(weights.data_ptr()),
+                                                                _dp(bias) if bias is not None else None, C.c_size_t(o), _dp(tv),
+                                                                C.c_size_t(n_tv), _dp(out)))
+            return out
+        res = np.zeros((q, o, words), dtype=np.uint32)
+        self._check(lib().tfhe_dense_bootstrap_batch(self._h, _hp(x), *sizes, C.c_void_p(weights.ctypes.data),
+                                                     _hp(bias) if bias is not None else None, C.c_size_t(o), _hp(tv),
+                                                     C.c_size_t(n_tv), _hp(res)))
+        return res
 
     def lut_gate(self, truth, cts, out=None):
         """Gate of m = len(cts) inputs (notes/Boolean Gates.md:2-11): one PBS of sum_i 2^i * cts[i]

@@ -598,7 +598,7 @@ void tfhe_context_destroy(tfhe_context* ctx) {
                   ctx->d_lwe_big, ctx->d_lwe_out, ctx->d_lwe_ks, ctx->d_glwe_a, ctx->d_glwe_b, ctx->d_glwe_c,
                   ctx->d_tv,     ctx->d_misc,   ctx->d_ggsw_tmp, ctx->d_ggsw_raw,
                   ctx->d_key_tmp, ctx->d_pksk, ctx->d_pack_cols, ctx->d_lookup_ws, ctx->d_tree_ws,
-                  ctx->d_demux_ws, ctx->d_program_ws};
+                  ctx->d_demux_ws, ctx->d_program_ws, ctx->d_dense_ws};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& g : ctx->gate_tvs)
@@ -1800,6 +1800,167 @@ int tfhe_lwe_linear_batch(tfhe_context* ctx, uint32_t c0, const uint32_t* ct0, u
   if (c1) TFHE_TRY(s.upload(kCt1, ct1));
   TFHE_TRY(tfhe_lwe_linear_batch_device(ctx, c0, s[kCt0], c1, c1 ? s[kCt1] : nullptr, batch, words_per_ct, s[kOut]));
   return s.download_and_wait(kOut, out);
+}
+
+// ---------------------------------------------------------------------------------- encrypted dense layers
+// include/tfhe_hip.h states the operations, lwe_dense.h::dense_tile the tiling, kernels.hip::dense_plan_for the plan.
+namespace {
+
+struct DenseShape {
+  size_t queries, inputs, outputs, words;
+};
+
+// everything about a dense call that can be refused without looking at the device; -> the plan
+int check_dense(tfhe_context* ctx, const DenseShape& d, launch::DensePlanInfo* plan) {
+  if (d.queries == 0 || d.inputs == 0 || d.outputs == 0 || d.words == 0)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "queries, inputs, outputs and words_per_ct must be at least 1");
+  if (d.queries > kMaxBatch || d.inputs > kMaxBatch || d.outputs > kMaxBatch || d.words > kMaxBatch ||
+      !launch::dense_plan(d.queries, (u32)d.inputs, (u32)d.outputs, (u32)d.words, ctx->dense_parts, plan))
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "the tiles of the call exceed one grid: queries * ceil(words_per_ct / 128) and inputs must be below 2^31, outputs at "
+                "most 32 * 65535");
+  return TFHE_OK;
+}
+
+int check_dense_args(tfhe_context* ctx, const void* x, const void* w, const void* out, const DenseShape& d,
+                     launch::DensePlanInfo* plan) {
+  TFHE_TRY(check_present(ctx, {x, w, out}, 1, "null pointer"));
+  return check_dense(ctx, d, plan);
+}
+
+int enqueue_dense(tfhe_context* ctx, const u32* x, const DenseShape& d, const int32_t* w, const u32* bias, u32* out) {
+  HIP_TRY(ctx, launch::lwe_dense(ctx->stream, x, d.queries, (u32)d.inputs, w, bias, (u32)d.outputs, (u32)d.words, ctx->dense_parts, out));
+  return TFHE_OK;
+}
+
+// The fused layer's workspace: [pre-activations: one ciphertext per bootstrap][test vectors: [N] per bootstrap], the
+// first at the larger boundary dimension so that switching the bootstrap order keeps a reservation valid
+size_t dense_row_words(const tfhe_context* ctx) { return std::max(lwe_words(ctx), big_lwe_words(ctx)) + ctx->N; }
+
+int reserve_dense(tfhe_context* ctx, size_t rows) {
+  TFHE_TRY(reserve(ctx, rows));
+  if (rows <= ctx->dense_rows) return TFHE_OK;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->dense_rows = 0;
+  size_t have = 0;
+  if (ctx->d_dense_ws) HIP_TRY(ctx, hipFree(ctx->d_dense_ws));
+  ctx->d_dense_ws = nullptr;
+  TFHE_TRY(ensure(ctx, &ctx->d_dense_ws, &have, rows * dense_row_words(ctx)));
+  ctx->dense_rows = rows;
+  return TFHE_OK;
+}
+
+int check_dense_bootstrap_args(tfhe_context* ctx, const void* x, const void* w, const void* tv, const void* out, const DenseShape& d,
+                               size_t tv_count, launch::DensePlanInfo* plan) {
+  TFHE_TRY(check_present(ctx, {x, w, tv, out}, 1, "null pointer"));
+  TFHE_TRY(check_dense(ctx, d, plan));
+  if (tv_count != 1 && tv_count != d.outputs) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "tv_count must be 1 or outputs");
+  if ((double)d.queries * (double)d.outputs > (double)kMaxBatch)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "queries * outputs exceeds 2^31 - 1 (one workgroup per bootstrap)");
+  // the bootstraps' own refusals (a key, what the loaded key supports), as tfhe_bootstrap_batch states them
+  return check_rotate_args(ctx, x, tv, out, d.queries * d.outputs, 1);
+}
+
+}  // namespace
+
+int tfhe_context_reserve_dense(tfhe_context* ctx, size_t max_queries, size_t max_outputs) {
+  TFHE_TRY(check_ctx(ctx));
+  if (max_queries == 0 || max_outputs == 0 || (double)max_queries * (double)max_outputs > (double)kMaxBatch)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "max_queries and max_outputs must be at least 1, their product below 2^31");
+  return reserve_dense(ctx, max_queries * max_outputs);
+}
+
+int tfhe_context_set_dense_split(tfhe_context* ctx, unsigned parts) {
+  if (!ctx) return TFHE_ERR_INVALID_ARGUMENT;
+  if (parts > 65535u) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "parts must be at most 65535 (0: automatic)");
+  ctx->dense_parts = parts;
+  return TFHE_OK;
+}
+
+int tfhe_debug_dense_plan(tfhe_context* ctx, size_t queries, size_t inputs, size_t outputs, size_t words_per_ct, unsigned* splits,
+                          unsigned* workgroups) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {splits, workgroups}, 1, "null pointer"));
+  launch::DensePlanInfo plan{};
+  TFHE_TRY(check_dense(ctx, DenseShape{queries, inputs, outputs, words_per_ct}, &plan));
+  *splits = plan.splits;
+  *workgroups = (unsigned)std::min<size_t>(plan.workgroups, 0xFFFFFFFFu);
+  return TFHE_OK;
+}
+
+int tfhe_lwe_dense_batch_device(tfhe_context* ctx, const uint32_t* x, size_t queries, size_t inputs, const int32_t* weights,
+                                const uint32_t* bias, size_t outputs, size_t words_per_ct, uint32_t* out) {
+  TFHE_TRY(check_ctx(ctx));
+  const DenseShape d{queries, inputs, outputs, words_per_ct};
+  launch::DensePlanInfo plan{};
+  TFHE_TRY(check_dense_args(ctx, x, weights, out, d, &plan));
+  if (overlap(out, queries * outputs * words_per_ct, x, queries * inputs * words_per_ct))
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "out overlaps x: every output reads every input of its query");
+  return enqueue_dense(ctx, x, d, weights, bias, out);
+}
+
+int tfhe_lwe_dense_batch(tfhe_context* ctx, const uint32_t* x, size_t queries, size_t inputs, const int32_t* weights,
+                         const uint32_t* bias, size_t outputs, size_t words_per_ct, uint32_t* out) {
+  TFHE_TRY(check_ctx(ctx));
+  const DenseShape d{queries, inputs, outputs, words_per_ct};
+  launch::DensePlanInfo plan{};
+  TFHE_TRY(check_dense_args(ctx, x, weights, out, d, &plan));
+  if (overlap(out, queries * outputs * words_per_ct, x, queries * inputs * words_per_ct))
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "out overlaps x: every output reads every input of its query");
+  enum { kX, kW, kBias, kOut };
+  Staging s(ctx, {queries * inputs * words_per_ct, outputs * inputs, bias ? outputs : 0, queries * outputs * words_per_ct});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(kX, x));
+  TFHE_TRY(s.upload(kW, weights));
+  if (bias) TFHE_TRY(s.upload(kBias, bias));
+  TFHE_TRY(enqueue_dense(ctx, s[kX], d, reinterpret_cast<const int32_t*>(s[kW]), bias ? s[kBias] : nullptr, s[kOut]));
+  return s.download_and_wait(kOut, out);
+}
+
+int tfhe_dense_bootstrap_batch_device(tfhe_context* ctx, const uint32_t* x, size_t queries, size_t inputs, const int32_t* weights,
+                                      const uint32_t* bias, size_t outputs, const uint32_t* test_vector_poly, size_t tv_count,
+                                      uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  const DenseShape d{queries, inputs, outputs, io_words(ctx)};
+  launch::DensePlanInfo plan{};
+  TFHE_TRY(check_dense_bootstrap_args(ctx, x, weights, test_vector_poly, lwe_out, d, tv_count, &plan));
+  const size_t rows = queries * outputs;
+  if (rows > ctx->dense_rows || rows > ctx->ws_batch)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "the call needs " + std::to_string(rows * dense_row_words(ctx) * sizeof(u32)) + " bytes of dense workspace (" +
+                    std::to_string(queries) + " queries, " + std::to_string(outputs) + " outputs), " +
+                    std::to_string(ctx->dense_rows * dense_row_words(ctx) * sizeof(u32)) +
+                    " are reserved (tfhe_context_reserve_dense)");
+  u32* pre = ctx->d_dense_ws;
+  u32* tvs = ctx->d_dense_ws + ctx->dense_rows * (dense_row_words(ctx) - ctx->N);
+  TFHE_TRY(enqueue_dense(ctx, x, d, weights, bias, pre));
+  const u32* tv = test_vector_poly;
+  if (tv_count != 1) {  // the rotation reads bootstrap r's test vector at r * N: neuron r % O's
+    HIP_TRY(ctx, launch::dense_tile_rows(ctx->stream, test_vector_poly, outputs, rows, ctx->N, tvs));
+    tv = tvs;
+  }
+  return enqueue_bootstrap(ctx, pre, rows, tv, tv_count == 1 ? 1 : rows, ctx->d_lwe_big, lwe_out);
+}
+
+int tfhe_dense_bootstrap_batch(tfhe_context* ctx, const uint32_t* x, size_t queries, size_t inputs, const int32_t* weights,
+                               const uint32_t* bias, size_t outputs, const uint32_t* test_vector_poly, size_t tv_count,
+                               uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  const size_t io = io_words(ctx);
+  launch::DensePlanInfo plan{};
+  TFHE_TRY(check_dense_bootstrap_args(ctx, x, weights, test_vector_poly, lwe_out, DenseShape{queries, inputs, outputs, io}, tv_count, &plan));
+  TFHE_TRY(check_tv_host(ctx, test_vector_poly, tv_count * ctx->N));
+  TFHE_TRY(reserve_dense(ctx, queries * outputs));
+  enum { kX, kW, kBias, kTv, kOut };
+  Staging s(ctx, {queries * inputs * io, outputs * inputs, bias ? outputs : 0, tv_count * ctx->N, queries * outputs * io});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(kX, x));
+  TFHE_TRY(s.upload(kW, weights));
+  if (bias) TFHE_TRY(s.upload(kBias, bias));
+  TFHE_TRY(s.upload(kTv, test_vector_poly));
+  TFHE_TRY(tfhe_dense_bootstrap_batch_device(ctx, s[kX], queries, inputs, reinterpret_cast<const int32_t*>(s[kW]),
+                                             bias ? s[kBias] : nullptr, outputs, s[kTv], tv_count, s[kOut]));
+  return s.download_and_wait(kOut, lwe_out);
 }
 
 // ---------------------------------------------------------------------------------- encryption side

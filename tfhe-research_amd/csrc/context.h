@@ -65,6 +65,11 @@ struct tfhe_context {
   ProgramImage program_images[kProgramImages];
   unsigned long long program_clock = 0;
   unsigned program_parts = 0;  // teams per query of a split level (tfhe_context_set_program_split); 0: automatic
+  // Dense layer (tfhe_context_reserve_dense): the fused layer's pre-activations [dense_rows][max(n, k N) + 1], then one
+  // test vector [N] per bootstrap, for dense_rows = max_queries * max_outputs bootstraps
+  u32* d_dense_ws = nullptr;
+  size_t dense_rows = 0;
+  unsigned dense_parts = 0;   // shares of the inputs (tfhe_context_set_dense_split); 0: automatic
   // tree LUT (tfhe_context_reserve_tree_lut): per-rotation inputs, segment state, the levels' results and packed GLWEs
   u32* d_tree_ws = nullptr;
   size_t tree_ws_words = 0;

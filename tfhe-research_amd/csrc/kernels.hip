@@ -10,6 +10,7 @@
 #include <cstdlib>
 
 #include "launch.h"
+#include "lwe_dense.h"
 
 namespace tfhe {
 namespace {
@@ -968,6 +969,28 @@ __global__ void lwe_linear_kernel(u32 c0, const u32* ct0, u32 c1, const u32* ct1
     u32 v = c0 * ct0[i] + (ct1 ? c1 * ct1[i] : 0u);
     if (words_per_ct && (i % words_per_ct) == words_per_ct - 1) v += b_add;
     out[i] = v;
+  }
+}
+
+// ------------------------------------------------------------------------------ dense layer
+// lwe_dense.h::dense_tile states the operations and the tiling; this is its workgroup context on the device.
+struct DenseWorkgroup {
+  __device__ u32 thread() const { return threadIdx.x; }
+  __device__ u32 block_x() const { return blockIdx.x; }
+  __device__ u32 block_y() const { return blockIdx.y; }
+  __device__ u32 block_z() const { return blockIdx.z; }
+  __device__ void barrier() const { __syncthreads(); }
+  __device__ u32* lds() const { return reinterpret_cast<u32*>(g_smem); }
+  __device__ void atomic_add(u32* p, u32 v) const { atomicAdd(p, v); }
+};
+__global__ void __launch_bounds__(kDenseThreads) lwe_dense_kernel(DenseArgs a) { dense_tile(DenseWorkgroup(), a); }
+// out [count][words], out[r] = in[r % period]: bootstrap r = (query, neuron) of a fused layer gets neuron r % O's test vector
+__global__ void __launch_bounds__(256) dense_tile_rows_kernel(const u32* __restrict__ in, size_t period, size_t count, u32 words,
+                                                              u32* __restrict__ out) {
+  for (size_t r = blockIdx.x; r < count; r += gridDim.x) {
+    const u32* src = in + (r % period) * words;
+    u32* dst = out + r * words;
+    for (u32 i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
   }
 }
 
@@ -2093,6 +2116,65 @@ hipError_t lwe_linear(hipStream_t s, u32 c0, const u32* ct0, u32 c1, const u32* 
                       u32* out, size_t words_per_ct, u32 b_add) {
   hipLaunchKernelGGL(lwe_linear_kernel, dim3(grid_for(words, 256)), dim3(256), 0, s, c0, ct0, c1, ct1,
                      words, words_per_ct, b_add, out);
+  return hipGetLastError();
+}
+
+// How a dense call goes out.  A workgroup owns (query, kDenseOuts outputs, kDenseCols columns): `tiles` of them.  A call
+// with few tiles does not fill the chip, so the inputs are split over gridDim.z until the launch reaches
+// kDenseTargetWgs workgroups -- one resident round: 20 KiB of LDS per workgroup puts 8 on each of the 256 CUs -- with
+// a split of at least 64 inputs and at most 32 splits (the key switch's limits).  A forced split is only held to at
+// least one staged step (kDenseRows inputs) per split.  Shares are a multiple of kDenseRows, so the count is recomputed
+// from the share: no split is empty.  The rule looks at the shape of the call only; the bits do not depend on it.
+constexpr size_t kDenseTargetWgs = 2048;
+constexpr u32 kMaxGridYZ = 65535u;
+inline bool dense_plan_for(size_t queries, u32 inputs, u32 outputs, u32 words, u32 forced_splits, launch::DensePlanInfo* info) {
+  if (queries == 0 || inputs == 0 || outputs == 0 || words == 0) return false;
+  const size_t col_tiles = ((size_t)words + kDenseCols - 1) / kDenseCols, out_tiles = ((size_t)outputs + kDenseOuts - 1) / kDenseOuts;
+  if ((double)queries * (double)col_tiles > (double)kMaxGrid || out_tiles > kMaxGridYZ) return false;
+  const size_t tiles = queries * col_tiles * out_tiles;
+  size_t splits = forced_splits;
+  if (splits == 0) {
+    splits = kDenseTargetWgs / tiles;
+    const size_t max_splits = ((size_t)inputs + 63) / 64;
+    if (splits > max_splits) splits = max_splits;
+    if (splits > 32) splits = 32;
+  } else {
+    const size_t max_splits = ((size_t)inputs + kDenseRows - 1) / kDenseRows;
+    if (splits > max_splits) splits = max_splits;
+    if (splits > kMaxGridYZ) splits = kMaxGridYZ;
+  }
+  if (splits < 1) splits = 1;
+  const size_t share = (((size_t)inputs + splits - 1) / splits + kDenseRows - 1) / kDenseRows * kDenseRows;
+  splits = ((size_t)inputs + share - 1) / share;
+  info->splits = (u32)splits;
+  info->rows_per_split = (u32)share;
+  info->col_tiles = (u32)col_tiles;
+  info->out_tiles = (u32)out_tiles;
+  info->workgroups = tiles * splits;
+  return true;
+}
+
+bool dense_plan(size_t queries, u32 inputs, u32 outputs, u32 words, u32 forced_splits, DensePlanInfo* info) {
+  return dense_plan_for(queries, inputs, outputs, words, forced_splits, info);
+}
+
+hipError_t lwe_dense(hipStream_t s, const u32* x, size_t queries, u32 inputs, const i32* w, const u32* bias, u32 outputs,
+                     u32 words, u32 forced_splits, u32* out) {
+  DensePlanInfo plan;
+  if (!dense_plan_for(queries, inputs, outputs, words, forced_splits, &plan)) return hipErrorInvalidValue;
+  if (plan.splits > 1) {
+    hipError_t e = hipMemsetAsync(out, 0, queries * outputs * (size_t)words * sizeof(u32), s);
+    if (e != hipSuccess) return e;
+  }
+  const DenseArgs a{x, w, bias, out, inputs, outputs, words, plan.col_tiles, plan.rows_per_split, plan.splits, 0u};
+  const dim3 grid((unsigned)(queries * plan.col_tiles), plan.out_tiles, plan.splits);
+  hipLaunchKernelGGL(lwe_dense_kernel, grid, dim3(kDenseThreads), kDenseLdsWords * sizeof(u32), s, a);
+  return hipGetLastError();
+}
+
+hipError_t dense_tile_rows(hipStream_t s, const u32* in, size_t period, size_t count, u32 words, u32* out) {
+  const unsigned grid = (unsigned)(count < ((size_t)1 << 20) ? count : (size_t)1 << 20);
+  hipLaunchKernelGGL(dense_tile_rows_kernel, dim3(grid), dim3(256), 0, s, in, period, count, words, out);
   return hipGetLastError();
 }
 

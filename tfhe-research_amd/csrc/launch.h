@@ -146,6 +146,22 @@ hipError_t program_plan(int field, const PbsParams& P, size_t queries, const u32
 // one pass: queries * pass.parts workgroups.  pass.query_stride in 8-byte words here.
 hipError_t cmux_program_pass(hipStream_t s, int field, const PbsParams& P, const void* tw, const CmuxProgramPass& pass, size_t queries);
 
+// ---- dense layer (lwe_dense.h::dense_tile; the plan: kernels.hip::dense_plan_for)
+struct DensePlanInfo {
+  u32 splits;          // shares of the inputs (gridDim.z); more than one: the output is zeroed first, partial sums are added
+  u32 rows_per_split;  // inputs per share, a multiple of the staged rows
+  u32 col_tiles, out_tiles;
+  size_t workgroups;   // queries * col_tiles * out_tiles * splits
+};
+// forced_splits 0: automatic.  false: a size is 0 or the tiles exceed the grid (queries * col_tiles < 2^31, out_tiles < 2^16)
+bool dense_plan(size_t queries, u32 inputs, u32 outputs, u32 words, u32 forced_splits, DensePlanInfo* info);
+// out[q][o][c] = sum_i (u32)w[o][i] x[q][i][c] mod 2^32, bias[o] (may be null) added to word `words - 1` (a memset node
+// and one launch, or one launch).  hipErrorInvalidValue: see dense_plan
+hipError_t lwe_dense(hipStream_t s, const u32* x, size_t queries, u32 inputs, const i32* w, const u32* bias, u32 outputs,
+                     u32 words, u32 forced_splits, u32* out);
+// out [count][words], out[r] = in[r % period]: the per-neuron test vectors of a fused layer, one per bootstrap
+hipError_t dense_tile_rows(hipStream_t s, const u32* in, size_t period, size_t count, u32 words, u32* out);
+
 // elementwise helpers.  first_shift = bit of the lowest kept limb (PbsParams::first_shift)
 hipError_t decompose_words(hipStream_t s, u32 log_base, u32 levels, u32 first_shift, const u32* values,
                            size_t count, u32* digits /* [count][levels] */);
