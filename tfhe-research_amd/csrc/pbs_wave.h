@@ -18,6 +18,8 @@
 //   blind-rotation loop       bootstrapping.rs:79-105
 //   sample_extract (index 0)  bootstrapping.rs:122-156
 #pragma once
+#include <utility>
+
 #include "wave_ntt.h"
 
 namespace tfhe {
@@ -129,6 +131,50 @@ TFHE_HD u32 decompose_limb_fast(u32& v, u32 shift, u32 log_base, u32 carry_width
 #endif
 }
 
+// The same limb with the carry in a register of its own: four integer instructions (three on the lowest kept limb)
+// and `v` is only read.
+//   res   = bit-field extract of the limb, + carry (CARRY_IN = false on the lowest kept limb: the limbs below it are
+//           zero after rounding, the add is not emitted)
+//   digit = (res ^ B/2) - B/2, one xor-add.  On every res in [0, B] it is the literal rule: res < B/2 keeps res; B/2 <= res
+//           < B clears bit log_base-1 and subtracts B/2 once more, res - B; res = B (limb B-1 plus a carry) has that bit
+//           clear, B + B/2 - B/2 = B -- the limb that keeps B and emits no carry (decomposer.rs:53-65).  No width limit.
+//   carry = bit log_base-1 of res, a second bit-field extract.
+// `half` = B/2 (wave-uniform, hoisted by the caller).  A register per coefficient for the carry and one for -B/2 are
+// there to be had only in the kernels of short_hot_loop() below; the others keep decompose_limb_fast.
+TFHE_HD u32 bit_field(u32 v, u32 shift, u32 width) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_ubfe(v, shift, width);
+#else
+  return (v >> shift) & ((1u << width) - 1u);  // width < 32
+#endif
+}
+template <bool CARRY_IN>
+TFHE_HD u32 decompose_limb_reg(u32 v, u32 shift, u32 log_base, u32 half, u32& carry) {
+  u32 res = bit_field(v, shift, log_base);
+  if (CARRY_IN) res += carry;
+  carry = bit_field(res, log_base - 1, 1);
+#if defined(__HIP_DEVICE_COMPILE__)
+  // (spelled out: with half and -half both in scalar registers the compiler emits an xor and a subtract; VOP3 reads one)
+  u32 digit;
+  asm("v_xad_u32 %0, %1, %2, %3" : "=v"(digit) : "v"(res), "s"(half), "v"(0u - half));
+  return digit;
+#else
+  return (res ^ half) - half;
+#endif
+}
+
+// Which blind-rotation kernels run the short hot loop -- the operand read of RotatingOperand (below) and
+// decompose_limb_reg: the complex transform's team kernels of the BASELINE shapes up to N = 1024 -- one sample per team
+// at k = 1 (cfg2 / cfg4, cfg1's shape below the pair kernel's batches) and N = 512, k = 2 (cfg3: two samples per team) --
+// its wide team at those shapes and the pair kernel.  Decided per shape from the register allocation of a build with the short
+// loop everywhere (profiles/digit_chain_ab.txt): these shapes have the registers (the operand read gives back the 16
+// coefficient indices the carries take); N = 2048, N = 1024 with k = 2 and the prime fields' 16-coefficient arrays
+// spill them, and every kernel outside this list is instruction for instruction what it was.
+template <class F, int LOGN, int K, int G, int NS>
+constexpr bool short_hot_loop() {
+  return F::kLogShrink == 1 && G == 1 && ((K == 1 && NS == 1) || (LOGN == 9 && K == 2));
+}
+
 // utils.rs:13-33 with log_from = 32: round(v * 2N / 2^32) mod 2N
 TFHE_HD u32 switch_modulus_2n(u32 v, u32 log_n) {
   const u32 sh = 32u - (log_n + 1u);
@@ -144,6 +190,95 @@ TFHE_HD u32 monomial_coeff(const u32* poly, int j, u32 m) {
   const u32 v = poly[(j - deg) & (N - 1)];
   const u32 negate = flip ^ (u32)(j < deg);
   return negate ? (0u - v) : v;
+}
+
+// The rotating CMUX's operand, X^m acc - acc, read and rounded in one go: rounded(r) = round_value_fast(monomial_coeff(acc,
+// j, m) - acc[j]) for the coefficient j = r T + lane of a thread that holds every T-th coefficient of a polynomial in
+// LDS -- the same wrapping arithmetic with everything that does not depend on r hoisted.  With deg = m mod N and
+// flip = bit log N of m, coefficient j comes from index j - deg, plus N where j < deg (the wrap), and is negated where
+// wrap != flip.  A thread's wrapped coefficients are its first k = ceil((deg - lane) / T): once per operand that gives
+// `signs`, bit r of which says "coefficient r is negated", and the two addresses a word is read through -- lane - deg,
+// one of them N further on; which one depends on flip alone (r T is the read's immediate offset).  Per coefficient: the
+// sign mask s in {0, ~0} is a signed one-bit field of `signs`, the address a bit-wise select by s, +-x - a + half =
+// (x ^ s) + c with c = half - a - s is two subtracts and an xor-add, and the `keep` mask ends it: six instructions
+// where the literal form takes nine, no compare, and no register per coefficient index.
+template <int LOGN, int T>
+struct RotatingOperand {
+  static constexpr int N = 1 << LOGN;
+  static constexpr int kCount = N / T;  // coefficients per thread
+  static_assert(kCount <= 32 && (T & (T - 1)) == 0, "one bit per coefficient; T a power of two");
+#if defined(__HIP_DEVICE_COMPILE__)
+  // (an LDS address is a 32-bit number: the bit-wise select works on it)
+  typedef const __attribute__((address_space(3))) u32* LdsWords;
+  typedef u32 Words;
+  TFHE_HD static Words words_at(const u32* p) { return (u32)(size_t)(LdsWords)p; }
+  TFHE_HD static u32 read(Words negated, Words kept, u32 s, int index) {
+    return ((LdsWords)(size_t)((negated & s) | (kept & ~s)))[index];
+  }
+#else
+  typedef const u32* Words;
+  TFHE_HD static Words words_at(const u32* p) { return p; }
+  TFHE_HD static u32 read(Words negated, Words kept, u32 s, int index) { return (s ? negated : kept)[index]; }
+#endif
+  const u32* own;         // acc + lane: own[r T] = acc[j]
+  Words negated, kept;    // read through where the coefficient is negated / where it is not
+  u32 signs;
+  TFHE_HD RotatingOperand() {}
+  TFHE_HD RotatingOperand(const u32* acc, int lane, u32 m) {
+    const int deg = (int)(m & (u32)(N - 1));
+    const bool flip = ((m >> LOGN) & 1u) != 0;
+    int log_t = 0;
+    while ((1 << log_t) < T) ++log_t;
+    const int k = (deg - lane + (T - 1)) >> log_t;  // deg - lane > -T: k = 0 .. kCount
+    own = acc + lane;
+    // base[r T] = acc[j - deg] where j >= deg.  (`base` itself may lie below the array, by less than N words: it is only
+    // dereferenced with the index that brings it back inside; on the device it is a positive LDS offset, the
+    // accumulators sit above the exchange buffers.)
+    const u32* base = own - deg;
+    negated = words_at(base + (flip ? 0 : N));
+    kept = words_at(base + (flip ? N : 0));
+    signs = (u32)(~0ull << k) ^ (flip ? 0u : ~0u);  // the first k: wrapped
+  }
+  TFHE_HD u32 rounded(int r, RoundConsts rc) const {
+    u32 s = (u32)((int)(signs << (31 - r)) >> 31);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(s));  // s as a plain value: seen as a shift, `- s` below becomes a second shift and an add
+#endif
+    const u32 c = (rc.half - own[r * T]) - s;
+    return ((read(negated, kept, s, r * T) ^ s) + c) & rc.keep;
+  }
+};
+// NS of them behind one name, for the kernels that multiply NS samples in one pass
+template <int LOGN, int T, int NS>
+struct RotatingOperands {
+  const RotatingOperand<LOGN, T>* of;
+  TFHE_HD u32 rounded(int s, int r, RoundConsts rc) const { return of[s].rounded(r, rc); }
+};
+// Rounded coefficient r T + lane of an external product's operand: a source that has a rounded() of its own (above) is
+// asked for it, any other is a functor of the coefficient index (the last argument, 0, prefers the former).
+template <class Src, class = u32>
+struct reads_rounded : std::false_type {};
+template <class Src>
+struct reads_rounded<Src, decltype(std::declval<const Src&>().rounded(0, 0, RoundConsts{}))> : std::true_type {};
+template <class Src, class = u32>
+struct reads_rounded1 : std::false_type {};
+template <class Src>
+struct reads_rounded1<Src, decltype(std::declval<const Src&>().rounded(0, RoundConsts{}))> : std::true_type {};
+template <int T, class Src>
+TFHE_HD auto rounded_coeff(const Src& src, int s, int r, int, RoundConsts rc, int) -> decltype(src.rounded(s, r, rc)) {
+  return src.rounded(s, r, rc);
+}
+template <int T, class Src>
+TFHE_HD u32 rounded_coeff(const Src& src, int s, int r, int lane, RoundConsts rc, long) {
+  return round_value_fast(src(s, r * T + lane), rc);
+}
+template <int T, class Src>
+TFHE_HD auto rounded_coeff(const Src& src, int r, int, RoundConsts rc, int) -> decltype(src.rounded(r, rc)) {
+  return src.rounded(r, rc);
+}
+template <int T, class Src>
+TFHE_HD u32 rounded_coeff(const Src& src, int r, int lane, RoundConsts rc, long) {
+  return round_value_fast(src(r * T + lane), rc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -215,19 +350,22 @@ TFHE_HD void external_product_team_multi(const Ctx& c, const PbsParams& P, const
         if (SPLIT) accum_lo[SPLIT ? q : 0][SPLIT ? r : 0] = F::zero();
       }
 
-  // v[s][r]: rounded coefficient; once a limb has been consumed its bit log_base-1 carries the digit
-  // chain's carry to the next limb (decompose_limb_fast)
+  // v[s][r]: rounded coefficient.  The digit chain's carry into the next limb: once a limb has been consumed its bit
+  // log_base-1 carries it (decompose_limb_fast); with CARRY_REG -- the operand is a RotatingOperand: the caller's choice,
+  // short_hot_loop() -- carry[s][r], first written by the lowest limb, which reads none (decompose_limb_reg)
+  constexpr bool CARRY_REG = reads_rounded<Src>::value;
   // The lane-uniform constants of the forward transforms' top window (wave_ntt.h::TopConsts) are fetched
   // while the operand is read and rounded, stay in scalar registers for all levels, and make room for
   // the inverse transforms' block after the last level.
   TopConsts<F, LT, G, true> ftop;
   ftop.issue(c.twiddles_uniform());
-  u32 v[NS][EC];
+  u32 v[NS][EC], carry[NS][CARRY_REG ? EC : 1];
   const RoundConsts rc = round_consts(P.ignored_bits);
+  const u32 half_base = 1u << (P.log_base - 1);
 #pragma unroll
   for (int s = 0; s < NS; ++s)
 #pragma unroll
-    for (int r = 0; r < EC; ++r) v[s][r] = round_value_fast(src(s, r * T + lane), rc);
+    for (int r = 0; r < EC; ++r) v[s][r] = rounded_coeff<T>(src, s, r, lane, rc, 0);
   ftop.ready();
 
   // Key tiles of one level for my column: idx = s * PARTS + q, s = source polynomial 0..K, q = part.
@@ -326,6 +464,30 @@ TFHE_HD void external_product_team_multi(const Ctx& c, const PbsParams& P, const
 #pragma unroll
     for (int s0 = 0; s0 < NS; s0 += FS) {
       elem work[FS][E];
+      if constexpr (CARRY_REG) {
+        // (wave-uniform branch: the lowest kept limb has no carry-in and does not emit the add)
+        if (t == 0) {
+#pragma unroll
+          for (int s = 0; s < FS; ++s)
+#pragma unroll
+            for (int r = 0; r < E; ++r) {
+              u32 dg[CO];
+#pragma unroll
+              for (int q = 0; q < CO; ++q) dg[q] = decompose_limb_reg<false>(v[s0 + s][r + q * E], shift, P.log_base, half_base, carry[s0 + s][CARRY_REG ? r + q * E : 0]);
+              work[s][r] = F::from_digits(dg);
+            }
+        } else {
+#pragma unroll
+          for (int s = 0; s < FS; ++s)
+#pragma unroll
+            for (int r = 0; r < E; ++r) {
+              u32 dg[CO];
+#pragma unroll
+              for (int q = 0; q < CO; ++q) dg[q] = decompose_limb_reg<true>(v[s0 + s][r + q * E], shift, P.log_base, half_base, carry[s0 + s][CARRY_REG ? r + q * E : 0]);
+              work[s][r] = F::from_digits(dg);
+            }
+        }
+      } else {
       // F::kMaxLogBase: the largest gadget base the field's exactness bound admits at all; only the
       // Goldilocks fields reach bases above 2^23 (one-level decompositions) and branch at run time
       if (F::kMaxLogBase <= 23 || P.log_base <= 23) {
@@ -348,6 +510,7 @@ TFHE_HD void external_product_team_multi(const Ctx& c, const PbsParams& P, const
             for (int q = 0; q < CO; ++q) dg[q] = decompose_limb_fast<false>(v[s0 + s][r + q * E], shift, P.log_base, carry_width);
             work[s][r] = F::from_digits(dg);
           }
+      }
       }
       // digits are tiny (|d| <= B <= 2^F::kSmallBits, enforced when the context picks the field):
       // the first butterfly stage uses F::mul_small.  A team barrier precedes every level (the
@@ -666,7 +829,14 @@ TFHE_HD void blind_rotate_team_multi(const Ctx& c, const PbsParams& P, const u32
     };
     // all rotated reads of acc happen before the first inverse transform: in-place update is safe
     auto out = [&](int, int s, int j, u32 value) { c.lds_add(c.acc(s) + j, value); };
-    external_product_team_multi<F, LOGN, K, G, 1, NS>(c, P, bsk + (size_t)i * ggsw_words, 0, src, out, [](int) {});
+    if constexpr (short_hot_loop<F, LOGN, K, G, NS>()) {
+      RotatingOperand<LOGN, T> rotated[NS];
+#pragma unroll
+      for (int s = 0; s < NS; ++s) rotated[s] = RotatingOperand<LOGN, T>(c.acc(s), lane, a_tilde[s]);
+      external_product_team_multi<F, LOGN, K, G, 1, NS>(c, P, bsk + (size_t)i * ggsw_words, 0, RotatingOperands<LOGN, T, NS>{rotated}, out, [](int) {});
+    } else {
+      external_product_team_multi<F, LOGN, K, G, 1, NS>(c, P, bsk + (size_t)i * ggsw_words, 0, src, out, [](int) {});
+    }
     // G > 1: the other waves of my group read what I just wrote (with two exchange buffers and one sample the
     // product already ended with a team barrier)
     if (NS > 1 || c.exchange_buffers() != 2) c.poly_sync();
@@ -785,10 +955,12 @@ TFHE_HD void external_product_team_wide(const Ctx& c, const PbsParams& P, const 
 
   TopConsts<F, LT, 1, true> ftop;
   ftop.issue(c.twiddles_uniform());
-  u32 v[EC];
+  constexpr bool CARRY_REG = reads_rounded1<Src>::value;  // (the caller's choice: short_hot_loop())
+  u32 v[EC], carry[CARRY_REG ? EC : 1];
   const RoundConsts rc = round_consts(P.ignored_bits);
+  const u32 half_base = 1u << (P.log_base - 1);
 #pragma unroll
-  for (int r = 0; r < EC; ++r) v[r] = round_value_fast(src(r * T + lane), rc);
+  for (int r = 0; r < EC; ++r) v[r] = rounded_coeff<T>(src, r, lane, rc, 0);
   ftop.ready();
 
   // (no ring) key chunks of my (column, part): row by row, CH elements at a time, double-buffered in registers
@@ -814,14 +986,34 @@ TFHE_HD void external_product_team_wide(const Ctx& c, const PbsParams& P, const 
 #pragma unroll 1
   for (u32 t = 0; t < t_end; ++t) {
     const u32 shift = P.first_shift + P.log_base * t;
-    const u32 carry_width = (t == 0) ? 0u : 1u;
     elem work[E];
+    if constexpr (CARRY_REG) {
+      if (t == 0) {  // (wave-uniform: the lowest kept limb has no carry-in)
 #pragma unroll
-    for (int r = 0; r < E; ++r) {
-      u32 dg[2];
-      dg[0] = decompose_limb_fast<true>(v[r], shift, P.log_base, carry_width);
-      dg[1] = decompose_limb_fast<true>(v[r + E], shift, P.log_base, carry_width);
-      work[r] = F::from_digits(dg);
+        for (int r = 0; r < E; ++r) {
+          u32 dg[2];
+          dg[0] = decompose_limb_reg<false>(v[r], shift, P.log_base, half_base, carry[CARRY_REG ? r : 0]);
+          dg[1] = decompose_limb_reg<false>(v[r + E], shift, P.log_base, half_base, carry[CARRY_REG ? r + E : 0]);
+          work[r] = F::from_digits(dg);
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < E; ++r) {
+          u32 dg[2];
+          dg[0] = decompose_limb_reg<true>(v[r], shift, P.log_base, half_base, carry[CARRY_REG ? r : 0]);
+          dg[1] = decompose_limb_reg<true>(v[r + E], shift, P.log_base, half_base, carry[CARRY_REG ? r + E : 0]);
+          work[r] = F::from_digits(dg);
+        }
+      }
+    } else {
+      const u32 carry_width = (t == 0) ? 0u : 1u;
+#pragma unroll
+      for (int r = 0; r < E; ++r) {
+        u32 dg[2];
+        dg[0] = decompose_limb_fast<true>(v[r], shift, P.log_base, carry_width);
+        dg[1] = decompose_limb_fast<true>(v[r + E], shift, P.log_base, carry_width);
+        work[r] = F::from_digits(dg);
+      }
     }
     if (t < t_begin) continue;  // (wave-uniform) my twin's limb: only the carries were needed
     const u32 row = (u32)me * levels + (levels - 1u - t);
@@ -931,7 +1123,11 @@ TFHE_HD void blind_rotate_team_wide(const Ctx& c, const PbsParams& P, const u32*
     const typename F::elem* ggsw = bsk + (size_t)i * ggsw_words;
     // the ring's refills of the last CMUX have no successor: they re-read this GGSW's first rows (valid memory, unused)
     const typename F::elem* ggsw_next = i + 1 < i_end ? ggsw + ggsw_words : ggsw;
-    external_product_team_wide<F, LOGN, K, LEVELS>(c, P, ggsw, ggsw_next, ring, src, out);
+    if constexpr (short_hot_loop<F, LOGN, K, 1, 1>()) {
+      external_product_team_wide<F, LOGN, K, LEVELS>(c, P, ggsw, ggsw_next, ring, RotatingOperand<LOGN, 64>(acc, lane, a_tilde), out);
+    } else {
+      external_product_team_wide<F, LOGN, K, LEVELS>(c, P, ggsw, ggsw_next, ring, src, out);
+    }
     c.team_sync();  // B: both halves of every column have added their part; all reads of the spectra are over
   }
 }
@@ -973,10 +1169,11 @@ TFHE_HD void external_product_pair(const Ctx& c, const PbsParams& P, const typen
 
   TopConsts<F, LT, G, true> ftop;
   ftop.issue(c.twiddles_uniform());
-  u32 v[EC];
+  u32 v[EC], carry[EC];
   const RoundConsts rc = round_consts(P.ignored_bits);
+  const u32 half_base = 1u << (P.log_base - 1);
 #pragma unroll
-  for (int r = 0; r < EC; ++r) v[r] = round_value_fast(src(r * T + tid), rc);
+  for (int r = 0; r < EC; ++r) v[r] = rounded_coeff<T>(src, r, tid, rc, 0);
   ftop.ready();
 
   // key chunks of a level for my column: source polynomial (mine first, then the other half's), piece of the spectrum, key
@@ -1000,16 +1197,25 @@ TFHE_HD void external_product_pair(const Ctx& c, const PbsParams& P, const typen
   for (u32 t = 0; t < P.levels; ++t) {
     const u32 level = P.levels - 1 - t;
     const u32 shift = P.first_shift + P.log_base * t;
-    const u32 carry_width = (t == 0) ? 0u : 1u;
     load_chunk(level, IntC<0>{}, 0);  // in flight under the forward transform
     c.compiler_fence();
     elem work[E];
+    if (t == 0) {  // (wave-uniform: the lowest kept limb has no carry-in)
 #pragma unroll
-    for (int r = 0; r < E; ++r) {
-      u32 dg[2];
-      dg[0] = decompose_limb_fast<true>(v[r], shift, P.log_base, carry_width);
-      dg[1] = decompose_limb_fast<true>(v[r + E], shift, P.log_base, carry_width);
-      work[r] = F::from_digits(dg);
+      for (int r = 0; r < E; ++r) {
+        u32 dg[2];
+        dg[0] = decompose_limb_reg<false>(v[r], shift, P.log_base, half_base, carry[r]);
+        dg[1] = decompose_limb_reg<false>(v[r + E], shift, P.log_base, half_base, carry[r + E]);
+        work[r] = F::from_digits(dg);
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < E; ++r) {
+        u32 dg[2];
+        dg[0] = decompose_limb_reg<true>(v[r], shift, P.log_base, half_base, carry[r]);
+        dg[1] = decompose_limb_reg<true>(v[r + E], shift, P.log_base, half_base, carry[r + E]);
+        work[r] = F::from_digits(dg);
+      }
     }
     ntt_forward<F, LT, G, true, true>(c, work, ftop);
     // hand my spectrum to the other half: through my buffer (free between two transforms)
@@ -1084,7 +1290,7 @@ TFHE_HD void blind_rotate_pair(const Ctx& c, const PbsParams& P, const u32* lwe 
 #pragma unroll 1
   for (u32 i = i_begin; i < i_end; ++i) {
     const u32 a_tilde = c.uniform(switch_modulus_2n(lwe[i], LOGN));
-    auto src = [&](int j) -> u32 { return monomial_coeff<LOGN>(acc, j, a_tilde) - acc[j]; };
+    const RotatingOperand<LOGN, T> src(acc, tid, a_tilde);
     // each half reads and updates only its own polynomial, the rotated reads all happen before the first update
     auto out = [&](int j, u32 value) { c.lds_add(acc + j, value); };
     external_product_pair<F, LOGN>(c, P, bsk + (size_t)i * ggsw_words, src, out);

@@ -5,12 +5,17 @@ histogram, read back from tfhe-research_amd/libtfhe_hip.so (not from a side comp
     python tools/isa_report.py                                  # resource table of every kernel
     python tools/isa_report.py --kernel 'blind_rotate_kernel<tfhe::FpField, 10, 1>' [--asm out.s]
     python tools/isa_report.py --digest [--lib other.so]        # one line per kernel, for diff
+    python tools/isa_report.py --kernel NAME --count 2aa08:2c390:1 --count 2c394:2d34c:3   # dynamic count, see below
 
 How: the gfx950 code object is unbundled from the .hip_fatbin section (llvm-objcopy +
 clang-offload-bundler), its AMDGPU metadata note gives VGPR / SGPR / AGPR counts, spills, scratch
 and LDS per kernel, llvm-objdump disassembles one kernel, and backward branches give the loop nest.
 For each loop the static instruction mix of its body is printed, so that dynamic counts (PMC
 SQ_INSTS_VALU per launch) can be reconciled:  dynamic = sum over loops of body x trip count.
+Where the compiler has rotated and interleaved the loops (the blind-rotation kernels: the level loop is entered in its
+middle and left in its middle) the per-loop bodies do not add up to an iteration by themselves: --count START:END:TIMES
+(hex addresses from the loop list or --asm, inclusive; repeatable) sums the mix of the named address ranges, each weighted
+with the times one iteration of the outer loop runs it.
 Runs without a GPU.  Output goes to stdout; commit what you want judged under profiles/.
 """
 from __future__ import annotations
@@ -177,6 +182,8 @@ def main():
     ap.add_argument("--lib", default=LIB)
     ap.add_argument("--kernel", action="append", default=[], help="substring of the demangled kernel name; repeatable")
     ap.add_argument("--asm", default="", help="also write the disassembly of the (last) selected kernel to this file")
+    ap.add_argument("--count", action="append", default=[], metavar="START:END:TIMES",
+                    help="address range (hex, inclusive) of the selected kernel and how often one outer iteration runs it; repeatable")
     ap.add_argument("--digest", action="store_true",
                     help="one line per kernel (resources + sha256 of the normalised instruction stream), sorted: diff two builds")
     args = ap.parse_args()
@@ -211,6 +218,16 @@ def main():
                     print(f"\n  loop @{insts[head][0]:#x}..{insts[tail][0]:#x} ({tail - head + 1} instructions, "
                           f"{len(inner)} nested loop(s)); body outside nested loops:")
                     print(fmt_hist(histogram(own), indent="      "))
+                if args.count:
+                    total = collections.Counter()
+                    print("\n  dynamic mix of one outer iteration (--count ranges x times):")
+                    for spec in args.count:
+                        lo, hi, times = spec.split(":")
+                        h = histogram([ins for ins in insts if int(lo, 16) <= ins[0] <= int(hi, 16)])
+                        print(f"    {lo}..{hi} x {times}: " + fmt_hist(h, indent="").splitlines()[0])
+                        for name, n in h.items():
+                            total[name] += n * int(times)
+                    print(fmt_hist(total, indent="      "))
                 if args.asm:
                     with open(args.asm, "w") as f:
                         f.write(text)
