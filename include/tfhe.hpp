@@ -164,6 +164,9 @@ class Engine {
   // TFHE_SHAPE_AUTO (default: by batch size), TFHE_SHAPE_WIDE (the latency shape: the reference's bootstrap() takes ONE
   // ciphertext, bootstrapping.rs:58-65) or TFHE_SHAPE_TEAM for every blind rotation of the engine; same bits either way
   void set_kernel_shape(int shape) { check_pool(tfhe_pool_set_kernel_shape(pool_.get(), shape)); }
+  // TFHE_KS_PATH_AUTO (default), TFHE_KS_PATH_SCALAR or TFHE_KS_PATH_MATRIX (int8 matrix cores over the prepared key;
+  // throws where the key-switch digits do not fit int8) for every key_switch_lwe (key_switching.rs:63-103); same bits
+  void set_key_switch_path(int path) { check_pool(tfhe_pool_set_key_switch_path(pool_.get(), path)); }
 
   const TfheParams& params() const { return params_; }
   tfhe_context* raw() const { return ctx_; }        // the first device's context (single-ciphertext calls)

@@ -721,6 +721,28 @@ int tfhe_context_set_bootstrap_order(tfhe_context *ctx, int ks_first);
 #define TFHE_SHAPE_TEAM 2
 int tfhe_context_set_kernel_shape(tfhe_context *ctx, int shape);
 
+/* ---- path of the key switch -------------------------------------------------------------------------
+ * key_switch_lwe (key_switching.rs:63-103) is out = (0, b) - sum_{i, l} digit_l(a_i) * ksk[i*l_ks + l], a wrapping-u32
+ * matrix product of small digits with a key that is constant between loads.  Two kernels compute the same bits:
+ *   TFHE_KS_PATH_SCALAR  one 32-bit multiply-add per term on the vector units: every parameter set;
+ *   TFHE_KS_PATH_MATRIX  the key as four signed byte planes (prepared at key load, 4 k N l_ks (n+1) more bytes plus
+ *                        padding to whole tiles), exact int8 x int8 -> int32 products on the matrix cores, the planes
+ *                        folded as sum_j plane_j << 8j.  Needs digits that fit int8 -- key-switch log_base <= 6: the
+ *                        literal decomposer can emit the value B itself -- and k N l_ks 2^(log_base + 7) < 2^31, so that
+ *                        no plane sum overflows; TFHE_ERR_UNSUPPORTED otherwise;
+ *   TFHE_KS_PATH_AUTO    (default) the matrix path wherever it is admitted (it measured faster at every batch, 1 to
+ *                        4,096), the scalar kernel elsewhere.
+ * Affects every entry point that key-switches (bootstrap in both orders, gates, tree LUTs, tfhe_key_switch_batch*). */
+#define TFHE_KS_PATH_AUTO 0
+#define TFHE_KS_PATH_SCALAR 1
+#define TFHE_KS_PATH_MATRIX 2
+int tfhe_context_set_key_switch_path(tfhe_context *ctx, int path);
+/* How a key switch of `batch` ciphertexts would go out under the current path: *path = TFHE_KS_PATH_SCALAR or
+ * TFHE_KS_PATH_MATRIX, the grid of workgroups (column tiles x sample tiles) and the shares of the mask words (more than
+ * one: the output is zeroed first and partial sums are added). */
+int tfhe_debug_key_switch_plan(tfhe_context *ctx, size_t batch, int *path, unsigned *grid_x, unsigned *grid_y,
+                               unsigned *splits);
+
 /* ---- decomposer alignment ------------------------------------------------------
  * 0 (default): the reference's literal decomposer -- limbs counted from bit 0 (decomposer.rs:48-70),
  * gadget factors beta^{floor(32/log_base)-(level+1)} (ggsw.rs:98, key_switching.rs:38), bit-exact
@@ -786,6 +808,10 @@ int tfhe_pool_shard(const tfhe_pool *pool, size_t batch, size_t member, size_t *
 int tfhe_pool_set_decomposer_alignment(tfhe_pool *pool, int aligned);
 int tfhe_pool_set_bootstrap_order(tfhe_pool *pool, int ks_first);
 int tfhe_pool_set_kernel_shape(tfhe_pool *pool, int shape); /* tfhe_context_set_kernel_shape for every member */
+int tfhe_pool_set_key_switch_path(tfhe_pool *pool, int path); /* tfhe_context_set_key_switch_path for every member */
+/* tfhe_debug_key_switch_plan of member `member` for its slice of `batch` */
+int tfhe_pool_debug_key_switch_plan(tfhe_pool *pool, size_t member, size_t batch, int *path, unsigned *grid_x,
+                                    unsigned *grid_y, unsigned *splits);
 int tfhe_pool_reserve(tfhe_pool *pool, size_t max_batch);
 int tfhe_pool_synchronize(tfhe_pool *pool);
 /* BootstrappingKey upload, layouts as tfhe_load_bootstrapping_key: host pointers, or (_device) pointers on member

@@ -43,6 +43,7 @@ extern "C" {
     fn tfhe_pool_gate_batch(pool: *mut TfhePool, truth: *const u32, ct0: *const u32, ct1: *const u32,
                             batch: usize, lwe_out: *mut u32) -> c_int;
     fn tfhe_pool_set_kernel_shape(pool: *mut TfhePool, shape: c_int) -> c_int;
+    fn tfhe_pool_set_key_switch_path(pool: *mut TfhePool, path: c_int) -> c_int;
     fn tfhe_last_error(ctx: *const TfheContext) -> *const c_char;
     fn tfhe_bootstrap_batch(ctx: *mut TfheContext, lwe_in: *const u32, batch: usize,
                             test_vector_poly: *const u32, tv_count: usize, lwe_out: *mut u32) -> c_int;
@@ -167,6 +168,18 @@ pub enum KernelShape { Auto = 0, Wide = 1, Team = 2 }
 impl GpuBootstrappingKey {
     pub fn set_kernel_shape(&self, shape: KernelShape) {
         check_pool(self.pool, unsafe { tfhe_pool_set_kernel_shape(self.pool, shape as c_int) }, "set kernel shape");
+    }
+}
+
+/// Path of `key_switch_lwe` (key_switching.rs:63-103; `tfhe_context_set_key_switch_path`): `Auto` takes the int8 matrix
+/// cores over the key prepared at load wherever the key-switch digits fit int8 (log_base <= 6),
+/// `Matrix` insists (and panics where they do not fit); the bits are the same.
+#[derive(Clone, Copy)]
+pub enum KeySwitchPath { Auto = 0, Scalar = 1, Matrix = 2 }
+
+impl GpuBootstrappingKey {
+    pub fn set_key_switch_path(&self, path: KeySwitchPath) {
+        check_pool(self.pool, unsafe { tfhe_pool_set_key_switch_path(self.pool, path as c_int) }, "set key-switch path");
     }
 }
 

@@ -32,6 +32,7 @@ FILE_BSK, FILE_KSK, FILE_LWE, FILE_GLWE, FILE_GGSW, FILE_WORDS, FILE_PKSK = 1, 2
 DECOMPOSER_PBS, DECOMPOSER_KS = 0, 1
 BACKEND_AUTO, BACKEND_GOLDILOCKS, BACKEND_FP64, BACKEND_GOLDILOCKS_SPLIT, BACKEND_FP64_P49, BACKEND_FP64_FFT = 0, 1, 2, 3, 4, 5
 SHAPE_AUTO, SHAPE_WIDE, SHAPE_TEAM = 0, 1, 2   # tfhe_context_set_kernel_shape
+KS_PATH_AUTO, KS_PATH_SCALAR, KS_PATH_MATRIX = 0, 1, 2   # tfhe_context_set_key_switch_path
 
 # truth[(lhs << 1) | rhs]
 GATE_AND = (0, 0, 0, 1)
@@ -386,6 +387,19 @@ class Context:
         """SHAPE_AUTO (default: by batch size), SHAPE_WIDE (2 (k+1) waves per sample: the latency shape, fp64-fft up to
         N = 1024) or SHAPE_TEAM (the throughput shape) for every blind rotation of this context; same bits either way"""
         self._check(lib().tfhe_context_set_kernel_shape(self._h, C.c_int(int(shape))))
+
+    def set_key_switch_path(self, path: int):
+        """KS_PATH_AUTO (default: the matrix cores wherever the key-switch decomposer admits them),
+        KS_PATH_SCALAR or KS_PATH_MATRIX (TfheError where digits do not fit int8: key-switch log_base > 6) for every
+        key_switch_lwe (key_switching.rs:63-103) of this context; same bits either way"""
+        self._check(lib().tfhe_context_set_key_switch_path(self._h, C.c_int(int(path))))
+
+    def key_switch_plan(self, batch: int) -> dict:
+        """how a key switch of `batch` ciphertexts goes out (tfhe_debug_key_switch_plan)"""
+        path, gx, gy, splits = C.c_int(), C.c_uint(), C.c_uint(), C.c_uint()
+        self._check(lib().tfhe_debug_key_switch_plan(self._h, C.c_size_t(batch), C.byref(path), C.byref(gx), C.byref(gy),
+                                                     C.byref(splits)))
+        return {"path": path.value, "grid": (gx.value, gy.value), "splits": splits.value}
 
     def set_bootstrap_order(self, ks_first: bool):
         """False: PBS then key switch (bootstrapping.rs:58-120), ciphertexts of n+1 words.  True:
@@ -1683,6 +1697,16 @@ class Pool:
 
     def set_kernel_shape(self, shape: int):
         self._check(lib().tfhe_pool_set_kernel_shape(self._h, C.c_int(int(shape))))
+
+    def set_key_switch_path(self, path: int):
+        self._check(lib().tfhe_pool_set_key_switch_path(self._h, C.c_int(int(path))))
+
+    def key_switch_plan(self, batch: int, member: int = 0) -> dict:
+        """how member `member` key-switches its slice of `batch` (tfhe_pool_debug_key_switch_plan)"""
+        path, gx, gy, splits = C.c_int(), C.c_uint(), C.c_uint(), C.c_uint()
+        self._check(lib().tfhe_pool_debug_key_switch_plan(self._h, C.c_size_t(member), C.c_size_t(batch), C.byref(path),
+                                                          C.byref(gx), C.byref(gy), C.byref(splits)))
+        return {"path": path.value, "grid": (gx.value, gy.value), "splits": splits.value}
 
     def set_bootstrap_order(self, ks_first: bool):
         self._check(lib().tfhe_pool_set_bootstrap_order(self._h, C.c_int(int(ks_first))))

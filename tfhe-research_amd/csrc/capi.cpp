@@ -302,7 +302,7 @@ int enqueue_bootstrap(tfhe_context* ctx, const u32* d_lwe_in, size_t batch, cons
   }
   auto key_switch = [&](const u32* in, u32* out) -> int {
     TFHE_TRY(span_begin(ctx, kKeySwitchSpan));
-    HIP_TRY(ctx, launch::key_switch(ctx->stream, ctx->ks, ctx->big_n, ctx->params.lwe_dimension, in, batch, ctx->d_ksk, out));
+    HIP_TRY(ctx, launch::key_switch(ctx->stream, ctx->ks, ctx->big_n, ctx->params.lwe_dimension, in, batch, ctx->d_ksk, out, ctx->d_ksk_matrix, ctx->ks_path));
     return span_end(ctx, kKeySwitchSpan, false);
   };
   if (ctx->ks_first) {  // notes/TFHE.md:367-400: key switch k*N -> n, then PBS back to k*N
@@ -362,9 +362,13 @@ int adopt_prepared_key(tfhe_context* dst, const tfhe_context* src) {
     dst->bsk_ggsws = ggsws;
   }
   if (!dst->d_ksk) HIP_TRY(dst, hipMalloc(reinterpret_cast<void**>(&dst->d_ksk), ksk_bytes));
+  const size_t ksm_bytes = src->d_ksk_matrix ? ksk_matrix_bytes(src) : 0;  // same parameters: admitted on both or neither
+  if (ksm_bytes && !dst->d_ksk_matrix) HIP_TRY(dst, hipMalloc(&dst->d_ksk_matrix, ksm_bytes));
   if (dst->device == src->device) {
     HIP_TRY(dst, hipMemcpyAsync(dst->d_bsk, src->d_bsk, bsk_bytes, hipMemcpyDeviceToDevice, dst->stream));
     HIP_TRY(dst, hipMemcpyAsync(dst->d_ksk, src->d_ksk, ksk_bytes, hipMemcpyDeviceToDevice, dst->stream));
+    if (ksm_bytes)
+      HIP_TRY(dst, hipMemcpyAsync(dst->d_ksk_matrix, src->d_ksk_matrix, ksm_bytes, hipMemcpyDeviceToDevice, dst->stream));
   } else {
     // direct xGMI copies where the link allows peer access; hipMemcpyPeerAsync stages through the host otherwise
     int can = 0;
@@ -375,6 +379,8 @@ int adopt_prepared_key(tfhe_context* dst, const tfhe_context* src) {
     }
     HIP_TRY(dst, hipMemcpyPeerAsync(dst->d_bsk, dst->device, src->d_bsk, src->device, bsk_bytes, dst->stream));
     HIP_TRY(dst, hipMemcpyPeerAsync(dst->d_ksk, dst->device, src->d_ksk, src->device, ksk_bytes, dst->stream));
+    if (ksm_bytes)
+      HIP_TRY(dst, hipMemcpyPeerAsync(dst->d_ksk_matrix, dst->device, src->d_ksk_matrix, src->device, ksm_bytes, dst->stream));
   }
   dst->have_key = true;
   dst->bmmp = src->bmmp;
@@ -598,7 +604,7 @@ void tfhe_context_destroy(tfhe_context* ctx) {
                   ctx->d_lwe_big, ctx->d_lwe_out, ctx->d_lwe_ks, ctx->d_glwe_a, ctx->d_glwe_b, ctx->d_glwe_c,
                   ctx->d_tv,     ctx->d_misc,   ctx->d_ggsw_tmp, ctx->d_ggsw_raw,
                   ctx->d_key_tmp, ctx->d_pksk, ctx->d_pack_cols, ctx->d_lookup_ws, ctx->d_tree_ws,
-                  ctx->d_demux_ws, ctx->d_program_ws, ctx->d_dense_ws};
+                  ctx->d_demux_ws, ctx->d_program_ws, ctx->d_dense_ws, ctx->d_ksk_matrix};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& g : ctx->gate_tvs)
@@ -650,6 +656,32 @@ int tfhe_context_set_kernel_shape(tfhe_context* ctx, int shape) {
   if (shape != TFHE_SHAPE_AUTO && shape != TFHE_SHAPE_WIDE && shape != TFHE_SHAPE_TEAM)
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "kernel shape: TFHE_SHAPE_AUTO, TFHE_SHAPE_WIDE or TFHE_SHAPE_TEAM");
   ctx->shape = shape;
+  return TFHE_OK;
+}
+
+int tfhe_context_set_key_switch_path(tfhe_context* ctx, int path) {
+  if (!ctx) return TFHE_ERR_INVALID_ARGUMENT;
+  if (path != TFHE_KS_PATH_AUTO && path != TFHE_KS_PATH_SCALAR && path != TFHE_KS_PATH_MATRIX)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "key-switch path: TFHE_KS_PATH_AUTO, TFHE_KS_PATH_SCALAR or TFHE_KS_PATH_MATRIX");
+  if (path == TFHE_KS_PATH_MATRIX && !ks_matrix_admitted(ctx))
+    return fail(ctx, TFHE_ERR_UNSUPPORTED,
+                "the matrix-core key switch needs key-switch digits that fit int8 (log_base <= 6) and int32 plane sums "
+                "that cannot overflow (k N levels 2^(log_base + 7) < 2^31): this parameter set runs the scalar kernel");
+  ctx->ks_path = path;
+  return TFHE_OK;
+}
+
+int tfhe_debug_key_switch_plan(tfhe_context* ctx, size_t batch, int* path, unsigned* grid_x, unsigned* grid_y,
+                               unsigned* splits) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {path, grid_x, grid_y, splits}, 1, "null pointer"));
+  if (batch == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "batch == 0");
+  launch::KeySwitchPlanInfo plan{};
+  HIP_TRY(ctx, launch::key_switch_plan(ctx->ks, ctx->big_n, ctx->params.lwe_dimension, batch, ctx->ks_path, &plan));
+  *path = plan.matrix ? TFHE_KS_PATH_MATRIX : TFHE_KS_PATH_SCALAR;
+  *grid_x = plan.grid_x;
+  *grid_y = plan.grid_y;
+  *splits = plan.splits;
   return TFHE_OK;
 }
 
@@ -813,6 +845,12 @@ static int load_key_common(tfhe_context* ctx, const u32* d_bsk_raw, const u32* d
   HIP_TRY(ctx, launch::bsk_prepare(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->pbs.k, ctx->d_tw, d_bsk_raw, bsk_polys, ctx->d_bsk));
   if (ksk_needs_copy)
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ksk, d_ksk_raw, ksk_words(ctx) * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
+  // the key-switching key's byte planes for the matrix cores, made once per key like the BSK's spectra
+  if (ks_matrix_admitted(ctx)) {
+    if (!ctx->d_ksk_matrix) HIP_TRY(ctx, hipMalloc(&ctx->d_ksk_matrix, ksk_matrix_bytes(ctx)));
+    HIP_TRY(ctx, launch::ksk_prepare_matrix(ctx->stream, ctx->ks, ctx->big_n, ctx->params.lwe_dimension, ctx->d_ksk,
+                                            ctx->d_ksk_matrix));
+  }
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->have_key = true;
   ctx->bmmp = bmmp;
@@ -994,7 +1032,7 @@ int tfhe_key_switch_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size
   TFHE_TRY(check_key_switch_args(ctx, lwe_in, lwe_out, batch));
   TFHE_TRY(span_begin(ctx, kKeySwitchSpan));
   HIP_TRY(ctx, launch::key_switch(ctx->stream, ctx->ks, ctx->big_n, ctx->params.lwe_dimension, lwe_in,
-                                  batch, ctx->d_ksk, lwe_out));
+                                  batch, ctx->d_ksk, lwe_out, ctx->d_ksk_matrix, ctx->ks_path));
   return span_end(ctx, kKeySwitchSpan);
 }
 
@@ -2527,7 +2565,7 @@ int tfhe_tree_lut_batch_device(tfhe_context* ctx, const uint32_t* const* digits,
   auto digit_of = [&](size_t t, const u32** out) -> int {
     *out = digits[t];
     if (!ctx->ks_first) return TFHE_OK;
-    HIP_TRY(ctx, launch::key_switch(s, ctx->ks, ctx->big_n, n, digits[t], batch, ctx->d_ksk, ks_digit));
+    HIP_TRY(ctx, launch::key_switch(s, ctx->ks, ctx->big_n, n, digits[t], batch, ctx->d_ksk, ks_digit, ctx->d_ksk_matrix, ctx->ks_path));
     *out = ks_digit;
     return TFHE_OK;
   };
@@ -2550,7 +2588,7 @@ int tfhe_tree_lut_batch_device(tfhe_context* ctx, const uint32_t* const* digits,
     cur = next;
     count = groups;
   }
-  if (!ctx->ks_first) HIP_TRY(ctx, launch::key_switch(s, ctx->ks, ctx->big_n, n, cur, count, ctx->d_ksk, lwe_out));
+  if (!ctx->ks_first) HIP_TRY(ctx, launch::key_switch(s, ctx->ks, ctx->big_n, n, cur, count, ctx->d_ksk, lwe_out, ctx->d_ksk_matrix, ctx->ks_path));
   return TFHE_OK;
 }
 

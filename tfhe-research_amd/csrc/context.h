@@ -28,6 +28,8 @@ struct tfhe_context {
   unsigned long long* d_queue = nullptr;  // ticket counter of the external-product kernel's work queue
   void* d_bsk = nullptr;      // prepared BSK [n][R][k+1][parts][N] (spectrum_slot order, x 1/N)
   u32* d_ksk = nullptr;       // [big_n*l_ks][n+1]
+  void* d_ksk_matrix = nullptr;  // the same key in the matrix path's layout (ks_matrix.h); null where it is not admitted
+  int ks_path = 0;            // path of the key switch (tfhe_context_set_key_switch_path): launch::kKsPath*
   bool have_key = false;
   bool bmmp = false;          // the loaded key is a BMMP key: n/2 * 3 GGSWs (tfhe_load_bootstrapping_key_bmmp)
   size_t bsk_ggsws = 0;       // GGSWs d_bsk was allocated for
@@ -139,7 +141,7 @@ inline int hip_fail(tfhe_context* ctx, hipError_t e, const char* what) {
 }
 
 // pool.cpp: allocate dst's key buffers like src's and copy the PREPARED bootstrapping key and the key-switching
-// key device to device (peer copy over xGMI, or a plain device copy when both contexts sit on one GPU) on dst's
+// key (raw and, where the matrix path is admitted, prepared) device to device (peer copy over xGMI, or a plain device copy when both contexts sit on one GPU) on dst's
 // stream; dst must have been created with the same parameters and backend (capi.cpp)
 int adopt_prepared_key(tfhe_context* dst, const tfhe_context* src);
 
@@ -152,6 +154,11 @@ inline size_t io_words(const tfhe_context* ctx) { return ctx->ks_first ? big_lwe
 inline size_t ggsw_words(const tfhe_context* ctx) { return (size_t)ctx->R * glwe_words(ctx); }  // a raw GGSW
 inline size_t prepared_ggsw_words(const tfhe_context* ctx) { return ggsw_words(ctx) * ctx->parts; }  // 8-byte words
 inline size_t ksk_words(const tfhe_context* ctx) { return (size_t)ctx->big_n * ctx->ks.levels * lwe_words(ctx); }
+// the matrix-core key switch serves this context's key-switch decomposer (ks_matrix.h::ksm_admitted)
+inline bool ks_matrix_admitted(const tfhe_context* ctx) { return ksm_admitted(ctx->ks.log_base, ctx->ks.levels, ctx->big_n); }
+inline size_t ksk_matrix_bytes(const tfhe_context* ctx) {
+  return launch::ksk_matrix_bytes(ctx->ks, ctx->big_n, ctx->params.lwe_dimension);
+}
 // the raw packing key from an LWE key of `from_dimension` bits: one GLWE row per (key bit, KS level)
 inline size_t packing_key_words(const tfhe_context* ctx, size_t from_dimension) {
   return from_dimension * ctx->ks.levels * glwe_words(ctx);

@@ -874,6 +874,110 @@ __global__ void __launch_bounds__(256) key_switch_kernel(KsParams Kp, u32 big_n,
   }
 }
 
+// ------------------------------------------------------------------------------ key switch on the matrix cores
+// The same sum as key_switch_kernel through v_mfma_i32_32x32x32_i8 over the prepared key of ks_matrix.h, which states
+// the layout and why the bits are the same.  One thread per (super-block, level, column tile, lane): the 16 key words
+// of the lane's fragment, split into their four byte planes.
+__global__ void __launch_bounds__(256) ksk_prepare_matrix_kernel(KsmLayout lo, const u32* __restrict__ ksk,
+                                                                 unsigned char* __restrict__ prepared) {
+  const size_t total = (size_t)lo.sblocks * lo.levels * lo.col_tiles * 64;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const u32 lane = (u32)(i & 63u);
+    size_t f = i >> 6;
+    const u32 ct = (u32)(f % lo.col_tiles);
+    f /= lo.col_tiles;
+    const u32 level = (u32)(f % lo.levels);
+    const u32 sb = (u32)(f / lo.levels);
+    u32 planes[kKsmPlanes][4];
+    ksm_prepare_lane(lo, ksk, sb, level, ct, lane, planes);
+#pragma unroll
+    for (u32 p = 0; p < kKsmPlanes; ++p)  // 16-byte aligned: fragments are 1 KiB, a lane's share 16 bytes
+      *reinterpret_cast<uint4*>(prepared + ksm_fragment(lo, sb, level, ct, p) + (size_t)lane * 16) =
+          make_uint4(planes[p][0], planes[p][1], planes[p][2], planes[p][3]);
+  }
+}
+
+// A workgroup is four waves, each with its own tile of 32 samples and the same kKsmColTiles column tiles (the waves
+// fetch the same key fragments: one trip to L2 serves four).  Per super-block a lane loads the 16 mask words of its
+// sample that its half of the MFMA's K covers, and per level -- LSB first, as the carry chain runs -- decomposes them
+// into its own A fragment; K is walked in that order, (super-block, level from the last down).  Each (column tile,
+// plane) keeps an int32 accumulator tile; ksm_admitted (checked by the launcher) bounds their sums, so they are folded
+// once at the end: total = sum_j plane_j << 8j in wrapping u32.  gridDim.z splits the super-blocks as
+// key_switch_kernel splits the mask words: partial sums are added to the pre-zeroed output with atomics.
+// workgroups a launch should reach before the super-blocks stop being split over gridDim.z: four per CU
+constexpr unsigned kKsmTargetWgs = 1024u;
+// smallest batch TFHE_KS_PATH_AUTO sends here.  Below one tile of 32 samples most of every MFMA is padding, and it still
+// wins: 0.019 ms against 0.055 ms at batch 1, cfg1 and cfg2 alike (profiles/key_switch_matrix_ab.txt), so: every batch
+constexpr size_t kKsMatrixMinBatch = 1;
+__global__ void __launch_bounds__(256, 2) key_switch_matrix_kernel(KsParams Kp, KsmLayout lo, const u32* __restrict__ lwe_in,
+                                                                size_t batch, const uint4* __restrict__ prepared,
+                                                                u32* __restrict__ lwe_out, u32 sblocks_per_split) {
+  const u32 lane = threadIdx.x & 63u;
+  const u32 r = lane & 31u, h = lane >> 5;
+  const size_t sample0 = ((size_t)blockIdx.y * 4 + (threadIdx.x >> 6)) * kKsmSamples;
+  if (sample0 >= batch) return;  // no barrier below: a wave without samples leaves
+  const size_t sample = sample0 + r;
+  const bool sample_ok = sample < batch;
+  const size_t stride = (size_t)lo.big_n + 1;
+  const u32* row = lwe_in + (sample_ok ? sample : sample0) * stride;
+  const u32 ct0 = blockIdx.x * kKsmColTiles;
+
+  i32x16 acc[kKsmColTiles][kKsmPlanes];
+#pragma unroll
+  for (u32 c = 0; c < kKsmColTiles; ++c)
+#pragma unroll
+    for (u32 p = 0; p < kKsmPlanes; ++p)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[c][p][e] = 0;
+
+  const u32 sb_begin = blockIdx.z * sblocks_per_split;
+  const u32 sb_end = sb_begin + sblocks_per_split < lo.sblocks ? sb_begin + sblocks_per_split : lo.sblocks;
+  for (u32 sb = sb_begin; sb < sb_end; ++sb) {
+    u32 v[16], carry[16];
+#pragma unroll
+    for (u32 j = 0; j < 16; ++j) {
+      const u32 word = sb * kKsmWords + h * 16 + j;
+      const u32 x = row[word < lo.big_n ? word : 0u];  // always in bounds; a padding word counts as zero, which
+      v[j] = round_value((sample_ok && word < lo.big_n) ? x : 0u, Kp.ignored_bits);  // rounds and decomposes to zeros
+      carry[j] = 0;
+    }
+    for (u32 t = 0; t < Kp.levels; ++t) {  // LSB -> MSB, level index counts from the MSB
+      const u32 level = Kp.levels - 1 - t;
+      const uint4* frag = prepared + ksm_fragment(lo, sb, level, ct0, 0) / 16 + lane;
+      uint4 b[kKsmColTiles][kKsmPlanes];
+#pragma unroll
+      for (u32 c = 0; c < kKsmColTiles; ++c)
+#pragma unroll
+        for (u32 p = 0; p < kKsmPlanes; ++p) b[c][p] = frag[(c * kKsmPlanes + p) * 64];
+      u32 digits[4];
+      ksm_digit_fragment(v, carry, Kp.first_shift + Kp.log_base * t, Kp.log_base, digits);
+      const i32x4 a = {(i32)digits[0], (i32)digits[1], (i32)digits[2], (i32)digits[3]};
+#pragma unroll
+      for (u32 c = 0; c < kKsmColTiles; ++c)
+#pragma unroll
+        for (u32 p = 0; p < kKsmPlanes; ++p) {
+          const i32x4 bf = {(i32)b[c][p].x, (i32)b[c][p].y, (i32)b[c][p].z, (i32)b[c][p].w};
+          acc[c][p] = mfma_i32_32x32x32_i8(a, bf, acc[c][p]);
+        }
+    }
+  }
+
+#pragma unroll
+  for (u32 c = 0; c < kKsmColTiles; ++c) {
+    const u32 col = (ct0 + c) * kKsmCols + r;
+    if (col >= lo.width) continue;
+#pragma unroll
+    for (u32 e = 0; e < 16; ++e) {
+      const size_t s = sample0 + (e & 3u) + 8 * (e >> 2) + 4 * h;
+      if (s >= batch) continue;
+      u32 out = 0u - ksm_fold((u32)acc[c][0][e], (u32)acc[c][1][e], (u32)acc[c][2][e], (u32)acc[c][3][e]);
+      if (col == lo.width - 1 && blockIdx.z == 0) out += lwe_in[s * stride + lo.big_n];
+      if (gridDim.z == 1) lwe_out[s * lo.width + col] = out;
+      else atomicAdd(&lwe_out[s * lo.width + col], out);
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------ elementwise
 __global__ void decompose_words_kernel(u32 log_base, u32 levels, u32 ignored_bits, u32 first_shift,
                                        const u32* __restrict__ values, size_t count,
@@ -2022,26 +2126,65 @@ hipError_t cmux_program_pass(hipStream_t s, int field, const PbsParams& P, const
   TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (launch_cmux_program_pass<FF, LL, KK>(s, P, tw, pass, queries))));
 }
 
-hipError_t key_switch(hipStream_t s, const KsParams& K, u32 big_n, u32 n, const u32* lwe_in,
-                      size_t batch, const u32* ksk, u32* lwe_out) {
-  const size_t lds = ((size_t)kKsWords * K.levels * kKsSamples + 2 * (size_t)kKsKeyRows * kKsCols) * sizeof(u32);
-  if (lds > 64 * 1024) return hipErrorInvalidValue;
-  dim3 grid((n + 1 + kKsCols - 1) / kKsCols, (unsigned)((batch + kKsSamples - 1) / kKsSamples));
+hipError_t key_switch_plan(const KsParams& K, u32 big_n, u32 n, size_t batch, int path, KeySwitchPlanInfo* out) {
+  if (batch == 0 || !out) return hipErrorInvalidValue;
+  const bool admitted = ksm_admitted(K.log_base, K.levels, big_n);
+  if (path == kKsPathMatrix && !admitted) return hipErrorInvalidValue;
+  out->matrix = path == kKsPathMatrix || (path == kKsPathAuto && admitted && batch >= kKsMatrixMinBatch);
+  if (out->matrix) {
+    const KsmLayout lo = ksm_layout(big_n, K.levels, n);
+    out->grid_x = lo.col_tiles / kKsmColTiles;
+    out->grid_y = (unsigned)((batch + 4 * kKsmSamples - 1) / (4 * kKsmSamples));
+    // aim at kKsmTargetWgs workgroups; a split covers whole super-blocks
+    unsigned splits = kKsmTargetWgs / (out->grid_x * out->grid_y);
+    if (splits > lo.sblocks) splits = lo.sblocks;
+    if (splits < 1u) splits = 1u;
+    out->per_split = (lo.sblocks + splits - 1) / splits;
+    out->splits = (lo.sblocks + out->per_split - 1) / out->per_split;
+    return hipSuccess;
+  }
+  out->grid_x = (n + 1 + kKsCols - 1) / kKsCols;
+  out->grid_y = (unsigned)((batch + kKsSamples - 1) / kKsSamples);
   // aim at kKsTargetWgs workgroups; a split covers a multiple of kKsWords words, at least 64
-  unsigned splits = kKsTargetWgs / (grid.x * grid.y);
+  unsigned splits = kKsTargetWgs / (out->grid_x * out->grid_y);
   const unsigned max_splits = (big_n + 63u) / 64u;
   if (splits > max_splits) splits = max_splits;
   if (splits > 32u) splits = 32u;
   if (splits < 1u) splits = 1u;
-  u32 words_per_split = ((big_n + splits - 1) / splits + kKsWords - 1) / kKsWords * kKsWords;
-  splits = (big_n + words_per_split - 1) / words_per_split;
-  grid.z = splits;
-  if (splits > 1) {
-    hipError_t e = hipMemsetAsync(lwe_out, 0, batch * ((size_t)n + 1) * sizeof(u32), s);
+  out->per_split = ((big_n + splits - 1) / splits + kKsWords - 1) / kKsWords * kKsWords;
+  out->splits = (big_n + out->per_split - 1) / out->per_split;
+  return hipSuccess;
+}
+
+size_t ksk_matrix_bytes(const KsParams& K, u32 big_n, u32 n) { return ksm_bytes(ksm_layout(big_n, K.levels, n)); }
+
+hipError_t ksk_prepare_matrix(hipStream_t s, const KsParams& K, u32 big_n, u32 n, const u32* ksk, void* prepared) {
+  const KsmLayout lo = ksm_layout(big_n, K.levels, n);
+  const size_t threads = (size_t)lo.sblocks * lo.levels * lo.col_tiles * 64;
+  hipLaunchKernelGGL(ksk_prepare_matrix_kernel, dim3(grid_for(threads, 256)), dim3(256), 0, s, lo, ksk,
+                     static_cast<unsigned char*>(prepared));
+  return hipGetLastError();
+}
+
+hipError_t key_switch(hipStream_t s, const KsParams& K, u32 big_n, u32 n, const u32* lwe_in,
+                      size_t batch, const u32* ksk, u32* lwe_out, const void* ksk_matrix, int path) {
+  KeySwitchPlanInfo plan{};
+  hipError_t e = key_switch_plan(K, big_n, n, batch, path, &plan);
+  if (e != hipSuccess) return e;
+  if (plan.matrix && !ksk_matrix) return hipErrorInvalidValue;  // a missing prepared key is an error, not a detour
+  const size_t lds = ((size_t)kKsWords * K.levels * kKsSamples + 2 * (size_t)kKsKeyRows * kKsCols) * sizeof(u32);
+  if (!plan.matrix && lds > 64 * 1024) return hipErrorInvalidValue;
+  if (plan.splits > 1) {
+    e = hipMemsetAsync(lwe_out, 0, batch * ((size_t)n + 1) * sizeof(u32), s);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(key_switch_kernel, grid, dim3(256), lds, s, K, big_n, n, lwe_in, batch, ksk,
-                     lwe_out, words_per_split);
+  const dim3 grid(plan.grid_x, plan.grid_y, plan.splits);
+  if (plan.matrix)
+    hipLaunchKernelGGL(key_switch_matrix_kernel, grid, dim3(256), 0, s, K, ksm_layout(big_n, K.levels, n), lwe_in, batch,
+                       static_cast<const uint4*>(ksk_matrix), lwe_out, plan.per_split);
+  else
+    hipLaunchKernelGGL(key_switch_kernel, grid, dim3(256), lds, s, K, big_n, n, lwe_in, batch, ksk, lwe_out,
+                       plan.per_split);
   return hipGetLastError();
 }
 

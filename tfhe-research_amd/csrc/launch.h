@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ks_matrix.h"
 #include "pbs_wave.h"
 
 namespace tfhe {
@@ -80,9 +81,24 @@ hipError_t external_product(hipStream_t s, int field, const PbsParams& P, const 
                             u32* ct1_inout, const u32* cmux_ct0, size_t batch, u32* glwe_out,
                             unsigned long long* queue /* one device word of scratch: ticket counter of long batches */);
 
-// key_switch_lwe over a batch: lwe_in [batch][big_n+1], ksk [big_n*levels][n+1], out [batch][n+1]
+// Path of a key switch (tfhe_context_set_key_switch_path): the launcher's own choice, always the u32 multiply-add
+// kernel, or always the int8 matrix-core kernel over the prepared key (ks_matrix.h; only where ksm_admitted)
+constexpr int kKsPathAuto = 0, kKsPathScalar = 1, kKsPathMatrix = 2;
+// How key_switch would send out a batch.  hipErrorInvalidValue: kKsPathMatrix on a decomposer that is not admitted.
+struct KeySwitchPlanInfo {
+  bool matrix;
+  unsigned grid_x, grid_y;  // column tiles and sample tiles of workgroups
+  unsigned splits;          // gridDim.z; more than one: the output is zeroed first, partial sums are added
+  u32 per_split;            // mask words (scalar) or 32-word super-blocks (matrix) per split
+};
+hipError_t key_switch_plan(const KsParams& K, u32 big_n, u32 n, size_t batch, int path, KeySwitchPlanInfo* out);
+// the prepared key of the matrix path: bytes, and ksk [big_n*levels][n+1] -> prepared
+size_t ksk_matrix_bytes(const KsParams& K, u32 big_n, u32 n);
+hipError_t ksk_prepare_matrix(hipStream_t s, const KsParams& K, u32 big_n, u32 n, const u32* ksk, void* prepared);
+// key_switch_lwe over a batch: lwe_in [batch][big_n+1], ksk [big_n*levels][n+1], out [batch][n+1]; ksk_matrix: the
+// same key prepared by ksk_prepare_matrix (may be null with kKsPathScalar)
 hipError_t key_switch(hipStream_t s, const KsParams& K, u32 big_n, u32 n, const u32* lwe_in,
-                      size_t batch, const u32* ksk, u32* lwe_out);
+                      size_t batch, const u32* ksk, u32* lwe_out, const void* ksk_matrix, int path);
 
 // ---- packing key switch (pbs_wave.h::pack_lwe_team): `groups` outputs of up to N LWE ciphertexts of dimension d each
 // cols [groups][d+1][N] = the transposed ciphertexts of lwe_in [groups][per_group][d+1], zero above per_group

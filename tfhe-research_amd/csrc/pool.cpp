@@ -137,6 +137,24 @@ int tfhe_pool_set_kernel_shape(tfhe_pool* pool, int shape) {
   return TFHE_OK;
 }
 
+int tfhe_pool_set_key_switch_path(tfhe_pool* pool, int path) {
+  if (!pool) return TFHE_ERR_INVALID_ARGUMENT;
+  for (size_t i = 0; i < pool->members.size(); ++i) {
+    int st = tfhe_context_set_key_switch_path(pool->members[i], path);
+    if (st) return member_fail(pool, i, st);
+  }
+  return TFHE_OK;
+}
+
+int tfhe_pool_debug_key_switch_plan(tfhe_pool* pool, size_t member, size_t batch, int* path, unsigned* grid_x,
+                                    unsigned* grid_y, unsigned* splits) {
+  if (!pool || member >= pool->members.size()) return TFHE_ERR_INVALID_ARGUMENT;
+  size_t first, count;
+  shard(batch, pool->members.size(), member, &first, &count);
+  int st = tfhe_debug_key_switch_plan(pool->members[member], count, path, grid_x, grid_y, splits);
+  return st ? member_fail(pool, member, st) : TFHE_OK;
+}
+
 int tfhe_pool_set_bootstrap_order(tfhe_pool* pool, int ks_first) {
   if (!pool) return TFHE_ERR_INVALID_ARGUMENT;
   for (size_t i = 0; i < pool->members.size(); ++i) {
