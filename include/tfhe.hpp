@@ -733,6 +733,68 @@ inline std::vector<LweCiphertext> dense_bootstrap(Engine& e, const std::vector<L
     out.push_back(LweCiphertext{std::vector<uint32_t>(res.begin() + o * words, res.begin() + (o + 1) * words)});
   return out;
 }
+// ---- encrypted convolutions (tfhe_hip.h states the operation; first device only) ----
+// A prepared set of clear weight polynomials: weights [O][C][N] row-major int32, |w| small enough for the backend
+// (TFHE_ERR_EXACTNESS with the reason otherwise).  Move-only; released with the object.
+class PolyWeights {
+ public:
+  PolyWeights(Engine& e, const std::vector<int32_t>& weights, size_t outputs, size_t channels) {
+    if (outputs == 0 || channels == 0 || weights.size() != outputs * channels * e.params().degree())
+      throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "weights [O][C][N]");
+    e.check(tfhe_prepare_poly_weights(e.raw(), weights.data(), outputs, channels, &w_));
+  }
+  PolyWeights(const PolyWeights&) = delete;
+  PolyWeights& operator=(const PolyWeights&) = delete;
+  PolyWeights(PolyWeights&& o) noexcept : w_(o.w_) { o.w_ = nullptr; }
+  ~PolyWeights() { tfhe_poly_weights_destroy(w_); }
+  const tfhe_poly_weights* raw() const { return w_; }
+  size_t outputs() const { return info().outputs; }
+  size_t channels() const { return info().channels; }
+  unsigned weight_bits() const { return info().weight_bits; }
+  unsigned rows_per_pass() const { return info().rows_per_pass; }
+
+ private:
+  struct Info {
+    size_t outputs = 0, channels = 0;
+    unsigned weight_bits = 0, rows_per_pass = 0;
+  };
+  Info info() const {
+    Info i;
+    (void)tfhe_poly_weights_info(w_, &i.outputs, &i.channels, &i.weight_bits, &i.rows_per_pass);
+    return i;
+  }
+  tfhe_poly_weights* w_ = nullptr;
+};
+// Conv(W, bias; x) for ONE query: x holds the C input ciphertexts, bias [O][N] already ENCODED words or empty -> O
+// ciphertexts, out[o] = sum_c W[o][c](X) * x[c] (+ bias[o] on the body), negacyclic, wrapping
+inline std::vector<GlweCiphertext> glwe_conv(Engine& e, const std::vector<GlweCiphertext>& x, const PolyWeights& weights,
+                                             const std::vector<uint32_t>& bias = {}) {
+  const size_t glwe = size_t(e.params().glwe_dimension + 1) * e.params().degree(), outputs = weights.outputs();
+  if (x.size() != weights.channels()) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "one ciphertext per channel");
+  if (!bias.empty() && bias.size() != outputs * e.params().degree()) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "bias [O][N]");
+  std::vector<uint32_t> flat;
+  flat.reserve(x.size() * glwe);
+  for (const GlweCiphertext& ct : x) {
+    if (ct.data.size() != glwe) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "GLWE length");
+    flat.insert(flat.end(), ct.data.begin(), ct.data.end());
+  }
+  std::vector<uint32_t> res(outputs * glwe);
+  e.check(tfhe_glwe_conv_batch(e.raw(), flat.data(), 1, weights.raw(), bias.empty() ? nullptr : bias.data(), res.data()));
+  std::vector<GlweCiphertext> out;
+  for (size_t o = 0; o < outputs; ++o)
+    out.push_back(GlweCiphertext{std::vector<uint32_t>(res.begin() + o * glwe, res.begin() + (o + 1) * glwe)});
+  return out;
+}
+// sample_extract at every index of the list (each below N), in the list's order
+inline std::vector<LweCiphertext> sample_extract_indices(Engine& e, const GlweCiphertext& glwe, const std::vector<uint32_t>& indices) {
+  const size_t words = e.params().lwe_dimension_post_pbs() + 1;
+  std::vector<uint32_t> res(indices.size() * words);
+  e.check(tfhe_sample_extract_indices(e.raw(), glwe.data.data(), 1, indices.data(), indices.size(), res.data()));
+  std::vector<LweCiphertext> out;
+  for (size_t i = 0; i < indices.size(); ++i)
+    out.push_back(LweCiphertext{std::vector<uint32_t>(res.begin() + i * words, res.begin() + (i + 1) * words)});
+  return out;
+}
 // bootstrapping_key_gen bootstrapping.rs:23-56; the generated key is also installed in the engine.
 // bmmp = true makes the key of the unrolled blind rotation instead (notes/BMMP Bootstrapping.md:22-24:
 // GGSW(s s'), GGSW(s (1-s')), GGSW(s' (1-s)) per pair of key bits; N = 512, even n).

@@ -600,6 +600,67 @@ int tfhe_dense_bootstrap_batch_device(tfhe_context *ctx, const uint32_t *x, size
                                       const int32_t *weights, const uint32_t *bias, size_t outputs,
                                       const uint32_t *test_vector_poly, size_t tv_count, uint32_t *lwe_out);
 
+/* ---- encrypted convolutions (no reference counterpart) --------------------------------------------
+ * A matrix of clear polynomials with small integer coefficients times a batch of GLWE ciphertexts: the general leveled
+ * operation on packed ciphertexts that needs no GGSW (tfhe_glwe_mul_monomial_batch is the case of one weight +-X^r).
+ *
+ *   Conv(W, bias; x):  out[q][o][p] = sum_{c<C} W[o][c](X) * x[q][c][p](X)   in Z_{2^32}[X] / (X^N + 1),   p = 0..k
+ *                      out[q][o][k] += bias[o]                                                  (bias may be NULL)
+ *
+ * x [queries][C][k+1][N]: C GLWE ciphertexts per query, one per input channel; W [O][C][N] int32 weight polynomials;
+ * bias [O][N] already ENCODED words; out [queries][O][k+1][N].  The arithmetic is wrapping 32-bit with the negacyclic
+ * wrap, so for any GLWE key phase(out[q][o]) = sum_c W[o][c] * phase(x[q][c]) + bias[o] mod 2^32 exactly, noise
+ * included: per output coefficient the noise variance is sum_c ||W[o][c]||_2^2 times the inputs'.  An H x W image packed
+ * row-major into one GLWE times a kernel whose tap (dy, dx) sits at coefficient (kh-1-dy) W + (kw-1-dx) carries output
+ * pixel (y, x) of the "valid" correlation at coefficient (y+kh-1) W + (x+kw-1); the sum over c is a convolution layer
+ * (nn.py::Conv2d).  The same product is the inner product of a packed query with a clear database column.
+ *
+ * Weights are prepared once (tfhe_prepare_poly_weights: their forward transforms, on the device; this one call
+ * synchronises, and it takes HOST weights because the admission needs max |w|).  weight_bits is the smallest b with
+ * every |w| <= 2^b, and the backend must admit some number of rows R >= 1 at base 2^weight_bits under its exactness
+ * rule for R rows (the complex transform: FftField::error_bound(log N, R, weight_bits) < 1/4; the prime fields: log2 R +
+ * log N + weight_bits + key_bits < exact_bits; each field's largest row count and small operand): rows_per_pass is the
+ * largest such R.  If there is none the call returns TFHE_ERR_EXACTNESS with the reason in tfhe_last_error.  At most
+ * rows_per_pass channels are summed in the transform domain; the passes are lifted to u32 on their own and meet in
+ * wrapping additions, so the words do not depend on rows_per_pass.  Splitting larger weights into limbs is out of
+ * scope (the noise grows with ||w||_2 anyway).  A weight set belongs to the device, backend and ring degree of the
+ * context that prepared it, outlives that context's calls, and is destroyed by the caller (NULL is allowed).
+ *
+ * Plan.  Per call the queries * C * (k+1) ciphertext polynomials are transformed into the workspace of
+ * tfhe_context_reserve_glwe_conv(max_queries, max_channels) (8 * parts * N bytes each, parts = 1 or 2 spectra by
+ * backend: host arithmetic only), then one launch of queries * O teams multiplies, accumulates, transforms back and
+ * lifts (csrc/glwe_conv.h).  tfhe_context_set_glwe_conv_rows(rows) fixes the channels per pass (0: automatic, the
+ * admitted maximum); a value above what the backend admits for any weights is refused there, one above a weight set's
+ * rows_per_pass at the call.  tfhe_debug_glwe_conv_plan reports rows per pass, passes and teams of a call.
+ *
+ * The _device forms enqueue on the context's stream only, allocate nothing after the reserve call and can be
+ * captured; a call beyond the reservation is refused and names its need in bytes.  The host forms reserve for
+ * themselves.  Refused with TFHE_ERR_INVALID_ARGUMENT and a message in tfhe_last_error: NULL x / weights / out,
+ * queries, outputs or channels of 0, out overlapping x, weights of another context's device, backend or ring,
+ * queries * O or queries * C * (k+1) >= 2^31.
+ *
+ * tfhe_sample_extract_indices: lwe_out[b][i] = tfhe_sample_extract_batch(glwe[b], indices[i]) for i < count -- a
+ * convolution layer reads hundreds of coefficients per GLWE.  glwe [batch][k+1][N], lwe_out [batch][count][k N + 1].
+ * The host form refuses an index >= N; the _device form takes indices on the device and reads them mod N. */
+typedef struct tfhe_poly_weights tfhe_poly_weights;
+int tfhe_prepare_poly_weights(tfhe_context *ctx, const int32_t *weights, size_t outputs, size_t channels,
+                              tfhe_poly_weights **out);
+void tfhe_poly_weights_destroy(tfhe_poly_weights *weights);
+int tfhe_poly_weights_info(const tfhe_poly_weights *weights, size_t *outputs, size_t *channels, unsigned *weight_bits,
+                           unsigned *rows_per_pass);
+int tfhe_context_reserve_glwe_conv(tfhe_context *ctx, size_t max_queries, size_t max_channels);
+int tfhe_context_set_glwe_conv_rows(tfhe_context *ctx, unsigned rows);
+int tfhe_debug_glwe_conv_plan(tfhe_context *ctx, const tfhe_poly_weights *weights, size_t queries, unsigned *rows_per_pass,
+                              unsigned *passes, unsigned *teams);
+int tfhe_glwe_conv_batch(tfhe_context *ctx, const uint32_t *x, size_t queries, const tfhe_poly_weights *weights,
+                         const uint32_t *bias, uint32_t *out);
+int tfhe_glwe_conv_batch_device(tfhe_context *ctx, const uint32_t *x, size_t queries, const tfhe_poly_weights *weights,
+                                const uint32_t *bias, uint32_t *out);
+int tfhe_sample_extract_indices(tfhe_context *ctx, const uint32_t *glwe, size_t batch, const uint32_t *indices, size_t count,
+                                uint32_t *lwe_out);
+int tfhe_sample_extract_indices_device(tfhe_context *ctx, const uint32_t *glwe, size_t batch, const uint32_t *indices,
+                                       size_t count, uint32_t *lwe_out);
+
 /* ---- test_vector.rs / boolean.rs ---------------------------------------------------------- */
 /* construct_test_from_lut: test_vector.rs:38-67 (host-side, no GPU).  out [N] */
 int tfhe_construct_test_from_lut(const tfhe_params *params, const uint32_t *lut, size_t lut_len,

@@ -26,6 +26,7 @@ pub struct CTfheParams {
 }
 
 #[repr(C)] pub struct TfheContext { _private: [u8; 0] }
+#[repr(C)] pub struct TfhePolyWeights { _private: [u8; 0] }
 #[repr(C)] pub struct TfhePool { _private: [u8; 0] }
 
 extern "C" {
@@ -86,6 +87,16 @@ extern "C" {
     fn tfhe_dense_bootstrap_batch(ctx: *mut TfheContext, x: *const u32, queries: usize, inputs: usize, weights: *const i32,
                                   bias: *const u32, outputs: usize, test_vector_poly: *const u32, tv_count: usize,
                                   lwe_out: *mut u32) -> c_int;
+    // encrypted convolutions (include/tfhe_hip.h)
+    fn tfhe_prepare_poly_weights(ctx: *mut TfheContext, weights: *const i32, outputs: usize, channels: usize,
+                                 out: *mut *mut TfhePolyWeights) -> c_int;
+    fn tfhe_poly_weights_destroy(weights: *mut TfhePolyWeights);
+    fn tfhe_poly_weights_info(weights: *const TfhePolyWeights, outputs: *mut usize, channels: *mut usize, weight_bits: *mut u32,
+                              rows_per_pass: *mut u32) -> c_int;
+    fn tfhe_glwe_conv_batch(ctx: *mut TfheContext, x: *const u32, queries: usize, weights: *const TfhePolyWeights,
+                            bias: *const u32, out: *mut u32) -> c_int;
+    fn tfhe_sample_extract_indices(ctx: *mut TfheContext, glwe: *const u32, batch: usize, indices: *const u32, count: usize,
+                                   lwe_out: *mut u32) -> c_int;
     fn tfhe_cmux_batch(ctx: *mut TfheContext, ggsw: *const u32, ggsw_count: usize, ct0: *const u32,
                        ct1: *mut u32, batch: usize, glwe_out: *mut u32) -> c_int;
     fn tfhe_gate_batch(ctx: *mut TfheContext, truth: *const u32, ct0: *const u32, ct1: *const u32,
@@ -458,6 +469,58 @@ pub fn dense_bootstrap(bk: &GpuBootstrappingKey, x: &Array3<u32>, weights: &Arra
                                    test_vectors.as_slice().unwrap().as_ptr(), test_vectors.nrows(),
                                    out.as_slice_mut().unwrap().as_mut_ptr())
     }, "dense_bootstrap");
+    out
+}
+
+/// A prepared set of clear weight polynomials `weights` (O, C, N) for `glwe_conv` (no reference counterpart); panics with
+/// the backend's reason where it admits no pass at their magnitude.  Released on drop.
+pub struct PolyWeights { raw: *mut TfhePolyWeights, pub outputs: usize, pub channels: usize, pub weight_bits: u32, pub rows_per_pass: u32 }
+
+impl PolyWeights {
+    pub fn new(bk: &GpuBootstrappingKey, weights: &Array3<i32>) -> Self {
+        let (outputs, channels, n) = weights.dim();
+        assert!(n == 1usize << bk.params.glwe_poly_degree, "PolyWeights: weights (O, C, N)");
+        let mut raw = std::ptr::null_mut();
+        check(bk.ctx, unsafe {
+            tfhe_prepare_poly_weights(bk.ctx, weights.as_slice().unwrap().as_ptr(), outputs, channels, &mut raw)
+        }, "prepare_poly_weights");
+        let (mut o, mut c, mut bits, mut rows) = (0usize, 0usize, 0u32, 0u32);
+        let st = unsafe { tfhe_poly_weights_info(raw, &mut o, &mut c, &mut bits, &mut rows) };
+        assert!(st == 0, "tfhe_poly_weights_info: status {st}");
+        PolyWeights { raw, outputs: o, channels: c, weight_bits: bits, rows_per_pass: rows }
+    }
+}
+
+impl Drop for PolyWeights {
+    fn drop(&mut self) {
+        unsafe { tfhe_poly_weights_destroy(self.raw) };
+    }
+}
+
+/// Conv(W, bias; x): `x` (queries * C, k+1, N) with the C channels of a query in a row, `bias` (O, N) already ENCODED words
+/// -> (queries * O, k+1, N), out[q][o] = sum_c W[o][c](X) * x[q][c] negacyclic and wrapping, bias[o] added to the body.
+pub fn glwe_conv(bk: &GpuBootstrappingKey, x: &Array3<u32>, weights: &PolyWeights, bias: Option<&Array2<u32>>) -> Array3<u32> {
+    let (rows, polys, n) = x.dim();
+    assert!(rows % weights.channels == 0 && polys == bk.params.glwe_dimension as usize + 1 && n == 1usize << bk.params.glwe_poly_degree
+            && bias.map_or(true, |b| b.dim() == (weights.outputs, n)), "glwe_conv: x (queries * C, k+1, N), bias (O, N)");
+    let queries = rows / weights.channels;
+    let mut out = Array3::<u32>::zeros((queries * weights.outputs, polys, n));
+    check(bk.ctx, unsafe {
+        tfhe_glwe_conv_batch(bk.ctx, x.as_slice().unwrap().as_ptr(), queries, weights.raw,
+                             bias.map_or(std::ptr::null(), |b| b.as_slice().unwrap().as_ptr()), out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "glwe_conv");
+    out
+}
+
+/// sample_extract of every GLWE of `glwe` (batch, k+1, N) at every index of `indices` (each below N) -> (batch, count, kN+1)
+pub fn sample_extract_indices(bk: &GpuBootstrappingKey, glwe: &Array3<u32>, indices: &Array1<u32>) -> Array3<u32> {
+    let (batch, polys, n) = glwe.dim();
+    assert!(polys == bk.params.glwe_dimension as usize + 1 && n == 1usize << bk.params.glwe_poly_degree, "sample_extract_indices: glwe (batch, k+1, N)");
+    let mut out = Array3::<u32>::zeros((batch, indices.len(), (polys - 1) * n + 1));
+    check(bk.ctx, unsafe {
+        tfhe_sample_extract_indices(bk.ctx, glwe.as_slice().unwrap().as_ptr(), batch, indices.as_slice().unwrap().as_ptr(), indices.len(),
+                                    out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "sample_extract_indices");
     out
 }
 

@@ -331,6 +331,39 @@ class SystemRng:
         return (loc + scale * z).reshape(shape)
 
 
+class PolyWeights:
+    """A prepared set of clear weight polynomials (Context.prepare_poly_weights): lives on the device of the context that
+    prepared it, for that context's backend and ring; usable until close()."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().tfhe_poly_weights_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self) -> dict:
+        """outputs, channels, weight_bits (the smallest b with every |w| <= 2^b) and rows_per_pass (the channels the
+        backend's exactness rule admits in one pass at that magnitude)"""
+        o, c, bits, rows = C.c_size_t(), C.c_size_t(), C.c_uint(), C.c_uint()
+        Context._check_quiet(lib().tfhe_poly_weights_info(self._h, C.byref(o), C.byref(c), C.byref(bits), C.byref(rows)),
+                             "the weight set is closed")
+        return {"outputs": o.value, "channels": c.value, "weight_bits": bits.value, "rows_per_pass": rows.value}
+
+
 class Context:
     """One GPU context = one device + one stream + one loaded BootstrappingKey."""
 
@@ -1314,6 +1347,115 @@ class Context:
                                                      C.c_size_t(n_tv), _hp(res)))
         return res
 
+    # -- encrypted convolutions (include/tfhe_hip.h states the operation; nn.py::Conv2d builds layers) ------------
+    def prepare_poly_weights(self, weights) -> "PolyWeights":
+        """weights [O][C][N] small integers (host) -> the prepared set glwe_conv takes.  Refused with TFHE_ERR_EXACTNESS
+        and the reason where the backend admits no pass at their magnitude.  Synchronises; prepare once, use often."""
+        w = np.asarray(weights)
+        if w.ndim != 3 or w.size == 0 or int(w.shape[2]) != self.params.N or not np.issubdtype(w.dtype, np.integer):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"prepare_poly_weights: integer weights [O][C][{self.params.N}] expected, got "
+                                                       f"{tuple(w.shape)}")
+        if int(w.max()) >= 1 << 31 or int(w.min()) < -(1 << 31):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "prepare_poly_weights: weights must fit int32")
+        w = np.ascontiguousarray(w, dtype=np.int32)
+        handle = C.c_void_p()
+        self._check(lib().tfhe_prepare_poly_weights(self._h, C.c_void_p(w.ctypes.data), C.c_size_t(w.shape[0]),
+                                                    C.c_size_t(w.shape[1]), C.byref(handle)))
+        return PolyWeights(handle)
+
+    def reserve_glwe_conv(self, max_queries: int, max_channels: int):
+        """size the workspace of the device form of glwe_conv: the prepared spectra of max_queries * max_channels
+        ciphertexts (a maximum: smaller calls fit)"""
+        self._check(lib().tfhe_context_reserve_glwe_conv(self._h, C.c_size_t(max_queries), C.c_size_t(max_channels)))
+
+    def set_glwe_conv_rows(self, rows: int):
+        """channels a convolution sums in the transform domain before it lifts (0: automatic, the admitted maximum); the
+        bits do not depend on it"""
+        self._check(lib().tfhe_context_set_glwe_conv_rows(self._h, C.c_uint(rows)))
+
+    def glwe_conv_plan(self, weights: "PolyWeights", queries: int) -> dict:
+        """how a convolution of this shape goes out (tfhe_debug_glwe_conv_plan)"""
+        rows, passes, teams = C.c_uint(), C.c_uint(), C.c_uint()
+        self._check(lib().tfhe_debug_glwe_conv_plan(self._h, weights._h, C.c_size_t(queries), C.byref(rows), C.byref(passes),
+                                                    C.byref(teams)))
+        return {"rows_per_pass": rows.value, "passes": passes.value, "teams": teams.value}
+
+    def glwe_conv(self, x, weights: "PolyWeights", bias=None, out=None):
+        """Conv(W, bias; x): out[q][o] = sum_c W[o][c](X) * x[q][c] (+ bias[o], already encoded, on the body), negacyclic,
+        wrapping.  x [queries][C][k+1][N] (or [C][k+1][N]: one query), bias [O][N] -> [queries][O][k+1][N].
+        numpy: host form, blocks.  torch: in the workspace of reserve_glwe_conv on torch's current stream, enqueues only;
+        `out` may name the result tensor."""
+        p = self.params
+        if not isinstance(weights, PolyWeights) or not weights._h:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "glwe_conv: weights from prepare_poly_weights expected")
+        info = weights.info()
+        on_device = _is_torch(x)
+        if on_device:
+            import torch
+            if x.dim() == 3:
+                x = x.unsqueeze(0)
+            if x.dim() != 4 or x.element_size() != 4 or x.is_floating_point() or not x.is_contiguous() or not x.is_cuda:
+                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "glwe_conv: x [queries][C][k+1][N] (contiguous 32-bit integers, on the device) expected")
+            if bias is not None and not _is_torch(bias):
+                bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.uint32).view(np.int32)).to(x.device)
+            if bias is not None and (bias.element_size() != 4 or bias.is_floating_point() or not bias.is_contiguous() or bias.device != x.device):
+                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"glwe_conv: bias must be a contiguous 32-bit integer tensor on {x.device}")
+        else:
+            x = _np(x)
+            if x.ndim == 3:
+                x = x[None]
+            bias = None if bias is None else _np(bias)
+        if len(x.shape) != 4 or tuple(int(v) for v in x.shape[1:]) != (info["channels"], p.k + 1, p.N):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"glwe_conv: x [queries][{info['channels']}][{p.k + 1}][{p.N}] expected, got "
+                                                       f"{tuple(x.shape)}")
+        if bias is not None and tuple(int(v) for v in bias.shape) != (info["outputs"], p.N):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"glwe_conv: bias [{info['outputs']}][{p.N}] expected, got {tuple(bias.shape)}")
+        q = int(x.shape[0])
+        shape = (q, info["outputs"], p.k + 1, p.N)
+        if on_device:
+            self._bind_torch()
+            out = self._lookup_out("glwe_conv", out, shape, x)
+            self._check(lib().tfhe_glwe_conv_batch_device(self._h, _dp(x), C.c_size_t(q), weights._h,
+                                                          _dp(bias) if bias is not None else None, _dp(out)))
+            return out
+        res = np.zeros(shape, dtype=np.uint32)
+        self._check(lib().tfhe_glwe_conv_batch(self._h, _hp(x), C.c_size_t(q), weights._h, _hp(bias) if bias is not None else None,
+                                               _hp(res)))
+        return res
+
+    def sample_extract_indices(self, glwe, indices, out=None):
+        """out[b][i] = sample_extract(glwe[b], indices[i]): glwe [batch][k+1][N], indices [count] < N ->
+        [batch][count][k N + 1].  numpy: host form.  torch: enqueues on torch's current stream (host indices are uploaded
+        on every call, which synchronises: pass a device tensor in a loop)."""
+        p = self.params
+        if _is_torch(glwe):
+            import torch
+            if glwe.element_size() != 4 or glwe.is_floating_point() or not glwe.is_contiguous() or not glwe.is_cuda or \
+                    tuple(glwe.shape[-2:]) != (p.k + 1, p.N):
+                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "sample_extract_indices: glwe [batch][k+1][N] (contiguous 32-bit integers, on the device) expected")
+            if not _is_torch(indices):
+                idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+                if idx.size == 0 or int(idx.min()) < 0 or int(idx.max()) >= p.N:
+                    raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "sample_extract_indices: indices in [0, N) expected")
+                indices = torch.from_numpy(idx.astype(np.uint32).view(np.int32)).to(glwe.device)
+            if indices.element_size() != 4 or indices.is_floating_point() or not indices.is_contiguous() or indices.device != glwe.device:
+                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"sample_extract_indices: indices must be a contiguous 32-bit integer tensor on {glwe.device}")
+            batch, count = glwe.numel() // ((p.k + 1) * p.N), indices.numel()
+            self._bind_torch()
+            out = self._lookup_out("sample_extract_indices", out, (batch, count, p.big_n + 1), glwe)
+            self._check(lib().tfhe_sample_extract_indices_device(self._h, _dp(glwe), C.c_size_t(batch), _dp(indices),
+                                                                 C.c_size_t(count), _dp(out)))
+            return out
+        g = _np(glwe).reshape(-1, p.k + 1, p.N)
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        if idx.size == 0 or int(idx.min()) < 0 or int(idx.max()) >= 1 << 32:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "sample_extract_indices: indices in [0, N) expected")
+        idx = idx.astype(np.uint32)
+        res = np.zeros((g.shape[0], idx.size, p.big_n + 1), dtype=np.uint32)
+        self._check(lib().tfhe_sample_extract_indices(self._h, _hp(g), C.c_size_t(g.shape[0]), _hp(idx), C.c_size_t(idx.size),
+                                                      _hp(res)))
+        return res
+
     def lut_gate(self, truth, cts, out=None):
         """Gate of m = len(cts) inputs (notes/Boolean Gates.md:2-11): one PBS of sum_i 2^i * cts[i]
         (cts[0] = rightmost input) with lut[x] = truth[x mod 2^m]; needs log_p >= m."""
@@ -1583,6 +1725,23 @@ class Context:
         samples = rng.integers(0, 1 << 32, size=(msg.size, p.k + 1, p.N), dtype=np.uint64).astype(np.uint32)
         samples[:, p.k, :] = self._noise(rng, p.glwe_std_dev, (msg.size, p.N))
         samples[:, p.k, 0] += msg << np.uint32(32 - p.log_p - p.padding_bits)
+        return self.glwe_encrypt_zero(glwe_sk, samples)
+
+    def encrypt_glwe_messages(self, glwe_sk, messages, rng=None) -> np.ndarray:
+        """GLWE encryptions under glwe_sk (glwe_std_dev) of messages [count][N] (or [N]: one), every coefficient j
+        carrying encode(messages[..][j]), values < 2^log_p -> [count][k+1][N]: a packed image for glwe_conv.  Masks and
+        errors come from the OS CSPRNG unless the test hook `rng=` is given (see generate_keys)."""
+        p = self.params
+        rng = rng if rng is not None else SystemRng()
+        msg = np.asarray(messages, dtype=np.uint32)
+        if msg.ndim == 1:
+            msg = msg[None]
+        if msg.ndim != 2 or int(msg.shape[1]) != p.N:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"encrypt_glwe_messages: messages [count][{p.N}] expected, got {tuple(msg.shape)}")
+        if msg.size and int(msg.max()) >> p.log_p:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "encrypt_glwe_messages: messages must be below 2^log_p")
+        samples = rng.integers(0, 1 << 32, size=(msg.shape[0], p.k + 1, p.N), dtype=np.uint64).astype(np.uint32)
+        samples[:, p.k, :] = self._noise(rng, p.glwe_std_dev, msg.shape) + (msg << np.uint32(32 - p.log_p - p.padding_bits))
         return self.glwe_encrypt_zero(glwe_sk, samples)
 
     def encrypt_test_vector(self, glwe_sk, lut, rng=None) -> np.ndarray:

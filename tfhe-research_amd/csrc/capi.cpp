@@ -217,6 +217,69 @@ PbsParams packing_params(const tfhe_context* ctx) {
   return P;
 }
 
+// Why this backend cannot sum `rows` products of digits of magnitude 2^lb with key words in the transform domain and lift
+// the sum exactly, or "" if it can: every backend's exactness rule in its (rows, log_base) form -- the complex transform's
+// FftField::error_bound(log N, rows, lb) < kMaxError, log2 rows + log N + lb + key_bits < exact_bits in the prime fields,
+// and each field's kMaxRows / kSmallBits / kMaxLogBase.  The nouns name what the caller sums: the packing key switch
+// the (k+1) l_ks rows of a slice in the KS base, the convolution the channels of a pass at the weights' magnitude.
+struct ExactnessNouns {
+  const char* base;  // what lb is
+  const char* rows;  // what the rows are
+  const char* unit;  // what is summed before a lift
+};
+std::string exactness_refusal(const tfhe_context* ctx, int rows, int lb, const ExactnessNouns& noun) {
+  const tfhe_params& p = ctx->params;
+  const double bits = std::log2((double)rows) + p.glwe_poly_degree + lb;
+  auto prime = [&](const char* name, double key_bits, double exact_bits, int max_rows, int small_bits, int max_log_base) {
+    char buf[256];
+    if (lb > max_log_base || lb > small_bits) {
+      std::snprintf(buf, sizeof buf, "%s: %s %d exceeds the backend's largest gadget base 2^%d", name, noun.base, lb,
+                    std::min(max_log_base, small_bits));
+      return std::string(buf);
+    }
+    if (rows > max_rows) {
+      std::snprintf(buf, sizeof buf, "%s: %s = %d rows per %s exceed the backend's %d", name, noun.rows, rows, noun.unit, max_rows);
+      return std::string(buf);
+    }
+    if (!(bits + key_bits < exact_bits)) {
+      std::snprintf(buf, sizeof buf, "%s: a %s of %s = %d rows in base 2^%d needs %.2f bits, the field lifts %.2f", name, noun.unit,
+                    noun.rows, rows, lb, bits + key_bits, exact_bits);
+      return std::string(buf);
+    }
+    return std::string();
+  };
+  switch (ctx->field) {
+    case launch::kFieldFp64:
+      return prime("fp64-p42", FpField::key_bits(), FpField::exact_bits(), FpField::kMaxRows, FpField::kSmallBits, FpField::kMaxLogBase);
+    case launch::kFieldFp49:
+      return prime("fp64-p49", Fp49Field::key_bits(), Fp49Field::exact_bits(), Fp49Field::kMaxRows, Fp49Field::kSmallBits, Fp49Field::kMaxLogBase);
+    case launch::kFieldGoldilocks:
+      return prime("goldilocks", GlField::key_bits(), GlField::exact_bits(), GlField::kMaxRows, GlField::kSmallBits, GlField::kMaxLogBase);
+    case launch::kFieldGoldilocksSplit:
+      return prime("goldilocks-split", GlSplitField::key_bits(), GlSplitField::exact_bits(), GlSplitField::kMaxRows,
+                   GlSplitField::kSmallBits, GlSplitField::kMaxLogBase);
+    default: {
+      char buf[256];
+      if (lb > FftField::kMaxLogBase || lb > FftField::kSmallBits) {
+        std::snprintf(buf, sizeof buf, "fp64-fft: %s %d exceeds FftField::kMaxLogBase = %d", noun.base, lb, FftField::kMaxLogBase);
+        return std::string(buf);
+      }
+      if (rows > FftField::kMaxRows) {
+        std::snprintf(buf, sizeof buf, "fp64-fft: %s = %d rows per %s exceed FftField::kMaxRows = %d", noun.rows, rows, noun.unit,
+                      FftField::kMaxRows);
+        return std::string(buf);
+      }
+      const double err = FftField::error_bound((int)p.glwe_poly_degree, rows, lb);
+      if (!(err < FftField::kMaxError)) {
+        std::snprintf(buf, sizeof buf, "fp64-fft: rounding bound %.4g of a %s of %d rows in base 2^%d is not below %.4g", err,
+                      noun.unit, rows, lb, FftField::kMaxError);
+        return std::string(buf);
+      }
+      return std::string();
+    }
+  }
+}
+
 // ---- timing spans: events 0/1 bracket a rotation, 2/3 a key switch (tfhe_last_kernel_ms)
 enum Span { kRotationSpan = 0, kKeySwitchSpan = 2 };
 
@@ -604,7 +667,7 @@ void tfhe_context_destroy(tfhe_context* ctx) {
                   ctx->d_lwe_big, ctx->d_lwe_out, ctx->d_lwe_ks, ctx->d_glwe_a, ctx->d_glwe_b, ctx->d_glwe_c,
                   ctx->d_tv,     ctx->d_misc,   ctx->d_ggsw_tmp, ctx->d_ggsw_raw,
                   ctx->d_key_tmp, ctx->d_pksk, ctx->d_pack_cols, ctx->d_lookup_ws, ctx->d_tree_ws,
-                  ctx->d_demux_ws, ctx->d_program_ws, ctx->d_dense_ws, ctx->d_ksk_matrix};
+                  ctx->d_demux_ws, ctx->d_program_ws, ctx->d_dense_ws, ctx->d_ksk_matrix, ctx->d_conv_ws};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& g : ctx->gate_tvs)
@@ -2001,6 +2064,222 @@ int tfhe_dense_bootstrap_batch(tfhe_context* ctx, const uint32_t* x, size_t quer
   return s.download_and_wait(kOut, lwe_out);
 }
 
+// ---------------------------------------------------------------------------------- encrypted convolutions
+// include/tfhe_hip.h states the operation, glwe_conv.h::glwe_conv_team the team and its exactness bound.
+namespace {
+
+constexpr ExactnessNouns kConvNouns = {"weight_bits", "rows_per_pass", "pass"};
+
+// The most channels this backend sums exactly in one pass at weights of magnitude 2^bits, or 0 with the reason in *why.
+// exactness_refusal is monotone in the rows, so the largest admitted count is found by bisection.
+unsigned conv_rows_admitted(const tfhe_context* ctx, int bits, std::string* why) {
+  *why = exactness_refusal(ctx, 1, bits, kConvNouns);
+  if (!why->empty()) return 0;
+  unsigned lo = 1, hi = (1u << 20) + 1;  // admitted, not admitted (beyond every field's kMaxRows)
+  while (hi - lo > 1) {
+    const unsigned mid = lo + (hi - lo) / 2;
+    (exactness_refusal(ctx, (int)mid, bits, kConvNouns).empty() ? lo : hi) = mid;
+  }
+  return lo;
+}
+
+size_t conv_poly_bytes(const tfhe_context* ctx) { return (size_t)ctx->parts * ctx->N * sizeof(u64); }  // one prepared polynomial
+
+int reserve_conv(tfhe_context* ctx, size_t polys) {
+  if (polys <= ctx->conv_ws_polys) return TFHE_OK;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->conv_ws_polys = 0;
+  if (ctx->d_conv_ws) {
+    hipError_t e = hipFree(ctx->d_conv_ws);
+    ctx->d_conv_ws = nullptr;
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipFree(conv workspace)");
+  }
+  HIP_TRY(ctx, hipMalloc(&ctx->d_conv_ws, polys * conv_poly_bytes(ctx)));
+  ctx->conv_ws_polys = polys;
+  return TFHE_OK;
+}
+
+// everything about a convolution that can be refused on the host; -> the plan
+int check_conv(tfhe_context* ctx, const tfhe_poly_weights* w, size_t queries, launch::GlweConvPlanInfo* plan) {
+  if (!w) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null weights");
+  if (w->device != ctx->device || w->field != ctx->field || w->log_n != ctx->pbs.log_n)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "the weights were prepared by a context of another device, backend or ring degree");
+  if (queries == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "queries must be at least 1");
+  if (ctx->conv_rows > w->rows_per_pass)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "tfhe_context_set_glwe_conv_rows(" + std::to_string(ctx->conv_rows) + ") exceeds the " + std::to_string(w->rows_per_pass) +
+                    " rows per pass the backend admits at weight_bits = " + std::to_string(w->weight_bits));
+  if (queries > kMaxBatch ||
+      !launch::glwe_conv_plan(queries, (u32)w->channels, (u32)w->outputs, w->rows_per_pass, ctx->conv_rows, plan))
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "queries * outputs exceeds 2^31 - 1 (one workgroup per output ciphertext)");
+  if ((double)queries * (double)w->channels * (double)(ctx->params.glwe_dimension + 1) > (double)kMaxBatch)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "queries * channels * (k+1) exceeds 2^31 - 1");
+  return TFHE_OK;
+}
+
+int check_conv_args(tfhe_context* ctx, const u32* x, const tfhe_poly_weights* w, const u32* out, size_t queries,
+                    launch::GlweConvPlanInfo* plan) {
+  TFHE_TRY(check_present(ctx, {x, out}, 1, "null pointer"));
+  TFHE_TRY(check_conv(ctx, w, queries, plan));
+  if (overlap(out, queries * w->outputs * glwe_words(ctx), x, queries * w->channels * glwe_words(ctx)))
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "out overlaps x: every output reads every channel of its query");
+  return TFHE_OK;
+}
+
+}  // namespace
+
+int tfhe_prepare_poly_weights(tfhe_context* ctx, const int32_t* weights, size_t outputs, size_t channels, tfhe_poly_weights** out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {weights, out}, 1, "null pointer"));
+  *out = nullptr;
+  if (outputs == 0 || channels == 0 || outputs > kMaxBatch || channels > kMaxBatch ||
+      (double)outputs * (double)channels > (double)kMaxBatch)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "outputs and channels must be at least 1, their product below 2^31");
+  const size_t polys = outputs * channels, words = polys * ctx->N;
+  int64_t largest = 0;
+  for (size_t i = 0; i < words; ++i) largest = std::max<int64_t>(largest, std::llabs((long long)weights[i]));
+  int bits = 0;
+  while (((int64_t)1 << bits) < largest) ++bits;
+  std::string why;
+  const unsigned rows = conv_rows_admitted(ctx, bits, &why);
+  if (rows == 0) return fail(ctx, TFHE_ERR_EXACTNESS, "polynomial weights refused: " + why);
+  tfhe_poly_weights* w = new (std::nothrow) tfhe_poly_weights();
+  if (!w) return fail(ctx, TFHE_ERR_HIP, "out of host memory");
+  w->device = ctx->device;
+  w->field = ctx->field;
+  w->log_n = ctx->pbs.log_n;
+  w->outputs = outputs;
+  w->channels = channels;
+  w->weight_bits = (unsigned)bits;
+  w->rows_per_pass = rows;
+  DeviceWords raw;
+  hipError_t e = raw.alloc(words);
+  if (e == hipSuccess) e = hipMalloc(&w->d_spec, polys * (size_t)ctx->N * sizeof(u64));
+  if (e == hipSuccess) e = hipMemcpyAsync(raw.p, weights, words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess)
+    e = launch::conv_weights(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->d_tw, reinterpret_cast<const i32*>(raw.p), polys, w->d_spec);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the staging buffer goes away with this call
+  if (e != hipSuccess) {
+    tfhe_poly_weights_destroy(w);
+    return hip_fail(ctx, e, "tfhe_prepare_poly_weights");
+  }
+  *out = w;
+  return TFHE_OK;
+}
+
+void tfhe_poly_weights_destroy(tfhe_poly_weights* weights) {
+  if (!weights) return;
+  if (weights->d_spec && hipSetDevice(weights->device) == hipSuccess) (void)hipFree(weights->d_spec);
+  delete weights;
+}
+
+int tfhe_poly_weights_info(const tfhe_poly_weights* weights, size_t* outputs, size_t* channels, unsigned* weight_bits,
+                           unsigned* rows_per_pass) {
+  if (!weights) return TFHE_ERR_INVALID_ARGUMENT;
+  if (outputs) *outputs = weights->outputs;
+  if (channels) *channels = weights->channels;
+  if (weight_bits) *weight_bits = weights->weight_bits;
+  if (rows_per_pass) *rows_per_pass = weights->rows_per_pass;
+  return TFHE_OK;
+}
+
+int tfhe_context_reserve_glwe_conv(tfhe_context* ctx, size_t max_queries, size_t max_channels) {
+  TFHE_TRY(check_ctx(ctx));
+  if (max_queries == 0 || max_channels == 0 ||
+      (double)max_queries * (double)max_channels * (double)(ctx->params.glwe_dimension + 1) > (double)kMaxBatch)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "max_queries and max_channels must be at least 1, their product times k+1 below 2^31");
+  return reserve_conv(ctx, max_queries * max_channels * (ctx->params.glwe_dimension + 1));
+}
+
+int tfhe_context_set_glwe_conv_rows(tfhe_context* ctx, unsigned rows) {
+  if (!ctx) return TFHE_ERR_INVALID_ARGUMENT;
+  std::string why;
+  const unsigned most = conv_rows_admitted(ctx, 0, &why);  // what the backend admits for the smallest weights there are
+  if (rows > most)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "rows exceeds the " + std::to_string(most) + " rows per pass this backend admits at all (0: automatic)" +
+                    (why.empty() ? "" : ": " + why));
+  ctx->conv_rows = rows;
+  return TFHE_OK;
+}
+
+int tfhe_debug_glwe_conv_plan(tfhe_context* ctx, const tfhe_poly_weights* weights, size_t queries, unsigned* rows_per_pass,
+                              unsigned* passes, unsigned* teams) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {rows_per_pass, passes, teams}, 1, "null pointer"));
+  launch::GlweConvPlanInfo plan{};
+  TFHE_TRY(check_conv(ctx, weights, queries, &plan));
+  *rows_per_pass = plan.rows_per_pass;
+  *passes = plan.passes;
+  *teams = (unsigned)plan.teams;
+  return TFHE_OK;
+}
+
+int tfhe_glwe_conv_batch_device(tfhe_context* ctx, const uint32_t* x, size_t queries, const tfhe_poly_weights* weights,
+                                const uint32_t* bias, uint32_t* out) {
+  TFHE_TRY(check_ctx(ctx));
+  launch::GlweConvPlanInfo plan{};
+  TFHE_TRY(check_conv_args(ctx, x, weights, out, queries, &plan));
+  const size_t polys = queries * weights->channels * (ctx->params.glwe_dimension + 1);
+  if (polys > ctx->conv_ws_polys)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "the call needs " + std::to_string(polys * conv_poly_bytes(ctx)) + " bytes of convolution workspace (" +
+                    std::to_string(queries) + " queries, " + std::to_string(weights->channels) + " channels), " +
+                    std::to_string(ctx->conv_ws_polys * conv_poly_bytes(ctx)) + " are reserved (tfhe_context_reserve_glwe_conv)");
+  HIP_TRY(ctx, launch::bsk_prepare(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->pbs.k, ctx->d_tw, x, polys, ctx->d_conv_ws));
+  const GlweConvArgs args{ctx->d_conv_ws, weights->d_spec, bias, out, (u32)weights->channels, (u32)weights->outputs, plan.rows_per_pass};
+  HIP_TRY(ctx, launch::glwe_conv(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->pbs.k, ctx->d_tw, args, queries));
+  return TFHE_OK;
+}
+
+int tfhe_glwe_conv_batch(tfhe_context* ctx, const uint32_t* x, size_t queries, const tfhe_poly_weights* weights,
+                         const uint32_t* bias, uint32_t* out) {
+  TFHE_TRY(check_ctx(ctx));
+  launch::GlweConvPlanInfo plan{};
+  TFHE_TRY(check_conv_args(ctx, x, weights, out, queries, &plan));
+  TFHE_TRY(reserve_conv(ctx, queries * weights->channels * (ctx->params.glwe_dimension + 1)));
+  enum { kX, kBias, kOut };
+  Staging s(ctx, {queries * weights->channels * glwe_words(ctx), bias ? weights->outputs * (size_t)ctx->N : 0,
+                  queries * weights->outputs * glwe_words(ctx)});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(kX, x));
+  if (bias) TFHE_TRY(s.upload(kBias, bias));
+  TFHE_TRY(tfhe_glwe_conv_batch_device(ctx, s[kX], queries, weights, bias ? s[kBias] : nullptr, s[kOut]));
+  return s.download_and_wait(kOut, out);
+}
+
+namespace {
+int check_extract_indices(tfhe_context* ctx, const void* glwe, const void* indices, const void* lwe_out, size_t batch, size_t count) {
+  TFHE_TRY(check_present(ctx, {glwe, indices, lwe_out}, 1, "null pointer"));
+  if (batch == 0 || count == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "batch and count must be at least 1");
+  if ((double)batch * (double)count > (double)kMaxBatch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "batch * count exceeds 2^31 - 1");
+  return TFHE_OK;
+}
+}  // namespace
+
+int tfhe_sample_extract_indices_device(tfhe_context* ctx, const uint32_t* glwe, size_t batch, const uint32_t* indices,
+                                       size_t count, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_extract_indices(ctx, glwe, indices, lwe_out, batch, count));
+  HIP_TRY(ctx, launch::sample_extract_indices(ctx->stream, ctx->pbs.log_n, ctx->pbs.k, glwe, batch, indices, count, lwe_out));
+  return TFHE_OK;
+}
+
+int tfhe_sample_extract_indices(tfhe_context* ctx, const uint32_t* glwe, size_t batch, const uint32_t* indices, size_t count,
+                                uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_extract_indices(ctx, glwe, indices, lwe_out, batch, count));
+  for (size_t i = 0; i < count; ++i)
+    if (indices[i] >= ctx->N) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "sample index >= N (bootstrapping.rs:127)");
+  enum { kIn, kIndex, kOut };
+  Staging s(ctx, {batch * glwe_words(ctx), count, batch * count * big_lwe_words(ctx)});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(kIn, glwe));
+  TFHE_TRY(s.upload(kIndex, indices));
+  TFHE_TRY(tfhe_sample_extract_indices_device(ctx, s[kIn], batch, s[kIndex], count, s[kOut]));
+  return s.download_and_wait(kOut, lwe_out);
+}
+
 // ---------------------------------------------------------------------------------- encryption side
 // keygen / encrypt / decrypt with the caller's randomness already in the buffers (tfhe_hip.h)
 namespace {
@@ -2251,57 +2530,8 @@ size_t pack_cols_words_per_group(const tfhe_context* ctx) { return (ctx->pksk_di
 // R_c = (k+1) l_ks rows of one slice in the transform domain and nothing more (pbs_wave.h::pack_lwe_team), so the bounds
 // are the external product's with R_c rows and the KS base.
 std::string packing_refusal(const tfhe_context* ctx) {
-  const tfhe_params& p = ctx->params;
-  const int rows = (int)((p.glwe_dimension + 1) * ctx->ks.levels);
-  const int lb = (int)ctx->ks.log_base;
-  const double bits = std::log2((double)rows) + p.glwe_poly_degree + lb;
-  auto prime = [&](const char* name, double key_bits, double exact_bits, int max_rows, int small_bits, int max_log_base) {
-    char buf[256];
-    if (lb > max_log_base || lb > small_bits) {
-      std::snprintf(buf, sizeof buf, "%s: KS log_base %d exceeds the backend's largest gadget base 2^%d", name, lb,
-                    std::min(max_log_base, small_bits));
-      return std::string(buf);
-    }
-    if (rows > max_rows) {
-      std::snprintf(buf, sizeof buf, "%s: (k+1) l_ks = %d rows per slice exceed the backend's %d", name, rows, max_rows);
-      return std::string(buf);
-    }
-    if (!(bits + key_bits < exact_bits)) {
-      std::snprintf(buf, sizeof buf, "%s: a slice of (k+1) l_ks = %d rows in base 2^%d needs %.2f bits, the field lifts %.2f",
-                    name, rows, lb, bits + key_bits, exact_bits);
-      return std::string(buf);
-    }
-    return std::string();
-  };
-  switch (ctx->field) {
-    case launch::kFieldFp64:
-      return prime("fp64-p42", FpField::key_bits(), FpField::exact_bits(), FpField::kMaxRows, FpField::kSmallBits, FpField::kMaxLogBase);
-    case launch::kFieldFp49:
-      return prime("fp64-p49", Fp49Field::key_bits(), Fp49Field::exact_bits(), Fp49Field::kMaxRows, Fp49Field::kSmallBits, Fp49Field::kMaxLogBase);
-    case launch::kFieldGoldilocks:
-      return prime("goldilocks", GlField::key_bits(), GlField::exact_bits(), GlField::kMaxRows, GlField::kSmallBits, GlField::kMaxLogBase);
-    case launch::kFieldGoldilocksSplit:
-      return prime("goldilocks-split", GlSplitField::key_bits(), GlSplitField::exact_bits(), GlSplitField::kMaxRows,
-                   GlSplitField::kSmallBits, GlSplitField::kMaxLogBase);
-    default: {
-      char buf[256];
-      if (lb > FftField::kMaxLogBase || lb > FftField::kSmallBits) {
-        std::snprintf(buf, sizeof buf, "fp64-fft: KS log_base %d exceeds FftField::kMaxLogBase = %d", lb, FftField::kMaxLogBase);
-        return std::string(buf);
-      }
-      if (rows > FftField::kMaxRows) {
-        std::snprintf(buf, sizeof buf, "fp64-fft: (k+1) l_ks = %d rows per slice exceed FftField::kMaxRows = %d", rows, FftField::kMaxRows);
-        return std::string(buf);
-      }
-      const double err = FftField::error_bound((int)p.glwe_poly_degree, rows, lb);
-      if (!(err < FftField::kMaxError)) {
-        std::snprintf(buf, sizeof buf, "fp64-fft: rounding bound %.4g of a slice of %d rows in base 2^%d is not below %.4g", err,
-                      rows, lb, FftField::kMaxError);
-        return std::string(buf);
-      }
-      return std::string();
-    }
-  }
+  return exactness_refusal(ctx, (int)((ctx->params.glwe_dimension + 1) * ctx->ks.levels), (int)ctx->ks.log_base,
+                           {"KS log_base", "(k+1) l_ks", "slice"});
 }
 
 // d_raw: [from_dimension * l_ks][k+1][N] on the device

@@ -72,6 +72,11 @@ struct tfhe_context {
   u32* d_dense_ws = nullptr;
   size_t dense_rows = 0;
   unsigned dense_parts = 0;   // shares of the inputs (tfhe_context_set_dense_split); 0: automatic
+  // Encrypted convolution (tfhe_context_reserve_glwe_conv): the prepared spectra of a call's ciphertext polynomials,
+  // conv_ws_polys = max_queries * max_channels * (k+1) of them, parts * N 8-byte words each
+  void* d_conv_ws = nullptr;
+  size_t conv_ws_polys = 0;
+  unsigned conv_rows = 0;     // channels per pass (tfhe_context_set_glwe_conv_rows); 0: automatic
   // tree LUT (tfhe_context_reserve_tree_lut): per-rotation inputs, segment state, the levels' results and packed GLWEs
   u32* d_tree_ws = nullptr;
   size_t tree_ws_words = 0;
@@ -126,6 +131,18 @@ struct tfhe_context {
   bool ev_valid_br = false, ev_valid_ks = false;
 
   std::string last_error;
+};
+
+// A prepared set of clear weight polynomials (tfhe_prepare_poly_weights): the transformed polynomials on the device of
+// the context that prepared them, for that context's backend and ring.
+struct tfhe_poly_weights {
+  int device = 0;
+  int field = 0;
+  u32 log_n = 0;
+  void* d_spec = nullptr;      // [outputs][channels] spectra, N 8-byte words each (glwe_conv.h::conv_weights_wave)
+  size_t outputs = 0, channels = 0;
+  unsigned weight_bits = 0;    // the smallest b with every |w| <= 2^b
+  unsigned rows_per_pass = 0;  // channels the backend's exactness rule admits in one pass at that magnitude
 };
 
 namespace tfhe {

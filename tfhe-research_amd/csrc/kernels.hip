@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "glwe_conv.h"
 #include "launch.h"
 #include "lwe_dense.h"
 
@@ -1098,6 +1099,76 @@ __global__ void __launch_bounds__(256) dense_tile_rows_kernel(const u32* __restr
   }
 }
 
+// ------------------------------------------------------------------------------ encrypted convolution
+// glwe_conv.h states the operation and its exactness bound.  Two kernels:
+//
+// conv_weights_kernel: once per weight set, the forward transforms of the O * C weight polynomials into the form the
+// multiply-accumulate consumes; one polynomial per group of G waves, as in bsk_prepare_kernel.
+//
+// glwe_conv_kernel: one team per (query, output), output fastest, so that the teams in flight at one time read the
+// prepared ciphertexts of a few queries and all weight sets while those are hot in the L2s.  The ciphertext spectra of
+// the call come from bsk_prepare_kernel, in the layout of the context's k.
+template <class F, int LOGN>
+__global__ void __launch_bounds__(256) conv_weights_kernel(const typename F::elem* __restrict__ tw, const i32* __restrict__ polys,
+                                                          size_t poly_count, typename F::elem* __restrict__ spectra) {
+  typedef typename F::elem elem;
+  constexpr int N = 1 << LOGN;
+  constexpr int G = GroupOf<F, LOGN>::value;
+  elem* twl = reinterpret_cast<elem*>(g_smem);
+  ntt_stage_twiddles<LOGN - F::kLogShrink, G>(twl, tw, (int)threadIdx.x, (int)blockDim.x);
+  __syncthreads();
+  const int group = (int)(threadIdx.x / (64u * G));
+  const int groups = (int)(blockDim.x / (64u * G));
+  // (G > 1: the transform holds workgroup barriers, so a group past the end redoes the last polynomial)
+  size_t poly = (size_t)blockIdx.x * groups + group;
+  if (poly >= poly_count) {
+    if (G == 1) return;
+    poly = poly_count - 1;
+  }
+  DeviceWave<elem, G> w;
+  w.group_ = 0;
+  w.group_stride_ = 0;
+  w.buffer_bytes_ = 0;
+  w.acc_words_ = 0;
+  w.team_base_ = nullptr;
+  w.tw_ = twl;
+  w.twg_ = tw;
+  w.scratch_ = reinterpret_cast<elem*>(g_smem + twiddle_bytes<F, LOGN>() + (size_t)group * N * 8);
+  w.acc_ = nullptr;
+  conv_weights_wave<F, LOGN, G>(w, polys + poly * N, spectra + poly * (N >> F::kLogShrink));
+}
+
+template <class F, int LOGN, int K>
+__global__ void __launch_bounds__((TeamCfg<F, LOGN, K, 1>::kThreads), (TeamCfg<F, LOGN, K, 1>::kMinWaves))
+glwe_conv_kernel(const typename F::elem* __restrict__ tw, GlweConvArgs a) {
+  using C = TeamCfg<F, LOGN, K, 1>;
+  auto w = make_wave<F, LOGN, K, 1>(g_smem, tw);
+  glwe_conv_team<F, LOGN, K, C::G>(w, a, (size_t)(blockIdx.x / a.outputs), blockIdx.x % a.outputs);
+}
+
+// lwe_out [batch][count][k N + 1]: sample_extract_kernel's words at indices[0 .. count) of every GLWE
+__global__ void sample_extract_indices_kernel(u32 log_n, u32 k, const u32* __restrict__ glwe, size_t batch,
+                                              const u32* __restrict__ indices, size_t count, u32* __restrict__ lwe_out) {
+  const u32 N = 1u << log_n;
+  const size_t width = (size_t)k * N + 1;
+  const size_t total = batch * count * width;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t row = i / width;
+    const size_t x = i % width;
+    const u32 sample_index = indices[row % count] & (N - 1u);  // (the host has refused indices >= N: never out of the GLWE)
+    const u32* ct = glwe + (row / count) * (size_t)(k + 1) * N;
+    u32 v;
+    if (x == (size_t)k * N) {
+      v = ct[(size_t)k * N + sample_index];
+    } else {
+      const u32 p = (u32)(x >> log_n);
+      const u32 pos = (u32)(x & (N - 1));
+      v = (pos <= sample_index) ? ct[(size_t)p * N + (sample_index - pos)] : (0u - ct[(size_t)p * N + (N + sample_index - pos)]);
+    }
+    lwe_out[i] = v;
+  }
+}
+
 // ------------------------------------------------------------------------------ encryption side
 // dst[row][j] = body_in[row][j] +/- sum_i masks[row][i] (*) sk[i]: one GLWE row [k+1][N] per group
 // of G waves, 4/G rows per workgroup.  Encrypt (glwe.rs:190-209): body_in holds the caller's error
@@ -1882,6 +1953,43 @@ hipError_t launch_bsk_prepare(hipStream_t s, const void* tw_v, const u32* polys,
 }
 
 template <class F, int LOGN>
+hipError_t launch_conv_weights(hipStream_t s, const void* tw_v, const i32* polys, size_t poly_count, void* spectra_v) {
+  if constexpr (!field_shape_ok<F, LOGN>()) {
+    return hipErrorInvalidValue;
+  } else {
+    constexpr int N = 1 << LOGN;
+    constexpr int G = GroupOf<F, LOGN>::value;
+    constexpr int groups = 4 / G;  // polynomials per 256-thread workgroup
+    const size_t lds = twiddle_bytes<F, LOGN>() + (size_t)N * 8 * groups;
+    auto kern = conv_weights_kernel<F, LOGN>;
+    static std::atomic<unsigned long long> lds_done{0};
+    hipError_t e = allow_lds(kern, lds, lds_done);
+    if (e != hipSuccess) return e;
+    const unsigned grid = (unsigned)((poly_count + groups - 1) / groups);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, static_cast<const typename F::elem*>(tw_v), polys, poly_count,
+                       static_cast<typename F::elem*>(spectra_v));
+    return hipGetLastError();
+  }
+}
+
+template <class F, int LOGN, int K>
+hipError_t launch_glwe_conv(hipStream_t s, const void* tw_v, const GlweConvArgs& args, size_t queries) {
+  if constexpr (!field_shape_ok<F, LOGN>()) {
+    return hipErrorInvalidValue;
+  } else {
+    using C = TeamCfg<F, LOGN, K, 1>;
+    auto kern = glwe_conv_kernel<F, LOGN, K>;
+    static std::atomic<unsigned long long> lds_done{0};
+    hipError_t e = allow_lds(kern, C::kLds, lds_done);
+    if (e != hipSuccess) return e;
+    const size_t teams = queries * args.outputs;
+    if (teams == 0 || teams > kMaxGrid || args.rows_per_pass == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kern, dim3((unsigned)teams), dim3(C::kThreads), C::kLds, s, static_cast<const typename F::elem*>(tw_v), args);
+    return hipGetLastError();
+  }
+}
+
+template <class F, int LOGN>
 hipError_t launch_glwe_body(hipStream_t s, const void* tw_v, u32 k, const u32* rows, size_t row_count,
                             const u32* sk, u32* dst, size_t dst_stride, u32 negate) {
   if constexpr (!field_shape_ok<F, LOGN>()) {
@@ -2318,6 +2426,35 @@ hipError_t lwe_dense(hipStream_t s, const u32* x, size_t queries, u32 inputs, co
 hipError_t dense_tile_rows(hipStream_t s, const u32* in, size_t period, size_t count, u32 words, u32* out) {
   const unsigned grid = (unsigned)(count < ((size_t)1 << 20) ? count : (size_t)1 << 20);
   hipLaunchKernelGGL(dense_tile_rows_kernel, dim3(grid), dim3(256), 0, s, in, period, count, words, out);
+  return hipGetLastError();
+}
+
+// How a convolution goes out: one team per (query, output); the channels in passes of rows_per_pass, the admitted
+// maximum (or the forced count) held to the channels there are.  The words do not depend on it.
+bool glwe_conv_plan(size_t queries, u32 channels, u32 outputs, u32 admitted_rows, u32 forced_rows, GlweConvPlanInfo* info) {
+  if (queries == 0 || channels == 0 || outputs == 0 || admitted_rows == 0 || forced_rows > admitted_rows) return false;
+  if ((double)queries * (double)outputs > (double)kMaxGrid) return false;
+  u32 rows = forced_rows ? forced_rows : admitted_rows;
+  if (rows > channels) rows = channels;
+  info->rows_per_pass = rows;
+  info->passes = (channels + rows - 1) / rows;
+  info->teams = queries * outputs;
+  return true;
+}
+
+hipError_t conv_weights(hipStream_t s, int field, u32 log_n, const void* tw, const i32* polys, size_t poly_count, void* spectra) {
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN(log_n, (launch_conv_weights<FF, LL>(s, tw, polys, poly_count, spectra))));
+}
+
+hipError_t glwe_conv(hipStream_t s, int field, u32 log_n, u32 k, const void* tw, const GlweConvArgs& args, size_t queries) {
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(log_n, k, (launch_glwe_conv<FF, LL, KK>(s, tw, args, queries))));
+}
+
+hipError_t sample_extract_indices(hipStream_t s, u32 log_n, u32 k, const u32* glwe, size_t batch, const u32* indices,
+                                  size_t count, u32* lwe_out) {
+  const size_t total = batch * count * ((size_t)k * ((size_t)1 << log_n) + 1);
+  hipLaunchKernelGGL(sample_extract_indices_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, log_n, k, glwe, batch, indices,
+                     count, lwe_out);
   return hipGetLastError();
 }
 

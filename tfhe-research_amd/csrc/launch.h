@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "glwe_conv.h"
 #include "ks_matrix.h"
 #include "pbs_wave.h"
 
@@ -177,6 +178,23 @@ hipError_t lwe_dense(hipStream_t s, const u32* x, size_t queries, u32 inputs, co
                      u32 words, u32 forced_splits, u32* out);
 // out [count][words], out[r] = in[r % period]: the per-neuron test vectors of a fused layer, one per bootstrap
 hipError_t dense_tile_rows(hipStream_t s, const u32* in, size_t period, size_t count, u32 words, u32* out);
+
+// ---- encrypted convolution (glwe_conv.h::glwe_conv_team; the plan: kernels.hip::glwe_conv_plan)
+struct GlweConvPlanInfo {
+  u32 rows_per_pass;  // channels summed in the transform domain before a lift
+  u32 passes;         // ceil(channels / rows_per_pass)
+  size_t teams;       // queries * outputs workgroups
+};
+// admitted_rows: what the backend's exactness rule admits at the weights' magnitude (capi.cpp::conv_rows_admitted);
+// forced_rows 0: automatic.  false: a size is 0, forced_rows exceeds admitted_rows, or queries * outputs >= 2^31
+bool glwe_conv_plan(size_t queries, u32 channels, u32 outputs, u32 admitted_rows, u32 forced_rows, GlweConvPlanInfo* info);
+// spectra [poly_count][N >> kLogShrink] field elements (8 N bytes each at most) = the transformed weight polynomials [poly_count][N]
+hipError_t conv_weights(hipStream_t s, int field, u32 log_n, const void* tw, const i32* polys, size_t poly_count, void* spectra);
+// args.x_spec: the call's ciphertext polynomials prepared by bsk_prepare(.., k, ..); one launch of queries * outputs teams
+hipError_t glwe_conv(hipStream_t s, int field, u32 log_n, u32 k, const void* tw, const GlweConvArgs& args, size_t queries);
+// lwe_out [batch][count][k N + 1] = sample_extract(glwe[b], indices[i]); indices [count] on the device, each below N
+hipError_t sample_extract_indices(hipStream_t s, u32 log_n, u32 k, const u32* glwe, size_t batch, const u32* indices,
+                                  size_t count, u32* lwe_out);
 
 // elementwise helpers.  first_shift = bit of the lowest kept limb (PbsParams::first_shift)
 hipError_t decompose_words(hipStream_t s, u32 log_base, u32 levels, u32 first_shift, const u32* values,

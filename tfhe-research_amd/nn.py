@@ -77,6 +77,194 @@ class Dense:
         return (self.weights.astype(np.float64) ** 2).sum(axis=1)
 
 
+class Conv2d:
+    """A convolution layer over PACKED images (include/tfhe_hip.h, "encrypted convolutions"): channel c of a query is ONE
+    GLWE whose coefficient y W + x carries pixel (y, x) of an H x W image, H W <= N.  The layer is the "valid"
+    cross-correlation  pre[o][y][x] = sum_{c,dy,dx} kernels[o][c][dy][dx] image[c][y+dy][x+dx] + bias[o]  followed by the
+    table: no stride, no padding, no pooling.
+
+    Tap (dy, dx) sits at coefficient (kh-1-dy) W + (kw-1-dx) of the weight polynomial, so the product carries output
+    (y, x) at coefficient (y+kh-1) W + (x+kw-1): the negacyclic wrap and the bleed from one image row into the next land
+    only in rows < kh-1 and columns < kw-1, which are never read.  run() extracts the read coefficients and bootstraps
+    each one, and returns LWE ciphertexts in (o, y, x) order: the inputs of a Network."""
+
+    def __init__(self, kernels, bias=None, lut=None, image=None):
+        w = np.asarray(kernels)
+        if w.ndim != 4 or w.size == 0 or not np.issubdtype(w.dtype, np.integer):
+            raise ValueError("kernels: a non-empty integer array [outputs][channels][kh][kw] expected")
+        if int(w.max()) >= 1 << 31 or int(w.min()) < -(1 << 31):
+            raise ValueError("kernels must fit int32")
+        if image is None or len(image) != 2 or int(image[0]) < w.shape[2] or int(image[1]) < w.shape[3]:
+            raise ValueError("image: (H, W), at least as large as the kernel, is required")
+        self.kernels = np.ascontiguousarray(w, dtype=np.int32)
+        self.image = (int(image[0]), int(image[1]))
+        b = np.zeros(w.shape[0], dtype=np.int64) if bias is None else np.asarray(bias, dtype=np.int64).reshape(-1)
+        if b.shape != (w.shape[0],):
+            raise ValueError(f"bias: {w.shape[0]} integers expected")
+        self.bias = b
+        if lut is None:
+            raise ValueError("lut: the activation's table (2^log_p entries, or one such row per output) is required")
+        t = np.asarray(lut, dtype=np.int64)
+        if t.ndim not in (1, 2) or (t.ndim == 2 and t.shape[0] != w.shape[0]) or t.shape[-1] < 2 or t.shape[-1] & (t.shape[-1] - 1):
+            raise ValueError("lut: 2^log_p entries, or [outputs][2^log_p]")
+        if int(t.min()) < 0 or int(t.max()) >= t.shape[-1]:
+            raise ValueError("lut entries must be messages: in [0, 2^log_p)")
+        self.lut = t
+
+    @property
+    def outputs(self) -> int:
+        return int(self.kernels.shape[0])
+
+    @property
+    def channels(self) -> int:
+        return int(self.kernels.shape[1])
+
+    @property
+    def log_p(self) -> int:
+        return int(self.lut.shape[-1]).bit_length() - 1
+
+    @property
+    def out_image(self):
+        """(outH, outW) of the valid correlation"""
+        return self.image[0] - self.kernels.shape[2] + 1, self.image[1] - self.kernels.shape[3] + 1
+
+    def luts(self) -> np.ndarray:
+        """[outputs][2^log_p]: the shared table repeated, or the per-output tables"""
+        return self.lut if self.lut.ndim == 2 else np.broadcast_to(self.lut, (self.outputs, self.lut.size))
+
+    def weight_polys(self, N: int) -> np.ndarray:
+        """[outputs][channels][N] int32: tap (dy, dx) at coefficient (kh-1-dy) W + (kw-1-dx)"""
+        (h, wd), (kh, kw) = self.image, self.kernels.shape[2:]
+        if h * wd > N:
+            raise ValueError(f"an image of {h} x {wd} pixels does not fit {N} coefficients")
+        polys = np.zeros(self.kernels.shape[:2] + (N,), dtype=np.int32)
+        for dy in range(kh):
+            for dx in range(kw):
+                polys[:, :, (kh - 1 - dy) * wd + (kw - 1 - dx)] = self.kernels[:, :, dy, dx]
+        return polys
+
+    def output_indices(self) -> np.ndarray:
+        """[outH * outW] in (y, x) order: output (y, x) sits at coefficient (y+kh-1) W + (x+kw-1)"""
+        wd, (kh, kw), (oh, ow) = self.image[1], self.kernels.shape[2:], self.out_image
+        y, x = np.meshgrid(np.arange(oh), np.arange(ow), indexing="ij")
+        return ((y + kh - 1) * wd + (x + kw - 1)).reshape(-1).astype(np.uint32)
+
+    def pack(self, images, N: int) -> np.ndarray:
+        """images [..][H][W] -> message polynomials [..][N], pixel (y, x) at coefficient y W + x, zero above H W"""
+        img = np.asarray(images)
+        if tuple(img.shape[-2:]) != self.image:
+            raise ValueError(f"images [..][{self.image[0]}][{self.image[1]}] expected")
+        out = np.zeros(img.shape[:-2] + (N,), dtype=img.dtype)
+        out[..., :self.image[0] * self.image[1]] = img.reshape(img.shape[:-2] + (-1,))
+        return out
+
+    def pre_activations(self, images) -> np.ndarray:
+        """images [..][channels][H][W] integers -> the valid correlation + bias [..][outputs][outH][outW], unbounded integers"""
+        img = np.asarray(images, dtype=np.int64)
+        if tuple(img.shape[-3:]) != (self.channels,) + self.image:
+            raise ValueError(f"images [..][{self.channels}][{self.image[0]}][{self.image[1]}] expected")
+        (kh, kw), (oh, ow) = self.kernels.shape[2:], self.out_image
+        k = self.kernels.astype(np.int64)
+        out = np.zeros(img.shape[:-3] + (self.outputs, oh, ow), dtype=np.int64)
+        for dy in range(kh):
+            for dx in range(kw):
+                # [.., 1, C, oh, ow] * [O, C, 1, 1] summed over C
+                out += (img[..., None, :, dy:dy + oh, dx:dx + ow] * k[:, :, dy, dx][:, :, None, None]).sum(axis=-3)
+        return out + self.bias[:, None, None]
+
+    def pre_activation_range(self, lo, hi):
+        """interval arithmetic: every pixel in [lo, hi] (scalars) -> (min, max) [outputs] of the pre-activations"""
+        w = self.kernels.astype(np.int64).reshape(self.outputs, -1)
+        pos, neg = np.maximum(w, 0).sum(axis=1), np.minimum(w, 0).sum(axis=1)
+        lo, hi = int(lo), int(hi)
+        return pos * lo + neg * hi + self.bias, pos * hi + neg * lo + self.bias
+
+    def squared_norms(self) -> np.ndarray:
+        """[outputs]: sum_c ||W[o][c]||_2^2, what an output multiplies the input noise's variance by"""
+        return (self.kernels.astype(np.float64) ** 2).reshape(self.outputs, -1).sum(axis=1)
+
+    def evaluate_clear(self, images) -> np.ndarray:
+        """images [..][channels][H][W] integer messages -> the layer's messages [..][outputs][outH][outW] (run() returns
+        them flattened in (o, y, x) order).  A pre-activation outside [0, 2^log_p) raises: check() tells beforehand."""
+        pre = self.pre_activations(images)
+        if int(pre.min()) < 0 or int(pre.max()) >= 1 << self.log_p:
+            raise ValueError(f"pre-activation {int(pre.min() if pre.min() < 0 else pre.max())} outside [0, 2^{self.log_p})")
+        return self.luts()[np.arange(self.outputs)[:, None, None], pre]
+
+    def check(self, params, input_range=(0, 1)):
+        """Raises ValueError unless the image fits the ring, the table matches params.log_p and, for pixels in
+        input_range = (lo, hi), every pre-activation PROVABLY stays in [0, 2^log_p)"""
+        if self.image[0] * self.image[1] > 1 << params.glwe_poly_degree:
+            raise ValueError(f"an image of {self.image[0]} x {self.image[1]} pixels does not fit N = {1 << params.glwe_poly_degree}")
+        if self.log_p != params.log_p:
+            raise ValueError(f"the tables have 2^{self.log_p} entries, the parameter set has log_p = {params.log_p}")
+        lo, hi = input_range
+        if lo < 0 or hi >= 1 << params.log_p or lo > hi:
+            raise ValueError(f"input_range must lie in [0, 2^{params.log_p})")
+        pmin, pmax = self.pre_activation_range(lo, hi)
+        bad = np.nonzero((pmin < 0) | (pmax >= 1 << params.log_p))[0]
+        if bad.size:
+            o = int(bad[0])
+            raise ValueError(f"output {o}: pre-activations range over [{int(pmin[o])}, {int(pmax[o])}], outside [0, 2^{params.log_p})")
+
+    def device_arrays(self, params):
+        """(weight polynomials [O][C][N] int32, bias [O][N] uint32 ENCODED on the read coefficients, test vectors [O][N]
+        or [N] un-encoded, output indices [outH outW])"""
+        from . import construct_test_from_lut
+        N = 1 << params.glwe_poly_degree
+        idx = self.output_indices()
+        bias = np.zeros((self.outputs, N), dtype=np.uint32)
+        bias[:, idx] = ((self.bias << (32 - params.log_p - params.padding_bits)) & 0xFFFFFFFF).astype(np.uint32)[:, None]
+        if self.lut.ndim == 1:
+            tv = construct_test_from_lut(params, self.lut.astype(np.uint32))
+        else:
+            tv = np.stack([construct_test_from_lut(params, row.astype(np.uint32)) for row in self.lut])
+        return self.weight_polys(N), bias, tv, idx
+
+    def pre_activation_ciphertexts(self, ctx, glwe, weights=None):
+        """glwe [queries][channels][k+1][N] -> the pre-activations as LWE ciphertexts [queries][O outH outW][k N + 1]
+        before any key switch or bootstrap: glwe_conv, then sample_extract_indices.  `weights`: the PolyWeights of
+        device_arrays()[0], prepared once by the caller; else they are prepared (and released) here."""
+        polys, bias, _, idx = self.device_arrays(ctx.params)
+        own = weights is None
+        if own:
+            weights = ctx.prepare_poly_weights(polys)
+        try:
+            is_torch = type(glwe).__module__.startswith("torch")
+            if is_torch:
+                import torch
+                bias = torch.from_numpy(bias.view(np.int32)).to(glwe.device)
+                idx = torch.from_numpy(idx.view(np.int32)).to(glwe.device)
+            conv = ctx.glwe_conv(glwe, weights, bias)
+            q = int(conv.shape[0])
+            lwe = ctx.sample_extract_indices(conv.reshape((q * self.outputs,) + tuple(conv.shape[2:])), idx)
+            if is_torch and own:
+                torch.cuda.current_stream().synchronize()  # the weights go away with this call
+            return lwe.reshape(q, self.outputs * int(idx.shape[0]), -1)
+        finally:
+            if own:
+                weights.close()
+
+    def run(self, ctx, glwe, weights=None):
+        """glwe [queries][channels][k+1][N] (numpy: host forms; torch: device forms in the workspaces of
+        ctx.reserve_glwe_conv and ctx.reserve) -> LWE ciphertexts [queries][O outH outW][io_dim + 1] in (o, y, x) order:
+        glwe_conv, sample_extract_indices, a key switch in the reference's bootstrap order (which takes n + 1 words; the
+        KS-first order takes the extracted k N + 1 words as they are), then one bootstrap per output pixel"""
+        lwe = self.pre_activation_ciphertexts(ctx, glwe, weights)
+        q, per_query = int(lwe.shape[0]), int(lwe.shape[1])
+        flat = lwe.reshape(q * per_query, -1)
+        if ctx.io_dim != ctx.params.big_n:
+            flat = ctx.key_switch(flat)
+        tv = self.device_arrays(ctx.params)[2]
+        if tv.ndim == 2:  # bootstrap r = (query, output, pixel) takes output (r / pixels) % O's test vector
+            tv = np.ascontiguousarray(np.broadcast_to(tv[None, :, None, :], (q, self.outputs, per_query // self.outputs, tv.shape[1]))
+                                      ).reshape(q * per_query, -1)
+        if type(flat).__module__.startswith("torch"):
+            import torch
+            tv = torch.from_numpy(tv.view(np.int32)).to(flat.device)
+        return ctx.bootstrap(flat, tv).reshape(q, per_query, -1)
+
+
 class Network:
     def __init__(self, layers):
         self.layers = list(layers)
