@@ -5,6 +5,8 @@
 // `pytest -m "not gpu"` check the exact device code (layouts, twiddles, swizzles, decomposer,
 // rotation signs) bit-for-bit against the oracle without a GPU.  It is a test of the product's
 // source, not a fallback: nothing in the shipped library can reach it.
+#ifndef TFHE_EMU_CPP  // the feature emulators (emu_lookup.cpp, ..) include this file; a sanitizer driver includes several of them
+#define TFHE_EMU_CPP
 #define TFHE_FFT_TRACK_ERROR 1  // record how far the complex transform's lifted values are from integers
 #include <pthread.h>
 
@@ -609,3 +611,4 @@ int emu_glwe_body(int field, int logn, int g, u32 k, size_t rows, const u32* glw
 }
 
 }  // extern "C"
+#endif  // TFHE_EMU_CPP

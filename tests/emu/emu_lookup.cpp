@@ -1,66 +1,36 @@
 // emu_lookup.cpp -- the CMUX tree / table lookup team (pbs_wave.h::cmux_tree_team) in the host SIMT emulator.
 //
 // Built into its own shared object by tests/test_emu_lookup.py; emu.cpp is included for HostWave / run_team and the key
-// preparation.  The passes are sequenced the way capi.cpp::run_lookup sequences the launches: every pass but the last
-// reduces `height` levels and leaves its results in one of two buffers, the last one takes the rest, the rotation
-// chain and the sample extraction.  Teams of a pass run one after the other on one emulated workgroup.
+// preparation.  The plan and the passes are the library's (csrc/passes.h: lookup_plan_for, lookup_passes) over ONE
+// exactly sized, poisoned workspace; here a pass is run where capi.cpp launches it.  Teams of a pass run one after the
+// other on one emulated workgroup.
 #include "emu.cpp"
+#include "passes.h"
 
 namespace {
 
 template <class F, int LOGN, int K, int G>
-void lookup(const PbsParams& P, const typename F::elem* selectors, size_t queries, u32 address_bits, u32 first, u32 tree_depth,
-            u32 height, const u32* leaves, const u32* table, int shared, u32 tables, u32* glwe_out, u32* lwe_out) {
+int lookup(const PbsParams& P, passes::LookupCall call, u32 height, size_t resident) {
   typedef typename F::elem elem;
   constexpr int N = 1 << LOGN;
-  constexpr size_t GLWE = (size_t)(K + 1) * N;
   if constexpr (!shape_ok<F, LOGN, G>()) std::abort();
   else {
-    const size_t ggsw_elems = (size_t)(K + 1) * P.levels * (K + 1) * F::kParts * (N >> F::kLogShrink);
-    const size_t trees = queries * tables;
-    const u32 h = tree_depth == 0 ? 0 : (height == 0 || height > tree_depth ? tree_depth : height);
-    const u32 launches = tree_depth == 0 ? 1 : (tree_depth + h - 1) / h;
-    std::vector<u32> results[2];
-    std::vector<u32> pending;
-    u32 done = 0;
-    for (u32 i = 0; i < launches; ++i) {
-      const u32 here = tree_depth - done < h ? tree_depth - done : h;
-      const bool last = i + 1 == launches;
-      CmuxTreePass pass{};
-      pass.selectors = selectors + (size_t)(first + done) * ggsw_elems;
-      pass.rot_selectors = selectors;
-      pass.query_stride = (size_t)address_bits * ggsw_elems;
-      pass.tables = tables;
-      pass.height = here;
-      pass.log_subtrees = tree_depth - done - here;
-      const size_t teams = trees << pass.log_subtrees;
-      if (i == 0 && table) {
-        pass.shared_sets = shared;
-        pass.table = table;
-        pass.table_stride = (size_t)1 << address_bits;
-        pass.log_entries = first;
-      } else {
-        const u32* base = i == 0 ? leaves : results[(i - 1) & 1].data();
-        pass.shared_sets = i == 0 && shared;
-        pass.even = base;
-        pass.odd = base + GLWE;
-        pass.pair_stride = 2 * GLWE;
-        pass.set_stride = ((size_t)1 << (tree_depth - done)) * GLWE;
-      }
-      pending.assign(teams * (here > 1 ? here - 1 : 0) * GLWE + 1, 0xDEADBEEFu);
-      pass.pending = pending.data();
-      if (!last) results[i & 1].assign(teams * GLWE, 0xDEADBEEFu);
-      pass.rot_steps = last && lwe_out ? first : 0u;
-      pass.glwe_out = last ? glwe_out : results[i & 1].data();
-      pass.lwe_out = last ? lwe_out : nullptr;
+    call.ggsw_words = (size_t)(K + 1) * P.levels * (K + 1) * F::kParts * (N >> F::kLogShrink) * (sizeof(elem) / 8);
+    call.glwe_words = (size_t)(K + 1) * N;
+    passes::TreePlan plan{};
+    if (!passes::lookup_plan_for(call.queries * call.tables, (u32)call.tree_depth, height, resident, call.glwe_words, &plan)) return 3;
+    std::vector<u32> ws(plan.workspace_words, 0xDEADBEEFu);
+    size_t ws_words = 0;
+    return passes::lookup_passes(plan, call, ws.data(), &ws_words, [&](CmuxTreePass pass, size_t teams) {
+      pass.query_stride /= sizeof(elem) / 8;  // as the launcher does: 8-byte words -> elements
       run_team<F>(LOGN, K + 1, G, [&](const HostWave<elem>& w) {
         for (size_t team = 0; team < teams; ++team) {
           cmux_tree_team<F, LOGN, K, G>(w, P, pass, team >> pass.log_subtrees, (u32)(team & (((size_t)1 << pass.log_subtrees) - 1)));
           w.team_sync();
         }
       });
-      done += here;
-    }
+      return 0;
+    });
   }
 }
 
@@ -70,16 +40,16 @@ extern "C" {
 
 // selectors: prepared (emu_bsk_prepare over [queries][address_bits][R][k+1][N]).  Tree: leaves != null, first = 0,
 // tree_depth = address_bits, glwe_out.  Lookup: table != null, first = min(address_bits, logn), tree_depth = the rest,
-// lwe_out.  height 0: one pass.  shared: one leaf / table set for all queries.
+// lwe_out.  height: tfhe_context_set_lookup_subtree_height's (0: automatic, for `resident` teams at once).  shared: one
+// leaf / table set for all queries.
 int emu_lookup(int field, int g, u32 k, u32 logn, u32 log_p, u32 padding, u32 log_base, u32 levels, const void* selectors,
-               size_t queries, u32 address_bits, u32 first, u32 tree_depth, u32 height, const u32* leaves, const u32* table,
-               int shared, u32 tables, u32* glwe_out, u32* lwe_out) {
+               size_t queries, u32 address_bits, u32 first, u32 tree_depth, u32 height, size_t resident, const u32* leaves,
+               const u32* table, int shared, u32 tables, u32* glwe_out, u32* lwe_out) {
   PbsParams P = make_params(0, k, logn, log_p, padding, log_base, levels);
+  const passes::LookupCall call{selectors, 0, 0, queries, address_bits, first, tree_depth, leaves, table, shared != 0, tables, glwe_out, lwe_out};
   // few shapes: the complex transform and Goldilocks at N = 512, the complex transform at N = 1024 (k = 1, one wave per
   // polynomial); the complex transform at k = 2: N = 512, and N = 2048 over four waves per polynomial
-#define LOOKUP(FF, L, KK, GG)                                                                                                \
-  lookup<FF, L, KK, GG>(P, (const FF::elem*)selectors, queries, address_bits, first, tree_depth, height, leaves, table, shared, \
-                        tables, glwe_out, lwe_out)
+#define LOOKUP(FF, L, KK, GG) return lookup<FF, L, KK, GG>(P, call, height, resident)
   if (k == 1 && g == 1) {
     if (field == 5 && logn == 9) LOOKUP(FftField, 9, 1, 1);
     else if (field == 5 && logn == 10) LOOKUP(FftField, 10, 1, 1);
@@ -93,7 +63,29 @@ int emu_lookup(int field, int g, u32 k, u32 logn, u32 log_p, u32 padding, u32 lo
     return 2;
   }
 #undef LOOKUP
-  return 0;
 }
+
+// The library's plan of a tree and (rows != null) where every pass's buffers lie: rows [launches][5] = teams, height,
+// then the word offsets from the workspace's first word of the pending slots (-1: the pass has none), of the input and
+// of the output (-1: not in the workspace -- the call's own leaves / result).  Pointer arithmetic on a workspace of
+// glwe_words-word GLWEs that is never read or written.  1: refused (the grid limit)
+int emu_tree_plan(size_t queries, size_t tables, u32 depth, u32 height, size_t resident, size_t glwe_words, u32* plan_height,
+                  u32* launches, size_t* workspace_words, size_t* ws_end, long long* rows) {
+  passes::TreePlan plan{};
+  if (!passes::lookup_plan_for(queries * tables, depth, height, resident, glwe_words, &plan)) return 1;
+  *plan_height = plan.height, *launches = plan.launches, *workspace_words = plan.workspace_words;
+  if (!rows) return 0;
+  std::vector<u32> ws(plan.workspace_words), outside(2 * glwe_words);
+  auto offset = [&](const u32* p) { return p >= ws.data() && p < ws.data() + ws.size() ? (long long)(p - ws.data()) : -1ll; };
+  const passes::LookupCall call{nullptr, 0, glwe_words, queries, depth, 0, depth, outside.data(), nullptr, false, tables, outside.data(), nullptr};
+  return passes::lookup_passes(plan, call, ws.data(), ws_end, [&](const CmuxTreePass& pass, size_t teams) {
+    const long long row[5] = {(long long)teams, pass.height, pass.height > 1 ? offset(pass.pending) : -1, offset(pass.even), offset(pass.glwe_out)};
+    rows = std::copy(row, row + 5, rows);
+    return 0;
+  });
+}
+
+// the words a reservation for (trees, depth) holds: what tfhe_context_reserve_lookup / _demux ask for
+size_t emu_tree_need(size_t trees, size_t depth, size_t glwe_words) { return passes::lookup_workspace_need(trees, depth, glwe_words); }
 
 }  // extern "C"

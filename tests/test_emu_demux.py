@@ -25,6 +25,7 @@ GL, FFT = 1, 5
 SHAPES = [(FFT, 9), (GL, 9), (FFT, 10)]
 # log_base, levels, aligned
 DECOMPOSERS = [(7, 3, False), (7, 3, True), (4, 6, False)]
+RESIDENT = C.c_size_t(1024)  # teams at once for the automatic height: every call here forces its height
 
 
 def p32(a):
@@ -78,11 +79,12 @@ def operands(logn, levels, queries, depth, values, seed, k=1):
 
 
 def run(emu, field, g, k, logn, lb, levels, aligned, exb, spec, queries, D, rot, depth, height, x, values, out, shared, accumulate):
+    """height: the forced subtree height, tfhe_context_set_demux_subtree_height's (depth: one pass; 0 would be automatic)"""
     emu.emu_set_aligned(int(aligned))
     emu.emu_set_exchange_buffers(exb)
     try:
-        rc = emu.emu_demux(field, g, k, logn, lb, levels, p64(spec), C.c_size_t(queries), D, rot, depth, height, p32(x), values,
-                           p32(out), int(shared), int(accumulate))
+        rc = emu.emu_demux(field, g, k, logn, lb, levels, p64(spec), C.c_size_t(queries), D, rot, depth, height, RESIDENT, p32(x),
+                           values, p32(out), int(shared), int(accumulate))
     finally:
         emu.emu_set_aligned(0)
         emu.emu_set_exchange_buffers(1)
@@ -104,7 +106,7 @@ def check_tree(emu, field, g, k, logn, lb, levels, aligned, exb, depth, queries=
     sel, x, want, fill = tree_case(logn, lb, levels, aligned, depth, k, queries, values)
     spec = prepared(emu, field, k, logn, sel, g)
     out = np.full(want.shape, 0xDEADBEEF, dtype=np.uint32)
-    run(emu, field, g, k, logn, lb, levels, aligned, exb, spec, queries, depth, 0, depth, 0, x, values, out, False, False)
+    run(emu, field, g, k, logn, lb, levels, aligned, exb, spec, queries, depth, 0, depth, depth, x, values, out, False, False)
     assert np.array_equal(out, want)
     assert np.array_equal(cm._u32(cm._u64(out).sum(axis=2)), x)  # I13 on the device code's own output
     height = max(1, depth - 1)  # depth 3: passes of 1 + 2 levels; depth 2: 1 + 1; depth 1: one pass again
@@ -144,7 +146,7 @@ def test_write_matches_the_model(emu, field, logn, lb, levels, aligned, extra):
     for q in range(2):
         want = cd.write_model(sel[q], x[q], want, lb, levels, aligned)
     spec = prepared(emu, field, 1, logn, sel)
-    run(emu, field, 1, 1, logn, lb, levels, aligned, 1, spec, 2, D, d_lo, D - d_lo, 0, x, 1, table, True, True)
+    run(emu, field, 1, 1, logn, lb, levels, aligned, 1, spec, 2, D, d_lo, D - d_lo, D - d_lo, x, 1, table, True, True)
     assert np.array_equal(table[0], want)
 
 

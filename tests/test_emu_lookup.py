@@ -27,6 +27,9 @@ SHAPES = [(FFT, 9), (GL, 9), (FFT, 10)]
 K2_SHAPES = [(9, 1, 1), (11, 4, 2)]
 # log_base, levels, aligned
 DECOMPOSERS = [(7, 3, False), (7, 3, True), (4, 6, False)]
+# teams at once for the automatic height; every call here forces its height (the height is the context's knob: 0 would be
+# automatic), so the value does not matter
+RESIDENT = C.c_size_t(1024)
 
 
 def p32(a):
@@ -99,14 +102,15 @@ def lookup_case(logn, lb, levels, aligned, D):
 @pytest.mark.parametrize("field,logn", SHAPES)
 @pytest.mark.parametrize("height", [0, 2])
 def test_tree_matches_the_model(emu_lookup, field, logn, lb, levels, aligned, height):
-    """depth 3 in one subtree (height 0: the whole tree) and as two passes (heights 2 + 1 through the result buffers)"""
+    """depth 3 in one subtree (parameter 0: the whole tree, a forced height of 3) and as two passes (heights 2 + 1 through
+    the result buffers)"""
     sel, leaves, want = tree_case(logn, lb, levels, aligned)
     spec = prepared(emu_lookup, field, 1, logn, sel)
     out = np.zeros((2, 2, 2, 1 << logn), dtype=np.uint32)
     emu_lookup.emu_set_aligned(int(aligned))
     try:
-        rc = emu_lookup.emu_lookup(field, 1, 1, logn, 4, 1, lb, levels, p64(spec), C.c_size_t(2), 3, 0, 3, height, p32(leaves), None,
-                                   1, 2, p32(out), None)
+        rc = emu_lookup.emu_lookup(field, 1, 1, logn, 4, 1, lb, levels, p64(spec), C.c_size_t(2), 3, 0, 3, height or 3, RESIDENT,
+                                   p32(leaves), None, 1, 2, p32(out), None)
     finally:
         emu_lookup.emu_set_aligned(0)
     assert rc == 0
@@ -125,8 +129,8 @@ def test_lookup_matches_the_model(emu_lookup, field, logn, lb, levels, aligned, 
     out = np.zeros((2, 1, (1 << logn) + 1), dtype=np.uint32)
     emu_lookup.emu_set_aligned(int(aligned))
     try:
-        rc = emu_lookup.emu_lookup(field, 1, 1, logn, log_p, 1, lb, levels, p64(spec), C.c_size_t(2), D, d_lo, D - d_lo, 0, None,
-                                   p32(table), 0, 1, None, p32(out))
+        rc = emu_lookup.emu_lookup(field, 1, 1, logn, log_p, 1, lb, levels, p64(spec), C.c_size_t(2), D, d_lo, D - d_lo, D - d_lo, RESIDENT,
+                                   None, p32(table), 0, 1, None, p32(out))
     finally:
         emu_lookup.emu_set_aligned(0)
     assert rc == 0
@@ -160,10 +164,10 @@ def test_tree_matches_the_model_at_k2(emu_lookup, logn, g, exb, lb, levels, alig
     emu_lookup.emu_set_aligned(int(aligned))
     emu_lookup.emu_set_exchange_buffers(exb)
     try:
-        for height in (0, depth - 1):
+        for height in (depth, depth - 1):
             out = np.zeros((queries, tables, 3, 1 << logn), dtype=np.uint32)
             rc = emu_lookup.emu_lookup(FFT, g, 2, logn, 4, 1, lb, levels, p64(spec), C.c_size_t(queries), depth, 0, depth, height,
-                                       p32(leaves), None, 1, tables, p32(out), None)
+                                       RESIDENT, p32(leaves), None, 1, tables, p32(out), None)
             assert rc == 0
             assert np.array_equal(out, want), height
     finally:
@@ -187,8 +191,8 @@ def test_lookup_matches_the_model_at_k2(emu_lookup, logn, g, exb):
     emu_lookup.emu_set_aligned(int(aligned))
     emu_lookup.emu_set_exchange_buffers(exb)
     try:
-        rc = emu_lookup.emu_lookup(FFT, g, 2, logn, log_p, 1, lb, levels, p64(spec), C.c_size_t(queries), D, d_lo, D - d_lo, 0, None,
-                                   p32(table), 0, 1, None, p32(out))
+        rc = emu_lookup.emu_lookup(FFT, g, 2, logn, log_p, 1, lb, levels, p64(spec), C.c_size_t(queries), D, d_lo, D - d_lo, D - d_lo,
+                                   RESIDENT, None, p32(table), 0, 1, None, p32(out))
     finally:
         emu_lookup.emu_set_aligned(0)
         emu_lookup.emu_set_exchange_buffers(1)

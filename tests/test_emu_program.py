@@ -92,7 +92,7 @@ def run(emu, field, g, k, logn, lb, levels, aligned, exb, spec, queries, shared,
     try:
         rc = emu.emu_program(field, g, k, logn, LOG_P, 1, lb, levels, p64(spec), C.c_size_t(queries), n_inputs, int(shared),
                              p32(nodes), nodes.shape[0], p32(terminals), terminals.shape[0], p32(outputs), outputs.size, parts,
-                             p32(glwe), p32(lwe))
+                             C.c_size_t(1024), p32(glwe), p32(lwe))  # parts is forced (>= 1): the resident teams do not matter
     finally:
         emu.emu_set_aligned(0)
         emu.emu_set_exchange_buffers(1)

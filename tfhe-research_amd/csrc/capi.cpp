@@ -4,6 +4,7 @@
 // memory management, key preparation and kernel sequencing.  No CPU implementation of the hot
 // path lives here: without a GPU every compute entry point fails with TFHE_ERR_NO_DEVICE.
 #include "context.h"
+#include "passes.h"
 
 #include <cmath>
 #include <cstdint>
@@ -1168,33 +1169,23 @@ int tfhe_cmux_batch(tfhe_context* ctx, const uint32_t* ggsw, size_t ggsw_count, 
 }
 
 // ---------------------------------------------------------------------------------- CMUX tree / table lookup
-// include/tfhe_hip.h states the operations, pbs_wave.h::cmux_tree_team the walk, kernels.hip::lookup_plan_for the plan.
+// include/tfhe_hip.h states the operations, pbs_wave.h::cmux_tree_team the walk, passes.h the plan and the passes.
 namespace {
 
 constexpr size_t kMaxTreeDepth = 20;
 
-int lookup_plan_of(tfhe_context* ctx, size_t trees, size_t depth, launch::LookupPlanInfo* plan) {
-  hipError_t e = launch::lookup_plan(ctx->field, ctx->pbs, trees, (u32)depth, ctx->lookup_height, plan);
+// the plan of a tree of the lookup (cmux_tree_kernel's residency, the lookup's forced height) or of the update
+int tree_plan_of(tfhe_context* ctx, bool demux, size_t trees, size_t depth, passes::TreePlan* plan) {
+  unsigned resident = 0;
+  hipError_t e = demux ? launch::demux_resident_teams(ctx->field, ctx->pbs, &resident)
+                       : launch::tree_resident_teams(ctx->field, ctx->pbs, &resident);
+  if (e == hipSuccess && !passes::lookup_plan_for(trees, (u32)depth, demux ? ctx->demux_height : ctx->lookup_height, resident,
+                                                  glwe_words(ctx), plan))
+    e = hipErrorInvalidValue;
   if (e == hipErrorInvalidValue)
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "trees * 2^(depth - subtree height) exceeds the 2^31 - 1 teams of one launch");
-  if (e != hipSuccess) return hip_fail(ctx, e, "lookup plan");
+  if (e != hipSuccess) return hip_fail(ctx, e, demux ? "demux plan" : "lookup plan");
   return TFHE_OK;
-}
-
-// Words that cover EVERY call of at most `trees` trees and tree depths up to `depth`, whatever the subtree height is
-// set to then: the need under a given height is proportional to the number of trees (launch::lookup_workspace_glwes)
-// and the automatic rule picks one of the heights 1 .. d -- so the largest need over all heights at `trees` bounds them
-// all (at most 3/4 trees 2^depth GLWEs: height 1).  (The automatic height itself is NOT monotone in the number of
-// trees: sampling tree counts would miss some.)  Heights whose first pass would not fit a grid are skipped: such a call
-// is refused.  Host arithmetic only.
-size_t lookup_workspace_need(const tfhe_context* ctx, size_t trees, size_t depth) {
-  size_t glwes = 0;
-  for (size_t d = 1; d <= depth; ++d)
-    for (u32 h = 1; h <= d; ++h) {
-      size_t n = 0;
-      if (launch::lookup_workspace_glwes(trees, (u32)d, h, &n)) glwes = std::max(glwes, n);
-    }
-  return std::max<size_t>(1, glwes * glwe_words(ctx));
 }
 
 int grow_lookup_workspace(tfhe_context* ctx, size_t words) {
@@ -1215,57 +1206,19 @@ struct LookupLeaves {
 // (lwe_out only) min(address_bits, log2 N) rotation steps with selectors [0, first) and the sample extraction
 int run_lookup(tfhe_context* ctx, const void* selectors, size_t queries, size_t address_bits, size_t first, size_t tree_depth,
                const LookupLeaves& leaves, size_t tables, u32* glwe_out, u32* lwe_out) {
-  const size_t trees = queries * tables;
-  const size_t glwe = glwe_words(ctx);
-  launch::LookupPlanInfo plan{};
-  TFHE_TRY(lookup_plan_of(ctx, trees, tree_depth, &plan));
+  passes::TreePlan plan{};
+  TFHE_TRY(tree_plan_of(ctx, false, queries * tables, tree_depth, &plan));
   if (plan.workspace_words > ctx->lookup_ws_words)
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
                 "the call needs " + std::to_string(plan.workspace_words) + " words of lookup workspace, " +
                     std::to_string(ctx->lookup_ws_words) + " are reserved (tfhe_context_reserve_lookup)");
-  const size_t ggsw8 = prepared_ggsw_words(ctx);
-  const unsigned char* sel = static_cast<const unsigned char*>(selectors);
-  // workspace: [results of passes 0, 2, ..][results of passes 1, 3, ..][pending slots]
-  const size_t h = plan.height;
-  const size_t res_a = plan.launches >= 2 ? (trees << (tree_depth - h)) * glwe : 0;
-  const size_t res_b = plan.launches >= 3 ? (trees << (tree_depth - 2 * h)) * glwe : 0;
-  u32* results[2] = {ctx->d_lookup_ws, ctx->d_lookup_ws + res_a};
-  u32* pending = ctx->d_lookup_ws + res_a + res_b;
-  size_t done = 0;
-  const u32* from = nullptr;  // the previous pass's results
-  for (u32 i = 0; i < plan.launches; ++i) {
-    const size_t here = std::min(h, tree_depth - done);  // 0 only for tree_depth == 0
-    const bool last = i + 1 == plan.launches;
-    CmuxTreePass pass{};
-    pass.selectors = sel + (first + done) * ggsw8 * 8;
-    pass.rot_selectors = sel;
-    pass.query_stride = address_bits * ggsw8;
-    pass.tables = (u32)tables;
-    pass.height = (u32)here;
-    pass.log_subtrees = (u32)(tree_depth - done - here);
-    const size_t leaves_per_tree = (size_t)1 << (tree_depth - done);
-    if (i == 0 && leaves.table) {
-      pass.shared_sets = leaves.shared;
-      pass.table = leaves.table;
-      pass.table_stride = (size_t)1 << address_bits;
-      pass.log_entries = (u32)first;
-    } else {
-      const u32* base = i == 0 ? leaves.glwe : from;
-      pass.shared_sets = i == 0 && leaves.shared;
-      pass.even = base;
-      pass.odd = base + glwe;
-      pass.pair_stride = 2 * glwe;
-      pass.set_stride = leaves_per_tree * glwe;
-    }
-    pass.pending = pending;
-    pass.rot_steps = last && lwe_out ? (u32)first : 0u;
-    pass.glwe_out = last ? glwe_out : results[i & 1];
-    pass.lwe_out = last ? lwe_out : nullptr;
-    HIP_TRY(ctx, launch::cmux_tree_pass(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, pass, trees << pass.log_subtrees));
-    from = results[i & 1];
-    done += here;
-  }
-  return TFHE_OK;
+  const passes::LookupCall call{selectors, prepared_ggsw_words(ctx), glwe_words(ctx), queries, address_bits, first, tree_depth,
+                                leaves.glwe, leaves.table, leaves.shared, tables, glwe_out, lwe_out};
+  size_t ws_words = 0;
+  return passes::lookup_passes(plan, call, ctx->d_lookup_ws, &ws_words, [&](const CmuxTreePass& pass, size_t teams) {
+    HIP_TRY(ctx, launch::cmux_tree_pass(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, pass, teams));
+    return (int)TFHE_OK;
+  });
 }
 
 int check_lookup_args(tfhe_context* ctx, const void* selectors, const void* data, const void* out, size_t queries, size_t depth,
@@ -1292,7 +1245,7 @@ int tfhe_context_reserve_lookup(tfhe_context* ctx, size_t max_trees, size_t max_
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "max_tree_depth and max_lookup_bits are both 0: nothing to reserve for");
   // a lookup of D address bits runs a tree of D - log2 N levels (none up to log2 N bits)
   const size_t lookup_depth = max_lookup_bits > ctx->pbs.log_n ? max_lookup_bits - ctx->pbs.log_n : 0;
-  return grow_lookup_workspace(ctx, lookup_workspace_need(ctx, max_trees, std::max(max_tree_depth, lookup_depth)));
+  return grow_lookup_workspace(ctx, passes::lookup_workspace_need(max_trees, std::max(max_tree_depth, lookup_depth), glwe_words(ctx)));
 }
 
 int tfhe_context_set_lookup_subtree_height(tfhe_context* ctx, unsigned height) {
@@ -1307,8 +1260,8 @@ int tfhe_debug_lookup_plan(tfhe_context* ctx, size_t trees, size_t depth, unsign
   TFHE_TRY(check_present(ctx, {subtree_height, launches}, 1, "null pointer"));
   if (trees == 0 || trees > kMaxBatch || depth > kMaxTreeDepth)
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "trees must be in [1, 2^31), depth in [0, 20]");
-  launch::LookupPlanInfo plan{};
-  TFHE_TRY(lookup_plan_of(ctx, trees, depth, &plan));
+  passes::TreePlan plan{};
+  TFHE_TRY(tree_plan_of(ctx, false, trees, depth, &plan));
   *subtree_height = plan.height;
   *launches = plan.launches;
   return TFHE_OK;
@@ -1354,8 +1307,8 @@ static int lookup_host(tfhe_context* ctx, const uint32_t* selectors, size_t quer
                        size_t sets, size_t tables, bool is_table, uint32_t* out) {
   const size_t d_lo = is_table ? std::min(depth, (size_t)ctx->pbs.log_n) : 0;
   const size_t trees = queries * tables;
-  launch::LookupPlanInfo plan{};
-  TFHE_TRY(lookup_plan_of(ctx, trees, depth - d_lo, &plan));
+  passes::TreePlan plan{};
+  TFHE_TRY(tree_plan_of(ctx, false, trees, depth - d_lo, &plan));
   TFHE_TRY(grow_lookup_workspace(ctx, std::max<size_t>(plan.workspace_words, 1)));
   enum { kIn, kOut };
   Staging s(ctx, {sets * tables * ((size_t)1 << depth) * (is_table ? 1 : glwe_words(ctx)),
@@ -1384,16 +1337,8 @@ int tfhe_table_lookup(tfhe_context* ctx, const uint32_t* selectors, size_t queri
 
 // ---------------------------------------------------------------------------------- DEMUX tree / table update
 // include/tfhe_hip.h states the operations, pbs_wave.h::demux_tree_team the walk; the plan is the lookup's walked in
-// reverse (kernels.hip::lookup_plan_for): the top pass takes what ceil(d / h) - 1 passes of h levels leave over.
+// reverse (passes.h): the top pass takes what ceil(d / h) - 1 passes of h levels leave over.
 namespace {
-
-int demux_plan_of(tfhe_context* ctx, size_t trees, size_t depth, launch::LookupPlanInfo* plan) {
-  hipError_t e = launch::demux_plan(ctx->field, ctx->pbs, trees, (u32)depth, ctx->demux_height, plan);
-  if (e == hipErrorInvalidValue)
-    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "trees * 2^(depth - subtree height) exceeds the 2^31 - 1 teams of one launch");
-  if (e != hipSuccess) return hip_fail(ctx, e, "demux plan");
-  return TFHE_OK;
-}
 
 int grow_demux_workspace(tfhe_context* ctx, size_t words) {
   if (words <= ctx->demux_ws_words) return TFHE_OK;
@@ -1415,45 +1360,19 @@ int run_demux(tfhe_context* ctx, const void* selectors, size_t queries, size_t a
   const size_t glwe = glwe_words(ctx);
   if (overlap(roots, trees * glwe, leaves, ((shared ? values : trees) << tree_depth) * glwe))
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "the output overlaps the input");
-  launch::LookupPlanInfo plan{};
-  TFHE_TRY(demux_plan_of(ctx, trees, tree_depth, &plan));
+  passes::TreePlan plan{};
+  TFHE_TRY(tree_plan_of(ctx, true, trees, tree_depth, &plan));
   if (plan.workspace_words > ctx->demux_ws_words)
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
                 "the call needs " + std::to_string(plan.workspace_words * sizeof(u32)) + " bytes of demux workspace, " +
                     std::to_string(ctx->demux_ws_words * sizeof(u32)) + " are reserved (tfhe_context_reserve_demux)");
-  const size_t ggsw8 = prepared_ggsw_words(ctx);
-  const unsigned char* sel = static_cast<const unsigned char*>(selectors);
-  // workspace: [nodes of the passes launches - 2, launches - 4, ..][nodes of the passes launches - 3, ..][parked nodes]
-  const size_t h = plan.height;
-  const size_t res_a = plan.launches >= 2 ? (trees << (tree_depth - h)) * glwe : 0;
-  const size_t res_b = plan.launches >= 3 ? (trees << (tree_depth - 2 * h)) * glwe : 0;
-  u32* results[2] = {ctx->d_demux_ws, ctx->d_demux_ws + res_a};
-  u32* pending = ctx->d_demux_ws + res_a + res_b;
-  size_t done = 0;
-  const u32* from = roots;
-  for (u32 i = 0; i < plan.launches; ++i) {
-    const size_t here = i == 0 ? tree_depth - (plan.launches - 1) * h : h;  // 0 only for tree_depth == 0
-    const bool last = i + 1 == plan.launches;
-    DemuxTreePass pass{};
-    pass.selectors = sel + (rot_steps + tree_depth - done - here) * ggsw8 * 8;
-    pass.rot_selectors = sel;
-    pass.query_stride = address_bits * ggsw8;
-    pass.values = (u32)values;
-    pass.height = (u32)here;
-    pass.log_subtrees = (u32)done;
-    pass.rot_steps = i == 0 ? (u32)rot_steps : 0u;
-    pass.roots = from;
-    pass.pending = pending;
-    u32* to = last ? leaves : results[(plan.launches - 2 - i) & 1];
-    pass.leaves = to;
-    pass.set_stride = ((size_t)1 << (done + here)) * glwe;
-    pass.shared_sets = last && shared;
-    pass.accumulate = last && accumulate;
-    HIP_TRY(ctx, launch::demux_tree_pass(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, pass, trees << done));
-    from = to;
-    done += here;
-  }
-  return TFHE_OK;
+  const passes::DemuxCall call{selectors, prepared_ggsw_words(ctx), glwe, queries, address_bits, rot_steps, tree_depth,
+                               roots, values, leaves, shared, accumulate};
+  size_t ws_words = 0;
+  return passes::demux_passes(plan, call, ctx->d_demux_ws, &ws_words, [&](const DemuxTreePass& pass, size_t teams) {
+    HIP_TRY(ctx, launch::demux_tree_pass(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, pass, teams));
+    return (int)TFHE_OK;
+  });
 }
 
 int check_demux_args(tfhe_context* ctx, const void* selectors, const void* in, const void* out, size_t queries, size_t depth,
@@ -1476,7 +1395,7 @@ int tfhe_context_reserve_demux(tfhe_context* ctx, size_t max_trees, size_t max_t
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "max_tree_depth and max_write_bits are both 0: nothing to reserve for");
   // a write of D address bits runs a tree of D - log2 N levels (none up to log2 N bits); the need is the lookup's
   const size_t write_depth = max_write_bits > ctx->pbs.log_n ? max_write_bits - ctx->pbs.log_n : 0;
-  return grow_demux_workspace(ctx, lookup_workspace_need(ctx, max_trees, std::max(max_tree_depth, write_depth)));
+  return grow_demux_workspace(ctx, passes::lookup_workspace_need(max_trees, std::max(max_tree_depth, write_depth), glwe_words(ctx)));
 }
 
 int tfhe_context_set_demux_subtree_height(tfhe_context* ctx, unsigned height) {
@@ -1491,8 +1410,8 @@ int tfhe_debug_demux_plan(tfhe_context* ctx, size_t trees, size_t depth, unsigne
   TFHE_TRY(check_present(ctx, {subtree_height, launches}, 1, "null pointer"));
   if (trees == 0 || trees > kMaxBatch || depth > kMaxTreeDepth)
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "trees must be in [1, 2^31), depth in [0, 20]");
-  launch::LookupPlanInfo plan{};
-  TFHE_TRY(demux_plan_of(ctx, trees, depth, &plan));
+  passes::TreePlan plan{};
+  TFHE_TRY(tree_plan_of(ctx, true, trees, depth, &plan));
   *subtree_height = plan.height;
   *launches = plan.launches;
   return TFHE_OK;
@@ -1533,8 +1452,8 @@ static int demux_host(tfhe_context* ctx, const uint32_t* selectors, size_t queri
   const size_t trees = queries * values, glwe = glwe_words(ctx);
   const size_t out_words = ((sets * values) << (depth - d_lo)) * glwe;
   if (overlap(in, trees * glwe, out, out_words)) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "the output overlaps the input");
-  launch::LookupPlanInfo plan{};
-  TFHE_TRY(demux_plan_of(ctx, trees, depth - d_lo, &plan));
+  passes::TreePlan plan{};
+  TFHE_TRY(tree_plan_of(ctx, true, trees, depth - d_lo, &plan));
   TFHE_TRY(grow_demux_workspace(ctx, std::max<size_t>(plan.workspace_words, 1)));
   enum { kIn, kOut };
   Staging s(ctx, {trees * glwe, out_words});
@@ -1568,8 +1487,8 @@ int tfhe_table_lookup_glwe(tfhe_context* ctx, const uint32_t* selectors, size_t 
   TFHE_TRY(check_lookup_args(ctx, selectors, leaves, lwe_out, queries, depth, ctx->pbs.log_n + kMaxTreeDepth, leaf_sets, tables));
   const size_t d_hi = depth - std::min(depth, (size_t)ctx->pbs.log_n);
   const size_t trees = queries * tables;
-  launch::LookupPlanInfo plan{};
-  TFHE_TRY(lookup_plan_of(ctx, trees, d_hi, &plan));
+  passes::TreePlan plan{};
+  TFHE_TRY(tree_plan_of(ctx, false, trees, d_hi, &plan));
   TFHE_TRY(grow_lookup_workspace(ctx, std::max<size_t>(plan.workspace_words, 1)));
   enum { kIn, kOut };
   Staging s(ctx, {((leaf_sets * tables) << d_hi) * glwe_words(ctx), trees * big_lwe_words(ctx)});
@@ -1581,11 +1500,12 @@ int tfhe_table_lookup_glwe(tfhe_context* ctx, const uint32_t* selectors, size_t 
 }
 
 // ---------------------------------------------------------------------------------- encrypted branching program
-// include/tfhe_hip.h states the operations, pbs_wave.h::cmux_program_team the run of one team,
-// kernels.hip::program_plan_for the plan.
+// include/tfhe_hip.h states the operations, pbs_wave.h::cmux_program_team the run of one team, passes.h the level
+// sort, the image, the plan and the passes.
 namespace {
 
-constexpr size_t kOpWords = sizeof(ProgramOp) / sizeof(u32);
+using passes::program_image_need;
+static_assert(sizeof(tfhe_program_node) == 4 * sizeof(u32), "passes.h reads the nodes as [n_nodes][4] words");
 
 struct ProgramArgs {
   size_t queries, n_inputs, selector_sets;
@@ -1620,36 +1540,23 @@ int check_program(tfhe_context* ctx, const ProgramArgs& a) {
   return TFHE_OK;
 }
 
-// dependency levels: terminals 0, a node one more than its deeper operand.  -> nodes per level 1 .. depth and
-// (order != nullptr) the nodes sorted by level, by index within a level
+// passes.h::program_levels of the call's nodes
 void program_levels(const ProgramArgs& a, std::vector<u32>* level_counts, std::vector<u32>* order) {
-  std::vector<u32> level(a.n_nodes);
-  std::vector<u32>& counts = *level_counts;
-  counts.clear();
-  for (size_t i = 0; i < a.n_nodes; ++i) {
-    auto of = [&](u32 ref) { return ref < a.n_terminals ? 0u : level[ref - a.n_terminals]; };
-    level[i] = 1 + std::max(of(a.nodes[i].lo), of(a.nodes[i].hi));
-    if (level[i] > counts.size()) counts.resize(level[i], 0);
-    ++counts[level[i] - 1];
-  }
-  if (order) {
-    std::vector<u32> at(counts.size() + 1, 0);
-    for (size_t l = 0; l < counts.size(); ++l) at[l + 1] = at[l] + counts[l];
-    order->resize(a.n_nodes);
-    for (size_t i = 0; i < a.n_nodes; ++i) (*order)[at[level[i] - 1]++] = (u32)i;
-  }
+  passes::program_levels(reinterpret_cast<const u32*>(a.nodes), a.n_nodes, a.n_terminals, level_counts, order);
 }
 
-size_t program_image_need(size_t nodes, size_t outputs) { return nodes * kOpWords + outputs; }
 size_t program_bytes(const tfhe_context* ctx, size_t queries, size_t nodes, size_t outputs) {
   return (queries * nodes * glwe_words(ctx) + tfhe_context::kProgramImages * program_image_need(nodes, outputs)) * sizeof(u32);
 }
 
 int plan_program_of(tfhe_context* ctx, size_t queries, const std::vector<u32>& counts, size_t n_outputs,
-                    std::vector<launch::ProgramLaunch>* launches, launch::ProgramPlanInfo* info) {
+                    std::vector<passes::ProgramLaunch>* launches, passes::ProgramPlan* info) {
   launches->resize(counts.size() + 1);
-  hipError_t e = launch::program_plan(ctx->field, ctx->pbs, queries, counts.data(), (u32)counts.size(), (u32)n_outputs,
-                                      ctx->program_parts, launches->data(), info);
+  unsigned resident = 0;
+  hipError_t e = launch::program_resident_teams(ctx->field, ctx->pbs, &resident);
+  if (e == hipSuccess && !passes::program_plan_for(queries, counts.data(), (u32)counts.size(), (u32)n_outputs, ctx->program_parts,
+                                                   resident, launches->data(), info))
+    e = hipErrorInvalidValue;
   if (e == hipErrorInvalidValue)
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "queries * teams per query exceeds the 2^31 - 1 teams of one launch");
   if (e != hipSuccess) return hip_fail(ctx, e, "program plan");
@@ -1696,12 +1603,7 @@ int program_image(tfhe_context* ctx, const ProgramArgs& a, u32** d_image, const 
     std::vector<u32> order, level_counts;
     program_levels(a, &level_counts, &order);
     std::vector<u32> image(program_image_need(a.n_nodes, a.n_outputs));
-    for (size_t i = 0; i < a.n_nodes; ++i) {
-      const tfhe_program_node& n = a.nodes[order[i]];
-      const u32 op[kOpWords] = {n.sel, n.lo, n.hi, n.rot, order[i]};
-      std::copy(op, op + kOpWords, image.begin() + i * kOpWords);
-    }
-    std::copy(a.outputs, a.outputs + a.n_outputs, image.begin() + a.n_nodes * kOpWords);
+    passes::program_image(reinterpret_cast<const u32*>(a.nodes), order, a.outputs, a.n_outputs, image.data());
     slot->key.clear();  // not a valid entry until the upload has succeeded
     u32* dst = ctx->d_program_ws + ctx->program_value_words + (size_t)(slot - ctx->program_images) * ctx->program_image_words;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // launches of the image this one replaces may be in flight
@@ -1739,8 +1641,8 @@ int tfhe_debug_program_plan(tfhe_context* ctx, size_t queries, const tfhe_progra
   const uint32_t out0 = 0;
   ProgramArgs a{queries, kMaxBatch, 1, nodes, n_nodes, n_terminals, &out0, 1};
   TFHE_TRY(check_program(ctx, a));
-  std::vector<launch::ProgramLaunch> plan;
-  launch::ProgramPlanInfo info{};
+  std::vector<passes::ProgramLaunch> plan;
+  passes::ProgramPlan info{};
   std::vector<u32> counts;
   program_levels(a, &counts, nullptr);
   TFHE_TRY(plan_program_of(ctx, queries, counts, 1, &plan, &info));
@@ -1767,29 +1669,15 @@ int tfhe_cmux_program_device(tfhe_context* ctx, const void* selectors_prepared, 
   u32* d_image = nullptr;
   const std::vector<u32>* counts = nullptr;
   TFHE_TRY(program_image(ctx, a, &d_image, &counts));
-  std::vector<launch::ProgramLaunch> plan;
-  launch::ProgramPlanInfo info{};
+  std::vector<passes::ProgramLaunch> plan;
+  passes::ProgramPlan info{};
   TFHE_TRY(plan_program_of(ctx, queries, *counts, n_outputs, &plan, &info));
-  CmuxProgramPass pass{};
-  pass.selectors = selectors_prepared;
-  pass.query_stride = selector_sets == 1 ? 0 : n_inputs * prepared_ggsw_words(ctx);
-  pass.ops = reinterpret_cast<const ProgramOp*>(d_image);
-  pass.outputs = d_image + n_nodes * kOpWords;
-  pass.terminals = terminals;
-  pass.n_terminals = (u32)n_terminals;
-  pass.n_nodes = (u32)n_nodes;
-  pass.n_outputs = (u32)n_outputs;
-  pass.values = ctx->d_program_ws;
-  pass.glwe_out = glwe_out;
-  pass.lwe_out = lwe_out;
-  for (size_t i = 0; i < plan.size(); ++i) {
-    pass.parts = plan[i].parts;
-    pass.op_begin = plan[i].op_begin;
-    pass.op_end = plan[i].op_end;
-    pass.out_end = i + 1 == plan.size() ? (u32)n_outputs : 0u;
+  const passes::ProgramCall call{selectors_prepared, selector_sets == 1 ? 0 : n_inputs * prepared_ggsw_words(ctx), d_image, terminals,
+                                 (u32)n_terminals, (u32)n_nodes, (u32)n_outputs, ctx->d_program_ws, glwe_out, lwe_out};
+  return passes::program_passes(plan.data(), plan.size(), call, [&](const CmuxProgramPass& pass) {
     HIP_TRY(ctx, launch::cmux_program_pass(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, pass, queries));
-  }
-  return TFHE_OK;
+    return (int)TFHE_OK;
+  });
 }
 
 // host form: selectors [selector_sets][n_inputs][R][k+1][N] raw; everything uploaded, the selectors prepared once

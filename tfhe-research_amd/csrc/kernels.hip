@@ -12,9 +12,12 @@
 #include "glwe_conv.h"
 #include "launch.h"
 #include "lwe_dense.h"
+#include "passes.h"
 
 namespace tfhe {
 namespace {
+
+using passes::kMaxGrid;
 
 // waves per polynomial: one, except N = 2048, where four waves hold 8 elements per array each.
 // (With two waves -- 16 elements, 256 VGPRs -- a k = 2 team is 6 waves on a CU that then has room
@@ -1697,233 +1700,43 @@ hipError_t launch_pack_lwe(hipStream_t s, const PbsParams& P, const void* tw_v, 
   }
 }
 
-// How a CMUX tree of `depth` levels over `trees` trees goes out (capi.cpp sequences the launches).
-//   height    levels a team reduces: passes = ceil(depth / height) launches; every pass but the last takes `height`
-//             levels, the last one the rest (and, in a lookup, the rotation chain and the sample extraction).  Pass i
-//             writes trees 2^(depth - levels so far) partial results to the workspace, the next one reads them as its
-//             leaves (two buffers in turn).  A depth of 0 (a lookup of at most log2 N address bits) is one launch.
-// The automatic height trades passes against teams: a team of height h makes 2^h - 1 products one after the other, a
-// pass of T teams on a chip that holds R of them at once takes ceil(T / R) rounds of that, and every launch costs
-// about kLookupLaunchCost products (launch + the chip draining and refilling; a guess, not measured).  The height with
-// the smallest sum over its passes is taken, the larger one on a tie -- many trees: one pass, deep subtrees, nothing
-// through the workspace; one tree: short passes that spread its leaves over the chip.  The rule depends on the shape
-// of the call only (trees, depth), never on data; tfhe_context_set_lookup_subtree_height overrides it.
-constexpr unsigned kLookupLaunchCost = 2;
-constexpr size_t kMaxGrid = 0x7FFFFFFFull;
-struct LookupPlan {
-  u32 height;
-  u32 launches;
-  size_t workspace_words;  // partial results of the passes + the teams' pending slots
-};
-template <class F, int LOGN, int K>
-struct TreeKernel {
+// The three pass kernels -- cmux_tree_kernel, demux_tree_kernel, cmux_program_kernel -- share a team (TeamCfg<.., 1>)
+// and a signature (P, the twiddles, the pass struct by value): one trait, the kernel named by its pass struct.  Which
+// passes go out, with how many teams and over which workspace, is host arithmetic (passes.h; capi.cpp sequences them).
+template <class F, int LOGN, int K, class Pass>
+struct PassKernel {
   using C = TeamCfg<F, LOGN, K, 1>;
   static constexpr int kThreads = C::kThreads;
   static constexpr size_t kLds = C::kLds;
-  static auto get() { return cmux_tree_kernel<F, LOGN, K>; }
+  static auto get() {
+    if constexpr (std::is_same<Pass, CmuxTreePass>::value) return cmux_tree_kernel<F, LOGN, K>;
+    else if constexpr (std::is_same<Pass, DemuxTreePass>::value) return demux_tree_kernel<F, LOGN, K>;
+    else return cmux_program_kernel<F, LOGN, K>;
+  }
 };
-// The DEMUX tree goes out by the same plan walked in reverse (capi.cpp::run_demux): the top pass takes the rest, every
-// later one `height` levels, so pass i of one is pass (launches - 1 - i) of the other -- the same teams, products and
-// workspace -- with the residency of its own kernel.
-template <class F, int LOGN, int K>
-struct DemuxKernel {
-  using C = TeamCfg<F, LOGN, K, 1>;
-  static constexpr int kThreads = C::kThreads;
-  static constexpr size_t kLds = C::kLds;
-  static auto get() { return demux_tree_kernel<F, LOGN, K>; }
-};
-inline double lookup_cost(size_t trees, u32 depth, u32 h, size_t resident) {
-  double cost = 0;
-  for (u32 done = 0; done < depth;) {
-    const u32 here = depth - done < h ? depth - done : h;
-    done += here;
-    const double teams = (double)trees * (double)((size_t)1 << (depth - done));
-    cost += std::ceil(teams / (double)resident) * (double)(((size_t)1 << here) - 1) + kLookupLaunchCost;
-  }
-  return cost;
-}
-inline bool lookup_plan_for(size_t trees, u32 depth, u32 forced_height, size_t resident, size_t glwe_words, LookupPlan* out) {
-  if (depth == 0) {
-    *out = LookupPlan{0u, 1u, 0};
-    return trees <= kMaxGrid;
-  }
-  u32 h = forced_height > depth ? depth : forced_height;
-  if (h == 0) {
-    double best = 0;
-    for (u32 cand = 1; cand <= depth; ++cand) {
-      if ((double)trees * (double)((size_t)1 << (depth - cand)) > (double)kMaxGrid) continue;
-      const double cost = lookup_cost(trees, depth, cand, resident);
-      if (h == 0 || cost <= best) {
-        best = cost;
-        h = cand;
-      }
-    }
-    if (h == 0) return false;
-  }
-  const u32 passes = (depth + h - 1) / h;
-  size_t glwes = 0;
-  if (!launch::lookup_workspace_glwes(trees, depth, h, &glwes)) return false;
-  *out = LookupPlan{h, passes, glwes * glwe_words};
-  return true;
+
+template <class F, int LOGN, int K, class Pass>
+hipError_t pass_resident_teams(unsigned* out) {
+  if constexpr (!field_shape_ok<F, LOGN>()) return hipErrorInvalidValue;
+  else return resident_teams<PassKernel<F, LOGN, K, Pass>>(out);
 }
 
-template <class F, int LOGN, int K, template <class, int, int> class Kernel = TreeKernel>
-hipError_t plan_lookup(size_t trees, u32 depth, u32 forced_height, launch::LookupPlanInfo* out) {
+// pass.query_stride arrives in 8-byte words, like launch_external_product's stride.  One instantiation per kernel, so
+// one lds_done flag per kernel.
+template <class F, int LOGN, int K, class Pass>
+hipError_t launch_pass(hipStream_t s, const PbsParams& P, const void* tw_v, Pass pass, size_t teams) {
   if constexpr (!field_shape_ok<F, LOGN>()) {
     return hipErrorInvalidValue;
   } else {
-    unsigned resident = 0;
-    hipError_t e = resident_teams<Kernel<F, LOGN, K>>(&resident);
-    if (e != hipSuccess) return e;
-    LookupPlan plan{};
-    if (!lookup_plan_for(trees, depth, forced_height, resident, (size_t)(K + 1) << LOGN, &plan)) return hipErrorInvalidValue;
-    out->height = plan.height;
-    out->launches = plan.launches;
-    out->workspace_words = plan.workspace_words;
-    return hipSuccess;
-  }
-}
-
-// pass.query_stride arrives in 8-byte words, like launch_external_product's stride
-template <class F, int LOGN, int K>
-hipError_t launch_cmux_tree_pass(hipStream_t s, const PbsParams& P, const void* tw_v, CmuxTreePass pass, size_t teams) {
-  if constexpr (!field_shape_ok<F, LOGN>()) {
-    return hipErrorInvalidValue;
-  } else {
-    using C = TeamCfg<F, LOGN, K, 1>;
+    using PK = PassKernel<F, LOGN, K, Pass>;
     if (teams == 0 || teams > kMaxGrid) return hipErrorInvalidValue;
     auto tw = static_cast<const typename F::elem*>(tw_v);
-    auto kern = cmux_tree_kernel<F, LOGN, K>;
+    auto kern = PK::get();
     static std::atomic<unsigned long long> lds_done{0};
-    hipError_t e = allow_lds(kern, C::kLds, lds_done);
+    hipError_t e = allow_lds(kern, PK::kLds, lds_done);
     if (e != hipSuccess) return e;
     pass.query_stride /= sizeof(typename F::elem) / 8;
-    hipLaunchKernelGGL(kern, dim3((unsigned)teams), dim3(C::kThreads), C::kLds, s, P, tw, pass);
-    return hipGetLastError();
-  }
-}
-
-template <class F, int LOGN, int K>
-hipError_t launch_demux_tree_pass(hipStream_t s, const PbsParams& P, const void* tw_v, DemuxTreePass pass, size_t teams) {
-  if constexpr (!field_shape_ok<F, LOGN>()) {
-    return hipErrorInvalidValue;
-  } else {
-    using C = TeamCfg<F, LOGN, K, 1>;
-    if (teams == 0 || teams > kMaxGrid) return hipErrorInvalidValue;
-    auto tw = static_cast<const typename F::elem*>(tw_v);
-    auto kern = demux_tree_kernel<F, LOGN, K>;
-    static std::atomic<unsigned long long> lds_done{0};
-    hipError_t e = allow_lds(kern, C::kLds, lds_done);
-    if (e != hipSuccess) return e;
-    pass.query_stride /= sizeof(typename F::elem) / 8;
-    hipLaunchKernelGGL(kern, dim3((unsigned)teams), dim3(C::kThreads), C::kLds, s, P, tw, pass);
-    return hipGetLastError();
-  }
-}
-
-// How a branching program goes out (capi.cpp sequences the launches).  The host orders the nodes by dependency level
-// (terminals 0, a node one more than its deeper operand), so the nodes of a level are consecutive and independent of
-// each other.  Under `parts` teams per query a level of c nodes is dealt to min(parts, c) teams in one launch of its own;
-// consecutive levels that get one team are merged into one launch (values that cross teams cross a launch boundary).
-// The outputs ride on the last launch if that one has one team per query, else on a launch of their own.  parts = 1 is
-// therefore ONE launch, one team per query: the throughput case.  The cost model is the lookup's: a launch of T teams
-// whose teams make m products one after the other takes ceil(T / resident) m products, plus kLookupLaunchCost products
-// per launch (that guess again: not measured).  The automatic rule takes the cheapest of parts = 1, 2, 4, .. up to the
-// widest level (the smaller one on a tie); it depends on the shape of the call only (queries, level widths).
-template <class F, int LOGN, int K>
-struct ProgramKernel {
-  using C = TeamCfg<F, LOGN, K, 1>;
-  static constexpr int kThreads = C::kThreads;
-  static constexpr size_t kLds = C::kLds;
-  static auto get() { return cmux_program_kernel<F, LOGN, K>; }
-};
-inline double program_split(size_t queries, const u32* counts, u32 levels, u32 n_outputs, u32 parts, size_t resident,
-                            launch::ProgramLaunch* out, u32* launches, u32* widest) {
-  double cost = 0;
-  u32 n = 0, at = 0, wide = 1, last_parts = 0;
-  auto teams_of = [&](u32 l) { return counts[l] < parts ? counts[l] : parts; };
-  for (u32 l = 0; l < levels;) {
-    const u32 tp = teams_of(l), begin = at;
-    u32 per_team = 0;
-    if (tp == 1) {
-      for (; l < levels && teams_of(l) == 1; ++l) per_team += counts[l], at += counts[l];
-    } else {
-      per_team = (counts[l] + tp - 1) / tp;
-      at += counts[l++];
-    }
-    if (out) out[n] = launch::ProgramLaunch{begin, at, tp};
-    ++n;
-    last_parts = tp;
-    if (tp > wide) wide = tp;
-    cost += std::ceil((double)queries * tp / (double)resident) * per_team + kLookupLaunchCost;
-  }
-  if (last_parts != 1) {  // no launch yet, or the last level is split
-    const u32 tp = n_outputs < parts ? n_outputs : parts;
-    if (out) out[n] = launch::ProgramLaunch{at, at, tp ? tp : 1u};
-    ++n;
-    cost += kLookupLaunchCost;
-  }
-  *launches = n;
-  *widest = wide;
-  return cost;
-}
-inline bool program_plan_for(size_t queries, const u32* counts, u32 levels, u32 n_outputs, u32 forced_parts, size_t resident,
-                             launch::ProgramLaunch* out, launch::ProgramPlanInfo* info) {
-  u32 widest_level = 1;
-  for (u32 l = 0; l < levels; ++l)
-    if (counts[l] > widest_level) widest_level = counts[l];
-  u32 parts = forced_parts;
-  u32 launches = 0, wide = 0;
-  if (parts == 0) {
-    double best = 0;
-    for (u32 cand = 1;; cand = cand * 2 < widest_level ? cand * 2 : widest_level) {
-      if ((double)queries * cand > (double)kMaxGrid) break;
-      const double cost = program_split(queries, counts, levels, n_outputs, cand, resident, nullptr, &launches, &wide);
-      if (parts == 0 || cost < best) {
-        best = cost;
-        parts = cand;
-      }
-      if (cand >= widest_level) break;
-    }
-    if (parts == 0) return false;
-  }
-  if (parts > widest_level && parts > n_outputs) parts = widest_level > n_outputs ? widest_level : n_outputs;
-  if ((double)queries * parts > (double)kMaxGrid) return false;
-  program_split(queries, counts, levels, n_outputs, parts, resident, out, &launches, &wide);
-  info->launches = launches;
-  info->teams_per_query = wide;
-  return true;
-}
-
-template <class F, int LOGN, int K>
-hipError_t plan_program(size_t queries, const u32* counts, u32 levels, u32 n_outputs, u32 forced_parts,
-                        launch::ProgramLaunch* out, launch::ProgramPlanInfo* info) {
-  if constexpr (!field_shape_ok<F, LOGN>()) {
-    return hipErrorInvalidValue;
-  } else {
-    unsigned resident = 0;
-    hipError_t e = resident_teams<ProgramKernel<F, LOGN, K>>(&resident);
-    if (e != hipSuccess) return e;
-    return program_plan_for(queries, counts, levels, n_outputs, forced_parts, resident, out, info) ? hipSuccess : hipErrorInvalidValue;
-  }
-}
-
-// pass.query_stride arrives in 8-byte words, like launch_cmux_tree_pass's
-template <class F, int LOGN, int K>
-hipError_t launch_cmux_program_pass(hipStream_t s, const PbsParams& P, const void* tw_v, CmuxProgramPass pass, size_t queries) {
-  if constexpr (!field_shape_ok<F, LOGN>()) {
-    return hipErrorInvalidValue;
-  } else {
-    using C = TeamCfg<F, LOGN, K, 1>;
-    const size_t teams = queries * pass.parts;
-    if (teams == 0 || teams > kMaxGrid) return hipErrorInvalidValue;
-    auto tw = static_cast<const typename F::elem*>(tw_v);
-    auto kern = cmux_program_kernel<F, LOGN, K>;
-    static std::atomic<unsigned long long> lds_done{0};
-    hipError_t e = allow_lds(kern, C::kLds, lds_done);
-    if (e != hipSuccess) return e;
-    pass.query_stride /= sizeof(typename F::elem) / 8;
-    hipLaunchKernelGGL(kern, dim3((unsigned)teams), dim3(C::kThreads), C::kLds, s, P, tw, pass);
+    hipLaunchKernelGGL(kern, dim3((unsigned)teams), dim3(PK::kThreads), PK::kLds, s, P, tw, pass);
     return hipGetLastError();
   }
 }
@@ -2193,45 +2006,28 @@ hipError_t packing_add_gadget(hipStream_t s, u32* pksk, size_t rows, u32 k, u32 
   return hipGetLastError();
 }
 
-bool lookup_workspace_glwes(size_t trees, u32 depth, u32 height, size_t* glwes) {
-  if (depth == 0) {
-    *glwes = 0;
-    return trees <= 0x7FFFFFFFull;
-  }
-  const u32 h = height > depth ? depth : height;
-  const u32 passes = (depth + h - 1) / h;
-  const double teams0 = (double)trees * (double)((size_t)1 << (depth - h));
-  if (h == 0 || teams0 > (double)0x7FFFFFFFull) return false;
-  size_t n = (size_t)teams0 * (h - 1);                              // pending slots: the first pass has the most teams
-  if (passes >= 2) n += (size_t)teams0;                              // results of passes 0, 2, ..
-  if (passes >= 3) n += trees * ((size_t)1 << (depth - 2 * h));      // results of passes 1, 3, ..
-  *glwes = n;
-  return true;
-}
-
-hipError_t lookup_plan(int field, const PbsParams& P, size_t trees, u32 depth, u32 forced_height, LookupPlanInfo* out) {
-  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (plan_lookup<FF, LL, KK>(trees, depth, forced_height, out))));
+hipError_t tree_resident_teams(int field, const PbsParams& P, unsigned* out) {
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (pass_resident_teams<FF, LL, KK, CmuxTreePass>(out))));
 }
 
 hipError_t cmux_tree_pass(hipStream_t s, int field, const PbsParams& P, const void* tw, const CmuxTreePass& pass, size_t teams) {
-  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (launch_cmux_tree_pass<FF, LL, KK>(s, P, tw, pass, teams))));
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (launch_pass<FF, LL, KK>(s, P, tw, pass, teams))));
 }
 
-hipError_t demux_plan(int field, const PbsParams& P, size_t trees, u32 depth, u32 forced_height, LookupPlanInfo* out) {
-  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (plan_lookup<FF, LL, KK, DemuxKernel>(trees, depth, forced_height, out))));
+hipError_t demux_resident_teams(int field, const PbsParams& P, unsigned* out) {
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (pass_resident_teams<FF, LL, KK, DemuxTreePass>(out))));
 }
 
 hipError_t demux_tree_pass(hipStream_t s, int field, const PbsParams& P, const void* tw, const DemuxTreePass& pass, size_t teams) {
-  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (launch_demux_tree_pass<FF, LL, KK>(s, P, tw, pass, teams))));
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (launch_pass<FF, LL, KK>(s, P, tw, pass, teams))));
 }
 
-hipError_t program_plan(int field, const PbsParams& P, size_t queries, const u32* level_counts, u32 levels, u32 n_outputs,
-                        u32 forced_parts, ProgramLaunch* out, ProgramPlanInfo* info) {
-  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (plan_program<FF, LL, KK>(queries, level_counts, levels, n_outputs, forced_parts, out, info))));
+hipError_t program_resident_teams(int field, const PbsParams& P, unsigned* out) {
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (pass_resident_teams<FF, LL, KK, CmuxProgramPass>(out))));
 }
 
 hipError_t cmux_program_pass(hipStream_t s, int field, const PbsParams& P, const void* tw, const CmuxProgramPass& pass, size_t queries) {
-  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (launch_cmux_program_pass<FF, LL, KK>(s, P, tw, pass, queries))));
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (launch_pass<FF, LL, KK>(s, P, tw, pass, queries * pass.parts))));
 }
 
 hipError_t key_switch_plan(const KsParams& K, u32 big_n, u32 n, size_t batch, int path, KeySwitchPlanInfo* out) {

@@ -123,44 +123,18 @@ hipError_t tree_lut_expand(hipStream_t s, const u32* in, size_t count, size_t pe
 hipError_t tree_lut_test_vectors(hipStream_t s, const u32* table, size_t set_stride, size_t count, size_t per_row, u32 log_p,
                                  u32 log_n, u32* tv);
 
-// ---- CMUX tree / encrypted table lookup (pbs_wave.h::cmux_tree_team)
-// How a tree of `depth` levels over `trees` trees goes out (kernels.hip::lookup_plan_for); forced_height 0: automatic.
-// hipErrorInvalidValue: no height keeps the first pass inside a grid of 2^31 - 1 teams.
-struct LookupPlanInfo {
-  u32 height;              // levels a team reduces (0 for depth 0)
-  u32 launches;            // ceil(depth / height), at least 1
-  size_t workspace_words;  // u32 words of scratch the passes need (partial results and pending slots)
-};
-hipError_t lookup_plan(int field, const PbsParams& P, size_t trees, u32 depth, u32 forced_height, LookupPlanInfo* out);
-// GLWEs of scratch a tree of `depth` levels over `trees` trees needs at subtree height `height` >= 1 (pending slots of
-// the first pass + the two result buffers): host arithmetic on the shape alone, proportional to `trees`.  false: the
-// first pass would not fit a grid of 2^31 - 1 teams.
-bool lookup_workspace_glwes(size_t trees, u32 depth, u32 height, size_t* glwes);
-// one pass: `teams` = trees << pass.log_subtrees workgroups.  pass.query_stride in 8-byte words here.
+// ---- CMUX tree / encrypted table lookup (pbs_wave.h::cmux_tree_team), DEMUX tree / encrypted table update
+// (demux_tree_team) and encrypted branching program (cmux_program_team).  Which passes go out is host arithmetic
+// (passes.h); here is what needs the device: the teams of a feature's kernel the current device holds at once (the
+// automatic rules' `resident`), and the launch of one pass.  pass.query_stride in 8-byte words here.
+hipError_t tree_resident_teams(int field, const PbsParams& P, unsigned* out);
+// `teams` = trees << pass.log_subtrees workgroups
 hipError_t cmux_tree_pass(hipStream_t s, int field, const PbsParams& P, const void* tw, const CmuxTreePass& pass, size_t teams);
-
-// ---- DEMUX tree / encrypted table update (pbs_wave.h::demux_tree_team): the lookup's plan walked in reverse -- the top
-// pass takes depth - (launches - 1) height levels, every later one `height` -- with the same workspace
-// (lookup_workspace_glwes) and the residency of the DEMUX kernel
-hipError_t demux_plan(int field, const PbsParams& P, size_t trees, u32 depth, u32 forced_height, LookupPlanInfo* out);
-// one pass: `teams` = trees << pass.log_subtrees workgroups.  pass.query_stride in 8-byte words here.
+hipError_t demux_resident_teams(int field, const PbsParams& P, unsigned* out);
+// `teams` = trees << pass.log_subtrees workgroups
 hipError_t demux_tree_pass(hipStream_t s, int field, const PbsParams& P, const void* tw, const DemuxTreePass& pass, size_t teams);
-
-// ---- encrypted branching program (pbs_wave.h::cmux_program_team; the plan: kernels.hip::program_plan_for)
-// one launch: ops [op_begin, op_end) of the execution order dealt to `parts` teams per query; the LAST launch of a plan
-// also carries the outputs (op_begin == op_end: only them)
-struct ProgramLaunch {
-  u32 op_begin, op_end, parts;
-};
-struct ProgramPlanInfo {
-  u32 launches;
-  u32 teams_per_query;  // the most teams any launch gives a query
-};
-// level_counts [levels]: nodes per dependency level in execution order; `out` has room for levels + 1 launches.
-// forced_parts 0: automatic.  hipErrorInvalidValue: queries * parts exceeds a grid of 2^31 - 1 teams.
-hipError_t program_plan(int field, const PbsParams& P, size_t queries, const u32* level_counts, u32 levels, u32 n_outputs,
-                        u32 forced_parts, ProgramLaunch* out, ProgramPlanInfo* info);
-// one pass: queries * pass.parts workgroups.  pass.query_stride in 8-byte words here.
+hipError_t program_resident_teams(int field, const PbsParams& P, unsigned* out);
+// queries * pass.parts workgroups
 hipError_t cmux_program_pass(hipStream_t s, int field, const PbsParams& P, const void* tw, const CmuxProgramPass& pass, size_t queries);
 
 // ---- dense layer (lwe_dense.h::dense_tile; the plan: kernels.hip::dense_plan_for)

@@ -1672,7 +1672,7 @@ TFHE_HD void demux_tree_team(const Ctx& c, const PbsParams& P, const DemuxTreePa
 // lanes wrote: its operand is staged in acc by the owning lanes, the product starts behind poly_sync, and all rotated
 // reads precede the product's first inverse transform; the sync that ends every product (poly_sync on one exchange
 // buffer, the product's own team barrier on two) keeps the next staging behind those reads.  Values that cross teams
-// cross a launch boundary (kernels.hip::program_plan_for), never a barrier inside a launch.
+// cross a launch boundary (passes.h::program_plan_for), never a barrier inside a launch.
 //
 // CmuxProgramPass: one launch (kernels.hip::cmux_program_kernel).  Team (query, part) runs the part-th share of ops
 // [op_begin, op_end) and of outputs [out_begin, out_end), shares of ceil(count / parts) consecutive entries.
