@@ -685,6 +685,34 @@ inline LweCiphertext tree_lut(Engine& e, const std::vector<LweCiphertext>& digit
   e.check(tfhe_tree_lut_batch(e.raw(), ptrs.data(), d, 1, table.data(), 1, 1, out.data.data()));
   return out;
 }
+// ---- digit extraction and the wide LUT (tfhe_hip.h states the operations; first device only) ----
+// (ciphertexts of n + 1 words: the reference's bootstrap order only, like the wrappers around them; the key-switch-first
+// order's k N + 1 words go through the C ABI)
+// ONE ciphertext of n + 1 words with phase v 2^lsb + e -> its `digits` digits of `digit_bits` bits at out_lsb, digit 0
+// least significant; remainder (may be null) receives the input with the extracted bits cleared: the carry
+inline std::vector<LweCiphertext> extract_digits(Engine& e, const LweCiphertext& ct, unsigned lsb, unsigned digit_bits, unsigned digits,
+                                                 unsigned out_lsb, LweCiphertext* remainder = nullptr) {
+  const size_t words = ct.data.size();
+  if (words != size_t(e.params().lwe_dimension) + 1) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "LWE length");
+  if (digits == 0 || digits > 16) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "digits in 1..16");
+  std::vector<LweCiphertext> out(digits, LweCiphertext{std::vector<uint32_t>(words)});
+  std::vector<uint32_t*> ptrs(digits);
+  for (unsigned t = 0; t < digits; ++t) ptrs[t] = out[t].data.data();
+  if (remainder) remainder->data.assign(words, 0u);
+  e.check(tfhe_extract_digits_batch(e.raw(), ct.data.data(), 1, lsb, digit_bits, digits, out_lsb, ptrs.data(),
+                                    remainder ? remainder->data.data() : nullptr));
+  return out;
+}
+// T[v] of the d log_p low bits v of ONE encrypted value (phase v 2^lsb + e): table holds B^d un-encoded entries
+inline LweCiphertext wide_lut(Engine& e, const LweCiphertext& ct, unsigned lsb, size_t d, const std::vector<uint32_t>& table) {
+  const TfheParams& p = e.params();
+  if (d == 0 || d * p.log_p > 16 || table.size() != (size_t)1 << (d * p.log_p))
+    throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "B^d table entries, d * log_p in 1..16");
+  if (ct.data.size() != size_t(p.lwe_dimension) + 1) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "LWE length");
+  LweCiphertext out{std::vector<uint32_t>(size_t(p.lwe_dimension) + 1)};
+  e.check(tfhe_wide_lut_batch(e.raw(), ct.data.data(), 1, lsb, d, table.data(), 1, 1, out.data.data()));
+  return out;
+}
 // ---- encrypted dense layers (tfhe_hip.h states the operations; first device only) ----
 // Dense(W, bias; x) for ONE query: x holds the I input ciphertexts (all of one length), weights [O][I] row-major int32,
 // bias [O] already ENCODED words or empty -> O ciphertexts of that length, out[o] = sum_i W[o][i] x[i] (+ bias[o] on the body)

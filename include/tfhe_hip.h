@@ -600,6 +600,78 @@ int tfhe_dense_bootstrap_batch_device(tfhe_context *ctx, const uint32_t *x, size
                                       const int32_t *weights, const uint32_t *bias, size_t outputs,
                                       const uint32_t *test_vector_poly, size_t tv_count, uint32_t *lwe_out);
 
+/* ---- digit extraction: one LWE sum into bits or digits (no reference counterpart) ------------------------------------
+ * The linear layers add ciphertexts exactly, so a sum of m inputs is log2 m bits wider than its inputs, while a
+ * bootstrap resolves log_p bits, the tree LUT takes separate digits and the gates single bits.  This call takes the
+ * wide value apart, least significant bit first, with one sign bootstrap per bit (FHE-DiNN's "sum, then split"; the
+ * radix schemes' carry extraction).  Every bit is decided at bit 31, with a margin of 2^30, whatever its position.
+ *
+ * All arithmetic is mod 2^32.  lwe_in [batch][io_words] (io_words = n + 1, or k N + 1 with the key switch first) has
+ * phase v 2^lsb + e.  The call extracts w = g d bits of v (g = digit_bits, d = digits), bit 0 first.  r_0 = lwe_in; for
+ * j = 0 .. w-1, with t = j div g and i = j mod g:
+ *   m_j     = min(lsb + j, out_lsb + i),   kappa_j = 2^(m_j - 1)
+ *   s_j     = 2^(31-lsb-j) r_j                                          on every word
+ *   o_j     = tfhe_bootstrap_glwe_batch(s_j; acc_in = (0, .., 0, kappa_j (1 + X + .. + X^(N-1))), acc_count = 1,
+ *                                       rotation_offset = N / 2)        in the context's bootstrap order: phase
+ *                                                                       +kappa_j for bit 0, -kappa_j for bit 1
+ *   beta_j  = (0, .., 0, kappa_j) - o_j                                 phase b_j 2^(m_j)
+ *   r_(j+1) = r_j - 2^(lsb+j-m_j) beta_j
+ *   D_t    += 2^(out_lsb+i-m_j) beta_j                                  D_t starts at 0
+ * digits_out is a host array of d pointers (device pointers in the _device form), each [batch][io_words]: digit t has
+ * phase x_t 2^out_lsb, digit 0 least significant.  remainder_out [batch][io_words] may be NULL; it is r_w, the input
+ * with the w extracted bits cleared: the bits of v above w stay in it (the carry).
+ *
+ * Limits: lsb >= 1 and out_lsb >= 1 (bit m_j - 1 holds the constant), lsb + w <= 32, out_lsb + g <= 32, 1 <= g, 1 <= d,
+ * w <= 16.  Three settings cover the uses: g = 1, out_lsb = 32 - log_p - padding_bits gives gate-compatible bits;
+ * g = log_p at the same out_lsb gives tree-LUT digits; lsb = out_lsb extracts a popcount of gate bits in place,
+ * padding bit included.
+ *
+ * The words equal, byte for byte, the composition of tfhe_lwe_linear_batch, tfhe_bootstrap_glwe_batch and
+ * tfhe_lwe_dense_batch with a bias for the constants.  Plan: the only host loop is over the w bits; a bit is one
+ * bootstrap call and ONE elementwise launch (csrc/lwe_extract.h) that does step j's epilogue and step j+1's prologue
+ * and writes the next constant accumulator: w bootstraps and w + 1 small launches per call, whatever the batch.
+ *
+ * Refused: TFHE_ERR_INVALID_ARGUMENT for a limit crossed, a NULL pointer, an empty batch, digit buffers that overlap
+ * each other, remainder_out or (device form) lwe_in; TFHE_ERR_NO_KEY without a bootstrapping key; TFHE_ERR_UNSUPPORTED
+ * with a BMMP key (the rotations start from a GLWE accumulator).
+ *
+ * Workspace: tfhe_context_reserve_extract(max_batch, max_digits) reserves, on top of tfhe_context_reserve(max_batch), r,
+ * s, o and max_digits digit buffers of max_batch * (max(n, k N) + 1) words each (either bootstrap order fits) and one
+ * accumulator of (k+1) N words.  After it the _device form allocates nothing, stays on the context's stream and can be
+ * captured; it writes the digits to the caller's buffers and uses no digit buffer of the workspace.  A call beyond the
+ * reservation returns TFHE_ERR_INVALID_ARGUMENT with the need in bytes.  The host form reserves for itself and blocks.
+ *
+ * Noise, in units of the 32-bit torus.  sigma_bs^2 is a bootstrap's output variance at the boundary: s_br^2 + s_ks^2 in
+ * the reference's order and s_br^2 with the key switch first, with s_br^2 as in the tree LUT above and
+ * s_ks^2 = k N l_ks (B_ks^2/12 + 1/6) (sigma_lwe 2^32)^2 + (k N / 2) 2^(2 ignored_bits_ks) / 12.  With
+ * A_j = 2^(lsb+j-m_j) and sigma_in^2 the input's variance,
+ *   Var(r_j) = sigma_in^2 + sum_{j' < j} A_j'^2 sigma_bs^2.
+ * Bit j is decided correctly while the error the rotation sees stays below 2^30: 2^(31-lsb-j) |e(r_j)|, plus the
+ * rotation's modulus-switch term of variance (1 + n/2) (2^32 / 2N)^2 / 12, plus -- with the key switch first -- the
+ * key-switch term s_ks^2, which is added after the scaling and so not amplified.  Digit t carries
+ *   sum_{i < g} 2^(2 (out_lsb+i-m_j)) sigma_bs^2,   j = t g + i,
+ * independent of sigma_in.  (Where out_lsb + i <= lsb + j, the usual case, every factor is 1: g sigma_bs^2.)
+ *
+ * ---- wide LUT: any function of a d log_p-bit encrypted value ----
+ * tfhe_wide_lut_batch is the extraction with g = log_p and out_lsb = 32 - log_p - padding_bits, remainder dropped,
+ * followed by tfhe_tree_lut_batch_device on the d digits: one call, byte-identical to that composition.  table, table_sets,
+ * tables and lwe_out [batch][tables][io_words] are the tree LUT's, with the tree LUT's limits, keys and refusals (the
+ * packing key included) on top of the extraction's.  tfhe_context_reserve_wide_lut(max_batch, max_digits, max_tables) is
+ * tfhe_context_reserve_extract(max_batch, max_digits) and tfhe_context_reserve_tree_lut(max_batch, max_digits,
+ * max_tables); the device form keeps its digits in the extraction workspace.  Noise: the extraction's digits enter the
+ * tree LUT with variance g sigma_bs^2; the output carries the tree LUT's own. */
+int tfhe_context_reserve_extract(tfhe_context *ctx, size_t max_batch, size_t max_digits);
+int tfhe_context_reserve_wide_lut(tfhe_context *ctx, size_t max_batch, size_t max_digits, size_t max_tables);
+int tfhe_extract_digits_batch(tfhe_context *ctx, const uint32_t *lwe_in, size_t batch, unsigned lsb, unsigned digit_bits,
+                              unsigned digits, unsigned out_lsb, uint32_t *const *digits_out, uint32_t *remainder_out);
+int tfhe_extract_digits_batch_device(tfhe_context *ctx, const uint32_t *lwe_in, size_t batch, unsigned lsb,
+                                     unsigned digit_bits, unsigned digits, unsigned out_lsb, uint32_t *const *digits_out,
+                                     uint32_t *remainder_out);
+int tfhe_wide_lut_batch(tfhe_context *ctx, const uint32_t *lwe_in, size_t batch, unsigned lsb, size_t d,
+                        const uint32_t *table, size_t table_sets, size_t tables, uint32_t *lwe_out);
+int tfhe_wide_lut_batch_device(tfhe_context *ctx, const uint32_t *lwe_in, size_t batch, unsigned lsb, size_t d,
+                               const uint32_t *table, size_t table_sets, size_t tables, uint32_t *lwe_out);
+
 /* ---- encrypted convolutions (no reference counterpart) --------------------------------------------
  * A matrix of clear polynomials with small integer coefficients times a batch of GLWE ciphertexts: the general leveled
  * operation on packed ciphertexts that needs no GGSW (tfhe_glwe_mul_monomial_batch is the case of one weight +-X^r).

@@ -11,7 +11,7 @@
 //!   construct_test_from_lut  test_vector.rs:38
 //!   bootstrapping_key_gen    bootstrapping.rs:23-28   encrypt_lwe_plaintext / decrypt_lwe  lwe.rs:138-173
 use ndarray::{Array1, Array2, Array3};
-use std::os::raw::{c_char, c_int, c_void};
+use std::os::raw::{c_char, c_int, c_uint, c_void};
 
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -80,6 +80,11 @@ extern "C" {
     fn tfhe_bootstrap_glwe_batch(ctx: *mut TfheContext, lwe_in: *const u32, batch: usize, acc_in: *const u32,
                                  acc_count: usize, rotation_offset: usize, lwe_out: *mut u32) -> c_int;
     fn tfhe_tree_lut_batch(ctx: *mut TfheContext, digits: *const *const u32, d: usize, batch: usize, table: *const u32,
+                           table_sets: usize, tables: usize, lwe_out: *mut u32) -> c_int;
+    // digit extraction and the wide LUT (include/tfhe_hip.h)
+    fn tfhe_extract_digits_batch(ctx: *mut TfheContext, lwe_in: *const u32, batch: usize, lsb: c_uint, digit_bits: c_uint,
+                                 digits: c_uint, out_lsb: c_uint, digits_out: *const *mut u32, remainder_out: *mut u32) -> c_int;
+    fn tfhe_wide_lut_batch(ctx: *mut TfheContext, lwe_in: *const u32, batch: usize, lsb: c_uint, d: usize, table: *const u32,
                            table_sets: usize, tables: usize, lwe_out: *mut u32) -> c_int;
     // encrypted dense layers (include/tfhe_hip.h)
     fn tfhe_lwe_dense_batch(ctx: *mut TfheContext, x: *const u32, queries: usize, inputs: usize, weights: *const i32,
@@ -433,6 +438,41 @@ pub fn tree_lut(bk: &GpuBootstrappingKey, digits: &Array2<u32>, table: &Array1<u
         tfhe_tree_lut_batch(bk.ctx, ptrs.as_ptr(), d, 1, table.as_slice().unwrap().as_ptr(), 1, 1,
                             out.as_slice_mut().unwrap().as_mut_ptr())
     }, "tree_lut");
+    out
+}
+
+/// Digit extraction: `lwe` (batch, n+1) with phase v 2^lsb + e -> (`digits` arrays (digits, batch, n+1) of `digit_bits`
+/// bits of v each at `out_lsb`, digit 0 least significant; the remainder (batch, n+1): the input with the extracted bits
+/// cleared).  One sign bootstrap per bit (no reference counterpart).  Ciphertexts of n+1 words: the reference's bootstrap
+/// order only, like the neighbouring wrappers (the key-switch-first order's k N + 1 words go through the C ABI).
+pub fn extract_digits(bk: &GpuBootstrappingKey, lwe: &Array2<u32>, lsb: u32, digit_bits: u32, digits: u32, out_lsb: u32)
+                      -> (Array3<u32>, Array2<u32>) {
+    let (batch, width) = lwe.dim();
+    assert!(width == bk.params.lwe_dimension as usize + 1 && batch >= 1 && digits >= 1 && digits <= 16,
+            "extract_digits: ciphertexts of n+1 words, digits in 1..=16");
+    let mut out = Array3::<u32>::zeros((digits as usize, batch, width));
+    let mut rem = Array2::<u32>::zeros((batch, width));
+    let flat = out.as_slice_mut().unwrap();
+    let ptrs: Vec<*mut u32> = (0..digits as usize).map(|t| flat[t * batch * width..].as_mut_ptr()).collect();
+    check(bk.ctx, unsafe {
+        tfhe_extract_digits_batch(bk.ctx, lwe.as_slice().unwrap().as_ptr(), batch, lsb as c_uint, digit_bits as c_uint,
+                                  digits as c_uint, out_lsb as c_uint, ptrs.as_ptr(), rem.as_slice_mut().unwrap().as_mut_ptr())
+    }, "extract_digits");
+    (out, rem)
+}
+
+/// Wide LUT: T[v] of the d log_p low bits v of every row of `lwe` (batch, n+1), phase v 2^lsb + e; `table` B^d un-encoded
+/// entries -> (batch, n+1).  extract_digits then tree_lut in one call.  The reference's bootstrap order only, as above.
+pub fn wide_lut(bk: &GpuBootstrappingKey, lwe: &Array2<u32>, lsb: u32, d: usize, table: &Array1<u32>) -> Array2<u32> {
+    let (batch, width) = lwe.dim();
+    let log_p = bk.params.log_p as usize;
+    assert!(d >= 1 && d * log_p <= 16 && width == bk.params.lwe_dimension as usize + 1, "wide_lut: n+1 words, d * log_p in 1..=16");
+    assert!(table.len() == 1usize << (d * log_p), "wide_lut: B^d entries");
+    let mut out = Array2::<u32>::zeros((batch, width));
+    check(bk.ctx, unsafe {
+        tfhe_wide_lut_batch(bk.ctx, lwe.as_slice().unwrap().as_ptr(), batch, lsb as c_uint, d, table.as_slice().unwrap().as_ptr(),
+                            1, 1, out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "wide_lut");
     out
 }
 

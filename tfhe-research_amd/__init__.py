@@ -720,6 +720,95 @@ class Context:
                                               C.c_size_t(tables), _hp(res)))
         return res
 
+    # -- digit extraction and the wide LUT (include/tfhe_hip.h states the operations) --------------
+    def reserve_extract(self, max_batch: int, max_digits: int):
+        """size the workspace of the device form of extract_digits (a maximum: smaller calls fit)"""
+        self._check(lib().tfhe_context_reserve_extract(self._h, C.c_size_t(max_batch), C.c_size_t(max_digits)))
+
+    def reserve_wide_lut(self, max_batch: int, max_digits: int, max_tables: int = 1):
+        """reserve_extract and reserve_tree_lut in one: the workspace of the device form of wide_lut"""
+        self._check(lib().tfhe_context_reserve_wide_lut(self._h, C.c_size_t(max_batch), C.c_size_t(max_digits),
+                                                        C.c_size_t(max_tables)))
+
+    def _extract_input(self, what, lwe_in):
+        """-> (lwe [batch][io_dim+1], batch, on the device?) after the checks the ABI cannot make on a bare pointer"""
+        width = self.io_dim + 1
+        dev = _is_torch(lwe_in)
+        lwe = lwe_in if dev else _np(lwe_in)
+        if len(lwe.shape) != 2 or int(lwe.shape[1]) != width or int(lwe.shape[0]) < 1 or \
+                (dev and (not lwe.is_cuda or not lwe.is_contiguous() or lwe.element_size() != 4 or lwe.is_floating_point())):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: lwe_in must be a contiguous 32-bit [batch][{width}] array")
+        return lwe, int(lwe.shape[0]), dev
+
+    def extract_digits(self, lwe_in, lsb: int, digit_bits: int, digits: int, out_lsb: int, remainder: bool = False, out=None):
+        """Split lwe_in [batch][io_dim+1] of phase v 2^lsb + e into `digits` digits of `digit_bits` bits of v, least
+        significant first, each a ciphertext of phase x_t 2^out_lsb: one sign bootstrap per bit.  -> the list of digit
+        arrays [batch][io_dim+1], or (that list, the remainder: lwe_in with the extracted bits cleared) with
+        remainder=True.  numpy (host form: reserves for itself, blocks) or a torch device tensor (reserve_extract first;
+        out: a list of `digits` tensors to write to)."""
+        lwe, batch, dev = self._extract_input("extract_digits", lwe_in)
+        for name, v in (("lsb", lsb), ("digit_bits", digit_bits), ("digits", digits), ("out_lsb", out_lsb)):
+            if not 0 <= int(v) <= 32:
+                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"extract_digits: {name} must be in [0, 32]")
+        if not 1 <= int(digits) <= 16:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "extract_digits: 1 <= digits <= 16 expected")
+        digits = int(digits)
+        shape = (batch, self.io_dim + 1)
+        args = (C.c_uint(int(lsb)), C.c_uint(int(digit_bits)), C.c_uint(digits), C.c_uint(int(out_lsb)))
+        ptrs = (_u32p * digits)()
+        if dev:
+            self._bind_torch()
+            import torch
+            if out is not None and len(out) != digits:
+                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"extract_digits: out must hold {digits} tensors")
+            outs = [self._lookup_out("extract_digits", None if out is None else out[t], shape, lwe) for t in range(digits)]
+            for t, x in enumerate(outs):
+                ptrs[t] = _dp(x)
+            rem = torch.empty(shape, dtype=lwe.dtype, device=lwe.device) if remainder else None
+            self._check(lib().tfhe_extract_digits_batch_device(self._h, _dp(lwe), C.c_size_t(batch), *args, ptrs,
+                                                               _dp(rem) if remainder else None))
+            return (outs, rem) if remainder else outs
+        outs = [np.zeros(shape, dtype=np.uint32) for _ in range(digits)]
+        for t, x in enumerate(outs):
+            ptrs[t] = _hp(x)
+        rem = np.zeros(shape, dtype=np.uint32) if remainder else None
+        self._check(lib().tfhe_extract_digits_batch(self._h, _hp(lwe), C.c_size_t(batch), *args, ptrs,
+                                                    _hp(rem) if remainder else None))
+        return (outs, rem) if remainder else outs
+
+    def wide_lut(self, lwe_in, lsb: int, digits: int, table, out=None):
+        """T[v] of the digits * log_p low bits v of an encrypted value (phase v 2^lsb + e): extract_digits with
+        digit_bits = log_p at the context's scale, then tree_lut on the digits, in one call.  table as in tree_lut:
+        [1 or batch][tables][B^digits] (or [tables][B^digits] / [B^digits]: shared) -> LWE [batch][tables][io_dim+1].
+        numpy (host form) or torch device tensors (reserve_wide_lut first)."""
+        p = self.params
+        lwe, batch, dev = self._extract_input("wide_lut", lwe_in)
+        d = int(digits)
+        if d < 1 or d * p.log_p > 16 or not 0 <= int(lsb) <= 32:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"wide_lut: 1 <= digits, digits * log_p <= 16 and lsb in [0, 32] expected")
+        if _is_torch(table) != dev:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "wide_lut: lwe_in and table must both be numpy or both torch")
+        if not dev:
+            table = _np(table)
+        while len(table.shape) < 3:
+            table = table.unsqueeze(0) if dev else table[None]
+        sets, tables = int(table.shape[0]), int(table.shape[1])
+        if len(table.shape) != 3 or sets not in (1, batch) or int(table.shape[2]) != 1 << (p.log_p * d) or \
+                (dev and (not table.is_cuda or not table.is_contiguous() or table.element_size() != 4 or table.is_floating_point())):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT,
+                            f"wide_lut: table [1 or {batch}][tables][{1 << (p.log_p * d)}] of 32-bit integers expected, got {tuple(table.shape)}")
+        shape = (batch, tables, self.io_dim + 1)
+        if dev:
+            self._bind_torch()
+            out = self._lookup_out("wide_lut", out, shape, lwe)
+            self._check(lib().tfhe_wide_lut_batch_device(self._h, _dp(lwe), C.c_size_t(batch), C.c_uint(int(lsb)), C.c_size_t(d),
+                                                         _dp(table), C.c_size_t(sets), C.c_size_t(tables), _dp(out)))
+            return out
+        res = np.zeros(shape, dtype=np.uint32)
+        self._check(lib().tfhe_wide_lut_batch(self._h, _hp(lwe), C.c_size_t(batch), C.c_uint(int(lsb)), C.c_size_t(d), _hp(table),
+                                              C.c_size_t(sets), C.c_size_t(tables), _hp(res)))
+        return res
+
     def sample_extract(self, glwe, sample_index: int = 0) -> np.ndarray:
         p = self.params
         g = _np(glwe).reshape(-1, p.k + 1, p.N)

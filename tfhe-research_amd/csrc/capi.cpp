@@ -668,7 +668,8 @@ void tfhe_context_destroy(tfhe_context* ctx) {
                   ctx->d_lwe_big, ctx->d_lwe_out, ctx->d_lwe_ks, ctx->d_glwe_a, ctx->d_glwe_b, ctx->d_glwe_c,
                   ctx->d_tv,     ctx->d_misc,   ctx->d_ggsw_tmp, ctx->d_ggsw_raw,
                   ctx->d_key_tmp, ctx->d_pksk, ctx->d_pack_cols, ctx->d_lookup_ws, ctx->d_tree_ws,
-                  ctx->d_demux_ws, ctx->d_program_ws, ctx->d_dense_ws, ctx->d_ksk_matrix, ctx->d_conv_ws};
+                  ctx->d_demux_ws, ctx->d_program_ws, ctx->d_dense_ws, ctx->d_ksk_matrix, ctx->d_conv_ws,
+                  ctx->d_extract_ws};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& g : ctx->gate_tvs)
@@ -2730,6 +2731,242 @@ int tfhe_tree_lut_batch(tfhe_context* ctx, const uint32_t* const* digits, size_t
   TFHE_TRY(s.upload(d, table));
   TFHE_TRY(tfhe_tree_lut_batch_device(ctx, ptrs.data(), d, batch, s[d], table_sets, tables, s[d + 1]));
   return s.download_and_wait(d + 1, lwe_out);
+}
+
+// ---------------------------------------------------------------------------------- digit extraction, wide LUT
+// tfhe_hip.h states the operation, lwe_extract.h::extract_step the launch between two bootstraps.  The only host loop
+// is the one over the w bits: one bootstrap call and one step launch each.
+namespace {
+
+constexpr unsigned kExtractMaxBits = 16;
+
+struct ExtractShape {
+  size_t batch;
+  unsigned lsb, g, d, out_lsb;
+};
+
+struct ExtractLayout {
+  size_t r = 0, s = 0, o = 0, acc = 0, digits = 0, digit_stride = 0;  // offsets in words
+  size_t words = 0;
+};
+
+// every row at the larger boundary dimension, so that switching the bootstrap order keeps a reservation valid
+void extract_layout(const tfhe_context* ctx, size_t batch, size_t digits, ExtractLayout* out) {
+  auto pad = [](size_t w) { return (w + 3) & ~(size_t)3; };  // 16-byte buffers
+  ExtractLayout& L = *out;
+  L.digit_stride = pad(batch * std::max(lwe_words(ctx), big_lwe_words(ctx)));
+  L.r = 0;
+  L.s = L.digit_stride;
+  L.o = 2 * L.digit_stride;
+  L.acc = 3 * L.digit_stride;
+  L.digits = L.acc + pad(glwe_words(ctx));
+  L.words = L.digits + digits * L.digit_stride;
+}
+
+size_t extract_bytes(const tfhe_context* ctx, size_t batch, size_t digits) {
+  ExtractLayout L;
+  extract_layout(ctx, batch, digits, &L);
+  return L.words * sizeof(u32);
+}
+
+int check_extract_shape(tfhe_context* ctx, const ExtractShape& e) {
+  if (e.batch == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "empty batch");
+  if (e.batch > kMaxBatch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "batch exceeds 2^31 - 1 (one workgroup per sample)");
+  if (e.g == 0 || e.d == 0 || e.g > kExtractMaxBits || e.d > kExtractMaxBits || e.g * e.d > kExtractMaxBits)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "digit_bits and digits must be at least 1 and w = digit_bits * digits at most " + std::to_string(kExtractMaxBits));
+  if (e.lsb == 0 || e.out_lsb == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "lsb and out_lsb must be at least 1 (bit m - 1 holds the constant)");
+  if (e.lsb > 32 || e.lsb + e.g * e.d > 32)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "lsb + w <= 32 is required: lsb = " + std::to_string(e.lsb) + ", w = " + std::to_string(e.g * e.d));
+  if (e.out_lsb > 32 || e.out_lsb + e.g > 32)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "out_lsb + digit_bits <= 32 is required: out_lsb = " + std::to_string(e.out_lsb) + ", digit_bits = " + std::to_string(e.g));
+  return TFHE_OK;
+}
+
+int reserve_extract(tfhe_context* ctx, size_t batch, size_t digits) {
+  TFHE_TRY(reserve(ctx, batch));
+  if (batch <= ctx->extract_batch && digits <= ctx->extract_digits) return TFHE_OK;
+  const size_t new_batch = std::max(batch, ctx->extract_batch), new_digits = std::max(digits, ctx->extract_digits);
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->extract_batch = ctx->extract_digits = 0;
+  TFHE_TRY(ensure(ctx, &ctx->d_extract_ws, &ctx->extract_ws_words, extract_bytes(ctx, new_batch, new_digits) / sizeof(u32)));
+  ctx->extract_batch = new_batch;
+  ctx->extract_digits = new_digits;
+  return TFHE_OK;
+}
+
+// the call fits what is reserved, with `ws_digits` digit buffers of the workspace in use (0: the caller's own)
+int check_extract_reserved(tfhe_context* ctx, size_t batch, size_t ws_digits) {
+  if (batch <= ctx->extract_batch && ws_digits <= ctx->extract_digits && batch <= ctx->ws_batch) return TFHE_OK;
+  return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+              "the call needs " + std::to_string(extract_bytes(ctx, batch, ws_digits)) +
+                  " bytes of extraction workspace (batch " + std::to_string(batch) + ", " + std::to_string(ws_digits) +
+                  " digit buffers), " +
+                  std::to_string(ctx->extract_batch && batch <= ctx->ws_batch ? ctx->extract_ws_words * sizeof(u32) : 0) +
+                  " are reserved (tfhe_context_reserve_extract)");
+}
+
+// the w sign bootstraps and the w + 1 step launches; everything has been checked
+int enqueue_extract(tfhe_context* ctx, const u32* lwe_in, const ExtractShape& e, u32* const* digits_out, u32* remainder_out) {
+  ExtractLayout L;
+  extract_layout(ctx, ctx->extract_batch, ctx->extract_digits, &L);
+  u32 *r = ctx->d_extract_ws + L.r, *s = ctx->d_extract_ws + L.s, *o = ctx->d_extract_ws + L.o, *acc = ctx->d_extract_ws + L.acc;
+  const u32 w = e.g * e.d;
+  auto m_of = [&](u32 j) { return std::min(e.lsb + j, e.out_lsb + j % e.g); };
+  ExtractStepArgs a{};
+  a.total = e.batch * io_words(ctx);
+  a.words = (u32)io_words(ctx);
+  a.acc_words = (u32)glwe_words(ctx);
+  a.acc_body = ctx->big_n;
+  // r_0 = lwe_in, s_0, the constant of bit 0
+  a.r_in = lwe_in;
+  a.r_out = r;
+  a.s_out = s;
+  a.acc = acc;
+  a.s_shift = 31u - e.lsb;
+  a.acc_kappa = 1u << (m_of(0) - 1);
+  HIP_TRY(ctx, launch::extract_step(ctx->stream, a));
+  for (u32 j = 0; j < w; ++j) {
+    TFHE_TRY(enqueue_bootstrap(ctx, s, e.batch, acc, 1, ctx->d_lwe_big, o, AccSource{true, ctx->N / 2}));
+    const u32 i = j % e.g, m = m_of(j);
+    const bool last = j + 1 == w;
+    a.r_in = r;
+    a.o = o;
+    a.r_out = last ? remainder_out : r;
+    a.s_out = last ? nullptr : s;
+    a.digit = digits_out[j / e.g];
+    a.acc = last ? nullptr : acc;
+    a.kappa = 1u << (m - 1);
+    a.r_shift = e.lsb + j - m;
+    a.d_shift = e.out_lsb + i - m;
+    a.s_shift = last ? 0u : 31u - e.lsb - (j + 1);
+    a.d_keep = i ? 0xFFFFFFFFu : 0u;
+    a.acc_kappa = last ? 0u : 1u << (m_of(j + 1) - 1);
+    HIP_TRY(ctx, launch::extract_step(ctx->stream, a));
+  }
+  return TFHE_OK;
+}
+
+// everything an extraction is refused for before its workspace is looked at
+int check_extract_args(tfhe_context* ctx, const void* lwe_in, const ExtractShape& e, uint32_t* const* digits_out, const void* remainder_out,
+                       bool device) {
+  TFHE_TRY(check_present(ctx, {lwe_in, digits_out}, 1, "null pointer"));
+  TFHE_TRY(check_extract_shape(ctx, e));
+  const size_t words = e.batch * io_words(ctx);
+  for (unsigned t = 0; t < e.d; ++t) {
+    if (!digits_out[t]) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null digit pointer");
+    for (unsigned u = 0; u < t; ++u)
+      if (overlap(digits_out[t], words, digits_out[u], words)) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "two digit buffers overlap");
+    if (remainder_out && overlap(digits_out[t], words, remainder_out, words))
+      return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "a digit buffer overlaps remainder_out");
+    if (device && overlap(digits_out[t], words, lwe_in, words))
+      return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "a digit buffer overlaps lwe_in");
+  }
+  // the bootstraps' own refusals: a key, and a plain one (the rotations start from a GLWE accumulator)
+  const size_t offset = ctx->N / 2;
+  return check_rotate_args(ctx, lwe_in, lwe_in, lwe_in, e.batch, 1, &offset);
+}
+
+// the wide LUT's fixed arguments of the extraction
+ExtractShape wide_lut_shape(const tfhe_context* ctx, size_t batch, unsigned lsb, size_t d) {
+  const u32 log_p = ctx->params.log_p, used = log_p + ctx->params.padding_bits;
+  return ExtractShape{batch, lsb, log_p, (unsigned)std::min<size_t>(d, kExtractMaxBits + 1), used < 32 ? 32 - used : 0};
+}
+
+int check_wide_lut_args(tfhe_context* ctx, const void* lwe_in, size_t batch, unsigned lsb, size_t d, const void* table,
+                        size_t table_sets, size_t tables, const void* lwe_out, TreeLutLayout* L) {
+  TFHE_TRY(check_present(ctx, {lwe_in, table, lwe_out}, 1, "null pointer"));
+  TFHE_TRY(check_tree_lut_shape(ctx, batch, d, tables, L));
+  TFHE_TRY(check_extract_shape(ctx, wide_lut_shape(ctx, batch, lsb, d)));
+  if (table_sets != 1 && table_sets != batch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "table_sets must be 1 or batch");
+  return check_tree_lut_keys(ctx);
+}
+
+}  // namespace
+
+int tfhe_context_reserve_extract(tfhe_context* ctx, size_t max_batch, size_t max_digits) {
+  TFHE_TRY(check_ctx(ctx));
+  if (max_batch == 0 || max_batch > kMaxBatch || max_digits == 0 || max_digits > kExtractMaxBits)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "max_batch must be in [1, 2^31 - 1] and max_digits in [1, " + std::to_string(kExtractMaxBits) + "]");
+  return reserve_extract(ctx, max_batch, max_digits);
+}
+
+int tfhe_context_reserve_wide_lut(tfhe_context* ctx, size_t max_batch, size_t max_digits, size_t max_tables) {
+  TFHE_TRY(check_ctx(ctx));
+  TreeLutLayout L;
+  TFHE_TRY(check_tree_lut_shape(ctx, max_batch, max_digits, max_tables, &L));
+  TFHE_TRY(reserve_extract(ctx, max_batch, max_digits));
+  return tfhe_context_reserve_tree_lut(ctx, max_batch, max_digits, max_tables);
+}
+
+int tfhe_extract_digits_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, unsigned lsb, unsigned digit_bits,
+                                     unsigned digits, unsigned out_lsb, uint32_t* const* digits_out, uint32_t* remainder_out) {
+  TFHE_TRY(check_ctx(ctx));
+  const ExtractShape e{batch, lsb, digit_bits, digits, out_lsb};
+  TFHE_TRY(check_extract_args(ctx, lwe_in, e, digits_out, remainder_out, true));
+  TFHE_TRY(check_extract_reserved(ctx, batch, 0));
+  return enqueue_extract(ctx, lwe_in, e, digits_out, remainder_out);
+}
+
+int tfhe_extract_digits_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, unsigned lsb, unsigned digit_bits,
+                              unsigned digits, unsigned out_lsb, uint32_t* const* digits_out, uint32_t* remainder_out) {
+  TFHE_TRY(check_ctx(ctx));
+  const ExtractShape e{batch, lsb, digit_bits, digits, out_lsb};
+  TFHE_TRY(check_extract_args(ctx, lwe_in, e, digits_out, remainder_out, false));
+  TFHE_TRY(reserve_extract(ctx, batch, digits));
+  const size_t words = batch * io_words(ctx);
+  // rows have an odd number of words: a gap keeps the remainder at the input's offset from a 16-byte boundary, so that
+  // the last step launch moves 16 bytes per access like the others
+  enum { kIn, kGap, kRemainder };
+  Staging s(ctx, {words, (4 - words % 4) % 4, remainder_out ? words : 0});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(kIn, lwe_in));
+  ExtractLayout L;
+  extract_layout(ctx, ctx->extract_batch, ctx->extract_digits, &L);
+  std::vector<u32*> ptrs(digits);
+  for (unsigned t = 0; t < digits; ++t) ptrs[t] = ctx->d_extract_ws + L.digits + t * L.digit_stride;
+  TFHE_TRY(enqueue_extract(ctx, s[kIn], e, ptrs.data(), remainder_out ? s[kRemainder] : nullptr));
+  for (unsigned t = 0; t < digits; ++t) TFHE_TRY(download(ctx, digits_out[t], ptrs[t], words));
+  if (remainder_out) TFHE_TRY(download(ctx, remainder_out, s[kRemainder], words));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return TFHE_OK;
+}
+
+int tfhe_wide_lut_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, unsigned lsb, size_t d, const uint32_t* table,
+                               size_t table_sets, size_t tables, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TreeLutLayout TL;
+  TFHE_TRY(check_wide_lut_args(ctx, lwe_in, batch, lsb, d, table, table_sets, tables, lwe_out, &TL));
+  TFHE_TRY(check_extract_reserved(ctx, batch, d));
+  if (TL.words > ctx->tree_ws_words)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "the call needs " + std::to_string(TL.words * sizeof(u32)) + " bytes of tree-LUT workspace, " +
+                    std::to_string(ctx->tree_ws_words * sizeof(u32)) + " are reserved (tfhe_context_reserve_wide_lut)");
+  ExtractLayout L;
+  extract_layout(ctx, ctx->extract_batch, ctx->extract_digits, &L);
+  std::vector<u32*> ptrs(d);
+  for (size_t t = 0; t < d; ++t) ptrs[t] = ctx->d_extract_ws + L.digits + t * L.digit_stride;
+  TFHE_TRY(enqueue_extract(ctx, lwe_in, wide_lut_shape(ctx, batch, lsb, d), ptrs.data(), nullptr));
+  return tfhe_tree_lut_batch_device(ctx, ptrs.data(), d, batch, table, table_sets, tables, lwe_out);
+}
+
+int tfhe_wide_lut_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, unsigned lsb, size_t d, const uint32_t* table,
+                        size_t table_sets, size_t tables, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TreeLutLayout TL;
+  TFHE_TRY(check_wide_lut_args(ctx, lwe_in, batch, lsb, d, table, table_sets, tables, lwe_out, &TL));
+  TFHE_TRY(tfhe_context_reserve_wide_lut(ctx, batch, d, tables));
+  const size_t io = io_words(ctx);
+  enum { kIn, kTable, kOut };
+  Staging s(ctx, {batch * io, table_sets * tables << (ctx->params.log_p * d), batch * tables * io});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(kIn, lwe_in));
+  TFHE_TRY(s.upload(kTable, table));
+  TFHE_TRY(tfhe_wide_lut_batch_device(ctx, s[kIn], batch, lsb, d, s[kTable], table_sets, tables, s[kOut]));
+  return s.download_and_wait(kOut, lwe_out);
 }
 
 // ---------------------------------------------------------------------------------- on-disk format

@@ -80,6 +80,12 @@ struct tfhe_context {
   // tree LUT (tfhe_context_reserve_tree_lut): per-rotation inputs, segment state, the levels' results and packed GLWEs
   u32* d_tree_ws = nullptr;
   size_t tree_ws_words = 0;
+  // digit extraction (tfhe_context_reserve_extract): the remainder r, the scaled input s and the result o of the bit's
+  // bootstrap, each [extract_batch][max(n, k N) + 1], the shared constant accumulator [k+1][N], then extract_digits digit
+  // buffers of the same rows (the host forms' and the wide LUT's digits)
+  u32* d_extract_ws = nullptr;
+  size_t extract_ws_words = 0;
+  size_t extract_batch = 0, extract_digits = 0;
   bool aligned = false;       // decomposer alignment (tfhe_context_set_decomposer_alignment)
   bool ks_first = false;      // bootstrap order (tfhe_context_set_bootstrap_order)
   int shape = 0;              // kernel shape of the blind rotation (tfhe_context_set_kernel_shape): launch::kShape*

@@ -12,6 +12,7 @@
 #include "glwe_conv.h"
 #include "launch.h"
 #include "lwe_dense.h"
+#include "lwe_extract.h"
 #include "passes.h"
 
 namespace tfhe {
@@ -1101,6 +1102,14 @@ __global__ void __launch_bounds__(256) dense_tile_rows_kernel(const u32* __restr
     for (u32 i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
   }
 }
+
+// ------------------------------------------------------------------------------ digit extraction
+// lwe_extract.h::extract_step states the step; this is its thread context on the device.
+struct ExtractThread {
+  __device__ size_t index() const { return (size_t)blockIdx.x * blockDim.x + threadIdx.x; }
+  __device__ size_t threads() const { return (size_t)gridDim.x * blockDim.x; }
+};
+__global__ void __launch_bounds__(kExtractThreads) extract_step_kernel(ExtractStepArgs a) { extract_step(ExtractThread(), a); }
 
 // ------------------------------------------------------------------------------ encrypted convolution
 // glwe_conv.h states the operation and its exactness bound.  Two kernels:
@@ -2222,6 +2231,13 @@ hipError_t lwe_dense(hipStream_t s, const u32* x, size_t queries, u32 inputs, co
 hipError_t dense_tile_rows(hipStream_t s, const u32* in, size_t period, size_t count, u32 words, u32* out) {
   const unsigned grid = (unsigned)(count < ((size_t)1 << 20) ? count : (size_t)1 << 20);
   hipLaunchKernelGGL(dense_tile_rows_kernel, dim3(grid), dim3(256), 0, s, in, period, count, words, out);
+  return hipGetLastError();
+}
+
+hipError_t extract_step(hipStream_t s, const ExtractStepArgs& a) {
+  if (a.total == 0 || a.words == 0 || (a.r_shift | a.d_shift | a.s_shift) > 31u) return hipErrorInvalidValue;
+  // a thread owns four words at a time
+  hipLaunchKernelGGL(extract_step_kernel, dim3(grid_for((a.total + 3) / 4, kExtractThreads)), dim3(kExtractThreads), 0, s, a);
   return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 
 #include "glwe_conv.h"
 #include "ks_matrix.h"
+#include "lwe_extract.h"
 #include "pbs_wave.h"
 
 namespace tfhe {
@@ -152,6 +153,10 @@ hipError_t lwe_dense(hipStream_t s, const u32* x, size_t queries, u32 inputs, co
                      u32 words, u32 forced_splits, u32* out);
 // out [count][words], out[r] = in[r % period]: the per-neuron test vectors of a fused layer, one per bootstrap
 hipError_t dense_tile_rows(hipStream_t s, const u32* in, size_t period, size_t count, u32 words, u32* out);
+
+// ---- digit extraction (lwe_extract.h::extract_step): the one elementwise launch between two sign bootstraps.
+// hipErrorInvalidValue: an empty call or a shift above 31
+hipError_t extract_step(hipStream_t s, const ExtractStepArgs& a);
 
 // ---- encrypted convolution (glwe_conv.h::glwe_conv_team; the plan: kernels.hip::glwe_conv_plan)
 struct GlweConvPlanInfo {
