@@ -823,6 +823,36 @@ inline std::vector<LweCiphertext> sample_extract_indices(Engine& e, const GlweCi
     out.push_back(LweCiphertext{std::vector<uint32_t>(res.begin() + i * words, res.begin() + (i + 1) * words)});
   return out;
 }
+// ---- multi-value bootstrapping (tfhe_hip.h states the operations; first device only) ----
+// every lookup table of `luts` (tables x B un-encoded values, row-major) of ONE ciphertext of n + 1 words from one blind
+// rotation (the reference's bootstrap order, like the neighbouring wrappers) -> one ciphertext per table
+inline std::vector<LweCiphertext> multi_value_bootstrap(Engine& e, const LweCiphertext& ct, const std::vector<uint32_t>& luts) {
+  const TfheParams& p = e.params();
+  const size_t words = ct.data.size(), big_b = (size_t)1 << p.log_p;
+  if (words != size_t(p.lwe_dimension) + 1) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "LWE length");
+  if (luts.empty() || luts.size() % big_b != 0) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "tables of B = 2^log_p values");
+  const size_t tables = luts.size() / big_b;
+  std::vector<uint32_t> res(tables * words);
+  e.check(tfhe_multi_value_bootstrap_batch(e.raw(), ct.data.data(), 1, luts.data(), 1, tables, res.data()));
+  std::vector<LweCiphertext> out;
+  for (size_t t = 0; t < tables; ++t)
+    out.push_back(LweCiphertext{std::vector<uint32_t>(res.begin() + t * words, res.begin() + (t + 1) * words)});
+  return out;
+}
+// the LWE ciphertexts (k N + 1 words) of coefficient 0 of (sum_m coeffs[t][m] X^positions[m]) * glwe, one per row t of
+// coeffs (tables x positions.size(), row-major); positions distinct and below N
+inline std::vector<LweCiphertext> glwe_sparse_extract(Engine& e, const GlweCiphertext& glwe, const std::vector<uint32_t>& positions,
+                                                      const std::vector<int32_t>& coeffs) {
+  const size_t words = e.params().lwe_dimension_post_pbs() + 1, terms = positions.size();
+  if (terms == 0 || coeffs.empty() || coeffs.size() % terms != 0) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "rows of one coefficient per position");
+  const size_t tables = coeffs.size() / terms;
+  std::vector<uint32_t> res(tables * words);
+  e.check(tfhe_glwe_sparse_extract_batch(e.raw(), glwe.data.data(), 1, positions.data(), terms, coeffs.data(), 1, tables, res.data()));
+  std::vector<LweCiphertext> out;
+  for (size_t t = 0; t < tables; ++t)
+    out.push_back(LweCiphertext{std::vector<uint32_t>(res.begin() + t * words, res.begin() + (t + 1) * words)});
+  return out;
+}
 // bootstrapping_key_gen bootstrapping.rs:23-56; the generated key is also installed in the engine.
 // bmmp = true makes the key of the unrolled blind rotation instead (notes/BMMP Bootstrapping.md:22-24:
 // GGSW(s s'), GGSW(s (1-s')), GGSW(s' (1-s)) per pair of key bits; N = 512, even n).

@@ -672,6 +672,79 @@ int tfhe_wide_lut_batch(tfhe_context *ctx, const uint32_t *lwe_in, size_t batch,
 int tfhe_wide_lut_batch_device(tfhe_context *ctx, const uint32_t *lwe_in, size_t batch, unsigned lsb, size_t d,
                                const uint32_t *table, size_t table_sets, size_t tables, uint32_t *lwe_out);
 
+/* ---- multi-value bootstrapping: several tables from one blind rotation (no reference counterpart) --------------------
+ * Several functions of ONE ciphertext cost one rotation, not one each (Carpov, Izabachene, Mollimard 2019): rotate a
+ * table-independent accumulator, then multiply it by a small clear polynomial per table.  Nothing is packed into spare
+ * bits of the input; the modulus switch and the rotation are the bootstrap's own.  The price is output noise, below.
+ *
+ * Let B = 2^log_p, rep = N / B >= 2 (log_p < log2 N), kappa = 2^(31 - log_p - padding_bits) (log_p + padding_bits <= 31).
+ * For a lookup table T[0 .. B) let h = (T[0] != 0 ? B - T[0] : 0), the value construct_test_from_lut writes in the place
+ * of T[0] on the half block that wraps to the top of the test vector (test_vector.rs:38-67).  With terms = B + 1:
+ *   m = 0          position p_0 = 0                       D[0] = T[0] + h
+ *   m = 1 .. B-1   position p_m = rep/2 + (m-1) rep       D[m] = T[m] - T[m-1]
+ *   m = B          position p_B = N - rep/2               D[B] = h - T[B-1]
+ * in int32 (two's complement wraps exactly mod 2^32).  sum_m D[m] X^(p_m) = (1 - X) tv(X) in Z[X]/(X^N + 1) with
+ * tv = construct_test_from_lut(T), and (1 + X + .. + X^(N-1)) (1 - X) = 2, so kappa (1 + .. + X^(N-1)) (1 - X) tv =
+ * tv << (32 - log_p - padding_bits), word for word mod 2^32.
+ *
+ * tfhe_multi_value_bootstrap_batch(lwe_in [batch][io_words], luts [lut_sets][tables][B] un-encoded values below B,
+ * lut_sets 1 or batch) -> lwe_out [batch][tables][io_words]:
+ *   1. A_q = tfhe_blind_rotate_glwe_batch(lwe_in[q]; acc_in = (0, .., 0, kappa (1 + X + .. + X^(N-1))), acc_count = 1,
+ *      rotation_offset = 0); with the key switch first, lwe_in is key-switched before, as in a bootstrap.
+ *   2. out[q][t] = D_t[0] SE_0(A_q) - sum_{m >= 1} D_t[m] SE_(N - p_m)(A_q), SE_j the words of
+ *      tfhe_sample_extract_batch at index j, wrapping u32 on the k N + 1 words (coefficient 0 of X^p A is -A[N - p] for
+ *      0 < p < N).  This is tfhe_glwe_sparse_extract_batch with positions p and coefficients D.
+ *   3. In the reference's order every out[q][t] is key-switched, AFTER the combination: the key switch's noise is not
+ *      amplified.
+ * The words equal that composition of public entry points byte for byte.  Under noise-free keys that ignore no bits the
+ * phase of lwe_out[q][t] is exactly the phase tfhe_bootstrap_batch gives with construct_test_from_lut(T_t), the
+ * padding-bit case included.
+ *
+ * tfhe_glwe_sparse_extract_batch(glwe [batch][k+1][N], positions [terms] in HOST memory in both forms, distinct, each
+ * below N; coeffs int32 [sets][tables][terms], sets 1 or batch) -> lwe_out [batch][tables][k N + 1] is step 2 for any
+ * sparse clear polynomials sum_m c[m] X^(p_m): out[q][t] = sum_m c[set][t][m] (p_m = 0 ? SE_0(A_q) : -SE_(N - p_m)(A_q)),
+ * the LWE ciphertext of coefficient 0 of the product.  No transform, no exactness rule: the same words in every backend.
+ *
+ * Plan (csrc/multi_value.h): one workgroup per (input, run of tables) stages A_q in LDS once and writes whole rows; with
+ * few inputs the tables are dealt over the grid.  The lookup tables become coefficient rows in one small launch.
+ *
+ * tfhe_context_set_tree_lut_level0(ctx, 1): level 0 of tfhe_tree_lut_batch[_device] (and of tfhe_wide_lut_batch) becomes
+ * ONE rotation per row and one step-2 launch over the tables * B^(d-1) sub-tables, whose table layout
+ * [table_sets][tables * B^(d-1)][B] is already luts'; the results keep the order (row, table, h) the packing of level 1
+ * expects.  Levels >= 1, the packing and the final key switch do not change; the call fits the workspace
+ * tfhe_context_reserve_tree_lut reserves.  Rotations per (row, table): 5 -> 2 at d = 2, 21 -> 6 at d = 3, 85 -> 22 at
+ * d = 4 (B = 4).  0 (the default): today's words, today's launches.  The setter allocates the constant accumulator.
+ *
+ * Refused: TFHE_ERR_INVALID_ARGUMENT for a NULL pointer, an empty batch, no table, sets / lut_sets not 1 or batch,
+ * batch * tables >= 2^31, a position >= N or repeated, terms outside [1, N], log_p + padding_bits > 31, log_p >= log2 N;
+ * TFHE_ERR_NO_KEY without a bootstrapping key; TFHE_ERR_UNSUPPORTED with a BMMP key (the shared rotation starts from a
+ * GLWE accumulator).
+ *
+ * Workspace: tfhe_context_reserve_multi_value(max_batch, max_tables) reserves the key-switched inputs
+ * [max_batch][n + 1], the rotated accumulators [max_batch][k+1][N], the coefficients [max_batch][max_tables][B + 1] and
+ * the combinations [max_batch][max_tables][k N + 1] (either bootstrap order fits), and the constants.  After it the
+ * _device forms allocate nothing, stay on the context's stream and can be captured (a caller's positions travel as
+ * kernel arguments).  A call beyond the reservation returns TFHE_ERR_INVALID_ARGUMENT with the need in bytes.  The host
+ * forms reserve for themselves and block.
+ *
+ * Noise, in units of the 32-bit torus.  The rotated accumulator carries s_br^2, the tree LUT's formula above; it does
+ * not depend on the table.  out_t carries ||D_t||_2^2 s_br^2, plus s_ks^2 in the reference's order (un-amplified: the
+ * key switch comes last), with ||D_t||_2^2 <= B^2 + B (B - 1)^2.  With ignored decomposer bits the rounding term scales
+ * with ||D_t||_1.  A tree with the switch on carries ||D||_2^2 s_br^2 + (d - 1) s_br^2 + (d - 1) s_pk^2 (+ s_ks^2),
+ * ||D||_2^2 the largest over its sub-tables.  A result decodes while 8 sigma stays below half a step,
+ * 2^(31 - log_p - padding_bits). */
+int tfhe_context_reserve_multi_value(tfhe_context *ctx, size_t max_batch, size_t max_tables);
+int tfhe_context_set_tree_lut_level0(tfhe_context *ctx, int multi_value);
+int tfhe_glwe_sparse_extract_batch(tfhe_context *ctx, const uint32_t *glwe, size_t batch, const uint32_t *positions,
+                                   size_t terms, const int32_t *coeffs, size_t sets, size_t tables, uint32_t *lwe_out);
+int tfhe_glwe_sparse_extract_batch_device(tfhe_context *ctx, const uint32_t *glwe, size_t batch, const uint32_t *positions,
+                                          size_t terms, const int32_t *coeffs, size_t sets, size_t tables,
+                                          uint32_t *lwe_out);
+int tfhe_multi_value_bootstrap_batch(tfhe_context *ctx, const uint32_t *lwe_in, size_t batch, const uint32_t *luts,
+                                     size_t lut_sets, size_t tables, uint32_t *lwe_out);
+int tfhe_multi_value_bootstrap_batch_device(tfhe_context *ctx, const uint32_t *lwe_in, size_t batch, const uint32_t *luts,
+                                            size_t lut_sets, size_t tables, uint32_t *lwe_out);
+
 /* ---- encrypted convolutions (no reference counterpart) --------------------------------------------
  * A matrix of clear polynomials with small integer coefficients times a batch of GLWE ciphertexts: the general leveled
  * operation on packed ciphertexts that needs no GGSW (tfhe_glwe_mul_monomial_batch is the case of one weight +-X^r).

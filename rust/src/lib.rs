@@ -86,6 +86,11 @@ extern "C" {
                                  digits: c_uint, out_lsb: c_uint, digits_out: *const *mut u32, remainder_out: *mut u32) -> c_int;
     fn tfhe_wide_lut_batch(ctx: *mut TfheContext, lwe_in: *const u32, batch: usize, lsb: c_uint, d: usize, table: *const u32,
                            table_sets: usize, tables: usize, lwe_out: *mut u32) -> c_int;
+    // multi-value bootstrapping (include/tfhe_hip.h)
+    fn tfhe_multi_value_bootstrap_batch(ctx: *mut TfheContext, lwe_in: *const u32, batch: usize, luts: *const u32, lut_sets: usize,
+                                        tables: usize, lwe_out: *mut u32) -> c_int;
+    fn tfhe_glwe_sparse_extract_batch(ctx: *mut TfheContext, glwe: *const u32, batch: usize, positions: *const u32, terms: usize,
+                                      coeffs: *const i32, sets: usize, tables: usize, lwe_out: *mut u32) -> c_int;
     // encrypted dense layers (include/tfhe_hip.h)
     fn tfhe_lwe_dense_batch(ctx: *mut TfheContext, x: *const u32, queries: usize, inputs: usize, weights: *const i32,
                             bias: *const u32, outputs: usize, words_per_ct: usize, out: *mut u32) -> c_int;
@@ -473,6 +478,36 @@ pub fn wide_lut(bk: &GpuBootstrappingKey, lwe: &Array2<u32>, lsb: u32, d: usize,
         tfhe_wide_lut_batch(bk.ctx, lwe.as_slice().unwrap().as_ptr(), batch, lsb as c_uint, d, table.as_slice().unwrap().as_ptr(),
                             1, 1, out.as_slice_mut().unwrap().as_mut_ptr())
     }, "wide_lut");
+    out
+}
+
+/// Multi-value bootstrap: every table of `luts` (tables, B) of un-encoded values of every row of `lwe` (batch, n+1), from ONE
+/// blind rotation per row -> (batch, tables, n+1) (no reference counterpart).  The reference's bootstrap order only, as above.
+pub fn multi_value_bootstrap(bk: &GpuBootstrappingKey, lwe: &Array2<u32>, luts: &Array2<u32>) -> Array3<u32> {
+    let (batch, width) = lwe.dim();
+    let (tables, values) = luts.dim();
+    assert!(width == bk.params.lwe_dimension as usize + 1 && batch >= 1, "multi_value_bootstrap: ciphertexts of n+1 words");
+    assert!(tables >= 1 && values == 1usize << bk.params.log_p, "multi_value_bootstrap: tables of B = 2^log_p values");
+    let mut out = Array3::<u32>::zeros((batch, tables, width));
+    check(bk.ctx, unsafe {
+        tfhe_multi_value_bootstrap_batch(bk.ctx, lwe.as_slice().unwrap().as_ptr(), batch, luts.as_slice().unwrap().as_ptr(), 1, tables,
+                                         out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "multi_value_bootstrap");
+    out
+}
+
+/// The LWE ciphertexts of coefficient 0 of (sum_m coeffs[t][m] X^positions[m]) * glwe[q]: `glwe` (batch, k+1, N), `positions`
+/// distinct and below N, `coeffs` (tables, terms) -> (batch, tables, k N + 1), wrapping (no reference counterpart).
+pub fn glwe_sparse_extract(bk: &GpuBootstrappingKey, glwe: &Array3<u32>, positions: &Array1<u32>, coeffs: &Array2<i32>) -> Array3<u32> {
+    let (batch, polys, n) = glwe.dim();
+    let (tables, terms) = coeffs.dim();
+    assert!(polys == bk.params.glwe_dimension as usize + 1 && n == 1usize << bk.params.glwe_poly_degree, "glwe_sparse_extract: glwe (batch, k+1, N)");
+    assert!(terms == positions.len() && terms >= 1 && tables >= 1, "glwe_sparse_extract: one coefficient per position");
+    let mut out = Array3::<u32>::zeros((batch, tables, (polys - 1) * n + 1));
+    check(bk.ctx, unsafe {
+        tfhe_glwe_sparse_extract_batch(bk.ctx, glwe.as_slice().unwrap().as_ptr(), batch, positions.as_slice().unwrap().as_ptr(), terms,
+                                       coeffs.as_slice().unwrap().as_ptr(), 1, tables, out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "glwe_sparse_extract");
     out
 }
 

@@ -224,6 +224,29 @@ def construct_test_from_lut(params: TfheParams, lut) -> np.ndarray:
     return out
 
 
+def multi_value_coefficients(params: TfheParams, luts):
+    """(positions [B + 1], D int32 [..][B + 1]): the non-zero coefficients of (1 - X) construct_test_from_lut(T) for every
+    lookup table T [..][B] of un-encoded values (include/tfhe_hip.h, "multi-value bootstrapping"; host side)."""
+    luts = np.asarray(luts, dtype=np.uint32)
+    big_b, n = 1 << params.log_p, params.N
+    if luts.shape[-1] != big_b or params.log_p >= params.glwe_poly_degree:
+        raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"multi_value_coefficients: tables of {big_b} values and log_p < log2 N expected")
+    rep = n // big_b
+    positions = np.concatenate([[0], rep // 2 + rep * np.arange(big_b - 1), [n - rep // 2]]).astype(np.uint32)
+    h = np.where(luts[..., :1] != 0, np.uint32(big_b) - luts[..., :1], np.uint32(0)).astype(np.uint32)
+    d = np.concatenate([luts[..., :1] + h, luts[..., 1:] - luts[..., :-1], h - luts[..., -1:]], axis=-1).astype(np.uint32)
+    return positions, d.view(np.int32)
+
+
+def multi_value_noise_factor(luts) -> int:
+    """max over the tables of ||D_t||_2^2: what a multi-value bootstrap multiplies the rotation's variance by"""
+    luts = np.asarray(luts, dtype=np.int64)
+    big_b = luts.shape[-1]
+    h = np.where(luts[..., :1] != 0, big_b - luts[..., :1], 0)
+    d = np.concatenate([luts[..., :1] + h, luts[..., 1:] - luts[..., :-1], h - luts[..., -1:]], axis=-1)
+    return int((d * d).sum(axis=-1).max())
+
+
 def construct_identity_test_vector(params: TfheParams) -> np.ndarray:
     """test_vector.rs:23-35"""
     return construct_test_from_lut(params, np.arange(1 << params.log_p, dtype=np.uint32))
@@ -807,6 +830,87 @@ class Context:
         res = np.zeros(shape, dtype=np.uint32)
         self._check(lib().tfhe_wide_lut_batch(self._h, _hp(lwe), C.c_size_t(batch), C.c_uint(int(lsb)), C.c_size_t(d), _hp(table),
                                               C.c_size_t(sets), C.c_size_t(tables), _hp(res)))
+        return res
+
+    # -- multi-value bootstrapping: several tables from one rotation (include/tfhe_hip.h states the operations) --
+    def reserve_multi_value(self, max_batch: int, max_tables: int = 1):
+        """size the workspace of the device forms of multi_value_bootstrap and glwe_sparse_extract (a maximum)"""
+        self._check(lib().tfhe_context_reserve_multi_value(self._h, C.c_size_t(max_batch), C.c_size_t(max_tables)))
+
+    def set_tree_lut_level0(self, multi_value: bool):
+        """True: level 0 of tree_lut / wide_lut is ONE rotation per row and one sparse combination over the sub-tables
+        (more output noise: the header's rule); False (the default): one rotation per (row, table, sub-table)"""
+        self._check(lib().tfhe_context_set_tree_lut_level0(self._h, C.c_int(1 if multi_value else 0)))
+
+    def multi_value_coefficients(self, luts):
+        """(positions, D) of luts [..][B] at this context's parameters: the module-level helper of the same name"""
+        return multi_value_coefficients(self.params, luts)
+
+    def _mv_table(self, what, table, width, batch, dev, dtype_name="32-bit integers"):
+        """-> table [sets][tables][width] after the checks the ABI cannot make on a bare pointer"""
+        while len(table.shape) < 3:
+            table = table.unsqueeze(0) if dev else table[None]
+        if len(table.shape) != 3 or int(table.shape[0]) not in (1, batch) or int(table.shape[2]) != width or int(table.shape[1]) < 1 or \
+                (dev and (not table.is_cuda or not table.is_contiguous() or table.element_size() != 4 or table.is_floating_point())):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT,
+                            f"{what}: [1 or {batch}][tables][{width}] of {dtype_name} expected, got {tuple(table.shape)}")
+        return table
+
+    def multi_value_bootstrap(self, lwe_in, luts, out=None):
+        """Every table of luts [1 or batch][tables][B] (or [tables][B] / [B]: shared; un-encoded values < B = 2^log_p) of
+        every row of lwe_in [batch][io_dim+1], from ONE blind rotation per row -> LWE [batch][tables][io_dim+1].  numpy
+        (host form: reserves for itself, blocks) or torch device tensors (reserve_multi_value first)."""
+        p = self.params
+        lwe, batch, dev = self._extract_input("multi_value_bootstrap", lwe_in)
+        if _is_torch(luts) != dev:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "multi_value_bootstrap: lwe_in and luts must both be numpy or both torch")
+        luts = self._mv_table("multi_value_bootstrap: luts", luts if dev else _np(luts), 1 << p.log_p, batch, dev)
+        sets, tables = int(luts.shape[0]), int(luts.shape[1])
+        shape = (batch, tables, self.io_dim + 1)
+        if dev:
+            self._bind_torch()
+            out = self._lookup_out("multi_value_bootstrap", out, shape, lwe)
+            self._check(lib().tfhe_multi_value_bootstrap_batch_device(self._h, _dp(lwe), C.c_size_t(batch), _dp(luts), C.c_size_t(sets),
+                                                                      C.c_size_t(tables), _dp(out)))
+            return out
+        res = np.zeros(shape, dtype=np.uint32)
+        self._check(lib().tfhe_multi_value_bootstrap_batch(self._h, _hp(lwe), C.c_size_t(batch), _hp(luts), C.c_size_t(sets),
+                                                           C.c_size_t(tables), _hp(res)))
+        return res
+
+    def glwe_sparse_extract(self, glwe, positions, coeffs, out=None):
+        """out[q][t] = the LWE ciphertext of coefficient 0 of (sum_m coeffs[set][t][m] X^positions[m]) * glwe[q]:
+        glwe [batch][k+1][N], positions [terms] (host integers, distinct, < N), coeffs int32 [1 or batch][tables][terms]
+        (or [tables][terms] / [terms]: shared) -> LWE [batch][tables][k N + 1].  numpy (host form) or torch device tensors
+        for glwe and coeffs (reserve_multi_value first)."""
+        p = self.params
+        dev = _is_torch(glwe)
+        if _is_torch(coeffs) != dev:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "glwe_sparse_extract: glwe and coeffs must both be numpy or both torch")
+        pos = np.ascontiguousarray(np.asarray(positions).reshape(-1), dtype=np.uint32)
+        if not dev:
+            glwe = _np(glwe)
+            coeffs = np.ascontiguousarray(coeffs, dtype=np.int32)
+        if len(glwe.shape) == 2:
+            glwe = glwe.unsqueeze(0) if dev else glwe[None]
+        if len(glwe.shape) != 3 or tuple(glwe.shape[1:]) != (p.k + 1, p.N) or int(glwe.shape[0]) < 1 or \
+                (dev and (not glwe.is_cuda or not glwe.is_contiguous() or glwe.element_size() != 4 or glwe.is_floating_point())):
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT,
+                            f"glwe_sparse_extract: glwe [batch][{p.k + 1}][{p.N}] of 32-bit integers expected, got {tuple(glwe.shape)}")
+        batch = int(glwe.shape[0])
+        coeffs = self._mv_table("glwe_sparse_extract: coeffs", coeffs, int(pos.size), batch, dev)
+        sets, tables = int(coeffs.shape[0]), int(coeffs.shape[1])
+        shape = (batch, tables, p.big_n + 1)
+        i32p = C.POINTER(C.c_int32)
+        if dev:
+            self._bind_torch()
+            out = self._lookup_out("glwe_sparse_extract", out, shape, glwe)
+            self._check(lib().tfhe_glwe_sparse_extract_batch_device(self._h, _dp(glwe), C.c_size_t(batch), _hp(pos), C.c_size_t(pos.size),
+                                                                    C.cast(_dp(coeffs), i32p), C.c_size_t(sets), C.c_size_t(tables), _dp(out)))
+            return out
+        res = np.zeros(shape, dtype=np.uint32)
+        self._check(lib().tfhe_glwe_sparse_extract_batch(self._h, _hp(glwe), C.c_size_t(batch), _hp(pos), C.c_size_t(pos.size),
+                                                         coeffs.ctypes.data_as(i32p), C.c_size_t(sets), C.c_size_t(tables), _hp(res)))
         return res
 
     def sample_extract(self, glwe, sample_index: int = 0) -> np.ndarray:

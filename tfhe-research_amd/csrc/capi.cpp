@@ -669,7 +669,7 @@ void tfhe_context_destroy(tfhe_context* ctx) {
                   ctx->d_tv,     ctx->d_misc,   ctx->d_ggsw_tmp, ctx->d_ggsw_raw,
                   ctx->d_key_tmp, ctx->d_pksk, ctx->d_pack_cols, ctx->d_lookup_ws, ctx->d_tree_ws,
                   ctx->d_demux_ws, ctx->d_program_ws, ctx->d_dense_ws, ctx->d_ksk_matrix, ctx->d_conv_ws,
-                  ctx->d_extract_ws};
+                  ctx->d_extract_ws, ctx->d_mv_const, ctx->d_mv_ws};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& g : ctx->gate_tvs)
@@ -2573,6 +2573,222 @@ int tfhe_pack_lwe_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t groups
   return s.download_and_wait(kOut, glwe_out);
 }
 
+// ---------------------------------------------------------------------------------- multi-value bootstrap
+// tfhe_hip.h states the operation, multi_value.h::sparse_extract_tile the per-table step.  ONE rotation of the constant
+// accumulator per input, then one launch that turns the lookup tables into coefficient rows and one that combines the
+// B + 1 sample extractions for every (input, table); in the reference's order the key switch runs over the combinations.
+namespace {
+
+struct MvLayout {
+  size_t ks = 0, acc = 0, coeffs = 0, big = 0;  // offsets in words
+  size_t words = 0;
+};
+
+void mv_layout(const tfhe_context* ctx, size_t batch, size_t tables, MvLayout* L) {
+  auto pad = [](size_t w) { return (w + 3) & ~(size_t)3; };  // 16-byte buffers
+  size_t at = 0;
+  auto take = [&](size_t w) { const size_t o = at; at += pad(w); return o; };
+  L->ks = take(batch * lwe_words(ctx));
+  L->acc = take(batch * glwe_words(ctx));
+  L->coeffs = take(batch * tables * (((size_t)1 << ctx->params.log_p) + 1));  // lut_sets = batch fits
+  L->big = take(batch * tables * big_lwe_words(ctx));
+  L->words = at;
+}
+
+size_t mv_bytes(const tfhe_context* ctx, size_t batch, size_t tables) {
+  MvLayout L;
+  mv_layout(ctx, batch, tables, &L);
+  return L.words * sizeof(u32);
+}
+
+u32* mv_acc0(const tfhe_context* ctx) { return ctx->d_mv_const; }
+u32* mv_positions(const tfhe_context* ctx) { return ctx->d_mv_const + glwe_words(ctx); }
+u32* mv_caller_positions(const tfhe_context* ctx) { return ctx->d_mv_const + glwe_words(ctx) + kSparseMaxTerms; }
+
+// what the parameters must allow: kappa = 2^(31 - log_p - padding) exists, a value covers at least two coefficients
+int check_mv_params(tfhe_context* ctx) {
+  const tfhe_params& p = ctx->params;
+  if (p.log_p + p.padding_bits > 31)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "multi-value bootstrapping needs log_p + padding_bits <= 31 (the accumulator holds half a step): " +
+                    std::to_string(p.log_p + p.padding_bits));
+  if (p.log_p >= ctx->pbs.log_n)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "multi-value bootstrapping needs log_p < log2 N (at least two coefficients per value)");
+  return TFHE_OK;
+}
+
+int check_mv_shape(tfhe_context* ctx, size_t batch, size_t tables) {
+  if (batch == 0 || tables == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "batch and tables must be at least 1");
+  if (batch > kMaxBatch || tables > kMaxBatch || (double)batch * (double)tables > (double)kMaxBatch)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "batch * tables exceeds 2^31 - 1 (one key switch per result)");
+  return TFHE_OK;
+}
+
+// the constants of the context's multi-value calls; allocates once (never inside a _device form)
+int ensure_mv_const(tfhe_context* ctx) {
+  if (ctx->d_mv_const) return TFHE_OK;
+  TFHE_TRY(check_mv_params(ctx));
+  const tfhe_params& p = ctx->params;
+  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_mv_const), (glwe_words(ctx) + 2 * (size_t)kSparseMaxTerms) * sizeof(u32)));
+  hipError_t e = launch::multi_value_constants(ctx->stream, p.log_p, ctx->pbs.log_n, ctx->pbs.k, 1u << (31 - p.log_p - p.padding_bits),
+                                               mv_acc0(ctx), mv_positions(ctx));
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the stream may be another one by the next call
+  if (e != hipSuccess) {
+    (void)hipFree(ctx->d_mv_const);
+    ctx->d_mv_const = nullptr;
+    return hip_fail(ctx, e, "multi_value_constants");
+  }
+  return TFHE_OK;
+}
+
+int reserve_mv(tfhe_context* ctx, size_t batch, size_t tables) {
+  TFHE_TRY(ensure_mv_const(ctx));
+  if (batch <= ctx->mv_batch && tables <= ctx->mv_tables) return TFHE_OK;
+  const size_t new_batch = std::max(batch, ctx->mv_batch), new_tables = std::max(tables, ctx->mv_tables);
+  TFHE_TRY(check_mv_shape(ctx, new_batch, new_tables));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->mv_batch = ctx->mv_tables = 0;
+  TFHE_TRY(ensure(ctx, &ctx->d_mv_ws, &ctx->mv_ws_words, mv_bytes(ctx, new_batch, new_tables) / sizeof(u32)));
+  ctx->mv_batch = new_batch;
+  ctx->mv_tables = new_tables;
+  return TFHE_OK;
+}
+
+// steps 1 and 2 on rotation inputs [batch][n + 1]: A [batch][k+1][N] and coeffs [sets][tables][B + 1] are scratch,
+// out [batch][tables][k N + 1].  The tree LUT's level 0 (tables = tables * B^(d-1) sub-tables) and the bootstrap share it;
+// timed: the rotation goes between the rotation span's events, as in a bootstrap (the tree LUT times nothing).
+int enqueue_mv_rotate_combine(tfhe_context* ctx, const u32* rot_in, size_t batch, const u32* luts, size_t lut_sets, size_t tables,
+                              u32* A, u32* coeffs, u32* out, bool timed) {
+  const u32 log_p = ctx->params.log_p;
+  const size_t sets = lut_sets == 1 ? 1 : batch;
+  if (timed) TFHE_TRY(span_begin(ctx, kRotationSpan));
+  HIP_TRY(ctx, enqueue_blind_rotate(ctx, rot_in, batch, mv_acc0(ctx), 1, A, nullptr, AccSource{true, 0u}));
+  if (timed) TFHE_TRY(span_end(ctx, kRotationSpan, false));
+  HIP_TRY(ctx, launch::multi_value_coefficients(ctx->stream, luts, sets * tables, log_p, reinterpret_cast<i32*>(coeffs)));
+  HIP_TRY(ctx, launch::glwe_sparse_extract(ctx->stream, A, batch, mv_positions(ctx), (1u << log_p) + 1u, reinterpret_cast<const i32*>(coeffs),
+                                           sets != 1, (u32)tables, ctx->pbs.log_n, ctx->pbs.k, out));
+  return TFHE_OK;
+}
+
+int check_mv_args(tfhe_context* ctx, const void* lwe_in, const void* luts, const void* lwe_out, size_t batch, size_t lut_sets, size_t tables) {
+  TFHE_TRY(check_present(ctx, {lwe_in, luts, lwe_out}, 1, "null pointer"));
+  TFHE_TRY(check_mv_shape(ctx, batch, tables));
+  if (lut_sets != 1 && lut_sets != batch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "lut_sets must be 1 or batch");
+  TFHE_TRY(check_mv_params(ctx));
+  if (!ctx->have_key) return fail(ctx, TFHE_ERR_NO_KEY, "load the bootstrapping key first");
+  if (ctx->bmmp)
+    return fail(ctx, TFHE_ERR_UNSUPPORTED,
+                "a BMMP key is loaded: the shared rotation starts from a GLWE accumulator, which the unrolled rotation does not do");
+  return TFHE_OK;
+}
+
+int check_sparse_args(tfhe_context* ctx, const void* glwe, size_t batch, const uint32_t* positions, size_t terms, const void* coeffs,
+                      size_t sets, size_t tables, const void* lwe_out) {
+  TFHE_TRY(check_present(ctx, {glwe, positions, coeffs, lwe_out}, 1, "null pointer"));
+  TFHE_TRY(check_mv_shape(ctx, batch, tables));
+  if (sets != 1 && sets != batch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "sets must be 1 or batch");
+  if (terms == 0 || terms > ctx->N || terms > kSparseMaxTerms)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "terms must be in [1, N]: the positions are distinct and below N = " + std::to_string(ctx->N));
+  std::vector<bool> seen(ctx->N, false);
+  for (size_t m = 0; m < terms; ++m) {
+    if (positions[m] >= ctx->N)
+      return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "position " + std::to_string(positions[m]) + " is not below N = " + std::to_string(ctx->N));
+    if (seen[positions[m]]) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "position " + std::to_string(positions[m]) + " is repeated");
+    seen[positions[m]] = true;
+  }
+  return TFHE_OK;
+}
+
+}  // namespace
+
+int tfhe_context_reserve_multi_value(tfhe_context* ctx, size_t max_batch, size_t max_tables) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_mv_shape(ctx, max_batch, max_tables));
+  return reserve_mv(ctx, max_batch, max_tables);
+}
+
+int tfhe_context_set_tree_lut_level0(tfhe_context* ctx, int multi_value) {
+  TFHE_TRY(check_ctx(ctx));
+  if (multi_value != 0 && multi_value != 1) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "multi_value must be 0 or 1");
+  if (multi_value) TFHE_TRY(ensure_mv_const(ctx));
+  ctx->tree_level0_multi_value = multi_value != 0;
+  return TFHE_OK;
+}
+
+int tfhe_glwe_sparse_extract_batch_device(tfhe_context* ctx, const uint32_t* glwe, size_t batch, const uint32_t* positions, size_t terms,
+                                          const int32_t* coeffs, size_t sets, size_t tables, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_sparse_args(ctx, glwe, batch, positions, terms, coeffs, sets, tables, lwe_out));
+  if (!ctx->d_mv_const)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "the call needs " + std::to_string(terms * sizeof(u32)) +
+                    " bytes for its positions on the device, 0 are reserved (tfhe_context_reserve_multi_value)");
+  HIP_TRY(ctx, launch::sparse_positions(ctx->stream, positions, (u32)terms, mv_caller_positions(ctx)));
+  HIP_TRY(ctx, launch::glwe_sparse_extract(ctx->stream, glwe, batch, mv_caller_positions(ctx), (u32)terms, coeffs, sets != 1,
+                                           (u32)tables, ctx->pbs.log_n, ctx->pbs.k, lwe_out));
+  return TFHE_OK;
+}
+
+int tfhe_glwe_sparse_extract_batch(tfhe_context* ctx, const uint32_t* glwe, size_t batch, const uint32_t* positions, size_t terms,
+                                   const int32_t* coeffs, size_t sets, size_t tables, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_sparse_args(ctx, glwe, batch, positions, terms, coeffs, sets, tables, lwe_out));
+  TFHE_TRY(ensure_mv_const(ctx));
+  enum { kIn, kCoeffs, kOut };
+  Staging s(ctx, {batch * glwe_words(ctx), sets * tables * terms, batch * tables * big_lwe_words(ctx)});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(kIn, glwe));
+  TFHE_TRY(s.upload(kCoeffs, coeffs));
+  TFHE_TRY(tfhe_glwe_sparse_extract_batch_device(ctx, s[kIn], batch, positions, terms, reinterpret_cast<const int32_t*>(s[kCoeffs]), sets,
+                                                 tables, s[kOut]));
+  return s.download_and_wait(kOut, lwe_out);
+}
+
+int tfhe_multi_value_bootstrap_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, const uint32_t* luts, size_t lut_sets,
+                                            size_t tables, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_mv_args(ctx, lwe_in, luts, lwe_out, batch, lut_sets, tables));
+  if (!ctx->d_mv_const || batch > ctx->mv_batch || tables > ctx->mv_tables)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "the call needs " + std::to_string(mv_bytes(ctx, batch, tables)) + " bytes of multi-value workspace (batch " +
+                    std::to_string(batch) + ", " + std::to_string(tables) + " tables), " +
+                    std::to_string(ctx->mv_batch ? mv_bytes(ctx, ctx->mv_batch, ctx->mv_tables) : 0) + " are reserved for batch " +
+                    std::to_string(ctx->mv_batch) + " and " + std::to_string(ctx->mv_tables) + " tables (tfhe_context_reserve_multi_value)");
+  MvLayout L;
+  mv_layout(ctx, ctx->mv_batch, ctx->mv_tables, &L);
+  u32* ws = ctx->d_mv_ws;
+  const u32 n = ctx->params.lwe_dimension;
+  auto key_switch = [&](const u32* in, size_t count, u32* out) -> int {
+    TFHE_TRY(span_begin(ctx, kKeySwitchSpan));
+    HIP_TRY(ctx, launch::key_switch(ctx->stream, ctx->ks, ctx->big_n, n, in, count, ctx->d_ksk, out, ctx->d_ksk_matrix, ctx->ks_path));
+    return span_end(ctx, kKeySwitchSpan, false);
+  };
+  if (ctx->ks_first) {
+    TFHE_TRY(key_switch(lwe_in, batch, ws + L.ks));
+    TFHE_TRY(enqueue_mv_rotate_combine(ctx, ws + L.ks, batch, luts, lut_sets, tables, ws + L.acc, ws + L.coeffs, lwe_out, true));
+  } else {
+    TFHE_TRY(enqueue_mv_rotate_combine(ctx, lwe_in, batch, luts, lut_sets, tables, ws + L.acc, ws + L.coeffs, ws + L.big, true));
+    TFHE_TRY(key_switch(ws + L.big, batch * tables, lwe_out));  // after the combination: its noise is not amplified
+  }
+  if (ctx->timing) ctx->ev_valid_br = ctx->ev_valid_ks = true;  // both spans, as after a bootstrap
+  return TFHE_OK;
+}
+
+int tfhe_multi_value_bootstrap_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, const uint32_t* luts, size_t lut_sets,
+                                     size_t tables, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_mv_args(ctx, lwe_in, luts, lwe_out, batch, lut_sets, tables));
+  TFHE_TRY(reserve_mv(ctx, batch, tables));
+  const size_t io = io_words(ctx);
+  enum { kIn, kLuts, kOut };
+  Staging s(ctx, {batch * io, lut_sets * tables << ctx->params.log_p, batch * tables * io});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(kIn, lwe_in));
+  TFHE_TRY(s.upload(kLuts, luts));
+  TFHE_TRY(tfhe_multi_value_bootstrap_batch_device(ctx, s[kIn], batch, s[kLuts], lut_sets, tables, s[kOut]));
+  return s.download_and_wait(kOut, lwe_out);
+}
+
 // ---------------------------------------------------------------------------------- tree LUT
 // tfhe_hip.h states the operation.  Level t is ONE rotation call over all rows x tables x sub-tables and one packing
 // call (in the chunks the packing workspace holds, like tfhe_pack_lwe_batch_device); the only host loop is the one over
@@ -2673,6 +2889,7 @@ int tfhe_tree_lut_batch_device(tfhe_context* ctx, const uint32_t* const* digits,
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
                 "the call needs " + std::to_string(L.words * sizeof(u32)) + " bytes of tree-LUT workspace, " +
                     std::to_string(ctx->tree_ws_words * sizeof(u32)) + " are reserved (tfhe_context_reserve_tree_lut)");
+  if (ctx->tree_level0_multi_value) TFHE_TRY(check_mv_params(ctx));
   const u32 log_p = ctx->params.log_p, log_n = ctx->pbs.log_n, n = ctx->params.lwe_dimension;
   const u32 log_rep = log_n - log_p;
   const size_t n1 = lwe_words(ctx);
@@ -2692,10 +2909,17 @@ int tfhe_tree_lut_batch_device(tfhe_context* ctx, const uint32_t* const* digits,
   size_t count = L.rotations;
   const u32* digit = nullptr;
   TFHE_TRY(digit_of(0, &digit));
-  HIP_TRY(ctx, launch::tree_lut_expand(s, digit, count, count / batch, (u32)n1, lwe));
-  HIP_TRY(ctx, launch::tree_lut_test_vectors(s, table, table_sets == 1 ? 0 : tables << (log_p * d), count, count / batch, log_p, log_n, tv));
   u32* cur = d == 1 && ctx->ks_first ? lwe_out : results[0];
-  HIP_TRY(ctx, enqueue_blind_rotate(ctx, lwe, count, tv, count, nullptr, cur, AccSource{false, 0u, state}));
+  if (ctx->tree_level0_multi_value) {
+    // ONE rotation per row; the tables * B^(d-1) sub-tables of a row are coefficient rows of the per-table step, in the
+    // order (table, h) of the table itself.  A sits where the segments' state would, the coefficients where the test
+    // vectors would: (B + 1) words against N per sub-table.
+    TFHE_TRY(enqueue_mv_rotate_combine(ctx, digit, batch, table, table_sets, count / batch, state, tv, cur, false));
+  } else {
+    HIP_TRY(ctx, launch::tree_lut_expand(s, digit, count, count / batch, (u32)n1, lwe));
+    HIP_TRY(ctx, launch::tree_lut_test_vectors(s, table, table_sets == 1 ? 0 : tables << (log_p * d), count, count / batch, log_p, log_n, tv));
+    HIP_TRY(ctx, enqueue_blind_rotate(ctx, lwe, count, tv, count, nullptr, cur, AccSource{false, 0u, state}));
+  }
   for (size_t t = 1; t < d; ++t) {
     // G_h = Pack of the B results [h B, (h + 1) B), each on N / B neighbouring coefficients
     const size_t groups = count >> log_p;

@@ -86,6 +86,17 @@ struct tfhe_context {
   u32* d_extract_ws = nullptr;
   size_t extract_ws_words = 0;
   size_t extract_batch = 0, extract_digits = 0;
+  // multi-value bootstrap.  d_mv_const (allocated by tfhe_context_reserve_multi_value, by tfhe_context_set_tree_lut_level0(1)
+  // and by the host forms): the constant accumulator (0, .., 0, kappa (1 + X + .. + X^(N-1))) [k+1][N], the B + 1 positions
+  // of a lookup table's coefficients [kSparseMaxTerms], a caller's positions [kSparseMaxTerms].  d_mv_ws
+  // (tfhe_context_reserve_multi_value): the key-switched inputs [mv_batch][n + 1], the rotated accumulators
+  // [mv_batch][k+1][N], the coefficients [mv_batch][mv_tables][B + 1], the combinations before the key switch
+  // [mv_batch][mv_tables][k N + 1]
+  u32* d_mv_const = nullptr;
+  u32* d_mv_ws = nullptr;
+  size_t mv_ws_words = 0;
+  size_t mv_batch = 0, mv_tables = 0;
+  bool tree_level0_multi_value = false;  // tfhe_context_set_tree_lut_level0
   bool aligned = false;       // decomposer alignment (tfhe_context_set_decomposer_alignment)
   bool ks_first = false;      // bootstrap order (tfhe_context_set_bootstrap_order)
   int shape = 0;              // kernel shape of the blind rotation (tfhe_context_set_kernel_shape): launch::kShape*

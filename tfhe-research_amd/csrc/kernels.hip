@@ -13,6 +13,7 @@
 #include "launch.h"
 #include "lwe_dense.h"
 #include "lwe_extract.h"
+#include "multi_value.h"
 #include "passes.h"
 
 namespace tfhe {
@@ -1110,6 +1111,49 @@ struct ExtractThread {
   __device__ size_t threads() const { return (size_t)gridDim.x * blockDim.x; }
 };
 __global__ void __launch_bounds__(kExtractThreads) extract_step_kernel(ExtractStepArgs a) { extract_step(ExtractThread(), a); }
+
+// ------------------------------------------------------------------------------ multi-value bootstrap
+// multi_value.h::sparse_extract_tile states the per-table step; this is its workgroup context on the device.  The
+// pointers arrive as kernel arguments of their own, not in the struct: only there does __restrict__ tell the compiler
+// that the stores to out cannot touch positions or coeffs, which is what lets it read both with scalar loads.
+struct SparseWorkgroup {
+  __device__ u32 thread() const { return threadIdx.x; }
+  __device__ u32 block_x() const { return blockIdx.x; }
+  __device__ u32 block_y() const { return blockIdx.y; }
+  __device__ void barrier() const { __syncthreads(); }
+  __device__ u32* lds() const { return reinterpret_cast<u32*>(g_smem); }
+};
+__global__ void __launch_bounds__(kSparseThreads)
+glwe_sparse_extract_kernel(const u32* __restrict__ glwe, const u32* __restrict__ positions, const i32* __restrict__ coeffs,
+                           u32* __restrict__ out, size_t set_stride, u32 log_n, u32 k, u32 terms, u32 tables, u32 tables_per_run) {
+  const SparseExtractArgs a{glwe, positions, coeffs, out, set_stride, log_n, k, terms, tables, tables_per_run};
+  sparse_extract_tile(SparseWorkgroup(), a);
+}
+// coeffs [rows][B + 1] = the coefficients of (1 - X) construct_test_from_lut(luts[row]), luts [rows][B]
+__global__ void __launch_bounds__(256) multi_value_coefficients_kernel(const u32* __restrict__ luts, size_t rows, u32 log_p,
+                                                                       i32* __restrict__ coeffs) {
+  const u32 terms = (1u << log_p) + 1u;
+  const size_t total = rows * terms;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+    coeffs[i] = (i32)multi_value_coefficient(luts + ((i / terms) << log_p), (u32)(i % terms), log_p);
+}
+// what a context's multi-value calls share: the accumulator (0, .., 0, kappa (1 + X + .. + X^(N-1))) and the B + 1 positions
+__global__ void __launch_bounds__(256) multi_value_constants_kernel(u32 log_p, u32 log_n, u32 k, u32 kappa, u32* __restrict__ acc,
+                                                                    u32* __restrict__ positions) {
+  const u32 acc_words = (k + 1u) << log_n, body = k << log_n, terms = (1u << log_p) + 1u;
+  for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < acc_words; i += gridDim.x * blockDim.x) acc[i] = i >= body ? kappa : 0u;
+  for (u32 m = blockIdx.x * blockDim.x + threadIdx.x; m < terms; m += gridDim.x * blockDim.x)
+    positions[m] = multi_value_position(m, log_p, log_n);
+}
+// a caller's positions come from host memory: up to kSparsePositionsPerLaunch of them travel as kernel arguments, so that a
+// captured call carries them in the graph
+constexpr u32 kSparsePositionsPerLaunch = 64;
+struct SparsePositions {
+  u32 v[kSparsePositionsPerLaunch];
+};
+__global__ void __launch_bounds__(64) sparse_positions_kernel(SparsePositions p, u32 count, u32* __restrict__ dst) {
+  if (threadIdx.x < count) dst[threadIdx.x] = p.v[threadIdx.x];
+}
 
 // ------------------------------------------------------------------------------ encrypted convolution
 // glwe_conv.h states the operation and its exactness bound.  Two kernels:
@@ -2239,6 +2283,46 @@ hipError_t extract_step(hipStream_t s, const ExtractStepArgs& a) {
   // a thread owns four words at a time
   hipLaunchKernelGGL(extract_step_kernel, dim3(grid_for((a.total + 3) / 4, kExtractThreads)), dim3(kExtractThreads), 0, s, a);
   return hipGetLastError();
+}
+
+hipError_t glwe_sparse_extract(hipStream_t s, const u32* glwe, size_t batch, const u32* positions, u32 terms, const i32* coeffs,
+                               bool per_sample_sets, u32 tables, u32 log_n, u32 k, u32* out) {
+  if (batch == 0 || batch > 0x7FFFFFFFull || tables == 0 || terms == 0 || terms > kSparseMaxTerms || terms > (1u << log_n))
+    return hipErrorInvalidValue;
+  const size_t lds = ((size_t)(k + 1) << log_n) * sizeof(u32);
+  if (lds > 64 * 1024) return hipErrorInvalidValue;
+  const u32 run = sparse_tables_per_run(batch, tables);
+  const dim3 grid((unsigned)batch, (tables + run - 1) / run);
+  hipLaunchKernelGGL(glwe_sparse_extract_kernel, grid, dim3(kSparseThreads), lds, s, glwe, positions, coeffs, out,
+                     per_sample_sets ? (size_t)tables * terms : (size_t)0, log_n, k, terms, tables, run);
+  return hipGetLastError();
+}
+
+hipError_t multi_value_coefficients(hipStream_t s, const u32* luts, size_t rows, u32 log_p, i32* coeffs) {
+  if (rows == 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(multi_value_coefficients_kernel, dim3(grid_for(rows * ((1u << log_p) + 1u), 256)), dim3(256), 0, s, luts, rows,
+                     log_p, coeffs);
+  return hipGetLastError();
+}
+
+hipError_t multi_value_constants(hipStream_t s, u32 log_p, u32 log_n, u32 k, u32 kappa, u32* acc, u32* positions) {
+  if (log_p >= log_n) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(multi_value_constants_kernel, dim3(grid_for((size_t)(k + 1) << log_n, 256)), dim3(256), 0, s, log_p, log_n, k,
+                     kappa, acc, positions);
+  return hipGetLastError();
+}
+
+hipError_t sparse_positions(hipStream_t s, const u32* host_positions, u32 terms, u32* dst) {
+  if (terms == 0 || terms > kSparseMaxTerms) return hipErrorInvalidValue;
+  for (u32 at = 0; at < terms; at += kSparsePositionsPerLaunch) {
+    SparsePositions p{};
+    const u32 count = terms - at < kSparsePositionsPerLaunch ? terms - at : kSparsePositionsPerLaunch;
+    for (u32 i = 0; i < count; ++i) p.v[i] = host_positions[at + i];
+    hipLaunchKernelGGL(sparse_positions_kernel, dim3(1), dim3(64), 0, s, p, count, dst + at);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 // How a convolution goes out: one team per (query, output); the channels in passes of rows_per_pass, the admitted

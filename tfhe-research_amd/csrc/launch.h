@@ -5,6 +5,7 @@
 #include "glwe_conv.h"
 #include "ks_matrix.h"
 #include "lwe_extract.h"
+#include "multi_value.h"
 #include "pbs_wave.h"
 
 namespace tfhe {
@@ -157,6 +158,19 @@ hipError_t dense_tile_rows(hipStream_t s, const u32* in, size_t period, size_t c
 // ---- digit extraction (lwe_extract.h::extract_step): the one elementwise launch between two sign bootstraps.
 // hipErrorInvalidValue: an empty call or a shift above 31
 hipError_t extract_step(hipStream_t s, const ExtractStepArgs& a);
+
+// ---- multi-value bootstrap (multi_value.h::sparse_extract_tile): out [batch][tables][k N + 1], the signed gather of
+// `terms` sample extractions of glwe [batch][k+1][N] at positions [terms] (device) times coeffs [1 or batch][tables][terms].
+// One workgroup per (sample, run of tables): multi_value.h::sparse_tables_per_run.
+// hipErrorInvalidValue: an empty call, more than kSparseMaxTerms or N terms, a ring whose GLWE exceeds 64 KiB of LDS
+hipError_t glwe_sparse_extract(hipStream_t s, const u32* glwe, size_t batch, const u32* positions, u32 terms, const i32* coeffs,
+                               bool per_sample_sets, u32 tables, u32 log_n, u32 k, u32* out);
+// coeffs [rows][B + 1] = multi_value_coefficient(luts [rows][B])
+hipError_t multi_value_coefficients(hipStream_t s, const u32* luts, size_t rows, u32 log_p, i32* coeffs);
+// acc [k+1][N] = (0, .., 0, kappa (1 + X + .. + X^(N-1))), positions [B + 1] = multi_value_position
+hipError_t multi_value_constants(hipStream_t s, u32 log_p, u32 log_n, u32 k, u32 kappa, u32* acc, u32* positions);
+// dst [terms] (device) = host_positions, as kernel arguments: no copy node, capturable
+hipError_t sparse_positions(hipStream_t s, const u32* host_positions, u32 terms, u32* dst);
 
 // ---- encrypted convolution (glwe_conv.h::glwe_conv_team; the plan: kernels.hip::glwe_conv_plan)
 struct GlweConvPlanInfo {
