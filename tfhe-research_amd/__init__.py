@@ -129,7 +129,6 @@ class TfheParams:
 
 
 _lib = None
-_u32p = C.POINTER(C.c_uint32)
 
 
 def library_available() -> bool:
@@ -171,19 +170,105 @@ def lib():
         _lib.tfhe_last_error.restype = C.c_char_p
         _lib.tfhe_status_string.restype = C.c_char_p
         _lib.tfhe_version.restype = C.c_char_p
+        _lib.tfhe_context_backend.restype = C.c_char_p
     return _lib
 
 
+# -- what every entry point's wrapper is made of: the facts about arguments, stated once -------------------------
 def _np(x) -> np.ndarray:
     return np.ascontiguousarray(x, dtype=np.uint32)
 
 
-def _hp(a: np.ndarray):
-    return a.ctypes.data_as(_u32p)
-
-
 def _is_torch(x) -> bool:
     return type(x).__module__.startswith("torch")
+
+
+def _invalid(text: str) -> "TfheError":
+    return TfheError(TFHE_ERR_INVALID_ARGUMENT, text)
+
+
+def _ptr(x, itemsize: int = 4):
+    """What the ABI takes for x: numpy array -> host pointer, torch tensor -> device pointer, None -> NULL.  A device
+    pointer is only ever taken from a contiguous CUDA tensor of `itemsize`-byte elements (8: prepared GGSWs)."""
+    if x is None:
+        return None
+    if isinstance(x, np.ndarray):
+        return C.c_void_p(x.ctypes.data)
+    if not (x.is_cuda and x.is_contiguous() and x.element_size() == itemsize):
+        raise _invalid(f"a contiguous device tensor of {itemsize}-byte elements is needed, got {x.dtype} on {x.device}")
+    return C.c_void_p(x.data_ptr())
+
+
+def _ptrs(xs):
+    """the array of pointers the ABI takes for a sequence of arrays"""
+    return (C.c_void_p * len(xs))(*[_ptr(x).value for x in xs])
+
+
+def _dims(shape) -> str:
+    return "[" + ", ".join("*" if s is None else str(s) for s in shape) + "]"
+
+
+def _check_u32(what, name, x, dev, shape=None, like=None, text=None):
+    """x is read or written by the ABI as 32-bit words through a bare pointer.  In a device form it must be a contiguous
+    torch tensor of a 4-byte integer dtype on the device (on `like`'s, where given); in a host form it is a uint32 array
+    already (_np).  `shape`, if given, is what it must measure (None: any size)."""
+    if dev:
+        ok = _is_torch(x) and x.element_size() == 4 and not x.is_floating_point() and x.is_contiguous() \
+            and (x.is_cuda if like is None else x.device == like.device)
+    else:
+        ok = isinstance(x, np.ndarray) and x.dtype.itemsize == 4 and x.flags.c_contiguous
+    if ok and shape is not None and x.shape != shape:
+        ok = len(x.shape) == len(shape) and all(s is None or int(d) == s for d, s in zip(x.shape, shape))
+    if ok:
+        return
+    if text is None and dev:
+        text = f"{what}: {name} must be a contiguous 32-bit integer tensor{'' if shape is None else ' ' + _dims(shape)} " \
+               f"on {'the device' if like is None else like.device}"
+    elif text is None:
+        text = f"{what}: {name} {_dims(shape)} expected, got {tuple(x.shape)}"
+    raise _invalid(text)
+
+
+def _same_kind(what, names, xs, every="both") -> bool:
+    """True: all of xs (None: not given) are torch tensors, the device form; False: none is, the host form"""
+    dev = _is_torch(xs[0])
+    if any(x is not None and _is_torch(x) != dev for x in xs):
+        raise _invalid(f"{what}: {names} must {every} be numpy or {every} torch")
+    return dev
+
+
+def _lead(x, dev):
+    """x under one more leading dimension of 1 (a view)"""
+    return x.unsqueeze(0) if dev else x[None]
+
+
+def _lift_table(what, table, dev, batch, width):
+    """table [1 or batch][tables][width] (or [tables][width] / [width]: shared) -> (table in three dimensions, sets,
+    tables) after the checks the ABI cannot make on a bare pointer"""
+    while len(table.shape) < 3:
+        table = _lead(table, dev)
+    text = f"{what} [1 or {batch}][tables][{width}] of 32-bit integers expected, got {tuple(table.shape)}"
+    if len(table.shape) != 3 or int(table.shape[0]) not in (1, batch) or int(table.shape[1]) < 1:
+        raise _invalid(text)
+    _check_u32(what, "table", table, dev, (None, None, width), text=text)
+    return table, int(table.shape[0]), int(table.shape[1])
+
+
+def _result(what, dev, out, shape, like):
+    """The array the ABI writes prod(shape) words to (shape None: as many as `like`, in its shape).  Host form: a fresh
+    array of zeros (`out` is not looked at).  Device form: the caller's `out` once it is checked, or a new tensor beside
+    `like`."""
+    if dev and out is None:
+        import torch
+        if shape is None or like.shape == shape:
+            return torch.empty_like(like)
+        return torch.empty(shape, dtype=like.dtype, device=like.device)
+    if shape is None:
+        shape = like.shape
+    if not dev:
+        return np.zeros(shape, dtype=np.uint32)
+    _check_u32(what, "out", out, True, shape, like)
+    return out
 
 
 _capture_gc_forced = False
@@ -207,18 +292,12 @@ def _collect_before_captures():
         pass
 
 
-def _dp(t):
-    """device pointer of a contiguous 4-byte torch tensor"""
-    assert t.is_cuda and t.is_contiguous() and t.element_size() == 4, "need contiguous 32-bit CUDA tensor"
-    return C.cast(C.c_void_p(t.data_ptr()), _u32p)
-
-
 def construct_test_from_lut(params: TfheParams, lut) -> np.ndarray:
     """test_vector.rs:38-67 (host side of the C ABI)."""
     lut = _np(lut)
     out = np.zeros(params.N, dtype=np.uint32)
     cp = params._c()
-    st = lib().tfhe_construct_test_from_lut(C.byref(cp), _hp(lut), C.c_size_t(lut.size), _hp(out))
+    st = lib().tfhe_construct_test_from_lut(C.byref(cp), _ptr(lut), C.c_size_t(lut.size), _ptr(out))
     if st:
         raise TfheError(st, "construct_test_from_lut")
     return out
@@ -257,7 +336,7 @@ def construct_test_vector_boolean(params: TfheParams, truth) -> np.ndarray:
     out = np.zeros(params.N, dtype=np.uint32)
     cp = params._c()
     arr = (C.c_uint32 * 4)(*[int(v) for v in truth])
-    st = lib().tfhe_construct_test_vector_boolean(C.byref(cp), arr, _hp(out))
+    st = lib().tfhe_construct_test_vector_boolean(C.byref(cp), arr, _ptr(out))
     if st:
         raise TfheError(st, "construct_test_vector_boolean")
     return out
@@ -271,7 +350,7 @@ def save_array(path: str, kind: int, params: TfheParams, array, aligned: bool = 
     dims = (C.c_uint32 * a.ndim)(*a.shape)
     cp = params._c()
     st = lib().tfhe_file_write(os.fsencode(path), C.c_uint32(kind), C.byref(cp), C.c_uint32(int(aligned)),
-                               dims, C.c_uint32(a.ndim), _hp(a))
+                               dims, C.c_uint32(a.ndim), _ptr(a))
     if st:
         raise TfheError(st, f"writing {path}")
 
@@ -287,7 +366,7 @@ def load_array(path: str):
     if st:
         raise TfheError(st, f"reading {path}")
     out = np.zeros(tuple(dims[i] for i in range(ndims.value)), dtype=np.uint32)
-    st = lib().tfhe_file_read(os.fsencode(path), _hp(out), C.c_uint64(out.size))
+    st = lib().tfhe_file_read(os.fsencode(path), _ptr(out), C.c_uint64(out.size))
     if st:
         raise TfheError(st, f"reading {path}")
     params = TfheParams(cp.glwe_dimension, cp.glwe_poly_degree, cp.lwe_dimension,
@@ -394,7 +473,6 @@ class Context:
         self.params = params
         self._h = C.c_void_p()
         cp = params._c()
-        lib().tfhe_context_backend.restype = C.c_char_p
         st = lib().tfhe_context_create_with_backend(C.byref(cp), C.c_int(device), C.c_int(backend),
                                                     C.byref(self._h))
         if st:
@@ -422,6 +500,14 @@ class Context:
     def _check(self, st: int):
         if st:
             raise TfheError(st, lib().tfhe_last_error(self._h).decode())
+
+    def _call(self, entry: str, dev: bool, *args):
+        """The one call path of an entry point with two forms: `entry` on host pointers, or `entry`_device on device
+        pointers, then on torch's current stream (bound first, and only then)."""
+        if dev:
+            self._bind_torch()
+            entry += "_device"
+        self._check(getattr(lib(), entry)(self._h, *args))
 
     @staticmethod
     def _check_quiet(st: int, message: str):
@@ -555,144 +641,112 @@ class Context:
         return br.value, ks.value
 
     # -- keys -----------------------------------------------------------------------------------
+    def _key_pair(self, what, bsk, ksk, bmmp: bool, copy: bool = False):
+        """-> (bsk, ksk, on the device?) in the reference layouts (numpy: as uint32 arrays, copied on request)"""
+        p = self.params
+        dev = _same_kind(what, "the two key arrays", (bsk, ksk))
+        if not dev:
+            bsk, ksk = (_np(bsk).copy(), _np(ksk).copy()) if copy else (_np(bsk), _np(ksk))
+        _check_u32(what, "the bootstrapping key", bsk, dev, p.bsk_bmmp_shape() if bmmp else p.bsk_shape())
+        _check_u32(what, "the key-switching key", ksk, dev, p.ksk_shape(), bsk if dev else None)
+        return bsk, ksk, dev
+
     def load_bootstrapping_key(self, bsk, ksk):
         """bsk [n][R][k+1][N], ksk [k*N*l_ks][n+1]: reference layouts (numpy or torch device)."""
-        p = self.params
-        if _is_torch(bsk):
-            self._bind_torch()
-            assert tuple(bsk.shape) == p.bsk_shape() and tuple(ksk.shape) == p.ksk_shape()
-            self._check(lib().tfhe_load_bootstrapping_key_device(self._h, _dp(bsk), _dp(ksk)))
-        else:
-            bsk, ksk = _np(bsk), _np(ksk)
-            assert bsk.shape == p.bsk_shape() and ksk.shape == p.ksk_shape()
-            self._check(lib().tfhe_load_bootstrapping_key(self._h, _hp(bsk), _hp(ksk)))
+        bsk, ksk, dev = self._key_pair("load_bootstrapping_key", bsk, ksk, False)
+        self._call("tfhe_load_bootstrapping_key", dev, _ptr(bsk), _ptr(ksk))
 
     def load_bootstrapping_key_bmmp(self, bsk_bmmp, ksk):
         """Key of the unrolled blind rotation (notes/BMMP Bootstrapping.md): bsk_bmmp [n/2*3][R][k+1][N]
         = GGSW(s s'), GGSW(s (1-s')), GGSW(s' (1-s)) per pair of key bits.  Bootstraps and gates then use
         it; needs N = 512 and even n.  Same plaintexts as the reference's bootstrap, different bits."""
-        p = self.params
-        if _is_torch(bsk_bmmp):
-            self._bind_torch()
-            assert tuple(bsk_bmmp.shape) == p.bsk_bmmp_shape() and tuple(ksk.shape) == p.ksk_shape()
-            self._check(lib().tfhe_load_bootstrapping_key_bmmp_device(self._h, _dp(bsk_bmmp), _dp(ksk)))
-        else:
-            bsk_bmmp, ksk = _np(bsk_bmmp), _np(ksk)
-            assert bsk_bmmp.shape == p.bsk_bmmp_shape() and ksk.shape == p.ksk_shape()
-            self._check(lib().tfhe_load_bootstrapping_key_bmmp(self._h, _hp(bsk_bmmp), _hp(ksk)))
+        bsk_bmmp, ksk, dev = self._key_pair("load_bootstrapping_key_bmmp", bsk_bmmp, ksk, True)
+        self._call("tfhe_load_bootstrapping_key_bmmp", dev, _ptr(bsk_bmmp), _ptr(ksk))
 
     @property
     def uses_bmmp(self) -> bool:
         return bool(lib().tfhe_context_uses_bmmp(self._h))
 
     # -- hot path -------------------------------------------------------------------------------
-    def _tv_count(self, tv, batch):
-        n_tv = 1 if tv.ndim == 1 else tv.shape[0]
-        assert tv.shape[-1] == self.params.N and n_tv in (1, batch)
-        return n_tv
+    def _lwe_rows(self, what, name, x, width, like=None):
+        """-> (x [batch][width], on the device?); numpy input of any leading shape is flattened to rows"""
+        dev = _is_torch(x if like is None else like)
+        if not dev:
+            x = _np(x)
+            if x.size % width:
+                raise _invalid(f"{what}: {name} of {width} words per ciphertext expected, got {tuple(x.shape)}")
+            x = x.reshape(-1, width)
+        _check_u32(what, name, x, dev, (None, width) if like is None else tuple(like.shape), like if dev else None)
+        return x, dev
+
+    def _test_vectors(self, what, tv, batch, dev, like):
+        """-> (tv, count): test vectors [N] (shared), [1][N] or [batch][N]"""
+        if not dev:
+            tv = _np(tv)
+        count = 1 if len(tv.shape) == 1 else int(tv.shape[0])
+        _check_u32(what, "test_vector_poly", tv, dev, None, like if dev else None)
+        if int(tv.shape[-1]) != self.params.N or count not in (1, batch) or (tv.numel() if dev else tv.size) != count * self.params.N:
+            raise _invalid(f"{what}: test vectors [{self.params.N}] or [1 or {batch}][{self.params.N}] expected, got {tuple(tv.shape)}")
+        return tv, count
+
+    def _rotate(self, entry, what, lwe_in, test_vector_poly, width, out_shape, out):
+        lwe, dev = self._lwe_rows(what, "lwe_in", lwe_in, width)
+        batch = int(lwe.shape[0])
+        tv, count = self._test_vectors(what, test_vector_poly, batch, dev, lwe)
+        res = _result(what, dev, out, (batch,) + out_shape, lwe)
+        self._call(entry, dev, _ptr(lwe), C.c_size_t(batch), _ptr(tv), C.c_size_t(count), _ptr(res))
+        return res
 
     def bootstrap(self, lwe_in, test_vector_poly, out=None):
         """bootstrap(): bootstrapping.rs:58-120 over a batch [batch][n+1]."""
-        p = self.params
-        if _is_torch(lwe_in):
-            self._bind_torch()
-            import torch
-            batch = lwe_in.shape[0]
-            assert lwe_in.shape[1] == self.io_dim + 1
-            if out is None:
-                out = torch.empty_like(lwe_in)
-            self._check(lib().tfhe_bootstrap_batch_device(
-                self._h, _dp(lwe_in), C.c_size_t(batch), _dp(test_vector_poly),
-                C.c_size_t(self._tv_count(test_vector_poly, batch)), _dp(out)))
-            return out
-        lwe_in, tv = _np(lwe_in), _np(test_vector_poly)
-        single = lwe_in.ndim == 1
-        lwe2 = lwe_in.reshape(-1, self.io_dim + 1)
-        res = np.zeros_like(lwe2)
-        self._check(lib().tfhe_bootstrap_batch(self._h, _hp(lwe2), C.c_size_t(lwe2.shape[0]), _hp(tv),
-                                               C.c_size_t(self._tv_count(tv, lwe2.shape[0])), _hp(res)))
-        return res[0] if single else res
+        res = self._rotate("tfhe_bootstrap_batch", "bootstrap", lwe_in, test_vector_poly, self.io_dim + 1, (self.io_dim + 1,), out)
+        return res[0] if not _is_torch(lwe_in) and np.ndim(lwe_in) == 1 else res   # numpy: one ciphertext in, one out
 
     def blind_rotate(self, lwe_in, test_vector_poly, out=None):
         """bootstrapping.rs:67-105 -> GLWE accumulators [batch][k+1][N]."""
         p = self.params
-        if _is_torch(lwe_in):
-            self._bind_torch()
-            import torch
-            batch = lwe_in.shape[0]
-            if out is None:
-                out = torch.empty((batch, p.k + 1, p.N), dtype=lwe_in.dtype, device=lwe_in.device)
-            self._check(lib().tfhe_blind_rotate_batch_device(
-                self._h, _dp(lwe_in), C.c_size_t(batch), _dp(test_vector_poly),
-                C.c_size_t(self._tv_count(test_vector_poly, batch)), _dp(out)))
-            return out
-        lwe2, tv = _np(lwe_in).reshape(-1, p.n + 1), _np(test_vector_poly)
-        res = np.zeros((lwe2.shape[0], p.k + 1, p.N), dtype=np.uint32)
-        self._check(lib().tfhe_blind_rotate_batch(self._h, _hp(lwe2), C.c_size_t(lwe2.shape[0]), _hp(tv),
-                                                  C.c_size_t(self._tv_count(tv, lwe2.shape[0])), _hp(res)))
-        return res
+        return self._rotate("tfhe_blind_rotate_batch", "blind_rotate", lwe_in, test_vector_poly, p.n + 1, (p.k + 1, p.N), out)
 
     # -- rotation from a GLWE accumulator (include/tfhe_hip.h states the operation) --------------
-    def _glwe_acc_args(self, what, lwe_in, acc_in, rotation_offset, width):
-        """-> (lwe [batch][width], acc [acc_count][k+1][N], acc_count) after the checks the ABI cannot make on bare
-        pointers: it reads batch * width and acc_count * (k+1) * N words"""
+    def _rotate_glwe(self, entry, what, lwe_in, acc_in, rotation_offset, width, out_shape, out):
+        """the checks the ABI cannot make on bare pointers (it reads batch * width and acc_count * (k+1) * N words), then
+        the call"""
         p = self.params
-        if _is_torch(lwe_in) != _is_torch(acc_in):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: lwe_in and acc_in must both be numpy or both torch")
-        if _is_torch(lwe_in):
+        dev = _same_kind(what, "lwe_in and acc_in", (lwe_in, acc_in))
+        if dev:
             for name, t in (("lwe_in", lwe_in), ("acc_in", acc_in)):
-                if not t.is_cuda or not t.is_contiguous() or t.element_size() != 4 or t.is_floating_point():
-                    raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: {name} must be a contiguous 32-bit integer device tensor")
-            lwe = lwe_in
-            acc = acc_in if acc_in.dim() == 3 else acc_in.unsqueeze(0)
+                _check_u32(what, name, t, dev, text=f"{what}: {name} must be a contiguous 32-bit integer device tensor")
+            lwe, acc = lwe_in, acc_in
         else:
-            lwe = _np(lwe_in)
+            lwe, acc = _np(lwe_in), _np(acc_in)
             lwe = lwe.reshape(-1, lwe.shape[-1])
-            acc = _np(acc_in)
-            acc = acc if acc.ndim == 3 else acc[None]
+        if len(acc.shape) != 3:
+            acc = _lead(acc, dev)
         if len(lwe.shape) != 2 or lwe.shape[1] != width:
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: lwe_in [batch][{width}] expected, got {tuple(lwe.shape)}")
+            raise _invalid(f"{what}: lwe_in [batch][{width}] expected, got {tuple(lwe.shape)}")
         batch = int(lwe.shape[0])
         if len(acc.shape) != 3 or tuple(acc.shape[1:]) != (p.k + 1, p.N) or int(acc.shape[0]) not in (1, batch):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT,
-                            f"{what}: acc_in [1 or {batch}][{p.k + 1}][{p.N}] expected, got {tuple(acc.shape)}")
+            raise _invalid(f"{what}: acc_in [1 or {batch}][{p.k + 1}][{p.N}] expected, got {tuple(acc.shape)}")
         if not 0 <= int(rotation_offset) < 2 * p.N:
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: rotation_offset must be in [0, 2N = {2 * p.N})")
-        return lwe, acc, int(acc.shape[0])
+            raise _invalid(f"{what}: rotation_offset must be in [0, 2N = {2 * p.N})")
+        res = _result(what, dev, out, (batch,) + out_shape, lwe)
+        self._call(entry, dev, _ptr(lwe), C.c_size_t(batch), _ptr(acc), C.c_size_t(int(acc.shape[0])),
+                   C.c_size_t(rotation_offset), _ptr(res))
+        return res
 
     def blind_rotate_glwe(self, lwe_in, acc_in, rotation_offset: int = 0, out=None):
         """Blind rotation that starts from GLWE ciphertext(s) acc_in [k+1][N] (shared) or [batch][k+1][N], words already
         encoded: X^{-(b~ + rotation_offset)} acc_in, then the n CMUXes -> [batch][k+1][N].  numpy (blocks) or torch
         device tensors (the context's stream)."""
         p = self.params
-        lwe, acc, count = self._glwe_acc_args("blind_rotate_glwe", lwe_in, acc_in, rotation_offset, p.n + 1)
-        batch = int(lwe.shape[0])
-        if _is_torch(lwe):
-            self._bind_torch()
-            out = self._lookup_out("blind_rotate_glwe", out, (batch, p.k + 1, p.N), lwe)
-            self._check(lib().tfhe_blind_rotate_glwe_batch_device(self._h, _dp(lwe), C.c_size_t(batch), _dp(acc), C.c_size_t(count),
-                                                                  C.c_size_t(rotation_offset), _dp(out)))
-            return out
-        res = np.zeros((batch, p.k + 1, p.N), dtype=np.uint32)
-        self._check(lib().tfhe_blind_rotate_glwe_batch(self._h, _hp(lwe), C.c_size_t(batch), _hp(acc), C.c_size_t(count),
-                                                       C.c_size_t(rotation_offset), _hp(res)))
-        return res
+        return self._rotate_glwe("tfhe_blind_rotate_glwe_batch", "blind_rotate_glwe", lwe_in, acc_in, rotation_offset,
+                                 p.n + 1, (p.k + 1, p.N), out)
 
     def bootstrap_glwe(self, lwe_in, acc_in, rotation_offset: int = 0, out=None):
         """blind_rotate_glwe + sample extraction at 0 + key switch, in the context's bootstrap order: [batch][io_dim+1]
         -> [batch][io_dim+1].  With acc_in = encrypt_test_vector(..) and offset 0: a bootstrap with a secret table."""
-        lwe, acc, count = self._glwe_acc_args("bootstrap_glwe", lwe_in, acc_in, rotation_offset, self.io_dim + 1)
-        batch = int(lwe.shape[0])
-        if _is_torch(lwe):
-            self._bind_torch()
-            out = self._lookup_out("bootstrap_glwe", out, (batch, self.io_dim + 1), lwe)
-            self._check(lib().tfhe_bootstrap_glwe_batch_device(self._h, _dp(lwe), C.c_size_t(batch), _dp(acc), C.c_size_t(count),
-                                                               C.c_size_t(rotation_offset), _dp(out)))
-            return out
-        res = np.zeros((batch, self.io_dim + 1), dtype=np.uint32)
-        self._check(lib().tfhe_bootstrap_glwe_batch(self._h, _hp(lwe), C.c_size_t(batch), _hp(acc), C.c_size_t(count),
-                                                    C.c_size_t(rotation_offset), _hp(res)))
-        return res
+        return self._rotate_glwe("tfhe_bootstrap_glwe_batch", "bootstrap_glwe", lwe_in, acc_in, rotation_offset,
+                                 self.io_dim + 1, (self.io_dim + 1,), out)
 
     # -- tree LUT: a function of d digits of log_p bits (include/tfhe_hip.h states the operation) --
     def reserve_tree_lut(self, max_batch: int, max_digits: int, max_tables: int = 1):
@@ -708,39 +762,20 @@ class Context:
         p = self.params
         d = len(digits)
         if d < 1 or d * p.log_p > 16:
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"tree_lut: 1 <= d and d * log_p <= 16 expected, got d = {d}")
-        dev = _is_torch(digits[0])
-        if any(_is_torch(x) != dev for x in list(digits) + [table]):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "tree_lut: digits and table must all be numpy or all torch")
+            raise _invalid(f"tree_lut: 1 <= d and d * log_p <= 16 expected, got d = {d}")
+        dev = _same_kind("tree_lut", "digits and table", list(digits) + [table], "all")
         if not dev:
             digits, table = [_np(x) for x in digits], _np(table)
-        while len(table.shape) < 3:
-            table = table.unsqueeze(0) if dev else table[None]
         batch = int(digits[0].shape[0]) if len(digits[0].shape) == 2 else -1
         width = self.io_dim + 1
         for x in digits:
-            if tuple(x.shape) != (batch, width) or (dev and (not x.is_cuda or not x.is_contiguous() or x.element_size() != 4
-                                                               or x.is_floating_point())):
-                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"tree_lut: every digit must be a contiguous 32-bit [batch][{width}] array")
-        sets, tables = int(table.shape[0]), int(table.shape[1])
-        if len(table.shape) != 3 or sets not in (1, batch) or int(table.shape[2]) != 1 << (p.log_p * d) or \
-                (dev and (not table.is_cuda or not table.is_contiguous() or table.element_size() != 4 or table.is_floating_point())):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT,
-                            f"tree_lut: table [1 or {batch}][tables][{1 << (p.log_p * d)}] of 32-bit integers expected, got {tuple(table.shape)}")
-        ptrs = (_u32p * d)()
-        if dev:
-            self._bind_torch()
-            for i, x in enumerate(digits):
-                ptrs[i] = _dp(x)
-            out = self._lookup_out("tree_lut", out, (batch, tables, width), digits[0])
-            self._check(lib().tfhe_tree_lut_batch_device(self._h, ptrs, C.c_size_t(d), C.c_size_t(batch), _dp(table),
-                                                         C.c_size_t(sets), C.c_size_t(tables), _dp(out)))
-            return out
-        for i, x in enumerate(digits):
-            ptrs[i] = _hp(x)
-        res = np.zeros((batch, tables, width), dtype=np.uint32)
-        self._check(lib().tfhe_tree_lut_batch(self._h, ptrs, C.c_size_t(d), C.c_size_t(batch), _hp(table), C.c_size_t(sets),
-                                              C.c_size_t(tables), _hp(res)))
+            _check_u32("tree_lut", "digit", x, dev, (batch, width),
+                       text=f"tree_lut: every digit must be a contiguous 32-bit [batch][{width}] array")
+        table, sets, tables = _lift_table("tree_lut: table", table, dev, batch, 1 << (p.log_p * d))
+        res = _result("tree_lut", dev, out, (batch, tables, width), digits[0])
+        ptrs = _ptrs(digits)
+        self._call("tfhe_tree_lut_batch", dev, ptrs, C.c_size_t(d), C.c_size_t(batch), _ptr(table), C.c_size_t(sets),
+                   C.c_size_t(tables), _ptr(res))
         return res
 
     # -- digit extraction and the wide LUT (include/tfhe_hip.h states the operations) --------------
@@ -758,9 +793,10 @@ class Context:
         width = self.io_dim + 1
         dev = _is_torch(lwe_in)
         lwe = lwe_in if dev else _np(lwe_in)
-        if len(lwe.shape) != 2 or int(lwe.shape[1]) != width or int(lwe.shape[0]) < 1 or \
-                (dev and (not lwe.is_cuda or not lwe.is_contiguous() or lwe.element_size() != 4 or lwe.is_floating_point())):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: lwe_in must be a contiguous 32-bit [batch][{width}] array")
+        text = f"{what}: lwe_in must be a contiguous 32-bit [batch][{width}] array"
+        _check_u32(what, "lwe_in", lwe, dev, (None, width), text=text)
+        if int(lwe.shape[0]) < 1:
+            raise _invalid(text)
         return lwe, int(lwe.shape[0]), dev
 
     def extract_digits(self, lwe_in, lsb: int, digit_bits: int, digits: int, out_lsb: int, remainder: bool = False, out=None):
@@ -772,31 +808,20 @@ class Context:
         lwe, batch, dev = self._extract_input("extract_digits", lwe_in)
         for name, v in (("lsb", lsb), ("digit_bits", digit_bits), ("digits", digits), ("out_lsb", out_lsb)):
             if not 0 <= int(v) <= 32:
-                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"extract_digits: {name} must be in [0, 32]")
+                raise _invalid(f"extract_digits: {name} must be in [0, 32]")
         if not 1 <= int(digits) <= 16:
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "extract_digits: 1 <= digits <= 16 expected")
+            raise _invalid("extract_digits: 1 <= digits <= 16 expected")
         digits = int(digits)
         shape = (batch, self.io_dim + 1)
-        args = (C.c_uint(int(lsb)), C.c_uint(int(digit_bits)), C.c_uint(digits), C.c_uint(int(out_lsb)))
-        ptrs = (_u32p * digits)()
-        if dev:
-            self._bind_torch()
-            import torch
-            if out is not None and len(out) != digits:
-                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"extract_digits: out must hold {digits} tensors")
-            outs = [self._lookup_out("extract_digits", None if out is None else out[t], shape, lwe) for t in range(digits)]
-            for t, x in enumerate(outs):
-                ptrs[t] = _dp(x)
-            rem = torch.empty(shape, dtype=lwe.dtype, device=lwe.device) if remainder else None
-            self._check(lib().tfhe_extract_digits_batch_device(self._h, _dp(lwe), C.c_size_t(batch), *args, ptrs,
-                                                               _dp(rem) if remainder else None))
-            return (outs, rem) if remainder else outs
-        outs = [np.zeros(shape, dtype=np.uint32) for _ in range(digits)]
-        for t, x in enumerate(outs):
-            ptrs[t] = _hp(x)
-        rem = np.zeros(shape, dtype=np.uint32) if remainder else None
-        self._check(lib().tfhe_extract_digits_batch(self._h, _hp(lwe), C.c_size_t(batch), *args, ptrs,
-                                                    _hp(rem) if remainder else None))
+        if not dev:
+            out = None   # the host form returns fresh arrays
+        elif out is not None and len(out) != digits:
+            raise _invalid(f"extract_digits: out must hold {digits} tensors")
+        outs = [_result("extract_digits", dev, None if out is None else out[t], shape, lwe) for t in range(digits)]
+        rem = _result("extract_digits", dev, None, shape, lwe) if remainder else None
+        ptrs = _ptrs(outs)
+        self._call("tfhe_extract_digits_batch", dev, _ptr(lwe), C.c_size_t(batch), C.c_uint(int(lsb)), C.c_uint(int(digit_bits)),
+                   C.c_uint(digits), C.c_uint(int(out_lsb)), ptrs, _ptr(rem))
         return (outs, rem) if remainder else outs
 
     def wide_lut(self, lwe_in, lsb: int, digits: int, table, out=None):
@@ -808,28 +833,12 @@ class Context:
         lwe, batch, dev = self._extract_input("wide_lut", lwe_in)
         d = int(digits)
         if d < 1 or d * p.log_p > 16 or not 0 <= int(lsb) <= 32:
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"wide_lut: 1 <= digits, digits * log_p <= 16 and lsb in [0, 32] expected")
-        if _is_torch(table) != dev:
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "wide_lut: lwe_in and table must both be numpy or both torch")
-        if not dev:
-            table = _np(table)
-        while len(table.shape) < 3:
-            table = table.unsqueeze(0) if dev else table[None]
-        sets, tables = int(table.shape[0]), int(table.shape[1])
-        if len(table.shape) != 3 or sets not in (1, batch) or int(table.shape[2]) != 1 << (p.log_p * d) or \
-                (dev and (not table.is_cuda or not table.is_contiguous() or table.element_size() != 4 or table.is_floating_point())):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT,
-                            f"wide_lut: table [1 or {batch}][tables][{1 << (p.log_p * d)}] of 32-bit integers expected, got {tuple(table.shape)}")
-        shape = (batch, tables, self.io_dim + 1)
-        if dev:
-            self._bind_torch()
-            out = self._lookup_out("wide_lut", out, shape, lwe)
-            self._check(lib().tfhe_wide_lut_batch_device(self._h, _dp(lwe), C.c_size_t(batch), C.c_uint(int(lsb)), C.c_size_t(d),
-                                                         _dp(table), C.c_size_t(sets), C.c_size_t(tables), _dp(out)))
-            return out
-        res = np.zeros(shape, dtype=np.uint32)
-        self._check(lib().tfhe_wide_lut_batch(self._h, _hp(lwe), C.c_size_t(batch), C.c_uint(int(lsb)), C.c_size_t(d), _hp(table),
-                                              C.c_size_t(sets), C.c_size_t(tables), _hp(res)))
+            raise _invalid("wide_lut: 1 <= digits, digits * log_p <= 16 and lsb in [0, 32] expected")
+        _same_kind("wide_lut", "lwe_in and table", (lwe_in, table))
+        table, sets, tables = _lift_table("wide_lut: table", table if dev else _np(table), dev, batch, 1 << (p.log_p * d))
+        res = _result("wide_lut", dev, out, (batch, tables, self.io_dim + 1), lwe)
+        self._call("tfhe_wide_lut_batch", dev, _ptr(lwe), C.c_size_t(batch), C.c_uint(int(lsb)), C.c_size_t(d), _ptr(table),
+                   C.c_size_t(sets), C.c_size_t(tables), _ptr(res))
         return res
 
     # -- multi-value bootstrapping: several tables from one rotation (include/tfhe_hip.h states the operations) --
@@ -846,36 +855,17 @@ class Context:
         """(positions, D) of luts [..][B] at this context's parameters: the module-level helper of the same name"""
         return multi_value_coefficients(self.params, luts)
 
-    def _mv_table(self, what, table, width, batch, dev, dtype_name="32-bit integers"):
-        """-> table [sets][tables][width] after the checks the ABI cannot make on a bare pointer"""
-        while len(table.shape) < 3:
-            table = table.unsqueeze(0) if dev else table[None]
-        if len(table.shape) != 3 or int(table.shape[0]) not in (1, batch) or int(table.shape[2]) != width or int(table.shape[1]) < 1 or \
-                (dev and (not table.is_cuda or not table.is_contiguous() or table.element_size() != 4 or table.is_floating_point())):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT,
-                            f"{what}: [1 or {batch}][tables][{width}] of {dtype_name} expected, got {tuple(table.shape)}")
-        return table
-
     def multi_value_bootstrap(self, lwe_in, luts, out=None):
         """Every table of luts [1 or batch][tables][B] (or [tables][B] / [B]: shared; un-encoded values < B = 2^log_p) of
         every row of lwe_in [batch][io_dim+1], from ONE blind rotation per row -> LWE [batch][tables][io_dim+1].  numpy
         (host form: reserves for itself, blocks) or torch device tensors (reserve_multi_value first)."""
-        p = self.params
         lwe, batch, dev = self._extract_input("multi_value_bootstrap", lwe_in)
-        if _is_torch(luts) != dev:
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "multi_value_bootstrap: lwe_in and luts must both be numpy or both torch")
-        luts = self._mv_table("multi_value_bootstrap: luts", luts if dev else _np(luts), 1 << p.log_p, batch, dev)
-        sets, tables = int(luts.shape[0]), int(luts.shape[1])
-        shape = (batch, tables, self.io_dim + 1)
-        if dev:
-            self._bind_torch()
-            out = self._lookup_out("multi_value_bootstrap", out, shape, lwe)
-            self._check(lib().tfhe_multi_value_bootstrap_batch_device(self._h, _dp(lwe), C.c_size_t(batch), _dp(luts), C.c_size_t(sets),
-                                                                      C.c_size_t(tables), _dp(out)))
-            return out
-        res = np.zeros(shape, dtype=np.uint32)
-        self._check(lib().tfhe_multi_value_bootstrap_batch(self._h, _hp(lwe), C.c_size_t(batch), _hp(luts), C.c_size_t(sets),
-                                                           C.c_size_t(tables), _hp(res)))
+        _same_kind("multi_value_bootstrap", "lwe_in and luts", (lwe_in, luts))
+        luts, sets, tables = _lift_table("multi_value_bootstrap: luts:", luts if dev else _np(luts), dev, batch,
+                                         1 << self.params.log_p)
+        res = _result("multi_value_bootstrap", dev, out, (batch, tables, self.io_dim + 1), lwe)
+        self._call("tfhe_multi_value_bootstrap_batch", dev, _ptr(lwe), C.c_size_t(batch), _ptr(luts), C.c_size_t(sets),
+                   C.c_size_t(tables), _ptr(res))
         return res
 
     def glwe_sparse_extract(self, glwe, positions, coeffs, out=None):
@@ -884,89 +874,63 @@ class Context:
         (or [tables][terms] / [terms]: shared) -> LWE [batch][tables][k N + 1].  numpy (host form) or torch device tensors
         for glwe and coeffs (reserve_multi_value first)."""
         p = self.params
-        dev = _is_torch(glwe)
-        if _is_torch(coeffs) != dev:
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "glwe_sparse_extract: glwe and coeffs must both be numpy or both torch")
+        dev = _same_kind("glwe_sparse_extract", "glwe and coeffs", (glwe, coeffs))
         pos = np.ascontiguousarray(np.asarray(positions).reshape(-1), dtype=np.uint32)
         if not dev:
             glwe = _np(glwe)
             coeffs = np.ascontiguousarray(coeffs, dtype=np.int32)
         if len(glwe.shape) == 2:
-            glwe = glwe.unsqueeze(0) if dev else glwe[None]
-        if len(glwe.shape) != 3 or tuple(glwe.shape[1:]) != (p.k + 1, p.N) or int(glwe.shape[0]) < 1 or \
-                (dev and (not glwe.is_cuda or not glwe.is_contiguous() or glwe.element_size() != 4 or glwe.is_floating_point())):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT,
-                            f"glwe_sparse_extract: glwe [batch][{p.k + 1}][{p.N}] of 32-bit integers expected, got {tuple(glwe.shape)}")
+            glwe = _lead(glwe, dev)
+        text = f"glwe_sparse_extract: glwe [batch][{p.k + 1}][{p.N}] of 32-bit integers expected, got {tuple(glwe.shape)}"
+        _check_u32("glwe_sparse_extract", "glwe", glwe, dev, (None, p.k + 1, p.N), text=text)
         batch = int(glwe.shape[0])
-        coeffs = self._mv_table("glwe_sparse_extract: coeffs", coeffs, int(pos.size), batch, dev)
-        sets, tables = int(coeffs.shape[0]), int(coeffs.shape[1])
-        shape = (batch, tables, p.big_n + 1)
-        i32p = C.POINTER(C.c_int32)
-        if dev:
-            self._bind_torch()
-            out = self._lookup_out("glwe_sparse_extract", out, shape, glwe)
-            self._check(lib().tfhe_glwe_sparse_extract_batch_device(self._h, _dp(glwe), C.c_size_t(batch), _hp(pos), C.c_size_t(pos.size),
-                                                                    C.cast(_dp(coeffs), i32p), C.c_size_t(sets), C.c_size_t(tables), _dp(out)))
-            return out
-        res = np.zeros(shape, dtype=np.uint32)
-        self._check(lib().tfhe_glwe_sparse_extract_batch(self._h, _hp(glwe), C.c_size_t(batch), _hp(pos), C.c_size_t(pos.size),
-                                                         coeffs.ctypes.data_as(i32p), C.c_size_t(sets), C.c_size_t(tables), _hp(res)))
+        if batch < 1:
+            raise _invalid(text)
+        coeffs, sets, tables = _lift_table("glwe_sparse_extract: coeffs:", coeffs, dev, batch, int(pos.size))
+        res = _result("glwe_sparse_extract", dev, out, (batch, tables, p.big_n + 1), glwe)
+        self._call("tfhe_glwe_sparse_extract_batch", dev, _ptr(glwe), C.c_size_t(batch), _ptr(pos), C.c_size_t(pos.size),
+                   _ptr(coeffs), C.c_size_t(sets), C.c_size_t(tables), _ptr(res))
         return res
 
     def sample_extract(self, glwe, sample_index: int = 0) -> np.ndarray:
         p = self.params
         g = _np(glwe).reshape(-1, p.k + 1, p.N)
         res = np.zeros((g.shape[0], p.big_n + 1), dtype=np.uint32)
-        self._check(lib().tfhe_sample_extract_batch(self._h, _hp(g), C.c_size_t(g.shape[0]),
-                                                    C.c_size_t(sample_index), _hp(res)))
+        self._check(lib().tfhe_sample_extract_batch(self._h, _ptr(g), C.c_size_t(g.shape[0]),
+                                                    C.c_size_t(sample_index), _ptr(res)))
         return res
 
     def key_switch(self, lwe_big, out=None):
         """key_switch_lwe(): key_switching.rs:63-103 with the loaded KSK."""
         p = self.params
-        if _is_torch(lwe_big):
-            self._bind_torch()
-            import torch
-            batch = lwe_big.shape[0]
-            if out is None:
-                out = torch.empty((batch, p.n + 1), dtype=lwe_big.dtype, device=lwe_big.device)
-            self._check(lib().tfhe_key_switch_batch_device(self._h, _dp(lwe_big), C.c_size_t(batch), _dp(out)))
-            return out
-        x = _np(lwe_big).reshape(-1, p.big_n + 1)
-        res = np.zeros((x.shape[0], p.n + 1), dtype=np.uint32)
-        self._check(lib().tfhe_key_switch_batch(self._h, _hp(x), C.c_size_t(x.shape[0]), _hp(res)))
+        x, dev = self._lwe_rows("key_switch", "lwe_big", lwe_big, p.big_n + 1)
+        res = _result("key_switch", dev, out, (int(x.shape[0]), p.n + 1), x)
+        self._call("tfhe_key_switch_batch", dev, _ptr(x), C.c_size_t(x.shape[0]), _ptr(res))
         return res
 
     # -- packing key switch: many LWE results into one GLWE (include/tfhe_hip.h states the operation) --
     def generate_packing_key(self, from_sk, glwe_sk, samples):
         """samples [from_dim*l_ks][k+1][N] pre-filled row by row like glwe_encrypt_zero (uniform masks, errors in
         the body) -> the packing key from `from_sk` (any dimension) to `glwe_sk`, with the context's ks_decomposer.
-        A torch device tensor is completed in place and returned."""
+        A torch device tensor is completed in place and returned; a numpy array is copied."""
         p = self.params
         f, sk = _np(from_sk).reshape(-1), _np(glwe_sk).reshape(p.k, p.N)
-        if _is_torch(samples):
-            self._bind_torch()
-            assert tuple(samples.shape) == p.pksk_shape(f.size)
-            self._check(lib().tfhe_generate_packing_key_device(self._h, _hp(f), C.c_size_t(f.size), _hp(sk),
-                                                               _dp(samples)))
-            return samples
-        out = _np(samples).copy()
-        assert out.shape == p.pksk_shape(f.size)
-        self._check(lib().tfhe_generate_packing_key(self._h, _hp(f), C.c_size_t(f.size), _hp(sk), _hp(out)))
-        return out
+        dev = _is_torch(samples)
+        key = samples if dev else _np(samples).copy()
+        _check_u32("generate_packing_key", "samples", key, dev, p.pksk_shape(f.size))
+        self._call("tfhe_generate_packing_key", dev, _ptr(f), C.c_size_t(f.size), _ptr(sk), _ptr(key))
+        return key
 
     def load_packing_key(self, pksk):
         """prepares pksk [from_dim*l_ks][k+1][N] (numpy or torch device tensor) and keeps it: independent of the
         bootstrapping key.  TfheError(TFHE_ERR_EXACTNESS) where the backend cannot pack exactly under the KS decomposer."""
         p = self.params
-        rows = int(pksk.shape[0])
-        assert tuple(pksk.shape[1:]) == (p.k + 1, p.N) and rows % p.ks_decomposer.levels == 0
-        dim = rows // p.ks_decomposer.levels
-        if _is_torch(pksk):
-            self._bind_torch()
-            self._check(lib().tfhe_load_packing_key_device(self._h, _dp(pksk), C.c_size_t(dim)))
-        else:
-            self._check(lib().tfhe_load_packing_key(self._h, _hp(_np(pksk)), C.c_size_t(dim)))
+        dev = _is_torch(pksk)
+        key = pksk if dev else _np(pksk)
+        _check_u32("load_packing_key", "pksk", key, dev, (None, p.k + 1, p.N))
+        if int(key.shape[0]) % p.ks_decomposer.levels:
+            raise _invalid(f"load_packing_key: {p.ks_decomposer.levels} rows per key bit expected, got {int(key.shape[0])} rows")
+        self._call("tfhe_load_packing_key", dev, _ptr(key), C.c_size_t(int(key.shape[0]) // p.ks_decomposer.levels))
 
     def pack_lwe(self, lwe, out=None):
         """lwe [groups][per_group][from_dim+1] (or [per_group][from_dim+1]: one group), per_group <= N ->
@@ -974,30 +938,20 @@ class Context:
         p = self.params
         dim = C.c_size_t()
         self._check_quiet(lib().tfhe_packing_key_dimension(self._h, C.byref(dim)), "load a packing key first")
-        if not _is_torch(lwe):
-            lwe = _np(lwe)
+        dev = _is_torch(lwe)
+        x = lwe if dev else _np(lwe)
         # the ABI reads from_dim+1 words per ciphertext: a wrong width would be read out of bounds
-        if lwe.ndim not in (2, 3) or lwe.shape[-1] != dim.value + 1:
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"pack_lwe: ciphertexts of {dim.value + 1} words expected "
-                                                       f"([groups][per_group][from_dim+1]), got shape {tuple(lwe.shape)}")
-        if _is_torch(lwe):
-            self._bind_torch()
-            import torch
-            if not lwe.is_contiguous():
-                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "pack_lwe: the device tensor must be contiguous")
-            x = lwe if lwe.dim() == 3 else lwe.unsqueeze(0)
-            if out is None:
-                out = torch.empty((x.shape[0], p.k + 1, p.N), dtype=lwe.dtype, device=lwe.device)
-            self._check(lib().tfhe_pack_lwe_batch_device(self._h, _dp(x), C.c_size_t(x.shape[0]),
-                                                         C.c_size_t(x.shape[1]), _dp(out)))
-            return out
-        x = _np(lwe)
-        x = x if x.ndim == 3 else x[None]
-        res = np.zeros((x.shape[0], p.k + 1, p.N), dtype=np.uint32)
-        self._check(lib().tfhe_pack_lwe_batch(self._h, _hp(x), C.c_size_t(x.shape[0]), C.c_size_t(x.shape[1]),
-                                              _hp(res)))
+        if len(x.shape) not in (2, 3) or x.shape[-1] != dim.value + 1:
+            raise _invalid(f"pack_lwe: ciphertexts of {dim.value + 1} words expected "
+                           f"([groups][per_group][from_dim+1]), got shape {tuple(x.shape)}")
+        if dev and not x.is_contiguous():
+            raise _invalid("pack_lwe: the device tensor must be contiguous")
+        _check_u32("pack_lwe", "lwe", x, dev)
+        if len(x.shape) == 2:
+            x = _lead(x, dev)
+        res = _result("pack_lwe", dev, out, (int(x.shape[0]), p.k + 1, p.N), x)
+        self._call("tfhe_pack_lwe_batch", dev, _ptr(x), C.c_size_t(x.shape[0]), C.c_size_t(x.shape[1]), _ptr(res))
         return res
-
     def external_product(self, ggsw, glwe) -> np.ndarray:
         """external_product(): ggsw.rs:132-161.  ggsw [R][k+1][N] (shared) or [batch][R][k+1][N]."""
         p = self.params
@@ -1005,32 +959,32 @@ class Context:
         gg = _np(ggsw)
         count = 1 if gg.ndim == 3 else gg.shape[0]
         res = np.zeros_like(g)
-        self._check(lib().tfhe_external_product_batch(self._h, _hp(gg), C.c_size_t(count), _hp(g),
-                                                      C.c_size_t(g.shape[0]), _hp(res)))
+        self._check(lib().tfhe_external_product_batch(self._h, _ptr(gg), C.c_size_t(count), _ptr(g),
+                                                      C.c_size_t(g.shape[0]), _ptr(res)))
         return res
 
     def prepare_ggsw_device(self, ggsw, out=None):
-        """device u32 GGSW(s) -> device NTT-domain GGSW(s) (torch int64 tensor)."""
-        import torch
-        self._bind_torch()
-        count = 1 if ggsw.dim() == 3 else ggsw.shape[0]
+        """device u32 GGSW(s) [R][k+1][N] or [count][R][k+1][N] -> device NTT-domain GGSW(s) (torch int64 tensor)."""
+        p = self.params
+        one = (p.R, p.k + 1, p.N)
+        _check_u32("prepare_ggsw_device", "ggsw", ggsw, True, one if len(ggsw.shape) == 3 else (None,) + one)
+        count = 1 if ggsw.dim() == 3 else int(ggsw.shape[0])
         if out is None:
+            import torch
             out = torch.empty((count, self.prepared_ggsw_words()), dtype=torch.int64, device=ggsw.device)
-        self._check(lib().tfhe_prepare_ggsw_device(self._h, _dp(ggsw), C.c_size_t(count),
-                                                   C.c_void_p(out.data_ptr())))
+        else:
+            self._check_prepared(out, (count,), "prepare_ggsw_device: out")
+        self._call("tfhe_prepare_ggsw", True, _ptr(ggsw), C.c_size_t(count), _ptr(out, 8))
         return out
 
     def external_product_prepared(self, ggsw_prepared, glwe, out=None):
-        import torch
-        self._bind_torch()
         p = self.params
-        batch = glwe.shape[0]
-        count = ggsw_prepared.shape[0]
-        if out is None:
-            out = torch.empty_like(glwe)
-        self._check(lib().tfhe_external_product_prepared_device(
-            self._h, C.c_void_p(ggsw_prepared.data_ptr()), C.c_size_t(count), _dp(glwe),
-            C.c_size_t(batch), _dp(out)))
+        _check_u32("external_product_prepared", "glwe", glwe, True, (None, p.k + 1, p.N))
+        batch = int(glwe.shape[0])
+        self._check_prepared(ggsw_prepared, (1, batch), "external_product_prepared")
+        out = _result("external_product_prepared", True, out, (batch, p.k + 1, p.N), glwe)
+        self._call("tfhe_external_product_prepared", True, _ptr(ggsw_prepared, 8), C.c_size_t(ggsw_prepared.shape[0]),
+                   _ptr(glwe), C.c_size_t(batch), _ptr(out))
         return out
 
     def cmux(self, ggsw, ct0, ct1):
@@ -1041,33 +995,46 @@ class Context:
         gg = _np(ggsw)
         count = 1 if gg.ndim == 3 else gg.shape[0]
         res = np.zeros_like(c0)
-        self._check(lib().tfhe_cmux_batch(self._h, _hp(gg), C.c_size_t(count), _hp(c0), _hp(c1),
-                                          C.c_size_t(c0.shape[0]), _hp(res)))
+        self._check(lib().tfhe_cmux_batch(self._h, _ptr(gg), C.c_size_t(count), _ptr(c0), _ptr(c1),
+                                          C.c_size_t(c0.shape[0]), _ptr(res)))
         return res, c1
 
     # -- CMUX tree / encrypted table lookup (include/tfhe_hip.h states the operations) ---------------------------
     def cmux_prepared(self, ggsw_prepared, ct0, ct1, out=None):
         """ct0 + external_product(ggsw, ct1 - ct0) on the device with prepared GGSW(s) [1 or batch][words] (int64);
         ct0 / ct1 [batch][k+1][N] device tensors, left intact."""
-        self._bind_torch()
         p = self.params
         if tuple(ct0.shape) != tuple(ct1.shape) or ct0.dim() != 3 or tuple(ct0.shape[1:]) != (p.k + 1, p.N):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"cmux_prepared: ct0 / ct1 [batch][k+1][N] expected, got "
-                                                       f"{tuple(ct0.shape)} and {tuple(ct1.shape)}")
+            raise _invalid(f"cmux_prepared: ct0 / ct1 [batch][k+1][N] expected, got "
+                           f"{tuple(ct0.shape)} and {tuple(ct1.shape)}")
         self._check_prepared(ggsw_prepared, (1, ct0.shape[0]), "cmux_prepared")
-        out = self._lookup_out("cmux_prepared", out, tuple(ct0.shape), ct0)
-        self._check(lib().tfhe_cmux_prepared_device(self._h, C.c_void_p(ggsw_prepared.data_ptr()),
-                                                    C.c_size_t(ggsw_prepared.shape[0]), _dp(ct0), _dp(ct1),
-                                                    C.c_size_t(ct0.shape[0]), _dp(out)))
+        _check_u32("cmux_prepared", "ct0", ct0, True)
+        _check_u32("cmux_prepared", "ct1", ct1, True, like=ct0)
+        out = _result("cmux_prepared", True, out, None, ct0)
+        self._call("tfhe_cmux_prepared", True, _ptr(ggsw_prepared, 8), C.c_size_t(ggsw_prepared.shape[0]), _ptr(ct0),
+                   _ptr(ct1), C.c_size_t(ct0.shape[0]), _ptr(out))
         return out
 
     def _check_prepared(self, prepared, counts, what: str):
         """the ABI reads prepared_ggsw_words() 8-byte words per GGSW: a wrong shape would be read out of bounds"""
         if (not _is_torch(prepared) or prepared.dim() != 2 or prepared.element_size() != 8 or not prepared.is_contiguous()
                 or prepared.shape[0] not in counts or prepared.shape[1] != self.prepared_ggsw_words()):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT,
-                            f"{what}: prepared GGSWs [{' or '.join(str(c) for c in counts)}][{self.prepared_ggsw_words()}] "
-                            f"of 8-byte words expected (prepare_ggsw_device)")
+            raise _invalid(f"{what}: prepared GGSWs [{' or '.join(str(c) for c in counts)}][{self.prepared_ggsw_words()}] "
+                           f"of 8-byte words expected (prepare_ggsw_device)")
+
+    def _selectors(self, what, selectors, dev, dims="[queries][depth]", text=None):
+        """Selectors are GGSWs, one per (query, address or input bit): prepared (prepare_ggsw_device) [..][..][words],
+        contiguous int64 on the device, in a device form; raw [..][..][R][k+1][N] in a host form.  -> the two leading
+        dimensions"""
+        p = self.params
+        if dev:
+            words = self.prepared_ggsw_words()
+            if selectors.dim() != 3 or selectors.element_size() != 8 or selectors.shape[2] != words \
+                    or not selectors.is_contiguous() or not selectors.is_cuda:
+                raise _invalid(text or f"{what}: prepared selectors {dims}[{words}] (contiguous int64, on the device) expected")
+        elif selectors.ndim != 5 or tuple(selectors.shape[2:]) != (p.R, p.k + 1, p.N):
+            raise _invalid(f"{what}: raw selectors {dims}[R][k+1][N] expected, got {tuple(selectors.shape)}")
+        return int(selectors.shape[0]), int(selectors.shape[1])
 
     def reserve_lookup(self, max_trees: int, max_tree_depth: int = 0, max_lookup_bits: int = 0):
         """size the workspace of the device forms for cmux_tree calls of up to max_tree_depth levels and table_lookup
@@ -1087,85 +1054,40 @@ class Context:
                                                  C.byref(launches)))
         return {"subtree_height": height.value, "launches": launches.value}
 
-    def _lookup_shapes(self, what, selectors, data, entry_shape):
-        """-> (queries, depth, sets, tables) after checking selectors [queries][depth][..] against data
-        [sets][tables][2^depth] + entry_shape"""
-        p = self.params
-        if _is_torch(selectors):
-            if selectors.dim() != 3 or selectors.element_size() != 8 or selectors.shape[2] != self.prepared_ggsw_words() \
-                    or not selectors.is_contiguous() or not selectors.is_cuda:
-                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: prepared selectors [queries][depth]"
-                                                           f"[{self.prepared_ggsw_words()}] (contiguous int64, on the device) expected")
-            # the ABI reads 4-byte words: an int64 table of the right shape would be read as pairs of words
-            if data.element_size() != 4 or data.is_floating_point() or not data.is_contiguous() or data.device != selectors.device:
-                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: data must be a contiguous 32-bit integer tensor on the "
-                                                           f"selectors' device, got {data.dtype} on {data.device}")
-        elif selectors.ndim != 5 or tuple(selectors.shape[2:]) != (p.R, p.k + 1, p.N):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: raw selectors [queries][depth][R][k+1][N] expected, got "
-                                                       f"{tuple(selectors.shape)}")
-        queries, depth = int(selectors.shape[0]), int(selectors.shape[1])
-        nd = 3 + len(entry_shape)
-        if len(data.shape) != nd or int(data.shape[0]) not in (1, queries) or depth >= 40 \
+    def _lookup(self, entry, what, names, selectors, data, entry_shape, out_shape, out):
+        """selectors [queries][depth][..] over data [1 or queries][tables][2^depth] + entry_shape ->
+        [queries][tables] + out_shape"""
+        dev = _same_kind(what, names, (selectors, data))
+        if not dev:
+            selectors, data = _np(selectors), _np(data)
+        queries, depth = self._selectors(what, selectors, dev)
+        # the ABI reads 4-byte words: an int64 table of the right shape would be read as pairs of words
+        if dev:
+            _check_u32(what, "data", data, dev, like=selectors, text=f"{what}: data must be a contiguous 32-bit integer tensor on "
+                                                                     f"the selectors' device, got {data.dtype} on {data.device}")
+        if len(data.shape) != 3 + len(entry_shape) or int(data.shape[0]) not in (1, queries) or depth >= 40 \
                 or int(data.shape[2]) != 1 << depth or tuple(data.shape[3:]) != tuple(entry_shape):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT,
-                            f"{what}: data [1 or {queries}][tables][2^{depth}]{list(entry_shape)} expected, got {tuple(data.shape)}")
-        return queries, depth, int(data.shape[0]), int(data.shape[1])
-
-    def _lookup_out(self, what, out, shape, like):
-        """the caller's output tensor, or a new one: the ABI writes prod(shape) 4-byte words"""
-        import torch
-        if out is None:
-            return torch.empty(shape, dtype=like.dtype, device=like.device)
-        if not _is_torch(out) or tuple(out.shape) != tuple(shape) or out.element_size() != 4 or out.is_floating_point() \
-                or not out.is_contiguous() or out.device != like.device:
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: out must be a contiguous 32-bit integer tensor {list(shape)} "
-                                                       f"on {like.device}")
-        return out
+            raise _invalid(f"{what}: data [1 or {queries}][tables][2^{depth}]{list(entry_shape)} expected, got {tuple(data.shape)}")
+        sets, tables = int(data.shape[0]), int(data.shape[1])
+        res = _result(what, dev, out, (queries, tables) + out_shape, data)
+        self._call(entry, dev, _ptr(selectors, 8), C.c_size_t(queries), C.c_size_t(depth), _ptr(data), C.c_size_t(sets),
+                   C.c_size_t(tables), _ptr(res))
+        return res
 
     def cmux_tree(self, selectors, leaves, out=None):
         """Tree(C_0 .. C_{d-1}; leaves): selector i is address bit i and the result is leaf sum_i b_i 2^i.
         numpy: raw selectors [queries][depth][R][k+1][N] and leaves [1 or queries][tables][2^depth][k+1][N] (host
         form, blocks).  torch: prepared selectors [queries][depth][words] (prepare_ggsw_device) and device leaves, in
         the workspace of reserve_lookup.  -> [queries][tables][k+1][N]"""
-        p = self.params
-        if _is_torch(selectors) != _is_torch(leaves):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "cmux_tree: selectors and leaves must both be numpy or both torch")
-        if not _is_torch(selectors):
-            selectors, leaves = _np(selectors), _np(leaves)
-        queries, depth, sets, tables = self._lookup_shapes("cmux_tree", selectors, leaves, (p.k + 1, p.N))
-        if _is_torch(selectors):
-            self._bind_torch()
-            out = self._lookup_out("cmux_tree", out, (queries, tables, p.k + 1, p.N), leaves)
-            self._check(lib().tfhe_cmux_tree_device(self._h, C.c_void_p(selectors.data_ptr()), C.c_size_t(queries),
-                                                    C.c_size_t(depth), _dp(leaves), C.c_size_t(sets), C.c_size_t(tables),
-                                                    _dp(out)))
-            return out
-        res = np.zeros((queries, tables, p.k + 1, p.N), dtype=np.uint32)
-        self._check(lib().tfhe_cmux_tree(self._h, _hp(selectors), C.c_size_t(queries), C.c_size_t(depth), _hp(leaves),
-                                         C.c_size_t(sets), C.c_size_t(tables), _hp(res)))
-        return res
+        glwe = (self.params.k + 1, self.params.N)
+        return self._lookup("tfhe_cmux_tree", "cmux_tree", "selectors and leaves", selectors, leaves, glwe, glwe, out)
 
     def table_lookup(self, selectors, table, out=None):
         """Encrypted lookup of T[address] in clear tables [1 or queries][tables][2^depth] of un-encoded values
         < 2^log_p; selectors as for cmux_tree (address bit i = selector i).  -> LWE [queries][tables][k N + 1] under
         the flattened GLWE key, phase encode(T[a]) + noise (key_switch brings it to dimension n)."""
-        p = self.params
-        if _is_torch(selectors) != _is_torch(table):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "table_lookup: selectors and table must both be numpy or both torch")
-        if not _is_torch(selectors):
-            selectors, table = _np(selectors), _np(table)
-        queries, depth, sets, tables = self._lookup_shapes("table_lookup", selectors, table, ())
-        if _is_torch(selectors):
-            self._bind_torch()
-            out = self._lookup_out("table_lookup", out, (queries, tables, p.big_n + 1), table)
-            self._check(lib().tfhe_table_lookup_device(self._h, C.c_void_p(selectors.data_ptr()), C.c_size_t(queries),
-                                                       C.c_size_t(depth), _dp(table), C.c_size_t(sets), C.c_size_t(tables),
-                                                       _dp(out)))
-            return out
-        res = np.zeros((queries, tables, p.big_n + 1), dtype=np.uint32)
-        self._check(lib().tfhe_table_lookup(self._h, _hp(selectors), C.c_size_t(queries), C.c_size_t(depth), _hp(table),
-                                            C.c_size_t(sets), C.c_size_t(tables), _hp(res)))
-        return res
+        return self._lookup("tfhe_table_lookup", "table_lookup", "selectors and table", selectors, table, (),
+                            (self.params.big_n + 1,), out)
 
     # -- DEMUX tree / encrypted table update (include/tfhe_hip.h states the operations) ---------------------------
     def reserve_demux(self, max_trees: int, max_tree_depth: int = 0, max_write_bits: int = 0):
@@ -1186,37 +1108,34 @@ class Context:
                                                 C.byref(launches)))
         return {"subtree_height": height.value, "launches": launches.value}
 
-    def _demux_shapes(self, what, selectors, glwe, out, accumulate, max_depth, tree_levels):
-        """-> (queries, depth, values, sets) after checking selectors [queries][depth][..], glwe [queries][values][k+1][N]
-        and (if given) out [1 or queries][values][2^tree_levels(depth)][k+1][N]"""
+    def _demux_args(self, what, names, selectors, glwe, out, host_out, accumulate, max_depth, tree_levels):
+        """-> (selectors, glwe, queries, depth, values, sets, on the device?) after checking selectors
+        [queries][depth][..], glwe [queries][values][k+1][N] and (if given) out [1 or queries][values][2^tree_levels(depth)]
+        [k+1][N], which a host form updates in place"""
         p = self.params
-        if _is_torch(selectors):
-            if selectors.dim() != 3 or selectors.element_size() != 8 or selectors.shape[2] != self.prepared_ggsw_words() \
-                    or not selectors.is_contiguous() or not selectors.is_cuda:
-                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: prepared selectors [queries][depth]"
-                                                           f"[{self.prepared_ggsw_words()}] (contiguous int64, on the device) expected")
-            for t in (glwe, out):
-                if t is not None and (not _is_torch(t) or t.element_size() != 4 or t.is_floating_point() or not t.is_contiguous()
-                                      or t.device != selectors.device):
-                    raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: inputs and outputs must be contiguous 32-bit integer "
-                                                               f"tensors on the selectors' device")
-        elif selectors.ndim != 5 or tuple(selectors.shape[2:]) != (p.R, p.k + 1, p.N):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: raw selectors [queries][depth][R][k+1][N] expected, got "
-                                                       f"{tuple(selectors.shape)}")
-        queries, depth = int(selectors.shape[0]), int(selectors.shape[1])
+        dev = _same_kind(what, names, (selectors, glwe, out), "all")
+        if not dev:
+            selectors, glwe = _np(selectors), _np(glwe)
+            if out is not None and (not isinstance(out, np.ndarray) or out.dtype != np.uint32 or not out.flags.c_contiguous):
+                raise _invalid(f"{what}: {host_out}")
+        queries, depth = self._selectors(what, selectors, dev)
+        for t in (glwe, out):
+            if dev and t is not None:
+                _check_u32(what, "data", t, dev, like=selectors, text=f"{what}: inputs and outputs must be contiguous 32-bit "
+                                                                      f"integer tensors on the selectors' device")
         if depth < 1 or depth > max_depth:
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: depth must be in [1, {max_depth}]")
+            raise _invalid(f"{what}: depth must be in [1, {max_depth}]")
         if len(glwe.shape) != 4 or int(glwe.shape[0]) != queries or tuple(glwe.shape[2:]) != (p.k + 1, p.N):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: GLWEs [{queries}][values][k+1][N] expected, got {tuple(glwe.shape)}")
+            raise _invalid(f"{what}: GLWEs [{queries}][values][k+1][N] expected, got {tuple(glwe.shape)}")
         values = int(glwe.shape[1])
         if out is None:
             if accumulate:
-                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: accumulate adds into `out`, which must be given")
-            return queries, depth, values, queries
+                raise _invalid(f"{what}: accumulate adds into `out`, which must be given")
+            return selectors, glwe, queries, depth, values, queries, dev
         want = (values, 1 << tree_levels(depth), p.k + 1, p.N)
         if len(out.shape) != 5 or int(out.shape[0]) not in (1, queries) or tuple(out.shape[1:]) != want:
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: out [1 or {queries}]{list(want)} expected, got {tuple(out.shape)}")
-        return queries, depth, values, int(out.shape[0])
+            raise _invalid(f"{what}: out [1 or {queries}]{list(want)} expected, got {tuple(out.shape)}")
+        return selectors, glwe, queries, depth, values, int(out.shape[0]), dev
 
     def demux_tree(self, selectors, glwe, out=None, accumulate: bool = False):
         """Demux(C_0 .. C_{d-1}; x): leaf sum_i b_i 2^i carries x, every other leaf an encryption of 0 -- the transpose of
@@ -1224,26 +1143,14 @@ class Context:
         accumulate=False stores into per-query sets (`out` optional); accumulate=True adds into `out` as it stands, one
         set per query or one shared by all (a scatter-add).  numpy: raw selectors, host form, `out` is updated in place
         and returned.  torch: prepared selectors and device tensors in the workspace of reserve_demux."""
-        if _is_torch(selectors) != _is_torch(glwe) or (out is not None and _is_torch(out) != _is_torch(glwe)):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "demux_tree: selectors, glwe and out must all be numpy or all torch")
         p = self.params
-        if not _is_torch(selectors):
-            selectors, glwe = _np(selectors), _np(glwe)
-            if out is not None and (not isinstance(out, np.ndarray) or out.dtype != np.uint32 or not out.flags.c_contiguous):
-                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "demux_tree: out must be a C-contiguous uint32 array")
-        queries, depth, values, sets = self._demux_shapes("demux_tree", selectors, glwe, out, accumulate, 20, lambda d: d)
-        shape = (sets, values, 1 << depth, p.k + 1, p.N)
-        if _is_torch(selectors):
-            self._bind_torch()
-            out = self._lookup_out("demux_tree", out, shape, glwe)
-            self._check(lib().tfhe_demux_tree_device(self._h, C.c_void_p(selectors.data_ptr()), C.c_size_t(queries),
-                                                     C.c_size_t(depth), _dp(glwe), C.c_size_t(values), _dp(out),
-                                                     C.c_size_t(sets), C.c_int(int(bool(accumulate)))))
-            return out
-        if out is None:
-            out = np.zeros(shape, dtype=np.uint32)
-        self._check(lib().tfhe_demux_tree(self._h, _hp(selectors), C.c_size_t(queries), C.c_size_t(depth), _hp(glwe),
-                                          C.c_size_t(values), _hp(out), C.c_size_t(sets), C.c_int(int(bool(accumulate)))))
+        selectors, glwe, queries, depth, values, sets, dev = self._demux_args(
+            "demux_tree", "selectors, glwe and out", selectors, glwe, out, "out must be a C-contiguous uint32 array",
+            accumulate, 20, lambda d: d)
+        if dev or out is None:   # the host form writes into the caller's array
+            out = _result("demux_tree", dev, out, (sets, values, 1 << depth, p.k + 1, p.N), glwe)
+        self._call("tfhe_demux_tree", dev, _ptr(selectors, 8), C.c_size_t(queries), C.c_size_t(depth), _ptr(glwe),
+                   C.c_size_t(values), _ptr(out), C.c_size_t(sets), C.c_int(int(bool(accumulate))))
         return out
 
     def table_write(self, selectors, values, table):
@@ -1252,23 +1159,13 @@ class Context:
         table [1 or queries][tables][2^d_hi][k+1][N] holds 2^d_lo = min(2^depth, N) entries per GLWE (the layout of
         table_lookup's leaves) and is updated in place and returned.  The write ADDS: to replace an entry write
         new - old, old read with table_lookup_glwe and packed with per_group = 1.  Selectors as for table_lookup."""
-        if _is_torch(selectors) != _is_torch(values) or _is_torch(table) != _is_torch(values):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "table_write: selectors, values and table must all be numpy or all torch")
         p = self.params
-        if not _is_torch(selectors):
-            selectors, values = _np(selectors), _np(values)
-            if not isinstance(table, np.ndarray) or table.dtype != np.uint32 or not table.flags.c_contiguous:
-                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "table_write: table must be a C-contiguous uint32 array (updated in place)")
-        queries, depth, tables, sets = self._demux_shapes("table_write", selectors, values, table, True, p.glwe_poly_degree + 20,
-                                                          lambda d: d - min(d, p.glwe_poly_degree))
-        if _is_torch(selectors):
-            self._bind_torch()
-            self._check(lib().tfhe_table_write_device(self._h, C.c_void_p(selectors.data_ptr()), C.c_size_t(queries),
-                                                      C.c_size_t(depth), _dp(values), _dp(table), C.c_size_t(sets),
-                                                      C.c_size_t(tables)))
-            return table
-        self._check(lib().tfhe_table_write(self._h, _hp(selectors), C.c_size_t(queries), C.c_size_t(depth), _hp(values),
-                                           _hp(table), C.c_size_t(sets), C.c_size_t(tables)))
+        selectors, values, queries, depth, tables, sets, dev = self._demux_args(
+            "table_write", "selectors, values and table", selectors, values, table,
+            "table must be a C-contiguous uint32 array (updated in place)", True, p.glwe_poly_degree + 20,
+            lambda d: d - min(d, p.glwe_poly_degree))
+        self._call("tfhe_table_write", dev, _ptr(selectors, 8), C.c_size_t(queries), C.c_size_t(depth), _ptr(values),
+                   _ptr(table), C.c_size_t(sets), C.c_size_t(tables))
         return table
 
     def table_lookup_glwe(self, selectors, leaves, out=None):
@@ -1276,37 +1173,24 @@ class Context:
         of a clear table: the tree over address bits log2 N and up, the rotation chain, the sample extraction.
         -> LWE [queries][tables][k N + 1].  torch: in the workspace of reserve_lookup (max_lookup_bits)."""
         p = self.params
-        if _is_torch(selectors) != _is_torch(leaves):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "table_lookup_glwe: selectors and leaves must both be numpy or both torch")
-        if not _is_torch(selectors):
+        dev = _same_kind("table_lookup_glwe", "selectors and leaves", (selectors, leaves))
+        if not dev:
             selectors, leaves = _np(selectors), _np(leaves)
         depth = int(selectors.shape[1]) if len(selectors.shape) > 1 else 0
         d_hi = depth - min(depth, p.glwe_poly_degree)
         if len(leaves.shape) != 5 or depth < 1 or depth > p.glwe_poly_degree + 20 or int(leaves.shape[2]) != 1 << d_hi:
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"table_lookup_glwe: leaves [1 or queries][tables][2^{d_hi}][k+1][N] "
-                                                       f"expected for {depth} address bits, got {tuple(leaves.shape)}")
+            raise _invalid(f"table_lookup_glwe: leaves [1 or queries][tables][2^{d_hi}][k+1][N] "
+                           f"expected for {depth} address bits, got {tuple(leaves.shape)}")
         queries, sets, tables = int(selectors.shape[0]), int(leaves.shape[0]), int(leaves.shape[1])
         if sets not in (1, queries) or tuple(leaves.shape[3:]) != (p.k + 1, p.N):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"table_lookup_glwe: leaves [1 or {queries}][tables][2^{d_hi}][k+1][N] "
-                                                       f"expected, got {tuple(leaves.shape)}")
-        if _is_torch(selectors):
-            self._bind_torch()
-            if selectors.dim() != 3 or selectors.element_size() != 8 or selectors.shape[2] != self.prepared_ggsw_words() \
-                    or not selectors.is_contiguous() or not selectors.is_cuda or leaves.element_size() != 4 \
-                    or leaves.is_floating_point() or not leaves.is_contiguous() or leaves.device != selectors.device:
-                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "table_lookup_glwe: prepared selectors [queries][depth][words] (int64) "
-                                                           "and contiguous 32-bit leaves on one device expected")
-            out = self._lookup_out("table_lookup_glwe", out, (queries, tables, p.big_n + 1), leaves)
-            self._check(lib().tfhe_table_lookup_glwe_device(self._h, C.c_void_p(selectors.data_ptr()), C.c_size_t(queries),
-                                                            C.c_size_t(depth), _dp(leaves), C.c_size_t(sets),
-                                                            C.c_size_t(tables), _dp(out)))
-            return out
-        if selectors.ndim != 5 or tuple(selectors.shape[2:]) != (p.R, p.k + 1, p.N):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"table_lookup_glwe: raw selectors [queries][depth][R][k+1][N] expected, "
-                                                       f"got {tuple(selectors.shape)}")
-        res = np.zeros((queries, tables, p.big_n + 1), dtype=np.uint32)
-        self._check(lib().tfhe_table_lookup_glwe(self._h, _hp(selectors), C.c_size_t(queries), C.c_size_t(depth), _hp(leaves),
-                                                 C.c_size_t(sets), C.c_size_t(tables), _hp(res)))
+            raise _invalid(f"table_lookup_glwe: leaves [1 or {queries}][tables][2^{d_hi}][k+1][N] "
+                           f"expected, got {tuple(leaves.shape)}")
+        text = "table_lookup_glwe: prepared selectors [queries][depth][words] (int64) and contiguous 32-bit leaves on one device expected"
+        self._selectors("table_lookup_glwe", selectors, dev, text=text)
+        _check_u32("table_lookup_glwe", "leaves", leaves, dev, like=selectors if dev else None, text=text)
+        res = _result("table_lookup_glwe", dev, out, (queries, tables, p.big_n + 1), leaves)
+        self._call("tfhe_table_lookup_glwe", dev, _ptr(selectors, 8), C.c_size_t(queries), C.c_size_t(depth), _ptr(leaves),
+                   C.c_size_t(sets), C.c_size_t(tables), _ptr(res))
         return res
 
     # -- encrypted branching programs (include/tfhe_hip.h states the operations; branching.py builds programs) ------
@@ -1342,51 +1226,28 @@ class Context:
         nodes, host_terminals, outputs = program.arrays() if hasattr(program, "arrays") else program
         nodes, host_terminals, outputs = _np(nodes).reshape(-1, 4), _np(host_terminals), _np(outputs).reshape(-1)
         if host_terminals.ndim != 2 or host_terminals.shape[1] != p.N:
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"cmux_program: terminals [n_terminals][{p.N}] expected, got "
-                                                       f"{tuple(host_terminals.shape)}")
+            raise _invalid(f"cmux_program: terminals [n_terminals][{p.N}] expected, got {tuple(host_terminals.shape)}")
         if want not in ("lwe", "glwe", "both"):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, 'cmux_program: want must be "lwe", "glwe" or "both"')
-        on_device = _is_torch(selectors)
-        if on_device:
-            if selectors.dim() != 3 or selectors.element_size() != 8 or selectors.shape[2] != self.prepared_ggsw_words() \
-                    or not selectors.is_contiguous() or not selectors.is_cuda:
-                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"cmux_program: prepared selectors [sets][n_inputs]"
-                                                           f"[{self.prepared_ggsw_words()}] (contiguous int64, on the device) expected")
-        else:
+            raise _invalid('cmux_program: want must be "lwe", "glwe" or "both"')
+        dev = _is_torch(selectors)
+        if not dev:
             selectors = _np(selectors)
-            if selectors.ndim != 5 or tuple(selectors.shape[2:]) != (p.R, p.k + 1, p.N):
-                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"cmux_program: raw selectors [sets][n_inputs][R][k+1][N] expected, "
-                                                           f"got {tuple(selectors.shape)}")
-        sets, n_inputs = int(selectors.shape[0]), int(selectors.shape[1])
+        sets, n_inputs = self._selectors("cmux_program", selectors, dev, "[sets][n_inputs]")
         queries = sets if queries is None else int(queries)
         n_out = outputs.size
-        shapes = {"glwe": (queries, n_out, p.k + 1, p.N), "lwe": (queries, n_out, p.big_n + 1)}
-        args = (C.c_size_t(queries), C.c_size_t(n_inputs), C.c_size_t(sets), C.c_void_p(nodes.ctypes.data),
-                C.c_size_t(nodes.shape[0]))
-        tail = (C.c_size_t(host_terminals.shape[0]), _hp(outputs), C.c_size_t(n_out))
-        if on_device:
+        if not dev:
+            terminals = host_terminals
+        elif terminals is None:   # the upload synchronises
             import torch
-            self._bind_torch()
-            if terminals is None:
-                terminals = torch.from_numpy(host_terminals.view(np.int32)).to(selectors.device)
-            elif not _is_torch(terminals) or tuple(terminals.shape) != host_terminals.shape or terminals.element_size() != 4 \
-                    or terminals.is_floating_point() or not terminals.is_contiguous() or terminals.device != selectors.device:
-                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"cmux_program: device terminals must be a contiguous 32-bit integer "
-                                                           f"tensor {list(host_terminals.shape)} on {selectors.device}")
-            given = {"lwe": out, "glwe": out}[want] if want != "both" else None
-            outs = {}
-            for which in ("glwe", "lwe"):
-                if want in (which, "both"):
-                    o = out[("glwe", "lwe").index(which)] if want == "both" and out is not None else given
-                    outs[which] = self._lookup_out("cmux_program", o, shapes[which], terminals)
-            self._check(lib().tfhe_cmux_program_device(self._h, C.c_void_p(selectors.data_ptr()), *args, _dp(terminals), *tail,
-                                                       _dp(outs["glwe"]) if "glwe" in outs else None,
-                                                       _dp(outs["lwe"]) if "lwe" in outs else None))
+            terminals = torch.from_numpy(host_terminals.view(np.int32)).to(selectors.device)
         else:
-            outs = {w: np.zeros(shapes[w], dtype=np.uint32) for w in ("glwe", "lwe") if want in (w, "both")}
-            self._check(lib().tfhe_cmux_program(self._h, _hp(selectors), *args, _hp(host_terminals), *tail,
-                                                _hp(outs["glwe"]) if "glwe" in outs else None,
-                                                _hp(outs["lwe"]) if "lwe" in outs else None))
+            _check_u32("cmux_program", "device terminals", terminals, dev, host_terminals.shape, selectors)
+        given = {"glwe": out, "lwe": out} if want != "both" or out is None else {"glwe": out[0], "lwe": out[1]}
+        shapes = {"glwe": (queries, n_out, p.k + 1, p.N), "lwe": (queries, n_out, p.big_n + 1)}
+        outs = {w: _result("cmux_program", dev, given[w], shapes[w], terminals) for w in ("glwe", "lwe") if want in (w, "both")}
+        self._call("tfhe_cmux_program", dev, _ptr(selectors, 8), C.c_size_t(queries), C.c_size_t(n_inputs), C.c_size_t(sets),
+                   C.c_void_p(nodes.ctypes.data), C.c_size_t(nodes.shape[0]), _ptr(terminals),
+                   C.c_size_t(host_terminals.shape[0]), _ptr(outputs), C.c_size_t(n_out), _ptr(outs.get("glwe")), _ptr(outs.get("lwe")))
         return (outs["glwe"], outs["lwe"]) if want == "both" else outs[want]
 
     # -- small ops ------------------------------------------------------------------------------
@@ -1394,21 +1255,21 @@ class Context:
         v = _np(values).ravel()
         d = self.params.pbs_decomposer if which == DECOMPOSER_PBS else self.params.ks_decomposer
         res = np.zeros((v.size, d.levels), dtype=np.uint32)
-        self._check(lib().tfhe_decompose(self._h, C.c_int(which), _hp(v), C.c_size_t(v.size), _hp(res)))
+        self._check(lib().tfhe_decompose(self._h, C.c_int(which), _ptr(v), C.c_size_t(v.size), _ptr(res)))
         return res
 
     def decompose_glwe(self, glwe) -> np.ndarray:
         p = self.params
         g = _np(glwe).reshape(-1, p.k + 1, p.N)
         res = np.zeros((g.shape[0], p.R, p.N), dtype=np.uint32)
-        self._check(lib().tfhe_decompose_glwe_batch(self._h, _hp(g), C.c_size_t(g.shape[0]), _hp(res)))
+        self._check(lib().tfhe_decompose_glwe_batch(self._h, _ptr(g), C.c_size_t(g.shape[0]), _ptr(res)))
         return res
 
     def switch_modulus(self, values, log_from: int, log_to: int) -> np.ndarray:
         v = _np(values).ravel()
         res = np.zeros_like(v)
-        self._check(lib().tfhe_switch_modulus(self._h, _hp(v), C.c_size_t(v.size), C.c_uint32(log_from),
-                                              C.c_uint32(log_to), _hp(res)))
+        self._check(lib().tfhe_switch_modulus(self._h, _ptr(v), C.c_size_t(v.size), C.c_uint32(log_from),
+                                              C.c_uint32(log_to), _ptr(res)))
         return res
 
     def glwe_mul_monomial(self, glwe, monomial_index) -> np.ndarray:
@@ -1416,30 +1277,31 @@ class Context:
         g = _np(glwe).reshape(-1, p.k + 1, p.N)
         idx = np.ascontiguousarray(np.broadcast_to(np.asarray(monomial_index, dtype=np.int64), (g.shape[0],)))
         res = np.zeros_like(g)
-        self._check(lib().tfhe_glwe_mul_monomial_batch(self._h, _hp(g), C.c_size_t(g.shape[0]),
-                                                       idx.ctypes.data_as(C.POINTER(C.c_int64)), _hp(res)))
+        self._check(lib().tfhe_glwe_mul_monomial_batch(self._h, _ptr(g), C.c_size_t(g.shape[0]),
+                                                       idx.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(res)))
         return res
+
+    def _words(self, what, name, x, width, like=None):
+        """-> (x, on the device?, rows): x of any shape that holds whole rows of `width` words (as many words as `like`)"""
+        dev = _is_torch(x if like is None else like)
+        if not dev:
+            x = _np(x)
+        _check_u32(what, name, x, dev, None, like if dev else None)
+        size = x.numel() if dev else x.size
+        if size % width or (like is not None and size != (like.numel() if dev else like.size)):
+            raise _invalid(f"{what}: {name} of {width} words per ciphertext{'' if like is None else ', as many as its partner,'} "
+                           f"expected, got {tuple(x.shape)}")
+        return x, dev, size // width
 
     def lwe_linear(self, c0: int, ct0, c1: int = 0, ct1=None, out=None):
         """c0*ct0 + c1*ct1 (wrapping): LweCiphertext Add / Mul<u32>, lwe.rs:9-23."""
-        if _is_torch(ct0):
-            self._bind_torch()
-            import torch
-            if out is None:
-                out = torch.empty_like(ct0)
-            width = ct0.shape[-1]
-            self._check(lib().tfhe_lwe_linear_batch_device(
-                self._h, C.c_uint32(c0 & 0xFFFFFFFF), _dp(ct0), C.c_uint32(c1 & 0xFFFFFFFF),
-                _dp(ct1) if ct1 is not None else None, C.c_size_t(ct0.numel() // width), C.c_size_t(width), _dp(out)))
-            return out
-        a = _np(ct0)
-        rows = a.reshape(-1, a.shape[-1])
-        b = _np(ct1).reshape(rows.shape) if ct1 is not None else None
-        res = np.zeros_like(rows)
-        self._check(lib().tfhe_lwe_linear_batch(self._h, C.c_uint32(c0 & 0xFFFFFFFF), _hp(rows),
-                                                C.c_uint32(c1 & 0xFFFFFFFF), _hp(b) if b is not None else None,
-                                                C.c_size_t(rows.shape[0]), C.c_size_t(rows.shape[1]), _hp(res)))
-        return res.reshape(a.shape)
+        width = int(ct0.shape[-1]) if _is_torch(ct0) else int(np.shape(ct0)[-1])
+        a, dev, rows = self._words("lwe_linear", "ct0", ct0, width)
+        b = None if ct1 is None else self._words("lwe_linear", "ct1", ct1, width, a)[0]
+        res = _result("lwe_linear", dev, out, None, a)
+        self._call("tfhe_lwe_linear_batch", dev, C.c_uint32(c0 & 0xFFFFFFFF), _ptr(a), C.c_uint32(c1 & 0xFFFFFFFF), _ptr(b),
+                   C.c_size_t(rows), C.c_size_t(width), _ptr(res))
+        return res
 
     # -- encrypted dense layers (include/tfhe_hip.h states the operations; nn.py builds networks) ----------------
     def reserve_dense(self, max_queries: int, max_outputs: int):
@@ -1458,86 +1320,69 @@ class Context:
                                                 C.c_size_t(words_per_ct), C.byref(splits), C.byref(wgs)))
         return {"splits": splits.value, "workgroups": wgs.value}
 
-    def _dense_args(self, what, x, weights, bias, width=None):
-        """-> (x [queries][I][words], W [O][I] int32, bias [O] or None) as numpy arrays or, with x on the device, torch
-        tensors there (host weights / bias are uploaded on every call, which synchronises: pass device tensors in a loop)"""
-        on_device = _is_torch(x)
-        if on_device:
+    @staticmethod
+    def _beside(what, name, a, like, dtype=np.uint32):
+        """`a` for a device form whose other operands are on `like`'s device: a device tensor is checked, host values
+        are uploaded (on every call, which synchronises: pass device tensors in a loop); None stays None"""
+        if a is None:
+            return None
+        if not _is_torch(a):
             import torch
-            if x.dim() == 2:
-                x = x.unsqueeze(0)
-            if x.dim() != 3 or x.element_size() != 4 or x.is_floating_point() or not x.is_contiguous() or not x.is_cuda:
-                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: x [queries][I][words] (contiguous 32-bit integers, on the device) expected")
+            a = torch.from_numpy(np.ascontiguousarray(a, dtype=dtype).view(np.int32)).to(like.device)
+        _check_u32(what, name, a, True, None, like)
+        return a
 
-            def dev(a, dtype, name):
-                if a is None:
-                    return None
-                if not _is_torch(a):
-                    a = torch.from_numpy(np.ascontiguousarray(a, dtype=dtype).view(np.int32)).to(x.device)
-                if a.element_size() != 4 or a.is_floating_point() or not a.is_contiguous() or a.device != x.device:
-                    raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: {name} must be a contiguous 32-bit integer tensor on {x.device}")
-                return a
-            weights, bias = dev(weights, np.int32, "weights"), dev(bias, np.uint32, "bias")
-        else:
+    def _dense_args(self, what, x, weights, bias, width=None):
+        """-> (x [queries][I][words], W [O][I] int32, bias [O] or None, on the device?) as numpy arrays or, with x on the
+        device, torch tensors there"""
+        dev = _is_torch(x)
+        if not dev:
             x = _np(x)
-            if x.ndim == 2:
-                x = x[None]
+        if len(x.shape) == 2:
+            x = _lead(x, dev)
+        if dev:
+            _check_u32(what, "x", x, dev, (None, None, None),
+                       text=f"{what}: x [queries][I][words] (contiguous 32-bit integers, on the device) expected")
+            weights, bias = self._beside(what, "weights", weights, x, np.int32), self._beside(what, "bias", bias, x)
+        else:
             weights = np.ascontiguousarray(weights, dtype=np.int32)
             bias = None if bias is None else _np(bias).reshape(-1)
         if len(x.shape) != 3 or len(weights.shape) != 2 or int(weights.shape[1]) != int(x.shape[1]) or \
                 (width is not None and int(x.shape[2]) != width):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: x [queries][I][{width or 'words'}] and weights [O][I] expected, got "
-                                                       f"{tuple(x.shape)} and {tuple(weights.shape)}")
+            raise _invalid(f"{what}: x [queries][I][{width or 'words'}] and weights [O][I] expected, got "
+                           f"{tuple(x.shape)} and {tuple(weights.shape)}")
         if bias is not None and tuple(bias.shape) != (int(weights.shape[0]),):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"{what}: bias [O] expected, got {tuple(bias.shape)}")
-        return x, weights, bias
+            raise _invalid(f"{what}: bias [O] expected, got {tuple(bias.shape)}")
+        return x, weights, bias, dev
 
     def dense(self, x, weights, bias=None, out=None):
         """Dense(W, bias; x): out[q][o] = sum_i W[o][i] * x[q][i] (+ bias[o], already encoded, on the body), wrapping.
         x [queries][I][words] (or [I][words]: one query), weights [O][I] int32 -> [queries][O][words]; any LWE size.
         numpy: host form, blocks.  torch: on torch's current stream, `out` may name the result tensor."""
-        x, weights, bias = self._dense_args("dense", x, weights, bias)
+        x, weights, bias, dev = self._dense_args("dense", x, weights, bias)
         q, i, words = (int(v) for v in x.shape)
         o = int(weights.shape[0])
-        sizes = (C.c_size_t(q), C.c_size_t(i))
-        if _is_torch(x):
-            self._bind_torch()
-            out = self._lookup_out("dense", out, (q, o, words), x)
-            self._check(lib().tfhe_lwe_dense_batch_device(self._h, _dp(x), *sizes, C.c_void_p(weights.data_ptr()),
-                                                          _dp(bias) if bias is not None else None, C.c_size_t(o),
-                                                          C.c_size_t(words), _dp(out)))
-            return out
-        res = np.zeros((q, o, words), dtype=np.uint32)
-        self._check(lib().tfhe_lwe_dense_batch(self._h, _hp(x), *sizes, C.c_void_p(weights.ctypes.data),
-                                               _hp(bias) if bias is not None else None, C.c_size_t(o), C.c_size_t(words), _hp(res)))
+        res = _result("dense", dev, out, (q, o, words), x)
+        self._call("tfhe_lwe_dense_batch", dev, _ptr(x), C.c_size_t(q), C.c_size_t(i), _ptr(weights), _ptr(bias), C.c_size_t(o),
+                   C.c_size_t(words), _ptr(res))
         return res
 
     def dense_bootstrap(self, x, weights, bias, test_vector_poly, out=None):
         """A whole layer: out[q][o] = bootstrap(Dense(W, bias; x)[q][o]; tv[o mod tv_count]).  x [queries][I][io_dim + 1] at
         the context's boundary dimension, test_vector_poly [N] or [O][N] (un-encoded, as for bootstrap) ->
         [queries][O][io_dim + 1].  numpy: host form, blocks.  torch: in the workspace of reserve_dense, enqueues only."""
-        x, weights, bias = self._dense_args("dense_bootstrap", x, weights, bias, self.io_dim + 1)
+        x, weights, bias, dev = self._dense_args("dense_bootstrap", x, weights, bias, self.io_dim + 1)
         q, i, words = (int(v) for v in x.shape)
         o = int(weights.shape[0])
         tv = test_vector_poly if _is_torch(test_vector_poly) else _np(test_vector_poly)
         n_tv = 1 if len(tv.shape) == 1 else int(tv.shape[0])
         if int(tv.shape[-1]) != self.params.N or len(tv.shape) > 2:
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"dense_bootstrap: test vectors [N] or [O][N] expected, got {tuple(tv.shape)}")
-        sizes = (C.c_size_t(q), C.c_size_t(i))
-        if _is_torch(x):
-            import torch
-            self._bind_torch()
-            if not _is_torch(tv):
-                tv = torch.from_numpy(tv.view(np.int32)).to(x.device)
-            out = self._lookup_out("dense_bootstrap", out, (q, o, words), x)
-            self._check(lib().tfhe_dense_bootstrap_batch_device(self._h, _dp(x), *sizes, C.c_void_p(weights.data_ptr()),
-                                                                _dp(bias) if bias is not None else None, C.c_size_t(o), _dp(tv),
-                                                                C.c_size_t(n_tv), _dp(out)))
-            return out
-        res = np.zeros((q, o, words), dtype=np.uint32)
-        self._check(lib().tfhe_dense_bootstrap_batch(self._h, _hp(x), *sizes, C.c_void_p(weights.ctypes.data),
-                                                     _hp(bias) if bias is not None else None, C.c_size_t(o), _hp(tv),
-                                                     C.c_size_t(n_tv), _hp(res)))
+            raise _invalid(f"dense_bootstrap: test vectors [N] or [O][N] expected, got {tuple(tv.shape)}")
+        if dev:
+            tv = self._beside("dense_bootstrap", "test_vector_poly", tv, x)
+        res = _result("dense_bootstrap", dev, out, (q, o, words), x)
+        self._call("tfhe_dense_bootstrap_batch", dev, _ptr(x), C.c_size_t(q), C.c_size_t(i), _ptr(weights), _ptr(bias),
+                   C.c_size_t(o), _ptr(tv), C.c_size_t(n_tv), _ptr(res))
         return res
 
     # -- encrypted convolutions (include/tfhe_hip.h states the operation; nn.py::Conv2d builds layers) ------------
@@ -1546,10 +1391,9 @@ class Context:
         and the reason where the backend admits no pass at their magnitude.  Synchronises; prepare once, use often."""
         w = np.asarray(weights)
         if w.ndim != 3 or w.size == 0 or int(w.shape[2]) != self.params.N or not np.issubdtype(w.dtype, np.integer):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"prepare_poly_weights: integer weights [O][C][{self.params.N}] expected, got "
-                                                       f"{tuple(w.shape)}")
+            raise _invalid(f"prepare_poly_weights: integer weights [O][C][{self.params.N}] expected, got {tuple(w.shape)}")
         if int(w.max()) >= 1 << 31 or int(w.min()) < -(1 << 31):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "prepare_poly_weights: weights must fit int32")
+            raise _invalid("prepare_poly_weights: weights must fit int32")
         w = np.ascontiguousarray(w, dtype=np.int32)
         handle = C.c_void_p()
         self._check(lib().tfhe_prepare_poly_weights(self._h, C.c_void_p(w.ctypes.data), C.c_size_t(w.shape[0]),
@@ -1576,44 +1420,30 @@ class Context:
     def glwe_conv(self, x, weights: "PolyWeights", bias=None, out=None):
         """Conv(W, bias; x): out[q][o] = sum_c W[o][c](X) * x[q][c] (+ bias[o], already encoded, on the body), negacyclic,
         wrapping.  x [queries][C][k+1][N] (or [C][k+1][N]: one query), bias [O][N] -> [queries][O][k+1][N].
-        numpy: host form, blocks.  torch: in the workspace of reserve_glwe_conv on torch's current stream, enqueues only;
-        `out` may name the result tensor."""
+        numpy: host form, blocks.  torch: in the workspace of reserve_glwe_conv on torch's current stream, enqueues only
+        (a host bias is uploaded on every call, which synchronises); `out` may name the result tensor."""
         p = self.params
         if not isinstance(weights, PolyWeights) or not weights._h:
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "glwe_conv: weights from prepare_poly_weights expected")
+            raise _invalid("glwe_conv: weights from prepare_poly_weights expected")
         info = weights.info()
-        on_device = _is_torch(x)
-        if on_device:
-            import torch
-            if x.dim() == 3:
-                x = x.unsqueeze(0)
-            if x.dim() != 4 or x.element_size() != 4 or x.is_floating_point() or not x.is_contiguous() or not x.is_cuda:
-                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "glwe_conv: x [queries][C][k+1][N] (contiguous 32-bit integers, on the device) expected")
-            if bias is not None and not _is_torch(bias):
-                bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.uint32).view(np.int32)).to(x.device)
-            if bias is not None and (bias.element_size() != 4 or bias.is_floating_point() or not bias.is_contiguous() or bias.device != x.device):
-                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"glwe_conv: bias must be a contiguous 32-bit integer tensor on {x.device}")
-        else:
+        dev = _is_torch(x)
+        if not dev:
             x = _np(x)
-            if x.ndim == 3:
-                x = x[None]
+        if len(x.shape) == 3:
+            x = _lead(x, dev)
+        if dev:
+            _check_u32("glwe_conv", "x", x, dev, (None,) * 4,
+                       text="glwe_conv: x [queries][C][k+1][N] (contiguous 32-bit integers, on the device) expected")
+            bias = self._beside("glwe_conv", "bias", bias, x)
+        else:
             bias = None if bias is None else _np(bias)
         if len(x.shape) != 4 or tuple(int(v) for v in x.shape[1:]) != (info["channels"], p.k + 1, p.N):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"glwe_conv: x [queries][{info['channels']}][{p.k + 1}][{p.N}] expected, got "
-                                                       f"{tuple(x.shape)}")
+            raise _invalid(f"glwe_conv: x [queries][{info['channels']}][{p.k + 1}][{p.N}] expected, got {tuple(x.shape)}")
         if bias is not None and tuple(int(v) for v in bias.shape) != (info["outputs"], p.N):
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"glwe_conv: bias [{info['outputs']}][{p.N}] expected, got {tuple(bias.shape)}")
+            raise _invalid(f"glwe_conv: bias [{info['outputs']}][{p.N}] expected, got {tuple(bias.shape)}")
         q = int(x.shape[0])
-        shape = (q, info["outputs"], p.k + 1, p.N)
-        if on_device:
-            self._bind_torch()
-            out = self._lookup_out("glwe_conv", out, shape, x)
-            self._check(lib().tfhe_glwe_conv_batch_device(self._h, _dp(x), C.c_size_t(q), weights._h,
-                                                          _dp(bias) if bias is not None else None, _dp(out)))
-            return out
-        res = np.zeros(shape, dtype=np.uint32)
-        self._check(lib().tfhe_glwe_conv_batch(self._h, _hp(x), C.c_size_t(q), weights._h, _hp(bias) if bias is not None else None,
-                                               _hp(res)))
+        res = _result("glwe_conv", dev, out, (q, info["outputs"], p.k + 1, p.N), x)
+        self._call("tfhe_glwe_conv_batch", dev, _ptr(x), C.c_size_t(q), weights._h, _ptr(bias), _ptr(res))
         return res
 
     def sample_extract_indices(self, glwe, indices, out=None):
@@ -1621,109 +1451,74 @@ class Context:
         [batch][count][k N + 1].  numpy: host form.  torch: enqueues on torch's current stream (host indices are uploaded
         on every call, which synchronises: pass a device tensor in a loop)."""
         p = self.params
-        if _is_torch(glwe):
-            import torch
-            if glwe.element_size() != 4 or glwe.is_floating_point() or not glwe.is_contiguous() or not glwe.is_cuda or \
-                    tuple(glwe.shape[-2:]) != (p.k + 1, p.N):
-                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "sample_extract_indices: glwe [batch][k+1][N] (contiguous 32-bit integers, on the device) expected")
-            if not _is_torch(indices):
-                idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
-                if idx.size == 0 or int(idx.min()) < 0 or int(idx.max()) >= p.N:
-                    raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "sample_extract_indices: indices in [0, N) expected")
-                indices = torch.from_numpy(idx.astype(np.uint32).view(np.int32)).to(glwe.device)
-            if indices.element_size() != 4 or indices.is_floating_point() or not indices.is_contiguous() or indices.device != glwe.device:
-                raise TfheError(TFHE_ERR_INVALID_ARGUMENT, f"sample_extract_indices: indices must be a contiguous 32-bit integer tensor on {glwe.device}")
-            batch, count = glwe.numel() // ((p.k + 1) * p.N), indices.numel()
-            self._bind_torch()
-            out = self._lookup_out("sample_extract_indices", out, (batch, count, p.big_n + 1), glwe)
-            self._check(lib().tfhe_sample_extract_indices_device(self._h, _dp(glwe), C.c_size_t(batch), _dp(indices),
-                                                                 C.c_size_t(count), _dp(out)))
-            return out
-        g = _np(glwe).reshape(-1, p.k + 1, p.N)
-        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
-        if idx.size == 0 or int(idx.min()) < 0 or int(idx.max()) >= 1 << 32:
-            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "sample_extract_indices: indices in [0, N) expected")
-        idx = idx.astype(np.uint32)
-        res = np.zeros((g.shape[0], idx.size, p.big_n + 1), dtype=np.uint32)
-        self._check(lib().tfhe_sample_extract_indices(self._h, _hp(g), C.c_size_t(g.shape[0]), _hp(idx), C.c_size_t(idx.size),
-                                                      _hp(res)))
+        dev = _is_torch(glwe)
+        if dev:
+            _check_u32("sample_extract_indices", "glwe", glwe, dev, text="sample_extract_indices: glwe [batch][k+1][N] "
+                                                                         "(contiguous 32-bit integers, on the device) expected")
+            if tuple(glwe.shape[-2:]) != (p.k + 1, p.N):
+                raise _invalid("sample_extract_indices: glwe [batch][k+1][N] (contiguous 32-bit integers, on the device) expected")
+            batch = glwe.numel() // ((p.k + 1) * p.N)
+        else:
+            glwe = _np(glwe).reshape(-1, p.k + 1, p.N)
+            batch = glwe.shape[0]
+        if not _is_torch(indices):
+            indices = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+            # a device form uploads the indices unseen by the ABI's host check of them
+            if indices.size == 0 or int(indices.min()) < 0 or int(indices.max()) >= (p.N if dev else 1 << 32):
+                raise _invalid("sample_extract_indices: indices in [0, N) expected")
+            indices = indices.astype(np.uint32)
+        if dev:
+            indices = self._beside("sample_extract_indices", "indices", indices, glwe)
+        count = indices.numel() if dev else indices.size
+        res = _result("sample_extract_indices", dev, out, (batch, count, p.big_n + 1), glwe)
+        self._call("tfhe_sample_extract_indices", dev, _ptr(glwe), C.c_size_t(batch), _ptr(indices), C.c_size_t(count), _ptr(res))
         return res
 
     def lut_gate(self, truth, cts, out=None):
         """Gate of m = len(cts) inputs (notes/Boolean Gates.md:2-11): one PBS of sum_i 2^i * cts[i]
         (cts[0] = rightmost input) with lut[x] = truth[x mod 2^m]; needs log_p >= m."""
-        p = self.params
         m = len(cts)
-        assert len(truth) == 1 << m
+        if m < 1 or len(truth) != 1 << m:
+            raise _invalid(f"lut_gate: a truth table of 2^{m} entries for {m} inputs expected, got {len(truth)}")
         arr = (C.c_uint32 * (1 << m))(*[int(v) for v in truth])
-        ptrs = (_u32p * m)()
-        if _is_torch(cts[0]):
-            self._bind_torch()
-            import torch
-            batch = cts[0].shape[0]
-            for i, t in enumerate(cts):
-                assert tuple(t.shape) == (batch, self.io_dim + 1)
-                ptrs[i] = _dp(t)
-            if out is None:
-                out = torch.empty_like(cts[0])
-            self._check(lib().tfhe_lut_gate_batch_device(self._h, arr, C.c_uint32(m), ptrs, C.c_size_t(batch), _dp(out)))
-            return out
-        host = [_np(t).reshape(-1, self.io_dim + 1) for t in cts]
-        for i, t in enumerate(host):
-            assert t.shape == host[0].shape
-            ptrs[i] = _hp(t)
-        res = np.zeros_like(host[0])
-        self._check(lib().tfhe_lut_gate_batch(self._h, arr, C.c_uint32(m), ptrs, C.c_size_t(host[0].shape[0]), _hp(res)))
+        first, dev = self._lwe_rows("lut_gate", "cts[0]", cts[0], self.io_dim + 1)
+        xs = [first] + [self._lwe_rows("lut_gate", f"cts[{i}]", cts[i], self.io_dim + 1, first)[0] for i in range(1, m)]
+        res = _result("lut_gate", dev, out, None, first)
+        ptrs = _ptrs(xs)
+        self._call("tfhe_lut_gate_batch", dev, arr, C.c_uint32(m), ptrs, C.c_size_t(first.shape[0]), _ptr(res))
         return res
 
     def lwe_not(self, ct, out=None):
         """NOT without a bootstrap: (-a, enc(1) - b)."""
-        p = self.params
-        if _is_torch(ct):
-            self._bind_torch()
-            import torch
-            if out is None:
-                out = torch.empty_like(ct)
-            self._check(lib().tfhe_lwe_not_batch_device(self._h, _dp(ct), C.c_size_t(ct.numel() // (self.io_dim + 1)), _dp(out)))
-            return out
-        a = _np(ct)
-        rows = a.reshape(-1, self.io_dim + 1)
-        res = np.zeros_like(rows)
-        self._check(lib().tfhe_lwe_not_batch(self._h, _hp(rows), C.c_size_t(rows.shape[0]), _hp(res)))
-        return res.reshape(a.shape)
+        a, dev, rows = self._words("lwe_not", "ct", ct, self.io_dim + 1)
+        res = _result("lwe_not", dev, out, None, a)
+        self._call("tfhe_lwe_not_batch", dev, _ptr(a), C.c_size_t(rows), _ptr(res))
+        return res
 
     def gate(self, truth, ct0, ct1, out=None):
         """and()/or(): boolean.rs:9-53 generalised: bootstrap(2*ct1 + ct0) with the closure's TV."""
-        p = self.params
         arr = (C.c_uint32 * 4)(*[int(v) for v in truth])
-        if _is_torch(ct0):
-            self._bind_torch()
-            import torch
-            batch = ct0.shape[0]
-            if out is None:
-                out = torch.empty_like(ct0)
-            self._check(lib().tfhe_gate_batch_device(self._h, arr, _dp(ct0), _dp(ct1), C.c_size_t(batch), _dp(out)))
-            return out
-        a, b = _np(ct0).reshape(-1, self.io_dim + 1), _np(ct1).reshape(-1, self.io_dim + 1)
-        res = np.zeros_like(a)
-        self._check(lib().tfhe_gate_batch(self._h, arr, _hp(a), _hp(b), C.c_size_t(a.shape[0]), _hp(res)))
+        a, dev = self._lwe_rows("gate", "ct0", ct0, self.io_dim + 1)
+        b = self._lwe_rows("gate", "ct1", ct1, self.io_dim + 1, a)[0]
+        res = _result("gate", dev, out, None, a)
+        self._call("tfhe_gate_batch", dev, arr, _ptr(a), _ptr(b), C.c_size_t(a.shape[0]), _ptr(res))
         return res
 
     # -- encryption side (SURVEY 8f-1): the caller's random draws arrive in the buffers --------
+    # A torch device tensor of samples is completed in place and returned; a numpy array is copied first.
     def glwe_encrypt_zero(self, glwe_sk, samples):
-        """encrypt_glwe_zero glwe.rs:190-209: samples [count][k+1][N] (uniform masks, errors in the
-        body) -> ciphertexts.  A torch device tensor is completed in place and returned."""
+        """encrypt_glwe_zero glwe.rs:190-209: samples [count][k+1][N] (uniform masks, errors in
+        the body) -> ciphertexts.  A torch device tensor is completed in place and returned."""
         p = self.params
         sk = _np(glwe_sk).reshape(p.k, p.N)
-        if _is_torch(samples):
-            self._bind_torch()
-            assert tuple(samples.shape[-2:]) == (p.k + 1, p.N)
-            self._check(lib().tfhe_glwe_encrypt_zero_batch_device(
-                self._h, _hp(sk), _dp(samples), C.c_size_t(samples.numel() // ((p.k + 1) * p.N))))
-            return samples
-        out = _np(samples).copy().reshape(-1, p.k + 1, p.N)
-        self._check(lib().tfhe_glwe_encrypt_zero_batch(self._h, _hp(sk), _hp(out), C.c_size_t(out.shape[0])))
-        return out
+        dev = _is_torch(samples)
+        buf = samples if dev else _np(samples).copy().reshape(-1, p.k + 1, p.N)
+        _check_u32("glwe_encrypt_zero", "samples", buf, dev)
+        if len(buf.shape) < 2 or tuple(buf.shape[-2:]) != (p.k + 1, p.N):
+            raise _invalid(f"glwe_encrypt_zero: samples [count][{p.k + 1}][{p.N}] expected, got {tuple(buf.shape)}")
+        count = (buf.numel() if dev else buf.size) // ((p.k + 1) * p.N)
+        self._call("tfhe_glwe_encrypt_zero_batch", dev, _ptr(sk), _ptr(buf), C.c_size_t(count))
+        return buf
 
     def glwe_decrypt(self, glwe_sk, glwe) -> np.ndarray:
         """decrypt_glwe_ciphertext glwe.rs:245-265 -> plaintext polynomials [count][N]."""
@@ -1731,7 +1526,7 @@ class Context:
         sk = _np(glwe_sk).reshape(p.k, p.N)
         g = _np(glwe).reshape(-1, p.k + 1, p.N)
         out = np.zeros((g.shape[0], p.N), dtype=np.uint32)
-        self._check(lib().tfhe_glwe_decrypt_batch(self._h, _hp(sk), _hp(g), C.c_size_t(g.shape[0]), _hp(out)))
+        self._check(lib().tfhe_glwe_decrypt_batch(self._h, _ptr(sk), _ptr(g), C.c_size_t(g.shape[0]), _ptr(out)))
         return out
 
     def ggsw_encrypt(self, glwe_sk, messages, samples):
@@ -1740,53 +1535,40 @@ class Context:
         p = self.params
         sk = _np(glwe_sk).reshape(p.k, p.N)
         msg = _np(messages).reshape(-1)
-        if _is_torch(samples):
-            self._bind_torch()
-            assert samples.numel() == msg.size * p.R * (p.k + 1) * p.N
-            self._check(lib().tfhe_ggsw_encrypt_batch_device(self._h, _hp(sk), _hp(msg), _dp(samples),
-                                                             C.c_size_t(msg.size)))
-            return samples
-        out = _np(samples).copy().reshape(msg.size, p.R, p.k + 1, p.N)
-        self._check(lib().tfhe_ggsw_encrypt_batch(self._h, _hp(sk), _hp(msg), _hp(out), C.c_size_t(msg.size)))
-        return out
+        dev = _is_torch(samples)
+        buf = samples if dev else _np(samples).copy().reshape(msg.size, p.R, p.k + 1, p.N)
+        _check_u32("ggsw_encrypt", "samples", buf, dev)
+        if (buf.numel() if dev else buf.size) != msg.size * p.R * (p.k + 1) * p.N:
+            raise _invalid(f"ggsw_encrypt: samples [{msg.size}][{p.R}][{p.k + 1}][{p.N}] expected, got {tuple(buf.shape)}")
+        self._call("tfhe_ggsw_encrypt_batch", dev, _ptr(sk), _ptr(msg), _ptr(buf), C.c_size_t(msg.size))
+        return buf
 
     def lwe_encrypt(self, lwe_sk, samples, plaintexts=None):
         """encrypt_lwe_plaintext lwe.rs:138-160: samples [batch][dim+1] (uniform masks, error in
         the b slot), plaintexts [batch] already encoded (None = encrypt_lwe_zero)."""
         sk = _np(lwe_sk).reshape(-1)
         dim = sk.size
-        if _is_torch(samples):
-            self._bind_torch()
-            assert samples.shape[-1] == dim + 1
-            self._check(lib().tfhe_lwe_encrypt_batch_device(
-                self._h, _hp(sk), C.c_size_t(dim), _dp(plaintexts) if plaintexts is not None else None,
-                _dp(samples), C.c_size_t(samples.numel() // (dim + 1))))
-            return samples
-        out = _np(samples).copy().reshape(-1, dim + 1)
-        pt = _np(plaintexts).reshape(-1) if plaintexts is not None else None
-        assert pt is None or pt.size == out.shape[0]
-        self._check(lib().tfhe_lwe_encrypt_batch(self._h, _hp(sk), C.c_size_t(dim),
-                                                 _hp(pt) if pt is not None else None, _hp(out),
-                                                 C.c_size_t(out.shape[0])))
-        return out
+        dev = _is_torch(samples)
+        buf = samples if dev else _np(samples).copy().reshape(-1, dim + 1)
+        _check_u32("lwe_encrypt", "samples", buf, dev)
+        if len(buf.shape) < 1 or int(buf.shape[-1]) != dim + 1:
+            raise _invalid(f"lwe_encrypt: samples [batch][{dim + 1}] expected, got {tuple(buf.shape)}")
+        batch = (buf.numel() if dev else buf.size) // (dim + 1)
+        pt = plaintexts
+        if pt is not None:
+            pt = pt if dev else _np(pt).reshape(-1)
+            _check_u32("lwe_encrypt", "plaintexts", pt, dev, None, buf if dev else None)
+            if (pt.numel() if dev else pt.size) != batch:
+                raise _invalid(f"lwe_encrypt: {batch} plaintexts expected, got {tuple(pt.shape)}")
+        self._call("tfhe_lwe_encrypt_batch", dev, _ptr(sk), C.c_size_t(dim), _ptr(pt), _ptr(buf), C.c_size_t(batch))
+        return buf
 
     def lwe_decrypt(self, lwe_sk, lwe, out=None):
         """decrypt_lwe lwe.rs:162-173 -> encoded plaintexts [batch] = b - <a, s>."""
         sk = _np(lwe_sk).reshape(-1)
-        dim = sk.size
-        if _is_torch(lwe):
-            self._bind_torch()
-            import torch
-            batch = lwe.numel() // (dim + 1)
-            if out is None:
-                out = torch.empty(batch, dtype=lwe.dtype, device=lwe.device)
-            self._check(lib().tfhe_lwe_decrypt_batch_device(self._h, _hp(sk), C.c_size_t(dim), _dp(lwe),
-                                                            C.c_size_t(batch), _dp(out)))
-            return out
-        rows = _np(lwe).reshape(-1, dim + 1)
-        res = np.zeros(rows.shape[0], dtype=np.uint32)
-        self._check(lib().tfhe_lwe_decrypt_batch(self._h, _hp(sk), C.c_size_t(dim), _hp(rows),
-                                                 C.c_size_t(rows.shape[0]), _hp(res)))
+        rows, dev, batch = self._words("lwe_decrypt", "lwe", lwe, sk.size + 1)
+        res = _result("lwe_decrypt", dev, out, (batch,), rows)
+        self._call("tfhe_lwe_decrypt_batch", dev, _ptr(sk), C.c_size_t(sk.size), _ptr(rows), C.c_size_t(batch), _ptr(res))
         return res
 
     def generate_ksk(self, from_sk, to_sk, samples) -> np.ndarray:
@@ -1794,44 +1576,29 @@ class Context:
         samples [from_dim*l_ks][to_dim+1] pre-filled."""
         f, t = _np(from_sk).reshape(-1), _np(to_sk).reshape(-1)
         out = _np(samples).copy()
-        assert out.shape == (f.size * self.params.ks_decomposer.levels, t.size + 1)
-        self._check(lib().tfhe_generate_ksk(self._h, _hp(f), C.c_size_t(f.size), _hp(t), C.c_size_t(t.size),
-                                            _hp(out)))
+        _check_u32("generate_ksk", "samples", out, False, (f.size * self.params.ks_decomposer.levels, t.size + 1))
+        self._check(lib().tfhe_generate_ksk(self._h, _ptr(f), C.c_size_t(f.size), _ptr(t), C.c_size_t(t.size),
+                                            _ptr(out)))
         return out
+
+    def _key_gen(self, entry, what, lwe_sk, glwe_sk, bsk_samples, ksk_samples, load, bmmp):
+        p = self.params
+        lsk, gsk = _np(lwe_sk).reshape(p.n), _np(glwe_sk).reshape(p.k, p.N)
+        bsk, ksk, dev = self._key_pair(what, bsk_samples, ksk_samples, bmmp, copy=True)
+        self._call(entry, dev, _ptr(lsk), _ptr(gsk), _ptr(bsk), _ptr(ksk), C.c_int(int(load)))
+        return bsk, ksk
 
     def bootstrapping_key_gen(self, lwe_sk, glwe_sk, bsk_samples, ksk_samples, load: bool = True):
         """bootstrapping_key_gen bootstrapping.rs:23-56 on pre-filled bsk / ksk buffers -> (bsk, ksk);
         `load` installs the key in this context.  Torch device tensors are completed in place."""
-        p = self.params
-        lsk, gsk = _np(lwe_sk).reshape(p.n), _np(glwe_sk).reshape(p.k, p.N)
-        if _is_torch(bsk_samples):
-            self._bind_torch()
-            assert tuple(bsk_samples.shape) == p.bsk_shape() and tuple(ksk_samples.shape) == p.ksk_shape()
-            self._check(lib().tfhe_bootstrapping_key_gen_device(self._h, _hp(lsk), _hp(gsk), _dp(bsk_samples),
-                                                                _dp(ksk_samples), C.c_int(int(load))))
-            return bsk_samples, ksk_samples
-        bsk, ksk = _np(bsk_samples).copy(), _np(ksk_samples).copy()
-        assert bsk.shape == p.bsk_shape() and ksk.shape == p.ksk_shape()
-        self._check(lib().tfhe_bootstrapping_key_gen(self._h, _hp(lsk), _hp(gsk), _hp(bsk), _hp(ksk),
-                                                     C.c_int(int(load))))
-        return bsk, ksk
+        return self._key_gen("tfhe_bootstrapping_key_gen", "bootstrapping_key_gen", lwe_sk, glwe_sk, bsk_samples, ksk_samples,
+                             load, False)
 
     def bootstrapping_key_gen_bmmp(self, lwe_sk, glwe_sk, bsk_samples, ksk_samples, load: bool = True):
         """The BMMP key on pre-filled buffers: bsk_samples [n/2*3][R][k+1][N], ksk_samples as for
         bootstrapping_key_gen -> (bsk_bmmp, ksk); `load` installs it.  Torch tensors in place."""
-        p = self.params
-        lsk, gsk = _np(lwe_sk).reshape(p.n), _np(glwe_sk).reshape(p.k, p.N)
-        if _is_torch(bsk_samples):
-            self._bind_torch()
-            assert tuple(bsk_samples.shape) == p.bsk_bmmp_shape() and tuple(ksk_samples.shape) == p.ksk_shape()
-            self._check(lib().tfhe_bootstrapping_key_gen_bmmp_device(self._h, _hp(lsk), _hp(gsk), _dp(bsk_samples),
-                                                                     _dp(ksk_samples), C.c_int(int(load))))
-            return bsk_samples, ksk_samples
-        bsk, ksk = _np(bsk_samples).copy(), _np(ksk_samples).copy()
-        assert bsk.shape == p.bsk_bmmp_shape() and ksk.shape == p.ksk_shape()
-        self._check(lib().tfhe_bootstrapping_key_gen_bmmp(self._h, _hp(lsk), _hp(gsk), _hp(bsk), _hp(ksk),
-                                                          C.c_int(int(load))))
-        return bsk, ksk
+        return self._key_gen("tfhe_bootstrapping_key_gen_bmmp", "bootstrapping_key_gen_bmmp", lwe_sk, glwe_sk, bsk_samples,
+                             ksk_samples, load, True)
 
     # -- convenience on top of the encryption-side entry points ---------------------------------
     @staticmethod
@@ -1977,7 +1744,6 @@ class _BorrowedContext(Context):
     def __init__(self, params: TfheParams, handle):
         self.params = params
         self._h = C.c_void_p(handle)
-        lib().tfhe_context_backend.restype = C.c_char_p
 
     def close(self):
         self._h = C.c_void_p()
@@ -2082,11 +1848,11 @@ class Pool:
             assert tuple(bsk.shape) == p.bsk_shape() and tuple(ksk.shape) == p.ksk_shape()
             import torch
             torch.cuda.synchronize(bsk.device)
-            self._check(lib().tfhe_pool_load_bootstrapping_key_device(self._h, _dp(bsk), _dp(ksk)))
+            self._check(lib().tfhe_pool_load_bootstrapping_key_device(self._h, _ptr(bsk), _ptr(ksk)))
             return
         bsk, ksk = _np(bsk), _np(ksk)
         assert bsk.shape == p.bsk_shape() and ksk.shape == p.ksk_shape()
-        self._check(lib().tfhe_pool_load_bootstrapping_key(self._h, _hp(bsk), _hp(ksk)))
+        self._check(lib().tfhe_pool_load_bootstrapping_key(self._h, _ptr(bsk), _ptr(ksk)))
 
     def replicate_key(self):
         """copy whatever key member 0 holds (prepared form + KSK) to every other member, device to device"""
@@ -2100,7 +1866,7 @@ class Pool:
         bsk, ksk = _np(bsk_samples).copy(), _np(ksk_samples).copy()
         assert bsk.shape == (p.bsk_bmmp_shape() if bmmp else p.bsk_shape()) and ksk.shape == p.ksk_shape()
         fn = lib().tfhe_pool_bootstrapping_key_gen_bmmp if bmmp else lib().tfhe_pool_bootstrapping_key_gen
-        self._check(fn(self._h, _hp(lsk), _hp(gsk), _hp(bsk), _hp(ksk), C.c_int(int(load))))
+        self._check(fn(self._h, _ptr(lsk), _ptr(gsk), _ptr(bsk), _ptr(ksk), C.c_int(int(load))))
         return bsk, ksk
 
     def generate_keys(self, rng=None, load: bool = True, bmmp: bool = False):
@@ -2117,8 +1883,8 @@ class Pool:
         lwe, tv = _np(lwe_in).reshape(-1, self.io_dim + 1), _np(test_vector_poly)
         tv_count = 1 if tv.ndim == 1 else tv.shape[0]
         res = np.zeros_like(lwe)
-        self._check(lib().tfhe_pool_bootstrap_batch(self._h, _hp(lwe), C.c_size_t(lwe.shape[0]), _hp(tv),
-                                                    C.c_size_t(tv_count), _hp(res)))
+        self._check(lib().tfhe_pool_bootstrap_batch(self._h, _ptr(lwe), C.c_size_t(lwe.shape[0]), _ptr(tv),
+                                                    C.c_size_t(tv_count), _ptr(res)))
         return res
 
     def gate(self, truth, ct0, ct1) -> np.ndarray:
@@ -2126,7 +1892,7 @@ class Pool:
         c0, c1 = _np(ct0).reshape(-1, self.io_dim + 1), _np(ct1).reshape(-1, self.io_dim + 1)
         t = (C.c_uint32 * 4)(*[int(v) for v in truth])
         res = np.zeros_like(c0)
-        self._check(lib().tfhe_pool_gate_batch(self._h, t, _hp(c0), _hp(c1), C.c_size_t(c0.shape[0]), _hp(res)))
+        self._check(lib().tfhe_pool_gate_batch(self._h, t, _ptr(c0), _ptr(c1), C.c_size_t(c0.shape[0]), _ptr(res)))
         return res
 
     def bootstrap_shards(self, lwe_shards, tv_shards, out_shards):
