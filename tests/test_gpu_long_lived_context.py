@@ -2,7 +2,8 @@
 context, mode switches with keys loaded, workspaces that grow and then serve small calls, refused calls, seeded
 interleavings of all of them, and the image cache of the branching programs (section G).  Every comparison is bit-exact.  Expected words come from the CPU oracle, from the clear
 models of tests/clear_model*.py, or from an earlier output of the same context that was itself checked against one of
-those -- never from a second context of the library under test.
+those -- never from a second context of the library under test, with one exception that says so: D5 .. D11 ask whether
+a context that regrew a feature workspace still computes what a fresh one does, and compare with exactly that.
 
 The gate cache and captured graphs (section A.3).  tfhe_gate_batch / tfhe_lut_gate_batch keep one device test vector
 per truth table seen, at most 64 of them, least recently used replaced.  A captured HIP graph has that buffer's
@@ -639,7 +640,7 @@ def test_d1_bootstrap_and_gate_batches_grow_then_shrink(world):
 
 
 def test_d2_scratch_buffer_grows_then_serves_small_calls(world):
-    """decompose of 10, 100000, 10 values (ensure_misc)"""
+    """decompose of 10, 100000, 10 values (d_misc)"""
     m = pkg()
     e = cm.edge_words()
     big = e[(np.arange(100000, dtype=np.int64) * 7919) % e.size]
@@ -673,6 +674,198 @@ def test_d4_key_scratch_grows_then_serves_small_calls(world, oracle):
             samples = lwe_samples(rng, p.lwe_std_dev, 4, sk.size)
             pts = (rng.integers(0, 8, 4).astype(np.uint32) << np.uint32(28)).astype(np.uint32)
             check(ctx.lwe_encrypt(sk, samples, pts), oracle.encrypt_lwe_from_samples(sk, samples, pts), ("step", step, "dimension", sk.size))
+
+
+# D5 .. D11: the feature workspaces.  Every host form below sizes its own workspace; the calls are deterministic in their
+# words, so the reference of a call on the long-lived context is THE SAME CALL on a fresh context that never regrew
+# (which the features' own modules check against their clear models).  The tree-LUT shape (k = 2, N = 512, n = 4,
+# log_p = 2: B = 4) is the smallest this module builds.  The packing key's buffers: test_b3 above reloads it at
+# dimensions 9, 7, 13, 7 and packs after each, which is this test for tfhe_load_packing_key.
+def regrown_against_fresh(tree_world, steps):
+    """steps: [(what, call(ctx) -> array or sequence of arrays)], all on one context in order; each against a fresh one"""
+    p, keys = tree_world
+
+    def fresh():
+        ctx = tcm.context(p)
+        keys.load(ctx)
+        return ctx
+
+    def arrays(res):
+        return [res] if isinstance(res, np.ndarray) else [a for part in res for a in arrays(part)]
+
+    with fresh() as long_lived:
+        for what, call in steps:
+            got = arrays(call(long_lived))
+            with fresh() as once:
+                want = arrays(call(once))
+            assert len(got) == len(want), what
+            for i, (g_, w_) in enumerate(zip(got, want)):
+                check(g_, w_, (what, "result", i))
+
+
+def test_d5_dense_workspace_grows_then_serves_small_calls(tree_world):
+    """dense_bootstrap at queries x outputs = 1 x 2, 3 x 3, 1 x 2 (reserve_dense: the layer's rows and the bootstraps')"""
+    p, _ = tree_world
+    rng = np.random.default_rng(105)
+    x = rand_u32(rng, (3, 5, p.n + 1))
+    w = rng.integers(-3, 4, (3, 5))
+    bias = rand_u32(rng, (3,))
+    tvs = rng.integers(0, 1 << p.log_p, (3, p.N)).astype(np.uint32)
+    regrown_against_fresh(tree_world, [((q, o), lambda ctx, q=q, o=o: ctx.dense_bootstrap(x[:q], w[:o], bias[:o], tvs[:o]))
+                                       for q, o in ((1, 2), (3, 3), (1, 2))])
+
+
+def test_d6_convolution_workspace_grows_then_serves_small_calls(tree_world):
+    """glwe_conv at queries x channels = 1 x 2, 3 x 3, 1 x 2 (reserve_conv); the weights are prepared by the context that
+    runs them"""
+    p, _ = tree_world
+    rng = np.random.default_rng(106)
+    x = rand_u32(rng, (3, 3, p.k + 1, p.N))
+    w = rng.integers(-4, 5, (2, 3, p.N))
+    bias = rand_u32(rng, (2, p.N))
+
+    def conv(ctx, q, c):
+        with ctx.prepare_poly_weights(w[:, :c]) as weights:
+            return ctx.glwe_conv(np.ascontiguousarray(x[:q, :c]), weights, bias)
+
+    regrown_against_fresh(tree_world, [((q, c), lambda ctx, q=q, c=c: conv(ctx, q, c)) for q, c in ((1, 2), (3, 3), (1, 2))])
+
+
+def test_d7_multi_value_workspace_grows_by_batch_then_by_tables(tree_world):
+    """multi_value_bootstrap at batch x tables = 2 x 1, 9 x 1, 2 x 1, 2 x 4, 9 x 1, 2 x 1 (reserve_mv: both logical sizes)"""
+    p, _ = tree_world
+    rng = np.random.default_rng(107)
+    lwe = rand_u32(rng, (9, p.n + 1))
+    luts = rng.integers(0, 1 << p.log_p, (4, 1 << p.log_p)).astype(np.uint32)
+    regrown_against_fresh(tree_world, [((b, t), lambda ctx, b=b, t=t: ctx.multi_value_bootstrap(lwe[:b], luts[:t]))
+                                       for b, t in ((2, 1), (9, 1), (2, 1), (2, 4), (9, 1), (2, 1))])
+
+
+def test_d8_extraction_workspace_grows_by_batch_then_by_digits(tree_world):
+    """extract_digits (with the remainder) at batch x digits = 2 x 1, 9 x 1, 2 x 1, 2 x 3, 2 x 1, then wide_lut at
+    2 x 1, 9 x 1, 2 x 3, 2 x 1 (reserve_extract: both logical sizes; the wide LUT grows the tree-LUT workspace with it)"""
+    p, _ = tree_world
+    B = 1 << p.log_p
+    rng = np.random.default_rng(108)
+    lwe = rand_u32(rng, (9, p.n + 1))
+    table = rng.integers(0, B, (2, B ** 3)).astype(np.uint32)
+    steps = [(("extract", b, d), lambda ctx, b=b, d=d: ctx.extract_digits(lwe[:b], 24, p.log_p, d, 29, remainder=True))
+             for b, d in ((2, 1), (9, 1), (2, 1), (2, 3), (2, 1))]
+    steps += [(("wide", b, d), lambda ctx, b=b, d=d: ctx.wide_lut(lwe[:b], 24, d, np.ascontiguousarray(table[:, :B ** d])))
+              for b, d in ((2, 1), (9, 1), (2, 3), (2, 1))]
+    regrown_against_fresh(tree_world, steps)
+
+
+def test_d9_tree_lut_workspace_grows_by_digits(tree_world):
+    """tree_lut of 1, 3, 1 digits at batch 2, two tables (tfhe_context_reserve_tree_lut: 2, 32, 2 rotations at level 0)"""
+    p, _ = tree_world
+    B = 1 << p.log_p
+    rng = np.random.default_rng(109)
+    digits = [rand_u32(rng, (2, p.n + 1)) for _ in range(3)]
+    table = rng.integers(0, B, (1, 2, B ** 3)).astype(np.uint32)
+    regrown_against_fresh(tree_world, [(d, lambda ctx, d=d: ctx.tree_lut(digits[:d], np.ascontiguousarray(table[:, :, :B ** d])))
+                                       for d in (1, 3, 1)])
+
+
+def test_d10_lookup_and_demux_workspaces_grow_by_depth(tree_world):
+    """table_lookup and table_write of two queries at log2 N + 1, log2 N + 3, log2 N + 1 address bits: trees of 1, 3, 1
+    levels (the lookup workspace, then the demux workspace; the tree of one level needs none)"""
+    p, _ = tree_world
+    rng = np.random.default_rng(110)
+    deep = p.glwe_poly_degree + 3
+    sel = rand_u32(rng, (2, deep, p.R, p.k + 1, p.N))
+    table = rng.integers(0, 1 << p.log_p, (1, 1, 1 << deep)).astype(np.uint32)
+    values = rand_u32(rng, (2, 1, p.k + 1, p.N))
+    leaves = rand_u32(rng, (1, 1, 8, p.k + 1, p.N))
+    depths = (deep - 2, deep, deep - 2)
+    steps = [(("lookup", d), lambda ctx, d=d: ctx.table_lookup(np.ascontiguousarray(sel[:, :d]), np.ascontiguousarray(table[:, :, :1 << d])))
+             for d in depths]
+    steps += [(("write", d), lambda ctx, d=d: ctx.table_write(np.ascontiguousarray(sel[:, :d]), values,
+                                                               np.ascontiguousarray(leaves[:, :, :1 << (d - p.glwe_poly_degree)])))
+              for d in depths]
+    regrown_against_fresh(tree_world, steps)
+
+
+# what a device form of D11 is refused with at size 9 on a context that reserved for size 2: tfhe_last_error, word for word
+# (a batch beyond tfhe_context_reserve's own rows reads as nothing reserved for the extraction: the two 0s)
+D11_REFUSALS = {
+    "dense": "the call needs 110664 bytes of dense workspace (9 queries, 2 outputs), 24592 are reserved (tfhe_context_reserve_dense)",
+    "conv": "the call needs 442368 bytes of convolution workspace (9 queries, 2 channels), 98304 are reserved (tfhe_context_reserve_glwe_conv)",
+    "multi-value": "the call needs 129664 bytes of multi-value workspace (batch 9, 2 tables), 28816 are reserved for batch 2 and 2 tables (tfhe_context_reserve_multi_value)",
+    "extract": "the call needs 116880 bytes of extraction workspace (batch 9, 0 digit buffers), 0 are reserved (tfhe_context_reserve_extract)",
+    "tree-lut": "the call needs 535632 bytes of tree-LUT workspace, 119040 are reserved (tfhe_context_reserve_tree_lut)",
+    "wide-lut": "the call needs 190704 bytes of extraction workspace (batch 9, 2 digit buffers), 0 are reserved (tfhe_context_reserve_extract)",
+    "lookup": "the call needs 13824 words of lookup workspace, 6144 are reserved (tfhe_context_reserve_lookup)",
+    "demux": "the call needs 55296 bytes of demux workspace, 24576 are reserved (tfhe_context_reserve_demux)",
+}
+
+
+def test_d11_device_forms_inside_and_beyond_a_reservation(tree_world):
+    """per feature: reserved for size 9, the device form at size 2 gives the host form's words (a fresh context's); reserved
+    for size 2 on a fresh context, the device form at size 9 is refused with D11_REFUSALS and the form at 2 still serves.
+    The size is the queries of the dense layer (two outputs), the convolution (two channels), the lookup and the write
+    (log2 N + 2 address bits), and the batch of the others (two tables, two digits)."""
+    p, keys = tree_world
+    B, deep = 1 << p.log_p, p.glwe_poly_degree + 2
+    rng = np.random.default_rng(111)
+    lwe = [rand_u32(rng, (9, p.n + 1)) for _ in range(2)]
+    x = rand_u32(rng, (9, 5, p.n + 1))
+    w, bias, tv = rng.integers(-3, 4, (2, 5)), rand_u32(rng, (2,)), rng.integers(0, B, p.N).astype(np.uint32)
+    glwe = rand_u32(rng, (9, 2, p.k + 1, p.N))
+    poly_w, poly_bias = rng.integers(-4, 5, (2, 2, p.N)), rand_u32(rng, (2, p.N))
+    luts = rng.integers(0, B, (2, B)).astype(np.uint32)
+    table = rng.integers(0, B, (1, 1, B ** 2)).astype(np.uint32)
+    sel = rand_u32(rng, (9, deep, p.R, p.k + 1, p.N))
+    clear = rng.integers(0, B, (1, 1, 1 << deep)).astype(np.uint32)
+    leaves = rand_u32(rng, (1, 1, 4, p.k + 1, p.N))
+
+    def selectors(ctx, s, to):
+        if to is not dev:
+            return np.ascontiguousarray(sel[:s])
+        return ctx.prepare_ggsw_device(dev(sel[:s].reshape(-1, p.R, p.k + 1, p.N))).reshape(s, deep, -1)
+
+    def conv(ctx, s, to):
+        with ctx.prepare_poly_weights(poly_w) as weights:
+            out = ctx.glwe_conv(to(glwe[:s]), weights, poly_bias)
+            ctx.synchronize()  # the weights go away with this block
+            return out
+
+    features = {  # name -> (reserve(ctx, size), call(ctx, size, to): the host form with to = np.ascontiguousarray, the device form with dev)
+        "dense": (lambda ctx, s: ctx.reserve_dense(s, 2), lambda ctx, s, to: ctx.dense_bootstrap(to(x[:s]), w, bias, tv)),
+        "conv": (lambda ctx, s: ctx.reserve_glwe_conv(s, 2), conv),
+        "multi-value": (lambda ctx, s: ctx.reserve_multi_value(s, 2), lambda ctx, s, to: ctx.multi_value_bootstrap(to(lwe[0][:s]), to(luts))),
+        "extract": (lambda ctx, s: ctx.reserve_extract(s, 2), lambda ctx, s, to: ctx.extract_digits(to(lwe[0][:s]), 24, p.log_p, 2, 29)),
+        "tree-lut": (lambda ctx, s: ctx.reserve_tree_lut(s, 2, 1), lambda ctx, s, to: ctx.tree_lut([to(c[:s]) for c in lwe], to(table))),
+        "wide-lut": (lambda ctx, s: ctx.reserve_wide_lut(s, 2, 1), lambda ctx, s, to: ctx.wide_lut(to(lwe[0][:s]), 24, 2, to(table))),
+        "lookup": (lambda ctx, s: ctx.reserve_lookup(s, 0, deep), lambda ctx, s, to: ctx.table_lookup(selectors(ctx, s, to), to(clear))),
+        "demux": (lambda ctx, s: ctx.reserve_demux(s, 0, deep),
+                  lambda ctx, s, to: ctx.table_write(selectors(ctx, s, to), to(glwe[:s, :1]), to(leaves.copy()))),
+    }
+
+    def words(res):
+        return [host(t) if torch.is_tensor(t) else t for t in (res if isinstance(res, (list, tuple)) else [res])]
+
+    def fresh():
+        ctx = tcm.context(p)
+        keys.load(ctx)
+        return ctx
+
+    refused = {}
+    for name, (reserve, call) in features.items():
+        with fresh() as ctx:
+            want = words(call(ctx, 2, np.ascontiguousarray))
+        with fresh() as ctx:
+            reserve(ctx, 9)
+            for g_, w_ in zip(words(call(ctx, 2, dev)), want):
+                check(g_, w_, (name, "size 2 inside a reservation for 9"))
+        with fresh() as ctx:
+            reserve(ctx, 2)
+            with pytest.raises(pkg().TfheError) as e:
+                call(ctx, 9, dev)
+            refused[name] = str(e.value).removeprefix("TFHE_ERR_INVALID_ARGUMENT: ")
+            for g_, w_ in zip(words(call(ctx, 2, dev)), want):
+                check(g_, w_, (name, "size 2 after the refusal"))
+    assert refused == D11_REFUSALS
 
 
 # ------------------------------------------------------------------------------------------------ E: refused calls

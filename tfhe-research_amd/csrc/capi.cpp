@@ -40,55 +40,22 @@ int decomposer_validate(const tfhe_decomposer_params& d) {
   return 0;
 }
 
-template <typename T>
-int ensure(tfhe_context* ctx, T** ptr, size_t* have, size_t want_elems) {
-  if (*have >= want_elems && *ptr) return TFHE_OK;
-  if (*ptr) HIP_TRY(ctx, hipFree(*ptr));
-  *ptr = nullptr;
-  *have = 0;
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(ptr), want_elems * sizeof(T)));
-  *have = want_elems;
-  return TFHE_OK;
-}
-
 int reserve(tfhe_context* ctx, size_t batch) {
   if (batch <= ctx->ws_batch) return TFHE_OK;
   // every LWE buffer can hold either boundary dimension (n for the reference's PBS-then-KS order,
   // k*N for KS-then-PBS), so switching the order never reallocates
   const size_t n1 = std::max((size_t)ctx->params.lwe_dimension, (size_t)ctx->big_n) + 1;
   const size_t glwe = glwe_words(ctx);
-  u32** ptrs[] = {&ctx->d_lwe_in, &ctx->d_lwe_in2, &ctx->d_lwe_big, &ctx->d_lwe_out, &ctx->d_lwe_ks,
-                  &ctx->d_glwe_a, &ctx->d_glwe_b,   &ctx->d_glwe_c,  &ctx->d_tv};
+  DeviceBuffer* bufs[] = {&ctx->d_lwe_in, &ctx->d_lwe_in2, &ctx->d_lwe_big, &ctx->d_lwe_out, &ctx->d_lwe_ks,
+                          &ctx->d_glwe_a, &ctx->d_glwe_b,   &ctx->d_glwe_c,  &ctx->d_tv};
   const size_t sizes[] = {batch * n1, batch * n1, batch * n1, batch * n1, batch * n1,
                           batch * glwe, batch * glwe, batch * glwe, batch * ctx->N};
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  // the old workspace is gone from here on: a failed allocation below must not leave ws_batch
-  // claiming buffers that are null (a later, smaller call would launch kernels on them)
+  // the old workspace is gone from here on: ws_batch claims nothing until all nine are there again
   ctx->ws_batch = 0;
-  for (int i = 0; i < 9; ++i) {
-    if (*ptrs[i]) {
-      hipError_t e = hipFree(*ptrs[i]);
-      *ptrs[i] = nullptr;
-      if (e != hipSuccess) return hip_fail(ctx, e, "hipFree(workspace)");
-    }
-  }
-  for (int i = 0; i < 9; ++i)
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(ptrs[i]), sizes[i] * sizeof(u32)));
+  // all nine go before one comes back: the peak of a large batch regrowing is the new workspace, not old plus new
+  for (DeviceBuffer* b : bufs) TFHE_TRY(b->resize(ctx, 0));
+  for (int i = 0; i < 9; ++i) TFHE_TRY(bufs[i]->grow(ctx, sizes[i] * sizeof(u32)));
   ctx->ws_batch = batch;
-  return TFHE_OK;
-}
-
-int ensure_misc(tfhe_context* ctx, size_t bytes) {
-  if (bytes <= ctx->misc_bytes) return TFHE_OK;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->misc_bytes = 0;
-  if (ctx->d_misc) {
-    hipError_t e = hipFree(ctx->d_misc);
-    ctx->d_misc = nullptr;
-    if (e != hipSuccess) return hip_fail(ctx, e, "hipFree(misc)");
-  }
-  HIP_TRY(ctx, hipMalloc(&ctx->d_misc, bytes));
-  ctx->misc_bytes = bytes;
   return TFHE_OK;
 }
 
@@ -154,14 +121,14 @@ int download_and_wait(tfhe_context* ctx, void* host, const u32* dev, size_t word
 class Staging {
  public:
   Staging(tfhe_context* ctx, std::vector<size_t> words) : ctx_(ctx), words_(std::move(words)) {}
-  // grows the scratch buffer if the segments need it (ensure_misc: synchronises only then); call first
+  // grows the scratch buffer if the segments need it (synchronises only then); call first
   int reserve() {
     size_t total = 0;
     for (size_t w : words_) total += w;
-    return ensure_misc(ctx_, total * sizeof(u32));
+    return ctx_->d_misc.grow(ctx_, total * sizeof(u32));
   }
   u32* operator[](size_t seg) const {
-    u32* p = static_cast<u32*>(ctx_->d_misc);
+    u32* p = ctx_->d_misc.as<u32>();
     for (size_t i = 0; i < seg; ++i) p += words_[i];
     return p;
   }
@@ -182,18 +149,6 @@ int in_place_host_form(tfhe_context* ctx, u32* host, size_t words, DeviceForm de
   TFHE_TRY(device_form(s[0]));
   return s.download_and_wait(0, host);
 }
-
-// a temporary device buffer of a key load / key generation from host memory: freed on every way out
-struct DeviceWords {
-  u32* p = nullptr;
-  DeviceWords() = default;
-  DeviceWords(const DeviceWords&) = delete;
-  DeviceWords& operator=(const DeviceWords&) = delete;
-  ~DeviceWords() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t words) { return hipMalloc(reinterpret_cast<void**>(&p), words * sizeof(u32)); }
-};
 
 // Row s*levels + level of a key-switching key (key_switching.rs:36-45) or a packing key carries
 // sk[s] * 2^{log_base*(l - (level+1))}, the KS decomposer's gadget factor of that level
@@ -341,16 +296,16 @@ struct AccSource {
 hipError_t enqueue_blind_rotate(tfhe_context* ctx, const u32* lwe_in, size_t batch, const u32* tv,
                                 size_t tv_count, u32* glwe_out, u32* lwe_extracted, AccSource from = AccSource()) {
   if (ctx->bmmp)
-    return launch::blind_rotate_bmmp(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, lwe_in, batch, tv,
-                                     tv_count == 1 ? 0 : ctx->N, ctx->d_bsk, glwe_out, lwe_extracted);
+    return launch::blind_rotate_bmmp(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw.as(), lwe_in, batch, tv,
+                                     tv_count == 1 ? 0 : ctx->N, ctx->d_bsk.as(), glwe_out, lwe_extracted);
   // accumulators between the launches of a segmented rotation: the caller's output, or the workspace (sized by reserve)
-  u32* state = glwe_out ? glwe_out : from.state ? from.state : (batch <= ctx->ws_batch ? ctx->d_glwe_c : nullptr);
+  u32* state = glwe_out ? glwe_out : from.state ? from.state : (batch <= ctx->ws_batch ? ctx->d_glwe_c.as<u32>() : nullptr);
   PbsParams P = ctx->pbs;
   P.acc_glwe = from.glwe ? 1u : 0u;
   P.acc_offset = from.offset;
   const size_t tv_words = from.glwe ? glwe_words(ctx) : (size_t)ctx->N;
-  return launch::blind_rotate(ctx->stream, ctx->field, P, ctx->d_tw, lwe_in, batch, tv, tv_count == 1 ? 0 : tv_words,
-                              ctx->d_bsk, glwe_out, lwe_extracted, state, &ctx->side, ctx->shape);
+  return launch::blind_rotate(ctx->stream, ctx->field, P, ctx->d_tw.as(), lwe_in, batch, tv, tv_count == 1 ? 0 : tv_words,
+                              ctx->d_bsk.as(), glwe_out, lwe_extracted, state, &ctx->side, ctx->shape);
 }
 
 // Enqueue the whole PBS on device buffers: blind rotation (+ fused sample extract), key switch (bootstrapping.rs:58-120),
@@ -366,12 +321,12 @@ int enqueue_bootstrap(tfhe_context* ctx, const u32* d_lwe_in, size_t batch, cons
   }
   auto key_switch = [&](const u32* in, u32* out) -> int {
     TFHE_TRY(span_begin(ctx, kKeySwitchSpan));
-    HIP_TRY(ctx, launch::key_switch(ctx->stream, ctx->ks, ctx->big_n, ctx->params.lwe_dimension, in, batch, ctx->d_ksk, out, ctx->d_ksk_matrix, ctx->ks_path));
+    HIP_TRY(ctx, launch::key_switch(ctx->stream, ctx->ks, ctx->big_n, ctx->params.lwe_dimension, in, batch, ctx->d_ksk.as<u32>(), out, ctx->d_ksk_matrix.as(), ctx->ks_path));
     return span_end(ctx, kKeySwitchSpan, false);
   };
   if (ctx->ks_first) {  // notes/TFHE.md:367-400: key switch k*N -> n, then PBS back to k*N
-    TFHE_TRY(key_switch(d_lwe_in, ctx->d_lwe_ks));
-    br_in = ctx->d_lwe_ks;
+    TFHE_TRY(key_switch(d_lwe_in, ctx->d_lwe_ks.as<u32>()));
+    br_in = ctx->d_lwe_ks.as<u32>();
     br_out = d_lwe_out;
   }
   TFHE_TRY(span_begin(ctx, kRotationSpan));
@@ -390,13 +345,25 @@ double convolution_bits(const tfhe_params* p, double key_bits) {
 }
 
 template <class F>
-hipError_t upload_twiddles(tfhe_context* ctx) {
+int upload_twiddles(tfhe_context* ctx) {
   // (the complex transform has N/2 points: F::kLogShrink = 1)
   std::vector<typename F::elem> tw(ntt_twiddle_words((int)(ctx->N >> F::kLogShrink)));
   F::fill_twiddles((int)ctx->params.glwe_poly_degree - F::kLogShrink, tw.data());
-  hipError_t e = hipMalloc(&ctx->d_tw, tw.size() * sizeof(typename F::elem));
-  if (e != hipSuccess) return e;
-  return hipMemcpy(ctx->d_tw, tw.data(), tw.size() * sizeof(typename F::elem), hipMemcpyHostToDevice);
+  TFHE_TRY(ctx->d_tw.grow(ctx, tw.size() * sizeof(typename F::elem)));
+  HIP_TRY(ctx, hipMemcpy(ctx->d_tw.as(), tw.data(), tw.size() * sizeof(typename F::elem), hipMemcpyHostToDevice));
+  return TFHE_OK;
+}
+
+// The prepared bootstrapping key for `ggsws` GGSWs (reallocated when the other kind of key was loaded before: its
+// footprint follows the key), the key-switching key and, where it is wanted, its matrix-path layout (allocated once:
+// their sizes are the context's).  The caller has taken the old key out of service (have_key) before.
+int ensure_key_buffers(tfhe_context* ctx, size_t ggsws, bool want_matrix) {
+  ctx->bsk_ggsws = 0;
+  TFHE_TRY(ctx->d_bsk.resize(ctx, prepared_bsk_bytes(ctx, ggsws)));
+  ctx->bsk_ggsws = ggsws;
+  TFHE_TRY(ctx->d_ksk.grow(ctx, ksk_words(ctx) * sizeof(u32)));
+  if (want_matrix) TFHE_TRY(ctx->d_ksk_matrix.grow(ctx, ksk_matrix_bytes(ctx)));
+  return TFHE_OK;
 }
 
 }  // namespace
@@ -415,24 +382,13 @@ int adopt_prepared_key(tfhe_context* dst, const tfhe_context* src) {
   HIP_TRY(dst, hipSetDevice(dst->device));
   const size_t ggsws = src->bsk_ggsws;
   const size_t bsk_bytes = prepared_bsk_bytes(src, ggsws), ksk_bytes = ksk_words(src) * sizeof(u32);
-  if (dst->d_bsk && dst->bsk_ggsws != ggsws) {
-    HIP_TRY(dst, hipStreamSynchronize(dst->stream));
-    hipError_t e = hipFree(dst->d_bsk);
-    dst->d_bsk = nullptr;
-    if (e != hipSuccess) return hip_fail(dst, e, "hipFree(bsk)");
-  }
-  if (!dst->d_bsk) {
-    HIP_TRY(dst, hipMalloc(&dst->d_bsk, bsk_bytes));
-    dst->bsk_ggsws = ggsws;
-  }
-  if (!dst->d_ksk) HIP_TRY(dst, hipMalloc(reinterpret_cast<void**>(&dst->d_ksk), ksk_bytes));
-  const size_t ksm_bytes = src->d_ksk_matrix ? ksk_matrix_bytes(src) : 0;  // same parameters: admitted on both or neither
-  if (ksm_bytes && !dst->d_ksk_matrix) HIP_TRY(dst, hipMalloc(&dst->d_ksk_matrix, ksm_bytes));
+  const size_t ksm_bytes = src->d_ksk_matrix.bytes();  // same parameters: admitted on both or neither
+  TFHE_TRY(ensure_key_buffers(dst, ggsws, ksm_bytes != 0));
   if (dst->device == src->device) {
-    HIP_TRY(dst, hipMemcpyAsync(dst->d_bsk, src->d_bsk, bsk_bytes, hipMemcpyDeviceToDevice, dst->stream));
-    HIP_TRY(dst, hipMemcpyAsync(dst->d_ksk, src->d_ksk, ksk_bytes, hipMemcpyDeviceToDevice, dst->stream));
+    HIP_TRY(dst, hipMemcpyAsync(dst->d_bsk.as(), src->d_bsk.as(), bsk_bytes, hipMemcpyDeviceToDevice, dst->stream));
+    HIP_TRY(dst, hipMemcpyAsync(dst->d_ksk.as<u32>(), src->d_ksk.as<u32>(), ksk_bytes, hipMemcpyDeviceToDevice, dst->stream));
     if (ksm_bytes)
-      HIP_TRY(dst, hipMemcpyAsync(dst->d_ksk_matrix, src->d_ksk_matrix, ksm_bytes, hipMemcpyDeviceToDevice, dst->stream));
+      HIP_TRY(dst, hipMemcpyAsync(dst->d_ksk_matrix.as(), src->d_ksk_matrix.as(), ksm_bytes, hipMemcpyDeviceToDevice, dst->stream));
   } else {
     // direct xGMI copies where the link allows peer access; hipMemcpyPeerAsync stages through the host otherwise
     int can = 0;
@@ -441,10 +397,10 @@ int adopt_prepared_key(tfhe_context* dst, const tfhe_context* src) {
       if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return hip_fail(dst, e, "hipDeviceEnablePeerAccess");
       (void)hipGetLastError();
     }
-    HIP_TRY(dst, hipMemcpyPeerAsync(dst->d_bsk, dst->device, src->d_bsk, src->device, bsk_bytes, dst->stream));
-    HIP_TRY(dst, hipMemcpyPeerAsync(dst->d_ksk, dst->device, src->d_ksk, src->device, ksk_bytes, dst->stream));
+    HIP_TRY(dst, hipMemcpyPeerAsync(dst->d_bsk.as(), dst->device, src->d_bsk.as(), src->device, bsk_bytes, dst->stream));
+    HIP_TRY(dst, hipMemcpyPeerAsync(dst->d_ksk.as<u32>(), dst->device, src->d_ksk.as<u32>(), src->device, ksk_bytes, dst->stream));
     if (ksm_bytes)
-      HIP_TRY(dst, hipMemcpyPeerAsync(dst->d_ksk_matrix, dst->device, src->d_ksk_matrix, src->device, ksm_bytes, dst->stream));
+      HIP_TRY(dst, hipMemcpyPeerAsync(dst->d_ksk_matrix.as(), dst->device, src->d_ksk_matrix.as(), src->device, ksm_bytes, dst->stream));
   }
   dst->have_key = true;
   dst->bmmp = src->bmmp;
@@ -623,14 +579,17 @@ int tfhe_context_create_with_backend(const tfhe_params* params, int device, int 
   for (auto& slot : ctx->ev_ring)
     for (auto& ev : slot)
     if ((e = hipEventCreate(&ev)) != hipSuccess) return bail(e, "hipEventCreate");
-  e = field == launch::kFieldFp64   ? upload_twiddles<FpField>(ctx)
-      : field == launch::kFieldFp49 ? upload_twiddles<Fp49Field>(ctx)
-      : field == launch::kFieldFft  ? upload_twiddles<FftField>(ctx)
-                                    : upload_twiddles<GlField>(ctx);  // both Goldilocks fields share the table
-  if (e != hipSuccess) return bail(e, "twiddle upload");
-  if ((e = hipMalloc(reinterpret_cast<void**>(&ctx->d_queue), 2 * sizeof(unsigned long long))) != hipSuccess ||
-      (e = hipMemset(ctx->d_queue, 0, 2 * sizeof(unsigned long long))) != hipSuccess)
-    return bail(e, "work queue");
+  st = field == launch::kFieldFp64   ? upload_twiddles<FpField>(ctx)
+       : field == launch::kFieldFp49 ? upload_twiddles<Fp49Field>(ctx)
+       : field == launch::kFieldFft  ? upload_twiddles<FftField>(ctx)
+                                     : upload_twiddles<GlField>(ctx);  // both Goldilocks fields share the table
+  if (st == TFHE_OK) st = ctx->d_queue.grow(ctx, 2 * sizeof(unsigned long long));
+  if (st != TFHE_OK) {
+    std::fprintf(stderr, "tfhe_context_create: twiddles / work queue: %s\n", ctx->last_error.c_str());
+    tfhe_context_destroy(ctx);
+    return TFHE_ERR_HIP;
+  }
+  if ((e = hipMemset(ctx->d_queue.as(), 0, 2 * sizeof(unsigned long long))) != hipSuccess) return bail(e, "work queue");
   // TFHE_KERNEL_SHAPE=wide|team: the starting value of tfhe_context_set_kernel_shape (test sweeps: the whole suite under
   // one shape); unset or anything else: TFHE_SHAPE_AUTO
   if (const char* shape = std::getenv("TFHE_KERNEL_SHAPE")) {
@@ -662,18 +621,9 @@ int tfhe_prepared_ggsw_words(const tfhe_context* ctx, size_t* words) {
 
 void tfhe_context_destroy(tfhe_context* ctx) {
   if (!ctx) return;
+  // the device is selected and both streams are drained before `delete` releases the context's device buffers
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
-  void* ptrs[] = {ctx->d_queue,  ctx->d_tw,     ctx->d_bsk,    ctx->d_ksk,    ctx->d_lwe_in, ctx->d_lwe_in2,
-                  ctx->d_lwe_big, ctx->d_lwe_out, ctx->d_lwe_ks, ctx->d_glwe_a, ctx->d_glwe_b, ctx->d_glwe_c,
-                  ctx->d_tv,     ctx->d_misc,   ctx->d_ggsw_tmp, ctx->d_ggsw_raw,
-                  ctx->d_key_tmp, ctx->d_pksk, ctx->d_pack_cols, ctx->d_lookup_ws, ctx->d_tree_ws,
-                  ctx->d_demux_ws, ctx->d_program_ws, ctx->d_dense_ws, ctx->d_ksk_matrix, ctx->d_conv_ws,
-                  ctx->d_extract_ws, ctx->d_mv_const, ctx->d_mv_ws};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  for (auto& g : ctx->gate_tvs)
-    if (g.d_tv) (void)hipFree(g.d_tv);
   for (auto& slot : ctx->ev_ring)
     for (auto& ev : slot)
     if (ev) (void)hipEventDestroy(ev);
@@ -781,11 +731,12 @@ int tfhe_measure_hbm_copy(tfhe_context* ctx, size_t bytes, int reps, double* gb_
   TFHE_TRY(check_ctx(ctx));
   if (!gb_per_s || bytes < 16 || reps <= 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "bytes >= 16, reps >= 1");
   bytes &= ~(size_t)15;
-  void *src = nullptr, *dst = nullptr;
+  DeviceBuffer src_buf, dst_buf;
+  TFHE_TRY(src_buf.grow(ctx, bytes));
+  TFHE_TRY(dst_buf.grow(ctx, bytes));
+  void *src = src_buf.as(), *dst = dst_buf.as();
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipError_t e = hipMalloc(&src, bytes);
-  if (e == hipSuccess) e = hipMalloc(&dst, bytes);
-  if (e == hipSuccess) e = hipMemsetAsync(src, 1, bytes, ctx->stream);
+  hipError_t e = hipMemsetAsync(src, 1, bytes, ctx->stream);
   if (e == hipSuccess) e = hipEventCreate(&e0);
   if (e == hipSuccess) e = hipEventCreate(&e1);
   for (int i = 0; i < 2 && e == hipSuccess; ++i) e = launch::stream_copy(ctx->stream, src, dst, bytes);
@@ -797,8 +748,6 @@ int tfhe_measure_hbm_copy(tfhe_context* ctx, size_t bytes, int reps, double* gb_
   if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  if (src) (void)hipFree(src);
-  if (dst) (void)hipFree(dst);
   if (e != hipSuccess) return hip_fail(ctx, e, "hbm copy probe");
   *gb_per_s = 2.0 * (double)bytes * reps / ((double)ms * 1e-3) / 1e9;  // read + write
   return TFHE_OK;
@@ -895,26 +844,14 @@ static int load_key_common(tfhe_context* ctx, const u32* d_bsk_raw, const u32* d
   // the key buffers are overwritten in place: until the new key is complete the context holds none (a failure half way
   // must not leave it bootstrapping under a half-written key)
   ctx->have_key = false;
-  if (ctx->d_bsk && ctx->bsk_ggsws != ggsws) {  // the other kind of key was loaded before
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    hipError_t e = hipFree(ctx->d_bsk);
-    ctx->d_bsk = nullptr;
-    if (e != hipSuccess) return hip_fail(ctx, e, "hipFree(bsk)");
-  }
-  if (!ctx->d_bsk) {
-    HIP_TRY(ctx, hipMalloc(&ctx->d_bsk, prepared_bsk_bytes(ctx, ggsws)));
-    ctx->bsk_ggsws = ggsws;
-  }
-  if (!ctx->d_ksk)
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_ksk), ksk_words(ctx) * sizeof(u32)));
-  HIP_TRY(ctx, launch::bsk_prepare(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->pbs.k, ctx->d_tw, d_bsk_raw, bsk_polys, ctx->d_bsk));
+  TFHE_TRY(ensure_key_buffers(ctx, ggsws, ks_matrix_admitted(ctx)));
+  HIP_TRY(ctx, launch::bsk_prepare(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->pbs.k, ctx->d_tw.as(), d_bsk_raw, bsk_polys, ctx->d_bsk.as()));
   if (ksk_needs_copy)
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ksk, d_ksk_raw, ksk_words(ctx) * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ksk.as<u32>(), d_ksk_raw, ksk_words(ctx) * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
   // the key-switching key's byte planes for the matrix cores, made once per key like the BSK's spectra
   if (ks_matrix_admitted(ctx)) {
-    if (!ctx->d_ksk_matrix) HIP_TRY(ctx, hipMalloc(&ctx->d_ksk_matrix, ksk_matrix_bytes(ctx)));
-    HIP_TRY(ctx, launch::ksk_prepare_matrix(ctx->stream, ctx->ks, ctx->big_n, ctx->params.lwe_dimension, ctx->d_ksk,
-                                            ctx->d_ksk_matrix));
+    HIP_TRY(ctx, launch::ksk_prepare_matrix(ctx->stream, ctx->ks, ctx->big_n, ctx->params.lwe_dimension, ctx->d_ksk.as<u32>(),
+                                            ctx->d_ksk_matrix.as()));
   }
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->have_key = true;
@@ -925,20 +862,19 @@ static int load_key_common(tfhe_context* ctx, const u32* d_bsk_raw, const u32* d
 static int load_key_host(tfhe_context* ctx, const uint32_t* bsk, const uint32_t* ksk, bool bmmp) {
   if (!bsk || !ksk) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null key pointer");
   const size_t bsk_words = key_ggsws(ctx, bmmp) * ggsw_words(ctx);
-  DeviceWords raw;
-  HIP_TRY(ctx, raw.alloc(bsk_words));
-  hipError_t e = hipMemcpy(raw.p, bsk, bsk_words * sizeof(u32), hipMemcpyHostToDevice);
-  if (e == hipSuccess && !ctx->d_ksk)
-    e = hipMalloc(reinterpret_cast<void**>(&ctx->d_ksk), ksk_words(ctx) * sizeof(u32));
+  DeviceBuffer raw;
+  TFHE_TRY(raw.grow(ctx, bsk_words * sizeof(u32)));
+  HIP_TRY(ctx, hipMemcpy(raw.as(), bsk, bsk_words * sizeof(u32), hipMemcpyHostToDevice));
+  // The key-switching key's buffer alone, absent only before a context's first key: the context still answers under
+  // the key it holds, so the prepared BSK is not touched here (ensure_key_buffers, in load_key_common, resizes it once
+  // that key is out of service).
+  TFHE_TRY(ctx->d_ksk.grow(ctx, ksk_words(ctx) * sizeof(u32)));
   // the key-switching key is overwritten in place by a copy that does not order itself behind the context's stream:
   // whatever was enqueued under the old key finishes first, and from here on the context holds no key
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e == hipSuccess) {
-    ctx->have_key = false;
-    e = hipMemcpy(ctx->d_ksk, ksk, ksk_words(ctx) * sizeof(u32), hipMemcpyHostToDevice);
-  }
-  if (e != hipSuccess) return hip_fail(ctx, e, "key upload");
-  return load_key_common(ctx, raw.p, nullptr, false, bmmp);
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->have_key = false;
+  HIP_TRY(ctx, hipMemcpy(ctx->d_ksk.as<u32>(), ksk, ksk_words(ctx) * sizeof(u32), hipMemcpyHostToDevice));
+  return load_key_common(ctx, raw.as<u32>(), nullptr, false, bmmp);
 }
 
 int tfhe_load_bootstrapping_key(tfhe_context* ctx, const uint32_t* bsk, const uint32_t* ksk) {
@@ -996,7 +932,7 @@ int tfhe_bootstrap_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_
   TFHE_TRY(check_ctx(ctx));
   TFHE_TRY(check_rotate_args(ctx, lwe_in, tv, lwe_out, batch, tv_count));
   TFHE_TRY(reserve(ctx, batch));
-  return enqueue_bootstrap(ctx, lwe_in, batch, tv, tv_count, ctx->d_lwe_big, lwe_out);
+  return enqueue_bootstrap(ctx, lwe_in, batch, tv, tv_count, ctx->d_lwe_big.as<u32>(), lwe_out);
 }
 
 int tfhe_bootstrap_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, const uint32_t* tv,
@@ -1005,10 +941,10 @@ int tfhe_bootstrap_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch
   TFHE_TRY(check_rotate_args(ctx, lwe_in, tv, lwe_out, batch, tv_count));
   TFHE_TRY(check_tv_host(ctx, tv, tv_count * ctx->N));
   TFHE_TRY(reserve(ctx, batch));
-  TFHE_TRY(upload(ctx, ctx->d_lwe_in, lwe_in, batch * io_words(ctx)));
-  TFHE_TRY(upload(ctx, ctx->d_tv, tv, tv_count * ctx->N));
-  TFHE_TRY(enqueue_bootstrap(ctx, ctx->d_lwe_in, batch, ctx->d_tv, tv_count, ctx->d_lwe_big, ctx->d_lwe_out));
-  return download_and_wait(ctx, lwe_out, ctx->d_lwe_out, batch * io_words(ctx));
+  TFHE_TRY(upload(ctx, ctx->d_lwe_in.as<u32>(), lwe_in, batch * io_words(ctx)));
+  TFHE_TRY(upload(ctx, ctx->d_tv.as<u32>(), tv, tv_count * ctx->N));
+  TFHE_TRY(enqueue_bootstrap(ctx, ctx->d_lwe_in.as<u32>(), batch, ctx->d_tv.as<u32>(), tv_count, ctx->d_lwe_big.as<u32>(), ctx->d_lwe_out.as<u32>()));
+  return download_and_wait(ctx, lwe_out, ctx->d_lwe_out.as<u32>(), batch * io_words(ctx));
 }
 
 int tfhe_blind_rotate_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch,
@@ -1025,10 +961,10 @@ int tfhe_blind_rotate_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t ba
   TFHE_TRY(check_rotate_args(ctx, lwe_in, tv, glwe_out, batch, tv_count));
   TFHE_TRY(check_tv_host(ctx, tv, tv_count * ctx->N));
   TFHE_TRY(reserve(ctx, batch));
-  TFHE_TRY(upload(ctx, ctx->d_lwe_in, lwe_in, batch * lwe_words(ctx)));
-  TFHE_TRY(upload(ctx, ctx->d_tv, tv, tv_count * ctx->N));
-  TFHE_TRY(rotate_device(ctx, ctx->d_lwe_in, batch, ctx->d_tv, tv_count, ctx->d_glwe_a, AccSource()));
-  return download_and_wait(ctx, glwe_out, ctx->d_glwe_a, batch * glwe_words(ctx));
+  TFHE_TRY(upload(ctx, ctx->d_lwe_in.as<u32>(), lwe_in, batch * lwe_words(ctx)));
+  TFHE_TRY(upload(ctx, ctx->d_tv.as<u32>(), tv, tv_count * ctx->N));
+  TFHE_TRY(rotate_device(ctx, ctx->d_lwe_in.as<u32>(), batch, ctx->d_tv.as<u32>(), tv_count, ctx->d_glwe_a.as<u32>(), AccSource()));
+  return download_and_wait(ctx, glwe_out, ctx->d_glwe_a.as<u32>(), batch * glwe_words(ctx));
 }
 
 // ------------------------------------------------- blind rotation / bootstrap from a GLWE accumulator
@@ -1044,10 +980,10 @@ int tfhe_blind_rotate_glwe_batch(tfhe_context* ctx, const uint32_t* lwe_in, size
   TFHE_TRY(check_ctx(ctx));
   TFHE_TRY(check_rotate_args(ctx, lwe_in, acc_in, glwe_out, batch, acc_count, &rotation_offset));
   TFHE_TRY(reserve(ctx, batch));
-  TFHE_TRY(upload(ctx, ctx->d_lwe_in, lwe_in, batch * lwe_words(ctx)));
-  TFHE_TRY(upload(ctx, ctx->d_glwe_a, acc_in, acc_count * glwe_words(ctx)));
-  TFHE_TRY(rotate_device(ctx, ctx->d_lwe_in, batch, ctx->d_glwe_a, acc_count, ctx->d_glwe_b, AccSource{true, (u32)rotation_offset}));
-  return download_and_wait(ctx, glwe_out, ctx->d_glwe_b, batch * glwe_words(ctx));
+  TFHE_TRY(upload(ctx, ctx->d_lwe_in.as<u32>(), lwe_in, batch * lwe_words(ctx)));
+  TFHE_TRY(upload(ctx, ctx->d_glwe_a.as<u32>(), acc_in, acc_count * glwe_words(ctx)));
+  TFHE_TRY(rotate_device(ctx, ctx->d_lwe_in.as<u32>(), batch, ctx->d_glwe_a.as<u32>(), acc_count, ctx->d_glwe_b.as<u32>(), AccSource{true, (u32)rotation_offset}));
+  return download_and_wait(ctx, glwe_out, ctx->d_glwe_b.as<u32>(), batch * glwe_words(ctx));
 }
 
 int tfhe_bootstrap_glwe_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, const uint32_t* acc_in,
@@ -1055,7 +991,7 @@ int tfhe_bootstrap_glwe_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, 
   TFHE_TRY(check_ctx(ctx));
   TFHE_TRY(check_rotate_args(ctx, lwe_in, acc_in, lwe_out, batch, acc_count, &rotation_offset));
   TFHE_TRY(reserve(ctx, batch));
-  return enqueue_bootstrap(ctx, lwe_in, batch, acc_in, acc_count, ctx->d_lwe_big, lwe_out, AccSource{true, (u32)rotation_offset});
+  return enqueue_bootstrap(ctx, lwe_in, batch, acc_in, acc_count, ctx->d_lwe_big.as<u32>(), lwe_out, AccSource{true, (u32)rotation_offset});
 }
 
 int tfhe_bootstrap_glwe_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, const uint32_t* acc_in,
@@ -1063,11 +999,11 @@ int tfhe_bootstrap_glwe_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t 
   TFHE_TRY(check_ctx(ctx));
   TFHE_TRY(check_rotate_args(ctx, lwe_in, acc_in, lwe_out, batch, acc_count, &rotation_offset));
   TFHE_TRY(reserve(ctx, batch));
-  TFHE_TRY(upload(ctx, ctx->d_lwe_in, lwe_in, batch * io_words(ctx)));
-  TFHE_TRY(upload(ctx, ctx->d_glwe_a, acc_in, acc_count * glwe_words(ctx)));
-  TFHE_TRY(enqueue_bootstrap(ctx, ctx->d_lwe_in, batch, ctx->d_glwe_a, acc_count, ctx->d_lwe_big, ctx->d_lwe_out,
+  TFHE_TRY(upload(ctx, ctx->d_lwe_in.as<u32>(), lwe_in, batch * io_words(ctx)));
+  TFHE_TRY(upload(ctx, ctx->d_glwe_a.as<u32>(), acc_in, acc_count * glwe_words(ctx)));
+  TFHE_TRY(enqueue_bootstrap(ctx, ctx->d_lwe_in.as<u32>(), batch, ctx->d_glwe_a.as<u32>(), acc_count, ctx->d_lwe_big.as<u32>(), ctx->d_lwe_out.as<u32>(),
                              AccSource{true, (u32)rotation_offset}));
-  return download_and_wait(ctx, lwe_out, ctx->d_lwe_out, batch * io_words(ctx));
+  return download_and_wait(ctx, lwe_out, ctx->d_lwe_out.as<u32>(), batch * io_words(ctx));
 }
 
 int tfhe_sample_extract_batch(tfhe_context* ctx, const uint32_t* glwe, size_t batch,
@@ -1077,10 +1013,10 @@ int tfhe_sample_extract_batch(tfhe_context* ctx, const uint32_t* glwe, size_t ba
   if (sample_index >= ctx->N)  // assert!(sample_index < degree), bootstrapping.rs:127
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "sample_index >= N (bootstrapping.rs:127)");
   TFHE_TRY(reserve(ctx, batch));
-  TFHE_TRY(upload(ctx, ctx->d_glwe_a, glwe, batch * glwe_words(ctx)));
-  HIP_TRY(ctx, launch::sample_extract(ctx->stream, ctx->pbs.log_n, ctx->pbs.k, ctx->d_glwe_a, batch,
-                                      (u32)sample_index, ctx->d_lwe_big));
-  return download_and_wait(ctx, lwe_out, ctx->d_lwe_big, batch * big_lwe_words(ctx));
+  TFHE_TRY(upload(ctx, ctx->d_glwe_a.as<u32>(), glwe, batch * glwe_words(ctx)));
+  HIP_TRY(ctx, launch::sample_extract(ctx->stream, ctx->pbs.log_n, ctx->pbs.k, ctx->d_glwe_a.as<u32>(), batch,
+                                      (u32)sample_index, ctx->d_lwe_big.as<u32>()));
+  return download_and_wait(ctx, lwe_out, ctx->d_lwe_big.as<u32>(), batch * big_lwe_words(ctx));
 }
 
 namespace {
@@ -1097,7 +1033,7 @@ int tfhe_key_switch_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size
   TFHE_TRY(check_key_switch_args(ctx, lwe_in, lwe_out, batch));
   TFHE_TRY(span_begin(ctx, kKeySwitchSpan));
   HIP_TRY(ctx, launch::key_switch(ctx->stream, ctx->ks, ctx->big_n, ctx->params.lwe_dimension, lwe_in,
-                                  batch, ctx->d_ksk, lwe_out, ctx->d_ksk_matrix, ctx->ks_path));
+                                  batch, ctx->d_ksk.as<u32>(), lwe_out, ctx->d_ksk_matrix.as(), ctx->ks_path));
   return span_end(ctx, kKeySwitchSpan);
 }
 
@@ -1105,9 +1041,9 @@ int tfhe_key_switch_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t batc
   TFHE_TRY(check_ctx(ctx));
   TFHE_TRY(check_key_switch_args(ctx, lwe_in, lwe_out, batch));
   TFHE_TRY(reserve(ctx, batch));
-  TFHE_TRY(upload(ctx, ctx->d_lwe_big, lwe_in, batch * big_lwe_words(ctx)));
-  TFHE_TRY(tfhe_key_switch_batch_device(ctx, ctx->d_lwe_big, batch, ctx->d_lwe_out));
-  return download_and_wait(ctx, lwe_out, ctx->d_lwe_out, batch * lwe_words(ctx));
+  TFHE_TRY(upload(ctx, ctx->d_lwe_big.as<u32>(), lwe_in, batch * big_lwe_words(ctx)));
+  TFHE_TRY(tfhe_key_switch_batch_device(ctx, ctx->d_lwe_big.as<u32>(), batch, ctx->d_lwe_out.as<u32>()));
+  return download_and_wait(ctx, lwe_out, ctx->d_lwe_out.as<u32>(), batch * lwe_words(ctx));
 }
 
 // ---------------------------------------------------------------------------------- ggsw.rs
@@ -1116,7 +1052,7 @@ int tfhe_prepare_ggsw_device(tfhe_context* ctx, const uint32_t* ggsw, size_t ggs
   TFHE_TRY(check_ctx(ctx));
   TFHE_TRY(check_present(ctx, {ggsw, ggsw_prepared}, ggsw_count, "null pointer / zero count"));
   const size_t polys = ggsw_count * ctx->R * (ctx->params.glwe_dimension + 1);
-  HIP_TRY(ctx, launch::bsk_prepare(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->pbs.k, ctx->d_tw, ggsw, polys, ggsw_prepared));
+  HIP_TRY(ctx, launch::bsk_prepare(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->pbs.k, ctx->d_tw.as(), ggsw, polys, ggsw_prepared));
   return TFHE_OK;
 }
 
@@ -1126,19 +1062,19 @@ int tfhe_external_product_prepared_device(tfhe_context* ctx, const void* ggsw_pr
   TFHE_TRY(check_ctx(ctx));
   TFHE_TRY(check_batch(ctx, {ggsw_prepared, glwe_in, glwe_out}, batch, ggsw_count, "ggsw_count", kProducts));
   TFHE_TRY(span_begin(ctx, kRotationSpan));
-  HIP_TRY(ctx, launch::external_product(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, ggsw_prepared,
+  HIP_TRY(ctx, launch::external_product(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw.as(), ggsw_prepared,
                                         ggsw_count == 1 ? 0 : prepared_ggsw_words(ctx), glwe_in,
-                                        nullptr, nullptr, batch, glwe_out, ctx->d_queue));
+                                        nullptr, nullptr, batch, glwe_out, ctx->d_queue.as<unsigned long long>()));
   return span_end(ctx, kRotationSpan);
 }
 
 // host GGSWs: uploaded raw, prepared into d_ggsw_tmp
 static int upload_and_prepare_ggsw(tfhe_context* ctx, const u32* ggsw, size_t ggsw_count) {
   const size_t words = ggsw_count * ggsw_words(ctx);
-  TFHE_TRY(ensure(ctx, &ctx->d_ggsw_raw, &ctx->ggsw_raw_words, words));
-  TFHE_TRY(ensure(ctx, &ctx->d_ggsw_tmp, &ctx->ggsw_tmp_words, words * ctx->parts));
-  TFHE_TRY(upload(ctx, ctx->d_ggsw_raw, ggsw, words));
-  return tfhe_prepare_ggsw_device(ctx, ctx->d_ggsw_raw, ggsw_count, ctx->d_ggsw_tmp);
+  TFHE_TRY(ctx->d_ggsw_raw.grow(ctx, words * sizeof(u32)));
+  TFHE_TRY(ctx->d_ggsw_tmp.grow(ctx, words * ctx->parts * sizeof(u64)));
+  TFHE_TRY(upload(ctx, ctx->d_ggsw_raw.as<u32>(), ggsw, words));
+  return tfhe_prepare_ggsw_device(ctx, ctx->d_ggsw_raw.as<u32>(), ggsw_count, ctx->d_ggsw_tmp.as());
 }
 
 int tfhe_external_product_batch(tfhe_context* ctx, const uint32_t* ggsw, size_t ggsw_count,
@@ -1147,10 +1083,10 @@ int tfhe_external_product_batch(tfhe_context* ctx, const uint32_t* ggsw, size_t 
   TFHE_TRY(check_batch(ctx, {ggsw, glwe_in, glwe_out}, batch, ggsw_count, "ggsw_count", kHostProducts));
   TFHE_TRY(reserve(ctx, batch));
   TFHE_TRY(upload_and_prepare_ggsw(ctx, ggsw, ggsw_count));
-  TFHE_TRY(upload(ctx, ctx->d_glwe_a, glwe_in, batch * glwe_words(ctx)));
-  TFHE_TRY(tfhe_external_product_prepared_device(ctx, ctx->d_ggsw_tmp, ggsw_count,
-                                                 ctx->d_glwe_a, batch, ctx->d_glwe_b));
-  return download_and_wait(ctx, glwe_out, ctx->d_glwe_b, batch * glwe_words(ctx));
+  TFHE_TRY(upload(ctx, ctx->d_glwe_a.as<u32>(), glwe_in, batch * glwe_words(ctx)));
+  TFHE_TRY(tfhe_external_product_prepared_device(ctx, ctx->d_ggsw_tmp.as(), ggsw_count,
+                                                 ctx->d_glwe_a.as<u32>(), batch, ctx->d_glwe_b.as<u32>()));
+  return download_and_wait(ctx, glwe_out, ctx->d_glwe_b.as<u32>(), batch * glwe_words(ctx));
 }
 
 int tfhe_cmux_batch(tfhe_context* ctx, const uint32_t* ggsw, size_t ggsw_count, const uint32_t* ct0,
@@ -1160,13 +1096,13 @@ int tfhe_cmux_batch(tfhe_context* ctx, const uint32_t* ggsw, size_t ggsw_count, 
   TFHE_TRY(reserve(ctx, batch));
   TFHE_TRY(upload_and_prepare_ggsw(ctx, ggsw, ggsw_count));
   const size_t words = batch * glwe_words(ctx);
-  TFHE_TRY(upload(ctx, ctx->d_glwe_a, ct0, words));
-  TFHE_TRY(upload(ctx, ctx->d_glwe_b, ct1, words));
-  HIP_TRY(ctx, launch::external_product(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, ctx->d_ggsw_tmp,
+  TFHE_TRY(upload(ctx, ctx->d_glwe_a.as<u32>(), ct0, words));
+  TFHE_TRY(upload(ctx, ctx->d_glwe_b.as<u32>(), ct1, words));
+  HIP_TRY(ctx, launch::external_product(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw.as(), ctx->d_ggsw_tmp.as(),
                                         ggsw_count == 1 ? 0 : prepared_ggsw_words(ctx), nullptr,
-                                        ctx->d_glwe_b, ctx->d_glwe_a, batch, ctx->d_glwe_c, ctx->d_queue));
-  TFHE_TRY(download(ctx, glwe_out, ctx->d_glwe_c, words));
-  return download_and_wait(ctx, ct1, ctx->d_glwe_b, words);
+                                        ctx->d_glwe_b.as<u32>(), ctx->d_glwe_a.as<u32>(), batch, ctx->d_glwe_c.as<u32>(), ctx->d_queue.as<unsigned long long>()));
+  TFHE_TRY(download(ctx, glwe_out, ctx->d_glwe_c.as<u32>(), words));
+  return download_and_wait(ctx, ct1, ctx->d_glwe_b.as<u32>(), words);
 }
 
 // ---------------------------------------------------------------------------------- CMUX tree / table lookup
@@ -1189,11 +1125,7 @@ int tree_plan_of(tfhe_context* ctx, bool demux, size_t trees, size_t depth, pass
   return TFHE_OK;
 }
 
-int grow_lookup_workspace(tfhe_context* ctx, size_t words) {
-  if (words <= ctx->lookup_ws_words) return TFHE_OK;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return ensure(ctx, &ctx->d_lookup_ws, &ctx->lookup_ws_words, words);
-}
+int grow_lookup_workspace(tfhe_context* ctx, size_t words) { return ctx->d_lookup_ws.grow(ctx, words * sizeof(u32)); }
 
 // What a tree / lookup call reads its leaves from: GLWEs [sets][tables][2^depth][k+1][N] or a clear table
 // [sets][tables][2^address_bits]
@@ -1209,15 +1141,15 @@ int run_lookup(tfhe_context* ctx, const void* selectors, size_t queries, size_t 
                const LookupLeaves& leaves, size_t tables, u32* glwe_out, u32* lwe_out) {
   passes::TreePlan plan{};
   TFHE_TRY(tree_plan_of(ctx, false, queries * tables, tree_depth, &plan));
-  if (plan.workspace_words > ctx->lookup_ws_words)
+  if (plan.workspace_words > ctx->d_lookup_ws.words())
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
                 "the call needs " + std::to_string(plan.workspace_words) + " words of lookup workspace, " +
-                    std::to_string(ctx->lookup_ws_words) + " are reserved (tfhe_context_reserve_lookup)");
+                    std::to_string(ctx->d_lookup_ws.words()) + " are reserved (tfhe_context_reserve_lookup)");
   const passes::LookupCall call{selectors, prepared_ggsw_words(ctx), glwe_words(ctx), queries, address_bits, first, tree_depth,
                                 leaves.glwe, leaves.table, leaves.shared, tables, glwe_out, lwe_out};
   size_t ws_words = 0;
-  return passes::lookup_passes(plan, call, ctx->d_lookup_ws, &ws_words, [&](const CmuxTreePass& pass, size_t teams) {
-    HIP_TRY(ctx, launch::cmux_tree_pass(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, pass, teams));
+  return passes::lookup_passes(plan, call, ctx->d_lookup_ws.as<u32>(), &ws_words, [&](const CmuxTreePass& pass, size_t teams) {
+    HIP_TRY(ctx, launch::cmux_tree_pass(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw.as(), pass, teams));
     return (int)TFHE_OK;
   });
 }
@@ -1282,7 +1214,7 @@ int tfhe_cmux_prepared_device(tfhe_context* ctx, const void* ggsw_prepared, size
   pass.odd = ct1;
   pass.set_stride = glwe_words(ctx);
   pass.glwe_out = glwe_out;
-  HIP_TRY(ctx, launch::cmux_tree_pass(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, pass, batch));
+  HIP_TRY(ctx, launch::cmux_tree_pass(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw.as(), pass, batch));
   return TFHE_OK;
 }
 
@@ -1317,8 +1249,8 @@ static int lookup_host(tfhe_context* ctx, const uint32_t* selectors, size_t quer
   TFHE_TRY(s.reserve());
   TFHE_TRY(upload_and_prepare_ggsw(ctx, selectors, queries * depth));
   TFHE_TRY(s.upload(kIn, data));
-  TFHE_TRY(is_table ? tfhe_table_lookup_device(ctx, ctx->d_ggsw_tmp, queries, depth, s[kIn], sets, tables, s[kOut])
-                    : tfhe_cmux_tree_device(ctx, ctx->d_ggsw_tmp, queries, depth, s[kIn], sets, tables, s[kOut]));
+  TFHE_TRY(is_table ? tfhe_table_lookup_device(ctx, ctx->d_ggsw_tmp.as(), queries, depth, s[kIn], sets, tables, s[kOut])
+                    : tfhe_cmux_tree_device(ctx, ctx->d_ggsw_tmp.as(), queries, depth, s[kIn], sets, tables, s[kOut]));
   return s.download_and_wait(kOut, out);
 }
 
@@ -1341,11 +1273,7 @@ int tfhe_table_lookup(tfhe_context* ctx, const uint32_t* selectors, size_t queri
 // reverse (passes.h): the top pass takes what ceil(d / h) - 1 passes of h levels leave over.
 namespace {
 
-int grow_demux_workspace(tfhe_context* ctx, size_t words) {
-  if (words <= ctx->demux_ws_words) return TFHE_OK;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return ensure(ctx, &ctx->d_demux_ws, &ctx->demux_ws_words, words);
-}
+int grow_demux_workspace(tfhe_context* ctx, size_t words) { return ctx->d_demux_ws.grow(ctx, words * sizeof(u32)); }
 
 bool overlap(const void* a, size_t a_words, const void* b, size_t b_words) {
   const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
@@ -1363,15 +1291,15 @@ int run_demux(tfhe_context* ctx, const void* selectors, size_t queries, size_t a
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "the output overlaps the input");
   passes::TreePlan plan{};
   TFHE_TRY(tree_plan_of(ctx, true, trees, tree_depth, &plan));
-  if (plan.workspace_words > ctx->demux_ws_words)
+  if (plan.workspace_words > ctx->d_demux_ws.words())
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
                 "the call needs " + std::to_string(plan.workspace_words * sizeof(u32)) + " bytes of demux workspace, " +
-                    std::to_string(ctx->demux_ws_words * sizeof(u32)) + " are reserved (tfhe_context_reserve_demux)");
+                    std::to_string(ctx->d_demux_ws.bytes()) + " are reserved (tfhe_context_reserve_demux)");
   const passes::DemuxCall call{selectors, prepared_ggsw_words(ctx), glwe, queries, address_bits, rot_steps, tree_depth,
                                roots, values, leaves, shared, accumulate};
   size_t ws_words = 0;
-  return passes::demux_passes(plan, call, ctx->d_demux_ws, &ws_words, [&](const DemuxTreePass& pass, size_t teams) {
-    HIP_TRY(ctx, launch::demux_tree_pass(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, pass, teams));
+  return passes::demux_passes(plan, call, ctx->d_demux_ws.as<u32>(), &ws_words, [&](const DemuxTreePass& pass, size_t teams) {
+    HIP_TRY(ctx, launch::demux_tree_pass(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw.as(), pass, teams));
     return (int)TFHE_OK;
   });
 }
@@ -1462,8 +1390,8 @@ static int demux_host(tfhe_context* ctx, const uint32_t* selectors, size_t queri
   TFHE_TRY(upload_and_prepare_ggsw(ctx, selectors, queries * depth));
   TFHE_TRY(s.upload(kIn, in));
   if (accumulate) TFHE_TRY(s.upload(kOut, out));
-  TFHE_TRY(is_write ? tfhe_table_write_device(ctx, ctx->d_ggsw_tmp, queries, depth, s[kIn], s[kOut], sets, values)
-                    : tfhe_demux_tree_device(ctx, ctx->d_ggsw_tmp, queries, depth, s[kIn], values, s[kOut], sets, accumulate));
+  TFHE_TRY(is_write ? tfhe_table_write_device(ctx, ctx->d_ggsw_tmp.as(), queries, depth, s[kIn], s[kOut], sets, values)
+                    : tfhe_demux_tree_device(ctx, ctx->d_ggsw_tmp.as(), queries, depth, s[kIn], values, s[kOut], sets, accumulate));
   return s.download_and_wait(kOut, out);
 }
 
@@ -1496,7 +1424,7 @@ int tfhe_table_lookup_glwe(tfhe_context* ctx, const uint32_t* selectors, size_t 
   TFHE_TRY(s.reserve());
   TFHE_TRY(upload_and_prepare_ggsw(ctx, selectors, queries * depth));
   TFHE_TRY(s.upload(kIn, leaves));
-  TFHE_TRY(tfhe_table_lookup_glwe_device(ctx, ctx->d_ggsw_tmp, queries, depth, s[kIn], leaf_sets, tables, s[kOut]));
+  TFHE_TRY(tfhe_table_lookup_glwe_device(ctx, ctx->d_ggsw_tmp.as(), queries, depth, s[kIn], leaf_sets, tables, s[kOut]));
   return s.download_and_wait(kOut, lwe_out);
 }
 
@@ -1569,10 +1497,9 @@ int reserve_program(tfhe_context* ctx, size_t queries, size_t nodes, size_t outp
   const size_t values = std::max<size_t>(1, queries * nodes * glwe_words(ctx)), image = program_image_need(nodes, outputs);
   if (values <= ctx->program_value_words && image <= ctx->program_image_words) return TFHE_OK;
   const size_t new_values = std::max(values, ctx->program_value_words), new_image = std::max(image, ctx->program_image_words);
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   for (auto& im : ctx->program_images) im = tfhe_context::ProgramImage{};
   ctx->program_value_words = ctx->program_image_words = 0;
-  TFHE_TRY(ensure(ctx, &ctx->d_program_ws, &ctx->program_ws_words, new_values + tfhe_context::kProgramImages * new_image));
+  TFHE_TRY(ctx->d_program_ws.grow(ctx, (new_values + tfhe_context::kProgramImages * new_image) * sizeof(u32)));
   ctx->program_value_words = new_values;
   ctx->program_image_words = new_image;
   return TFHE_OK;
@@ -1606,7 +1533,7 @@ int program_image(tfhe_context* ctx, const ProgramArgs& a, u32** d_image, const 
     std::vector<u32> image(program_image_need(a.n_nodes, a.n_outputs));
     passes::program_image(reinterpret_cast<const u32*>(a.nodes), order, a.outputs, a.n_outputs, image.data());
     slot->key.clear();  // not a valid entry until the upload has succeeded
-    u32* dst = ctx->d_program_ws + ctx->program_value_words + (size_t)(slot - ctx->program_images) * ctx->program_image_words;
+    u32* dst = ctx->d_program_ws.as<u32>() + ctx->program_value_words + (size_t)(slot - ctx->program_images) * ctx->program_image_words;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // launches of the image this one replaces may be in flight
     HIP_TRY(ctx, hipMemcpy(dst, image.data(), image.size() * sizeof(u32), hipMemcpyHostToDevice));
     slot->key = std::move(key);
@@ -1614,7 +1541,7 @@ int program_image(tfhe_context* ctx, const ProgramArgs& a, u32** d_image, const 
   }
   slot->last_use = ++ctx->program_clock;
   if (capturing) slot->pinned = true;
-  *d_image = ctx->d_program_ws + ctx->program_value_words + (size_t)(slot - ctx->program_images) * ctx->program_image_words;
+  *d_image = ctx->d_program_ws.as<u32>() + ctx->program_value_words + (size_t)(slot - ctx->program_images) * ctx->program_image_words;
   *counts = &slot->level_counts;
   return TFHE_OK;
 }
@@ -1666,7 +1593,7 @@ int tfhe_cmux_program_device(tfhe_context* ctx, const void* selectors_prepared, 
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
                 "the call needs " + std::to_string(program_bytes(ctx, queries, n_nodes, n_outputs)) + " bytes of program workspace (" +
                     std::to_string(queries) + " queries, " + std::to_string(n_nodes) + " nodes, " + std::to_string(n_outputs) +
-                    " outputs), " + std::to_string(ctx->program_ws_words * sizeof(u32)) + " are reserved (tfhe_context_reserve_program)");
+                    " outputs), " + std::to_string(ctx->d_program_ws.bytes()) + " are reserved (tfhe_context_reserve_program)");
   u32* d_image = nullptr;
   const std::vector<u32>* counts = nullptr;
   TFHE_TRY(program_image(ctx, a, &d_image, &counts));
@@ -1674,9 +1601,9 @@ int tfhe_cmux_program_device(tfhe_context* ctx, const void* selectors_prepared, 
   passes::ProgramPlan info{};
   TFHE_TRY(plan_program_of(ctx, queries, *counts, n_outputs, &plan, &info));
   const passes::ProgramCall call{selectors_prepared, selector_sets == 1 ? 0 : n_inputs * prepared_ggsw_words(ctx), d_image, terminals,
-                                 (u32)n_terminals, (u32)n_nodes, (u32)n_outputs, ctx->d_program_ws, glwe_out, lwe_out};
+                                 (u32)n_terminals, (u32)n_nodes, (u32)n_outputs, ctx->d_program_ws.as<u32>(), glwe_out, lwe_out};
   return passes::program_passes(plan.data(), plan.size(), call, [&](const CmuxProgramPass& pass) {
-    HIP_TRY(ctx, launch::cmux_program_pass(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw, pass, queries));
+    HIP_TRY(ctx, launch::cmux_program_pass(ctx->stream, ctx->field, ctx->pbs, ctx->d_tw.as(), pass, queries));
     return (int)TFHE_OK;
   });
 }
@@ -1696,7 +1623,7 @@ int tfhe_cmux_program(tfhe_context* ctx, const uint32_t* selectors, size_t queri
   TFHE_TRY(s.reserve());
   if (n_nodes > 0) TFHE_TRY(upload_and_prepare_ggsw(ctx, selectors, selector_sets * n_inputs));
   TFHE_TRY(s.upload(kTerminals, terminals));
-  TFHE_TRY(tfhe_cmux_program_device(ctx, n_nodes > 0 ? ctx->d_ggsw_tmp : nullptr, queries, n_inputs, selector_sets, nodes, n_nodes,
+  TFHE_TRY(tfhe_cmux_program_device(ctx, n_nodes > 0 ? ctx->d_ggsw_tmp.as() : nullptr, queries, n_inputs, selector_sets, nodes, n_nodes,
                                     s[kTerminals], n_terminals, outputs, n_outputs, glwe_out ? s[kGlwe] : nullptr,
                                     lwe_out ? s[kLwe] : nullptr));
   if (glwe_out && lwe_out) TFHE_TRY(download(ctx, glwe_out, s[kGlwe], queries * n_outputs * glwe_words(ctx)));
@@ -1830,12 +1757,8 @@ size_t dense_row_words(const tfhe_context* ctx) { return std::max(lwe_words(ctx)
 int reserve_dense(tfhe_context* ctx, size_t rows) {
   TFHE_TRY(reserve(ctx, rows));
   if (rows <= ctx->dense_rows) return TFHE_OK;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->dense_rows = 0;
-  size_t have = 0;
-  if (ctx->d_dense_ws) HIP_TRY(ctx, hipFree(ctx->d_dense_ws));
-  ctx->d_dense_ws = nullptr;
-  TFHE_TRY(ensure(ctx, &ctx->d_dense_ws, &have, rows * dense_row_words(ctx)));
+  TFHE_TRY(ctx->d_dense_ws.grow(ctx, rows * dense_row_words(ctx) * sizeof(u32)));
   ctx->dense_rows = rows;
   return TFHE_OK;
 }
@@ -1921,15 +1844,15 @@ int tfhe_dense_bootstrap_batch_device(tfhe_context* ctx, const uint32_t* x, size
                     std::to_string(queries) + " queries, " + std::to_string(outputs) + " outputs), " +
                     std::to_string(ctx->dense_rows * dense_row_words(ctx) * sizeof(u32)) +
                     " are reserved (tfhe_context_reserve_dense)");
-  u32* pre = ctx->d_dense_ws;
-  u32* tvs = ctx->d_dense_ws + ctx->dense_rows * (dense_row_words(ctx) - ctx->N);
+  u32* pre = ctx->d_dense_ws.as<u32>();
+  u32* tvs = ctx->d_dense_ws.as<u32>() + ctx->dense_rows * (dense_row_words(ctx) - ctx->N);
   TFHE_TRY(enqueue_dense(ctx, x, d, weights, bias, pre));
   const u32* tv = test_vector_poly;
   if (tv_count != 1) {  // the rotation reads bootstrap r's test vector at r * N: neuron r % O's
     HIP_TRY(ctx, launch::dense_tile_rows(ctx->stream, test_vector_poly, outputs, rows, ctx->N, tvs));
     tv = tvs;
   }
-  return enqueue_bootstrap(ctx, pre, rows, tv, tv_count == 1 ? 1 : rows, ctx->d_lwe_big, lwe_out);
+  return enqueue_bootstrap(ctx, pre, rows, tv, tv_count == 1 ? 1 : rows, ctx->d_lwe_big.as<u32>(), lwe_out);
 }
 
 int tfhe_dense_bootstrap_batch(tfhe_context* ctx, const uint32_t* x, size_t queries, size_t inputs, const int32_t* weights,
@@ -1976,14 +1899,8 @@ size_t conv_poly_bytes(const tfhe_context* ctx) { return (size_t)ctx->parts * ct
 
 int reserve_conv(tfhe_context* ctx, size_t polys) {
   if (polys <= ctx->conv_ws_polys) return TFHE_OK;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->conv_ws_polys = 0;
-  if (ctx->d_conv_ws) {
-    hipError_t e = hipFree(ctx->d_conv_ws);
-    ctx->d_conv_ws = nullptr;
-    if (e != hipSuccess) return hip_fail(ctx, e, "hipFree(conv workspace)");
-  }
-  HIP_TRY(ctx, hipMalloc(&ctx->d_conv_ws, polys * conv_poly_bytes(ctx)));
+  TFHE_TRY(ctx->d_conv_ws.grow(ctx, polys * conv_poly_bytes(ctx)));
   ctx->conv_ws_polys = polys;
   return TFHE_OK;
 }
@@ -2041,16 +1958,19 @@ int tfhe_prepare_poly_weights(tfhe_context* ctx, const int32_t* weights, size_t 
   w->channels = channels;
   w->weight_bits = (unsigned)bits;
   w->rows_per_pass = rows;
-  DeviceWords raw;
-  hipError_t e = raw.alloc(words);
-  if (e == hipSuccess) e = hipMalloc(&w->d_spec, polys * (size_t)ctx->N * sizeof(u64));
-  if (e == hipSuccess) e = hipMemcpyAsync(raw.p, weights, words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess)
-    e = launch::conv_weights(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->d_tw, reinterpret_cast<const i32*>(raw.p), polys, w->d_spec);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the staging buffer goes away with this call
-  if (e != hipSuccess) {
+  DeviceBuffer raw;
+  int st = raw.grow(ctx, words * sizeof(u32));
+  if (st == TFHE_OK) st = w->d_spec.grow(ctx, polys * (size_t)ctx->N * sizeof(u64));
+  if (st == TFHE_OK) {
+    hipError_t e = hipMemcpyAsync(raw.as(), weights, words * sizeof(u32), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess)
+      e = launch::conv_weights(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->d_tw.as(), raw.as<const i32>(), polys, w->d_spec.as());
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the staging buffer goes away with this call
+    if (e != hipSuccess) st = hip_fail(ctx, e, "tfhe_prepare_poly_weights");
+  }
+  if (st != TFHE_OK) {
     tfhe_poly_weights_destroy(w);
-    return hip_fail(ctx, e, "tfhe_prepare_poly_weights");
+    return st;
   }
   *out = w;
   return TFHE_OK;
@@ -2058,7 +1978,7 @@ int tfhe_prepare_poly_weights(tfhe_context* ctx, const int32_t* weights, size_t 
 
 void tfhe_poly_weights_destroy(tfhe_poly_weights* weights) {
   if (!weights) return;
-  if (weights->d_spec && hipSetDevice(weights->device) == hipSuccess) (void)hipFree(weights->d_spec);
+  (void)hipSetDevice(weights->device);  // before `delete` releases the spectra
   delete weights;
 }
 
@@ -2115,9 +2035,9 @@ int tfhe_glwe_conv_batch_device(tfhe_context* ctx, const uint32_t* x, size_t que
                 "the call needs " + std::to_string(polys * conv_poly_bytes(ctx)) + " bytes of convolution workspace (" +
                     std::to_string(queries) + " queries, " + std::to_string(weights->channels) + " channels), " +
                     std::to_string(ctx->conv_ws_polys * conv_poly_bytes(ctx)) + " are reserved (tfhe_context_reserve_glwe_conv)");
-  HIP_TRY(ctx, launch::bsk_prepare(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->pbs.k, ctx->d_tw, x, polys, ctx->d_conv_ws));
-  const GlweConvArgs args{ctx->d_conv_ws, weights->d_spec, bias, out, (u32)weights->channels, (u32)weights->outputs, plan.rows_per_pass};
-  HIP_TRY(ctx, launch::glwe_conv(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->pbs.k, ctx->d_tw, args, queries));
+  HIP_TRY(ctx, launch::bsk_prepare(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->pbs.k, ctx->d_tw.as(), x, polys, ctx->d_conv_ws.as()));
+  const GlweConvArgs args{ctx->d_conv_ws.as(), weights->d_spec.as(), bias, out, (u32)weights->channels, (u32)weights->outputs, plan.rows_per_pass};
+  HIP_TRY(ctx, launch::glwe_conv(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->pbs.k, ctx->d_tw.as(), args, queries));
   return TFHE_OK;
 }
 
@@ -2180,14 +2100,10 @@ int check_binary(tfhe_context* ctx, const u32* sk, size_t words, const char* wha
   return TFHE_OK;
 }
 
-int ensure_key_tmp(tfhe_context* ctx, size_t words) {
-  if (words <= ctx->key_tmp_words) return TFHE_OK;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return ensure(ctx, &ctx->d_key_tmp, &ctx->key_tmp_words, words);
-}
+int ensure_key_tmp(tfhe_context* ctx, size_t words) { return ctx->d_key_tmp.grow(ctx, words * sizeof(u32)); }
 
 int to_key_tmp(tfhe_context* ctx, const u32* host, size_t words, size_t at) {
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_key_tmp + at, host, words * sizeof(u32), hipMemcpyHostToDevice,
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_key_tmp.as<u32>() + at, host, words * sizeof(u32), hipMemcpyHostToDevice,
                               ctx->stream));
   return TFHE_OK;
 }
@@ -2195,8 +2111,8 @@ int to_key_tmp(tfhe_context* ctx, const u32* host, size_t words, size_t at) {
 // rows of GLWE ciphertexts [rows][k+1][N] on the device; sk already at d_key_tmp[0 .. kN)
 int glwe_rows_add_mask_dot_key(tfhe_context* ctx, u32* d_rows, size_t rows) {
   const u32 k = ctx->params.glwe_dimension;
-  HIP_TRY(ctx, launch::glwe_body(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->d_tw, k, d_rows, rows,
-                                 ctx->d_key_tmp, d_rows + (size_t)k * ctx->N,
+  HIP_TRY(ctx, launch::glwe_body(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->d_tw.as(), k, d_rows, rows,
+                                 ctx->d_key_tmp.as<u32>(), d_rows + (size_t)k * ctx->N,
                                  (size_t)(k + 1) * ctx->N, false));
   return TFHE_OK;
 }
@@ -2209,8 +2125,8 @@ int ksk_gen_device(tfhe_context* ctx, const u32* from_sk, size_t from_dim, const
   TFHE_TRY(ensure_key_tmp(ctx, to_dim + rows));
   TFHE_TRY(to_key_tmp(ctx, to_sk, to_dim, 0));
   TFHE_TRY(to_key_tmp(ctx, factor.data(), rows, to_dim));
-  HIP_TRY(ctx, launch::lwe_body(ctx->stream, d_ksk, rows, (u32)to_dim, ctx->d_key_tmp,
-                                ctx->d_key_tmp + to_dim, d_ksk + to_dim, to_dim + 1, false));
+  HIP_TRY(ctx, launch::lwe_body(ctx->stream, d_ksk, rows, (u32)to_dim, ctx->d_key_tmp.as<u32>(),
+                                ctx->d_key_tmp.as<u32>() + to_dim, d_ksk + to_dim, to_dim + 1, false));
   // `factor` is pageable host memory: the async copy has staged it before returning
   return TFHE_OK;
 }
@@ -2248,8 +2164,8 @@ int tfhe_glwe_decrypt_batch(tfhe_context* ctx, const uint32_t* glwe_sk, const ui
   TFHE_TRY(s.reserve());
   TFHE_TRY(to_key_tmp(ctx, glwe_sk, kn, 0));
   TFHE_TRY(s.upload(kIn, glwe));
-  HIP_TRY(ctx, launch::glwe_body(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->d_tw, k, s[kIn], count,
-                                 ctx->d_key_tmp, s[kOut], ctx->N, true));
+  HIP_TRY(ctx, launch::glwe_body(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->d_tw.as(), k, s[kIn], count,
+                                 ctx->d_key_tmp.as<u32>(), s[kOut], ctx->N, true));
   return s.download_and_wait(kOut, plaintext_out);
 }
 
@@ -2266,7 +2182,7 @@ int tfhe_ggsw_encrypt_batch_device(tfhe_context* ctx, const uint32_t* glwe_sk, c
   TFHE_TRY(glwe_rows_add_mask_dot_key(ctx, ggsw, count * ctx->R));
   HIP_TRY(ctx, launch::ggsw_add_gadget(ctx->stream, ggsw, count, k, ctx->pbs.log_n, ctx->pbs.levels,
                                        ctx->pbs.log_base, gadget_top(ctx, ctx->pbs.log_base),
-                                       ctx->d_key_tmp + kn));
+                                       ctx->d_key_tmp.as<u32>() + kn));
   return TFHE_OK;
 }
 
@@ -2286,7 +2202,7 @@ int tfhe_lwe_encrypt_batch_device(tfhe_context* ctx, const uint32_t* lwe_sk, siz
   TFHE_TRY(check_binary(ctx, lwe_sk, dimension, "lwe secret key"));
   TFHE_TRY(ensure_key_tmp(ctx, dimension));
   TFHE_TRY(to_key_tmp(ctx, lwe_sk, dimension, 0));
-  HIP_TRY(ctx, launch::lwe_body(ctx->stream, lwe, batch, (u32)dimension, ctx->d_key_tmp, plaintexts,
+  HIP_TRY(ctx, launch::lwe_body(ctx->stream, lwe, batch, (u32)dimension, ctx->d_key_tmp.as<u32>(), plaintexts,
                                 lwe + dimension, dimension + 1, false));
   return TFHE_OK;
 }
@@ -2312,7 +2228,7 @@ int tfhe_lwe_decrypt_batch_device(tfhe_context* ctx, const uint32_t* lwe_sk, siz
   TFHE_TRY(check_binary(ctx, lwe_sk, dimension, "lwe secret key"));
   TFHE_TRY(ensure_key_tmp(ctx, dimension));
   TFHE_TRY(to_key_tmp(ctx, lwe_sk, dimension, 0));
-  HIP_TRY(ctx, launch::lwe_body(ctx->stream, lwe, batch, (u32)dimension, ctx->d_key_tmp, nullptr,
+  HIP_TRY(ctx, launch::lwe_body(ctx->stream, lwe, batch, (u32)dimension, ctx->d_key_tmp.as<u32>(), nullptr,
                                 plaintext_out, 1, true));
   return TFHE_OK;
 }
@@ -2373,16 +2289,16 @@ static int key_gen_host(tfhe_context* ctx, const u32* lwe_sk, const u32* glwe_sk
   TFHE_TRY(check_present(ctx, {lwe_sk, glwe_sk, bsk, ksk}, 1, "null pointer"));
   if (bmmp) TFHE_TRY(check_bmmp(ctx));
   const size_t bsk_bytes = key_ggsws(ctx, bmmp) * ggsw_words(ctx) * sizeof(u32), ksk_bytes = ksk_words(ctx) * sizeof(u32);
-  DeviceWords d_bsk, d_ksk;
-  hipError_t e = d_bsk.alloc(bsk_bytes / sizeof(u32));
-  if (e == hipSuccess) e = d_ksk.alloc(ksk_bytes / sizeof(u32));
-  if (e == hipSuccess) e = hipMemcpy(d_bsk.p, bsk, bsk_bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_ksk.p, ksk, ksk_bytes, hipMemcpyHostToDevice);
+  DeviceBuffer d_bsk, d_ksk;
+  TFHE_TRY(d_bsk.grow(ctx, bsk_bytes));
+  TFHE_TRY(d_ksk.grow(ctx, ksk_bytes));
+  hipError_t e = hipMemcpy(d_bsk.as(), bsk, bsk_bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_ksk.as(), ksk, ksk_bytes, hipMemcpyHostToDevice);
   if (e != hipSuccess) return hip_fail(ctx, e, "key buffers");
-  TFHE_TRY(key_gen_device(ctx, lwe_sk, glwe_sk, d_bsk.p, d_ksk.p, load, bmmp));
+  TFHE_TRY(key_gen_device(ctx, lwe_sk, glwe_sk, d_bsk.as<u32>(), d_ksk.as<u32>(), load, bmmp));
   e = hipStreamSynchronize(ctx->stream);
-  if (e == hipSuccess) e = hipMemcpy(bsk, d_bsk.p, bsk_bytes, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(ksk, d_ksk.p, ksk_bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(bsk, d_bsk.as(), bsk_bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(ksk, d_ksk.as(), ksk_bytes, hipMemcpyDeviceToHost);
   return e == hipSuccess ? TFHE_OK : hip_fail(ctx, e, "key download");
 }
 
@@ -2434,26 +2350,13 @@ int load_packing_key_common(tfhe_context* ctx, const u32* d_raw, size_t from_dim
   const size_t bytes = slices * k1 * ctx->ks.levels * k1 * poly_bytes;
   // until the new key is complete the context holds none
   ctx->have_pksk = false;
-  if (ctx->d_pksk && ctx->pksk_bytes != bytes) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    hipError_t e = hipFree(ctx->d_pksk);
-    ctx->d_pksk = nullptr;
-    if (e != hipSuccess) return hip_fail(ctx, e, "hipFree(pksk)");
-  }
-  if (!ctx->d_pksk) {
-    HIP_TRY(ctx, hipMalloc(&ctx->d_pksk, bytes));
-    ctx->pksk_bytes = bytes;
-  }
+  TFHE_TRY(ctx->d_pksk.resize(ctx, bytes));
   ctx->pksk_dim = from_dimension;
-  const size_t want_cols = std::max(kPackColsWords, pack_cols_words_per_group(ctx));
-  if (ctx->pack_cols_words < want_cols) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    TFHE_TRY(ensure(ctx, &ctx->d_pack_cols, &ctx->pack_cols_words, want_cols));
-  }
+  TFHE_TRY(ctx->d_pack_cols.grow(ctx, std::max(kPackColsWords, pack_cols_words_per_group(ctx)) * sizeof(u32)));
   // rows past from_dimension (the last slice, when k+1 does not divide it): zero spectra
   if (polys * poly_bytes < bytes)
-    HIP_TRY(ctx, hipMemsetAsync(static_cast<unsigned char*>(ctx->d_pksk) + polys * poly_bytes, 0, bytes - polys * poly_bytes, ctx->stream));
-  HIP_TRY(ctx, launch::bsk_prepare(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->pbs.k, ctx->d_tw, d_raw, polys, ctx->d_pksk));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_pksk.as<unsigned char>() + polys * poly_bytes, 0, bytes - polys * poly_bytes, ctx->stream));
+  HIP_TRY(ctx, launch::bsk_prepare(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->pbs.k, ctx->d_tw.as(), d_raw, polys, ctx->d_pksk.as()));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->have_pksk = true;
   return TFHE_OK;
@@ -2478,12 +2381,12 @@ int enqueue_pack(tfhe_context* ctx, const u32* lwe_in, size_t groups, u32 per_gr
   const size_t glwe = glwe_words(ctx);
   const PbsParams P = packing_params(ctx);
   HIP_TRY(ctx, hipMemsetAsync(glwe_out, 0, groups * glwe * sizeof(u32), ctx->stream));
-  const size_t chunk = ctx->pack_cols_words / pack_cols_words_per_group(ctx);  // >= 1 by construction
+  const size_t chunk = ctx->d_pack_cols.words() / pack_cols_words_per_group(ctx);  // >= 1 by construction
   for (size_t g0 = 0; g0 < groups; g0 += chunk) {
     const size_t here = std::min(chunk, groups - g0);
     HIP_TRY(ctx, launch::pack_transpose(ctx->stream, lwe_in + g0 * per_group * ((size_t)d + 1), here, per_group, d,
-                                        ctx->pbs.log_n, ctx->d_pack_cols, log_rep));
-    HIP_TRY(ctx, launch::pack_lwe(ctx->stream, ctx->field, P, ctx->d_tw, ctx->d_pksk, ctx->d_pack_cols, d, here,
+                                        ctx->pbs.log_n, ctx->d_pack_cols.as<u32>(), log_rep));
+    HIP_TRY(ctx, launch::pack_lwe(ctx->stream, ctx->field, P, ctx->d_tw.as(), ctx->d_pksk.as(), ctx->d_pack_cols.as<u32>(), d, here,
                                   glwe_out + g0 * glwe));
   }
   return TFHE_OK;
@@ -2505,7 +2408,7 @@ int tfhe_generate_packing_key_device(tfhe_context* ctx, const uint32_t* from_sk,
   TFHE_TRY(to_key_tmp(ctx, glwe_sk, kn, 0));
   TFHE_TRY(to_key_tmp(ctx, factor.data(), rows, kn));
   TFHE_TRY(glwe_rows_add_mask_dot_key(ctx, pksk, rows));
-  HIP_TRY(ctx, launch::packing_add_gadget(ctx->stream, pksk, rows, ctx->params.glwe_dimension, ctx->pbs.log_n, ctx->d_key_tmp + kn));
+  HIP_TRY(ctx, launch::packing_add_gadget(ctx->stream, pksk, rows, ctx->params.glwe_dimension, ctx->pbs.log_n, ctx->d_key_tmp.as<u32>() + kn));
   // `factor` is pageable host memory: the async copy has staged it before returning
   return TFHE_OK;
 }
@@ -2531,11 +2434,10 @@ int tfhe_load_packing_key(tfhe_context* ctx, const uint32_t* pksk, size_t from_d
   const std::string why = packing_refusal(ctx);  // before the upload
   if (!why.empty()) return fail(ctx, TFHE_ERR_EXACTNESS, "packing key refused: " + why);
   const size_t words = packing_key_words(ctx, from_dimension);
-  DeviceWords raw;
-  HIP_TRY(ctx, raw.alloc(words));
-  hipError_t e = hipMemcpy(raw.p, pksk, words * sizeof(u32), hipMemcpyHostToDevice);
-  if (e != hipSuccess) return hip_fail(ctx, e, "packing key upload");
-  return load_packing_key_common(ctx, raw.p, from_dimension);
+  DeviceBuffer raw;
+  TFHE_TRY(raw.grow(ctx, words * sizeof(u32)));
+  HIP_TRY(ctx, hipMemcpy(raw.as(), pksk, words * sizeof(u32), hipMemcpyHostToDevice));
+  return load_packing_key_common(ctx, raw.as<u32>(), from_dimension);
 }
 
 int tfhe_packing_key_dimension(const tfhe_context* ctx, size_t* from_dimension) {
@@ -2601,9 +2503,9 @@ size_t mv_bytes(const tfhe_context* ctx, size_t batch, size_t tables) {
   return L.words * sizeof(u32);
 }
 
-u32* mv_acc0(const tfhe_context* ctx) { return ctx->d_mv_const; }
-u32* mv_positions(const tfhe_context* ctx) { return ctx->d_mv_const + glwe_words(ctx); }
-u32* mv_caller_positions(const tfhe_context* ctx) { return ctx->d_mv_const + glwe_words(ctx) + kSparseMaxTerms; }
+u32* mv_acc0(const tfhe_context* ctx) { return ctx->d_mv_const.as<u32>(); }
+u32* mv_positions(const tfhe_context* ctx) { return ctx->d_mv_const.as<u32>() + glwe_words(ctx); }
+u32* mv_caller_positions(const tfhe_context* ctx) { return ctx->d_mv_const.as<u32>() + glwe_words(ctx) + kSparseMaxTerms; }
 
 // what the parameters must allow: kappa = 2^(31 - log_p - padding) exists, a value covers at least two coefficients
 int check_mv_params(tfhe_context* ctx) {
@@ -2629,13 +2531,12 @@ int ensure_mv_const(tfhe_context* ctx) {
   if (ctx->d_mv_const) return TFHE_OK;
   TFHE_TRY(check_mv_params(ctx));
   const tfhe_params& p = ctx->params;
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_mv_const), (glwe_words(ctx) + 2 * (size_t)kSparseMaxTerms) * sizeof(u32)));
+  TFHE_TRY(ctx->d_mv_const.grow(ctx, (glwe_words(ctx) + 2 * (size_t)kSparseMaxTerms) * sizeof(u32)));
   hipError_t e = launch::multi_value_constants(ctx->stream, p.log_p, ctx->pbs.log_n, ctx->pbs.k, 1u << (31 - p.log_p - p.padding_bits),
                                                mv_acc0(ctx), mv_positions(ctx));
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the stream may be another one by the next call
   if (e != hipSuccess) {
-    (void)hipFree(ctx->d_mv_const);
-    ctx->d_mv_const = nullptr;
+    (void)ctx->d_mv_const.resize(ctx, 0);  // no constants: the next call starts over
     return hip_fail(ctx, e, "multi_value_constants");
   }
   return TFHE_OK;
@@ -2646,9 +2547,8 @@ int reserve_mv(tfhe_context* ctx, size_t batch, size_t tables) {
   if (batch <= ctx->mv_batch && tables <= ctx->mv_tables) return TFHE_OK;
   const size_t new_batch = std::max(batch, ctx->mv_batch), new_tables = std::max(tables, ctx->mv_tables);
   TFHE_TRY(check_mv_shape(ctx, new_batch, new_tables));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->mv_batch = ctx->mv_tables = 0;
-  TFHE_TRY(ensure(ctx, &ctx->d_mv_ws, &ctx->mv_ws_words, mv_bytes(ctx, new_batch, new_tables) / sizeof(u32)));
+  TFHE_TRY(ctx->d_mv_ws.grow(ctx, mv_bytes(ctx, new_batch, new_tables)));
   ctx->mv_batch = new_batch;
   ctx->mv_tables = new_tables;
   return TFHE_OK;
@@ -2756,11 +2656,11 @@ int tfhe_multi_value_bootstrap_batch_device(tfhe_context* ctx, const uint32_t* l
                     std::to_string(ctx->mv_batch) + " and " + std::to_string(ctx->mv_tables) + " tables (tfhe_context_reserve_multi_value)");
   MvLayout L;
   mv_layout(ctx, ctx->mv_batch, ctx->mv_tables, &L);
-  u32* ws = ctx->d_mv_ws;
+  u32* ws = ctx->d_mv_ws.as<u32>();
   const u32 n = ctx->params.lwe_dimension;
   auto key_switch = [&](const u32* in, size_t count, u32* out) -> int {
     TFHE_TRY(span_begin(ctx, kKeySwitchSpan));
-    HIP_TRY(ctx, launch::key_switch(ctx->stream, ctx->ks, ctx->big_n, n, in, count, ctx->d_ksk, out, ctx->d_ksk_matrix, ctx->ks_path));
+    HIP_TRY(ctx, launch::key_switch(ctx->stream, ctx->ks, ctx->big_n, n, in, count, ctx->d_ksk.as<u32>(), out, ctx->d_ksk_matrix.as(), ctx->ks_path));
     return span_end(ctx, kKeySwitchSpan, false);
   };
   if (ctx->ks_first) {
@@ -2875,9 +2775,7 @@ int tfhe_context_reserve_tree_lut(tfhe_context* ctx, size_t max_batch, size_t ma
   TFHE_TRY(check_ctx(ctx));
   TreeLutLayout L;
   TFHE_TRY(check_tree_lut_shape(ctx, max_batch, max_digits, max_tables, &L));
-  if (L.words <= ctx->tree_ws_words) return TFHE_OK;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return ensure(ctx, &ctx->d_tree_ws, &ctx->tree_ws_words, L.words);
+  return ctx->d_tree_ws.grow(ctx, L.words * sizeof(u32));
 }
 
 int tfhe_tree_lut_batch_device(tfhe_context* ctx, const uint32_t* const* digits, size_t d, size_t batch, const uint32_t* table,
@@ -2885,15 +2783,15 @@ int tfhe_tree_lut_batch_device(tfhe_context* ctx, const uint32_t* const* digits,
   TFHE_TRY(check_ctx(ctx));
   TreeLutLayout L;
   TFHE_TRY(check_tree_lut_args(ctx, digits, d, batch, table, table_sets, tables, lwe_out, &L));
-  if (L.words > ctx->tree_ws_words)
+  if (L.words > ctx->d_tree_ws.words())
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
                 "the call needs " + std::to_string(L.words * sizeof(u32)) + " bytes of tree-LUT workspace, " +
-                    std::to_string(ctx->tree_ws_words * sizeof(u32)) + " are reserved (tfhe_context_reserve_tree_lut)");
+                    std::to_string(ctx->d_tree_ws.bytes()) + " are reserved (tfhe_context_reserve_tree_lut)");
   if (ctx->tree_level0_multi_value) TFHE_TRY(check_mv_params(ctx));
   const u32 log_p = ctx->params.log_p, log_n = ctx->pbs.log_n, n = ctx->params.lwe_dimension;
   const u32 log_rep = log_n - log_p;
   const size_t n1 = lwe_words(ctx);
-  u32* ws = ctx->d_tree_ws;
+  u32* ws = ctx->d_tree_ws.as<u32>();
   u32 *ks_digit = ws + L.ks_digit, *lwe = ws + L.lwe, *tv = ws + L.tv, *state = ws + L.state, *glwes = ws + L.glwe;
   u32* results[2] = {ws + L.res_a, ws + L.res_b};
   hipStream_t s = ctx->stream;
@@ -2901,7 +2799,7 @@ int tfhe_tree_lut_batch_device(tfhe_context* ctx, const uint32_t* const* digits,
   auto digit_of = [&](size_t t, const u32** out) -> int {
     *out = digits[t];
     if (!ctx->ks_first) return TFHE_OK;
-    HIP_TRY(ctx, launch::key_switch(s, ctx->ks, ctx->big_n, n, digits[t], batch, ctx->d_ksk, ks_digit, ctx->d_ksk_matrix, ctx->ks_path));
+    HIP_TRY(ctx, launch::key_switch(s, ctx->ks, ctx->big_n, n, digits[t], batch, ctx->d_ksk.as<u32>(), ks_digit, ctx->d_ksk_matrix.as(), ctx->ks_path));
     *out = ks_digit;
     return TFHE_OK;
   };
@@ -2931,7 +2829,7 @@ int tfhe_tree_lut_batch_device(tfhe_context* ctx, const uint32_t* const* digits,
     cur = next;
     count = groups;
   }
-  if (!ctx->ks_first) HIP_TRY(ctx, launch::key_switch(s, ctx->ks, ctx->big_n, n, cur, count, ctx->d_ksk, lwe_out, ctx->d_ksk_matrix, ctx->ks_path));
+  if (!ctx->ks_first) HIP_TRY(ctx, launch::key_switch(s, ctx->ks, ctx->big_n, n, cur, count, ctx->d_ksk.as<u32>(), lwe_out, ctx->d_ksk_matrix.as(), ctx->ks_path));
   return TFHE_OK;
 }
 
@@ -3013,9 +2911,8 @@ int reserve_extract(tfhe_context* ctx, size_t batch, size_t digits) {
   TFHE_TRY(reserve(ctx, batch));
   if (batch <= ctx->extract_batch && digits <= ctx->extract_digits) return TFHE_OK;
   const size_t new_batch = std::max(batch, ctx->extract_batch), new_digits = std::max(digits, ctx->extract_digits);
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->extract_batch = ctx->extract_digits = 0;
-  TFHE_TRY(ensure(ctx, &ctx->d_extract_ws, &ctx->extract_ws_words, extract_bytes(ctx, new_batch, new_digits) / sizeof(u32)));
+  TFHE_TRY(ctx->d_extract_ws.grow(ctx, extract_bytes(ctx, new_batch, new_digits)));
   ctx->extract_batch = new_batch;
   ctx->extract_digits = new_digits;
   return TFHE_OK;
@@ -3028,7 +2925,7 @@ int check_extract_reserved(tfhe_context* ctx, size_t batch, size_t ws_digits) {
               "the call needs " + std::to_string(extract_bytes(ctx, batch, ws_digits)) +
                   " bytes of extraction workspace (batch " + std::to_string(batch) + ", " + std::to_string(ws_digits) +
                   " digit buffers), " +
-                  std::to_string(ctx->extract_batch && batch <= ctx->ws_batch ? ctx->extract_ws_words * sizeof(u32) : 0) +
+                  std::to_string(ctx->extract_batch && batch <= ctx->ws_batch ? ctx->d_extract_ws.bytes() : 0) +
                   " are reserved (tfhe_context_reserve_extract)");
 }
 
@@ -3036,7 +2933,7 @@ int check_extract_reserved(tfhe_context* ctx, size_t batch, size_t ws_digits) {
 int enqueue_extract(tfhe_context* ctx, const u32* lwe_in, const ExtractShape& e, u32* const* digits_out, u32* remainder_out) {
   ExtractLayout L;
   extract_layout(ctx, ctx->extract_batch, ctx->extract_digits, &L);
-  u32 *r = ctx->d_extract_ws + L.r, *s = ctx->d_extract_ws + L.s, *o = ctx->d_extract_ws + L.o, *acc = ctx->d_extract_ws + L.acc;
+  u32 *r = ctx->d_extract_ws.as<u32>() + L.r, *s = ctx->d_extract_ws.as<u32>() + L.s, *o = ctx->d_extract_ws.as<u32>() + L.o, *acc = ctx->d_extract_ws.as<u32>() + L.acc;
   const u32 w = e.g * e.d;
   auto m_of = [&](u32 j) { return std::min(e.lsb + j, e.out_lsb + j % e.g); };
   ExtractStepArgs a{};
@@ -3053,7 +2950,7 @@ int enqueue_extract(tfhe_context* ctx, const u32* lwe_in, const ExtractShape& e,
   a.acc_kappa = 1u << (m_of(0) - 1);
   HIP_TRY(ctx, launch::extract_step(ctx->stream, a));
   for (u32 j = 0; j < w; ++j) {
-    TFHE_TRY(enqueue_bootstrap(ctx, s, e.batch, acc, 1, ctx->d_lwe_big, o, AccSource{true, ctx->N / 2}));
+    TFHE_TRY(enqueue_bootstrap(ctx, s, e.batch, acc, 1, ctx->d_lwe_big.as<u32>(), o, AccSource{true, ctx->N / 2}));
     const u32 i = j % e.g, m = m_of(j);
     const bool last = j + 1 == w;
     a.r_in = r;
@@ -3151,7 +3048,7 @@ int tfhe_extract_digits_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t 
   ExtractLayout L;
   extract_layout(ctx, ctx->extract_batch, ctx->extract_digits, &L);
   std::vector<u32*> ptrs(digits);
-  for (unsigned t = 0; t < digits; ++t) ptrs[t] = ctx->d_extract_ws + L.digits + t * L.digit_stride;
+  for (unsigned t = 0; t < digits; ++t) ptrs[t] = ctx->d_extract_ws.as<u32>() + L.digits + t * L.digit_stride;
   TFHE_TRY(enqueue_extract(ctx, s[kIn], e, ptrs.data(), remainder_out ? s[kRemainder] : nullptr));
   for (unsigned t = 0; t < digits; ++t) TFHE_TRY(download(ctx, digits_out[t], ptrs[t], words));
   if (remainder_out) TFHE_TRY(download(ctx, remainder_out, s[kRemainder], words));
@@ -3165,14 +3062,14 @@ int tfhe_wide_lut_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_t
   TreeLutLayout TL;
   TFHE_TRY(check_wide_lut_args(ctx, lwe_in, batch, lsb, d, table, table_sets, tables, lwe_out, &TL));
   TFHE_TRY(check_extract_reserved(ctx, batch, d));
-  if (TL.words > ctx->tree_ws_words)
+  if (TL.words > ctx->d_tree_ws.words())
     return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
                 "the call needs " + std::to_string(TL.words * sizeof(u32)) + " bytes of tree-LUT workspace, " +
-                    std::to_string(ctx->tree_ws_words * sizeof(u32)) + " are reserved (tfhe_context_reserve_wide_lut)");
+                    std::to_string(ctx->d_tree_ws.bytes()) + " are reserved (tfhe_context_reserve_wide_lut)");
   ExtractLayout L;
   extract_layout(ctx, ctx->extract_batch, ctx->extract_digits, &L);
   std::vector<u32*> ptrs(d);
-  for (size_t t = 0; t < d; ++t) ptrs[t] = ctx->d_extract_ws + L.digits + t * L.digit_stride;
+  for (size_t t = 0; t < d; ++t) ptrs[t] = ctx->d_extract_ws.as<u32>() + L.digits + t * L.digit_stride;
   TFHE_TRY(enqueue_extract(ctx, lwe_in, wide_lut_shape(ctx, batch, lsb, d), ptrs.data(), nullptr));
   return tfhe_tree_lut_batch_device(ctx, ptrs.data(), d, batch, table, table_sets, tables, lwe_out);
 }
@@ -3395,20 +3292,20 @@ static int lut_gate_device(tfhe_context* ctx, const u32* truth, u32 inputs, cons
     if (unpinned < tfhe_context::kMaxGateTvs) {  // room left, or every entry is pinned: the cache grows
       ctx->gate_tvs.emplace_back();
       slot = &ctx->gate_tvs.back();
-      HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&slot->d_tv), ctx->N * sizeof(u32)));
+      TFHE_TRY(slot->d_tv.grow(ctx, ctx->N * sizeof(u32)));
     }
     slot->truth.clear();  // not a valid entry until the upload has succeeded
-    HIP_TRY(ctx, hipMemcpy(slot->d_tv, tv.data(), ctx->N * sizeof(u32), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(slot->d_tv.as(), tv.data(), ctx->N * sizeof(u32), hipMemcpyHostToDevice));
     slot->truth.assign(truth, truth + entries);
   }
   slot->last_use = ++ctx->gate_clock;
   if (capturing) slot->pinned = true;
   const u32* d_in = cts[0];
   for (u32 i = 1; i < inputs; ++i) {  // 2*ct1 + ct0 (boolean.rs:18), then + 4*ct2, ...
-    HIP_TRY(ctx, launch::lwe_linear(ctx->stream, 1u, d_in, 1u << i, cts[i], words, ctx->d_lwe_in2));
-    d_in = ctx->d_lwe_in2;
+    HIP_TRY(ctx, launch::lwe_linear(ctx->stream, 1u, d_in, 1u << i, cts[i], words, ctx->d_lwe_in2.as<u32>()));
+    d_in = ctx->d_lwe_in2.as<u32>();
   }
-  return enqueue_bootstrap(ctx, d_in, batch, slot->d_tv, 1, ctx->d_lwe_big, lwe_out);
+  return enqueue_bootstrap(ctx, d_in, batch, slot->d_tv.as<u32>(), 1, ctx->d_lwe_big.as<u32>(), lwe_out);
 }
 
 int tfhe_gate_batch_device(tfhe_context* ctx, const uint32_t truth[4], const uint32_t* ct0,

@@ -12,6 +12,42 @@
 
 using namespace tfhe;
 
+// A device allocation that its holder owns: every workspace, key buffer and temporary of the host sources is one.  The
+// destructor frees it (with its device current: tfhe_context_destroy and tfhe_poly_weights_destroy select it first).
+// The size changes in two ways only, grow and resize, and both keep ONE rule: the buffer never claims a capacity it
+// does not have.  They drain ctx->stream (work enqueued on the old allocation ends first), read as null with capacity
+// 0 from before the old allocation is freed, and record the new capacity only after the new allocation succeeded --
+// so after any failure the buffer is null, capacity 0, and a later, smaller call is refused or allocates again
+// instead of launching kernels on memory that is gone.  An owner's logical sizes (ws_batch, mv_batch, ..) follow the
+// same discipline around the call: zeroed before, set after.
+class DeviceBuffer {
+ public:
+  DeviceBuffer() = default;
+  DeviceBuffer(const DeviceBuffer&) = delete;
+  DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+  DeviceBuffer(DeviceBuffer&& o) noexcept : ptr_(o.ptr_), bytes_(o.bytes_) {
+    o.ptr_ = nullptr;
+    o.bytes_ = 0;
+  }
+  ~DeviceBuffer() {
+    if (ptr_) (void)hipFree(ptr_);
+  }
+  template <class T = void>
+  T* as() const { return static_cast<T*>(ptr_); }
+  explicit operator bool() const { return ptr_ != nullptr; }
+  size_t bytes() const { return bytes_; }
+  size_t words() const { return bytes_ / sizeof(u32); }
+  // at least `bytes`: nothing happens (no HIP call) when the capacity covers them; never shrinks
+  int grow(tfhe_context* ctx, size_t bytes) { return bytes <= bytes_ ? TFHE_OK : reallocate(ctx, bytes); }
+  // exactly `bytes` (0: released): the prepared keys, whose footprint follows the kind and dimension of the loaded key
+  int resize(tfhe_context* ctx, size_t bytes) { return bytes == bytes_ ? TFHE_OK : reallocate(ctx, bytes); }
+
+ private:
+  int reallocate(tfhe_context* ctx, size_t bytes);  // below, after tfhe_context
+  void* ptr_ = nullptr;
+  size_t bytes_ = 0;
+};
+
 struct tfhe_context {
   tfhe_params params;
   PbsParams pbs;
@@ -24,29 +60,25 @@ struct tfhe_context {
 
   int field = 0;              // launch::kFieldGoldilocks | launch::kFieldFp64
   int parts = 1;              // spectra per key polynomial in this field
-  void* d_tw = nullptr;       // psi_rev[N], 8-byte field elements
-  unsigned long long* d_queue = nullptr;  // ticket counter of the external-product kernel's work queue
-  void* d_bsk = nullptr;      // prepared BSK [n][R][k+1][parts][N] (spectrum_slot order, x 1/N)
-  u32* d_ksk = nullptr;       // [big_n*l_ks][n+1]
-  void* d_ksk_matrix = nullptr;  // the same key in the matrix path's layout (ks_matrix.h); null where it is not admitted
+  DeviceBuffer d_tw;          // psi_rev[N], 8-byte field elements
+  DeviceBuffer d_queue;       // ticket counter of the external-product kernel's work queue (unsigned long long)
+  DeviceBuffer d_bsk;         // prepared BSK [n][R][k+1][parts][N] (spectrum_slot order, x 1/N)
+  DeviceBuffer d_ksk;         // [big_n*l_ks][n+1]
+  DeviceBuffer d_ksk_matrix;  // the same key in the matrix path's layout (ks_matrix.h); null where it is not admitted
   int ks_path = 0;            // path of the key switch (tfhe_context_set_key_switch_path): launch::kKsPath*
   bool have_key = false;
   bool bmmp = false;          // the loaded key is a BMMP key: n/2 * 3 GGSWs (tfhe_load_bootstrapping_key_bmmp)
   size_t bsk_ggsws = 0;       // GGSWs d_bsk was allocated for
   // packing key (tfhe_load_packing_key): independent of the bootstrapping key
-  void* d_pksk = nullptr;     // prepared: ceil(pksk_dim / (k+1)) slices of [(k+1) l_ks][k+1][parts][N], zero-filled past pksk_dim
-  size_t pksk_bytes = 0;
+  DeviceBuffer d_pksk;        // prepared: ceil(pksk_dim / (k+1)) slices of [(k+1) l_ks][k+1][parts][N], zero-filled past pksk_dim
   size_t pksk_dim = 0;        // dimension of the LWE key it packs from
   bool have_pksk = false;
-  u32* d_pack_cols = nullptr; // transposed inputs of a packing call, kPackColsWords words (capi.cpp) or one output's worth
-  size_t pack_cols_words = 0;
+  DeviceBuffer d_pack_cols;   // transposed inputs of a packing call, kPackColsWords words (capi.cpp) or one output's worth
   // CMUX tree / table lookup (tfhe_context_reserve_lookup): partial results of the passes and the teams' pending slots
-  u32* d_lookup_ws = nullptr;
-  size_t lookup_ws_words = 0;
+  DeviceBuffer d_lookup_ws;
   unsigned lookup_height = 0; // subtree height a team reduces (tfhe_context_set_lookup_subtree_height); 0: automatic
   // DEMUX tree / table update (tfhe_context_reserve_demux): the passes' nodes and the teams' parked nodes
-  u32* d_demux_ws = nullptr;
-  size_t demux_ws_words = 0;
+  DeviceBuffer d_demux_ws;
   unsigned demux_height = 0;  // subtree height a team expands (tfhe_context_set_demux_subtree_height); 0: automatic
   // Encrypted branching program (tfhe_context_reserve_program): one buffer, [values: one GLWE per (query, node)] then
   // kProgramImages images of program_image_words words each -- a program compiled for the device (its ops in execution
@@ -61,30 +93,27 @@ struct tfhe_context {
     unsigned long long last_use = 0;
     bool pinned = false;
   };
-  u32* d_program_ws = nullptr;
-  size_t program_ws_words = 0;
+  DeviceBuffer d_program_ws;
   size_t program_value_words = 0, program_image_words = 0;
   ProgramImage program_images[kProgramImages];
   unsigned long long program_clock = 0;
   unsigned program_parts = 0;  // teams per query of a split level (tfhe_context_set_program_split); 0: automatic
   // Dense layer (tfhe_context_reserve_dense): the fused layer's pre-activations [dense_rows][max(n, k N) + 1], then one
   // test vector [N] per bootstrap, for dense_rows = max_queries * max_outputs bootstraps
-  u32* d_dense_ws = nullptr;
+  DeviceBuffer d_dense_ws;
   size_t dense_rows = 0;
   unsigned dense_parts = 0;   // shares of the inputs (tfhe_context_set_dense_split); 0: automatic
   // Encrypted convolution (tfhe_context_reserve_glwe_conv): the prepared spectra of a call's ciphertext polynomials,
   // conv_ws_polys = max_queries * max_channels * (k+1) of them, parts * N 8-byte words each
-  void* d_conv_ws = nullptr;
+  DeviceBuffer d_conv_ws;
   size_t conv_ws_polys = 0;
   unsigned conv_rows = 0;     // channels per pass (tfhe_context_set_glwe_conv_rows); 0: automatic
   // tree LUT (tfhe_context_reserve_tree_lut): per-rotation inputs, segment state, the levels' results and packed GLWEs
-  u32* d_tree_ws = nullptr;
-  size_t tree_ws_words = 0;
+  DeviceBuffer d_tree_ws;
   // digit extraction (tfhe_context_reserve_extract): the remainder r, the scaled input s and the result o of the bit's
   // bootstrap, each [extract_batch][max(n, k N) + 1], the shared constant accumulator [k+1][N], then extract_digits digit
   // buffers of the same rows (the host forms' and the wide LUT's digits)
-  u32* d_extract_ws = nullptr;
-  size_t extract_ws_words = 0;
+  DeviceBuffer d_extract_ws;
   size_t extract_batch = 0, extract_digits = 0;
   // multi-value bootstrap.  d_mv_const (allocated by tfhe_context_reserve_multi_value, by tfhe_context_set_tree_lut_level0(1)
   // and by the host forms): the constant accumulator (0, .., 0, kappa (1 + X + .. + X^(N-1))) [k+1][N], the B + 1 positions
@@ -92,9 +121,8 @@ struct tfhe_context {
   // (tfhe_context_reserve_multi_value): the key-switched inputs [mv_batch][n + 1], the rotated accumulators
   // [mv_batch][k+1][N], the coefficients [mv_batch][mv_tables][B + 1], the combinations before the key switch
   // [mv_batch][mv_tables][k N + 1]
-  u32* d_mv_const = nullptr;
-  u32* d_mv_ws = nullptr;
-  size_t mv_ws_words = 0;
+  DeviceBuffer d_mv_const;
+  DeviceBuffer d_mv_ws;
   size_t mv_batch = 0, mv_tables = 0;
   bool tree_level0_multi_value = false;  // tfhe_context_set_tree_lut_level0
   bool aligned = false;       // decomposer alignment (tfhe_context_set_decomposer_alignment)
@@ -103,15 +131,15 @@ struct tfhe_context {
 
   // workspace (grown on demand by host-pointer calls or tfhe_context_reserve)
   size_t ws_batch = 0;
-  u32* d_lwe_in = nullptr;    // [batch][n+1]
-  u32* d_lwe_in2 = nullptr;   // [batch][n+1] second gate operand
-  u32* d_lwe_big = nullptr;   // [batch][big_n+1]
-  u32* d_lwe_out = nullptr;   // [batch][n+1]
-  u32* d_lwe_ks = nullptr;    // [batch][n+1] key-switched input of the KS-then-PBS order
-  u32* d_glwe_a = nullptr;    // [batch][k+1][N]
-  u32* d_glwe_b = nullptr;
-  u32* d_glwe_c = nullptr;
-  u32* d_tv = nullptr;        // [batch][N] (or [1][N])
+  DeviceBuffer d_lwe_in;      // [batch][n+1]
+  DeviceBuffer d_lwe_in2;     // [batch][n+1] second gate operand
+  DeviceBuffer d_lwe_big;     // [batch][big_n+1]
+  DeviceBuffer d_lwe_out;     // [batch][n+1]
+  DeviceBuffer d_lwe_ks;      // [batch][n+1] key-switched input of the KS-then-PBS order
+  DeviceBuffer d_glwe_a;      // [batch][k+1][N]
+  DeviceBuffer d_glwe_b;
+  DeviceBuffer d_glwe_c;
+  DeviceBuffer d_tv;          // [batch][N] (or [1][N])
   // test vectors of gate calls, one [N] device buffer per truth table seen (a gate graph alternates
   // between a handful of tables; re-uploading on every switch would synchronise the stream).  kMaxGateTvs unpinned
   // tables are kept, the least recently used one is replaced.  A table looked up while the stream is capturing is
@@ -120,21 +148,17 @@ struct tfhe_context {
   static constexpr size_t kMaxGateTvs = 64;
   struct GateTv {
     std::vector<u32> truth;  // 2^inputs entries
-    u32* d_tv = nullptr;
+    DeviceBuffer d_tv;
     unsigned long long last_use = 0;
     bool pinned = false;
   };
   std::vector<GateTv> gate_tvs;
   unsigned long long gate_clock = 0;
   // generic scratch for the small entry points
-  void* d_misc = nullptr;
-  size_t misc_bytes = 0;
-  u64* d_ggsw_tmp = nullptr;  // prepared GGSWs of external_product / cmux host calls (8-byte words)
-  size_t ggsw_tmp_words = 0;
-  u32* d_ggsw_raw = nullptr;
-  size_t ggsw_raw_words = 0;
-  u32* d_key_tmp = nullptr;   // secret keys / messages of the encryption-side calls
-  size_t key_tmp_words = 0;
+  DeviceBuffer d_misc;
+  DeviceBuffer d_ggsw_tmp;    // prepared GGSWs of external_product / cmux host calls (8-byte words)
+  DeviceBuffer d_ggsw_raw;
+  DeviceBuffer d_key_tmp;     // secret keys / messages of the encryption-side calls
 
   bool timing = false;
   // br start/stop, ks start/stop of the current timing slot.  Bootstraps rotate through kTimingSlots sets of
@@ -156,7 +180,7 @@ struct tfhe_poly_weights {
   int device = 0;
   int field = 0;
   u32 log_n = 0;
-  void* d_spec = nullptr;      // [outputs][channels] spectra, N 8-byte words each (glwe_conv.h::conv_weights_wave)
+  DeviceBuffer d_spec;         // [outputs][channels] spectra, N 8-byte words each (glwe_conv.h::conv_weights_wave)
   size_t outputs = 0, channels = 0;
   unsigned weight_bits = 0;    // the smallest b with every |w| <= 2^b
   unsigned rows_per_pass = 0;  // channels the backend's exactness rule admits in one pass at that magnitude
@@ -216,3 +240,19 @@ inline size_t prepared_bsk_bytes(const tfhe_context* ctx, size_t ggsws) {
     int _st = (expr);           \
     if (_st != TFHE_OK) return _st; \
   } while (0)
+
+// the one place that allocates and frees device memory (DeviceBuffer above states the rule it keeps)
+inline int DeviceBuffer::reallocate(tfhe_context* ctx, size_t bytes) {
+  void* old = ptr_;
+  ptr_ = nullptr;
+  bytes_ = 0;
+  hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (old) {  // freed whatever the stream said: nothing else holds it
+    const hipError_t freed = hipFree(old);
+    if (e == hipSuccess) e = freed;
+  }
+  if (e == hipSuccess && bytes && (e = hipMalloc(&ptr_, bytes)) != hipSuccess) ptr_ = nullptr;
+  if (e != hipSuccess) return tfhe::host::hip_fail(ctx, e, "DeviceBuffer (hipStreamSynchronize / hipFree / hipMalloc)");
+  bytes_ = bytes;
+  return TFHE_OK;
+}
