@@ -18,7 +18,10 @@
 // rint(z~_j) = z_j.  Bound on e (Higham, Accuracy and Stability of Numerical Algorithms, 2nd ed., Thm 24.2:
 // a radix-2 FFT of n stages computed with twiddles of absolute error <= mu satisfies
 // ||X~ - X||_2 <= n eta / (1 - n eta) ||X||_2, eta = mu + gamma_4 (sqrt 2 + mu), gamma_4 = 4u / (1 - 4u),
-// u = 2^-53; our twiddles are correctly rounded from long double, each component within u/2, |error| <= u / sqrt 2,
+// u = 2^-53; our twiddles are correctly rounded from long double, each component within u/2, |error| <= u / sqrt 2
+// -- the even nodes of a stage from cosl / sinl of their angle, the odd ones as (-im, re) of their even neighbour, whose
+// angle is a quarter turn less: cos(t + pi/2) = -sin t and sin(t + pi/2) = cos t exactly, so those components are the
+// correctly rounded cosine and sine of the odd node's own angle as well (kSiblingTwiddleIsRotation below) --,
 // so eta <= 7.1 u = 7.9e-16 with room to spare; the forward transforms here use a six-FMA butterfly whose own
 // per-stage perturbation is 4.32 u, derived at FftField::butterfly_forward below; the inverse ones the textbook
 // sum / difference-times-twiddle form; the theorem's mechanism is an induction that needs nothing but a per-stage
@@ -141,6 +144,14 @@ struct FftField {
   }
   // the low register windows' twiddles are read a transpose ahead of their pass (wave_ntt.h::PassTwiddles)
   static constexpr bool kPreloadTwiddles = true;
+  // Node 2j + 1 of a stage is i times node 2j: bitrev_s(2j + 1) = bitrev_s(2j) + h/2, a quarter turn on top of the angle.
+  // fill_twiddles writes the odd nodes AS that rotation, so a pass reads the even ones only (wave_ntt.h::PassTwiddles) and
+  // the value it derives is the table's, bit for bit.  The butterflies take a twiddle's components only as FMA / multiply
+  // operands, where a sign is an input modifier: the swap and the sign cost no instruction.
+  static constexpr bool kSiblingTwiddleIsRotation = true;
+  TFHE_HD static elem rotate_twiddle(elem w) { return elem{-w.im, w.re}; }
+  // one-wave teams keep their group index in a scalar register (pbs_wave.h::ScalarGroupIndex)
+  static constexpr bool kScalarGroupIndex = true;
   // acc + d * k: 4 FMAs
   static constexpr bool kFusedMac = true;
   TFHE_HD static elem mul_add(elem d, elem k, elem acc) {
@@ -199,6 +210,12 @@ struct FftField {
     for (int s = 0; (1 << s) < m; ++s) {
       const int h = 1 << s;
       for (int i = 0; i < h; ++i) {
+        // odd nodes: the even neighbour turned by a quarter (kSiblingTwiddleIsRotation) -- cos(t + pi/2) = -sin t and
+        // sin(t + pi/2) = cos t exactly, so these components are correctly rounded values of the node's own angle too
+        if (i & 1) {
+          out[h + i] = rotate_twiddle(out[h + i - 1]);
+          continue;
+        }
         int rev = 0;
         for (int b = 0; b < s; ++b) rev |= ((i >> b) & 1) << (s - 1 - b);
         const long double angle = pi * (long double)(1 + 4 * rev) / (long double)(4 * h);

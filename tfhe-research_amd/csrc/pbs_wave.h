@@ -307,6 +307,21 @@ TFHE_HD u32 rounded_coeff(const Src& src, int r, int lane, RoundConsts rc, long)
 // notes/BMMP Bootstrapping.md needs three products of the same accumulator).  out(m, j, value) is
 // called for key m = 0 .. KEYS-1 in turn, end_of_key(m) once after the last coefficient of key m.
 // ---------------------------------------------------------------------------------------------
+// F::kScalarGroupIndex: the field's one-wave-per-polynomial teams read their group index into a scalar register.  Opt-in per
+// field because it moves the register allocation of EVERY kernel built on external_product_team_multi -- blind rotation,
+// external product, CMUX tree, DEMUX tree, programs, packing --, mostly down (cfg2's team 256 VGPRs with 4 spilled -> 247
+// with none; the N = 2048 tree and program kernels spill less), at the price of ~10 SGPRs each, and not everywhere:
+// demux_tree_kernel<FftField, 10, 2> goes from 244 VGPRs to 256 with 10 spilled (profiles/twiddle_reads_ab.txt).  The
+// prime fields do not ask for it and their kernels stay instruction for instruction what they were.
+template <class F, class = void>
+struct ScalarGroupIndex {
+  static constexpr bool value = false;
+};
+template <class F>
+struct ScalarGroupIndex<F, decltype((void)F::kScalarGroupIndex)> {
+  static constexpr bool value = F::kScalarGroupIndex;
+};
+
 // NS > 1: the team multiplies NS GLWE operands (NS independent samples of a batch) with the SAME prepared GGSW in
 // one pass.  Every key chunk is fetched from L2 once and used NS times, the NS transforms of a step run in lockstep
 // through one set of transposes and barriers (ntt_forward_multi), and a team barrier covers NS products instead
@@ -332,7 +347,10 @@ TFHE_HD void external_product_team_multi(const Ctx& c, const PbsParams& P, const
   constexpr int N = 1 << LT;                       // transform elements per polynomial
   constexpr int PARTS = F::kParts;
   const int lane = c.tid();   // thread index inside my polynomial's group of G waves
-  const int me = c.group();   // polynomial / output column owned by my group
+  // polynomial / output column owned by my group.  Where a group is ONE wave the index is wave-uniform, and a field may ask
+  // for it as a scalar (F::kScalarGroupIndex, ScalarGroupIndex above): the key tiles' addresses are then scalar arithmetic on
+  // a scalar base, which gives back the vector registers the tile pointer and its offsets held for the whole product.
+  const int me = (ScalarGroupIndex<F>::value && G == 1) ? (int)c.uniform((u32)c.group()) : c.group();
   // (h, l) accumulator pairs only for a single key and sample: a second set per accumulator does not fit otherwise
   constexpr bool SPLIT = F::template split_accum<E>() && KEYS == 1 && NS == 1;
   constexpr int ACCS = KEYS * PARTS;  // accumulator a = m * PARTS + q of a sample: key m, key part q
@@ -1147,8 +1165,9 @@ TFHE_HD void blind_rotate_team_wide(const Ctx& c, const PbsParams& P, const u32*
 //   its two accumulators (one after the other's transposes: ntt_inverse_pair) and updates accumulator polynomial c.
 // Ctx: tid() = lane within the half (0..31), group() = half = polynomial, scratch() / scratch_of(c) = a half's buffer.
 // ---------------------------------------------------------------------------------------------
-template <class F, int LOGN, class Ctx, class Src, class Out>
-TFHE_HD void external_product_pair(const Ctx& c, const PbsParams& P, const typename F::elem* ggsw, Src src, Out out) {
+template <class F, int LOGN, class Ctx, class Src, class Out, class Low = NoPassTwiddles>
+TFHE_HD void external_product_pair(const Ctx& c, const PbsParams& P, const typename F::elem* ggsw, Src src, Out out,
+                                   const Low& low = Low{}) {
   typedef typename F::elem elem;
   static_assert(F::kParts == 2 && F::kLogShrink == 1 && F::kCoeffs == 2, "the complex transform: two key parts, two coefficients per element");
   constexpr int K = 1;
@@ -1217,7 +1236,7 @@ TFHE_HD void external_product_pair(const Ctx& c, const PbsParams& P, const typen
         work[r] = F::from_digits(dg);
       }
     }
-    ntt_forward<F, LT, G, true, true>(c, work, ftop);
+    ntt_forward<F, LT, G, true, true>(c, work, ftop, low);
     // hand my spectrum to the other half: through my buffer (free between two transforms)
     elem* mine = c.scratch();
 #pragma unroll
@@ -1253,7 +1272,7 @@ TFHE_HD void external_product_pair(const Ctx& c, const PbsParams& P, const typen
     accum[1][r] = F::before_inverse(accum[1][r]);
   }
   itop.ready();
-  ntt_inverse_pair<F, LT, G>(c, accum[0], accum[1], itop);
+  ntt_inverse_pair<F, LT, G>(c, accum[0], accum[1], itop, NothingBefore{}, low);
 #pragma unroll
   for (int r = 0; r < E; ++r) {
     elem parts[2] = {accum[0][r], accum[1][r]};
@@ -1286,6 +1305,12 @@ TFHE_HD void blind_rotate_pair(const Ctx& c, const PbsParams& P, const u32* lwe 
     rotate_init_fill<LOGN, K, EC>(P, ri, tv, me, acc, [&](int r) { return r * T + tid; });
   }
   c.wave_sync();
+  // The lowest window's twiddles (its two stages: 3 elements, 12 VGPRs) stay in registers for the whole rotation instead of
+  // being read before every transform's last / first pass (wave_ntt.h::LowestWindowTwiddles): 242 VGPRs instead of 230, no
+  // spill, cfg1 8.53 -> 8.47 ms.  Only here: the same set in the team and wide kernels was built and measured, and
+  // either spilled, lost time or moved nothing that was timed (profiles/twiddle_reads_ab.txt, `part2`).
+  typename LowestWindowTwiddles<F, LOGN - 1, 0>::type low;
+  low.load(c);
   const size_t ggsw_words = (size_t)(K + 1) * P.levels * (K + 1) * 2 * (N >> 1);  // elements
 #pragma unroll 1
   for (u32 i = i_begin; i < i_end; ++i) {
@@ -1293,7 +1318,7 @@ TFHE_HD void blind_rotate_pair(const Ctx& c, const PbsParams& P, const u32* lwe 
     const RotatingOperand<LOGN, T> src(acc, tid, a_tilde);
     // each half reads and updates only its own polynomial, the rotated reads all happen before the first update
     auto out = [&](int j, u32 value) { c.lds_add(acc + j, value); };
-    external_product_pair<F, LOGN>(c, P, bsk + (size_t)i * ggsw_words, src, out);
+    external_product_pair<F, LOGN>(c, P, bsk + (size_t)i * ggsw_words, src, out, low);
     c.wave_sync();
   }
 }

@@ -520,11 +520,11 @@ TFHE_HD void ntt_transpose(const Ctx& c, typename F::elem (&x)[NttShape<LOGN, G>
 // In the low windows every lane has its own twiddles (hi = tid >> LO differs), read from the working copy in LDS.
 // Left to the compiler each ds_read sits right in front of its butterfly -- the wave-level fences of the
 // transposes forbid hoisting it -- behind an s_waitcnt that exposes the LDS round trip: a dozen of them per pass
-// in the ISA of round 2's kernel.  PassTwiddles reads all of a pass's twiddles (1 + 2 + 4 for a three-bit window)
-// in one clump BEFORE the transpose that precedes the pass: the LDS pipe is in order per wave, so they arrive
-// before the transposed elements do, and the pass starts with every operand in registers.  Costs their registers
-// (28 VGPRs for 16-byte elements at e = 3) across the transpose, so a field opts in (F::kPreloadTwiddles): the
-// complex transform has them, the 8-byte fields at 16 elements per lane do not.
+// in the ISA of round 2's kernel.  PassTwiddles reads all of a pass's twiddles (1 + 2 + 4 for a three-bit window; the
+// complex transform 1 + 1 + 2, see below) in one clump BEFORE the transpose that precedes the pass: the LDS pipe is in
+// order per wave, so they arrive before the transposed elements do, and the pass starts with every operand in registers.
+// Costs their registers (16 VGPRs for the complex transform's four 16-byte elements at e = 3) across the transpose, so a
+// field opts in (F::kPreloadTwiddles): the complex transform has them, the 8-byte fields at 16 elements per lane do not.
 // ---------------------------------------------------------------------------------------------
 template <class F, class = void>
 struct PreloadsTwiddles {
@@ -550,11 +550,30 @@ TFHE_HD int ntt_low_twiddle_slot(int tid, int b, int i) {
   return TR ? m + (cnt - 1 - i) * H + (H - 1 - hi) : 2 * m - 1 - hi * cnt - i;
 }
 
+// Siblings by rotation (F::kSiblingTwiddleIsRotation: the complex transform).  Where node 2j + 1 of a stage is i times node
+// 2j -- field_fft.h: the table is written that way, bit for bit -- a stage that uses cnt >= 2 twiddles per lane reads only
+// its even ones, cnt / 2, and get() hands out the odd ones as (-im, re) of their neighbour: a value permutation with one
+// sign, which the butterflies' FMAs take as input modifiers, no instruction of its own.  Node parity is the parity of i:
+// the node is m + hi cnt + i with m and cnt even.  4 reads instead of 7 for a three-bit window, 2 instead of 3 for a
+// two-bit one; the prime fields have no such relation and keep every read.
+template <class F, class = void>
+struct SiblingTwiddleIsRotation {
+  static constexpr bool value = false;
+};
+template <class F>
+struct SiblingTwiddleIsRotation<F, decltype((void)F::kSiblingTwiddleIsRotation)> {
+  static constexpr bool value = F::kSiblingTwiddleIsRotation;
+};
+
 template <class F, int LOGN, int G, int LO, int BHI, int BLO, bool INVERSE>
 struct PassTwiddles {
   typedef typename F::elem elem;
   static constexpr int E = NttShape<LOGN, G>::kE;
-  static constexpr int count_from(int b) { return b > BHI ? 0 : (E >> (b - LO + 1)) + count_from(b + 1); }
+  static constexpr bool ROT = SiblingTwiddleIsRotation<F>::value;
+  static constexpr int used(int b) { return E >> (b - LO + 1); }  // twiddles a lane uses at stage b
+  static constexpr bool halved(int b) { return ROT && used(b) >= 2; }
+  static constexpr int held(int b) { return halved(b) ? used(b) / 2 : used(b); }  // ... and reads
+  static constexpr int count_from(int b) { return b > BHI ? 0 : held(b) + count_from(b + 1); }
   static constexpr int kCount = count_from(BLO);
   // stage b's twiddles start behind those of the stages above it (b + 1 .. BHI)
   static constexpr int offset(int b) { return count_from(b + 1); }
@@ -566,9 +585,18 @@ struct PassTwiddles {
 #pragma unroll
     for (int b = BHI; b >= BLO; --b)
 #pragma unroll
-      for (int i = 0; i < (E >> (b - LO + 1)); ++i) w[offset(b) + i] = tw[ntt_low_twiddle_slot<F, LOGN, G, LO, INVERSE>(tid, b, i)];
+      for (int i = 0; i < held(b); ++i)
+        w[offset(b) + i] = tw[ntt_low_twiddle_slot<F, LOGN, G, LO, INVERSE>(tid, b, halved(b) ? 2 * i : i)];
   }
-  TFHE_HD elem get(int b, int i) const { return w[offset(b) + i]; }
+  TFHE_HD elem get(int b, int i) const {
+    if constexpr (ROT) {
+      if (halved(b)) {
+        const elem even = w[offset(b) + (i >> 1)];
+        return (i & 1) ? F::rotate_twiddle(even) : even;
+      }
+    }
+    return w[offset(b) + i];
+  }
 };
 // the pass reads its twiddles itself, one by one (fields that do not preload, and every top window)
 struct NoPassTwiddles {};
@@ -733,17 +761,36 @@ struct LowPassTwiddles<F, LOGN, G, LO, BHI, BLO, INVERSE, false> : NoPassTwiddle
   TFHE_HD void load(const Ctx&) {}
 };
 
+// The LOWEST window's twiddles, resident.  The forward transform's last pass and the inverse transform's first one work in
+// window [0, ..) on the same nodes -- for a field whose inverse butterfly reads the forward entry (the complex transform:
+// ntt_low_twiddle_slot returns the same slot, butterfly_inverse conjugates) -- and they are the same for every transform of a
+// blind rotation.  A caller that has the registers loads them once (LowestWindowTwiddles<F, LOGN, G>::type, load()) and
+// hands them to ntt_forward / ntt_forward_multi and ntt_inverse_pair as `low`, in place of that window's clump of reads;
+// the default NoPassTwiddles keeps the per-transform reads.
+template <class F, int LOGN, int G>
+struct LowestWindowTwiddles {
+  using S = NttShape<LOGN, G>;
+  static_assert(F::kLogShrink == 1, "one set for both directions: the inverse butterfly reads the forward entry");
+  static constexpr int kBHi = (S::kPasses == 3 ? S::kLo2 : S::kPasses == 4 ? S::kLo3 : S::kLo4) - 1;
+  typedef PassTwiddles<F, LOGN, G, 0, kBHi, 0, false> type;
+};
+template <class Low>
+constexpr bool has_resident_twiddles() {
+  return !std::is_base_of<NoPassTwiddles, Low>::value;
+}
+
 // before_first_store(): called once, after the first register pass and before the first store into the buffer -- the
 // place for a barrier that only has to precede the buffer's reuse (pbs_wave.h: LATE)
 struct NothingBefore {
   TFHE_HD void operator()() const {}
 };
 template <class F, int LOGN, int G, bool SMALL_INPUT = false, bool AFTER_BARRIER = false, int NS, class Ctx, class Top,
-          class Before = NothingBefore>
+          class Before = NothingBefore, class Low = NoPassTwiddles>
 TFHE_HD void ntt_forward_multi(const Ctx (&c)[NS], typename F::elem (&x)[NS][NttShape<LOGN, G>::kE], const Top& top,
-                               const Before& before_first_store = Before{}) {
+                               const Before& before_first_store = Before{}, const Low& low = Low{}) {
   using S = NttShape<LOGN, G>;
   constexpr bool PRE = PreloadsTwiddles<F>::value;
+  constexpr bool RES = has_resident_twiddles<Low>();  // the last pass takes `low`
   ntt_pass_forward_each<F, LOGN, G, S::kLo1, LOGN - 1, S::kTBits, SMALL_INPUT>(c, x, top, NoPassTwiddles{});
   // every low pass's twiddles are read before the transpose in front of it (PassTwiddles)
   LowPassTwiddles<F, LOGN, G, S::kLo2, S::kTBits - 1, S::kLo2, false, PRE> t2;
@@ -751,17 +798,28 @@ TFHE_HD void ntt_forward_multi(const Ctx (&c)[NS], typename F::elem (&x)[NS][Ntt
   before_first_store();
   ntt_transpose_multi<F, LOGN, G, S::kLo1, S::kLo2, AFTER_BARRIER>(c, x);
   ntt_pass_forward_each<F, LOGN, G, S::kLo2, S::kTBits - 1, S::kLo2, false>(c, x, top, t2);
-  LowPassTwiddles<F, LOGN, G, S::kLo3, S::kLo2 - 1, S::kLo3, false, PRE> t3;
-  t3.load(c[0]);
-  ntt_transpose_multi<F, LOGN, G, S::kLo2, S::kLo3>(c, x);
-  ntt_pass_forward_each<F, LOGN, G, S::kLo3, S::kLo2 - 1, S::kLo3, false>(c, x, top, t3);
+  if constexpr (RES && S::kPasses == 3) {
+    ntt_transpose_multi<F, LOGN, G, S::kLo2, S::kLo3>(c, x);
+    ntt_pass_forward_each<F, LOGN, G, S::kLo3, S::kLo2 - 1, S::kLo3, false>(c, x, top, low);
+  } else {
+    LowPassTwiddles<F, LOGN, G, S::kLo3, S::kLo2 - 1, S::kLo3, false, PRE> t3;
+    t3.load(c[0]);
+    ntt_transpose_multi<F, LOGN, G, S::kLo2, S::kLo3>(c, x);
+    ntt_pass_forward_each<F, LOGN, G, S::kLo3, S::kLo2 - 1, S::kLo3, false>(c, x, top, t3);
+  }
   if constexpr (S::kPasses >= 4) {
-    LowPassTwiddles<F, LOGN, G, S::kLo4, S::kLo3 - 1, S::kLo4, false, PRE> t4;
-    t4.load(c[0]);
-    ntt_transpose_multi<F, LOGN, G, S::kLo3, S::kLo4>(c, x);
-    ntt_pass_forward_each<F, LOGN, G, S::kLo4, S::kLo3 - 1, S::kLo4, false>(c, x, top, t4);
+    if constexpr (RES && S::kPasses == 4) {
+      ntt_transpose_multi<F, LOGN, G, S::kLo3, S::kLo4>(c, x);
+      ntt_pass_forward_each<F, LOGN, G, S::kLo4, S::kLo3 - 1, S::kLo4, false>(c, x, top, low);
+    } else {
+      LowPassTwiddles<F, LOGN, G, S::kLo4, S::kLo3 - 1, S::kLo4, false, PRE> t4;
+      t4.load(c[0]);
+      ntt_transpose_multi<F, LOGN, G, S::kLo3, S::kLo4>(c, x);
+      ntt_pass_forward_each<F, LOGN, G, S::kLo4, S::kLo3 - 1, S::kLo4, false>(c, x, top, t4);
+    }
   }
   if constexpr (S::kPasses == 5) {
+    static_assert(!RES || S::kPasses < 5, "no resident set in the five-pass shapes");
     LowPassTwiddles<F, LOGN, G, S::kLo5, S::kLo4 - 1, 0, false, PRE> t5;
     t5.load(c[0]);
     ntt_transpose_multi<F, LOGN, G, S::kLo4, S::kLo5>(c, x);
@@ -769,11 +827,11 @@ TFHE_HD void ntt_forward_multi(const Ctx (&c)[NS], typename F::elem (&x)[NS][Ntt
   }
 }
 
-template <class F, int LOGN, int G, bool SMALL_INPUT = false, bool AFTER_BARRIER = false, class Ctx, class Top>
-TFHE_HD void ntt_forward(const Ctx& c, typename F::elem (&x)[NttShape<LOGN, G>::kE], const Top& top) {
+template <class F, int LOGN, int G, bool SMALL_INPUT = false, bool AFTER_BARRIER = false, class Ctx, class Top, class Low = NoPassTwiddles>
+TFHE_HD void ntt_forward(const Ctx& c, typename F::elem (&x)[NttShape<LOGN, G>::kE], const Top& top, const Low& low = Low{}) {
   const Ctx cs[1] = {c};
   ntt_forward_multi<F, LOGN, G, SMALL_INPUT, AFTER_BARRIER, 1>(
-      cs, reinterpret_cast<typename F::elem (&)[1][NttShape<LOGN, G>::kE]>(x), top);
+      cs, reinterpret_cast<typename F::elem (&)[1][NttShape<LOGN, G>::kE]>(x), top, NothingBefore{}, low);
 }
 
 template <class F, int LOGN, int G, bool SMALL_INPUT = false, bool AFTER_BARRIER = false, class Ctx>
@@ -833,19 +891,33 @@ TFHE_HD void ntt_inverse(const Ctx& c, typename F::elem (&x)[NttShape<LOGN, G>::
   ntt_inverse<F, LOGN, G>(c, x, top);
 }
 
+// the first inverse pass's twiddles: the resident set itself, or a set read here
+template <class Own, class Ctx, class Low>
+TFHE_HD typename std::conditional<has_resident_twiddles<Low>(), const Low&, Own>::type first_pass_twiddles(const Ctx& c, const Low& low) {
+  if constexpr (has_resident_twiddles<Low>()) {
+    return low;
+  } else {
+    Own t;
+    t.load(c);
+    return t;
+  }
+}
+
 // Two polynomials through ONE wave-private buffer, half a step apart: pass(a); T(a); pass(b); T(b); pass'(a); ...  A
 // transpose is eight stores and eight loads; the wave's LDS operations execute in order, so b's stores follow a's loads
 // into the same buffer without a wait, and the round trip of a's transpose is covered by b's register pass (and the
 // other way round) instead of by nothing.  Three-pass shapes with wave-local transposes only (G = 1).
-template <class F, int LOGN, int G, class Ctx, class Top, class Before = NothingBefore>
+template <class F, int LOGN, int G, class Ctx, class Top, class Before = NothingBefore, class Low = NoPassTwiddles>
 TFHE_HD void ntt_inverse_pair(const Ctx& c, typename F::elem (&a)[NttShape<LOGN, G>::kE],
                               typename F::elem (&b)[NttShape<LOGN, G>::kE], const Top& top,
-                              const Before& before_first_store = Before{}) {
+                              const Before& before_first_store = Before{}, const Low& low = Low{}) {
   using S = NttShape<LOGN, G>;
   static_assert(G <= 1 && S::kPasses == 3, "wave-local transposes, three passes");
   constexpr bool PRE = PreloadsTwiddles<F>::value;
-  LowPassTwiddles<F, LOGN, G, S::kLo3, S::kLo2 - 1, S::kLo3, true, PRE> t3;
-  t3.load(c);
+  // (the first pass of both: the caller's resident set, or read on entry)
+  typename std::conditional<has_resident_twiddles<Low>(), const Low&,
+                            LowPassTwiddles<F, LOGN, G, S::kLo3, S::kLo2 - 1, S::kLo3, true, PRE>>::type t3 = first_pass_twiddles<
+      LowPassTwiddles<F, LOGN, G, S::kLo3, S::kLo2 - 1, S::kLo3, true, PRE>>(c, low);
   ntt_pass_inverse<F, LOGN, G, S::kLo3, S::kLo2 - 1, S::kLo3>(c, a, top, t3);
   before_first_store();
   ntt_transpose<F, LOGN, G, S::kLo3, S::kLo2>(c, a);
