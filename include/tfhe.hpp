@@ -823,6 +823,57 @@ inline std::vector<LweCiphertext> sample_extract_indices(Engine& e, const GlweCi
     out.push_back(LweCiphertext{std::vector<uint32_t>(res.begin() + i * words, res.begin() + (i + 1) * words)});
   return out;
 }
+// ---- GLWE key switching and automorphisms X -> X^t (tfhe_hip.h states the operation; first device only) ----
+// sigma_t of a binary GLWE key [k][N] -> [k][N] with entries in {-1, 0, 1}: the from_polys of the automorphism key for t
+inline std::vector<int32_t> glwe_sk_automorphism(const TfheParams& p, const std::vector<uint32_t>& glwe_sk, size_t t) {
+  if (glwe_sk.size() != size_t(p.glwe_dimension) * p.degree()) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "GLWE key [k][N]");
+  std::vector<int32_t> out(glwe_sk.size());
+  const int st = tfhe_glwe_sk_automorphism(glwe_sk.data(), p.glwe_dimension, p.glwe_poly_degree, t, out.data());
+  if (st != TFHE_OK) throw TfheError(st, "glwe_sk_automorphism: a binary key and an odd t in [1, 2N)");
+  return out;
+}
+// A prepared switch key.  `samples` [k l_ks][k+1][N]: pre-filled row by row like encrypt_glwe_zero (uniform masks, errors
+// in the body) and completed here for from_polys [k][N] (entries in {-1, 0, 1}) and glwe_sk [k][N]; or an already
+// generated key.  TFHE_ERR_EXACTNESS with the reason where the backend refuses a packing key.  Move-only; released with
+// the object, before its engine.
+class GlweSwitchKey {
+ public:
+  GlweSwitchKey(Engine& e, const std::vector<int32_t>& from_polys, const std::vector<uint32_t>& glwe_sk, std::vector<uint32_t> samples) {
+    const size_t kn = size_t(e.params().glwe_dimension) * e.params().degree();
+    if (from_polys.size() != kn || glwe_sk.size() != kn) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "from_polys and glwe_sk [k][N]");
+    check_words(e, samples);
+    e.check(tfhe_generate_glwe_switch_key(e.raw(), from_polys.data(), glwe_sk.data(), samples.data()));
+    e.check(tfhe_prepare_glwe_switch_key(e.raw(), samples.data(), &key_));
+  }
+  GlweSwitchKey(Engine& e, const std::vector<uint32_t>& key) {
+    check_words(e, key);
+    e.check(tfhe_prepare_glwe_switch_key(e.raw(), key.data(), &key_));
+  }
+  GlweSwitchKey(const GlweSwitchKey&) = delete;
+  GlweSwitchKey& operator=(const GlweSwitchKey&) = delete;
+  GlweSwitchKey(GlweSwitchKey&& o) noexcept : key_(o.key_) { o.key_ = nullptr; }
+  ~GlweSwitchKey() { tfhe_glwe_switch_key_destroy(key_); }
+  const tfhe_glwe_switch_key* raw() const { return key_; }
+
+ private:
+  static void check_words(Engine& e, const std::vector<uint32_t>& key) {
+    const TfheParams& p = e.params();
+    if (key.size() != size_t(p.glwe_dimension) * p.ks_decomposer.levels * (p.glwe_dimension + 1) * p.degree())
+      throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "switch key [k l_ks][k+1][N]");
+  }
+  tfhe_glwe_switch_key* key_ = nullptr;
+};
+// Auto_t(ct; key) (+ ct with add_input): X -> X^t and the switch back to the engine's key, for ONE ciphertext
+inline GlweCiphertext glwe_automorphism(Engine& e, const GlweCiphertext& ct, size_t t, const GlweSwitchKey& key, bool add_input = false) {
+  if (ct.data.size() != size_t(e.params().glwe_dimension + 1) * e.params().degree()) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "GLWE length");
+  GlweCiphertext out{std::vector<uint32_t>(ct.data.size())};
+  e.check(tfhe_glwe_automorphism_batch(e.raw(), ct.data.data(), 1, t, key.raw(), add_input ? 1 : 0, out.data.data()));
+  return out;
+}
+// the plain GLWE key switch (t = 1): from the key's source key to the engine's
+inline GlweCiphertext glwe_key_switch(Engine& e, const GlweCiphertext& ct, const GlweSwitchKey& key) {
+  return glwe_automorphism(e, ct, 1, key);
+}
 // ---- multi-value bootstrapping (tfhe_hip.h states the operations; first device only) ----
 // every lookup table of `luts` (tables x B un-encoded values, row-major) of ONE ciphertext of n + 1 words from one blind
 // rotation (the reference's bootstrap order, like the neighbouring wrappers) -> one ciphertext per table

@@ -249,6 +249,71 @@ int tfhe_pack_lwe_batch(tfhe_context *ctx, const uint32_t *lwe_in, size_t groups
 int tfhe_pack_lwe_batch_device(tfhe_context *ctx, const uint32_t *lwe_in, size_t groups, size_t per_group,
                                uint32_t *glwe_out);
 
+/* ---- GLWE key switching and automorphisms (no reference counterpart): X -> X^t in one fused launch ------------------
+ * Ring Z_{2^32}[X] / (X^N + 1).  For odd t in [1, 2N), sigma_t(p)(X) = p(X^t): coefficient j of p lands on index
+ * j*t mod N, negated when j*t mod 2N >= N.  Gather form, with u = t^-1 mod 2N: sigma_t(p)[m] = p[m*u mod 2N] if that
+ * index is < N, else -p[(m*u mod 2N) - N].  The sigma_t are exactly the signed coefficient permutations that respect the
+ * ring's product: t = 2N-1 reverses, and x + sigma_t(x) is one step of the trace (below).
+ *
+ * A switch key for polynomials F_0 .. F_{k-1} with coefficients in {-1, 0, 1} is key [k*l_ks][k+1][N]: row i*l_ks + l
+ * a GLWE encryption under the context's GLWE key S of F_i(X) * g_l, g_l the KS decomposer's gadget factor in the
+ * context's alignment mode exactly as tfhe_generate_packing_key uses it (a coefficient -1 adds 0 - g_l).
+ * F = sigma_t(S) (tfhe_glwe_sk_automorphism) gives the automorphism key for t; F = S' (binary) the key that switches
+ * from S' to S.  For c = (A_0 .. A_{k-1}, B):
+ *
+ *   Auto_t(c; KEY) = (0, .., 0, sigma_t(B)) - sum_{i<k} sum_{l<l_ks} dec_l(sigma_t(A_i)) (*) KEY[i*l_ks + l]
+ *
+ * with dec_l and (*) as in the packing formula above.  With add_input the input ciphertext is added to the result in
+ * wrapping 32-bit words: x + Auto_t(x), one trace step.  t = 1 is the plain GLWE key switch.  An automorphism turns
+ * a ciphertext under S into one under sigma_t(S) and is usable only together with the switch back: key == NULL is the
+ * bare permutation (one elementwise launch, the result under sigma_t(S); add_input is refused), for clients and tests.
+ *
+ * Identity.  Under a noise-free key, for any masks, phi_S(Auto_t(c)) = sigma_t(B) - sum_i F_i (*) Rec(sigma_t(A_i)),
+ * Rec the decomposer's recomposition coefficient by coefficient.  Where no bits are ignored this is sigma_t(phi_S(c))
+ * exactly (F = sigma_t(S)); with the aligned decomposer and ig ignored bits it holds within k*N*2^(ig-1); the literal
+ * decomposer at bases that do not divide 32 keeps its known quirk and only the Rec form holds.
+ *
+ * Partial trace.  Step j = 1..s applies x <- x + Auto_{t_j}(x) with t_j = N/2^(j-1) + 1.  After s steps a coefficient
+ * whose index is a multiple of 2^s holds 2^s TIMES its value and every other coefficient holds 0 -- cleared without
+ * knowing any of them, which no product with a clear mask can do.  The factor 2^s is unavoidable (N has no inverse mod
+ * 2^32): it comes out of the caller's scale, so encode s bits below the scale the result is read at.
+ *
+ * Noise.  An output coefficient carries its permuted input's noise (on a kept coefficient of a trace step exactly
+ * twice the input's: the same error is added to itself) plus variance
+ *   s_ks^2 = k * l_ks * N * (B_ks^2/12 + 1/6) * (sigma_glwe * 2^32)^2 + (k*N/2) * 2^(2*ignored_bits_ks) / 12
+ * in units of the 32-bit torus: the packing formula's with d*m replaced by k polynomials of N coefficients.  After s
+ * trace steps: 4^s * var_in + s_ks^2 * (4^s - 1) / 3.
+ *
+ * Exactness: the product sums ONE slice of (k+1) l_ks rows in the KS base -- the packing key's rule, unchanged.  A
+ * backend that refuses a packing key under the context's parameters refuses a switch key
+ * (tfhe_prepare_glwe_switch_key*: TFHE_ERR_EXACTNESS, the reason in tfhe_last_error); nothing is computed outside a
+ * proven bound.
+ *
+ * tfhe_generate_glwe_switch_key completes a buffer pre-filled row by row like tfhe_glwe_encrypt_zero_batch (masks
+ * uniform, body = error); from_polys [k][N] (int32, entries in {-1, 0, 1}, else TFHE_ERR_INVALID_ARGUMENT) and glwe_sk
+ * [k][N] (binary) are host arrays; the _device form takes key on the device.  tfhe_glwe_sk_automorphism is host-only
+ * arithmetic: out [k][N] = sigma_t(glwe_sk).  tfhe_prepare_glwe_switch_key makes an opaque handle that owns the
+ * prepared key on the device (this one call synchronises).  The handle belongs to the context that made it -- another
+ * context's or backend's is TFHE_ERR_INVALID_ARGUMENT --, is independent of the bootstrapping and the packing key
+ * (loading either leaves it valid), and is destroyed by the caller (NULL is allowed) before its context.  Any number
+ * may live at once; a trace needs log2 N at most.
+ *
+ * glwe_in, glwe_out [batch][k+1][N], 1 <= batch < 2^31; glwe_out may BE glwe_in (any other overlap is refused).  One
+ * launch of `batch` teams: no workspace, nothing allocated or synchronised, so the _device form can be captured as it
+ * stands.  An even t or t >= 2N is TFHE_ERR_INVALID_ARGUMENT with the reason in tfhe_last_error. */
+typedef struct tfhe_glwe_switch_key tfhe_glwe_switch_key;
+int tfhe_glwe_sk_automorphism(const uint32_t *glwe_sk, size_t k, unsigned log_n, size_t t, int32_t *out);
+int tfhe_generate_glwe_switch_key(tfhe_context *ctx, const int32_t *from_polys, const uint32_t *glwe_sk, uint32_t *key);
+int tfhe_generate_glwe_switch_key_device(tfhe_context *ctx, const int32_t *from_polys, const uint32_t *glwe_sk,
+                                         uint32_t *key);
+int tfhe_prepare_glwe_switch_key(tfhe_context *ctx, const uint32_t *key, tfhe_glwe_switch_key **out);
+int tfhe_prepare_glwe_switch_key_device(tfhe_context *ctx, const uint32_t *key, tfhe_glwe_switch_key **out);
+void tfhe_glwe_switch_key_destroy(tfhe_glwe_switch_key *key);
+int tfhe_glwe_automorphism_batch(tfhe_context *ctx, const uint32_t *glwe_in, size_t batch, size_t t,
+                                 const tfhe_glwe_switch_key *key, int add_input, uint32_t *glwe_out);
+int tfhe_glwe_automorphism_batch_device(tfhe_context *ctx, const uint32_t *glwe_in, size_t batch, size_t t,
+                                        const tfhe_glwe_switch_key *key, int add_input, uint32_t *glwe_out);
+
 /* ---- tree LUT: a function of d digits of log_p bits each (no reference counterpart) ---------------------------------
  * The tree-based bootstrap of Guimaraes, Borin and Aranha (2021).  Inputs and output are ordinary LWE ciphertexts at
  * the bootstrap boundary, so it composes with gates, gate graphs and itself; its noise does not depend on the table

@@ -27,6 +27,7 @@ pub struct CTfheParams {
 
 #[repr(C)] pub struct TfheContext { _private: [u8; 0] }
 #[repr(C)] pub struct TfhePolyWeights { _private: [u8; 0] }
+#[repr(C)] pub struct TfheGlweSwitchKey { _private: [u8; 0] }
 #[repr(C)] pub struct TfhePool { _private: [u8; 0] }
 
 extern "C" {
@@ -107,6 +108,13 @@ extern "C" {
                             bias: *const u32, out: *mut u32) -> c_int;
     fn tfhe_sample_extract_indices(ctx: *mut TfheContext, glwe: *const u32, batch: usize, indices: *const u32, count: usize,
                                    lwe_out: *mut u32) -> c_int;
+    // GLWE key switching and automorphisms (include/tfhe_hip.h)
+    fn tfhe_glwe_sk_automorphism(glwe_sk: *const u32, k: usize, log_n: u32, t: usize, out: *mut i32) -> c_int;
+    fn tfhe_generate_glwe_switch_key(ctx: *mut TfheContext, from_polys: *const i32, glwe_sk: *const u32, key: *mut u32) -> c_int;
+    fn tfhe_prepare_glwe_switch_key(ctx: *mut TfheContext, key: *const u32, out: *mut *mut TfheGlweSwitchKey) -> c_int;
+    fn tfhe_glwe_switch_key_destroy(key: *mut TfheGlweSwitchKey);
+    fn tfhe_glwe_automorphism_batch(ctx: *mut TfheContext, glwe_in: *const u32, batch: usize, t: usize,
+                                    key: *const TfheGlweSwitchKey, add_input: c_int, glwe_out: *mut u32) -> c_int;
     fn tfhe_cmux_batch(ctx: *mut TfheContext, ggsw: *const u32, ggsw_count: usize, ct0: *const u32,
                        ct1: *mut u32, batch: usize, glwe_out: *mut u32) -> c_int;
     fn tfhe_gate_batch(ctx: *mut TfheContext, truth: *const u32, ct0: *const u32, ct1: *const u32,
@@ -597,6 +605,66 @@ pub fn sample_extract_indices(bk: &GpuBootstrappingKey, glwe: &Array3<u32>, indi
                                     out.as_slice_mut().unwrap().as_mut_ptr())
     }, "sample_extract_indices");
     out
+}
+
+/// sigma_t of a binary GLWE key (k, N) -> (k, N) with entries in {-1, 0, 1}: the `from_polys` of the automorphism key for t
+pub fn glwe_sk_automorphism(glwe_sk: &Array2<u32>, t: usize) -> Array2<i32> {
+    let (k, n) = glwe_sk.dim();
+    assert!(n.is_power_of_two(), "glwe_sk_automorphism: glwe_sk (k, N)");
+    let mut out = Array2::<i32>::zeros((k, n));
+    let st = unsafe {
+        tfhe_glwe_sk_automorphism(glwe_sk.as_slice().unwrap().as_ptr(), k, n.trailing_zeros(), t, out.as_slice_mut().unwrap().as_mut_ptr())
+    };
+    assert!(st == 0, "glwe_sk_automorphism: a binary key and an odd t in [1, 2N) expected (status {st})");
+    out
+}
+
+/// A prepared GLWE switch key (no reference counterpart): `samples` (k * l_ks, k+1, N) pre-filled row by row like
+/// encrypt_glwe_zero (uniform masks, errors in the body) are completed for `from_polys` (k, N), entries in {-1, 0, 1},
+/// and `glwe_sk` (k, N), then prepared on the device; panics with the backend's reason where it refuses a packing key.
+/// Released on drop, before the key it was made with.
+pub struct GlweSwitchKey { raw: *mut TfheGlweSwitchKey }
+
+impl GlweSwitchKey {
+    pub fn new(bk: &GpuBootstrappingKey, from_polys: &Array2<i32>, glwe_sk: &Array2<u32>, samples: &Array3<u32>) -> Self {
+        let (k, n) = (bk.params.glwe_dimension as usize, 1usize << bk.params.glwe_poly_degree);
+        assert!(from_polys.dim() == (k, n) && glwe_sk.dim() == (k, n)
+                && samples.dim() == (k * bk.params.ks_decomposer.levels as usize, k + 1, n),
+                "GlweSwitchKey: from_polys (k, N), glwe_sk (k, N), samples (k * l_ks, k+1, N)");
+        let mut key = samples.clone();
+        check(bk.ctx, unsafe {
+            tfhe_generate_glwe_switch_key(bk.ctx, from_polys.as_slice().unwrap().as_ptr(), glwe_sk.as_slice().unwrap().as_ptr(),
+                                          key.as_slice_mut().unwrap().as_mut_ptr())
+        }, "generate_glwe_switch_key");
+        let mut raw = std::ptr::null_mut();
+        check(bk.ctx, unsafe { tfhe_prepare_glwe_switch_key(bk.ctx, key.as_slice().unwrap().as_ptr(), &mut raw) },
+              "prepare_glwe_switch_key");
+        GlweSwitchKey { raw }
+    }
+}
+
+impl Drop for GlweSwitchKey {
+    fn drop(&mut self) {
+        unsafe { tfhe_glwe_switch_key_destroy(self.raw) };
+    }
+}
+
+/// Auto_t(glwe; key) (+ glwe with `add_input`) for every ciphertext of `glwe` (batch, k+1, N): X -> X^t and the switch back
+/// to the context's key in one launch; t odd and below 2N
+pub fn glwe_automorphism(bk: &GpuBootstrappingKey, glwe: &Array3<u32>, t: usize, key: &GlweSwitchKey, add_input: bool) -> Array3<u32> {
+    let (batch, polys, n) = glwe.dim();
+    assert!(polys == bk.params.glwe_dimension as usize + 1 && n == 1usize << bk.params.glwe_poly_degree, "glwe_automorphism: glwe (batch, k+1, N)");
+    let mut out = Array3::<u32>::zeros((batch, polys, n));
+    check(bk.ctx, unsafe {
+        tfhe_glwe_automorphism_batch(bk.ctx, glwe.as_slice().unwrap().as_ptr(), batch, t, key.raw, add_input as c_int,
+                                     out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "glwe_automorphism");
+    out
+}
+
+/// the plain GLWE key switch (t = 1): from the key's source key to the context's
+pub fn glwe_key_switch(bk: &GpuBootstrappingKey, glwe: &Array3<u32>, key: &GlweSwitchKey) -> Array3<u32> {
+    glwe_automorphism(bk, glwe, 1, key, false)
 }
 
 /// ggsw.rs:132-136

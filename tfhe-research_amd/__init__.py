@@ -114,6 +114,10 @@ class TfheParams:
         """the packing key from an LWE key of `from_dimension` bits: one GLWE row per (key bit, KS level)"""
         return (from_dimension * self.ks_decomposer.levels, self.k + 1, self.N)
 
+    def glwe_switch_key_shape(self):
+        """a GLWE switch key: one GLWE row per (polynomial of the source key, KS level)"""
+        return (self.k * self.ks_decomposer.levels, self.k + 1, self.N)
+
     def external_product_bytes(self) -> int:
         """algorithmic bytes of one GGSW x GLWE external product in the reference's u32 layout,
         each operand moved once: 4*N*(k+1)*((k+1)*l + 2)  """
@@ -464,6 +468,31 @@ class PolyWeights:
         Context._check_quiet(lib().tfhe_poly_weights_info(self._h, C.byref(o), C.byref(c), C.byref(bits), C.byref(rows)),
                              "the weight set is closed")
         return {"outputs": o.value, "channels": c.value, "weight_bits": bits.value, "rows_per_pass": rows.value}
+
+
+class GlweSwitchKey:
+    """A prepared GLWE switch key (Context.prepare_glwe_switch_key): lives on the device of the context that prepared it
+    and belongs to that context; usable until close() (close it before its context)."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().tfhe_glwe_switch_key_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class Context:
@@ -952,6 +981,129 @@ class Context:
         res = _result("pack_lwe", dev, out, (int(x.shape[0]), p.k + 1, p.N), x)
         self._call("tfhe_pack_lwe_batch", dev, _ptr(x), C.c_size_t(x.shape[0]), C.c_size_t(x.shape[1]), _ptr(res))
         return res
+
+    # -- GLWE key switching and automorphisms X -> X^t (include/tfhe_hip.h states the operation) --
+    def glwe_sk_automorphism(self, glwe_sk, t: int) -> np.ndarray:
+        """sigma_t(glwe_sk) as int32 [k][N] with entries in {-1, 0, 1}: the from_polys of the automorphism key for t
+        (host arithmetic only)"""
+        p = self.params
+        sk = _np(glwe_sk).reshape(p.k, p.N)
+        out = np.zeros((p.k, p.N), dtype=np.int32)
+        if t < 0:
+            raise _invalid("glwe_sk_automorphism: t must be odd and in [1, 2N)")
+        self._check_quiet(lib().tfhe_glwe_sk_automorphism(_ptr(sk), C.c_size_t(p.k), C.c_uint(p.glwe_poly_degree), C.c_size_t(t),
+                                                          C.c_void_p(out.ctypes.data)),
+                          "glwe_sk_automorphism: a binary key and an odd t in [1, 2N) expected")
+        return out
+
+    def _from_polys(self, what, from_polys) -> np.ndarray:
+        p = self.params
+        f = np.asarray(from_polys)
+        if f.size != p.k * p.N or not (np.issubdtype(f.dtype, np.integer) or f.dtype == np.bool_):
+            raise _invalid(f"{what}: integer from_polys [{p.k}][{p.N}] expected, got {tuple(f.shape)}")
+        f = f.astype(np.int64).reshape(p.k, p.N)
+        f = np.where(f > (1 << 31), f - (1 << 32), f)  # a -1 that arrives as the u32 word 2^32 - 1
+        if f.size and (int(f.max()) > 1 or int(f.min()) < -1):
+            raise _invalid(f"{what}: from_polys must have coefficients in {{-1, 0, 1}}")
+        return np.ascontiguousarray(f, dtype=np.int32)
+
+    def generate_glwe_switch_key(self, from_polys, glwe_sk, samples):
+        """samples [k*l_ks][k+1][N] pre-filled row by row like glwe_encrypt_zero (uniform masks, errors in the body) -> the
+        switch key from the polynomials from_polys [k][N] (entries in {-1, 0, 1}: another binary GLWE key, or
+        glwe_sk_automorphism(glwe_sk, t)) to glwe_sk, with the context's ks_decomposer.  A torch device tensor is
+        completed in place and returned; a numpy array is copied."""
+        p = self.params
+        f = self._from_polys("generate_glwe_switch_key", from_polys)
+        sk = _np(glwe_sk).reshape(p.k, p.N)
+        dev = _is_torch(samples)
+        key = samples if dev else _np(samples).copy()
+        _check_u32("generate_glwe_switch_key", "samples", key, dev, (p.k * p.ks_decomposer.levels, p.k + 1, p.N))
+        self._call("tfhe_generate_glwe_switch_key", dev, C.c_void_p(f.ctypes.data), _ptr(sk), _ptr(key))
+        return key
+
+    def generate_glwe_switch_key_random(self, from_polys, glwe_sk, rng=None) -> np.ndarray:
+        """generate_glwe_switch_key with masks and errors (glwe_std_dev) drawn here, the way generate_keys draws the
+        bootstrapping key's (the OS CSPRNG unless the test hook `rng=` is given)"""
+        p = self.params
+        rng = rng if rng is not None else SystemRng()
+        shape = (p.k * p.ks_decomposer.levels, p.k + 1, p.N)
+        samples = rng.integers(0, 1 << 32, size=shape, dtype=np.uint64).astype(np.uint32)
+        samples[:, p.k, :] = self._noise(rng, p.glwe_std_dev, (shape[0], p.N))
+        return self.generate_glwe_switch_key(from_polys, glwe_sk, samples)
+
+    def prepare_glwe_switch_key(self, key) -> "GlweSwitchKey":
+        """key [k*l_ks][k+1][N] (numpy or torch device tensor) -> the prepared handle glwe_automorphism takes.
+        TfheError(TFHE_ERR_EXACTNESS) where the backend cannot pack exactly under the KS decomposer.  Synchronises;
+        prepare once, use often."""
+        p = self.params
+        dev = _is_torch(key)
+        raw = key if dev else _np(key)
+        _check_u32("prepare_glwe_switch_key", "key", raw, dev, (p.k * p.ks_decomposer.levels, p.k + 1, p.N))
+        handle = C.c_void_p()
+        self._call("tfhe_prepare_glwe_switch_key", dev, _ptr(raw), C.byref(handle))
+        prepared = GlweSwitchKey(handle)
+        prepared._ctx = self  # the handle must not outlive its context
+        return prepared
+
+    def glwe_automorphism(self, glwe, t: int, key: "GlweSwitchKey | None" = None, add_input: bool = False, out=None):
+        """Auto_t(glwe; key) (+ glwe with add_input): X -> X^t and the switch back to the context's key in one launch.
+        glwe [batch][k+1][N] (or [k+1][N]: one).  key=None: the bare permutation, the result under sigma_t(S).
+        numpy: host form, blocks.  torch: on torch's current stream, enqueues only, nothing allocated; `out` may name the
+        result tensor and may be `glwe` itself."""
+        p = self.params
+        what = "glwe_automorphism"
+        if key is not None and (not isinstance(key, GlweSwitchKey) or not key._h or not key._h.value):
+            raise _invalid(f"{what}: an open key from prepare_glwe_switch_key expected")
+        if not isinstance(t, (int, np.integer)) or t < 0:
+            raise _invalid(f"{what}: t must be odd and in [1, 2N)")
+        dev = _is_torch(glwe)
+        x = glwe if dev else _np(glwe)
+        single = len(x.shape) == 2
+        if single:
+            x = _lead(x, dev)
+        _check_u32(what, "glwe", x, dev, (None, p.k + 1, p.N))
+        if int(x.shape[0]) == 0:
+            raise _invalid(f"{what}: empty batch")
+        if single and dev and out is not None and len(out.shape) == 2:
+            out = _lead(out, dev)
+        res = _result(what, dev, out, tuple(int(v) for v in x.shape), x)
+        self._call("tfhe_glwe_automorphism_batch", dev, _ptr(x), C.c_size_t(int(x.shape[0])), C.c_size_t(int(t)),
+                   key._h if key is not None else None, C.c_int(1 if add_input else 0), _ptr(res))
+        return res[0] if single else res
+
+    def glwe_key_switch(self, glwe, key: "GlweSwitchKey", out=None):
+        """the plain GLWE key switch (t = 1): glwe under the key's source key S' -> the same messages under the context's"""
+        if key is None:
+            raise _invalid("glwe_key_switch: a key from prepare_glwe_switch_key expected")
+        return self.glwe_automorphism(glwe, 1, key, False, out)
+
+    def generate_trace_keys(self, glwe_sk, steps: int, rng=None):
+        """the prepared automorphism keys of a `steps`-step partial trace: step j = 1..steps uses t_j = N / 2^(j-1) + 1"""
+        p = self.params
+        if not 1 <= steps <= p.glwe_poly_degree:
+            raise _invalid(f"generate_trace_keys: steps must be in [1, {p.glwe_poly_degree}]")
+        keys = []
+        for j in range(1, steps + 1):
+            t = (p.N >> (j - 1)) + 1
+            raw = self.generate_glwe_switch_key_random(self.glwe_sk_automorphism(glwe_sk, t), glwe_sk, rng)
+            keys.append(self.prepare_glwe_switch_key(raw))
+        return keys
+
+    def glwe_partial_trace(self, glwe, steps: int, keys, out=None):
+        """x <- x + Auto_{t_j}(x) for j = 1..steps, t_j = N / 2^(j-1) + 1, keys from generate_trace_keys: a coefficient whose
+        index is a multiple of 2^steps ends up 2^steps TIMES its value, every other coefficient 0.  The factor comes out
+        of the caller's scale.  Device tensors: `steps` launches in place on the result, nothing else on the GPU."""
+        p = self.params
+        if not 1 <= steps <= p.glwe_poly_degree or len(keys) < steps:
+            raise _invalid(f"glwe_partial_trace: steps in [1, {p.glwe_poly_degree}] and as many keys expected")
+        x = self.glwe_automorphism(glwe, p.N + 1, keys[0], True, out)
+        for j in range(2, steps + 1):
+            if _is_torch(x):
+                self.glwe_automorphism(x, (p.N >> (j - 1)) + 1, keys[j - 1], True, x)
+            else:
+                x = self.glwe_automorphism(x, (p.N >> (j - 1)) + 1, keys[j - 1], True)
+        return x
+
     def external_product(self, ggsw, glwe) -> np.ndarray:
         """external_product(): ggsw.rs:132-161.  ggsw [R][k+1][N] (shared) or [batch][R][k+1][N]."""
         p = self.params

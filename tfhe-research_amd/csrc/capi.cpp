@@ -2475,6 +2475,178 @@ int tfhe_pack_lwe_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t groups
   return s.download_and_wait(kOut, glwe_out);
 }
 
+// ---------------------------------------------------------------------------------- GLWE key switch / automorphism
+// tfhe_hip.h states the operation, glwe_switch.h::glwe_switch_team the team's work.  A switch key is ONE packing slice of
+// dimension k, so it is admitted exactly where a packing key is (packing_refusal) and prepared the same way.
+namespace {
+
+int check_switch_key_gen(tfhe_context* ctx, const int32_t* from_polys, const u32* glwe_sk, const u32* key) {
+  TFHE_TRY(check_present(ctx, {from_polys, glwe_sk, key}, 1, "null pointer"));
+  const size_t kn = ctx->big_n;
+  for (size_t i = 0; i < kn; ++i)
+    if (from_polys[i] < -1 || from_polys[i] > 1)
+      return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "from_polys must have coefficients in {-1, 0, 1}");
+  return check_binary(ctx, glwe_sk, kn, "glwe secret key");
+}
+
+int switch_key_refusal(tfhe_context* ctx) {
+  const std::string why = packing_refusal(ctx);
+  if (!why.empty()) return fail(ctx, TFHE_ERR_EXACTNESS, "GLWE switch key refused: " + why);
+  return TFHE_OK;
+}
+
+// d_raw: [k l_ks][k+1][N] on the device
+int prepare_switch_key_common(tfhe_context* ctx, const u32* d_raw, tfhe_glwe_switch_key** out) {
+  const u32 k = ctx->params.glwe_dimension, k1 = k + 1;
+  const size_t poly_bytes = (size_t)ctx->parts * ctx->N * sizeof(u64);  // one prepared key polynomial
+  const size_t polys = (size_t)k * ctx->ks.levels * k1;
+  const size_t bytes = (size_t)k1 * ctx->ks.levels * k1 * poly_bytes;
+  tfhe_glwe_switch_key* h = new (std::nothrow) tfhe_glwe_switch_key();
+  if (!h) return fail(ctx, TFHE_ERR_HIP, "out of host memory");
+  h->owner = ctx;
+  h->device = ctx->device;
+  h->field = ctx->field;
+  h->log_n = ctx->pbs.log_n;
+  h->k = k;
+  h->levels = ctx->ks.levels;
+  int st = h->d_key.grow(ctx, bytes);
+  if (st == TFHE_OK) {
+    // polynomial k of the slice reads zeros against zero key rows: the packing slice's own padding
+    hipError_t e = hipMemsetAsync(h->d_key.as<unsigned char>() + polys * poly_bytes, 0, bytes - polys * poly_bytes, ctx->stream);
+    if (e == hipSuccess)
+      e = launch::bsk_prepare(ctx->stream, ctx->field, ctx->pbs.log_n, ctx->pbs.k, ctx->d_tw.as(), d_raw, polys, h->d_key.as());
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the caller's raw key is free again on return
+    if (e != hipSuccess) st = hip_fail(ctx, e, "tfhe_prepare_glwe_switch_key");
+  }
+  if (st != TFHE_OK) {
+    tfhe_glwe_switch_key_destroy(h);
+    return st;
+  }
+  *out = h;
+  return TFHE_OK;
+}
+
+// t odd in [1, 2N) -> t^-1 mod 2N (Newton's iteration on the 2-adic inverse: five steps give 32 bits)
+int automorphism_inverse(tfhe_context* ctx, size_t t, u32* t_inv) {
+  if (!(t & 1u) || t >= 2 * (size_t)ctx->N)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "t must be odd and below 2N: X -> X^t is a ring automorphism only then");
+  u32 u = (u32)t;
+  for (int i = 0; i < 5; ++i) u *= 2u - (u32)t * u;
+  *t_inv = u & (2u * ctx->N - 1u);
+  return TFHE_OK;
+}
+
+int check_automorphism_args(tfhe_context* ctx, const u32* in, size_t batch, size_t t, const tfhe_glwe_switch_key* key,
+                            const u32* out, u32* t_inv) {
+  TFHE_TRY(check_present(ctx, {in, out}, 1, "null pointer"));
+  if (batch == 0 || batch > kMaxBatch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "batch must be in [1, 2^31)");
+  TFHE_TRY(automorphism_inverse(ctx, t, t_inv));
+  if (key && (key->owner != ctx || key->device != ctx->device || key->field != ctx->field || key->log_n != ctx->pbs.log_n ||
+              key->k != ctx->params.glwe_dimension || key->levels != ctx->ks.levels || !key->d_key))
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "the switch key was prepared by another context or backend");
+  const size_t words = batch * glwe_words(ctx);
+  if (in != out && overlap(in, words, out, words))
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "glwe_out overlaps glwe_in without being it: in place means the same pointer");
+  return TFHE_OK;
+}
+
+}  // namespace
+
+int tfhe_glwe_sk_automorphism(const uint32_t* glwe_sk, size_t k, unsigned log_n, size_t t, int32_t* out) {
+  if (!glwe_sk || !out || k == 0 || log_n == 0 || log_n > 30) return TFHE_ERR_INVALID_ARGUMENT;
+  const size_t N = (size_t)1 << log_n;
+  if (!(t & 1u) || t >= 2 * N) return TFHE_ERR_INVALID_ARGUMENT;
+  for (size_t i = 0; i < k * N; ++i)
+    if (glwe_sk[i] > 1u) return TFHE_ERR_INVALID_ARGUMENT;
+  for (size_t p = 0; p < k; ++p)
+    for (size_t j = 0; j < N; ++j) {  // coefficient j lands on j t mod N, negated when j t mod 2N >= N
+      const size_t at = (j * t) & (2 * N - 1);
+      const int32_t s = (int32_t)glwe_sk[p * N + j];
+      out[p * N + (at & (N - 1))] = at >= N ? -s : s;
+    }
+  return TFHE_OK;
+}
+
+int tfhe_generate_glwe_switch_key_device(tfhe_context* ctx, const int32_t* from_polys, const uint32_t* glwe_sk, uint32_t* key) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_switch_key_gen(ctx, from_polys, glwe_sk, key));
+  const size_t kn = ctx->big_n;
+  const size_t rows = (size_t)ctx->params.glwe_dimension * ctx->ks.levels;
+  // row i*levels + level is a zero encryption plus from_polys[i] g_level on the body
+  TFHE_TRY(ensure_key_tmp(ctx, 2 * kn));
+  TFHE_TRY(to_key_tmp(ctx, glwe_sk, kn, 0));
+  TFHE_TRY(to_key_tmp(ctx, reinterpret_cast<const u32*>(from_polys), kn, kn));
+  TFHE_TRY(glwe_rows_add_mask_dot_key(ctx, key, rows));
+  HIP_TRY(ctx, launch::glwe_switch_add_gadget(ctx->stream, key, ctx->params.glwe_dimension, ctx->pbs.log_n, ctx->ks.levels,
+                                              ctx->ks.log_base, gadget_top(ctx, ctx->ks.log_base),
+                                              reinterpret_cast<const i32*>(ctx->d_key_tmp.as<u32>() + kn)));
+  // the host arrays are pageable memory: the async copies have staged them before returning
+  return TFHE_OK;
+}
+
+int tfhe_generate_glwe_switch_key(tfhe_context* ctx, const int32_t* from_polys, const uint32_t* glwe_sk, uint32_t* key) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_switch_key_gen(ctx, from_polys, glwe_sk, key));
+  return in_place_host_form(ctx, key, glwe_switch_key_words(ctx), [&](u32* d) {
+    return tfhe_generate_glwe_switch_key_device(ctx, from_polys, glwe_sk, d);
+  });
+}
+
+int tfhe_prepare_glwe_switch_key_device(tfhe_context* ctx, const uint32_t* key, tfhe_glwe_switch_key** out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {key, out}, 1, "null pointer"));
+  *out = nullptr;
+  TFHE_TRY(switch_key_refusal(ctx));
+  return prepare_switch_key_common(ctx, key, out);
+}
+
+int tfhe_prepare_glwe_switch_key(tfhe_context* ctx, const uint32_t* key, tfhe_glwe_switch_key** out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {key, out}, 1, "null pointer"));
+  *out = nullptr;
+  TFHE_TRY(switch_key_refusal(ctx));  // before the upload
+  const size_t words = glwe_switch_key_words(ctx);
+  DeviceBuffer raw;
+  TFHE_TRY(raw.grow(ctx, words * sizeof(u32)));
+  HIP_TRY(ctx, hipMemcpy(raw.as(), key, words * sizeof(u32), hipMemcpyHostToDevice));
+  return prepare_switch_key_common(ctx, raw.as<u32>(), out);
+}
+
+void tfhe_glwe_switch_key_destroy(tfhe_glwe_switch_key* key) {
+  if (!key) return;
+  (void)hipSetDevice(key->device);  // before `delete` releases the spectra
+  delete key;
+}
+
+int tfhe_glwe_automorphism_batch_device(tfhe_context* ctx, const uint32_t* glwe_in, size_t batch, size_t t,
+                                        const tfhe_glwe_switch_key* key, int add_input, uint32_t* glwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  u32 t_inv = 0;
+  TFHE_TRY(check_automorphism_args(ctx, glwe_in, batch, t, key, glwe_out, &t_inv));
+  if (!key) {
+    if (add_input)
+      return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "add_input needs a key: without one the result is under another key than the input");
+    HIP_TRY(ctx, launch::glwe_automorphism(ctx->stream, glwe_in, batch * (ctx->params.glwe_dimension + 1), ctx->pbs.log_n, t_inv, glwe_out));
+    return TFHE_OK;
+  }
+  HIP_TRY(ctx, launch::glwe_switch(ctx->stream, ctx->field, packing_params(ctx), ctx->d_tw.as(), key->d_key.as(), glwe_in, batch,
+                                   t_inv, add_input != 0, glwe_out));
+  return TFHE_OK;
+}
+
+int tfhe_glwe_automorphism_batch(tfhe_context* ctx, const uint32_t* glwe_in, size_t batch, size_t t,
+                                 const tfhe_glwe_switch_key* key, int add_input, uint32_t* glwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  u32 t_inv = 0;
+  TFHE_TRY(check_automorphism_args(ctx, glwe_in, batch, t, key, glwe_out, &t_inv));
+  const size_t words = batch * glwe_words(ctx);
+  Staging s(ctx, {words});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(0, glwe_in));
+  TFHE_TRY(tfhe_glwe_automorphism_batch_device(ctx, s[0], batch, t, key, add_input, s[0]));  // in place
+  return s.download_and_wait(0, glwe_out);
+}
+
 // ---------------------------------------------------------------------------------- multi-value bootstrap
 // tfhe_hip.h states the operation, multi_value.h::sparse_extract_tile the per-table step.  ONE rotation of the constant
 // accumulator per input, then one launch that turns the lookup tables into coefficient rows and one that combines the

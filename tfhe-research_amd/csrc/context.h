@@ -186,6 +186,16 @@ struct tfhe_poly_weights {
   unsigned rows_per_pass = 0;  // channels the backend's exactness rule admits in one pass at that magnitude
 };
 
+// A prepared GLWE switch key (tfhe_prepare_glwe_switch_key): one packing slice of dimension k -- (k+1) l_ks key rows, the
+// last l_ks zero spectra -- on the device of the context that prepared it, for that context's backend, ring and KS levels.
+struct tfhe_glwe_switch_key {
+  const tfhe_context* owner = nullptr;  // compared, never dereferenced
+  int device = 0;
+  int field = 0;
+  u32 log_n = 0, k = 0, levels = 0;
+  DeviceBuffer d_key;  // [(k+1) l_ks][k+1][parts][N] 8-byte words (spectrum_slot order, x 1/N)
+};
+
 namespace tfhe {
 namespace host {
 
@@ -220,6 +230,10 @@ inline size_t ksk_matrix_bytes(const tfhe_context* ctx) {
 // the raw packing key from an LWE key of `from_dimension` bits: one GLWE row per (key bit, KS level)
 inline size_t packing_key_words(const tfhe_context* ctx, size_t from_dimension) {
   return from_dimension * ctx->ks.levels * glwe_words(ctx);
+}
+// the raw GLWE switch key: one GLWE row per (polynomial of the source key, KS level)
+inline size_t glwe_switch_key_words(const tfhe_context* ctx) {
+  return (size_t)ctx->params.glwe_dimension * ctx->ks.levels * glwe_words(ctx);
 }
 inline size_t prepared_bsk_bytes(const tfhe_context* ctx, size_t ggsws) {
   return ggsws * prepared_ggsw_words(ctx) * sizeof(u64);

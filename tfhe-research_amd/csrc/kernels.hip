@@ -10,6 +10,7 @@
 #include <cstdlib>
 
 #include "glwe_conv.h"
+#include "glwe_switch.h"
 #include "launch.h"
 #include "lwe_dense.h"
 #include "lwe_extract.h"
@@ -752,6 +753,45 @@ cmux_program_kernel(PbsParams P, const typename F::elem* __restrict__ tw, CmuxPr
 __global__ void packing_add_gadget_kernel(u32* pksk, size_t rows, u32 k, u32 log_n, const u32* __restrict__ factor) {
   for (size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x; row < rows; row += (size_t)gridDim.x * blockDim.x)
     pksk[(row * (k + 1) + k) << log_n] += factor[row];
+}
+
+// ------------------------------------------------------------------------------ GLWE key switch / automorphism
+// glwe_switch.h::glwe_switch_team states the operation.  One team per ciphertext, one launch per call: no workspace, no
+// memset, nothing but the team's own ciphertext is touched (glwe_out may be glwe_in).  The team's LDS and registers are
+// pack_lwe_kernel's.
+template <class F, int LOGN, int K>
+__global__ void __launch_bounds__((TeamCfg<F, LOGN, K, 1>::kThreads), (TeamCfg<F, LOGN, K, 1>::kMinWaves))
+glwe_switch_kernel(PbsParams P /* the KS decomposer */, const typename F::elem* __restrict__ tw,
+                   const typename F::elem* __restrict__ key, const u32* glwe_in, u32 t_inv, u32 add_input, u32* glwe_out) {
+  using C = TeamCfg<F, LOGN, K, 1>;
+  auto w = make_wave<F, LOGN, K, 1>(g_smem, tw);
+  const size_t at = (size_t)blockIdx.x * (K + 1) * C::N;
+  glwe_switch_team<F, LOGN, K, C::G>(w, P, glwe_in + at, t_inv, add_input, key, glwe_out + at);
+}
+
+// glwe_switch.h::automorphism_poly: the bare permutation, one workgroup per polynomial (grid-strided)
+struct AutomorphismWorkgroup {
+  __device__ u32 thread() const { return threadIdx.x; }
+  __device__ u32 threads() const { return blockDim.x; }
+  __device__ void barrier() const { __syncthreads(); }
+  __device__ u32* lds() const { return reinterpret_cast<u32*>(g_smem); }
+};
+__global__ void __launch_bounds__(256) glwe_automorphism_kernel(const u32* in, size_t polys, u32 log_n, u32 t_inv, u32* out) {
+  for (size_t p = blockIdx.x; p < polys; p += gridDim.x)
+    automorphism_poly(AutomorphismWorkgroup(), in + (p << log_n), log_n, t_inv, out + (p << log_n));
+}
+
+// key [k l_ks][k+1][N]: the body of row i l_ks + l += from_polys[i] (coefficients in {-1, 0, 1}) times the gadget factor
+// g_l = 2^(top - log_base (l + 1)); a -1 adds 0 - g_l
+__global__ void __launch_bounds__(256) glwe_switch_add_gadget_kernel(u32* key, u32 k, u32 log_n, u32 levels, u32 log_base, u32 top,
+                                                                     const i32* __restrict__ from_polys) {
+  const size_t total = ((size_t)k * levels) << log_n;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t row = i >> log_n;
+    const u32 j = (u32)(i & ((1u << log_n) - 1u));
+    const u32 g = 1u << (top - log_base * ((u32)(row % levels) + 1u));
+    key[((row * (k + 1) + k) << log_n) + j] += (u32)from_polys[((row / levels) << log_n) + j] * g;
+  }
 }
 
 // ------------------------------------------------------------------------------ key switch
@@ -1753,6 +1793,25 @@ hipError_t launch_pack_lwe(hipStream_t s, const PbsParams& P, const void* tw_v, 
   }
 }
 
+template <class F, int LOGN, int K>
+hipError_t launch_glwe_switch(hipStream_t s, const PbsParams& P, const void* tw_v, const void* key_v, const u32* glwe_in,
+                              size_t batch, u32 t_inv, bool add_input, u32* glwe_out) {
+  if constexpr (!field_shape_ok<F, LOGN>()) {
+    return hipErrorInvalidValue;
+  } else {
+    using C = TeamCfg<F, LOGN, K, 1>;
+    auto tw = static_cast<const typename F::elem*>(tw_v);
+    auto key = static_cast<const typename F::elem*>(key_v);
+    auto kern = glwe_switch_kernel<F, LOGN, K>;
+    static std::atomic<unsigned long long> lds_done{0};
+    hipError_t e = allow_lds(kern, C::kLds, lds_done);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(C::kThreads), C::kLds, s, P, tw, key, glwe_in, t_inv,
+                       add_input ? 1u : 0u, glwe_out);
+    return hipGetLastError();
+  }
+}
+
 // The three pass kernels -- cmux_tree_kernel, demux_tree_kernel, cmux_program_kernel -- share a team (TeamCfg<.., 1>)
 // and a signature (P, the twiddles, the pass struct by value): one trait, the kernel named by its pass struct.  Which
 // passes go out, with how many teams and over which workspace, is host arithmetic (passes.h; capi.cpp sequences them).
@@ -2056,6 +2115,28 @@ hipError_t pack_lwe(hipStream_t s, int field, const PbsParams& P, const void* tw
 
 hipError_t packing_add_gadget(hipStream_t s, u32* pksk, size_t rows, u32 k, u32 log_n, const u32* factor) {
   hipLaunchKernelGGL(packing_add_gadget_kernel, dim3(grid_for(rows, 256)), dim3(256), 0, s, pksk, rows, k, log_n, factor);
+  return hipGetLastError();
+}
+
+hipError_t glwe_switch(hipStream_t s, int field, const PbsParams& P, const void* tw, const void* key, const u32* glwe_in,
+                       size_t batch, u32 t_inv, bool add_input, u32* glwe_out) {
+  if (batch == 0 || batch > 0x7FFFFFFFull || !(t_inv & 1u) || t_inv >= (2u << P.log_n)) return hipErrorInvalidValue;
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (launch_glwe_switch<FF, LL, KK>(s, P, tw, key, glwe_in, batch, t_inv,
+                                                                                              add_input, glwe_out))));
+}
+
+hipError_t glwe_automorphism(hipStream_t s, const u32* glwe_in, size_t polys, u32 log_n, u32 t_inv, u32* glwe_out) {
+  if (polys == 0 || log_n > 14 || !(t_inv & 1u) || t_inv >= (2u << log_n)) return hipErrorInvalidValue;  // N words of LDS
+  const unsigned grid = (unsigned)(polys < ((size_t)1 << 20) ? polys : (size_t)1 << 20);
+  hipLaunchKernelGGL(glwe_automorphism_kernel, dim3(grid), dim3(256), sizeof(u32) << log_n, s, glwe_in, polys, log_n, t_inv, glwe_out);
+  return hipGetLastError();
+}
+
+hipError_t glwe_switch_add_gadget(hipStream_t s, u32* key, u32 k, u32 log_n, u32 levels, u32 log_base, u32 top,
+                                  const i32* from_polys) {
+  const size_t total = ((size_t)k * levels) << log_n;
+  hipLaunchKernelGGL(glwe_switch_add_gadget_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, key, k, log_n, levels, log_base, top,
+                     from_polys);
   return hipGetLastError();
 }
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "glwe_conv.h"
+#include "glwe_switch.h"
 #include "ks_matrix.h"
 #include "lwe_extract.h"
 #include "multi_value.h"
@@ -116,6 +117,19 @@ hipError_t pack_lwe(hipStream_t s, int field, const PbsParams& P, const void* tw
                     size_t groups, u32* glwe_out);
 // pksk [rows][k+1][N]: body coefficient 0 of row r += factor[r]
 hipError_t packing_add_gadget(hipStream_t s, u32* pksk, size_t rows, u32 k, u32 log_n, const u32* factor);
+
+// ---- GLWE key switch / automorphism (glwe_switch.h::glwe_switch_team): glwe_out [batch][k+1][N] = Auto_t(glwe_in[b]; key)
+// (+ glwe_in[b] with add_input), one launch of `batch` teams; t_inv = t^-1 mod 2N.  P as for pack_lwe; key: the switch
+// key [k l_ks][k+1][N] prepared by bsk_prepare(.., k, ..) followed by l_ks (k+1) zero spectra (one packing slice of
+// dimension k).  glwe_out may be glwe_in.  hipErrorInvalidValue: an empty batch, one of 2^31 or more, an even t_inv
+hipError_t glwe_switch(hipStream_t s, int field, const PbsParams& P, const void* tw, const void* key, const u32* glwe_in,
+                       size_t batch, u32 t_inv, bool add_input, u32* glwe_out);
+// the bare permutation of `polys` polynomials [N] (glwe_switch.h::automorphism_poly); glwe_out may be glwe_in
+hipError_t glwe_automorphism(hipStream_t s, const u32* glwe_in, size_t polys, u32 log_n, u32 t_inv, u32* glwe_out);
+// key [k levels][k+1][N]: the body of row i levels + l += from_polys[i] (device, [k][N], entries in {-1, 0, 1}) times
+// 2^(top - log_base (l + 1))
+hipError_t glwe_switch_add_gadget(hipStream_t s, u32* key, u32 k, u32 log_n, u32 levels, u32 log_base, u32 top,
+                                  const i32* from_polys);
 
 // ---- tree LUT (capi.cpp::tfhe_tree_lut_batch_device): the per-rotation inputs of a level, in the reserved workspace
 // out [count][words], out[r] = in[r / per_row]: rotation r's copy of its row's digit
