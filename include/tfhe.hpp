@@ -874,6 +874,56 @@ inline GlweCiphertext glwe_automorphism(Engine& e, const GlweCiphertext& ct, siz
 inline GlweCiphertext glwe_key_switch(Engine& e, const GlweCiphertext& ct, const GlweSwitchKey& key) {
   return glwe_automorphism(e, ct, 1, key);
 }
+// ---- multi-bit blind rotation (tfhe_hip.h states the operation; first device only) ----
+// A prepared multi-bit bootstrapping key for g in {2, 3, 4} key bits per step: from samples pre-filled like a GGSW batch
+// (uniform masks, errors in the body) and completed here for lwe_sk [n] and glwe_sk [k][N]; or an already generated key.
+// TFHE_ERR_UNSUPPORTED with the reason where the wide team is not offered.  Move-only; released with the object, before
+// its engine.
+class MultibitKey {
+ public:
+  MultibitKey(Engine& e, const std::vector<uint32_t>& lwe_sk, const std::vector<uint32_t>& glwe_sk, unsigned g, std::vector<uint32_t> samples) {
+    const TfheParams& p = e.params();
+    if (lwe_sk.size() != p.lwe_dimension || glwe_sk.size() != size_t(p.glwe_dimension) * p.degree())
+      throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "lwe_sk [n] and glwe_sk [k][N]");
+    check_words(e, g, samples);
+    e.check(tfhe_generate_multibit_key(e.raw(), lwe_sk.data(), glwe_sk.data(), g, samples.data()));
+    e.check(tfhe_prepare_multibit_key(e.raw(), samples.data(), g, &key_));
+  }
+  MultibitKey(Engine& e, const std::vector<uint32_t>& key, unsigned g) {
+    check_words(e, g, key);
+    e.check(tfhe_prepare_multibit_key(e.raw(), key.data(), g, &key_));
+  }
+  MultibitKey(const MultibitKey&) = delete;
+  MultibitKey& operator=(const MultibitKey&) = delete;
+  MultibitKey(MultibitKey&& o) noexcept : key_(o.key_) { o.key_ = nullptr; }
+  ~MultibitKey() { tfhe_multibit_key_destroy(key_); }
+  const tfhe_multibit_key* raw() const { return key_; }
+
+ private:
+  static void check_words(Engine& e, unsigned g, const std::vector<uint32_t>& key) {
+    const TfheParams& p = e.params();
+    if (g < 2 || g > 4) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "g must be 2, 3 or 4");
+    const size_t groups = (size_t(p.lwe_dimension) + g - 1) / g, k1 = size_t(p.glwe_dimension) + 1;
+    if (key.size() != groups * ((size_t(1) << g) - 1) * k1 * p.pbs_decomposer.levels * k1 * p.degree())
+      throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "multi-bit key [ceil(n/g)][2^g - 1][(k+1) l][k+1][N]");
+  }
+  tfhe_multibit_key* key_ = nullptr;
+};
+// the multi-bit bootstrap of ONE ciphertext at the engine's boundary dimension against a clear test vector [N]
+inline LweCiphertext multibit_bootstrap(Engine& e, const MultibitKey& key, const LweCiphertext& ct, const std::vector<uint32_t>& test_vector) {
+  if (test_vector.size() != e.params().degree()) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "test vector [N]");
+  LweCiphertext out{std::vector<uint32_t>(ct.data.size())};
+  e.check(tfhe_multibit_bootstrap_batch(e.raw(), key.raw(), ct.data.data(), 1, test_vector.data(), 1, out.data.data()));
+  return out;
+}
+// the multi-bit blind rotation of ONE ciphertext of n + 1 words from a clear test vector [N] -> the GLWE accumulator
+inline GlweCiphertext multibit_blind_rotate(Engine& e, const MultibitKey& key, const LweCiphertext& ct, const std::vector<uint32_t>& test_vector) {
+  const TfheParams& p = e.params();
+  if (ct.data.size() != size_t(p.lwe_dimension) + 1 || test_vector.size() != p.degree()) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "LWE length / test vector [N]");
+  GlweCiphertext out{std::vector<uint32_t>(size_t(p.glwe_dimension + 1) * p.degree())};
+  e.check(tfhe_multibit_blind_rotate_batch(e.raw(), key.raw(), ct.data.data(), 1, test_vector.data(), 1, nullptr, 0, out.data.data(), nullptr));
+  return out;
+}
 // ---- multi-value bootstrapping (tfhe_hip.h states the operations; first device only) ----
 // every lookup table of `luts` (tables x B un-encoded values, row-major) of ONE ciphertext of n + 1 words from one blind
 // rotation (the reference's bootstrap order, like the neighbouring wrappers) -> one ciphertext per table

@@ -314,6 +314,93 @@ int tfhe_glwe_automorphism_batch(tfhe_context *ctx, const uint32_t *glwe_in, siz
 int tfhe_glwe_automorphism_batch_device(tfhe_context *ctx, const uint32_t *glwe_in, size_t batch, size_t t,
                                         const tfhe_glwe_switch_key *key, int add_input, uint32_t *glwe_out);
 
+/* ---- multi-bit blind rotation (no reference counterpart): g key bits per external product, for small batches -------
+ * The multi-bit blind rotation of Joye and Paillier (2022).  A blind rotation's latency is the number of SEQUENTIAL
+ * external products times the latency of one; this variant runs ceil(n / g) of them instead of n, and what it adds --
+ * forming one GGSW per (sample, group of g key bits), the BUNDLE -- is independent work for the CUs a small batch leaves
+ * idle.  Opt-in: a separate key handle and separate entry points; the context's loaded key and every other entry point
+ * are untouched.  All arithmetic is mod 2^32.
+ *
+ * Groups and patterns.  g in {2, 3, 4}; G = ceil(n / g) groups; group i covers key bits g*i .. min(n, g*i + g) - 1, g_i of
+ * them (the last group may be ragged).  A pattern is an integer p in [1, 2^g_i): bit j of p stands for key bit g*i + j.
+ *
+ * Key.  bsk_mb [G][2^g - 1][(k+1)*l][k+1][N]: slot (i, p - 1) is a GGSW in the reference's layout (ggsw.rs:37-41) that
+ * encrypts  prod_{j in p} s_{g*i+j} * prod_{j not in p, j < g_i} (1 - s_{g*i+j})  in {0, 1}: "the group's bits are exactly
+ * p".  Slots of a ragged group with p >= 2^g_i are never read (tfhe_generate_multibit_key encrypts 0 there).  The pattern
+ * "no bit set" needs no GGSW: the indicators of a group sum to 1, which is why the step below is acc + ...
+ *
+ * Rotation.  a~_m = switch_modulus_2n(a_m) and b~ are the bootstrap's own; e_{i,p} = sum_{j in p} a~_{g*i+j} mod 2N.
+ * acc_0 is the bootstrap's, X^(-b~) * (0, .., 0, tv << tv_shift), or the rotated GLWE accumulator of
+ * tfhe_blind_rotate_glwe_batch (acc_in, rotation_offset).  For i = 0 .. G - 1:
+ *   Bundle_i[r][c][.] = sum_p ( X^(e_{i,p}) * K_{i,p}[r][c] - K_{i,p}[r][c] )    wordwise wrapping u32, the negacyclic shift
+ *                       of utils.rs:183-207, over all (k+1)*l rows and k+1 columns
+ *   acc <- acc + external_product(Bundle_i, acc)                                  ggsw.rs:132-161 with the PBS decomposer,
+ *                                                                                 literal or aligned as the context is set
+ * Output: the GLWE accumulator and / or sample_extract(., 0).  The bundle is formed on the RAW key words before it is
+ * transformed, so it is an ordinary GGSW of arbitrary words: the context's exactness rule covers it as it covers any
+ * bootstrapping key, and the result is byte for byte "bundle, tfhe_external_product_batch, wrapping add" repeated G times.
+ * The bootstrap form adds the context's key switch after the rotation or before it, as tfhe_context_set_bootstrap_order
+ * says: byte for byte tfhe_key_switch_batch_device composed with the rotation.
+ *
+ * This is NOT the reference's bootstrap(): the plaintext is the same, the key material and the ciphertext bits differ
+ * (as with a BMMP key).
+ *
+ * Identity.  Under noise-free GGSWs and with no ignored bits, phi_S(acc_final) = X^(rho - b~) * phi_S(acc_0) exactly,
+ * rho = sum_m a~_m s_m.  With the aligned decomposer and ig ignored bits a step rounds every word of acc by at most
+ * 2^(ig-1), the phase of the rounded accumulator moves by at most (1 + k*N) 2^(ig-1), and the step's message X^rho_i - 1
+ * is two monomials: within G * 2 * (1 + k*N) * 2^(ig-1) per coefficient after the G steps.
+ *
+ * Noise (derived, then compared with measurements: DESIGN.md).  A bundle row's error is sum_p (X^e - 1) e_p, variance
+ * 2 (2^g_i - 1) sigma^2, and its message X^(sum a~ s) - 1 is two monomials, so the decomposer's rounding counts twice.
+ * Per group, in units of the 32-bit torus:
+ *   2 (2^g_i - 1) (k+1) l N (B^2/12 + 1/6) (sigma_glwe 2^32)^2  +  2 (1 + k N / 2) 2^(2 ig_pbs) / 12
+ * and s_mb^2 is the sum over the groups; the modulus-switch and key-switch terms are the bootstrap's.  Against the
+ * ordinary rotation's s_br^2 that is about 2 (2^g - 1) / g: 3x, 4.7x, 7.5x the variance for g = 2, 3, 4 -- the price of
+ * the shorter chain and the reason it is opt-in.
+ *
+ * Offered where the launcher offers the wide team: the fp64-fft backend, N <= 1024, (k+1) l row buffers within a CU's LDS;
+ * elsewhere tfhe_prepare_multibit_key* and tfhe_context_reserve_multibit return TFHE_ERR_UNSUPPORTED with the reason in
+ * tfhe_last_error.  g outside {2, 3, 4}, a NULL pointer, an empty batch, one beyond 65535 or beyond the reservation:
+ * TFHE_ERR_INVALID_ARGUMENT.
+ *
+ * tfhe_generate_multibit_key completes a buffer pre-filled like tfhe_ggsw_encrypt_batch's (every GLWE row: masks uniform,
+ * body = error); its words equal tfhe_ggsw_encrypt_batch with the indicator products as messages.  lwe_sk [n] and glwe_sk
+ * [k][N] are host arrays and must be binary; the _device form takes bsk_mb on the device.  tfhe_prepare_multibit_key makes
+ * an opaque handle that owns the raw key on the device (this one call synchronises).  The handle belongs to the context
+ * that made it -- another context's is TFHE_ERR_INVALID_ARGUMENT --, is independent of the loaded bootstrapping key, and is
+ * destroyed by the caller (NULL is allowed) before its context.  Any number may live at once, with different g.
+ *
+ * tfhe_context_reserve_multibit reserves the bundle workspace, max_batch * G * prepared-GGSW bytes (41 MB per sample at
+ * k = 1, N = 1024, n = 630, l = 3, g = 3), and the LWE workspace of tfhe_context_reserve.  The host forms reserve what they
+ * need; a _device call beyond the reservation is refused and names its need in bytes.  After it the _device forms allocate
+ * nothing, stay on the context's stream and can be captured: two launches per rotation (bundles: one workgroup per four
+ * bundle polynomials and sample; rotation: one wide team per sample), plus the key switch in the bootstrap form.
+ *
+ * lwe_in [batch][n+1] (the bootstrap form: the context's boundary dimension).  Pass EITHER test_vector_poly [tv_count][N]
+ * (clear, tv_count 1 or batch) OR acc_in [tv_count][k+1][N] with rotation_offset < 2N; the other is NULL.  Pass glwe_out
+ * [batch][k+1][N], lwe_extracted [batch][k*N+1] or both.  The bootstrap form is TFHE_ERR_NO_KEY while the context holds
+ * no key-switching key.  With tfhe_context_set_timing, tfhe_multibit_last_kernel_ms reports the two launches of the last
+ * tfhe_multibit_blind_rotate_batch[_device] separately. */
+typedef struct tfhe_multibit_key tfhe_multibit_key;
+int tfhe_generate_multibit_key(tfhe_context *ctx, const uint32_t *lwe_sk, const uint32_t *glwe_sk, unsigned g, uint32_t *bsk_mb);
+int tfhe_generate_multibit_key_device(tfhe_context *ctx, const uint32_t *lwe_sk, const uint32_t *glwe_sk, unsigned g,
+                                      uint32_t *bsk_mb);
+int tfhe_prepare_multibit_key(tfhe_context *ctx, const uint32_t *bsk_mb, unsigned g, tfhe_multibit_key **out);
+int tfhe_prepare_multibit_key_device(tfhe_context *ctx, const uint32_t *bsk_mb, unsigned g, tfhe_multibit_key **out);
+void tfhe_multibit_key_destroy(tfhe_multibit_key *key);
+int tfhe_context_reserve_multibit(tfhe_context *ctx, size_t max_batch, unsigned g);
+int tfhe_multibit_blind_rotate_batch(tfhe_context *ctx, const tfhe_multibit_key *key, const uint32_t *lwe_in, size_t batch,
+                                     const uint32_t *test_vector_poly, size_t tv_count, const uint32_t *acc_in,
+                                     size_t rotation_offset, uint32_t *glwe_out, uint32_t *lwe_extracted);
+int tfhe_multibit_blind_rotate_batch_device(tfhe_context *ctx, const tfhe_multibit_key *key, const uint32_t *lwe_in, size_t batch,
+                                            const uint32_t *test_vector_poly, size_t tv_count, const uint32_t *acc_in,
+                                            size_t rotation_offset, uint32_t *glwe_out, uint32_t *lwe_extracted);
+int tfhe_multibit_bootstrap_batch(tfhe_context *ctx, const tfhe_multibit_key *key, const uint32_t *lwe_in, size_t batch,
+                                  const uint32_t *test_vector_poly, size_t tv_count, uint32_t *lwe_out);
+int tfhe_multibit_bootstrap_batch_device(tfhe_context *ctx, const tfhe_multibit_key *key, const uint32_t *lwe_in, size_t batch,
+                                         const uint32_t *test_vector_poly, size_t tv_count, uint32_t *lwe_out);
+int tfhe_multibit_last_kernel_ms(tfhe_context *ctx, float *bundle_ms, float *rotate_ms);
+
 /* ---- tree LUT: a function of d digits of log_p bits each (no reference counterpart) ---------------------------------
  * The tree-based bootstrap of Guimaraes, Borin and Aranha (2021).  Inputs and output are ordinary LWE ciphertexts at
  * the bootstrap boundary, so it composes with gates, gate graphs and itself; its noise does not depend on the table

@@ -28,6 +28,7 @@ pub struct CTfheParams {
 #[repr(C)] pub struct TfheContext { _private: [u8; 0] }
 #[repr(C)] pub struct TfhePolyWeights { _private: [u8; 0] }
 #[repr(C)] pub struct TfheGlweSwitchKey { _private: [u8; 0] }
+#[repr(C)] pub struct TfheMultibitKey { _private: [u8; 0] }
 #[repr(C)] pub struct TfhePool { _private: [u8; 0] }
 
 extern "C" {
@@ -113,6 +114,11 @@ extern "C" {
     fn tfhe_generate_glwe_switch_key(ctx: *mut TfheContext, from_polys: *const i32, glwe_sk: *const u32, key: *mut u32) -> c_int;
     fn tfhe_prepare_glwe_switch_key(ctx: *mut TfheContext, key: *const u32, out: *mut *mut TfheGlweSwitchKey) -> c_int;
     fn tfhe_glwe_switch_key_destroy(key: *mut TfheGlweSwitchKey);
+    fn tfhe_generate_multibit_key(ctx: *mut TfheContext, lwe_sk: *const u32, glwe_sk: *const u32, g: c_uint, bsk_mb: *mut u32) -> c_int;
+    fn tfhe_prepare_multibit_key(ctx: *mut TfheContext, bsk_mb: *const u32, g: c_uint, out: *mut *mut TfheMultibitKey) -> c_int;
+    fn tfhe_multibit_key_destroy(key: *mut TfheMultibitKey);
+    fn tfhe_multibit_bootstrap_batch(ctx: *mut TfheContext, key: *const TfheMultibitKey, lwe_in: *const u32, batch: usize,
+                                     test_vector_poly: *const u32, tv_count: usize, lwe_out: *mut u32) -> c_int;
     fn tfhe_glwe_automorphism_batch(ctx: *mut TfheContext, glwe_in: *const u32, batch: usize, t: usize,
                                     key: *const TfheGlweSwitchKey, add_input: c_int, glwe_out: *mut u32) -> c_int;
     fn tfhe_cmux_batch(ctx: *mut TfheContext, ggsw: *const u32, ggsw_count: usize, ct0: *const u32,
@@ -665,6 +671,50 @@ pub fn glwe_automorphism(bk: &GpuBootstrappingKey, glwe: &Array3<u32>, t: usize,
 /// the plain GLWE key switch (t = 1): from the key's source key to the context's
 pub fn glwe_key_switch(bk: &GpuBootstrappingKey, glwe: &Array3<u32>, key: &GlweSwitchKey) -> Array3<u32> {
     glwe_automorphism(bk, glwe, 1, key, false)
+}
+
+/// A prepared multi-bit bootstrapping key (no reference counterpart), g in {2, 3, 4} key bits per step: `samples`
+/// [ceil(n/g) * (2^g - 1) * (k+1) l][k+1][N], pre-filled like a batch of GGSWs (uniform masks, errors in the body), are
+/// completed for `lwe_sk` (n) and `glwe_sk` (k, N), then handed to the device; panics with the reason where the wide team
+/// is not offered.  Released on drop, before the key it was made with.
+pub struct MultibitKey { raw: *mut TfheMultibitKey }
+
+impl MultibitKey {
+    pub fn new(bk: &GpuBootstrappingKey, lwe_sk: &Array1<u32>, glwe_sk: &Array2<u32>, g: u32, samples: &Array3<u32>) -> Self {
+        let (k, n) = (bk.params.glwe_dimension as usize, 1usize << bk.params.glwe_poly_degree);
+        let dim = bk.params.lwe_dimension as usize;
+        assert!((2..=4).contains(&g), "MultibitKey: g must be 2, 3 or 4");
+        let rows = ((dim + g as usize - 1) / g as usize) * ((1usize << g) - 1) * (k + 1) * bk.params.pbs_decomposer.levels as usize;
+        assert!(lwe_sk.len() == dim && glwe_sk.dim() == (k, n) && samples.dim() == (rows, k + 1, n),
+                "MultibitKey: lwe_sk (n), glwe_sk (k, N), samples (ceil(n/g) * (2^g - 1) * (k+1) l, k+1, N)");
+        let mut key = samples.clone();
+        check(bk.ctx, unsafe {
+            tfhe_generate_multibit_key(bk.ctx, lwe_sk.as_slice().unwrap().as_ptr(), glwe_sk.as_slice().unwrap().as_ptr(), g as c_uint,
+                                       key.as_slice_mut().unwrap().as_mut_ptr())
+        }, "generate_multibit_key");
+        let mut raw = std::ptr::null_mut();
+        check(bk.ctx, unsafe { tfhe_prepare_multibit_key(bk.ctx, key.as_slice().unwrap().as_ptr(), g as c_uint, &mut raw) },
+              "prepare_multibit_key");
+        MultibitKey { raw }
+    }
+}
+
+impl Drop for MultibitKey {
+    fn drop(&mut self) {
+        unsafe { tfhe_multibit_key_destroy(self.raw) };
+    }
+}
+
+/// the multi-bit bootstrap of every ciphertext of `lwe_ciphertexts` (batch, boundary dimension + 1) against one clear test
+/// vector: the plaintexts of `bootstrap_batch`, other ciphertext bits
+pub fn multibit_bootstrap_batch(bk: &GpuBootstrappingKey, key: &MultibitKey, lwe_ciphertexts: &Array2<u32>, test_vector_poly: &Array1<u32>) -> Array2<u32> {
+    assert!(test_vector_poly.len() == 1usize << bk.params.glwe_poly_degree, "multibit_bootstrap_batch: test vector (N)");
+    let mut out = Array2::<u32>::zeros(lwe_ciphertexts.raw_dim());
+    check(bk.ctx, unsafe {
+        tfhe_multibit_bootstrap_batch(bk.ctx, key.raw, lwe_ciphertexts.as_slice().unwrap().as_ptr(), lwe_ciphertexts.nrows(),
+                                      test_vector_poly.as_slice().unwrap().as_ptr(), 1, out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "multibit_bootstrap_batch");
+    out
 }
 
 /// ggsw.rs:132-136

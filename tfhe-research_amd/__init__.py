@@ -118,6 +118,14 @@ class TfheParams:
         """a GLWE switch key: one GLWE row per (polynomial of the source key, KS level)"""
         return (self.k * self.ks_decomposer.levels, self.k + 1, self.N)
 
+    def multibit_groups(self, g: int) -> int:
+        """groups of g key bits of the multi-bit blind rotation: ceil(n / g), the last one may be ragged"""
+        return -(-self.n // g)
+
+    def multibit_key_shape(self, g: int):
+        """the multi-bit bootstrapping key: per group of g key bits one GGSW per non-empty pattern of its bits"""
+        return (self.multibit_groups(g), (1 << g) - 1, (self.k + 1) * self.pbs_decomposer.levels, self.k + 1, self.N)
+
     def external_product_bytes(self) -> int:
         """algorithmic bytes of one GGSW x GLWE external product in the reference's u32 layout,
         each operand moved once: 4*N*(k+1)*((k+1)*l + 2)  """
@@ -330,6 +338,41 @@ def multi_value_noise_factor(luts) -> int:
     return int((d * d).sum(axis=-1).max())
 
 
+def multibit_messages(lwe_sk, g: int) -> np.ndarray:
+    """[ceil(n / g)][2^g - 1] messages of the multi-bit key (include/tfhe_hip.h, "multi-bit blind rotation"): slot (i, p - 1)
+    is 1 exactly when the bits of group i equal the pattern p; slots past a ragged group's patterns are 0"""
+    sk = np.asarray(lwe_sk, dtype=np.int64).reshape(-1)
+    n = sk.size
+    groups = -(-n // g)
+    out = np.zeros((groups, (1 << g) - 1), dtype=np.uint32)
+    for i in range(groups):
+        bits = sk[i * g:min(n, i * g + g)]
+        value = int((bits << np.arange(bits.size)).sum())
+        if value:
+            out[i, value - 1] = 1
+    return out
+
+
+def multibit_noise_variance(params: TfheParams, g: int, aligned: bool = True) -> float:
+    """s_mb^2 of include/tfhe_hip.h ("multi-bit blind rotation", Noise): the variance a multi-bit blind rotation with g key
+    bits per group adds to a coefficient, in units of the 32-bit torus (squared).  The modulus-switch and key-switch terms
+    of a bootstrap are the ordinary bootstrap's and not included."""
+    if g not in (2, 3, 4):
+        raise _invalid("multibit_noise_variance: g must be 2, 3 or 4")
+    k, big_n, n = params.k, params.N, params.n
+    lb, levels = params.pbs_decomposer.log_base, params.pbs_decomposer.levels
+    top = 32 if aligned else lb * (32 // lb)
+    ignored = top - lb * levels
+    sigma = params.glwe_std_dev * 2.0 ** 32
+    per_row = (k + 1) * levels * big_n * ((2.0 ** lb) ** 2 / 12.0 + 1.0 / 6.0) * sigma * sigma
+    rounding = 2.0 * (1.0 + k * big_n / 2.0) * 2.0 ** (2 * ignored) / 12.0
+    total = 0.0
+    for i in range(-(-n // g)):
+        bits = min(g, n - i * g)
+        total += 2.0 * ((1 << bits) - 1) * per_row + rounding
+    return total
+
+
 def construct_identity_test_vector(params: TfheParams) -> np.ndarray:
     """test_vector.rs:23-35"""
     return construct_test_from_lut(params, np.arange(1 << params.log_p, dtype=np.uint32))
@@ -480,6 +523,32 @@ class GlweSwitchKey:
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             lib().tfhe_glwe_switch_key_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class MultibitKey:
+    """A prepared multi-bit bootstrapping key (Context.prepare_multibit_key): lives on the device of the context that
+    prepared it and belongs to that context; usable until close() (close it before its context)."""
+
+    def __init__(self, handle, g: int):
+        self._h = handle
+        self.g = g
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().tfhe_multibit_key_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -1103,6 +1172,119 @@ class Context:
             else:
                 x = self.glwe_automorphism(x, (p.N >> (j - 1)) + 1, keys[j - 1], True)
         return x
+
+    # -- multi-bit blind rotation: g key bits per external product (include/tfhe_hip.h states the operation) --
+    def generate_multibit_key(self, lwe_sk, glwe_sk, g: int, samples):
+        """samples [ceil(n/g)][2^g - 1][(k+1) l][k+1][N] pre-filled like ggsw_encrypt's (uniform masks, errors in the body)
+        -> the multi-bit key: slot (i, p - 1) a GGSW of "the bits of group i are exactly p".  A torch device tensor is
+        completed in place and returned; a numpy array is copied."""
+        p = self.params
+        sk, gsk = _np(lwe_sk).reshape(p.n), _np(glwe_sk).reshape(p.k, p.N)
+        dev = _is_torch(samples)
+        key = samples if dev else _np(samples).copy()
+        if g not in (2, 3, 4):
+            raise _invalid("generate_multibit_key: g must be 2, 3 or 4")
+        _check_u32("generate_multibit_key", "samples", key, dev, p.multibit_key_shape(g))
+        self._call("tfhe_generate_multibit_key", dev, _ptr(sk), _ptr(gsk), C.c_uint(g), _ptr(key))
+        return key
+
+    def generate_multibit_key_random(self, lwe_sk, glwe_sk, g: int, rng=None) -> np.ndarray:
+        """generate_multibit_key with masks and errors (glwe_std_dev) drawn here, the way generate_keys draws the
+        bootstrapping key's (the OS CSPRNG unless the test hook `rng=` is given)"""
+        p = self.params
+        if g not in (2, 3, 4):
+            raise _invalid("generate_multibit_key_random: g must be 2, 3 or 4")
+        rng = rng if rng is not None else SystemRng()
+        shape = p.multibit_key_shape(g)
+        samples = rng.integers(0, 1 << 32, size=shape, dtype=np.uint64).astype(np.uint32)
+        samples[:, :, :, p.k, :] = self._noise(rng, p.glwe_std_dev, shape[:3] + (p.N,))
+        return self.generate_multibit_key(lwe_sk, glwe_sk, g, samples)
+
+    def prepare_multibit_key(self, bsk_mb, g: int) -> "MultibitKey":
+        """bsk_mb [ceil(n/g)][2^g - 1][(k+1) l][k+1][N] (numpy or torch device tensor) -> the handle multibit_blind_rotate
+        and multibit_bootstrap take.  TfheError(TFHE_ERR_UNSUPPORTED) where the wide team is not offered (another backend
+        than fp64-fft, N = 2048).  Synchronises; prepare once, use often."""
+        p = self.params
+        if g not in (2, 3, 4):
+            raise _invalid("prepare_multibit_key: g must be 2, 3 or 4")
+        dev = _is_torch(bsk_mb)
+        raw = bsk_mb if dev else _np(bsk_mb)
+        _check_u32("prepare_multibit_key", "bsk_mb", raw, dev, p.multibit_key_shape(g))
+        handle = C.c_void_p()
+        self._call("tfhe_prepare_multibit_key", dev, _ptr(raw), C.c_uint(g), C.byref(handle))
+        prepared = MultibitKey(handle, g)
+        prepared._ctx = self  # the handle must not outlive its context
+        return prepared
+
+    def reserve_multibit(self, max_batch: int, g: int):
+        """size the bundle workspace of the device forms: max_batch * ceil(n/g) prepared GGSWs (a maximum for this g;
+        the header states the bytes), and the LWE workspace of reserve()"""
+        self._check(lib().tfhe_context_reserve_multibit(self._h, C.c_size_t(max_batch), C.c_uint(g)))
+
+    @staticmethod
+    def _open_multibit_key(what, key):
+        if not isinstance(key, MultibitKey) or not key._h or not key._h.value:
+            raise _invalid(f"{what}: an open key from prepare_multibit_key expected")
+        return key._h
+
+    def multibit_blind_rotate(self, key: "MultibitKey", lwe_in, test_vector_poly=None, acc_in=None, rotation_offset: int = 0,
+                              glwe_out=True, lwe_extracted=False):
+        """The multi-bit blind rotation of lwe_in [batch][n+1] from clear test vectors ([N] or [1 or batch][N]) or from
+        GLWE accumulators acc_in ([k+1][N] or [1 or batch][k+1][N], with rotation_offset).  glwe_out / lwe_extracted:
+        False (not wanted), True (a new array) or, in the device form, the tensor to write -> the GLWE accumulators
+        [batch][k+1][N], their sample extracts [batch][k N + 1], or the pair of them.  numpy: host form, blocks.  torch:
+        on torch's current stream, after reserve_multibit enqueues only."""
+        p = self.params
+        what = "multibit_blind_rotate"
+        handle = self._open_multibit_key(what, key)
+        if (test_vector_poly is None) == (acc_in is None):
+            raise _invalid(f"{what}: pass either test_vector_poly or acc_in")
+        if glwe_out is False and lwe_extracted is False:
+            raise _invalid(f"{what}: ask for glwe_out, lwe_extracted or both")
+        lwe, dev = self._lwe_rows(what, "lwe_in", lwe_in, p.n + 1)
+        batch = int(lwe.shape[0])
+        tv = acc = None
+        if acc_in is None:
+            tv, count = self._test_vectors(what, test_vector_poly, batch, dev, lwe)
+            if rotation_offset:
+                raise _invalid(f"{what}: rotation_offset goes with acc_in")
+        else:
+            if _is_torch(acc_in) != dev:
+                raise _invalid(f"{what}: lwe_in and acc_in must both be numpy or both torch")
+            acc = acc_in if dev else _np(acc_in)
+            if len(acc.shape) != 3:
+                acc = _lead(acc, dev)
+            _check_u32(what, "acc_in", acc, dev, (None, p.k + 1, p.N), lwe if dev else None)
+            count = int(acc.shape[0])
+            if count not in (1, batch):
+                raise _invalid(f"{what}: acc_in [1 or {batch}][{p.k + 1}][{p.N}] expected, got {tuple(acc.shape)}")
+            if not 0 <= int(rotation_offset) < 2 * p.N:
+                raise _invalid(f"{what}: rotation_offset must be in [0, 2N = {2 * p.N})")
+        want = lambda o, shape: None if o is False else _result(what, dev, None if o is True else o, shape, lwe)  # noqa: E731
+        glwe = want(glwe_out, (batch, p.k + 1, p.N))
+        ext = want(lwe_extracted, (batch, p.big_n + 1))
+        self._call("tfhe_multibit_blind_rotate_batch", dev, handle, _ptr(lwe), C.c_size_t(batch), _ptr(tv), C.c_size_t(count),
+                   _ptr(acc), C.c_size_t(int(rotation_offset)), _ptr(glwe), _ptr(ext))
+        return glwe if ext is None else ext if glwe is None else (glwe, ext)
+
+    def multibit_bootstrap(self, key: "MultibitKey", lwe_in, test_vector_poly, out=None):
+        """multibit_blind_rotate + sample extraction at 0 + the context's key switch, in the context's bootstrap order:
+        [batch][io_dim+1] -> [batch][io_dim+1].  The same plaintexts as bootstrap(), other ciphertext bits.  Needs a loaded
+        key-switching key (load_bootstrapping_key)."""
+        what = "multibit_bootstrap"
+        handle = self._open_multibit_key(what, key)
+        lwe, dev = self._lwe_rows(what, "lwe_in", lwe_in, self.io_dim + 1)
+        batch = int(lwe.shape[0])
+        tv, count = self._test_vectors(what, test_vector_poly, batch, dev, lwe)
+        res = _result(what, dev, out, (batch, self.io_dim + 1), lwe)
+        self._call("tfhe_multibit_bootstrap_batch", dev, handle, _ptr(lwe), C.c_size_t(batch), _ptr(tv), C.c_size_t(count), _ptr(res))
+        return res
+
+    def multibit_last_kernel_ms(self):
+        """(bundle launch ms, rotate launch ms) of the last multibit_blind_rotate under set_timing(True)"""
+        a, b = C.c_float(), C.c_float()
+        self._check(lib().tfhe_multibit_last_kernel_ms(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def external_product(self, ggsw, glwe) -> np.ndarray:
         """external_product(): ggsw.rs:132-161.  ggsw [R][k+1][N] (shared) or [batch][R][k+1][N]."""

@@ -240,6 +240,7 @@ std::string exactness_refusal(const tfhe_context* ctx, int rows, int lb, const E
 enum Span { kRotationSpan = 0, kKeySwitchSpan = 2 };
 
 int span_begin(tfhe_context* ctx, Span span) {
+  ctx->ev_valid_mb = false;  // the events of a multi-bit rotation's launches (tfhe_multibit_last_kernel_ms) are reused
   if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[span], ctx->stream));
   return TFHE_OK;
 }
@@ -310,8 +311,9 @@ hipError_t enqueue_blind_rotate(tfhe_context* ctx, const u32* lwe_in, size_t bat
 
 // Enqueue the whole PBS on device buffers: blind rotation (+ fused sample extract), key switch (bootstrapping.rs:58-120),
 // or the key switch first.  d_lwe_big: [batch][k*N+1] scratch of the reference order (unused when the key switch comes first)
-int enqueue_bootstrap(tfhe_context* ctx, const u32* d_lwe_in, size_t batch, const u32* d_tv,
-                      size_t tv_count, u32* d_lwe_big, u32* d_lwe_out, AccSource from = AccSource()) {
+// rotate(br_in, br_out) enqueues the rotation with its sample extract: the loaded key's, or a multi-bit key's
+template <class Rotate>
+int enqueue_bootstrap_with(tfhe_context* ctx, const u32* d_lwe_in, size_t batch, u32* d_lwe_big, u32* d_lwe_out, Rotate rotate) {
   const u32* br_in = d_lwe_in;
   u32* br_out = d_lwe_big;
   if (ctx->timing) {  // next slot of the ring
@@ -330,11 +332,18 @@ int enqueue_bootstrap(tfhe_context* ctx, const u32* d_lwe_in, size_t batch, cons
     br_out = d_lwe_out;
   }
   TFHE_TRY(span_begin(ctx, kRotationSpan));
-  HIP_TRY(ctx, enqueue_blind_rotate(ctx, br_in, batch, d_tv, tv_count, nullptr, br_out, from));
+  HIP_TRY(ctx, rotate(br_in, br_out));
   TFHE_TRY(span_end(ctx, kRotationSpan, false));
   if (!ctx->ks_first) TFHE_TRY(key_switch(d_lwe_big, d_lwe_out));
   if (ctx->timing) ctx->ev_valid_br = ctx->ev_valid_ks = true;
   return TFHE_OK;
+}
+
+int enqueue_bootstrap(tfhe_context* ctx, const u32* d_lwe_in, size_t batch, const u32* d_tv,
+                      size_t tv_count, u32* d_lwe_big, u32* d_lwe_out, AccSource from = AccSource()) {
+  return enqueue_bootstrap_with(ctx, d_lwe_in, batch, d_lwe_big, d_lwe_out, [&](const u32* br_in, u32* br_out) {
+    return enqueue_blind_rotate(ctx, br_in, batch, d_tv, tv_count, nullptr, br_out, from);
+  });
 }
 
 // log2 of the worst-case |integer convolution value| one inverse transform has to lift:
@@ -722,7 +731,7 @@ int tfhe_context_reserve(tfhe_context* ctx, size_t max_batch) {
 int tfhe_context_set_timing(tfhe_context* ctx, int enable) {
   if (!ctx) return TFHE_ERR_INVALID_ARGUMENT;
   ctx->timing = enable != 0;
-  ctx->ev_valid_br = ctx->ev_valid_ks = false;
+  ctx->ev_valid_br = ctx->ev_valid_ks = ctx->ev_valid_mb = false;
   ctx->timed_bootstraps = 0;
   return TFHE_OK;
 }
@@ -2645,6 +2654,270 @@ int tfhe_glwe_automorphism_batch(tfhe_context* ctx, const uint32_t* glwe_in, siz
   TFHE_TRY(s.upload(0, glwe_in));
   TFHE_TRY(tfhe_glwe_automorphism_batch_device(ctx, s[0], batch, t, key, add_input, s[0]));  // in place
   return s.download_and_wait(0, glwe_out);
+}
+
+// ---------------------------------------------------------------------------------- multi-bit blind rotation
+// tfhe_hip.h states the operation, multibit.h the two launches: the bundles of a call -- one prepared GGSW per (sample,
+// group of g key bits) -- go to the reserved workspace, the wide team then rotates over them.
+namespace {
+
+int check_multibit_bits(tfhe_context* ctx, unsigned g) {
+  if (g < 2 || g > (unsigned)kMultibitMaxBits)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "g must be 2, 3 or 4 key bits per group, got " + std::to_string(g));
+  return TFHE_OK;
+}
+
+// the multi-bit rotation runs on the wide team: refused wherever the launcher does not offer that shape
+int multibit_refusal(tfhe_context* ctx) {
+  int why = 0;
+  if (launch::multibit_refusal(ctx->field, ctx->pbs, &why) != hipSuccess) why = launch::kMultibitNoRing;
+  const std::string head = "the multi-bit blind rotation runs on the wide team, which is offered ";
+  switch (why) {
+    case 0: return TFHE_OK;
+    case launch::kMultibitNoBackend:
+      return fail(ctx, TFHE_ERR_UNSUPPORTED, head + "in the fp64-fft backend only; this context uses " + tfhe_context_backend(ctx));
+    case launch::kMultibitNoLds:
+      return fail(ctx, TFHE_ERR_UNSUPPORTED, head + "while its (k+1) l = " + std::to_string(ctx->R) +
+                                                 " row buffers fit the 160 KiB of LDS of a CU; these parameters need more");
+    default:
+      return fail(ctx, TFHE_ERR_UNSUPPORTED, head + "up to N = 1024; this context has N = " + std::to_string(ctx->N));
+  }
+}
+
+int check_multibit_key(tfhe_context* ctx, const tfhe_multibit_key* key) {
+  if (!key) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  if (key->owner != ctx || key->device != ctx->device || !key->d_key || key->groups != multibit_groups(ctx, key->g))
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "the multi-bit key was prepared by another context");
+  return TFHE_OK;
+}
+
+int check_multibit_batch(tfhe_context* ctx, size_t batch, size_t count, const char* count_name) {
+  if (batch == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "empty batch");
+  if (batch > 65535) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "batch exceeds 65535 (the bundle launch's second grid dimension)");
+  if (count != 1 && count != batch) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, std::string(count_name) + " must be 1 or batch");
+  return TFHE_OK;
+}
+
+int check_multibit_reserved(tfhe_context* ctx, const tfhe_multibit_key* key, size_t batch) {
+  const size_t need = multibit_bundle_bytes(ctx, batch, key->g);
+  if (need > ctx->d_mb_ws.bytes() || batch > ctx->ws_batch)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "the bundles of " + std::to_string(batch) + " samples at g = " + std::to_string(key->g) + " need " + std::to_string(need) +
+                    " bytes, reserved " + std::to_string(ctx->d_mb_ws.bytes()) + ": call tfhe_context_reserve_multibit(ctx, " +
+                    std::to_string(batch) + ", " + std::to_string(key->g) + ") first");
+  return TFHE_OK;
+}
+
+int reserve_multibit(tfhe_context* ctx, size_t batch, unsigned g) {
+  TFHE_TRY(reserve(ctx, batch));
+  return ctx->d_mb_ws.grow(ctx, multibit_bundle_bytes(ctx, batch, g));
+}
+
+// what a rotation starts from: clear test vectors [tv_count][N], or GLWE accumulators [tv_count][k+1][N] and an offset
+struct MultibitSource {
+  const u32* acc;
+  size_t count;
+  bool glwe;
+  u32 offset;
+};
+
+hipError_t enqueue_multibit_rotate(tfhe_context* ctx, const tfhe_multibit_key* key, const u32* lwe_in, size_t batch, const MultibitSource& from,
+                                   u32* glwe_out, u32* lwe_extracted, bool time_launches = false) {
+  PbsParams P = ctx->pbs;
+  P.acc_glwe = from.glwe ? 1u : 0u;
+  P.acc_offset = from.offset;
+  const size_t words = from.glwe ? glwe_words(ctx) : (size_t)ctx->N;
+  auto mark = [&](int i) { return time_launches && ctx->timing ? hipEventRecord(ctx->ev[i], ctx->stream) : hipSuccess; };
+  hipError_t e = mark(0);
+  if (e == hipSuccess)
+    e = launch::multibit_bundle(ctx->stream, ctx->field, P, ctx->d_tw.as(), key->d_key.as<u32>(), key->g, lwe_in, batch, ctx->d_mb_ws.as());
+  if (e == hipSuccess) e = mark(1);
+  if (e == hipSuccess) e = mark(2);
+  if (e == hipSuccess)
+    e = launch::multibit_rotate(ctx->stream, ctx->field, P, ctx->d_tw.as(), lwe_in, batch, from.acc, from.count == 1 ? 0 : words,
+                                ctx->d_mb_ws.as(), key->groups, glwe_out, lwe_extracted);
+  if (e == hipSuccess) e = mark(3);
+  return e;
+}
+
+int check_multibit_rotate_args(tfhe_context* ctx, const tfhe_multibit_key* key, const void* lwe_in, size_t batch, const void* tv,
+                               size_t tv_count, const void* acc_in, size_t rotation_offset, const void* glwe_out, const void* lwe_extracted) {
+  TFHE_TRY(check_multibit_key(ctx, key));
+  if (!lwe_in) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  if ((tv != nullptr) == (acc_in != nullptr))
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "pass either test_vector_poly or acc_in, not both and not neither");
+  if (!glwe_out && !lwe_extracted) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "pass glwe_out, lwe_extracted or both");
+  TFHE_TRY(check_multibit_batch(ctx, batch, tv_count, acc_in ? "acc_count" : "tv_count"));
+  if (acc_in && rotation_offset >= 2 * (size_t)ctx->N)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "rotation_offset must be below 2N = " + std::to_string(2 * (size_t)ctx->N));
+  if (!acc_in && rotation_offset != 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "rotation_offset goes with acc_in");
+  return TFHE_OK;
+}
+
+int check_multibit_bootstrap_args(tfhe_context* ctx, const tfhe_multibit_key* key, const void* lwe_in, size_t batch, const void* tv,
+                                  size_t tv_count, const void* lwe_out) {
+  TFHE_TRY(check_multibit_key(ctx, key));
+  TFHE_TRY(check_present(ctx, {lwe_in, tv, lwe_out}, 1, "null pointer"));
+  TFHE_TRY(check_multibit_batch(ctx, batch, tv_count, "tv_count"));
+  if (!ctx->have_key) return fail(ctx, TFHE_ERR_NO_KEY, "load a key-switching key first (tfhe_load_bootstrapping_key carries it)");
+  return TFHE_OK;
+}
+
+// message of slot (group, p - 1): the group's bits are exactly the pattern p; slots past a ragged group's patterns hold 0
+void multibit_messages(const u32* lwe_sk, size_t n, unsigned g, std::vector<u32>* out) {
+  const size_t groups = (n + g - 1) / g, slots = ((size_t)1 << g) - 1;
+  std::vector<u32>& m = *out;
+  m.assign(groups * slots, 0u);
+  for (size_t i = 0; i < groups; ++i) {
+    const size_t bits = std::min<size_t>(g, n - i * g);
+    for (size_t p = 1; p < ((size_t)1 << bits); ++p) {
+      u32 v = 1u;
+      for (size_t j = 0; j < bits; ++j) v *= ((p >> j) & 1u) ? lwe_sk[i * g + j] : 1u - lwe_sk[i * g + j];
+      m[i * slots + p - 1] = v;
+    }
+  }
+}
+
+int check_multibit_key_gen(tfhe_context* ctx, const u32* lwe_sk, const u32* glwe_sk, unsigned g, const u32* bsk_mb) {
+  TFHE_TRY(check_present(ctx, {lwe_sk, glwe_sk, bsk_mb}, 1, "null pointer"));
+  TFHE_TRY(check_multibit_bits(ctx, g));
+  TFHE_TRY(check_binary(ctx, lwe_sk, ctx->params.lwe_dimension, "lwe secret key"));
+  return check_binary(ctx, glwe_sk, ctx->big_n, "glwe secret key");
+}
+
+int prepare_multibit_key_common(tfhe_context* ctx, const u32* raw, unsigned g, bool raw_on_device, tfhe_multibit_key** out) {
+  TFHE_TRY(check_present(ctx, {raw, out}, 1, "null pointer"));
+  *out = nullptr;
+  TFHE_TRY(check_multibit_bits(ctx, g));
+  TFHE_TRY(multibit_refusal(ctx));
+  tfhe_multibit_key* h = new (std::nothrow) tfhe_multibit_key();
+  if (!h) return fail(ctx, TFHE_ERR_HIP, "out of host memory");
+  h->owner = ctx;
+  h->device = ctx->device;
+  h->g = g;
+  h->groups = (u32)multibit_groups(ctx, g);
+  const size_t bytes = multibit_key_ggsws(ctx, g) * ggsw_words(ctx) * sizeof(u32);
+  int st = h->d_key.grow(ctx, bytes);
+  if (st == TFHE_OK) {
+    hipError_t e = hipMemcpyAsync(h->d_key.as(), raw, bytes, raw_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the caller's raw key is free again on return
+    if (e != hipSuccess) st = hip_fail(ctx, e, "tfhe_prepare_multibit_key");
+  }
+  if (st != TFHE_OK) {
+    tfhe_multibit_key_destroy(h);
+    return st;
+  }
+  *out = h;
+  return TFHE_OK;
+}
+
+}  // namespace
+
+int tfhe_generate_multibit_key_device(tfhe_context* ctx, const uint32_t* lwe_sk, const uint32_t* glwe_sk, unsigned g, uint32_t* bsk_mb) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_multibit_key_gen(ctx, lwe_sk, glwe_sk, g, bsk_mb));
+  std::vector<u32> messages;
+  multibit_messages(lwe_sk, ctx->params.lwe_dimension, g, &messages);
+  // `messages` is pageable host memory: the async copy inside has staged it before returning
+  return tfhe_ggsw_encrypt_batch_device(ctx, glwe_sk, messages.data(), bsk_mb, messages.size());
+}
+
+int tfhe_generate_multibit_key(tfhe_context* ctx, const uint32_t* lwe_sk, const uint32_t* glwe_sk, unsigned g, uint32_t* bsk_mb) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_multibit_key_gen(ctx, lwe_sk, glwe_sk, g, bsk_mb));
+  return in_place_host_form(ctx, bsk_mb, multibit_key_ggsws(ctx, g) * ggsw_words(ctx),
+                            [&](u32* d) { return tfhe_generate_multibit_key_device(ctx, lwe_sk, glwe_sk, g, d); });
+}
+
+int tfhe_prepare_multibit_key_device(tfhe_context* ctx, const uint32_t* bsk_mb, unsigned g, tfhe_multibit_key** out) {
+  TFHE_TRY(check_ctx(ctx));
+  return prepare_multibit_key_common(ctx, bsk_mb, g, true, out);
+}
+
+int tfhe_prepare_multibit_key(tfhe_context* ctx, const uint32_t* bsk_mb, unsigned g, tfhe_multibit_key** out) {
+  TFHE_TRY(check_ctx(ctx));
+  return prepare_multibit_key_common(ctx, bsk_mb, g, false, out);
+}
+
+void tfhe_multibit_key_destroy(tfhe_multibit_key* key) {
+  if (!key) return;
+  (void)hipSetDevice(key->device);  // before `delete` releases the key
+  delete key;
+}
+
+int tfhe_context_reserve_multibit(tfhe_context* ctx, size_t max_batch, unsigned g) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_multibit_bits(ctx, g));
+  TFHE_TRY(check_multibit_batch(ctx, max_batch, 1, "max_batch"));
+  TFHE_TRY(multibit_refusal(ctx));
+  return reserve_multibit(ctx, max_batch, g);
+}
+
+int tfhe_multibit_last_kernel_ms(tfhe_context* ctx, float* bundle_ms, float* rotate_ms) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_present(ctx, {bundle_ms, rotate_ms}, 1, "null pointer"));
+  if (!ctx->timing || !ctx->ev_valid_mb) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "no timed multi-bit rotation: enable tfhe_context_set_timing first");
+  HIP_TRY(ctx, hipEventSynchronize(ctx->ev[3]));
+  HIP_TRY(ctx, hipEventElapsedTime(bundle_ms, ctx->ev[0], ctx->ev[1]));
+  HIP_TRY(ctx, hipEventElapsedTime(rotate_ms, ctx->ev[2], ctx->ev[3]));
+  return TFHE_OK;
+}
+
+int tfhe_multibit_blind_rotate_batch_device(tfhe_context* ctx, const tfhe_multibit_key* key, const uint32_t* lwe_in, size_t batch,
+                                            const uint32_t* test_vector_poly, size_t tv_count, const uint32_t* acc_in,
+                                            size_t rotation_offset, uint32_t* glwe_out, uint32_t* lwe_extracted) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_multibit_rotate_args(ctx, key, lwe_in, batch, test_vector_poly, tv_count, acc_in, rotation_offset, glwe_out, lwe_extracted));
+  TFHE_TRY(check_multibit_reserved(ctx, key, batch));
+  const MultibitSource from{acc_in ? acc_in : test_vector_poly, tv_count, acc_in != nullptr, (u32)rotation_offset};
+  HIP_TRY(ctx, enqueue_multibit_rotate(ctx, key, lwe_in, batch, from, glwe_out, lwe_extracted, true));
+  if (ctx->timing) {  // events 0/1 bracket the bundle launch, 2/3 the rotate launch: tfhe_multibit_last_kernel_ms
+    ctx->ev_valid_br = ctx->ev_valid_ks = false;
+    ctx->ev_valid_mb = true;
+  }
+  return TFHE_OK;
+}
+
+int tfhe_multibit_blind_rotate_batch(tfhe_context* ctx, const tfhe_multibit_key* key, const uint32_t* lwe_in, size_t batch,
+                                     const uint32_t* test_vector_poly, size_t tv_count, const uint32_t* acc_in, size_t rotation_offset,
+                                     uint32_t* glwe_out, uint32_t* lwe_extracted) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_multibit_rotate_args(ctx, key, lwe_in, batch, test_vector_poly, tv_count, acc_in, rotation_offset, glwe_out, lwe_extracted));
+  if (!acc_in) TFHE_TRY(check_tv_host(ctx, test_vector_poly, tv_count * ctx->N));
+  TFHE_TRY(reserve_multibit(ctx, batch, key->g));
+  TFHE_TRY(upload(ctx, ctx->d_lwe_in.as<u32>(), lwe_in, batch * lwe_words(ctx)));
+  if (acc_in) TFHE_TRY(upload(ctx, ctx->d_glwe_a.as<u32>(), acc_in, tv_count * glwe_words(ctx)));
+  else TFHE_TRY(upload(ctx, ctx->d_tv.as<u32>(), test_vector_poly, tv_count * ctx->N));
+  TFHE_TRY(tfhe_multibit_blind_rotate_batch_device(ctx, key, ctx->d_lwe_in.as<u32>(), batch, acc_in ? nullptr : ctx->d_tv.as<u32>(), tv_count,
+                                                   acc_in ? ctx->d_glwe_a.as<u32>() : nullptr, rotation_offset,
+                                                   glwe_out ? ctx->d_glwe_b.as<u32>() : nullptr, lwe_extracted ? ctx->d_lwe_big.as<u32>() : nullptr));
+  if (glwe_out) TFHE_TRY(download(ctx, glwe_out, ctx->d_glwe_b.as<u32>(), batch * glwe_words(ctx)));
+  if (lwe_extracted) TFHE_TRY(download(ctx, lwe_extracted, ctx->d_lwe_big.as<u32>(), batch * big_lwe_words(ctx)));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return TFHE_OK;
+}
+
+int tfhe_multibit_bootstrap_batch_device(tfhe_context* ctx, const tfhe_multibit_key* key, const uint32_t* lwe_in, size_t batch,
+                                         const uint32_t* test_vector_poly, size_t tv_count, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_multibit_bootstrap_args(ctx, key, lwe_in, batch, test_vector_poly, tv_count, lwe_out));
+  TFHE_TRY(check_multibit_reserved(ctx, key, batch));
+  const MultibitSource from{test_vector_poly, tv_count, false, 0u};
+  return enqueue_bootstrap_with(ctx, lwe_in, batch, ctx->d_lwe_big.as<u32>(), lwe_out, [&](const u32* br_in, u32* br_out) {
+    return enqueue_multibit_rotate(ctx, key, br_in, batch, from, nullptr, br_out);
+  });
+}
+
+int tfhe_multibit_bootstrap_batch(tfhe_context* ctx, const tfhe_multibit_key* key, const uint32_t* lwe_in, size_t batch,
+                                  const uint32_t* test_vector_poly, size_t tv_count, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_multibit_bootstrap_args(ctx, key, lwe_in, batch, test_vector_poly, tv_count, lwe_out));
+  TFHE_TRY(check_tv_host(ctx, test_vector_poly, tv_count * ctx->N));
+  TFHE_TRY(reserve_multibit(ctx, batch, key->g));
+  TFHE_TRY(upload(ctx, ctx->d_lwe_in.as<u32>(), lwe_in, batch * io_words(ctx)));
+  TFHE_TRY(upload(ctx, ctx->d_tv.as<u32>(), test_vector_poly, tv_count * ctx->N));
+  TFHE_TRY(tfhe_multibit_bootstrap_batch_device(ctx, key, ctx->d_lwe_in.as<u32>(), batch, ctx->d_tv.as<u32>(), tv_count, ctx->d_lwe_out.as<u32>()));
+  return download_and_wait(ctx, lwe_out, ctx->d_lwe_out.as<u32>(), batch * io_words(ctx));
 }
 
 // ---------------------------------------------------------------------------------- multi-value bootstrap

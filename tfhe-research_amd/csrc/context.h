@@ -125,6 +125,8 @@ struct tfhe_context {
   DeviceBuffer d_mv_ws;
   size_t mv_batch = 0, mv_tables = 0;
   bool tree_level0_multi_value = false;  // tfhe_context_set_tree_lut_level0
+  // multi-bit blind rotation (tfhe_context_reserve_multibit): the bundles of one call, per sample ceil(n / g) prepared GGSWs
+  DeviceBuffer d_mb_ws;
   bool aligned = false;       // decomposer alignment (tfhe_context_set_decomposer_alignment)
   bool ks_first = false;      // bootstrap order (tfhe_context_set_bootstrap_order)
   int shape = 0;              // kernel shape of the blind rotation (tfhe_context_set_kernel_shape): launch::kShape*
@@ -170,6 +172,7 @@ struct tfhe_context {
   int ev_slot = 0;
   unsigned long long timed_bootstraps = 0;
   bool ev_valid_br = false, ev_valid_ks = false;
+  bool ev_valid_mb = false;  // the current slot's events bracket a multi-bit rotation's two launches (tfhe_multibit_last_kernel_ms)
 
   std::string last_error;
 };
@@ -194,6 +197,16 @@ struct tfhe_glwe_switch_key {
   int field = 0;
   u32 log_n = 0, k = 0, levels = 0;
   DeviceBuffer d_key;  // [(k+1) l_ks][k+1][parts][N] 8-byte words (spectrum_slot order, x 1/N)
+};
+
+// A prepared multi-bit bootstrapping key (tfhe_prepare_multibit_key): the raw u32 GGSWs [ceil(n / g)][2^g - 1][(k+1) l][k+1][N]
+// on the device of the context that prepared it -- the bundle launch reads them word by word (multibit.h), nothing is
+// transformed ahead of a call.
+struct tfhe_multibit_key {
+  const tfhe_context* owner = nullptr;  // compared, never dereferenced
+  int device = 0;
+  u32 g = 0, groups = 0;
+  DeviceBuffer d_key;
 };
 
 namespace tfhe {
@@ -234,6 +247,13 @@ inline size_t packing_key_words(const tfhe_context* ctx, size_t from_dimension) 
 // the raw GLWE switch key: one GLWE row per (polynomial of the source key, KS level)
 inline size_t glwe_switch_key_words(const tfhe_context* ctx) {
   return (size_t)ctx->params.glwe_dimension * ctx->ks.levels * glwe_words(ctx);
+}
+// the multi-bit key for g bits per group: 2^g - 1 raw GGSWs per group of key bits
+inline size_t multibit_groups(const tfhe_context* ctx, unsigned g) { return ((size_t)ctx->params.lwe_dimension + g - 1) / g; }
+inline size_t multibit_key_ggsws(const tfhe_context* ctx, unsigned g) { return multibit_groups(ctx, g) * (((size_t)1 << g) - 1); }
+// the bundles of `batch` samples: one prepared GGSW per (sample, group)
+inline size_t multibit_bundle_bytes(const tfhe_context* ctx, size_t batch, unsigned g) {
+  return batch * multibit_groups(ctx, g) * prepared_ggsw_words(ctx) * sizeof(u64);
 }
 inline size_t prepared_bsk_bytes(const tfhe_context* ctx, size_t ggsws) {
   return ggsws * prepared_ggsw_words(ctx) * sizeof(u64);

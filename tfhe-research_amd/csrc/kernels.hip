@@ -529,6 +529,77 @@ blind_rotate_wide_kernel(PbsParams P, const typename F::elem* __restrict__ tw, c
   }
 }
 
+// ------------------------------------------------------------------------------ multi-bit blind rotation
+// multibit.h states the two steps.  The bundle launch is bsk_prepare_kernel's shape -- one polynomial per wave, four per
+// workgroup -- over (every polynomial of every group's bundle, the batch): at cfg2 with g = 3 that is 630 workgroups per
+// sample, the launch that fills the chip at batch 1.  The rotate launch is blind_rotate_wide_kernel's: one wide team per
+// sample, its key the sample's own bundles.
+template <class F, int LOGN, int GBITS>
+__global__ void __launch_bounds__(256) multibit_bundle_kernel(const typename F::elem* __restrict__ tw, const u32* __restrict__ key,
+                                                             const u32* __restrict__ lwe_in, u32 n, u32 groups, u32 ggsw_polys,
+                                                             typename F::elem* __restrict__ bundles, typename F::elem n_inv, int layout_e) {
+  typedef typename F::elem elem;
+  constexpr int N = 1 << LOGN;
+  static_assert(GroupOf<F, LOGN>::value == 1, "one wave per polynomial: a wave past the end of the list may leave");
+  elem* twl = reinterpret_cast<elem*>(g_smem);
+  ntt_stage_twiddles<LOGN - F::kLogShrink, 1>(twl, tw, (int)threadIdx.x, (int)blockDim.x);
+  __syncthreads();
+  const int wave = (int)(threadIdx.x / 64u);
+  const size_t polys = (size_t)groups * ggsw_polys;  // of one sample's bundles
+  const size_t poly = (size_t)blockIdx.x * (blockDim.x / 64u) + wave;
+  if (poly >= polys) return;
+  const size_t sample = blockIdx.y;
+  DeviceWave<elem, 1> w;
+  w.group_ = 0;
+  w.group_stride_ = 0;
+  w.buffer_bytes_ = 0;
+  w.acc_words_ = 0;
+  w.team_base_ = nullptr;
+  w.tw_ = twl;
+  w.twg_ = tw;
+  w.scratch_ = reinterpret_cast<elem*>(g_smem + twiddle_bytes<F, LOGN>() + (size_t)wave * N * 8);
+  w.acc_ = nullptr;
+  const u32 group = w.uniform((u32)(poly / ggsw_polys)), rc = w.uniform((u32)(poly % ggsw_polys));
+  const u32* lwe = lwe_in + sample * ((size_t)n + 1);
+  elem* spec = bundles + (sample * polys + poly) * (N >> F::kLogShrink) * F::kParts;
+  const size_t ggsw_words = (size_t)ggsw_polys * N;
+  if constexpr (key_layout_e<F, LOGN, 1>() != 0) {
+    if (layout_e == key_layout_e<F, LOGN, 1>()) {
+      multibit_bundle_wave<F, LOGN, 1, GBITS, key_layout_e<F, LOGN, 1>()>(w, key, ggsw_words, lwe, n, group, rc, spec, n_inv);
+      return;
+    }
+  }
+  multibit_bundle_wave<F, LOGN, 1, GBITS, 0>(w, key, ggsw_words, lwe, n, group, rc, spec, n_inv);
+}
+
+// LDS and registers: blind_rotate_wide_kernel's (the key ring and its budget are explained there)
+template <class F, int LOGN, int K, int LEVELS>
+__global__ void __launch_bounds__((WideCfg<F, LOGN, K>::kThreads), (K == 1 && LEVELS > 0 ? 1 : kWideMinWaves))
+multibit_rotate_wide_kernel(PbsParams P, const typename F::elem* __restrict__ tw, const u32* __restrict__ lwe_in,
+                            const u32* __restrict__ tv, size_t tv_stride, const typename F::elem* __restrict__ bundles, u32 groups,
+                            u32* glwe_out, u32* __restrict__ lwe_extracted) {
+  typedef typename F::elem elem;
+  using C = WideCfg<F, LOGN, K>;
+  constexpr int N = C::N;
+  elem* twl = reinterpret_cast<elem*>(g_smem);
+  ntt_stage_twiddles<LOGN - F::kLogShrink, 1, elem, staged_twiddle_words<F, LOGN>()>(twl, tw, (int)threadIdx.x, (int)blockDim.x);
+  __syncthreads();
+  WideWave<elem> w;
+  w.wave_ = (int)(threadIdx.x >> 6);
+  w.rows_ = g_smem + C::kTwBytes;
+  w.row_bytes_ = C::kRowBytes;
+  w.scratch_ = reinterpret_cast<elem*>(w.rows_ + ((size_t)(K + 1) * P.levels + w.wave_) * C::kRowBytes);
+  w.acc_ = reinterpret_cast<u32*>(w.rows_ + C::row_buffers(P.levels) * C::kRowBytes) + (size_t)w.group() * N;
+  w.tw_ = twl;
+  w.twg_ = tw;
+  const size_t sample = blockIdx.x;  // grid = batch
+  const size_t ggsw_elems = (size_t)(K + 1) * P.levels * (K + 1) * N;  // 2 parts x N/2 elements per polynomial
+  multibit_rotate_team_wide<F, LOGN, K, LEVELS, wide_ring_rows<LOGN, K, LEVELS>()>(
+      w, P, lwe_in + sample * (P.n + 1), tv + sample * tv_stride, bundles + sample * groups * ggsw_elems, groups,
+      glwe_out ? glwe_out + sample * (size_t)(K + 1) * N : nullptr,
+      lwe_extracted ? lwe_extracted + sample * ((size_t)K * N + 1) : nullptr);
+}
+
 // unrolled blind rotation (two key bits per step, pbs_wave.h::blind_rotate_bmmp_team); offered where a
 // lane holds 8 elements per array and one wave owns a polynomial: N = 512
 constexpr int kBmmpMinWaves = 3;
@@ -1585,6 +1656,83 @@ hipError_t launch_blind_rotate_wide(hipStream_t s, const PbsParams& P, const typ
   }
 }
 
+// Multi-bit blind rotation (multibit.h): offered exactly where the wide team is.  0: offered; else launch::kMultibitNo*
+template <class F, int LOGN, int K>
+int multibit_refusal_of(const PbsParams& P) {
+  if constexpr (F::kLogShrink != 1 || F::kParts != 2) {
+    return launch::kMultibitNoBackend;
+  } else if constexpr (!wide_shape_ok<F, LOGN, K>()) {
+    return launch::kMultibitNoRing;
+  } else {
+    return WideCfg<F, LOGN, K>::lds(P.levels) > (size_t)160 * 1024 ? launch::kMultibitNoLds : 0;
+  }
+}
+
+template <class F, int LOGN, int K>
+hipError_t launch_multibit_bundle(hipStream_t s, const PbsParams& P, const void* tw_v, const u32* key, u32 g, const u32* lwe_in,
+                                  size_t batch, void* bundles_v) {
+  if constexpr (!wide_shape_ok<F, LOGN, K>()) {
+    return hipErrorInvalidValue;
+  } else {
+    constexpr int N = 1 << LOGN;
+    constexpr int waves = 4;  // polynomials per 256-thread workgroup
+    const size_t lds = twiddle_bytes<F, LOGN>() + (size_t)N * 8 * waves;
+    auto tw = static_cast<const typename F::elem*>(tw_v);
+    auto bundles = static_cast<typename F::elem*>(bundles_v);
+    const u32 groups = multibit_groups(P.n, g);
+    const u32 ggsw_polys = (K + 1) * P.levels * (K + 1);
+    const size_t polys = (size_t)groups * ggsw_polys;
+    if (polys > (size_t)0x7FFFFFFF || batch > 65535) return hipErrorInvalidValue;
+    auto launch = [&](auto g_c) -> hipError_t {
+      constexpr int GBITS = decltype(g_c)::value;
+      auto kern = multibit_bundle_kernel<F, LOGN, GBITS>;
+      static std::atomic<unsigned long long> lds_done{0};
+      hipError_t e = allow_lds(kern, lds, lds_done);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(kern, dim3((unsigned)((polys + waves - 1) / waves), (unsigned)batch), dim3(256), lds, s, tw, key, lwe_in, P.n,
+                         groups, ggsw_polys, bundles, F::n_inv(LOGN - F::kLogShrink), key_layout_e<F, LOGN, K>());
+      return hipGetLastError();
+    };
+    switch (g) {
+      case 2: return launch(IntC<2>{});
+      case 3: return launch(IntC<3>{});
+      case 4: return launch(IntC<4>{});
+      default: return hipErrorInvalidValue;
+    }
+  }
+}
+
+template <class F, int LOGN, int K>
+hipError_t launch_multibit_rotate(hipStream_t s, const PbsParams& P, const void* tw_v, const u32* lwe_in, size_t batch, const u32* tv,
+                                  size_t tv_stride, const void* bundles_v, u32 groups, u32* glwe_out, u32* lwe_extracted) {
+  if constexpr (!wide_shape_ok<F, LOGN, K>()) {
+    return hipErrorInvalidValue;
+  } else {
+    using W = WideCfg<F, LOGN, K>;
+    if (W::lds(P.levels) > (size_t)160 * 1024) return hipErrorInvalidValue;
+    auto tw = static_cast<const typename F::elem*>(tw_v);
+    auto bundles = static_cast<const typename F::elem*>(bundles_v);
+    // the level counts with a key-ring instantiation, as launch_blind_rotate_wide picks them
+    auto launch = [&](auto levels_c) -> hipError_t {
+      constexpr int LEVELS = decltype(levels_c)::value;
+      auto kern = multibit_rotate_wide_kernel<F, LOGN, K, LEVELS>;
+      static std::atomic<unsigned long long> lds_done{0};
+      hipError_t e = allow_lds(kern, (size_t)160 * 1024, lds_done);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(W::kThreads), W::lds(P.levels), s, P, tw, lwe_in, tv, tv_stride, bundles,
+                         groups, glwe_out, lwe_extracted);
+      return hipGetLastError();
+    };
+    switch (P.levels) {
+      case 2: return launch(IntC<2>{});
+      case 3: return launch(IntC<3>{});
+      case 4: return launch(IntC<4>{});
+      case 6: return launch(IntC<6>{});
+      default: return launch(IntC<0>{});
+    }
+  }
+}
+
 template <class RK, class F, int LOGN, int K>
 hipError_t plan_blind_rotate_with(const PbsParams& P, size_t batch, bool can_park, bool have_side, launch::BlindRotatePlanInfo* out, int shape) {
   {
@@ -2054,6 +2202,23 @@ int samples_per_team(int field, u32 log_n, u32 k) {
 hipError_t bsk_prepare(hipStream_t s, int field, u32 log_n, u32 k, const void* tw, const u32* polys,
                        size_t poly_count, void* spectra) {
   TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN(log_n, (launch_bsk_prepare<FF, LL>(s, tw, polys, poly_count, spectra, k))));
+}
+
+hipError_t multibit_refusal(int field, const PbsParams& P, int* why) {
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (*why = multibit_refusal_of<FF, LL, KK>(P), hipSuccess)));
+}
+
+hipError_t multibit_bundle(hipStream_t s, int field, const PbsParams& P, const void* tw, const u32* key, u32 g, const u32* lwe_in,
+                           size_t batch, void* bundles) {
+  if (batch == 0) return hipErrorInvalidValue;
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (launch_multibit_bundle<FF, LL, KK>(s, P, tw, key, g, lwe_in, batch, bundles))));
+}
+
+hipError_t multibit_rotate(hipStream_t s, int field, const PbsParams& P, const void* tw, const u32* lwe_in, size_t batch, const u32* tv,
+                           size_t tv_stride, const void* bundles, u32 groups, u32* glwe_out, u32* lwe_extracted) {
+  if (batch == 0 || batch > 0x7FFFFFFFull || groups == 0) return hipErrorInvalidValue;
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (launch_multibit_rotate<FF, LL, KK>(s, P, tw, lwe_in, batch, tv, tv_stride,
+                                                                                                 bundles, groups, glwe_out, lwe_extracted))));
 }
 
 hipError_t blind_rotate(hipStream_t s, int field, const PbsParams& P, const void* tw,

@@ -7,6 +7,7 @@
 #include "ks_matrix.h"
 #include "lwe_extract.h"
 #include "multi_value.h"
+#include "multibit.h"
 #include "pbs_wave.h"
 
 namespace tfhe {
@@ -75,6 +76,20 @@ bool field_supported_bmmp(int field);  // Goldilocks and fp64-p49: the fields wh
 hipError_t blind_rotate_bmmp(hipStream_t s, int field, const PbsParams& P, const void* tw,
                              const u32* lwe_in, size_t batch, const u32* tv, size_t tv_stride,
                              const void* bsk, u32* glwe_out, u32* lwe_extracted);
+
+// ---- multi-bit blind rotation (multibit.h): g key bits per external product, offered where the wide team is.
+// *why = 0 where (field, P) is offered, else which of its conditions fails
+constexpr int kMultibitNoBackend = 1, kMultibitNoRing = 2, kMultibitNoLds = 3;  // not the complex transform / N > 1024 / the row buffers
+hipError_t multibit_refusal(int field, const PbsParams& P, int* why);
+// bundles [batch][ceil(n / g)] prepared GGSWs (the layout of a bootstrapping key for P.k) from the raw key
+// [ceil(n / g)][2^g - 1][(k+1) l][k+1][N] and lwe_in [batch][n+1]: one launch of (polynomials, batch) workgroups.
+// hipErrorInvalidValue: g outside {2, 3, 4}, an empty batch, one beyond 65535, a shape that is not offered
+hipError_t multibit_bundle(hipStream_t s, int field, const PbsParams& P, const void* tw, const u32* key, u32 g, const u32* lwe_in,
+                           size_t batch, void* bundles);
+// the rotation over `groups` bundles per sample, one wide team per sample; tv, tv_stride, P.acc_glwe / P.acc_offset and
+// the optional outputs as for blind_rotate
+hipError_t multibit_rotate(hipStream_t s, int field, const PbsParams& P, const void* tw, const u32* lwe_in, size_t batch, const u32* tv,
+                           size_t tv_stride, const void* bundles, u32 groups, u32* glwe_out, u32* lwe_extracted);
 
 // out = external_product(ggsw[g], glwe[b]) (+ ct0 for the CMUX form).
 //   cmux_ct0 == nullptr : src = glwe_in
