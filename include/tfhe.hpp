@@ -924,6 +924,30 @@ inline GlweCiphertext multibit_blind_rotate(Engine& e, const MultibitKey& key, c
   e.check(tfhe_multibit_blind_rotate_batch(e.raw(), key.raw(), ct.data.data(), 1, test_vector.data(), 1, nullptr, 0, out.data.data(), nullptr));
   return out;
 }
+// ---- block-binary blind rotation (tfhe_hip.h states the operation; first device only) ----
+// `block` key bits per decomposition on the engine's loaded, ordinary bootstrapping key: meaningful for an LWE secret with
+// at most one 1 per block of `block` consecutive bits.  TFHE_ERR_EXACTNESS above block_rotate_max_block(),
+// TFHE_ERR_UNSUPPORTED outside the fp64-fft backend at N = 512 / 1024.
+inline unsigned block_rotate_max_block(Engine& e) {
+  unsigned b = 0;
+  e.check(tfhe_block_rotate_max_block(e.raw(), &b));
+  return b;
+}
+// the block-binary bootstrap of ONE ciphertext at the engine's boundary dimension against a clear test vector [N]
+inline LweCiphertext block_bootstrap(Engine& e, const LweCiphertext& ct, unsigned block, const std::vector<uint32_t>& test_vector) {
+  if (test_vector.size() != e.params().degree()) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "test vector [N]");
+  LweCiphertext out{std::vector<uint32_t>(ct.data.size())};
+  e.check(tfhe_block_bootstrap_batch(e.raw(), ct.data.data(), 1, block, test_vector.data(), 1, out.data.data()));
+  return out;
+}
+// the block-binary blind rotation of ONE ciphertext of n + 1 words from a clear test vector [N] -> the GLWE accumulator
+inline GlweCiphertext block_blind_rotate(Engine& e, const LweCiphertext& ct, unsigned block, const std::vector<uint32_t>& test_vector) {
+  const TfheParams& p = e.params();
+  if (ct.data.size() != size_t(p.lwe_dimension) + 1 || test_vector.size() != p.degree()) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "LWE length / test vector [N]");
+  GlweCiphertext out{std::vector<uint32_t>(size_t(p.glwe_dimension + 1) * p.degree())};
+  e.check(tfhe_block_blind_rotate_batch(e.raw(), ct.data.data(), 1, block, test_vector.data(), 1, nullptr, 0, out.data.data(), nullptr));
+  return out;
+}
 // ---- multi-value bootstrapping (tfhe_hip.h states the operations; first device only) ----
 // every lookup table of `luts` (tables x B un-encoded values, row-major) of ONE ciphertext of n + 1 words from one blind
 // rotation (the reference's bootstrap order, like the neighbouring wrappers) -> one ciphertext per table

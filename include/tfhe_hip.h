@@ -401,6 +401,75 @@ int tfhe_multibit_bootstrap_batch_device(tfhe_context *ctx, const tfhe_multibit_
                                          const uint32_t *test_vector_poly, size_t tv_count, uint32_t *lwe_out);
 int tfhe_multibit_last_kernel_ms(tfhe_context *ctx, float *bundle_ms, float *rotate_ms);
 
+/* ---- block-binary blind rotation (no reference counterpart): b key bits per decomposition, for large batches ----------
+ * The blind rotation of Lee, Min, Seo and Song, "Faster TFHE Bootstrapping with Block Binary Keys" (2023).  The LWE secret
+ * is drawn with AT MOST ONE 1 per block of b consecutive bits.  Over the bits j of one block that makes
+ *   X^(sum_j a~_j s_j) = 1 + sum_j s_j (X^(a~_j) - 1),
+ * so the b external products of a block are all taken of the SAME accumulator: they share one rounding, one digit chain
+ * and one set of forward transforms, and -- the monomial factors being pointwise in the transform domain -- one
+ * accumulator set, one pair of inverse transforms and one lift.  The key is the context's loaded, ORDINARY bootstrapping
+ * key (n GGSWs of the bits, the reference's layout, tfhe_generate_keys / tfhe_load_bootstrapping_key): only the secret's
+ * distribution and the rotation's formula change.  No key type, no per-sample workspace.  All arithmetic is mod 2^32.
+ * Whether a block-binary secret of dimension n reaches a given security level is not this library's claim: the paper
+ * treats it, and choosing n is the caller's business.
+ *
+ * Definition.  block = b >= 2.  Block i covers key bits b*i .. min(n, b*i + b) - 1 (the last block may be ragged).
+ * a~_m = switch_modulus_2n(a_m) and b~ are the bootstrap's own; acc_0 is the bootstrap's, X^(-b~) * (0, .., 0, tv << tv_shift),
+ * or the rotated GLWE accumulator of tfhe_blind_rotate_glwe_batch (acc_in, rotation_offset), as
+ * tfhe_multibit_blind_rotate_batch takes them.  For every block in turn:
+ *   P_j  = external_product(BSK_j, acc)           ggsw.rs:132-161 with the PBS decomposer, literal or aligned as the context
+ *                                                 is set; every P_j of a block from the SAME acc
+ *   acc <- acc + sum_j ( X^(a~_j) * P_j - P_j )    the negacyclic shift of utils.rs:183-207, wrapping u32
+ * Output: the GLWE accumulator and / or sample_extract(., 0).  The words are, byte for byte, tfhe_external_product_batch,
+ * tfhe_glwe_mul_monomial_batch and wrapping adds composed that way.  The bootstrap form adds the context's key switch after
+ * the rotation or before it, as tfhe_context_set_bootstrap_order says.
+ *
+ * This is NOT the reference's bootstrap(): the plaintext is the same (for a block-binary secret), the ciphertext bits
+ * differ.  With b = 1 it would still not be the ordinary CMUX, which decomposes the rotated difference X^a~ acc - acc, not
+ * acc; b = 1 is refused.
+ *
+ * Identity.  Under noise-free GGSWs and a block-binary secret, phi_S(acc_final) = X^(rho - b~) * phi_S(acc_0),
+ * rho = sum_m a~_m s_m, within ceil(n/b) * 2 * (1 + k*N) * 2^(ig-1) per coefficient (ig ignored bits; exactly with none): a
+ * step rounds every word of acc once, by at most 2^(ig-1), and the step's message X^rho_i - 1 is two monomials.  A secret
+ * with two 1s in one block does NOT satisfy it.
+ *
+ * Noise.  Per key bit the external product's variance counts twice, for (X^a~ - 1); per block the decomposer's rounding
+ * counts twice.  In units of the 32-bit torus:
+ *   s_bb^2 = 2 n (k+1) l N (B^2/12 + 1/6) (sigma_glwe 2^32)^2  +  2 ceil(n/b) (1 + k N / 2) 2^(2 ig_pbs) / 12
+ * about twice the ordinary rotation's variance (against 3x - 7.5x for the multi-bit rotation).  The modulus-switch and
+ * key-switch terms are the bootstrap's.
+ *
+ * Exactness.  The b (k+1) l products of a block are summed in the transform domain, each with a factor of modulus <= 2:
+ * FftField::block_error_bound (csrc/field_fft.h) below 1/4 admits b.  tfhe_block_rotate_max_block returns the largest
+ * admitted b (6 at k = 1, N = 1024, B = 2^7, l = 3), or 0 with the reason in tfhe_last_error and the status that says why;
+ * a block above it is TFHE_ERR_EXACTNESS and names the largest admitted one.
+ *
+ * Offered in the fp64-fft backend with one wave per polynomial, N = 512 and N = 1024, on an ordinary key:
+ * TFHE_ERR_UNSUPPORTED with the reason for the prime-field backends, N = 2048 and a BMMP-loaded key.  block < 2, a NULL
+ * pointer, an empty batch, both or neither of test_vector_poly / acc_in: TFHE_ERR_INVALID_ARGUMENT.  No loaded key:
+ * TFHE_ERR_NO_KEY.
+ *
+ * One team of k+1 waves rotates one sample at EVERY batch size: the batches the ordinary rotation gives to the wide team
+ * or to the pair kernel run on this team kernel too.  Large batches go out as the ordinary rotation's do -- chunks,
+ * segments over slices of the key with the accumulators parked in the workspace of tfhe_context_reserve, two streams --
+ * with every segment a whole number of blocks.  After tfhe_context_reserve the _device forms allocate nothing, stay on the
+ * context's stream and can be captured.
+ *
+ * lwe_in [batch][n+1] (the bootstrap form: the context's boundary dimension).  Pass EITHER test_vector_poly [tv_count][N]
+ * (clear, tv_count 1 or batch) OR acc_in [tv_count][k+1][N] with rotation_offset < 2N; the other is NULL.  Pass glwe_out
+ * [batch][k+1][N], lwe_extracted [batch][k*N+1] or both. */
+int tfhe_block_rotate_max_block(tfhe_context *ctx, unsigned *max_block);
+int tfhe_block_blind_rotate_batch(tfhe_context *ctx, const uint32_t *lwe_in, size_t batch, unsigned block,
+                                  const uint32_t *test_vector_poly, size_t tv_count, const uint32_t *acc_in,
+                                  size_t rotation_offset, uint32_t *glwe_out, uint32_t *lwe_extracted);
+int tfhe_block_blind_rotate_batch_device(tfhe_context *ctx, const uint32_t *lwe_in, size_t batch, unsigned block,
+                                         const uint32_t *test_vector_poly, size_t tv_count, const uint32_t *acc_in,
+                                         size_t rotation_offset, uint32_t *glwe_out, uint32_t *lwe_extracted);
+int tfhe_block_bootstrap_batch(tfhe_context *ctx, const uint32_t *lwe_in, size_t batch, unsigned block,
+                               const uint32_t *test_vector_poly, size_t tv_count, uint32_t *lwe_out);
+int tfhe_block_bootstrap_batch_device(tfhe_context *ctx, const uint32_t *lwe_in, size_t batch, unsigned block,
+                                      const uint32_t *test_vector_poly, size_t tv_count, uint32_t *lwe_out);
+
 /* ---- tree LUT: a function of d digits of log_p bits each (no reference counterpart) ---------------------------------
  * The tree-based bootstrap of Guimaraes, Borin and Aranha (2021).  Inputs and output are ordinary LWE ciphertexts at
  * the bootstrap boundary, so it composes with gates, gate graphs and itself; its noise does not depend on the table

@@ -119,6 +119,9 @@ extern "C" {
     fn tfhe_multibit_key_destroy(key: *mut TfheMultibitKey);
     fn tfhe_multibit_bootstrap_batch(ctx: *mut TfheContext, key: *const TfheMultibitKey, lwe_in: *const u32, batch: usize,
                                      test_vector_poly: *const u32, tv_count: usize, lwe_out: *mut u32) -> c_int;
+    fn tfhe_block_rotate_max_block(ctx: *mut TfheContext, max_block: *mut c_uint) -> c_int;
+    fn tfhe_block_bootstrap_batch(ctx: *mut TfheContext, lwe_in: *const u32, batch: usize, block: c_uint,
+                                  test_vector_poly: *const u32, tv_count: usize, lwe_out: *mut u32) -> c_int;
     fn tfhe_glwe_automorphism_batch(ctx: *mut TfheContext, glwe_in: *const u32, batch: usize, t: usize,
                                     key: *const TfheGlweSwitchKey, add_input: c_int, glwe_out: *mut u32) -> c_int;
     fn tfhe_cmux_batch(ctx: *mut TfheContext, ggsw: *const u32, ggsw_count: usize, ct0: *const u32,
@@ -714,6 +717,25 @@ pub fn multibit_bootstrap_batch(bk: &GpuBootstrappingKey, key: &MultibitKey, lwe
         tfhe_multibit_bootstrap_batch(bk.ctx, key.raw, lwe_ciphertexts.as_slice().unwrap().as_ptr(), lwe_ciphertexts.nrows(),
                                       test_vector_poly.as_slice().unwrap().as_ptr(), 1, out.as_slice_mut().unwrap().as_mut_ptr())
     }, "multibit_bootstrap_batch");
+    out
+}
+
+/// The largest block the exactness rule admits for the block-binary blind rotation on this key's context (tfhe_hip.h).
+pub fn block_rotate_max_block(bk: &GpuBootstrappingKey) -> u32 {
+    let mut b: c_uint = 0;
+    check(bk.ctx, unsafe { tfhe_block_rotate_max_block(bk.ctx, &mut b) }, "block_rotate_max_block");
+    b as u32
+}
+
+/// The block-binary bootstrap (tfhe_hip.h, "block-binary blind rotation"): `block` key bits per decomposition on the loaded,
+/// ordinary key -- for LWE secrets with at most one 1 per block of `block` consecutive bits.  One shared test vector (N).
+pub fn block_bootstrap_batch(bk: &GpuBootstrappingKey, lwe_ciphertexts: &Array2<u32>, block: u32, test_vector_poly: &Array1<u32>) -> Array2<u32> {
+    assert!(test_vector_poly.len() == 1usize << bk.params.glwe_poly_degree, "block_bootstrap_batch: test vector (N)");
+    let mut out = Array2::<u32>::zeros(lwe_ciphertexts.raw_dim());
+    check(bk.ctx, unsafe {
+        tfhe_block_bootstrap_batch(bk.ctx, lwe_ciphertexts.as_slice().unwrap().as_ptr(), lwe_ciphertexts.nrows(), block as c_uint,
+                                   test_vector_poly.as_slice().unwrap().as_ptr(), 1, out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "block_bootstrap_batch");
     out
 }
 

@@ -373,6 +373,49 @@ def multibit_noise_variance(params: TfheParams, g: int, aligned: bool = True) ->
     return total
 
 
+def block_binary_key(n: int, block: int, rng=None) -> np.ndarray:
+    """An LWE secret [n] for the block-binary blind rotation (include/tfhe_hip.h, "block-binary blind rotation"): at most
+    one 1 per block of `block` consecutive bits -- per block, uniform over "no bit" and each single bit of the block (the
+    last block may be shorter).  The OS CSPRNG unless the test hook `rng=` is given."""
+    if block < 2 or n < 1:
+        raise _invalid("block_binary_key: n >= 1 and block >= 2")
+    rng = rng if rng is not None else SystemRng()
+    sk = np.zeros(n, dtype=np.uint32)
+    for first in range(0, n, block):
+        size = min(block, n - first)
+        span = 1 << size.bit_length()  # a power of two above size: draw and reject, no modulo bias
+        pick = span
+        while pick > size:
+            pick = int(rng.integers(0, span))
+        if pick:
+            sk[first + pick - 1] = 1
+    return sk
+
+
+def is_block_binary(sk, block: int) -> bool:
+    """True if sk is binary with at most one 1 in every block of `block` consecutive bits"""
+    s = np.asarray(sk).reshape(-1)
+    if block < 1 or not np.isin(s, (0, 1)).all():
+        return False
+    return all(int(s[first:first + block].sum()) <= 1 for first in range(0, s.size, block))
+
+
+def block_noise_variance(params: TfheParams, block: int, aligned: bool = True) -> float:
+    """s_bb^2 of include/tfhe_hip.h ("block-binary blind rotation", Noise): the variance a block-binary blind rotation with
+    `block` key bits per decomposition adds to a coefficient, in units of the 32-bit torus (squared).  The modulus-switch
+    and key-switch terms of a bootstrap are the ordinary bootstrap's and not included."""
+    if block < 2:
+        raise _invalid("block_noise_variance: block must be at least 2")
+    k, big_n, n = params.k, params.N, params.n
+    lb, levels = params.pbs_decomposer.log_base, params.pbs_decomposer.levels
+    top = 32 if aligned else lb * (32 // lb)
+    ignored = top - lb * levels
+    sigma = params.glwe_std_dev * 2.0 ** 32
+    products = 2.0 * n * (k + 1) * levels * big_n * ((2.0 ** lb) ** 2 / 12.0 + 1.0 / 6.0) * sigma * sigma
+    rounding = 2.0 * (-(-n // block)) * (1.0 + k * big_n / 2.0) * 2.0 ** (2 * ignored) / 12.0
+    return products + rounding
+
+
 def construct_identity_test_vector(params: TfheParams) -> np.ndarray:
     """test_vector.rs:23-35"""
     return construct_test_from_lut(params, np.arange(1 << params.log_p, dtype=np.uint32))
@@ -1285,6 +1328,74 @@ class Context:
         a, b = C.c_float(), C.c_float()
         self._check(lib().tfhe_multibit_last_kernel_ms(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    # -- block-binary blind rotation: b key bits per decomposition on the loaded key (include/tfhe_hip.h states it) --
+    def block_rotate_max_block(self) -> int:
+        """the largest block the exactness rule admits for this context; TfheError with the reason (TFHE_ERR_UNSUPPORTED,
+        TFHE_ERR_EXACTNESS) where the block-binary rotation is not offered"""
+        b = C.c_uint()
+        self._check(lib().tfhe_block_rotate_max_block(self._h, C.byref(b)))
+        return int(b.value)
+
+    def block_blind_rotate(self, lwe_in, block: int, test_vector_poly=None, acc_in=None, rotation_offset: int = 0,
+                           glwe_out=True, lwe_extracted=False, out=None):
+        """The block-binary blind rotation of lwe_in [batch][n+1] with `block` key bits per decomposition, on the loaded
+        (ordinary) bootstrapping key -- meaningful for secrets with at most one 1 per block (block_binary_key) -- from clear
+        test vectors ([N] or [1 or batch][N]) or from GLWE accumulators acc_in ([k+1][N] or [1 or batch][k+1][N], with
+        rotation_offset).  glwe_out / lwe_extracted: False (not wanted), True (a new array) or, in the device form, the
+        tensor to write; `out`: the device form's tensor for the one output that is asked for with True -> the GLWE
+        accumulators [batch][k+1][N], their sample extracts [batch][k N + 1], or the pair of them.  numpy: host form,
+        blocks.  torch: on torch's current stream, after reserve() enqueues only."""
+        p = self.params
+        what = "block_blind_rotate"
+        if (test_vector_poly is None) == (acc_in is None):
+            raise _invalid(f"{what}: pass either test_vector_poly or acc_in")
+        if glwe_out is False and lwe_extracted is False:
+            raise _invalid(f"{what}: ask for glwe_out, lwe_extracted or both")
+        if out is not None:
+            if (glwe_out is True) == (lwe_extracted is True):
+                raise _invalid(f"{what}: out= names the one output asked for with True")
+            if glwe_out is True:
+                glwe_out = out
+            else:
+                lwe_extracted = out
+        lwe, dev = self._lwe_rows(what, "lwe_in", lwe_in, p.n + 1)
+        batch = int(lwe.shape[0])
+        tv = acc = None
+        if acc_in is None:
+            tv, count = self._test_vectors(what, test_vector_poly, batch, dev, lwe)
+            if rotation_offset:
+                raise _invalid(f"{what}: rotation_offset goes with acc_in")
+        else:
+            if _is_torch(acc_in) != dev:
+                raise _invalid(f"{what}: lwe_in and acc_in must both be numpy or both torch")
+            acc = acc_in if dev else _np(acc_in)
+            if len(acc.shape) != 3:
+                acc = _lead(acc, dev)
+            _check_u32(what, "acc_in", acc, dev, (None, p.k + 1, p.N), lwe if dev else None)
+            count = int(acc.shape[0])
+            if count not in (1, batch):
+                raise _invalid(f"{what}: acc_in [1 or {batch}][{p.k + 1}][{p.N}] expected, got {tuple(acc.shape)}")
+            if not 0 <= int(rotation_offset) < 2 * p.N:
+                raise _invalid(f"{what}: rotation_offset must be in [0, 2N = {2 * p.N})")
+        want = lambda o, shape: None if o is False else _result(what, dev, None if o is True else o, shape, lwe)  # noqa: E731
+        glwe = want(glwe_out, (batch, p.k + 1, p.N))
+        ext = want(lwe_extracted, (batch, p.big_n + 1))
+        self._call("tfhe_block_blind_rotate_batch", dev, _ptr(lwe), C.c_size_t(batch), C.c_uint(int(block)), _ptr(tv), C.c_size_t(count),
+                   _ptr(acc), C.c_size_t(int(rotation_offset)), _ptr(glwe), _ptr(ext))
+        return glwe if ext is None else ext if glwe is None else (glwe, ext)
+
+    def block_bootstrap(self, lwe_in, block: int, test_vector_poly, out=None):
+        """block_blind_rotate + sample extraction at 0 + the context's key switch, in the context's bootstrap order:
+        [batch][io_dim+1] -> [batch][io_dim+1].  For a block-binary secret the same plaintexts as bootstrap(), other
+        ciphertext bits."""
+        what = "block_bootstrap"
+        lwe, dev = self._lwe_rows(what, "lwe_in", lwe_in, self.io_dim + 1)
+        batch = int(lwe.shape[0])
+        tv, count = self._test_vectors(what, test_vector_poly, batch, dev, lwe)
+        res = _result(what, dev, out, (batch, self.io_dim + 1), lwe)
+        self._call("tfhe_block_bootstrap_batch", dev, _ptr(lwe), C.c_size_t(batch), C.c_uint(int(block)), _ptr(tv), C.c_size_t(count), _ptr(res))
+        return res
 
     def external_product(self, ggsw, glwe) -> np.ndarray:
         """external_product(): ggsw.rs:132-161.  ggsw [R][k+1][N] (shared) or [batch][R][k+1][N]."""

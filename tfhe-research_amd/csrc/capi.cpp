@@ -363,6 +363,16 @@ int upload_twiddles(tfhe_context* ctx) {
   return TFHE_OK;
 }
 
+// the block-binary rotation's factor table (block_rotate.h::fill_block_roots), where that rotation is offered
+int upload_block_roots(tfhe_context* ctx) {
+  if (!launch::block_rotate_supported(ctx->field, ctx->params.glwe_poly_degree, ctx->params.glwe_dimension)) return TFHE_OK;
+  std::vector<cplx> roots(block_root_words((int)ctx->params.glwe_poly_degree));
+  fill_block_roots((int)ctx->params.glwe_poly_degree, roots.data());
+  TFHE_TRY(ctx->d_block_roots.grow(ctx, roots.size() * sizeof(cplx)));
+  HIP_TRY(ctx, hipMemcpy(ctx->d_block_roots.as(), roots.data(), roots.size() * sizeof(cplx), hipMemcpyHostToDevice));
+  return TFHE_OK;
+}
+
 // The prepared bootstrapping key for `ggsws` GGSWs (reallocated when the other kind of key was loaded before: its
 // footprint follows the key), the key-switching key and, where it is wanted, its matrix-path layout (allocated once:
 // their sizes are the context's).  The caller has taken the old key out of service (have_key) before.
@@ -592,6 +602,7 @@ int tfhe_context_create_with_backend(const tfhe_params* params, int device, int 
        : field == launch::kFieldFp49 ? upload_twiddles<Fp49Field>(ctx)
        : field == launch::kFieldFft  ? upload_twiddles<FftField>(ctx)
                                      : upload_twiddles<GlField>(ctx);  // both Goldilocks fields share the table
+  if (st == TFHE_OK) st = upload_block_roots(ctx);
   if (st == TFHE_OK) st = ctx->d_queue.grow(ctx, 2 * sizeof(unsigned long long));
   if (st != TFHE_OK) {
     std::fprintf(stderr, "tfhe_context_create: twiddles / work queue: %s\n", ctx->last_error.c_str());
@@ -2917,6 +2928,147 @@ int tfhe_multibit_bootstrap_batch(tfhe_context* ctx, const tfhe_multibit_key* ke
   TFHE_TRY(upload(ctx, ctx->d_lwe_in.as<u32>(), lwe_in, batch * io_words(ctx)));
   TFHE_TRY(upload(ctx, ctx->d_tv.as<u32>(), test_vector_poly, tv_count * ctx->N));
   TFHE_TRY(tfhe_multibit_bootstrap_batch_device(ctx, key, ctx->d_lwe_in.as<u32>(), batch, ctx->d_tv.as<u32>(), tv_count, ctx->d_lwe_out.as<u32>()));
+  return download_and_wait(ctx, lwe_out, ctx->d_lwe_out.as<u32>(), batch * io_words(ctx));
+}
+
+// ---------------------------------------------------------------------------------- block-binary blind rotation
+// tfhe_hip.h states the operation, block_rotate.h the step: `block` key bits per decomposition on the loaded, ordinary
+// key.  The workspace is tfhe_context_reserve's: the parked accumulators and the LWE buffers.
+namespace {
+
+// the largest block the exactness rule admits (FftField::block_error_bound below kMaxError, b R rows within kMaxRows),
+// 0 with the reason where the rotation is not offered
+int block_rotate_max_block(tfhe_context* ctx, unsigned* max_block) {
+  *max_block = 0;
+  const tfhe_params& p = ctx->params;
+  if (ctx->field != launch::kFieldFft)
+    return fail(ctx, TFHE_ERR_UNSUPPORTED, std::string("the block-binary blind rotation is offered in the fp64-fft backend only; this context uses ") +
+                                               tfhe_context_backend(ctx));
+  if (!launch::block_rotate_supported(ctx->field, p.glwe_poly_degree, p.glwe_dimension))
+    return fail(ctx, TFHE_ERR_UNSUPPORTED, "the block-binary blind rotation is offered with one wave per polynomial, N = 512 and N = 1024; this context has N = " +
+                                               std::to_string(ctx->N));
+  unsigned b = 1;
+  while ((b + 1) * ctx->R <= (unsigned)FftField::kMaxRows &&
+         FftField::block_error_bound((int)p.glwe_poly_degree, (int)ctx->R, (int)p.pbs_decomposer.log_base, (int)(b + 1)) < FftField::kMaxError)
+    ++b;
+  *max_block = b >= 2 ? b : 0;
+  if (b < 2) {
+    char buf[256];
+    std::snprintf(buf, sizeof buf, "fp64-fft: rounding bound %.4g of a block of 2 key bits of %u rows in base 2^%u is not below %.4g",
+                  FftField::block_error_bound((int)p.glwe_poly_degree, (int)ctx->R, (int)p.pbs_decomposer.log_base, 2), ctx->R,
+                  p.pbs_decomposer.log_base, FftField::kMaxError);
+    return fail(ctx, TFHE_ERR_EXACTNESS, buf);
+  }
+  return TFHE_OK;
+}
+
+int check_block(tfhe_context* ctx, unsigned block) {
+  if (block < 2) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "block must be at least 2 key bits, got " + std::to_string(block));
+  if (ctx->have_key && ctx->bmmp)
+    return fail(ctx, TFHE_ERR_UNSUPPORTED, "the block-binary blind rotation needs an ordinary bootstrapping key; a BMMP key is loaded");
+  unsigned max_block = 0;
+  TFHE_TRY(block_rotate_max_block(ctx, &max_block));
+  if (block > max_block) {
+    char buf[256];
+    std::snprintf(buf, sizeof buf, "fp64-fft: rounding bound %.4g of a block of %u key bits is not below %.4g; the largest admitted block is %u",
+                  FftField::block_error_bound((int)ctx->params.glwe_poly_degree, (int)ctx->R, (int)ctx->params.pbs_decomposer.log_base, (int)block),
+                  block, FftField::kMaxError, max_block);
+    return fail(ctx, TFHE_ERR_EXACTNESS, buf);
+  }
+  return TFHE_OK;
+}
+
+int check_block_rotate_args(tfhe_context* ctx, const void* lwe_in, size_t batch, unsigned block, const void* tv, size_t tv_count,
+                            const void* acc_in, size_t rotation_offset, const void* glwe_out, const void* lwe_extracted) {
+  if (!lwe_in) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null pointer");
+  if ((tv != nullptr) == (acc_in != nullptr))
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "pass either test_vector_poly or acc_in, not both and not neither");
+  if (!glwe_out && !lwe_extracted) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "pass glwe_out, lwe_extracted or both");
+  TFHE_TRY(check_batch(ctx, {lwe_in}, batch, tv_count, acc_in ? "acc_count" : "tv_count"));
+  if (acc_in && rotation_offset >= 2 * (size_t)ctx->N)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "rotation_offset must be below 2N = " + std::to_string(2 * (size_t)ctx->N));
+  if (!acc_in && rotation_offset != 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "rotation_offset goes with acc_in");
+  TFHE_TRY(check_block(ctx, block));
+  if (!ctx->have_key) return fail(ctx, TFHE_ERR_NO_KEY, "no bootstrapping key loaded");
+  return TFHE_OK;
+}
+
+int check_block_bootstrap_args(tfhe_context* ctx, const void* lwe_in, size_t batch, unsigned block, const void* tv, size_t tv_count,
+                               const void* lwe_out) {
+  TFHE_TRY(check_batch(ctx, {lwe_in, tv, lwe_out}, batch, tv_count, "tv_count"));
+  TFHE_TRY(check_block(ctx, block));
+  if (!ctx->have_key) return fail(ctx, TFHE_ERR_NO_KEY, "no bootstrapping key loaded");
+  return TFHE_OK;
+}
+
+hipError_t enqueue_block_rotate(tfhe_context* ctx, const u32* lwe_in, size_t batch, unsigned block, const u32* src, size_t count, bool glwe,
+                                u32 offset, u32* glwe_out, u32* lwe_extracted) {
+  // accumulators between the launches of a segmented rotation: the caller's output, or the workspace (sized by reserve)
+  u32* state = glwe_out ? glwe_out : (batch <= ctx->ws_batch ? ctx->d_glwe_c.as<u32>() : nullptr);
+  PbsParams P = ctx->pbs;
+  P.acc_glwe = glwe ? 1u : 0u;
+  P.acc_offset = offset;
+  const size_t words = glwe ? glwe_words(ctx) : (size_t)ctx->N;
+  return launch::block_rotate(ctx->stream, ctx->field, P, ctx->d_tw.as(), ctx->d_block_roots.as(), lwe_in, batch, src, count == 1 ? 0 : words,
+                              ctx->d_bsk.as(), block, glwe_out, lwe_extracted, state, &ctx->side);
+}
+
+}  // namespace
+
+int tfhe_block_rotate_max_block(tfhe_context* ctx, unsigned* max_block) {
+  if (!ctx || !max_block) return TFHE_ERR_INVALID_ARGUMENT;
+  return block_rotate_max_block(ctx, max_block);
+}
+
+int tfhe_block_blind_rotate_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, unsigned block,
+                                         const uint32_t* test_vector_poly, size_t tv_count, const uint32_t* acc_in, size_t rotation_offset,
+                                         uint32_t* glwe_out, uint32_t* lwe_extracted) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_block_rotate_args(ctx, lwe_in, batch, block, test_vector_poly, tv_count, acc_in, rotation_offset, glwe_out, lwe_extracted));
+  TFHE_TRY(span_begin(ctx, kRotationSpan));
+  HIP_TRY(ctx, enqueue_block_rotate(ctx, lwe_in, batch, block, acc_in ? acc_in : test_vector_poly, tv_count, acc_in != nullptr,
+                                    (u32)rotation_offset, glwe_out, lwe_extracted));
+  return span_end(ctx, kRotationSpan);
+}
+
+int tfhe_block_blind_rotate_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, unsigned block, const uint32_t* test_vector_poly,
+                                  size_t tv_count, const uint32_t* acc_in, size_t rotation_offset, uint32_t* glwe_out,
+                                  uint32_t* lwe_extracted) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_block_rotate_args(ctx, lwe_in, batch, block, test_vector_poly, tv_count, acc_in, rotation_offset, glwe_out, lwe_extracted));
+  if (!acc_in) TFHE_TRY(check_tv_host(ctx, test_vector_poly, tv_count * ctx->N));
+  TFHE_TRY(reserve(ctx, batch));
+  TFHE_TRY(upload(ctx, ctx->d_lwe_in.as<u32>(), lwe_in, batch * lwe_words(ctx)));
+  if (acc_in) TFHE_TRY(upload(ctx, ctx->d_glwe_a.as<u32>(), acc_in, tv_count * glwe_words(ctx)));
+  else TFHE_TRY(upload(ctx, ctx->d_tv.as<u32>(), test_vector_poly, tv_count * ctx->N));
+  TFHE_TRY(tfhe_block_blind_rotate_batch_device(ctx, ctx->d_lwe_in.as<u32>(), batch, block, acc_in ? nullptr : ctx->d_tv.as<u32>(), tv_count,
+                                                acc_in ? ctx->d_glwe_a.as<u32>() : nullptr, rotation_offset,
+                                                glwe_out ? ctx->d_glwe_b.as<u32>() : nullptr, lwe_extracted ? ctx->d_lwe_big.as<u32>() : nullptr));
+  if (glwe_out) TFHE_TRY(download(ctx, glwe_out, ctx->d_glwe_b.as<u32>(), batch * glwe_words(ctx)));
+  if (lwe_extracted) TFHE_TRY(download(ctx, lwe_extracted, ctx->d_lwe_big.as<u32>(), batch * big_lwe_words(ctx)));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return TFHE_OK;
+}
+
+int tfhe_block_bootstrap_batch_device(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, unsigned block,
+                                      const uint32_t* test_vector_poly, size_t tv_count, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_block_bootstrap_args(ctx, lwe_in, batch, block, test_vector_poly, tv_count, lwe_out));
+  TFHE_TRY(reserve(ctx, batch));  // (nothing to do after tfhe_context_reserve)
+  return enqueue_bootstrap_with(ctx, lwe_in, batch, ctx->d_lwe_big.as<u32>(), lwe_out, [&](const u32* br_in, u32* br_out) {
+    return enqueue_block_rotate(ctx, br_in, batch, block, test_vector_poly, tv_count, false, 0u, nullptr, br_out);
+  });
+}
+
+int tfhe_block_bootstrap_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch, unsigned block, const uint32_t* test_vector_poly,
+                               size_t tv_count, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_block_bootstrap_args(ctx, lwe_in, batch, block, test_vector_poly, tv_count, lwe_out));
+  TFHE_TRY(check_tv_host(ctx, test_vector_poly, tv_count * ctx->N));
+  TFHE_TRY(reserve(ctx, batch));
+  TFHE_TRY(upload(ctx, ctx->d_lwe_in.as<u32>(), lwe_in, batch * io_words(ctx)));
+  TFHE_TRY(upload(ctx, ctx->d_tv.as<u32>(), test_vector_poly, tv_count * ctx->N));
+  TFHE_TRY(tfhe_block_bootstrap_batch_device(ctx, ctx->d_lwe_in.as<u32>(), batch, block, ctx->d_tv.as<u32>(), tv_count, ctx->d_lwe_out.as<u32>()));
   return download_and_wait(ctx, lwe_out, ctx->d_lwe_out.as<u32>(), batch * io_words(ctx));
 }
 

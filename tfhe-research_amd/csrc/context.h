@@ -127,6 +127,9 @@ struct tfhe_context {
   bool tree_level0_multi_value = false;  // tfhe_context_set_tree_lut_level0
   // multi-bit blind rotation (tfhe_context_reserve_multibit): the bundles of one call, per sample ceil(n / g) prepared GGSWs
   DeviceBuffer d_mb_ws;
+  // block-binary blind rotation (block_rotate.h): the factors zeta^e - 1, e in [0, 2N); made with the context where the
+  // rotation is offered, empty elsewhere
+  DeviceBuffer d_block_roots;
   bool aligned = false;       // decomposer alignment (tfhe_context_set_decomposer_alignment)
   bool ks_first = false;      // bootstrap order (tfhe_context_set_bootstrap_order)
   int shape = 0;              // kernel shape of the blind rotation (tfhe_context_set_kernel_shape): launch::kShape*

@@ -233,6 +233,31 @@ struct FftField {
     // transforms (forward digits, forward key, inverse) + the FMA chain that accumulates r rows
     return 1.001 * (3.0 * n * eta + 1.42 * (r + 1.0) * u) * r * m * sqrt(m) * x * y;
   }
+  // The block-binary rotation (block_rotate.h) sums, before ONE lift, the b products of a block, each digit spectrum
+  // multiplied pointwise by a factor f = zeta^e - 1, |f| <= 2:  P = sum_{j < b} sum_{r <= R} (f_j o X_r) o Y_{j,r}.
+  // On top of the derivation in the header comment:
+  //   the factor     f~ is the table entry, each component correctly rounded (re in [-2, 0]: within u; im in [-1, 1]:
+  //                  within u/2): |f~ - f| <= 1.12 u.  D~ = fl(X~ f~) is a complex product of two multiplies and two
+  //                  FMAs, |fl(ab) - ab| <= sqrt 5 u |a| |b| (Brent, Percival, Zimmermann 2007; the FMA form is no worse).
+  //                  ||D~ - D||_2 <= 2 ||X~ - X||_2 + 1.12 u ||X||_2 + 2.24 u 2 ||X||_2 <= (n eta + 2.8 u) 2 M |x|:
+  //                  the forward error of a digit row with |x| doubled, plus 2.8 u.
+  //   products       a term is (f o X) o Y with ||.||_2 <= 2 M^2 |x| |y|; there are b R of them.  Forward errors:
+  //                  b R (2 n eta + 2.8 u) 2 M^2 |x| |y|.  The FMA chain over b R terms of that size: sqrt 2 u b R (b R + 1)
+  //                  2 M^2 |x| |y|.
+  //   inverse        ||z||_2 <= sqrt M b R 2 M |x| |y|, times n eta.
+  //   ==> max_j |e_j| <= (3 n eta + 2.8 u + sqrt 2 (b R + 1) u) 2 b R M^1.5 |x| |y|.
+  // What is EVALUATED is the same expression with the factor's modulus charged as a doubling of the row count wherever
+  // the rows enter -- R' = 2 b R, (3 n eta + 2.8 u + sqrt 2 (R' + 1) u) R' M^1.5 |x| |y| --, i.e. error_bound() of 2 b R
+  // rows plus the factor's 2.8 u: it over-counts the chain term (by less than 2x, and that term is the smaller one),
+  // never under-counts, and keeps one rule for "rows summed before a lift".  cfg2 (R = 6, B = 2^7): b = 3: 0.096,
+  // b = 4: 0.138, b = 6: 0.232, b = 7: 0.286 -- six key bits per step at most.  The reference's defaults (N = 512, k = 2,
+  // l = 6, B = 2^4): b = 4: 0.026.  N = 1024, k = 1, l = 4, B = 2^8: b = 2: 0.167, b = 3: 0.274 -- refused.
+  static inline double block_error_bound(int log_n, int rows, int log_base, int block) {
+    const double u = 1.1102230246251565e-16, eta = 7.1 * u;
+    const double m = (double)(1 << (log_n - 1)), n = (double)(log_n - 1), r = 2.0 * (double)block * (double)rows;
+    const double x = 1.4142135623730951 * (double)(1u << log_base), y = 1.4142135623730951 * 32768.0;
+    return 1.001 * (3.0 * n * eta + 2.8 * u + 1.42 * (r + 1.0) * u) * r * m * sqrt(m) * x * y;
+  }
   static inline double exact_bits() { return 0.0; }  // not used: error_bound() decides
   static inline double key_bits() { return 15.0; }
 };

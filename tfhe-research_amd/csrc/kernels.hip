@@ -600,6 +600,40 @@ multibit_rotate_wide_kernel(PbsParams P, const typename F::elem* __restrict__ tw
       lwe_extracted ? lwe_extracted + sample * ((size_t)K * N + 1) : nullptr);
 }
 
+// ------------------------------------------------------------------------------ block-binary blind rotation
+// block_rotate.h states the step.  blind_rotate_kernel's shape with ONE sample per team whatever the shape's loop kernel
+// takes: K+1 one-wave groups, the same LDS and register budget, segments [i_begin, i_end) that start on a block boundary
+// and park their accumulators in glwe_state.  `block` is a kernel argument: one instantiation per (N, K).
+template <class F, int LOGN, int K>
+__global__ void __launch_bounds__((TeamCfg<F, LOGN, K, 1>::kThreads), (TeamCfg<F, LOGN, K, 1>::kMinWaves))
+block_rotate_kernel(PbsParams P, const typename F::elem* __restrict__ tw, const typename F::elem* __restrict__ roots,
+                    const u32* __restrict__ lwe_in, const u32* __restrict__ tv, size_t tv_stride,
+                    const typename F::elem* __restrict__ bsk, u32 block,
+                    u32* glwe_out /* may be glwe_state: no restrict */, u32* __restrict__ lwe_extracted, u32 i_begin, u32 i_end,
+                    u32* glwe_state /* [batch][K+1][N]: accumulators between segments */) {
+  using C = TeamCfg<F, LOGN, K, 1>;
+  constexpr int N = C::N;
+  constexpr int E = NttShape<LOGN, 1>::kE;
+  static_assert(C::G == 1 && C::EXB == 1, "one wave per polynomial, one exchange buffer");
+  auto w = make_wave<F, LOGN, K, 1>(g_smem, tw);
+  const size_t sample = blockIdx.x;  // grid = batch
+  block_rotate_team<F, LOGN, K>(w, P, lwe_in + sample * (P.n + 1), tv + sample * tv_stride, bsk, roots, block, i_begin, i_end,
+                                i_begin > 0 ? glwe_state + sample * (size_t)(K + 1) * N : nullptr);
+  const int tid = w.tid();
+  if (i_end < P.n) {  // not the last segment: park the accumulators
+    u32* dst = glwe_state + (sample * (size_t)(K + 1) + w.group()) * N;
+#pragma unroll
+    for (int r = 0; r < E; ++r) dst[r * 64 + tid] = w.acc()[r * 64 + tid];
+    return;
+  }
+  if (glwe_out) {
+    u32* dst = glwe_out + (sample * (size_t)(K + 1) + w.group()) * N;
+#pragma unroll
+    for (int r = 0; r < E; ++r) dst[r * 64 + tid] = w.acc()[r * 64 + tid];
+  }
+  if (lwe_extracted) sample_extract_team<LOGN, K, 1>(w, lwe_extracted + sample * ((size_t)K * N + 1));
+}
+
 // unrolled blind rotation (two key bits per step, pbs_wave.h::blind_rotate_bmmp_team); offered where a
 // lane holds 8 elements per array and one wave owns a polynomial: N = 512
 constexpr int kBmmpMinWaves = 3;
@@ -1849,6 +1883,82 @@ hipError_t launch_blind_rotate(hipStream_t s, const PbsParams& P, const void* tw
   }
 }
 
+// Block-binary blind rotation (block_rotate.h): the complex transform with one wave per polynomial, N = 512 and 1024
+template <class F, int LOGN, int K>
+constexpr bool block_shape_ok() {
+  return F::kLogShrink == 1 && F::kParts == 2 && LOGN >= 9 && LOGN <= 10;
+}
+template <class F, int LOGN, int K>
+struct BlockRotateKernel {
+  using C = TeamCfg<F, LOGN, K, 1>;
+  static constexpr int kThreads = C::kThreads;
+  static constexpr size_t kLds = C::kLds;
+  static constexpr int kSamples = 1;
+  static constexpr int kWaves = C::kWaves;
+  static auto get() { return block_rotate_kernel<F, LOGN, K>; }
+};
+
+// launch_blind_rotate_with's walk -- blind_rotate_plan unchanged, chunks, segments, two streams -- with every segment's
+// length rounded up to a multiple of `block`, so that a launch starts on a block boundary
+template <class F, int LOGN, int K>
+hipError_t launch_block_rotate(hipStream_t s, const PbsParams& P, const void* tw_v, const void* roots_v, const u32* lwe_in, size_t batch,
+                               const u32* tv, size_t tv_stride, const void* bsk_v, u32 block, u32* glwe_out, u32* lwe_extracted,
+                               u32* state, const launch::SideStream* side) {
+  if constexpr (!block_shape_ok<F, LOGN, K>()) {
+    return hipErrorInvalidValue;
+  } else {
+    using RK = BlockRotateKernel<F, LOGN, K>;
+    using C = typename RK::C;
+    auto tw = static_cast<const typename F::elem*>(tw_v);
+    auto roots = static_cast<const typename F::elem*>(roots_v);
+    auto bsk = static_cast<const typename F::elem*>(bsk_v);
+    auto kern = RK::get();
+    static std::atomic<unsigned long long> lds_done{0};
+    hipError_t e = allow_lds(kern, RK::kLds, lds_done);
+    if (e != hipSuccess) return e;
+    unsigned capacity = 0;
+    if ((e = resident_teams<RK>(&capacity)) != hipSuccess) return e;
+    bool have_side = side && side->stream && side->fork && side->join;
+    if (have_side) {  // one stream inside a capture, as launch_blind_rotate_with
+      hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+      if (hipStreamIsCapturing(s, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) have_side = false;
+    }
+    const size_t key_bytes = (size_t)P.n * (K + 1) * P.levels * (K + 1) * F::kParts * C::N * 8;
+    const BlindRotatePlan plan = blind_rotate_plan<F>(batch, state != nullptr, have_side, P.n, key_bytes, (u32)LOGN, (size_t)capacity);
+    u32 per = (P.n + plan.segments - 1) / plan.segments;
+    per = (per + block - 1) / block * block;
+    const int parts = plan.streams == 2 && per < P.n ? 2 : 1;
+    if (parts == 2) {
+      if ((e = hipEventRecord(side->fork, s)) != hipSuccess) return e;
+      if ((e = hipStreamWaitEvent(side->stream, side->fork, 0)) != hipSuccess) return e;
+    }
+    for (size_t off = 0; off < batch; off += plan.chunk) {
+      const size_t here = batch - off < plan.chunk ? batch - off : plan.chunk;
+      const size_t share = (here + parts - 1) / parts;
+      for (u32 i0 = 0; i0 < P.n; i0 += per) {
+        const u32 i1 = P.n - i0 > per ? i0 + per : P.n;
+        for (int q = 0; q < parts; ++q) {
+          if ((size_t)q * share >= here) break;
+          const size_t o = off + (size_t)q * share;
+          const size_t cnt = here - (size_t)q * share < share ? here - (size_t)q * share : share;
+          hipLaunchKernelGGL(kern, dim3((unsigned)cnt), dim3(RK::kThreads), RK::kLds, q ? side->stream : s, P, tw, roots,
+                             lwe_in + o * ((size_t)P.n + 1), tv + o * tv_stride, tv_stride, bsk, block,
+                             glwe_out ? glwe_out + o * (size_t)(K + 1) * C::N : nullptr,
+                             lwe_extracted ? lwe_extracted + o * ((size_t)K * C::N + 1) : nullptr, i0, i1,
+                             state ? state + o * (size_t)(K + 1) * C::N : nullptr);
+          e = hipGetLastError();
+          if (e != hipSuccess) return e;
+        }
+      }
+    }
+    if (parts == 2) {
+      if ((e = hipEventRecord(side->join, side->stream)) != hipSuccess) return e;
+      if ((e = hipStreamWaitEvent(s, side->join, 0)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
+}
+
 template <class F, int LOGN, int K>
 hipError_t launch_blind_rotate_bmmp(hipStream_t s, const PbsParams& P, const void* tw_v, const u32* lwe_in,
                                     size_t batch, const u32* tv, size_t tv_stride, const void* bsk_v,
@@ -2219,6 +2329,18 @@ hipError_t multibit_rotate(hipStream_t s, int field, const PbsParams& P, const v
   if (batch == 0 || batch > 0x7FFFFFFFull || groups == 0) return hipErrorInvalidValue;
   TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (launch_multibit_rotate<FF, LL, KK>(s, P, tw, lwe_in, batch, tv, tv_stride,
                                                                                                  bundles, groups, glwe_out, lwe_extracted))));
+}
+
+bool block_rotate_supported(int field, u32 log_n, u32 k) {
+  return field == kFieldFft && (log_n == 9 || log_n == 10) && (k == 1 || k == 2);
+}
+
+hipError_t block_rotate(hipStream_t s, int field, const PbsParams& P, const void* tw, const void* roots, const u32* lwe_in, size_t batch,
+                        const u32* tv, size_t tv_stride, const void* bsk, u32 block, u32* glwe_out, u32* lwe_extracted, u32* state,
+                        const SideStream* side) {
+  if (batch == 0 || block < 2 || !block_rotate_supported(field, P.log_n, P.k)) return hipErrorInvalidValue;
+  TFHE_DISPATCH_FIELD(field, TFHE_DISPATCH_LOGN_K(P.log_n, P.k, (launch_block_rotate<FF, LL, KK>(s, P, tw, roots, lwe_in, batch, tv, tv_stride, bsk,
+                                                                                              block, glwe_out, lwe_extracted, state, side))));
 }
 
 hipError_t blind_rotate(hipStream_t s, int field, const PbsParams& P, const void* tw,

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "block_rotate.h"
 #include "glwe_conv.h"
 #include "glwe_switch.h"
 #include "ks_matrix.h"
@@ -90,6 +91,16 @@ hipError_t multibit_bundle(hipStream_t s, int field, const PbsParams& P, const v
 // the optional outputs as for blind_rotate
 hipError_t multibit_rotate(hipStream_t s, int field, const PbsParams& P, const void* tw, const u32* lwe_in, size_t batch, const u32* tv,
                            size_t tv_stride, const void* bundles, u32 groups, u32* glwe_out, u32* lwe_extracted);
+
+// ---- block-binary blind rotation (block_rotate.h): `block` key bits per decomposition on the loaded, ordinary key.
+// Offered for the complex transform at N = 512 and 1024 (one wave per polynomial).  One team of k+1 waves per sample at
+// EVERY batch: the batches blind_rotate gives to the wide team or the pair kernel run on this team kernel too.
+bool block_rotate_supported(int field, u32 log_n, u32 k);
+// `roots`: block_root_words(log_n) elements of fill_block_roots on the device.  Chunks, segments and streams as
+// blind_rotate sends them out (the same plan), segment lengths rounded up to a multiple of `block`; `state` and `side` as there.
+hipError_t block_rotate(hipStream_t s, int field, const PbsParams& P, const void* tw, const void* roots, const u32* lwe_in, size_t batch,
+                        const u32* tv, size_t tv_stride, const void* bsk, u32 block, u32* glwe_out, u32* lwe_extracted,
+                        u32* state = nullptr, const SideStream* side = nullptr);
 
 // out = external_product(ggsw[g], glwe[b]) (+ ct0 for the CMUX form).
 //   cmux_ct0 == nullptr : src = glwe_in
