@@ -713,6 +713,42 @@ inline LweCiphertext wide_lut(Engine& e, const LweCiphertext& ct, unsigned lsb, 
   e.check(tfhe_wide_lut_batch(e.raw(), ct.data.data(), 1, lsb, d, table.data(), 1, 1, out.data.data()));
   return out;
 }
+// ---- radix integers (tfhe_hip.h states the operations; first device only) ----
+// A radix integer is `blocks` ciphertexts of n + 1 words back to back, block 0 least significant (the reference's bootstrap
+// order only, like the wrappers above).
+struct RadixCiphertext {
+  size_t blocks = 0;
+  std::vector<uint32_t> data;  // [blocks][n + 1]
+};
+// blocks of any value below 2^log_p -> the clean integer of the same value: 3 + ceil(log2(blocks - 1)) bootstrap levels
+inline RadixCiphertext radix_propagate(Engine& e, const RadixCiphertext& x) {
+  if (x.blocks == 0 || x.data.size() != x.blocks * (size_t(e.params().lwe_dimension) + 1)) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "radix length");
+  RadixCiphertext out{x.blocks, std::vector<uint32_t>(x.data.size())};
+  e.check(tfhe_radix_propagate_batch(e.raw(), x.data.data(), 1, x.blocks, out.data.data()));
+  return out;
+}
+// one level: out_j = tables[table_of_block[j]][wa a_j + wb b_j], tables holding un-encoded values below 2^log_p (b may be
+// null: a univariate lookup); the operands block by block, unshifted
+inline RadixCiphertext radix_map(Engine& e, const RadixCiphertext& a, uint32_t wa, const RadixCiphertext* b, uint32_t wb,
+                                 const std::vector<uint32_t>& tables, const std::vector<uint32_t>& table_of_block) {
+  const size_t width = size_t(e.params().lwe_dimension) + 1, P = size_t(1) << e.params().log_p;
+  if (a.blocks == 0 || a.data.size() != a.blocks * width || table_of_block.size() != a.blocks || tables.empty() || tables.size() % P != 0 ||
+      (b && (b->blocks != a.blocks || b->data.size() != a.data.size())))
+    throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "radix_map: operands of equal length, tables [count][2^log_p], one table index per block");
+  RadixCiphertext out{a.blocks, std::vector<uint32_t>(a.data.size())};
+  e.check(tfhe_radix_map_batch(e.raw(), a.data.data(), a.blocks, wa, 0, -1, b ? b->data.data() : nullptr, b ? b->blocks : 0, wb, 0, -1, 1,
+                               a.blocks, tables.data(), tables.size() / P, table_of_block.data(), out.data.data()));
+  return out;
+}
+// clean a, b of equal length and a predicate TFHE_RADIX_EQ .. TFHE_RADIX_GE -> one block in {0, 1}
+inline LweCiphertext radix_compare(Engine& e, const RadixCiphertext& a, const RadixCiphertext& b, unsigned predicate) {
+  const size_t width = size_t(e.params().lwe_dimension) + 1;
+  if (a.blocks == 0 || a.blocks != b.blocks || a.data.size() != a.blocks * width || b.data.size() != a.data.size())
+    throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "radix_compare: two integers of equal length");
+  LweCiphertext out{std::vector<uint32_t>(width)};
+  e.check(tfhe_radix_compare_batch(e.raw(), a.data.data(), b.data.data(), 1, a.blocks, predicate, out.data.data()));
+  return out;
+}
 // ---- encrypted dense layers (tfhe_hip.h states the operations; first device only) ----
 // Dense(W, bias; x) for ONE query: x holds the I input ciphertexts (all of one length), weights [O][I] row-major int32,
 // bias [O] already ENCODED words or empty -> O ciphertexts of that length, out[o] = sum_i W[o][i] x[i] (+ bias[o] on the body)

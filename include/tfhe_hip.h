@@ -893,6 +893,99 @@ int tfhe_wide_lut_batch(tfhe_context *ctx, const uint32_t *lwe_in, size_t batch,
 int tfhe_wide_lut_batch_device(tfhe_context *ctx, const uint32_t *lwe_in, size_t batch, unsigned lsb, size_t d,
                                const uint32_t *table, size_t table_sets, size_t tables, uint32_t *lwe_out);
 
+/* ---- radix integers: blocks with carry space, log-depth carry propagation (no reference counterpart) ------------------
+ * An encrypted integer is D blocks, each one LWE ciphertext with m message bits and m carry bits: log_p = 2 m, m >= 2,
+ * P = 2^log_p, Bm = 2^m, Delta = 2^(32 - log_p - padding_bits), padding_bits >= 1.  A block of value v < P has phase
+ * v Delta + e.  A radix integer is [batch][D][io_words] (io_words = n + 1, or k N + 1 with the key switch first), block 0
+ * least significant; it is clean when every block is below Bm, and stands for sum_j v_j Bm^j mod Bm^D.  Blockwise sums
+ * are plain wrapping adds of words (tfhe_lwe_linear_batch); these calls do what needs a bootstrap.  All arithmetic is
+ * mod 2^32 on every word.
+ *
+ * Table lookup.  With rep = N / 2^(log_p + padding_bits - 1) >= 2 (N / P at padding_bits = 1: P <= N / 2), every lookup is
+ *   LUT_T(x) = tfhe_bootstrap_glwe_batch(x; acc_in = (0, .., 0, sum_i T[i div rep] Delta X^i), acc_count = batch,
+ *                                        rotation_offset = rep / 2)
+ * one accumulator per rotation, in the context's bootstrap order (T is read for i div rep < P only).  The offset puts a
+ * block's centre on the middle of its rep coefficients, so no table entry is negated; inputs must be below P (padding
+ * bit clear).  Between two bootstrap levels there is ONE elementwise launch (csrc/radix.h): for every rotation of the
+ * next level it forms  wa A[q][ia(j)] + wb B[q][ib(j)]  -- ia, ib a shifted or a fixed (broadcast) block index, an index
+ * outside the operand reading the trivial zero ciphertext -- and writes that rotation's accumulator.  Shifts, weights and
+ * table choices are kernel arguments computed on the host from (operation, D, level): nothing is uploaded per call.
+ *
+ * tfhe_radix_propagate_batch: blocks v_j <= P - 1 -> the clean integer of the same value mod Bm^D, in
+ * 3 + ceil(log2(D - 1)) levels for D >= 2 (one for D = 1) instead of D:
+ *   1. M_j = LUT_{x mod Bm}(v_j) and C_j = LUT_{x >> m}(v_j), one call of 2 D rotations per row (D = 1: M only, done)
+ *   2. w_j = M_j + C_(j-1), C_(-1) = 0                                            (w_j <= 2 Bm - 2)
+ *      S_0 = LUT_{[x >= Bm]}(w_0) -- complete, a carry in {0, 1};
+ *      S_j = LUT_{0 none, 1 propagate (x = Bm - 1), 2 generate (x >= Bm)}(w_j), 1 <= j <= D - 2
+ *   3. for r = 1, 2, 4, .. while r < D - 1: blocks j < r stay; for r <= j <= D - 2, x = 4 S_j + S_(j-r) (<= 10) and
+ *        r <= j < 2 r:  S_j = LUT_{[hi = 2 or (hi = 1 and lo = 1)]}(x)    (the lower operand is complete: a carry)
+ *        j >= 2 r:      S_j = LUT_{hi if hi != 1 else lo}(x)              with hi = x div 4, lo = x mod 4
+ *   4. out_j = LUT_{x mod Bm}(w_j + S_(j-1)), S_(-1) = 0
+ *
+ * tfhe_radix_map_batch: one level,  out[q][j] = LUT_{tables[table_of_block[j]]}(wa a[q][ia(j)] + wb b[q][ib(j)])  for
+ * j < blocks, with ia(j) = a_fixed if a_fixed >= 0 else j - a_shift (zero outside [0, a_blocks)), ib likewise; b may be
+ * NULL (a univariate lookup).  a is [batch][a_blocks][io_words], b [batch][b_blocks][io_words], out [batch][blocks][io_words].
+ * tables [table_count][P] holds un-encoded values below P, table_count <= 254 (a device pointer in the _device form,
+ * where its values cannot be checked); table_of_block [blocks] is a host array in both forms.  That
+ * wa v_a + wb v_b stays below P cannot be checked on ciphertexts: it is the caller's degree rule (clean operands with
+ * (wa, wb) = (Bm, 1) keep it).  This is the primitive behind bitwise operations, partial products, shifts and select.
+ *
+ * tfhe_radix_compare_batch: clean a, b [batch][D][io_words] and a predicate -> out [batch][io_words], one block in {0, 1}:
+ *   1. c_j = LUT_{0 equal, 1 less, 2 greater}(Bm a_j + b_j)
+ *   2. while more than one code is left: pairs (hi, lo) of neighbours become LUT_{hi if hi != 0 else lo}(4 hi + lo); with
+ *      an odd count the least significant code passes through (it is not bootstrapped) and the pairs start at code 1:
+ *      ceil(log2 D) levels
+ *   the predicate's table is composed into the last level's (level 1 for D = 1).
+ *
+ * The words of every call equal, byte for byte, the composition of tfhe_lwe_linear_batch (the sums) and
+ * tfhe_bootstrap_glwe_batch on clear accumulators, one call per line above: the sums are exact, and the rotation kernels'
+ * shapes agree bit for bit whatever the batch of a level.  (No line adds a constant, so tfhe_lwe_dense_batch's bias has
+ * no part in it.)
+ *
+ * Limits and refusals.  TFHE_ERR_INVALID_ARGUMENT: log_p odd or below 4, padding_bits = 0, rep < 2, D = 0 or above 64, an
+ * empty batch, 2 batch D above 2^31 - 1, a NULL pointer (b excepted), an output that overlaps an input other than exactly
+ * in place, a table index out of range, (host form) a table value >= P, an unknown predicate.  TFHE_ERR_NO_KEY without a
+ * bootstrapping key; TFHE_ERR_UNSUPPORTED with a BMMP key (the rotations start from a GLWE accumulator).  Nothing is
+ * enqueued by a refused call.
+ *
+ * Workspace: tfhe_context_reserve_radix(max_batch, max_blocks) reserves tfhe_context_reserve(R), R = 2 max_batch max_blocks
+ * rotations, and on top of it, with W = max(n, k N) + 1 (either bootstrap order fits):
+ *   6 roundup4(max_batch max_blocks W) + R (k+1) N   words of 4 bytes
+ * -- a level's inputs and level 1's results (R rows each), the sums w and the states s (R / 2 rows each), and R
+ * accumulators -- plus the 20 fixed tables of P words, written once (that call may synchronise).  After it the _device
+ * forms allocate nothing, stay on the context's stream and can be captured.  A call beyond the reservation returns
+ * TFHE_ERR_INVALID_ARGUMENT with the need in bytes.  The host forms reserve for themselves and block.
+ *
+ * Noise, in units of the 32-bit torus, with sigma_bs^2 a bootstrap's output variance at the boundary exactly as the digit
+ * extraction above defines it.  A level's input is a combination with weights (wa, wb) of bootstrap outputs: variance
+ * (wa^2 + wb^2) sigma_bs^2, the weights at most (4, 1) inside propagate and compare, (Bm, 1) for a bivariate map on fresh
+ * blocks; level 1 sees the caller's variance.  A block is decided correctly while that error, plus the rotation's
+ * modulus-switch term of variance (1 + n/2) (2^32 / 2N)^2 / 12, plus -- with the key switch first -- the key-switch term
+ * s_ks^2, stays below half a block, Delta / 2 = 2^32 / (2^(padding_bits + 1) P). */
+#define TFHE_RADIX_EQ 0
+#define TFHE_RADIX_NE 1
+#define TFHE_RADIX_LT 2
+#define TFHE_RADIX_LE 3
+#define TFHE_RADIX_GT 4
+#define TFHE_RADIX_GE 5
+int tfhe_context_reserve_radix(tfhe_context *ctx, size_t max_batch, size_t max_blocks);
+int tfhe_radix_propagate_batch(tfhe_context *ctx, const uint32_t *blocks_in, size_t batch, size_t blocks,
+                               uint32_t *blocks_out);
+int tfhe_radix_propagate_batch_device(tfhe_context *ctx, const uint32_t *blocks_in, size_t batch, size_t blocks,
+                                      uint32_t *blocks_out);
+int tfhe_radix_map_batch(tfhe_context *ctx, const uint32_t *a, size_t a_blocks, uint32_t wa, int32_t a_shift,
+                         int32_t a_fixed, const uint32_t *b, size_t b_blocks, uint32_t wb, int32_t b_shift,
+                         int32_t b_fixed, size_t batch, size_t blocks, const uint32_t *tables, size_t table_count,
+                         const uint32_t *table_of_block, uint32_t *out);
+int tfhe_radix_map_batch_device(tfhe_context *ctx, const uint32_t *a, size_t a_blocks, uint32_t wa, int32_t a_shift,
+                                int32_t a_fixed, const uint32_t *b, size_t b_blocks, uint32_t wb, int32_t b_shift,
+                                int32_t b_fixed, size_t batch, size_t blocks, const uint32_t *tables, size_t table_count,
+                                const uint32_t *table_of_block, uint32_t *out);
+int tfhe_radix_compare_batch(tfhe_context *ctx, const uint32_t *a, const uint32_t *b, size_t batch, size_t blocks,
+                             unsigned predicate, uint32_t *out);
+int tfhe_radix_compare_batch_device(tfhe_context *ctx, const uint32_t *a, const uint32_t *b, size_t batch, size_t blocks,
+                                    unsigned predicate, uint32_t *out);
+
 /* ---- multi-value bootstrapping: several tables from one blind rotation (no reference counterpart) --------------------
  * Several functions of ONE ciphertext cost one rotation, not one each (Carpov, Izabachene, Mollimard 2019): rotate a
  * table-independent accumulator, then multiply it by a small clear polynomial per table.  Nothing is packed into spare

@@ -88,6 +88,13 @@ extern "C" {
                                  digits: c_uint, out_lsb: c_uint, digits_out: *const *mut u32, remainder_out: *mut u32) -> c_int;
     fn tfhe_wide_lut_batch(ctx: *mut TfheContext, lwe_in: *const u32, batch: usize, lsb: c_uint, d: usize, table: *const u32,
                            table_sets: usize, tables: usize, lwe_out: *mut u32) -> c_int;
+    // radix integers (include/tfhe_hip.h)
+    fn tfhe_radix_propagate_batch(ctx: *mut TfheContext, blocks_in: *const u32, batch: usize, blocks: usize, blocks_out: *mut u32) -> c_int;
+    fn tfhe_radix_map_batch(ctx: *mut TfheContext, a: *const u32, a_blocks: usize, wa: u32, a_shift: i32, a_fixed: i32, b: *const u32,
+                            b_blocks: usize, wb: u32, b_shift: i32, b_fixed: i32, batch: usize, blocks: usize, tables: *const u32,
+                            table_count: usize, table_of_block: *const u32, out: *mut u32) -> c_int;
+    fn tfhe_radix_compare_batch(ctx: *mut TfheContext, a: *const u32, b: *const u32, batch: usize, blocks: usize, predicate: c_uint,
+                                out: *mut u32) -> c_int;
     // multi-value bootstrapping (include/tfhe_hip.h)
     fn tfhe_multi_value_bootstrap_batch(ctx: *mut TfheContext, lwe_in: *const u32, batch: usize, luts: *const u32, lut_sets: usize,
                                         tables: usize, lwe_out: *mut u32) -> c_int;
@@ -495,6 +502,52 @@ pub fn wide_lut(bk: &GpuBootstrappingKey, lwe: &Array2<u32>, lsb: u32, d: usize,
         tfhe_wide_lut_batch(bk.ctx, lwe.as_slice().unwrap().as_ptr(), batch, lsb as c_uint, d, table.as_slice().unwrap().as_ptr(),
                             1, 1, out.as_slice_mut().unwrap().as_mut_ptr())
     }, "wide_lut");
+    out
+}
+
+/// Radix carry propagation: `x` (batch, blocks, n+1), blocks of any value below 2^log_p (log_p = 2 m: m message bits and m
+/// carry bits), block 0 least significant -> the clean integers of the same values, in 3 + ceil(log2(blocks - 1)) bootstrap
+/// levels (no reference counterpart).  The reference's bootstrap order only, as above.
+pub fn radix_propagate(bk: &GpuBootstrappingKey, x: &Array3<u32>) -> Array3<u32> {
+    let (batch, blocks, width) = x.dim();
+    assert!(width == bk.params.lwe_dimension as usize + 1 && batch >= 1 && blocks >= 1, "radix_propagate: ciphertexts of n+1 words");
+    let mut out = Array3::<u32>::zeros((batch, blocks, width));
+    check(bk.ctx, unsafe {
+        tfhe_radix_propagate_batch(bk.ctx, x.as_slice().unwrap().as_ptr(), batch, blocks, out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "radix_propagate");
+    out
+}
+
+/// One level of table lookups on radix blocks: out[q][j] = tables[table_of_block[j]][wa a[q][j] + wb b[q][j]], `tables`
+/// (count, 2^log_p) of un-encoded values; `b` None: a univariate lookup.  The caller keeps wa v_a + wb v_b below 2^log_p.
+pub fn radix_map(bk: &GpuBootstrappingKey, a: &Array3<u32>, wa: u32, b: Option<&Array3<u32>>, wb: u32, tables: &Array2<u32>,
+                 table_of_block: &Array1<u32>) -> Array3<u32> {
+    let (batch, blocks, width) = a.dim();
+    let (count, values) = tables.dim();
+    assert!(width == bk.params.lwe_dimension as usize + 1 && batch >= 1 && blocks >= 1, "radix_map: ciphertexts of n+1 words");
+    assert!(count >= 1 && values == 1usize << bk.params.log_p && table_of_block.len() == blocks, "radix_map: tables of 2^log_p values, one index per block");
+    assert!(b.map_or(true, |b| b.dim() == a.dim()), "radix_map: operands of one shape");
+    let mut out = Array3::<u32>::zeros((batch, blocks, width));
+    check(bk.ctx, unsafe {
+        tfhe_radix_map_batch(bk.ctx, a.as_slice().unwrap().as_ptr(), blocks, wa, 0, -1,
+                             b.map_or(std::ptr::null(), |b| b.as_slice().unwrap().as_ptr()), blocks, wb, 0, -1, batch, blocks,
+                             tables.as_slice().unwrap().as_ptr(), count, table_of_block.as_slice().unwrap().as_ptr(),
+                             out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "radix_map");
+    out
+}
+
+/// Radix comparison of clean `a`, `b` (batch, blocks, n+1): predicate 0 eq, 1 ne, 2 lt, 3 le, 4 gt, 5 ge -> (batch, n+1), one
+/// block in {0, 1} per row, in 1 + ceil(log2 blocks) bootstrap levels.
+pub fn radix_compare(bk: &GpuBootstrappingKey, a: &Array3<u32>, b: &Array3<u32>, predicate: u32) -> Array2<u32> {
+    let (batch, blocks, width) = a.dim();
+    assert!(width == bk.params.lwe_dimension as usize + 1 && batch >= 1 && blocks >= 1 && b.dim() == a.dim() && predicate <= 5,
+            "radix_compare: two integers of one shape, ciphertexts of n+1 words, a predicate in 0..=5");
+    let mut out = Array2::<u32>::zeros((batch, width));
+    check(bk.ctx, unsafe {
+        tfhe_radix_compare_batch(bk.ctx, a.as_slice().unwrap().as_ptr(), b.as_slice().unwrap().as_ptr(), batch, blocks, predicate as c_uint,
+                                 out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "radix_compare");
     out
 }
 

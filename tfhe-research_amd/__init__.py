@@ -39,6 +39,8 @@ GATE_AND = (0, 0, 0, 1)
 GATE_OR = (0, 1, 1, 1)
 GATE_NAND = (1, 1, 1, 0)
 GATE_XOR = (0, 1, 1, 0)
+# predicates of Context.radix_compare (TFHE_RADIX_EQ .. TFHE_RADIX_GE)
+RADIX_EQ, RADIX_NE, RADIX_LT, RADIX_LE, RADIX_GT, RADIX_GE = range(6)
 
 
 class TfheError(RuntimeError):
@@ -981,6 +983,88 @@ class Context:
         self._call("tfhe_wide_lut_batch", dev, _ptr(lwe), C.c_size_t(batch), C.c_uint(int(lsb)), C.c_size_t(d), _ptr(table),
                    C.c_size_t(sets), C.c_size_t(tables), _ptr(res))
         return res
+
+    # -- radix integers: blocks of m message and m carry bits (include/tfhe_hip.h states the operations) --
+    def reserve_radix(self, max_batch: int, max_blocks: int):
+        """size the workspace of the device forms of radix_propagate, radix_map and radix_compare (a maximum)"""
+        self._check(lib().tfhe_context_reserve_radix(self._h, C.c_size_t(max_batch), C.c_size_t(max_blocks)))
+
+    def _radix_blocks(self, what, name, x, dev, batch=None):
+        """-> (x [batch][blocks][io_dim+1], batch, blocks) after the checks the ABI cannot make on a bare pointer"""
+        width = self.io_dim + 1
+        if not dev:
+            x = _np(x)
+        text = f"{what}: {name} must be a contiguous 32-bit [{'batch' if batch is None else batch}][blocks][{width}] array"
+        if len(x.shape) != 3 or int(x.shape[0]) < 1 or int(x.shape[1]) < 1 or (batch is not None and int(x.shape[0]) != batch):
+            raise _invalid(text)
+        _check_u32(what, name, x, dev, (None, None, width), text=text)
+        return x, int(x.shape[0]), int(x.shape[1])
+
+    def radix_propagate(self, blocks, out=None):
+        """blocks [batch][D][io_dim+1] of any value below 2^log_p -> the clean integer of the same value mod Bm^D, in
+        3 + ceil(log2(D - 1)) bootstrap levels.  numpy (host form: reserves for itself, blocks) or a torch device tensor
+        (reserve_radix first; out may be `blocks` itself)."""
+        dev = _is_torch(blocks)
+        x, batch, d = self._radix_blocks("radix_propagate", "blocks", blocks, dev)
+        res = _result("radix_propagate", dev, out, None, x)
+        self._call("tfhe_radix_propagate_batch", dev, _ptr(x), C.c_size_t(batch), C.c_size_t(d), _ptr(res))
+        return res
+
+    def radix_map(self, a, tables, table_of_block, b=None, wa: int = 1, wb: int = 1, a_shift: int = 0, a_block: int | None = None,
+                  b_shift: int = 0, b_block: int | None = None, out=None):
+        """One level: out[q][j] = tables[table_of_block[j]][wa a[q][ia(j)] + wb b[q][ib(j)]] for every j of table_of_block,
+        ia(j) = a_block if given (broadcast) else j - a_shift, a block outside the operand reading as zero; tables
+        [count][2^log_p] of un-encoded values; b None: a univariate lookup.  The caller keeps wa v_a + wb v_b below 2^log_p.
+        numpy (host form) or torch device tensors (reserve_radix first; table_of_block is a host sequence in both)."""
+        dev = _same_kind("radix_map", "a, b and tables", (a, b, tables), "all")
+        a, batch, a_blocks = self._radix_blocks("radix_map", "a", a, dev)
+        b_blocks = 0
+        if b is not None:
+            b, _, b_blocks = self._radix_blocks("radix_map", "b", b, dev, batch)
+        if not dev:
+            tables = _np(tables)
+        values = 1 << self.params.log_p
+        _check_u32("radix_map", "tables", tables, dev, (None, values), a if dev else None,
+                   text=f"radix_map: tables [count][{values}] of 32-bit integers expected")
+        sel = np.ascontiguousarray(table_of_block, dtype=np.uint32).reshape(-1)
+        if sel.size < 1:
+            raise _invalid("radix_map: table_of_block must name a table for every output block")
+        fixed = [-1 if v is None else int(v) for v in (a_block, b_block)]
+        if min(fixed) < -1 or any(abs(int(v)) >= 1 << 31 for v in (a_shift, b_shift, *fixed)):
+            raise _invalid("radix_map: a block index or shift is out of range")
+        res = _result("radix_map", dev, out, (batch, sel.size, self.io_dim + 1), a)
+        self._call("tfhe_radix_map_batch", dev, _ptr(a), C.c_size_t(a_blocks), C.c_uint32(int(wa) & 0xFFFFFFFF), C.c_int32(int(a_shift)),
+                   C.c_int32(fixed[0]), _ptr(b), C.c_size_t(b_blocks), C.c_uint32(int(wb) & 0xFFFFFFFF), C.c_int32(int(b_shift)),
+                   C.c_int32(fixed[1]), C.c_size_t(batch), C.c_size_t(sel.size), _ptr(tables), C.c_size_t(int(tables.shape[0])),
+                   _ptr(sel), _ptr(res))
+        return res
+
+    def radix_compare(self, a, b, predicate: int, out=None):
+        """clean a, b [batch][D][io_dim+1] and a predicate RADIX_EQ .. RADIX_GE -> [batch][io_dim+1], one block in {0, 1} per
+        row, in 1 + ceil(log2 D) bootstrap levels.  numpy (host form) or torch device tensors (reserve_radix first)."""
+        dev = _same_kind("radix_compare", "a and b", (a, b))
+        a, batch, d = self._radix_blocks("radix_compare", "a", a, dev)
+        b, _, db = self._radix_blocks("radix_compare", "b", b, dev, batch)
+        if db != d:
+            raise _invalid(f"radix_compare: a and b must have as many blocks, got {d} and {db}")
+        res = _result("radix_compare", dev, out, (batch, self.io_dim + 1), a)
+        self._call("tfhe_radix_compare_batch", dev, _ptr(a), _ptr(b), C.c_size_t(batch), C.c_size_t(d), C.c_uint(int(predicate)), _ptr(res))
+        return res
+
+    def encrypt_radix(self, sk, values, blocks: int, rng=None) -> np.ndarray:
+        """values (non-negative integers, taken mod Bm^blocks) -> clean radix integers [batch][blocks][dim+1] under `sk`, the
+        key of the bootstrap's boundary (the LWE key, or the flattened GLWE key with the key switch first)"""
+        m = self.params.log_p // 2
+        digits = [[(int(v) >> (m * j)) & ((1 << m) - 1) for j in range(blocks)] for v in np.asarray(values, dtype=object).reshape(-1)]
+        return self.encrypt_bits(sk, np.array(digits, dtype=np.uint32), rng).reshape(len(digits), blocks, -1)
+
+    def decrypt_radix(self, sk, x) -> list:
+        """radix integers [batch][blocks][dim+1] (clean or not) -> the Python integers sum_j v_j Bm^j mod Bm^blocks"""
+        x = x.cpu().numpy() if _is_torch(x) else _np(x)
+        batch, blocks = int(x.shape[0]), int(x.shape[1])
+        m = self.params.log_p // 2
+        v = self.decrypt_bits(sk, x.reshape(batch * blocks, -1).view(np.uint32)).reshape(batch, blocks)
+        return [sum(int(v[q, j]) << (m * j) for j in range(blocks)) % (1 << (m * blocks)) for q in range(batch)]
 
     # -- multi-value bootstrapping: several tables from one rotation (include/tfhe_hip.h states the operations) --
     def reserve_multi_value(self, max_batch: int, max_tables: int = 1):

@@ -3687,6 +3687,349 @@ int tfhe_wide_lut_batch(tfhe_context* ctx, const uint32_t* lwe_in, size_t batch,
   return s.download_and_wait(kOut, lwe_out);
 }
 
+// ---------------------------------------------------------------------------------- radix integers
+// tfhe_hip.h states the operations, radix.h::radix_glue the launch in front of every bootstrap level.  A level is one
+// glue launch and one bootstrap call with an accumulator per rotation; the host loops below are over the levels only.
+namespace {
+
+struct RadixShape {
+  u32 m, log_rep, log_delta;
+};
+
+// log_p = 2 m >= 4, a padding bit, and every block value on rep >= 2 coefficients
+int check_radix_params(tfhe_context* ctx, RadixShape* shape) {
+  const tfhe_params& p = ctx->params;
+  if (p.log_p < 4 || p.log_p % 2 != 0)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "radix integers need log_p = 2 m with m >= 2, got log_p = " + std::to_string(p.log_p));
+  if (p.padding_bits == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "radix integers need padding_bits >= 1");
+  if (p.log_p + p.padding_bits > p.glwe_poly_degree)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+                "radix integers need rep = N / 2^(log_p + padding_bits - 1) >= 2 coefficients per block value (P <= N / 2)");
+  shape->m = p.log_p / 2;
+  shape->log_rep = p.glwe_poly_degree + 1 - p.log_p - p.padding_bits;
+  shape->log_delta = 32 - p.log_p - p.padding_bits;
+  return TFHE_OK;
+}
+
+int check_radix_size(tfhe_context* ctx, size_t batch, size_t blocks) {
+  if (batch == 0) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "empty batch");
+  if (blocks == 0 || blocks > kRadixMaxBlocks)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "blocks must be in [1, " + std::to_string(kRadixMaxBlocks) + "]");
+  if (batch > kMaxBatch / (2 * blocks))
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "2 * batch * blocks exceeds 2^31 - 1 (one workgroup per rotation)");
+  return TFHE_OK;
+}
+
+struct RadixLayout {
+  size_t x = 0, o = 0, w = 0, s = 0, acc = 0;  // offsets in words
+  size_t words = 0;
+};
+
+// every row at the larger boundary dimension, so that switching the bootstrap order keeps a reservation valid
+void radix_layout(const tfhe_context* ctx, size_t batch, size_t blocks, RadixLayout* out) {
+  auto pad = [](size_t w) { return (w + 3) & ~(size_t)3; };  // 16-byte buffers
+  const size_t row = std::max(lwe_words(ctx), big_lwe_words(ctx)), half = pad(batch * blocks * row);
+  RadixLayout& L = *out;
+  L.x = 0;
+  L.o = 2 * half;
+  L.w = 4 * half;
+  L.s = 5 * half;
+  L.acc = 6 * half;
+  L.words = L.acc + 2 * batch * blocks * glwe_words(ctx);
+}
+
+size_t radix_bytes(const tfhe_context* ctx, size_t batch, size_t blocks) {
+  RadixLayout L;
+  radix_layout(ctx, batch, blocks, &L);
+  return L.words * sizeof(u32);
+}
+
+int reserve_radix(tfhe_context* ctx, size_t batch, size_t blocks) {
+  RadixShape shape;
+  TFHE_TRY(check_radix_params(ctx, &shape));
+  if (!ctx->d_radix_tables) {  // once: the tables depend on the parameters only
+    const u32 P = 1u << ctx->params.log_p;
+    std::vector<u32> tables((size_t)kRadixTables * P);
+    for (u32 t = 0; t < kRadixTables; ++t)
+      for (u32 x = 0; x < P; ++x) tables[(size_t)t * P + x] = radix_table_value(t, shape.m, x);
+    TFHE_TRY(ctx->d_radix_tables.grow(ctx, tables.size() * sizeof(u32)));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_radix_tables.as(), tables.data(), tables.size() * sizeof(u32), hipMemcpyHostToDevice));
+  }
+  const size_t new_batch = std::max(batch, ctx->radix_batch), new_blocks = std::max(blocks, ctx->radix_blocks);
+  TFHE_TRY(reserve(ctx, 2 * new_batch * new_blocks));
+  if (batch <= ctx->radix_batch && blocks <= ctx->radix_blocks) return TFHE_OK;
+  ctx->radix_batch = ctx->radix_blocks = 0;
+  TFHE_TRY(ctx->d_radix_ws.grow(ctx, radix_bytes(ctx, new_batch, new_blocks)));
+  ctx->radix_batch = new_batch;
+  ctx->radix_blocks = new_blocks;
+  return TFHE_OK;
+}
+
+int check_radix_reserved(tfhe_context* ctx, size_t batch, size_t blocks) {
+  const bool base = 2 * ctx->radix_batch * ctx->radix_blocks <= ctx->ws_batch && ctx->d_radix_tables;
+  if (base && batch <= ctx->radix_batch && blocks <= ctx->radix_blocks) return TFHE_OK;
+  return fail(ctx, TFHE_ERR_INVALID_ARGUMENT,
+              "the call needs " + std::to_string(radix_bytes(ctx, batch, blocks)) + " bytes of radix workspace (batch " +
+                  std::to_string(batch) + ", " + std::to_string(blocks) + " blocks), " +
+                  std::to_string(base && ctx->radix_batch ? ctx->d_radix_ws.bytes() : 0) + " are reserved (tfhe_context_reserve_radix)");
+}
+
+// the keys every level needs: a plain bootstrapping key (the rotations start from GLWE accumulators)
+int check_radix_keys(tfhe_context* ctx) {
+  const size_t offset = 0;
+  return check_rotate_args(ctx, ctx, ctx, ctx, 1, 1, &offset);
+}
+
+// `out` [words] is `in` exactly, or apart from it
+int check_radix_in_place(tfhe_context* ctx, const void* out, const void* in, size_t in_words, size_t out_words, const char* name) {
+  if (!in || out == in || !overlap(out, out_words, in, in_words)) return TFHE_OK;
+  return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, std::string("the output overlaps ") + name + " without being exactly in place");
+}
+
+// One level: the glue launch, then the bootstrap of its `rotations` outputs x with their accumulators into `out`.
+struct RadixLevels {
+  tfhe_context* ctx;
+  RadixShape shape;
+  size_t rows;
+  u32 *x, *o, *w, *s, *acc;
+
+  RadixLevels(tfhe_context* c, const RadixShape& sh, size_t r) : ctx(c), shape(sh), rows(r) {
+    RadixLayout L;
+    radix_layout(ctx, ctx->radix_batch, ctx->radix_blocks, &L);
+    u32* ws = ctx->d_radix_ws.as<u32>();
+    x = ws + L.x, o = ws + L.o, w = ws + L.w, s = ws + L.s, acc = ws + L.acc;
+  }
+  // a caller's integer [row][block] of `blocks` blocks, or a workspace buffer [block][row]
+  RadixOperand rows_of(const u32* p, size_t blocks, u32 weight) const {
+    return RadixOperand{p, (u32)blocks, 1u, -1, 1, 0, (u32)blocks, weight};
+  }
+  RadixOperand columns_of(const u32* p, size_t blocks, u32 weight, i32 mul = 1, i32 shift = 0) const {
+    return RadixOperand{p, 1u, (u32)rows, -1, mul, shift, (u32)blocks, weight};
+  }
+  RadixGlueArgs glue(const RadixOperand& a, const RadixOperand& b, u32 j0, u32 nj, bool out_rows, u32* out) const {
+    RadixGlueArgs g{};
+    g.a = a;
+    g.b = b;
+    g.out = out;
+    g.acc = acc;
+    g.tables = ctx->d_radix_tables.as<u32>();
+    g.rows = (u32)rows, g.j0 = j0, g.nj = nj, g.nt = 1;
+    g.out_stride_q = out_rows ? nj : 1u;
+    g.out_stride_j = out_rows ? 1u : (u32)rows;
+    g.out_stride_t = nj * (u32)rows;
+    g.words = (u32)io_words(ctx);
+    g.acc_words = (u32)glwe_words(ctx);
+    g.acc_body = ctx->big_n;
+    g.log_rep = shape.log_rep, g.log_delta = shape.log_delta;
+    g.table_words = 1u << ctx->params.log_p;
+    return g;
+  }
+  void tables(RadixGlueArgs* g, u32 first, u32 count, u32 table) const {
+    for (u32 j = first; j < first + count; ++j) g->sel[j] = (unsigned char)table;
+  }
+  int run(const RadixGlueArgs& g, const u32* in, size_t rotations, u32* out) const {
+    HIP_TRY(ctx, launch::radix_glue(ctx->stream, g));
+    return enqueue_bootstrap(ctx, in, rotations, acc, rotations, ctx->d_lwe_big.as<u32>(), out, AccSource{true, (1u << shape.log_rep) / 2});
+  }
+};
+
+int enqueue_radix_propagate(tfhe_context* ctx, const RadixShape& shape, const u32* in, size_t rows, u32 D, u32* out) {
+  const RadixLevels L(ctx, shape, rows);
+  const RadixOperand none{};
+  const size_t ct = rows * io_words(ctx);  // words of one block of every row
+  // level 1: the message and (D > 1) the carry of every block
+  RadixGlueArgs g = L.glue(L.rows_of(in, D, 1), none, 0, D, D == 1, L.x);
+  g.nt = D == 1 ? 1 : 2;
+  L.tables(&g, 0, D, kRadixMessage);
+  TFHE_TRY(L.run(g, L.x, g.nt * D * rows, D == 1 ? out : L.o));
+  if (D == 1) return TFHE_OK;
+  // w_j = M_j + C_(j-1); level 2: the states of blocks 0 .. D-2
+  g = L.glue(L.columns_of(L.o, D, 1), L.columns_of(L.o + D * ct, D, 1, 1, 1), 0, D, false, L.w);
+  L.tables(&g, 0, 1, kRadixFirstState);
+  L.tables(&g, 1, D - 2, kRadixState);
+  L.tables(&g, D - 1, 1, kRadixNoTable);
+  TFHE_TRY(L.run(g, L.w, (D - 1) * rows, L.s));
+  // prefix levels: blocks below r are complete and stay where they are
+  for (u32 r = 1; r < D - 1; r *= 2) {
+    const u32 nj = D - 1 - r;
+    g = L.glue(L.columns_of(L.s, D - 1, 4), L.columns_of(L.s, D - 1, 1, 1, (i32)r), r, nj, false, L.x);
+    L.tables(&g, 0, std::min(r, nj), kRadixPrefixCarry);
+    if (nj > r) L.tables(&g, r, nj - r, kRadixPrefixState);
+    TFHE_TRY(L.run(g, L.x, nj * rows, L.s + r * ct));
+  }
+  // the carries enter: out_j = (w_j + S_(j-1)) mod Bm
+  g = L.glue(L.columns_of(L.w, D, 1), L.columns_of(L.s, D - 1, 1, 1, 1), 0, D, true, L.x);
+  L.tables(&g, 0, D, kRadixMessage);
+  return L.run(g, L.x, D * rows, out);
+}
+
+int enqueue_radix_compare(tfhe_context* ctx, const RadixShape& shape, const u32* a, const u32* b, size_t rows, u32 D, u32 predicate, u32* out) {
+  const RadixLevels L(ctx, shape, rows);
+  const size_t ct = rows * io_words(ctx);
+  RadixGlueArgs g = L.glue(L.rows_of(a, D, 1u << shape.m), L.rows_of(b, D, 1), 0, D, D == 1, L.x);
+  L.tables(&g, 0, D, D == 1 ? kRadixComparePred + predicate : kRadixCompare);
+  TFHE_TRY(L.run(g, L.x, D * rows, D == 1 ? out : L.s));
+  for (u32 c = D; c > 1; c = c / 2 + c % 2) {
+    // pairs (2j + 1, 2j) into j; with an odd count block 0 passes through and pairs (2j, 2j - 1) go into j >= 1
+    const u32 odd = c % 2, pairs = c / 2;
+    const bool last = pairs + odd == 1;
+    g = L.glue(L.columns_of(L.s, c, 4, 2, odd ? 0 : -1), L.columns_of(L.s, c, 1, 2, odd ? 1 : 0), odd, pairs, false, L.x);
+    L.tables(&g, 0, pairs, last ? kRadixTreePred + predicate : kRadixTree);
+    TFHE_TRY(L.run(g, L.x, pairs * rows, last ? out : L.s + odd * ct));
+  }
+  return TFHE_OK;
+}
+
+struct RadixMapArgs {
+  const u32 *a, *b;
+  size_t a_blocks, b_blocks;
+  u32 wa, wb;
+  i32 a_shift, a_fixed, b_shift, b_fixed;
+  size_t batch, blocks;
+  const u32* tables;
+  size_t table_count;
+  const u32* sel;
+  u32* out;
+};
+
+int check_radix_map(tfhe_context* ctx, const RadixMapArgs& m, RadixShape* shape) {
+  TFHE_TRY(check_present(ctx, {m.a, m.tables, m.sel, m.out}, 1, "null pointer"));
+  TFHE_TRY(check_radix_params(ctx, shape));
+  TFHE_TRY(check_radix_size(ctx, m.batch, m.blocks));
+  if (m.a_blocks == 0 || m.a_blocks > kRadixMaxBlocks || (m.b && (m.b_blocks == 0 || m.b_blocks > kRadixMaxBlocks)))
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "a_blocks and b_blocks must be in [1, " + std::to_string(kRadixMaxBlocks) + "]");
+  if (m.a_fixed >= (i64)m.a_blocks || (m.b && m.b_fixed >= (i64)m.b_blocks))
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "a broadcast block index is out of range");
+  if (m.table_count == 0 || m.table_count > kRadixNoTable)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "table_count must be in [1, " + std::to_string(kRadixNoTable) + "]");
+  for (size_t j = 0; j < m.blocks; ++j)
+    if (m.sel[j] >= m.table_count) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "table index " + std::to_string(m.sel[j]) + " of block " + std::to_string(j) + " is out of range");
+  const size_t io = io_words(ctx), out_words = m.batch * m.blocks * io;
+  TFHE_TRY(check_radix_in_place(ctx, m.out, m.a, m.batch * m.a_blocks * io, out_words, "a"));
+  TFHE_TRY(check_radix_in_place(ctx, m.out, m.b, m.batch * m.b_blocks * io, out_words, "b"));
+  return check_radix_keys(ctx);
+}
+
+int enqueue_radix_map(tfhe_context* ctx, const RadixShape& shape, const RadixMapArgs& m) {
+  const RadixLevels L(ctx, shape, m.batch);
+  RadixOperand a = L.rows_of(m.a, m.a_blocks, m.wa), b = L.rows_of(m.b, m.b ? m.b_blocks : 0, m.wb);
+  a.fixed = m.a_fixed < 0 ? -1 : m.a_fixed, a.shift = m.a_shift;
+  b.fixed = m.b_fixed < 0 ? -1 : m.b_fixed, b.shift = m.b_shift;
+  RadixGlueArgs g = L.glue(a, b, 0, (u32)m.blocks, true, L.x);
+  g.tables = m.tables;
+  for (size_t j = 0; j < m.blocks; ++j) g.sel[j] = (unsigned char)m.sel[j];
+  return L.run(g, L.x, m.blocks * m.batch, m.out);
+}
+
+int check_radix_propagate(tfhe_context* ctx, const void* in, size_t batch, size_t blocks, const void* out, RadixShape* shape) {
+  TFHE_TRY(check_present(ctx, {in, out}, 1, "null pointer"));
+  TFHE_TRY(check_radix_params(ctx, shape));
+  TFHE_TRY(check_radix_size(ctx, batch, blocks));
+  const size_t words = batch * blocks * io_words(ctx);
+  TFHE_TRY(check_radix_in_place(ctx, out, in, words, words, "blocks_in"));
+  return check_radix_keys(ctx);
+}
+
+int check_radix_compare(tfhe_context* ctx, const void* a, const void* b, size_t batch, size_t blocks, unsigned predicate, const void* out,
+                        RadixShape* shape) {
+  TFHE_TRY(check_present(ctx, {a, b, out}, 1, "null pointer"));
+  TFHE_TRY(check_radix_params(ctx, shape));
+  TFHE_TRY(check_radix_size(ctx, batch, blocks));
+  if (predicate > TFHE_RADIX_GE) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "predicate must be one of TFHE_RADIX_EQ .. TFHE_RADIX_GE");
+  const size_t io = io_words(ctx);
+  // the result is written by the last level only, after every read of a and b: row 0 of either is "in place"
+  TFHE_TRY(check_radix_in_place(ctx, out, a, batch * blocks * io, batch * io, "a"));
+  TFHE_TRY(check_radix_in_place(ctx, out, b, batch * blocks * io, batch * io, "b"));
+  return check_radix_keys(ctx);
+}
+
+}  // namespace
+
+int tfhe_context_reserve_radix(tfhe_context* ctx, size_t max_batch, size_t max_blocks) {
+  TFHE_TRY(check_ctx(ctx));
+  TFHE_TRY(check_radix_size(ctx, max_batch, max_blocks));
+  return reserve_radix(ctx, max_batch, max_blocks);
+}
+
+int tfhe_radix_propagate_batch_device(tfhe_context* ctx, const uint32_t* blocks_in, size_t batch, size_t blocks, uint32_t* blocks_out) {
+  TFHE_TRY(check_ctx(ctx));
+  RadixShape shape;
+  TFHE_TRY(check_radix_propagate(ctx, blocks_in, batch, blocks, blocks_out, &shape));
+  TFHE_TRY(check_radix_reserved(ctx, batch, blocks));
+  return enqueue_radix_propagate(ctx, shape, blocks_in, batch, (u32)blocks, blocks_out);
+}
+
+int tfhe_radix_propagate_batch(tfhe_context* ctx, const uint32_t* blocks_in, size_t batch, size_t blocks, uint32_t* blocks_out) {
+  TFHE_TRY(check_ctx(ctx));
+  RadixShape shape;
+  TFHE_TRY(check_radix_propagate(ctx, blocks_in, batch, blocks, blocks_out, &shape));
+  TFHE_TRY(reserve_radix(ctx, batch, blocks));
+  Staging s(ctx, {batch * blocks * io_words(ctx)});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(0, blocks_in));
+  TFHE_TRY(enqueue_radix_propagate(ctx, shape, s[0], batch, (u32)blocks, s[0]));
+  return s.download_and_wait(0, blocks_out);
+}
+
+int tfhe_radix_compare_batch_device(tfhe_context* ctx, const uint32_t* a, const uint32_t* b, size_t batch, size_t blocks, unsigned predicate,
+                                    uint32_t* out) {
+  TFHE_TRY(check_ctx(ctx));
+  RadixShape shape;
+  TFHE_TRY(check_radix_compare(ctx, a, b, batch, blocks, predicate, out, &shape));
+  TFHE_TRY(check_radix_reserved(ctx, batch, blocks));
+  return enqueue_radix_compare(ctx, shape, a, b, batch, (u32)blocks, predicate, out);
+}
+
+int tfhe_radix_compare_batch(tfhe_context* ctx, const uint32_t* a, const uint32_t* b, size_t batch, size_t blocks, unsigned predicate,
+                             uint32_t* out) {
+  TFHE_TRY(check_ctx(ctx));
+  RadixShape shape;
+  TFHE_TRY(check_radix_compare(ctx, a, b, batch, blocks, predicate, out, &shape));
+  TFHE_TRY(reserve_radix(ctx, batch, blocks));
+  const size_t io = io_words(ctx);
+  enum { kA, kB, kOut };
+  Staging s(ctx, {batch * blocks * io, batch * blocks * io, batch * io});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(kA, a));
+  TFHE_TRY(s.upload(kB, b));
+  TFHE_TRY(enqueue_radix_compare(ctx, shape, s[kA], s[kB], batch, (u32)blocks, predicate, s[kOut]));
+  return s.download_and_wait(kOut, out);
+}
+
+int tfhe_radix_map_batch_device(tfhe_context* ctx, const uint32_t* a, size_t a_blocks, uint32_t wa, int32_t a_shift, int32_t a_fixed,
+                                const uint32_t* b, size_t b_blocks, uint32_t wb, int32_t b_shift, int32_t b_fixed, size_t batch, size_t blocks,
+                                const uint32_t* tables, size_t table_count, const uint32_t* table_of_block, uint32_t* out) {
+  TFHE_TRY(check_ctx(ctx));
+  const RadixMapArgs m{a, b, a_blocks, b_blocks, wa, wb, a_shift, a_fixed, b_shift, b_fixed, batch, blocks, tables, table_count, table_of_block, out};
+  RadixShape shape;
+  TFHE_TRY(check_radix_map(ctx, m, &shape));
+  TFHE_TRY(check_radix_reserved(ctx, batch, blocks));
+  return enqueue_radix_map(ctx, shape, m);
+}
+
+int tfhe_radix_map_batch(tfhe_context* ctx, const uint32_t* a, size_t a_blocks, uint32_t wa, int32_t a_shift, int32_t a_fixed,
+                         const uint32_t* b, size_t b_blocks, uint32_t wb, int32_t b_shift, int32_t b_fixed, size_t batch, size_t blocks,
+                         const uint32_t* tables, size_t table_count, const uint32_t* table_of_block, uint32_t* out) {
+  TFHE_TRY(check_ctx(ctx));
+  RadixMapArgs m{a, b, a_blocks, b_blocks, wa, wb, a_shift, a_fixed, b_shift, b_fixed, batch, blocks, tables, table_count, table_of_block, out};
+  RadixShape shape;
+  TFHE_TRY(check_radix_map(ctx, m, &shape));
+  const size_t P = (size_t)1 << ctx->params.log_p;
+  for (size_t i = 0; i < table_count * P; ++i)
+    if (tables[i] >= P) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "table value >= 2^log_p");
+  TFHE_TRY(reserve_radix(ctx, batch, blocks));
+  const size_t io = io_words(ctx);
+  enum { kA, kB, kTables, kOut };
+  Staging s(ctx, {batch * a_blocks * io, b ? batch * b_blocks * io : 0, table_count * P, batch * blocks * io});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(s.upload(kA, a));
+  if (b) TFHE_TRY(s.upload(kB, b));
+  TFHE_TRY(s.upload(kTables, tables));
+  m.a = s[kA], m.b = b ? s[kB] : nullptr, m.tables = s[kTables], m.out = s[kOut];
+  TFHE_TRY(enqueue_radix_map(ctx, shape, m));
+  return s.download_and_wait(kOut, out);
+}
+
 // ---------------------------------------------------------------------------------- on-disk format
 namespace {
 

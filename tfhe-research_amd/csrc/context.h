@@ -115,6 +115,13 @@ struct tfhe_context {
   // buffers of the same rows (the host forms' and the wide LUT's digits)
   DeviceBuffer d_extract_ws;
   size_t extract_batch = 0, extract_digits = 0;
+  // radix integers (tfhe_context_reserve_radix).  With R = 2 radix_batch radix_blocks rotations and rows of
+  // max(n, k N) + 1 words: a level's inputs x [R], level 1's results o [R], the sums w [R / 2] and the states s [R / 2],
+  // all [block][row] between two levels, then a level's accumulators [R][k+1][N].  d_radix_tables: the fixed tables
+  // [kRadixTables][2^log_p] (radix.h::RadixTable), written once by the first reservation.
+  DeviceBuffer d_radix_ws;
+  DeviceBuffer d_radix_tables;
+  size_t radix_batch = 0, radix_blocks = 0;
   // multi-value bootstrap.  d_mv_const (allocated by tfhe_context_reserve_multi_value, by tfhe_context_set_tree_lut_level0(1)
   // and by the host forms): the constant accumulator (0, .., 0, kappa (1 + X + .. + X^(N-1))) [k+1][N], the B + 1 positions
   // of a lookup table's coefficients [kSparseMaxTerms], a caller's positions [kSparseMaxTerms].  d_mv_ws

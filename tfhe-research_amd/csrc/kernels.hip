@@ -16,6 +16,7 @@
 #include "lwe_extract.h"
 #include "multi_value.h"
 #include "passes.h"
+#include "radix.h"
 
 namespace tfhe {
 namespace {
@@ -1256,6 +1257,14 @@ struct ExtractThread {
   __device__ size_t threads() const { return (size_t)gridDim.x * blockDim.x; }
 };
 __global__ void __launch_bounds__(kExtractThreads) extract_step_kernel(ExtractStepArgs a) { extract_step(ExtractThread(), a); }
+
+// ------------------------------------------------------------------------------ radix integers
+// radix.h::radix_glue states the launch between two bootstrap levels; this is its thread context on the device.
+struct RadixThread {
+  __device__ size_t index() const { return (size_t)blockIdx.x * blockDim.x + threadIdx.x; }
+  __device__ size_t threads() const { return (size_t)gridDim.x * blockDim.x; }
+};
+__global__ void __launch_bounds__(kRadixThreads) radix_glue_kernel(RadixGlueArgs a) { radix_glue(RadixThread(), a); }
 
 // ------------------------------------------------------------------------------ multi-value bootstrap
 // multi_value.h::sparse_extract_tile states the per-table step; this is its workgroup context on the device.  The
@@ -2650,6 +2659,16 @@ hipError_t extract_step(hipStream_t s, const ExtractStepArgs& a) {
   if (a.total == 0 || a.words == 0 || (a.r_shift | a.d_shift | a.s_shift) > 31u) return hipErrorInvalidValue;
   // a thread owns four words at a time
   hipLaunchKernelGGL(extract_step_kernel, dim3(grid_for((a.total + 3) / 4, kExtractThreads)), dim3(kExtractThreads), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t radix_glue(hipStream_t s, const RadixGlueArgs& a) {
+  const size_t rotations = (size_t)a.nt * a.nj * a.rows;
+  if (rotations == 0 || a.words == 0 || !a.out || a.nj > kRadixMaxBlocks || (a.acc && (!a.tables || a.acc_words % 4 != 0 || a.log_delta > 31u)))
+    return hipErrorInvalidValue;
+  // a thread owns one word of a ciphertext, then four of an accumulator
+  const size_t work = std::max(rotations * a.words, a.acc ? rotations * (a.acc_words / 4) : (size_t)0);
+  hipLaunchKernelGGL(radix_glue_kernel, dim3(grid_for(work, kRadixThreads)), dim3(kRadixThreads), 0, s, a);
   return hipGetLastError();
 }
 

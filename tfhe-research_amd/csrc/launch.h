@@ -10,6 +10,7 @@
 #include "multi_value.h"
 #include "multibit.h"
 #include "pbs_wave.h"
+#include "radix.h"
 
 namespace tfhe {
 namespace launch {
@@ -198,6 +199,10 @@ hipError_t dense_tile_rows(hipStream_t s, const u32* in, size_t period, size_t c
 // ---- digit extraction (lwe_extract.h::extract_step): the one elementwise launch between two sign bootstraps.
 // hipErrorInvalidValue: an empty call or a shift above 31
 hipError_t extract_step(hipStream_t s, const ExtractStepArgs& a);
+
+// ---- radix integers (radix.h::radix_glue): the one elementwise launch in front of a bootstrap level.
+// hipErrorInvalidValue: no rotation, more than kRadixMaxBlocks blocks, accumulators without tables
+hipError_t radix_glue(hipStream_t s, const RadixGlueArgs& a);
 
 // ---- multi-value bootstrap (multi_value.h::sparse_extract_tile): out [batch][tables][k N + 1], the signed gather of
 // `terms` sample extractions of glwe [batch][k+1][N] at positions [terms] (device) times coeffs [1 or batch][tables][terms].
