@@ -749,6 +749,72 @@ inline LweCiphertext radix_compare(Engine& e, const RadixCiphertext& a, const Ra
   e.check(tfhe_radix_compare_batch(e.raw(), a.data.data(), b.data.data(), 1, a.blocks, predicate, out.data.data()));
   return out;
 }
+// ---- seeded ciphertexts and compressed keys (tfhe_hip.h states the generator, the layouts and the security rule) ----
+// A seeded object is a seed and the bodies; the masks are G(seed, domain) (tfhe_seed_words).  NEVER use one
+// (key, domain, stream) for two objects under the same secret key.
+struct SeededLweRows {
+  tfhe_seed seed{};
+  size_t dimension = 0;
+  std::vector<uint32_t> bodies;  // [rows]
+};
+struct SeededGlweRows {
+  tfhe_seed seed{};
+  std::vector<uint32_t> bodies;  // [rows][N]
+};
+// G(seed, domain)[first_word .. first_word + count): host code, no engine
+inline std::vector<uint32_t> seed_words(const tfhe_seed& seed, uint32_t domain, uint64_t first_word, size_t count) {
+  std::vector<uint32_t> out(count);
+  if (int st = tfhe_seed_words(&seed, domain, first_word, count, out.data())) throw TfheError(st, "seed_words: the word range must stay within 2^36");
+  return out;
+}
+// rows [first_row, first_row + rows) of the seeded object -> [rows][dimension + 1] / [rows][k+1][N]
+inline std::vector<uint32_t> expand_lwe_rows(Engine& e, const SeededLweRows& x, uint64_t first_row = 0) {
+  std::vector<uint32_t> out(x.bodies.size() * (x.dimension + 1));
+  e.check(tfhe_expand_lwe_rows(e.raw(), &x.seed, x.bodies.data(), first_row, x.bodies.size(), x.dimension, out.data()));
+  return out;
+}
+inline std::vector<uint32_t> expand_glwe_rows(Engine& e, const SeededGlweRows& x, uint64_t first_row = 0) {
+  const size_t n = e.params().degree(), rows = x.bodies.size() / n;
+  if (rows == 0 || x.bodies.size() != rows * n) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "expand_glwe_rows: bodies [rows][N]");
+  std::vector<uint32_t> out(rows * (e.params().glwe_dimension + 1) * n);
+  e.check(tfhe_expand_glwe_rows(e.raw(), &x.seed, x.bodies.data(), first_row, rows, out.data()));
+  return out;
+}
+// the bodies of full rows
+inline std::vector<uint32_t> compress_lwe_rows(Engine& e, const std::vector<uint32_t>& lwe, size_t dimension) {
+  const size_t rows = lwe.size() / (dimension + 1);
+  if (rows == 0 || lwe.size() != rows * (dimension + 1)) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "compress_lwe_rows: lwe [rows][dimension + 1]");
+  std::vector<uint32_t> out(rows);
+  e.check(tfhe_compress_lwe_rows(e.raw(), lwe.data(), rows, dimension, out.data()));
+  return out;
+}
+inline std::vector<uint32_t> compress_glwe_rows(Engine& e, const std::vector<uint32_t>& glwe) {
+  const size_t n = e.params().degree(), row = (e.params().glwe_dimension + 1) * n, rows = glwe.size() / row;
+  if (rows == 0 || glwe.size() != rows * row) throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "compress_glwe_rows: glwe [rows][k+1][N]");
+  std::vector<uint32_t> out(rows * n);
+  e.check(tfhe_compress_glwe_rows(e.raw(), glwe.data(), rows, out.data()));
+  return out;
+}
+// the key from its seeded form: bsk bodies [n][(k+1)l][N], ksk bodies [kN l_ks] of dimension n (first device only)
+inline void load_bootstrapping_key_seeded(Engine& e, const SeededGlweRows& bsk, const SeededLweRows& ksk) {
+  const TfheParams& p = e.params();
+  if (bsk.bodies.size() != size_t(p.lwe_dimension) * p.ggsw_rows() * p.degree() || ksk.dimension != p.lwe_dimension ||
+      ksk.bodies.size() != p.lwe_dimension_post_pbs() * p.ks_decomposer.levels)
+    throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "load_bootstrapping_key_seeded: bsk bodies [n][(k+1)l][N], ksk bodies [kN l_ks] of dimension n");
+  e.check(tfhe_load_bootstrapping_key_seeded(e.raw(), &bsk.seed, bsk.bodies.data(), &ksk.seed, ksk.bodies.data()));
+}
+// bootstrap() of seeded inputs (rows first_row .. of the seed, the reference's bootstrap order: dimension n)
+inline std::vector<LweCiphertext> bootstrap_seeded(Engine& e, const SeededLweRows& x, const std::vector<uint32_t>& test_vector_poly,
+                                                   uint64_t first_row = 0) {
+  const size_t width = size_t(e.params().lwe_dimension) + 1, batch = x.bodies.size();
+  if (batch == 0 || x.dimension + 1 != width || test_vector_poly.size() != e.params().degree())
+    throw TfheError(TFHE_ERR_INVALID_ARGUMENT, "bootstrap_seeded: seeded rows of dimension n and one test vector [N]");
+  std::vector<uint32_t> flat(batch * width);
+  e.check(tfhe_bootstrap_batch_seeded(e.raw(), &x.seed, first_row, x.bodies.data(), batch, test_vector_poly.data(), 1, flat.data()));
+  std::vector<LweCiphertext> out(batch);
+  for (size_t i = 0; i < batch; ++i) out[i].data.assign(flat.begin() + i * width, flat.begin() + (i + 1) * width);
+  return out;
+}
 // ---- encrypted dense layers (tfhe_hip.h states the operations; first device only) ----
 // Dense(W, bias; x) for ONE query: x holds the I input ciphertexts (all of one length), weights [O][I] row-major int32,
 // bias [O] already ENCODED words or empty -> O ciphertexts of that length, out[o] = sum_i W[o][i] x[i] (+ bias[o] on the body)

@@ -1217,6 +1217,89 @@ int tfhe_bootstrapping_key_gen_bmmp_device(tfhe_context *ctx, const uint32_t *lw
                                            const uint32_t *glwe_sk, uint32_t *bsk_bmmp, uint32_t *ksk,
                                            int load);
 
+/* ---- seeded ciphertexts and compressed keys (no reference counterpart) ------------------------------------------------
+ * The uniform mask words of a fresh ciphertext or of a key are public randomness; only the bodies depend on the key, the
+ * message and the noise.  A seeded object is a short seed plus the bodies, and the masks are re-derived here by a public,
+ * deterministic expansion function.  Secrets and errors are still the caller's draws (see "encryption side" above): this
+ * is not a random number generator for them.
+ *
+ * The generator.  G(seed, domain)[w], for w < TFHE_SEED_MAX_WORDS = 2^36, is word (w mod 16) of the ChaCha20 block
+ * function of RFC 8439 section 2.3 (20 rounds) with
+ *   key           = seed.key, as eight little-endian words,
+ *   block counter = w div 16 (below 2^32),
+ *   nonce words   = (domain, low half of seed.stream, high half of seed.stream),
+ *   output        = the sixteen state words after the final addition, as uint32_t.
+ * With key bytes 00..1f, domain = 0x09000000 and stream = 0x4a000000 the words 16..31 are the RFC's own vector (2.3.2):
+ * e4e7f110 15593bd1 ...  4e3c50a2.  tfhe_seed_words is the definition: host code, no context, no GPU.
+ *
+ * Layouts.  Seeded LWE rows are bodies[rows] plus a dimension d:
+ *   full[r][j] = G(seed, TFHE_SEED_DOMAIN_LWE)[(first_row + r) d + j] for j < d,  full[r][d] = bodies[r]
+ * (LWE batches of either boundary dimension, the key-switching key).  Seeded GLWE rows are bodies[rows][N]:
+ *   full[r][i][j] = G(seed, TFHE_SEED_DOMAIN_GLWE)[((first_row + r) k + i) N + j] for i < k,  full[r][k][.] = bodies[r][.]
+ * (GLWE, GGSW, the bootstrapping key -- ordinary, BMMP, multi-bit --, the packing key, the GLWE switch keys: all rows of
+ * [k+1][N]).  first_row: a shard or a chunk expands rows [first_row, first_row + rows) of a larger object without the
+ * rest.
+ *
+ * GGSWs.  Row (i, level) of a GGSW in the reference's form (ggsw.rs:76-130) is an encryption of zero plus m g_level on
+ * polynomial i, and for i < k that is a MASK polynomial: a' = a + m g_level e_i.  a' is as uniform as a, so the seeded form
+ * takes a' = G(seed) and the body says the rest: b = <a', s> + e - m g_level s_i for i < k (and b = <a', s> + e + m g_level for
+ * i = k, as ever).  The expansion is then a GGSW of the reference's form, bit for bit what tfhe_ggsw_encrypt_batch makes
+ * from masks a' - m g_level e_i.  The encryption side needs no entry of its own for it: fill the masks, take m g_level off
+ * coefficient 0 of mask polynomial i, call tfhe_ggsw_encrypt_batch or the key generation, compress (the Python helpers
+ * do).  Rows of LWE and GLWE ciphertexts and of the key-switching key carry their message in the body and need nothing.
+ *
+ * SECURITY RULE.  One (key, domain, stream) must never produce the masks of two objects encrypted under the same secret
+ * key: with equal masks the difference of their bodies is the difference of their messages and errors, in the clear.
+ * Draw a fresh 256-bit key per object (the Python helpers do, from the operating system's generator), or number the
+ * objects of one client key with `stream`; row ranges of ONE object share its seed and are told apart by first_row.
+ *
+ * Entry points.  The seed is a HOST struct in both forms and reaches the kernel by value: a captured _device expansion
+ * replays its seed (and first_row); only the bodies and the output are read through their pointers at replay.
+ * bodies == NULL: the body words of the output are left as they are -- the mask fill of the encryption side (put the
+ * errors in the bodies, fill the masks, call the encrypt / keygen entry, compress).
+ * Refused with TFHE_ERR_INVALID_ARGUMENT, nothing enqueued and nothing written: a NULL seed or output (compress: input
+ * or output); rows == 0 or dimension == 0 (or a dimension of 2^31 or more); a word range that reaches past
+ * TFHE_SEED_MAX_WORDS ((first_row + rows) d > 2^36); any overlap of `bodies` and the output; any overlap of input and
+ * output in compress.  BMMP, multi-bit, packing and switch keys need no entry of their own: expand on the device, then
+ * call the existing _device loader or prepare. */
+typedef struct tfhe_seed {
+    uint32_t key[8];
+    uint64_t stream;
+} tfhe_seed;
+#define TFHE_SEED_DOMAIN_LWE 0x3145574cu  /* "LWE1" */
+#define TFHE_SEED_DOMAIN_GLWE 0x31574c47u /* "GLW1" */
+#define TFHE_SEED_MAX_WORDS (1ull << 36)
+/* out[i] = G(seed, domain)[first_word + i] for i < count; TFHE_ERR_INVALID_ARGUMENT: NULL seed or out (count != 0), or
+ * first_word + count > TFHE_SEED_MAX_WORDS */
+int tfhe_seed_words(const tfhe_seed *seed, uint32_t domain, uint64_t first_word, size_t count, uint32_t *out);
+/* lwe_out [rows][dimension+1]: masks from the seed, bodies [rows] into the last word of each row (or left, NULL) */
+int tfhe_expand_lwe_rows(tfhe_context *ctx, const tfhe_seed *seed, const uint32_t *bodies, uint64_t first_row, size_t rows,
+                         size_t dimension, uint32_t *lwe_out);
+int tfhe_expand_lwe_rows_device(tfhe_context *ctx, const tfhe_seed *seed, const uint32_t *bodies, uint64_t first_row,
+                                size_t rows, size_t dimension, uint32_t *lwe_out);
+/* glwe_out [rows][k+1][N]: the k mask polynomials from the seed, bodies [rows][N] into the last (or left, NULL) */
+int tfhe_expand_glwe_rows(tfhe_context *ctx, const tfhe_seed *seed, const uint32_t *bodies, uint64_t first_row, size_t rows,
+                          uint32_t *glwe_out);
+int tfhe_expand_glwe_rows_device(tfhe_context *ctx, const tfhe_seed *seed, const uint32_t *bodies, uint64_t first_row,
+                                 size_t rows, uint32_t *glwe_out);
+/* the strided gathers of the bodies: bodies_out [rows] of lwe [rows][dimension+1], bodies_out [rows][N] of glwe
+ * [rows][k+1][N] */
+int tfhe_compress_lwe_rows(tfhe_context *ctx, const uint32_t *lwe, size_t rows, size_t dimension, uint32_t *bodies_out);
+int tfhe_compress_lwe_rows_device(tfhe_context *ctx, const uint32_t *lwe, size_t rows, size_t dimension,
+                                  uint32_t *bodies_out);
+int tfhe_compress_glwe_rows(tfhe_context *ctx, const uint32_t *glwe, size_t rows, uint32_t *bodies_out);
+int tfhe_compress_glwe_rows_device(tfhe_context *ctx, const uint32_t *glwe, size_t rows, uint32_t *bodies_out);
+/* Host forms only.  tfhe_load_bootstrapping_key from the seeded key: bsk_bodies [n][(k+1)l][N] are GLWE rows 0 ..
+ * n (k+1) l - 1 of bsk_seed, ksk_bodies [kN*l_ks] are LWE rows of dimension n of ksk_seed.  The bodies are uploaded, the
+ * arrays expanded into a temporary device buffer and handed to tfhe_load_bootstrapping_key_device: the prepared key is
+ * byte-identical to the one tfhe_load_bootstrapping_key builds from the expanded arrays. */
+int tfhe_load_bootstrapping_key_seeded(tfhe_context *ctx, const tfhe_seed *bsk_seed, const uint32_t *bsk_bodies,
+                                       const tfhe_seed *ksk_seed, const uint32_t *ksk_bodies);
+/* tfhe_bootstrap_batch on seeded inputs: bodies [batch] are LWE rows first_row .. first_row + batch - 1 of `seed` at the
+ * context's boundary dimension (n, or k N with the key switch first); batch words go up instead of batch (dimension + 1) */
+int tfhe_bootstrap_batch_seeded(tfhe_context *ctx, const tfhe_seed *seed, uint64_t first_row, const uint32_t *bodies,
+                                size_t batch, const uint32_t *test_vector_poly, size_t tv_count, uint32_t *lwe_out);
+
 /* ---- bootstrap order --------------------------------------------------------------
  * 0 (default): the reference's order, PBS then key switch (bootstrapping.rs:58-120): ciphertexts at
  * the boundary have n+1 words.

@@ -95,6 +95,18 @@ extern "C" {
                             table_count: usize, table_of_block: *const u32, out: *mut u32) -> c_int;
     fn tfhe_radix_compare_batch(ctx: *mut TfheContext, a: *const u32, b: *const u32, batch: usize, blocks: usize, predicate: c_uint,
                                 out: *mut u32) -> c_int;
+    // seeded ciphertexts and compressed keys (include/tfhe_hip.h)
+    fn tfhe_seed_words(seed: *const TfheSeed, domain: u32, first_word: u64, count: usize, out: *mut u32) -> c_int;
+    fn tfhe_expand_lwe_rows(ctx: *mut TfheContext, seed: *const TfheSeed, bodies: *const u32, first_row: u64, rows: usize, dimension: usize,
+                            lwe_out: *mut u32) -> c_int;
+    fn tfhe_expand_glwe_rows(ctx: *mut TfheContext, seed: *const TfheSeed, bodies: *const u32, first_row: u64, rows: usize,
+                             glwe_out: *mut u32) -> c_int;
+    fn tfhe_compress_lwe_rows(ctx: *mut TfheContext, lwe: *const u32, rows: usize, dimension: usize, bodies_out: *mut u32) -> c_int;
+    fn tfhe_compress_glwe_rows(ctx: *mut TfheContext, glwe: *const u32, rows: usize, bodies_out: *mut u32) -> c_int;
+    fn tfhe_load_bootstrapping_key_seeded(ctx: *mut TfheContext, bsk_seed: *const TfheSeed, bsk_bodies: *const u32, ksk_seed: *const TfheSeed,
+                                          ksk_bodies: *const u32) -> c_int;
+    fn tfhe_bootstrap_batch_seeded(ctx: *mut TfheContext, seed: *const TfheSeed, first_row: u64, bodies: *const u32, batch: usize,
+                                   test_vector_poly: *const u32, tv_count: usize, lwe_out: *mut u32) -> c_int;
     // multi-value bootstrapping (include/tfhe_hip.h)
     fn tfhe_multi_value_bootstrap_batch(ctx: *mut TfheContext, lwe_in: *const u32, batch: usize, luts: *const u32, lut_sets: usize,
                                         tables: usize, lwe_out: *mut u32) -> c_int;
@@ -548,6 +560,94 @@ pub fn radix_compare(bk: &GpuBootstrappingKey, a: &Array3<u32>, b: &Array3<u32>,
         tfhe_radix_compare_batch(bk.ctx, a.as_slice().unwrap().as_ptr(), b.as_slice().unwrap().as_ptr(), batch, blocks, predicate as c_uint,
                                  out.as_slice_mut().unwrap().as_mut_ptr())
     }, "radix_compare");
+    out
+}
+
+/// The public seed of a seeded object (tfhe_seed): a 256-bit key and a stream number.  One (key, domain, stream) must never
+/// produce the masks of two objects under the same secret key.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct TfheSeed { pub key: [u32; 8], pub stream: u64 }
+
+pub const SEED_DOMAIN_LWE: u32 = 0x3145574c;
+pub const SEED_DOMAIN_GLWE: u32 = 0x31574c47;
+
+/// G(seed, domain)[first_word .. first_word + count): the definition of the mask generator (host code, no GPU).
+pub fn seed_words(seed: &TfheSeed, domain: u32, first_word: u64, count: usize) -> Array1<u32> {
+    let mut out = Array1::<u32>::zeros(count);
+    let st = unsafe { tfhe_seed_words(seed, domain, first_word, count, out.as_slice_mut().unwrap().as_mut_ptr()) };
+    assert!(st == 0, "seed_words: the word range must stay within 2^36");
+    out
+}
+
+/// Seeded LWE rows: `bodies` (rows) of rows first_row.. of `seed` -> (rows, dimension + 1).
+pub fn expand_lwe_rows(bk: &GpuBootstrappingKey, seed: &TfheSeed, bodies: &Array1<u32>, first_row: u64, dimension: usize) -> Array2<u32> {
+    let rows = bodies.len();
+    assert!(rows >= 1 && dimension >= 1, "expand_lwe_rows: at least one row and one mask word");
+    let mut out = Array2::<u32>::zeros((rows, dimension + 1));
+    check(bk.ctx, unsafe {
+        tfhe_expand_lwe_rows(bk.ctx, seed, bodies.as_slice().unwrap().as_ptr(), first_row, rows, dimension, out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "expand_lwe_rows");
+    out
+}
+
+/// Seeded GLWE rows: `bodies` (rows, N) of rows first_row.. of `seed` -> (rows, k+1, N).
+pub fn expand_glwe_rows(bk: &GpuBootstrappingKey, seed: &TfheSeed, bodies: &Array2<u32>, first_row: u64) -> Array3<u32> {
+    let (rows, n) = bodies.dim();
+    assert!(rows >= 1 && n == 1usize << bk.params.glwe_poly_degree, "expand_glwe_rows: bodies (rows, N)");
+    let mut out = Array3::<u32>::zeros((rows, bk.params.glwe_dimension as usize + 1, n));
+    check(bk.ctx, unsafe {
+        tfhe_expand_glwe_rows(bk.ctx, seed, bodies.as_slice().unwrap().as_ptr(), first_row, rows, out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "expand_glwe_rows");
+    out
+}
+
+/// The bodies (rows) of full LWE rows (rows, dimension + 1).
+pub fn compress_lwe_rows(bk: &GpuBootstrappingKey, lwe: &Array2<u32>) -> Array1<u32> {
+    let (rows, width) = lwe.dim();
+    assert!(rows >= 1 && width >= 2, "compress_lwe_rows: lwe (rows, dimension + 1)");
+    let mut out = Array1::<u32>::zeros(rows);
+    check(bk.ctx, unsafe {
+        tfhe_compress_lwe_rows(bk.ctx, lwe.as_slice().unwrap().as_ptr(), rows, width - 1, out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "compress_lwe_rows");
+    out
+}
+
+/// The body polynomials (rows, N) of full GLWE rows (rows, k+1, N).
+pub fn compress_glwe_rows(bk: &GpuBootstrappingKey, glwe: &Array3<u32>) -> Array2<u32> {
+    let (rows, polys, n) = glwe.dim();
+    assert!(rows >= 1 && polys == bk.params.glwe_dimension as usize + 1 && n == 1usize << bk.params.glwe_poly_degree, "compress_glwe_rows: glwe (rows, k+1, N)");
+    let mut out = Array2::<u32>::zeros((rows, n));
+    check(bk.ctx, unsafe {
+        tfhe_compress_glwe_rows(bk.ctx, glwe.as_slice().unwrap().as_ptr(), rows, out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "compress_glwe_rows");
+    out
+}
+
+/// Replace the loaded key by its seeded form: bsk bodies (n (k+1) l, N) under `bsk_seed`, ksk bodies (kN l_ks) of dimension n
+/// under `ksk_seed`; the masks are expanded on the device.
+pub fn load_bootstrapping_key_seeded(bk: &GpuBootstrappingKey, bsk_seed: &TfheSeed, bsk_bodies: &Array2<u32>, ksk_seed: &TfheSeed,
+                                     ksk_bodies: &Array1<u32>) {
+    let p = &bk.params;
+    let n = 1usize << p.glwe_poly_degree;
+    assert!(bsk_bodies.dim() == (p.lwe_dimension as usize * (p.glwe_dimension as usize + 1) * p.pbs_decomposer.levels as usize, n)
+            && ksk_bodies.len() == p.glwe_dimension as usize * n * p.ks_decomposer.levels as usize,
+            "load_bootstrapping_key_seeded: bsk bodies (n (k+1) l, N), ksk bodies (kN l_ks)");
+    check(bk.ctx, unsafe {
+        tfhe_load_bootstrapping_key_seeded(bk.ctx, bsk_seed, bsk_bodies.as_slice().unwrap().as_ptr(), ksk_seed, ksk_bodies.as_slice().unwrap().as_ptr())
+    }, "load_bootstrapping_key_seeded");
+}
+
+/// bootstrap_batch on seeded inputs: `bodies` (batch) are rows first_row.. of `seed` at dimension n.
+pub fn bootstrap_batch_seeded(bk: &GpuBootstrappingKey, seed: &TfheSeed, first_row: u64, bodies: &Array1<u32>,
+                              test_vector_poly: &Array1<u32>) -> Array2<u32> {
+    let batch = bodies.len();
+    assert!(batch >= 1 && test_vector_poly.len() == 1usize << bk.params.glwe_poly_degree, "bootstrap_batch_seeded: one test vector (N)");
+    let mut out = Array2::<u32>::zeros((batch, bk.params.lwe_dimension as usize + 1));
+    check(bk.ctx, unsafe {
+        tfhe_bootstrap_batch_seeded(bk.ctx, seed, first_row, bodies.as_slice().unwrap().as_ptr(), batch,
+                                    test_vector_poly.as_slice().unwrap().as_ptr(), 1, out.as_slice_mut().unwrap().as_mut_ptr())
+    }, "bootstrap_batch_seeded");
     out
 }
 

@@ -525,6 +525,113 @@ class SystemRng:
         return (loc + scale * z).reshape(shape)
 
 
+# -- seeded ciphertexts and compressed keys (include/tfhe_hip.h, "seeded ciphertexts") ----------------------------
+SEED_DOMAIN_LWE = 0x3145574C
+SEED_DOMAIN_GLWE = 0x31574C47
+SEED_MAX_WORDS = 1 << 36
+
+
+class _CSeed(C.Structure):
+    _fields_ = [("key", C.c_uint32 * 8), ("stream", C.c_uint64)]
+
+
+class Seed:
+    """The public seed of a seeded object: a 256-bit key (eight 32-bit words) and a 64-bit stream number.  SECURITY: one
+    (key, domain, stream) must never produce the masks of two objects encrypted under the same secret key -- the
+    difference of their bodies would be in the clear.  Seed.fresh() draws a new key for every object."""
+
+    def __init__(self, key, stream: int = 0):
+        self.key = tuple(int(w) & 0xFFFFFFFF for w in np.asarray(key, dtype=np.uint64).reshape(-1))
+        self.stream = int(stream) & 0xFFFFFFFFFFFFFFFF
+        if len(self.key) != 8:
+            raise _invalid("Seed: a key of eight 32-bit words expected")
+
+    @classmethod
+    def fresh(cls, rng=None, stream: int = 0) -> "Seed":
+        """a new 256-bit key from the operating system's CSPRNG (`rng=` is a test hook, as in generate_keys)"""
+        rng = rng if rng is not None else SystemRng()
+        return cls(rng.integers(0, 1 << 32, size=8, dtype=np.uint64), stream)
+
+    def words(self) -> np.ndarray:
+        """the ten words a seed is stored as: the key, then the low and the high half of the stream"""
+        return np.array(self.key + (self.stream & 0xFFFFFFFF, self.stream >> 32), dtype=np.uint32)
+
+    @classmethod
+    def from_words(cls, words) -> "Seed":
+        w = [int(v) for v in np.asarray(words).reshape(-1)]
+        if len(w) != 10:
+            raise _invalid("Seed.from_words: ten words expected")
+        return cls(w[:8], w[8] | (w[9] << 32))
+
+    def _c(self) -> _CSeed:
+        return _CSeed((C.c_uint32 * 8)(*self.key), self.stream)
+
+    def __eq__(self, other):
+        return isinstance(other, Seed) and (self.key, self.stream) == (other.key, other.stream)
+
+    def __repr__(self):
+        return "Seed(key=(" + ", ".join(f"0x{w:08x}" for w in self.key) + f"), stream={self.stream})"
+
+
+def seed_words(seed: Seed, domain: int, first_word: int, count: int) -> np.ndarray:
+    """G(seed, domain)[first_word .. first_word + count): tfhe_seed_words, the definition of the mask generator (host
+    code: no context, no GPU)"""
+    out = np.zeros(int(count), dtype=np.uint32)
+    cs = seed._c()
+    if int(first_word) < 0 or int(count) < 0 or int(first_word) + int(count) > SEED_MAX_WORDS:
+        raise _invalid("seed_words: the word range must stay within TFHE_SEED_MAX_WORDS = 2^36")
+    st = lib().tfhe_seed_words(C.byref(cs), C.c_uint32(int(domain) & 0xFFFFFFFF), C.c_uint64(int(first_word)), C.c_size_t(int(count)),
+                               _ptr(out))
+    if st:
+        raise TfheError(st, "seed_words")
+    return out
+
+
+class SeededRows:
+    """A seeded object: the seed and the bodies.  kind "lwe": bodies [..] of rows of `dimension` + 1 words; kind "glwe":
+    bodies [..][N] of rows of [k+1][N], `dimension` = k.  The leading shape is the object's own (a key-switching key
+    [kN l_ks], a bootstrapping key [n][(k+1)l][N], selectors [queries][depth][(k+1)l][N])."""
+
+    def __init__(self, seed: Seed, bodies, kind: str, dimension: int):
+        if kind not in ("lwe", "glwe"):
+            raise _invalid("SeededRows: kind must be 'lwe' or 'glwe'")
+        self.seed, self.bodies, self.kind, self.dimension = seed, _np(bodies), kind, int(dimension)
+
+    @property
+    def rows(self) -> int:
+        return self.bodies.size if self.kind == "lwe" else self.bodies.size // int(self.bodies.shape[-1])
+
+    @property
+    def nbytes(self) -> int:
+        """what crosses the wire: the bodies and the seed's ten words"""
+        return int(self.bodies.nbytes) + 40
+
+    @property
+    def full_nbytes(self) -> int:
+        """bytes of the expanded object"""
+        per_row = self.dimension + 1 if self.kind == "lwe" else (self.dimension + 1) * int(self.bodies.shape[-1])
+        return 4 * self.rows * per_row
+
+
+def save_seeded(prefix: str, params: TfheParams, seeded: SeededRows, aligned: bool = False) -> None:
+    """<prefix>.seed (TFHE_FILE_WORDS: the seed's ten words, then the domain and the dimension the bodies were made for)
+    and <prefix>.bodies (TFHE_FILE_WORDS: the bodies in their own shape).  The on-disk format is save_array's."""
+    domain = SEED_DOMAIN_LWE if seeded.kind == "lwe" else SEED_DOMAIN_GLWE
+    save_array(prefix + ".seed", FILE_WORDS, params, np.concatenate([seeded.seed.words(), np.array([domain, seeded.dimension], dtype=np.uint32)]),
+               aligned)
+    save_array(prefix + ".bodies", FILE_WORDS, params, seeded.bodies, aligned)
+
+
+def load_seeded(prefix: str):
+    """-> (TfheParams, aligned, SeededRows) of what save_seeded wrote"""
+    kind, params, aligned, words = load_array(prefix + ".seed")
+    kind_b, params_b, aligned_b, bodies = load_array(prefix + ".bodies")
+    if kind != FILE_WORDS or kind_b != FILE_WORDS or words.shape != (12,) or int(words[10]) not in (SEED_DOMAIN_LWE, SEED_DOMAIN_GLWE) \
+            or bytes(params._c()) != bytes(params_b._c()) or aligned != aligned_b:
+        raise TfheError(TFHE_ERR_IO, f"{prefix}.seed / {prefix}.bodies are not a seeded object")
+    return params, aligned, SeededRows(Seed.from_words(words[:10]), bodies, "lwe" if int(words[10]) == SEED_DOMAIN_LWE else "glwe", int(words[11]))
+
+
 class PolyWeights:
     """A prepared set of clear weight polynomials (Context.prepare_poly_weights): lives on the device of the context that
     prepared it, for that context's backend and ring; usable until close()."""
@@ -667,6 +774,7 @@ class Context:
         """False: the reference's literal decomposer (bit-exact with the crate).  True: limbs and
         gadget factors counted down from bit 32, so bases with log_base not dividing 32 decrypt."""
         self._check(lib().tfhe_context_set_decomposer_alignment(self._h, C.c_int(int(aligned))))
+        self._aligned = bool(aligned)
 
     def set_kernel_shape(self, shape: int):
         """SHAPE_AUTO (default: by batch size), SHAPE_WIDE (2 (k+1) waves per sample: the latency shape, fp64-fft up to
@@ -2128,6 +2236,180 @@ class Context:
         bootstrapping_key_gen -> (bsk_bmmp, ksk); `load` installs it.  Torch tensors in place."""
         return self._key_gen("tfhe_bootstrapping_key_gen_bmmp", "bootstrapping_key_gen_bmmp", lwe_sk, glwe_sk, bsk_samples,
                              ksk_samples, load, True)
+
+    # -- seeded ciphertexts and compressed keys (include/tfhe_hip.h states the generator and the layouts) --
+    def _expand(self, what, seed, bodies, out, body_shape, row_shape):
+        """bodies [..] + body_shape (or None: out's body words stay) -> rows [rows] + row_shape"""
+        if not isinstance(seed, Seed):
+            raise _invalid(f"{what}: a Seed expected")
+        if bodies is None and out is None:
+            raise _invalid(f"{what}: without bodies, `out` holds the rows whose masks are filled")
+        dev = _is_torch(bodies if bodies is not None else out)
+        body_words = int(np.prod(body_shape, dtype=np.int64)) if body_shape else 1
+        row_words = int(np.prod(row_shape, dtype=np.int64))
+        if bodies is not None:
+            if not dev:
+                bodies = _np(bodies)
+            _check_u32(what, "bodies", bodies, dev)
+            size = bodies.numel() if dev else bodies.size
+            if size == 0 or size % body_words or (body_shape and tuple(bodies.shape[-len(body_shape):]) != tuple(body_shape)):
+                raise _invalid(f"{what}: bodies [rows]{_dims(body_shape) if body_shape else ''} expected, got {tuple(bodies.shape)}")
+            rows = size // body_words
+            res = _result(what, dev, out, (rows,) + tuple(row_shape), bodies) if dev or out is None else None
+        else:
+            res = None
+        if res is None:  # a caller's array is completed in place (numpy: it must be a contiguous uint32 array)
+            _check_u32(what, "out", out, dev)
+            if not dev and out.dtype != np.uint32:
+                raise _invalid(f"{what}: out must be a uint32 array")
+            size = out.numel() if dev else out.size
+            if size == 0 or size % row_words or (bodies is not None and size // row_words != rows):
+                raise _invalid(f"{what}: out [rows]{_dims(row_shape)} expected, got {tuple(out.shape)}")
+            rows, res = size // row_words, out
+        cs = seed._c()
+        return cs, bodies, rows, res, dev
+
+    def expand_lwe(self, seed: Seed, bodies, dimension: int, first_row: int = 0, out=None):
+        """Seeded LWE rows -> [rows][dimension+1]: row r's mask is G(seed, LWE)[(first_row + r) dimension ..], its last
+        word bodies[r].  bodies None: the masks of `out` are filled and its body words stay (the encryption side).
+        numpy (host form) or torch device tensors (device form, capturable: the seed and first_row are baked in)."""
+        d = int(dimension)
+        cs, bodies, rows, res, dev = self._expand("expand_lwe", seed, bodies, out, (), (d + 1,))
+        self._call("tfhe_expand_lwe_rows", dev, C.byref(cs), _ptr(bodies), C.c_uint64(int(first_row)), C.c_size_t(rows), C.c_size_t(d),
+                   _ptr(res))
+        return res
+
+    def expand_glwe(self, seed: Seed, bodies, first_row: int = 0, out=None):
+        """Seeded GLWE rows: bodies [..][N] -> [rows][k+1][N], the k mask polynomials of row r from
+        G(seed, GLWE)[(first_row + r) k N ..].  bodies None: the masks of `out` are filled, its body polynomials stay."""
+        p = self.params
+        cs, bodies, rows, res, dev = self._expand("expand_glwe", seed, bodies, out, (p.N,), (p.k + 1, p.N))
+        self._call("tfhe_expand_glwe_rows", dev, C.byref(cs), _ptr(bodies), C.c_uint64(int(first_row)), C.c_size_t(rows), _ptr(res))
+        return res
+
+    def compress_lwe(self, lwe, out=None):
+        """lwe [rows][dimension+1] -> the bodies [rows] (the strided gather of the last words)"""
+        dev = _is_torch(lwe)
+        if not dev:
+            lwe = _np(lwe)
+        _check_u32("compress_lwe", "lwe", lwe, dev)
+        if len(lwe.shape) != 2 or int(lwe.shape[0]) < 1 or int(lwe.shape[1]) < 2:
+            raise _invalid(f"compress_lwe: lwe [rows][dimension+1] expected, got {tuple(lwe.shape)}")
+        rows, d = int(lwe.shape[0]), int(lwe.shape[1]) - 1
+        res = _result("compress_lwe", dev, out, (rows,), lwe)
+        self._call("tfhe_compress_lwe_rows", dev, _ptr(lwe), C.c_size_t(rows), C.c_size_t(d), _ptr(res))
+        return res
+
+    def compress_glwe(self, glwe, out=None):
+        """glwe [..][k+1][N] -> the body polynomials [rows][N]"""
+        p = self.params
+        dev = _is_torch(glwe)
+        if not dev:
+            glwe = _np(glwe)
+        _check_u32("compress_glwe", "glwe", glwe, dev)
+        size = glwe.numel() if dev else glwe.size
+        if len(glwe.shape) < 2 or tuple(glwe.shape[-2:]) != (p.k + 1, p.N) or size == 0:
+            raise _invalid(f"compress_glwe: glwe [rows][{p.k + 1}][{p.N}] expected, got {tuple(glwe.shape)}")
+        rows = size // ((p.k + 1) * p.N)
+        res = _result("compress_glwe", dev, out, (rows, p.N), glwe)
+        self._call("tfhe_compress_glwe_rows", dev, _ptr(glwe), C.c_size_t(rows), _ptr(res))
+        return res
+
+    def expand(self, seeded: SeededRows, first_row: int = 0, out=None):
+        """a SeededRows -> the full object in the bodies' leading shape: [..][dimension+1] or [..][k+1][N]"""
+        if seeded.kind == "lwe":
+            return self.expand_lwe(seeded.seed, seeded.bodies, seeded.dimension, first_row, out).reshape(seeded.bodies.shape + (-1,))
+        p = self.params
+        return self.expand_glwe(seeded.seed, seeded.bodies, first_row, out).reshape(seeded.bodies.shape[:-1] + (p.k + 1, p.N))
+
+    def _seeded_ggsw_samples(self, seed: Seed, messages, rng) -> np.ndarray:
+        """The pre-filled samples [count][R][k+1][N] from which ggsw_encrypt makes GGSWs whose MASKS are exactly the seed's.
+        Row (i, level) of a GGSW is an encryption of zero plus m g_level on polynomial i; for i < k that polynomial is a mask
+        polynomial.  The seeded form keeps the masks a' = G(seed) and carries the term in the body instead,
+        b = <a', s> + e - m g_level s_i (include/tfhe_hip.h): so m g_level is taken off coefficient 0 of mask polynomial i
+        here, and the existing entry point adds it back."""
+        p = self.params
+        lb, levels = p.pbs_decomposer.log_base, p.pbs_decomposer.levels
+        top = 32 if getattr(self, "_aligned", False) else lb * (32 // lb)
+        msg = np.asarray(messages, dtype=np.uint64).reshape(-1)
+        samples = np.zeros((msg.size, p.R, p.k + 1, p.N), dtype=np.uint32)
+        samples[:, :, p.k, :] = self._noise(rng, p.glwe_std_dev, (msg.size, p.R, p.N))
+        self.expand_glwe(seed, None, out=samples)
+        gadget = np.array([1 << (top - lb * (level + 1)) for level in range(levels)], dtype=np.uint64)
+        term = ((msg[:, None] * gadget[None, :]) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+        for i in range(p.k):
+            samples[:, i * levels:(i + 1) * levels, i, 0] -= term
+        return samples
+
+    def encrypt_bits_seeded(self, lwe_sk, messages, rng=None, seed: Seed | None = None) -> SeededRows:
+        """encrypt_bits with the masks from a seed: -> SeededRows (kind "lwe", bodies [batch]) whose expansion is the
+        batch encrypt_bits would give for those masks.  The errors are drawn here (the OS CSPRNG unless the test hook
+        `rng=`), the seed is Seed.fresh() unless given -- NEVER give one seed to two batches under one key."""
+        p = self.params
+        rng = rng if rng is not None else SystemRng()
+        seed = seed if seed is not None else Seed.fresh(rng)
+        msg = np.asarray(messages, dtype=np.uint32).reshape(-1)
+        if msg.size == 0 or int(msg.max()) >> p.log_p:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "assertion failed: m < 1 << log_p (lwe.rs:84)")
+        sk = _np(lwe_sk).reshape(-1)
+        samples = np.zeros((msg.size, sk.size + 1), dtype=np.uint32)
+        samples[:, sk.size] = self._noise(rng, p.lwe_std_dev, msg.size)
+        self.expand_lwe(seed, None, sk.size, out=samples)
+        full = self.lwe_encrypt(sk, samples, (msg << (32 - p.log_p - p.padding_bits)).astype(np.uint32))
+        return SeededRows(seed, self.compress_lwe(full), "lwe", sk.size)
+
+    def encrypt_address_seeded(self, glwe_sk, addresses, depth: int, rng=None, seed: Seed | None = None) -> SeededRows:
+        """encrypt_address with the masks from a seed: -> SeededRows (kind "glwe", bodies [queries][depth][R][N]); expand()
+        gives the raw selectors [queries][depth][R][k+1][N] of cmux_tree / table_lookup"""
+        p = self.params
+        rng = rng if rng is not None else SystemRng()
+        seed = seed if seed is not None else Seed.fresh(rng)
+        addr = np.asarray(addresses, dtype=np.uint64).reshape(-1)
+        if addr.size == 0 or depth < 1 or depth > 63 or int(addr.max()) >> depth:
+            raise TfheError(TFHE_ERR_INVALID_ARGUMENT, "encrypt_address_seeded: addresses must be below 2^depth, depth in [1, 63]")
+        bits = ((addr[:, None] >> np.arange(depth, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.uint32).reshape(-1)
+        full = self.ggsw_encrypt(glwe_sk, bits, self._seeded_ggsw_samples(seed, bits, rng))
+        return SeededRows(seed, self.compress_glwe(full).reshape(addr.size, depth, p.R, p.N), "glwe", p.k)
+
+    def generate_keys_seeded(self, rng=None, load: bool = True):
+        """generate_keys with the masks of both keys from fresh seeds -> (lwe_sk [n], glwe_sk [k][N], bsk: SeededRows
+        "glwe" with bodies [n][R][N], ksk: SeededRows "lwe" with bodies [kN l_ks], dimension n).  Secrets and errors are
+        drawn here as in generate_keys; `load` installs the key."""
+        p = self.params
+        rng = rng if rng is not None else SystemRng()
+        lwe_sk = rng.integers(0, 2, size=p.n).astype(np.uint32)
+        glwe_sk = rng.integers(0, 2, size=(p.k, p.N)).astype(np.uint32)
+        bsk_seed, ksk_seed = Seed.fresh(rng), Seed.fresh(rng)
+        bsk = self._seeded_ggsw_samples(bsk_seed, lwe_sk, rng)
+        ksk = np.zeros(p.ksk_shape(), dtype=np.uint32)
+        ksk[:, p.n] = self._noise(rng, p.lwe_std_dev, ksk.shape[0])
+        self.expand_lwe(ksk_seed, None, p.n, out=ksk)
+        bsk, ksk = self.bootstrapping_key_gen(lwe_sk, glwe_sk, bsk, ksk, load=load)
+        return (lwe_sk, glwe_sk, SeededRows(bsk_seed, self.compress_glwe(bsk).reshape(p.n, p.R, p.N), "glwe", p.k),
+                SeededRows(ksk_seed, self.compress_lwe(ksk), "lwe", p.n))
+
+    def load_bootstrapping_key_seeded(self, bsk: SeededRows, ksk: SeededRows):
+        """tfhe_load_bootstrapping_key_seeded: the bodies go up, the masks are expanded on the device"""
+        p = self.params
+        if bsk.kind != "glwe" or ksk.kind != "lwe" or ksk.dimension != p.n or bsk.bodies.size != p.n * p.R * p.N \
+                or int(bsk.bodies.shape[-1]) != p.N or ksk.bodies.size != p.ksk_shape()[0]:
+            raise _invalid(f"load_bootstrapping_key_seeded: bsk bodies [{p.n}][{p.R}][{p.N}] (glwe) and ksk bodies "
+                           f"[{p.ksk_shape()[0]}] (lwe, dimension {p.n}) expected")
+        cb, ck = bsk.seed._c(), ksk.seed._c()
+        self._check(lib().tfhe_load_bootstrapping_key_seeded(self._h, C.byref(cb), _ptr(bsk.bodies), C.byref(ck), _ptr(ksk.bodies)))
+
+    def bootstrap_seeded(self, seeded: SeededRows, test_vector_poly, first_row: int = 0) -> np.ndarray:
+        """bootstrap() of seeded LWE inputs at the boundary dimension: batch words go up instead of batch (io_dim + 1)"""
+        if seeded.kind != "lwe" or seeded.dimension != self.io_dim:
+            raise _invalid(f"bootstrap_seeded: seeded LWE rows of dimension {self.io_dim} expected")
+        bodies = seeded.bodies.reshape(-1)
+        batch = bodies.size
+        tv, count = self._test_vectors("bootstrap_seeded", test_vector_poly, batch, False, None)
+        res = np.zeros((batch, self.io_dim + 1), dtype=np.uint32)
+        cs = seeded.seed._c()
+        self._check(lib().tfhe_bootstrap_batch_seeded(self._h, C.byref(cs), C.c_uint64(int(first_row)), _ptr(bodies), C.c_size_t(batch),
+                                                      _ptr(tv), C.c_size_t(count), _ptr(res)))
+        return res
 
     # -- convenience on top of the encryption-side entry points ---------------------------------
     @staticmethod

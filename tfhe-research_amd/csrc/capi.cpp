@@ -4307,4 +4307,197 @@ int tfhe_lwe_not_batch(tfhe_context* ctx, const uint32_t* ct, size_t batch, uint
   return s.download_and_wait(kOut, lwe_out);
 }
 
+// ---------------------------------------------------------------------------------- seeded ciphertexts
+// include/tfhe_hip.h ("seeded ciphertexts") states the generator and the two layouts; seeded.h the launches.
+namespace {
+
+SeededStream seeded_stream(const tfhe_seed* seed, u32 domain) {
+  SeededStream s;
+  for (int i = 0; i < 8; ++i) s.key[i] = seed->key[i];
+  s.nonce[0] = domain, s.nonce[1] = (u32)seed->stream, s.nonce[2] = (u32)(seed->stream >> 32);
+  return s;
+}
+
+bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa < pb + b_bytes && pb < pa + a_bytes;
+}
+
+// rows of mask_words mask words and 2^body_shift body words: the one shape behind both layouts
+struct SeededShape {
+  size_t mask_words;
+  u32 body_shift;
+  u32 domain;
+  size_t body_words() const { return (size_t)1 << body_shift; }
+  size_t row_words() const { return mask_words + body_words(); }
+};
+SeededShape lwe_shape(size_t dimension) { return {dimension, 0, TFHE_SEED_DOMAIN_LWE}; }
+SeededShape glwe_shape(const tfhe_context* ctx) { return {(size_t)ctx->big_n, ctx->pbs.log_n, TFHE_SEED_DOMAIN_GLWE}; }
+
+// every refusal of an expansion; *first_word = first_row * mask_words
+int check_expand(tfhe_context* ctx, const tfhe_seed* seed, const u32* bodies, u64 first_row, size_t rows, const SeededShape& sh,
+                 const u32* out, u64* first_word) {
+  if (!seed || !out) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null seed or output");
+  if (rows == 0 || sh.mask_words == 0 || sh.mask_words >= ((size_t)1 << 31))
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "no rows, or a dimension that is zero or 2^31 and above");
+  const u64 max_rows = kSeededMaxWords / sh.mask_words;
+  if (rows > max_rows || first_row > max_rows - rows)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "the word range (first_row + rows) * dimension reaches past TFHE_SEED_MAX_WORDS = 2^36");
+  if (bodies && ranges_overlap(bodies, rows * sh.body_words() * sizeof(u32), out, rows * sh.row_words() * sizeof(u32)))
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "bodies and the output overlap");
+  *first_word = first_row * sh.mask_words;
+  return TFHE_OK;
+}
+
+int check_compress(tfhe_context* ctx, const u32* in, size_t rows, const SeededShape& sh, const u32* out) {
+  if (!in || !out) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null input or output");
+  if (rows == 0 || sh.mask_words == 0 || sh.mask_words >= ((size_t)1 << 31) || rows > kSeededMaxWords / sh.mask_words)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "no rows, a dimension that is zero or 2^31 and above, or more than 2^36 mask words");
+  if (ranges_overlap(in, rows * sh.row_words() * sizeof(u32), out, rows * sh.body_words() * sizeof(u32)))
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "the input and the output overlap");
+  return TFHE_OK;
+}
+
+int expand_device(tfhe_context* ctx, const tfhe_seed* seed, const u32* bodies, u64 first_row, size_t rows, const SeededShape& sh, u32* out) {
+  u64 first_word = 0;
+  TFHE_TRY(check_expand(ctx, seed, bodies, first_row, rows, sh, out, &first_word));
+  const SeededRowsArgs a{seeded_stream(seed, sh.domain), bodies, out, first_word, rows, (u32)sh.mask_words, sh.body_shift};
+  HIP_TRY(ctx, launch::seeded_expand(ctx->stream, a));
+  return TFHE_OK;
+}
+
+// bodies go up (or, without bodies, the rows themselves: their body words stay), the rows come back
+int expand_host(tfhe_context* ctx, const tfhe_seed* seed, const u32* bodies, u64 first_row, size_t rows, const SeededShape& sh, u32* out) {
+  u64 first_word = 0;
+  TFHE_TRY(check_expand(ctx, seed, bodies, first_row, rows, sh, out, &first_word));
+  enum { kBodies, kRows };
+  Staging s(ctx, {(rows * sh.body_words() + 3) & ~(size_t)3, rows * sh.row_words()});
+  TFHE_TRY(s.reserve());
+  if (bodies)
+    TFHE_TRY(upload(ctx, s[kBodies], bodies, rows * sh.body_words()));
+  else
+    TFHE_TRY(s.upload(kRows, out));
+  TFHE_TRY(expand_device(ctx, seed, bodies ? s[kBodies] : nullptr, first_row, rows, sh, s[kRows]));
+  return s.download_and_wait(kRows, out);
+}
+
+int compress_device(tfhe_context* ctx, const u32* in, size_t rows, const SeededShape& sh, u32* out) {
+  TFHE_TRY(check_compress(ctx, in, rows, sh, out));
+  const SeededRowsArgs a{SeededStream{}, in, out, 0, rows, (u32)sh.mask_words, sh.body_shift};
+  HIP_TRY(ctx, launch::seeded_compress(ctx->stream, a));
+  return TFHE_OK;
+}
+
+int compress_host(tfhe_context* ctx, const u32* in, size_t rows, const SeededShape& sh, u32* out) {
+  TFHE_TRY(check_compress(ctx, in, rows, sh, out));
+  enum { kRows, kBodies };
+  Staging s(ctx, {(rows * sh.row_words() + 3) & ~(size_t)3, rows * sh.body_words()});
+  TFHE_TRY(s.reserve());
+  TFHE_TRY(upload(ctx, s[kRows], in, rows * sh.row_words()));
+  TFHE_TRY(compress_device(ctx, s[kRows], rows, sh, s[kBodies]));
+  return s.download_and_wait(kBodies, out);
+}
+
+}  // namespace
+
+int tfhe_seed_words(const tfhe_seed* seed, uint32_t domain, uint64_t first_word, size_t count, uint32_t* out) {
+  if (first_word > kSeededMaxWords || count > kSeededMaxWords - first_word) return TFHE_ERR_INVALID_ARGUMENT;
+  if (count == 0) return TFHE_OK;
+  if (!seed || !out) return TFHE_ERR_INVALID_ARGUMENT;
+  const SeededStream s = seeded_stream(seed, domain);
+  u32 x[16];
+  u64 w = first_word;
+  const u64 end = first_word + count;
+  while (w < end) {
+    seeded_block(s, (u32)(w / kSeededBlockWords), x);
+    for (u32 i = (u32)(w % kSeededBlockWords); i < kSeededBlockWords && w < end; ++i, ++w) out[w - first_word] = x[i];
+  }
+  return TFHE_OK;
+}
+
+int tfhe_expand_lwe_rows_device(tfhe_context* ctx, const tfhe_seed* seed, const uint32_t* bodies, uint64_t first_row, size_t rows,
+                                size_t dimension, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  return expand_device(ctx, seed, bodies, first_row, rows, lwe_shape(dimension), lwe_out);
+}
+
+int tfhe_expand_lwe_rows(tfhe_context* ctx, const tfhe_seed* seed, const uint32_t* bodies, uint64_t first_row, size_t rows,
+                         size_t dimension, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  return expand_host(ctx, seed, bodies, first_row, rows, lwe_shape(dimension), lwe_out);
+}
+
+int tfhe_expand_glwe_rows_device(tfhe_context* ctx, const tfhe_seed* seed, const uint32_t* bodies, uint64_t first_row, size_t rows,
+                                 uint32_t* glwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  return expand_device(ctx, seed, bodies, first_row, rows, glwe_shape(ctx), glwe_out);
+}
+
+int tfhe_expand_glwe_rows(tfhe_context* ctx, const tfhe_seed* seed, const uint32_t* bodies, uint64_t first_row, size_t rows,
+                          uint32_t* glwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  return expand_host(ctx, seed, bodies, first_row, rows, glwe_shape(ctx), glwe_out);
+}
+
+int tfhe_compress_lwe_rows_device(tfhe_context* ctx, const uint32_t* lwe, size_t rows, size_t dimension, uint32_t* bodies_out) {
+  TFHE_TRY(check_ctx(ctx));
+  return compress_device(ctx, lwe, rows, lwe_shape(dimension), bodies_out);
+}
+
+int tfhe_compress_lwe_rows(tfhe_context* ctx, const uint32_t* lwe, size_t rows, size_t dimension, uint32_t* bodies_out) {
+  TFHE_TRY(check_ctx(ctx));
+  return compress_host(ctx, lwe, rows, lwe_shape(dimension), bodies_out);
+}
+
+int tfhe_compress_glwe_rows_device(tfhe_context* ctx, const uint32_t* glwe, size_t rows, uint32_t* bodies_out) {
+  TFHE_TRY(check_ctx(ctx));
+  return compress_device(ctx, glwe, rows, glwe_shape(ctx), bodies_out);
+}
+
+int tfhe_compress_glwe_rows(tfhe_context* ctx, const uint32_t* glwe, size_t rows, uint32_t* bodies_out) {
+  TFHE_TRY(check_ctx(ctx));
+  return compress_host(ctx, glwe, rows, glwe_shape(ctx), bodies_out);
+}
+
+int tfhe_load_bootstrapping_key_seeded(tfhe_context* ctx, const tfhe_seed* bsk_seed, const uint32_t* bsk_bodies,
+                                       const tfhe_seed* ksk_seed, const uint32_t* ksk_bodies) {
+  TFHE_TRY(check_ctx(ctx));
+  if (!bsk_seed || !bsk_bodies || !ksk_seed || !ksk_bodies) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null seed or key pointer");
+  const size_t n = ctx->params.lwe_dimension;
+  const size_t bsk_rows = n * ctx->R, bsk_body_words = bsk_rows * ctx->N, ksk_rows = (size_t)ctx->big_n * ctx->ks.levels;
+  // bodies, then the raw arrays: temporaries of this call (the device loader drains the stream before it returns)
+  DeviceBuffer bodies, raw_bsk, raw_ksk;
+  TFHE_TRY(bodies.grow(ctx, (bsk_body_words + ksk_rows) * sizeof(u32)));
+  TFHE_TRY(raw_bsk.grow(ctx, bsk_rows * glwe_words(ctx) * sizeof(u32)));
+  TFHE_TRY(raw_ksk.grow(ctx, ksk_words(ctx) * sizeof(u32)));
+  TFHE_TRY(upload(ctx, bodies.as<u32>(), bsk_bodies, bsk_body_words));
+  TFHE_TRY(upload(ctx, bodies.as<u32>() + bsk_body_words, ksk_bodies, ksk_rows));
+  int st = expand_device(ctx, bsk_seed, bodies.as<u32>(), 0, bsk_rows, glwe_shape(ctx), raw_bsk.as<u32>());
+  if (st == TFHE_OK) st = expand_device(ctx, ksk_seed, bodies.as<u32>() + bsk_body_words, 0, ksk_rows, lwe_shape(n), raw_ksk.as<u32>());
+  if (st == TFHE_OK) st = tfhe_load_bootstrapping_key_device(ctx, raw_bsk.as<u32>(), raw_ksk.as<u32>());
+  // the temporaries are freed on return: whatever was enqueued on them ends first, also after a failure
+  const hipError_t drained = hipStreamSynchronize(ctx->stream);
+  if (st == TFHE_OK && drained != hipSuccess) return hip_fail(ctx, drained, "hipStreamSynchronize");
+  return st;
+}
+
+int tfhe_bootstrap_batch_seeded(tfhe_context* ctx, const tfhe_seed* seed, uint64_t first_row, const uint32_t* bodies, size_t batch,
+                                const uint32_t* tv, size_t tv_count, uint32_t* lwe_out) {
+  TFHE_TRY(check_ctx(ctx));
+  if (!seed) return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "null seed");
+  TFHE_TRY(check_rotate_args(ctx, bodies, tv, lwe_out, batch, tv_count));
+  TFHE_TRY(check_tv_host(ctx, tv, tv_count * ctx->N));
+  const SeededShape sh = lwe_shape(io_words(ctx) - 1);
+  const u64 max_rows = kSeededMaxWords / sh.mask_words;
+  if (batch > max_rows || first_row > max_rows - batch)
+    return fail(ctx, TFHE_ERR_INVALID_ARGUMENT, "the word range (first_row + batch) * dimension reaches past TFHE_SEED_MAX_WORDS = 2^36");
+  TFHE_TRY(reserve(ctx, batch));
+  // the bodies wait in the second operand's buffer, the expanded rows are the first operand
+  TFHE_TRY(upload(ctx, ctx->d_lwe_in2.as<u32>(), bodies, batch));
+  TFHE_TRY(upload(ctx, ctx->d_tv.as<u32>(), tv, tv_count * ctx->N));
+  TFHE_TRY(expand_device(ctx, seed, ctx->d_lwe_in2.as<u32>(), first_row, batch, sh, ctx->d_lwe_in.as<u32>()));
+  TFHE_TRY(enqueue_bootstrap(ctx, ctx->d_lwe_in.as<u32>(), batch, ctx->d_tv.as<u32>(), tv_count, ctx->d_lwe_big.as<u32>(), ctx->d_lwe_out.as<u32>()));
+  return download_and_wait(ctx, lwe_out, ctx->d_lwe_out.as<u32>(), batch * io_words(ctx));
+}
+
 }  // extern "C"

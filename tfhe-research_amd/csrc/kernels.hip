@@ -17,6 +17,7 @@
 #include "multi_value.h"
 #include "passes.h"
 #include "radix.h"
+#include "seeded.h"
 
 namespace tfhe {
 namespace {
@@ -1265,6 +1266,27 @@ struct RadixThread {
   __device__ size_t threads() const { return (size_t)gridDim.x * blockDim.x; }
 };
 __global__ void __launch_bounds__(kRadixThreads) radix_glue_kernel(RadixGlueArgs a) { radix_glue(RadixThread(), a); }
+
+// ------------------------------------------------------------------------------ seeded ciphertexts
+// seeded.h::seeded_expand / seeded_compress state the launches; this is their workgroup context on the device.  V: words
+// per store (4 where rows, masks and both pointers are 16-byte aligned).
+struct SeededWorkgroup {
+  u32* lds_;
+  __device__ u32 thread() const { return threadIdx.x; }
+  __device__ size_t block() const { return blockIdx.x; }
+  __device__ size_t blocks() const { return gridDim.x; }
+  __device__ void barrier() const { __syncthreads(); }
+  __device__ u32* lds() const { return lds_; }
+};
+template <int V>
+__global__ void __launch_bounds__(kSeededThreads) seeded_expand_kernel(SeededRowsArgs a) {
+  __shared__ __attribute__((aligned(16))) u32 stage[kSeededLdsWords];
+  seeded_expand<V>(SeededWorkgroup{stage}, a);
+}
+template <int V>
+__global__ void __launch_bounds__(kSeededThreads) seeded_compress_kernel(SeededRowsArgs a) {
+  seeded_compress<V>(SeededWorkgroup{nullptr}, a);
+}
 
 // ------------------------------------------------------------------------------ multi-value bootstrap
 // multi_value.h::sparse_extract_tile states the per-table step; this is its workgroup context on the device.  The
@@ -2669,6 +2691,37 @@ hipError_t radix_glue(hipStream_t s, const RadixGlueArgs& a) {
   // a thread owns one word of a ciphertext, then four of an accumulator
   const size_t work = std::max(rotations * a.words, a.acc ? rotations * (a.acc_words / 4) : (size_t)0);
   hipLaunchKernelGGL(radix_glue_kernel, dim3(grid_for(work, kRadixThreads)), dim3(kRadixThreads), 0, s, a);
+  return hipGetLastError();
+}
+
+// 16-byte stores where every row, mask run and pointer admits them
+static bool seeded_quads(const SeededRowsArgs& a) {
+  return a.body_shift >= 2 && a.mask_words % 4 == 0 && a.first_word % kSeededBlockWords == 0 &&
+         ((uintptr_t)a.out | (uintptr_t)a.in) % 16 == 0;
+}
+static bool seeded_rows_ok(const SeededRowsArgs& a) {
+  return a.out && a.rows != 0 && a.mask_words != 0 && a.mask_words < (1u << 31) && a.body_shift < 31 &&
+         a.rows <= kSeededMaxWords / a.mask_words && a.first_word <= kSeededMaxWords - a.rows * a.mask_words;
+}
+
+hipError_t seeded_expand(hipStream_t s, const SeededRowsArgs& a) {
+  if (!seeded_rows_ok(a)) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)seeded_workgroups(a.first_word, a.rows * a.mask_words));  // at most 2^36 / 4,096
+  if (seeded_quads(a))
+    hipLaunchKernelGGL(seeded_expand_kernel<4>, grid, dim3(kSeededThreads), 0, s, a);
+  else
+    hipLaunchKernelGGL(seeded_expand_kernel<1>, grid, dim3(kSeededThreads), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t seeded_compress(hipStream_t s, const SeededRowsArgs& a) {
+  if (!seeded_rows_ok(a) || !a.in) return hipErrorInvalidValue;
+  const bool quads = seeded_quads(a);
+  const dim3 grid(grid_for((size_t)(a.rows << a.body_shift) / (quads ? 4 : 1), kSeededThreads));
+  if (quads)
+    hipLaunchKernelGGL(seeded_compress_kernel<4>, grid, dim3(kSeededThreads), 0, s, a);
+  else
+    hipLaunchKernelGGL(seeded_compress_kernel<1>, grid, dim3(kSeededThreads), 0, s, a);
   return hipGetLastError();
 }
 

@@ -11,6 +11,7 @@
 #include "multibit.h"
 #include "pbs_wave.h"
 #include "radix.h"
+#include "seeded.h"
 
 namespace tfhe {
 namespace launch {
@@ -203,6 +204,12 @@ hipError_t extract_step(hipStream_t s, const ExtractStepArgs& a);
 // ---- radix integers (radix.h::radix_glue): the one elementwise launch in front of a bootstrap level.
 // hipErrorInvalidValue: no rotation, more than kRadixMaxBlocks blocks, accumulators without tables
 hipError_t radix_glue(hipStream_t s, const RadixGlueArgs& a);
+
+// ---- seeded ciphertexts (seeded.h): rows of mask_words mask words and 2^body_shift body words.  seeded_expand writes
+// the masks from the stream (and the bodies from a.in, unless null); seeded_compress gathers the bodies of a.in into a.out.
+// hipErrorInvalidValue: no row, no mask word, a null pointer, a word range past 2^36
+hipError_t seeded_expand(hipStream_t s, const SeededRowsArgs& a);
+hipError_t seeded_compress(hipStream_t s, const SeededRowsArgs& a);
 
 // ---- multi-value bootstrap (multi_value.h::sparse_extract_tile): out [batch][tables][k N + 1], the signed gather of
 // `terms` sample extractions of glwe [batch][k+1][N] at positions [terms] (device) times coeffs [1 or batch][tables][terms].
